@@ -9,14 +9,17 @@ Workload (BASELINE.json configs[1]): synthetic Gaussian (rows, 9) float32 -> (ro
 rows = 1,000,000 per GPU.  A "step" is one K1 launch over one resident batch.  Inputs and outputs
 rotate over 8 buffer pairs (576 MB per GPU) so the 256 MiB Infinity Cache cannot serve replays:
 the reported number is an HBM number.  With N > 1 every rank owns its own rows (weak scaling, no
-data-path collective); after the timed region the mean geodesic angle error is reduced on the
-device per rank (K4) and summed with ONE all-reduce (RCCL), and rank 0's line gains
+data-path collective); with --full, after the timed region the mean geodesic angle error is reduced
+on the device per rank (K4) and summed with ONE all-reduce (RCCL), and rank 0's line gains
 secondary.config5 = BASELINE configs[4] (2M rows per rank: 16M over 8), timed the same way.
 
-Prints ONE JSON line on rank 0 (contract in the task statement): value = whole-job projections/s.
-Extra objects: "roofline" (HBM roofline of k_project_fwd from HIP events on the launch stream) and
-"cpu_baseline" (the oracle's torch port -- the reference's ATen call sequence -- timed on this box's
-host cores; N = 1 only).
+Prints ONE JSON line on rank 0: value = whole-job projections/s.  A plain run sets up, warms up, times
+the K steps and prints the headline; --dump-outputs DIR also writes what the last timed step computed
+(DIR/rotations.npy, float32; see dump_rows).  --full adds everything else the benchmark measures and
+checks: "roofline" (HBM roofline of k_project_fwd from HIP events on the launch stream, per-launch
+spread), the mean angle error against the reference's number, every rank's device and clocks,
+"sustained", "secondary" (the other BASELINE configs; configs[4] when N > 1) and "cpu_baseline" (the
+oracle's torch port -- the reference's ATen call sequence -- timed on the host cores; N = 1 only).
 """
 from __future__ import annotations
 
@@ -159,8 +162,13 @@ def parse():
     ap.add_argument("--config", type=int, default=2, choices=(2, 5),
                     help="2: BASELINE configs[1], 1M rows per GPU (the headline).  5: configs[4], 16M rows sharded over 8 GPUs = 2M rows per GPU, "
                          "rank r generated with seed r, one RCCL all-reduce of (sum, count) for the mean angle error")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the brief timing of configs #3 and #4")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: roofline and per-launch spread, parity metric, per-rank report, sustained clock, the other "
+                         "configs and the CPU baseline (a plain run times the K steps and prints the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the sustained clock and the other configs")
     ap.add_argument("--eager", action="store_true", help="launch every step from Python instead of replaying one hipGraph of K launches")
     ap.add_argument("--cpu-rows", type=int, default=1_000_000, help="rows of the CPU baseline sample")
     return ap.parse_args()
@@ -223,6 +231,28 @@ def first_buffer(rank: int, rows: int) -> torch.Tensor:
     """Buffer 0 of rank r is config #2 / #5's generator: torch.manual_seed(r); randn(rows, 9) on the CPU."""
     g = torch.Generator().manual_seed(rank)
     return torch.randn(rows, 9, generator=g)
+
+
+DUMP_BYTES = 64_000_000            # --dump-outputs: at most this much in all
+
+
+def dump_rows(out_dir: str, name: str, rows: torch.Tensor, limit: int = DUMP_BYTES) -> list:
+    """--dump-outputs: write the per-row output `rows` ((n, ...) float32, any device) as out_dir/<name>.npy -- all of it when it fits
+    in `limit` bytes, else a fixed sample of rows (seed 0, ascending) with their row indices as out_dir/<name>_rows.npy (float64).
+    Returns the paths written."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = rows.shape[0]
+    per_row = rows[0].numel() * 4
+    paths = [os.path.join(out_dir, name + ".npy")]
+    if n * per_row <= limit:
+        np.save(paths[0], rows.detach().to("cpu", torch.float32).numpy())
+        return paths
+    keep = np.sort(np.random.default_rng(0).choice(n, limit // (per_row + 8), replace=False))
+    sample = rows[torch.from_numpy(keep).to(rows.device)]
+    np.save(paths[0], sample.detach().to("cpu", torch.float32).numpy())
+    paths.append(os.path.join(out_dir, name + "_rows.npy"))
+    np.save(paths[1], keep.astype(np.float64))
+    return paths
 
 
 def timed_region(run, sync, barrier=None, now=time.perf_counter) -> float:
@@ -556,9 +586,15 @@ def config5_leg(lib, rr, dist, dev, rank: int, world: int, steps: int, warmup: i
         step(i)
     e0.record(stream); e1.record(stream)
     own = {}
+    ev = {}
+
+    def region_ms():                          # read ONCE: the job's MAX and this rank's report are the same reading
+        ev["ms"] = e0.elapsed_time(e1)
+        return ev["ms"]
+
     line, times = run_skeleton(rank, world, steps, warmup, rows, step, torch.cuda.synchronize, dist, dev, config,
-                               extra_times=(lambda: e0.elapsed_time(e1),), run=region, do_warmup=False, own=own)
-    own_ev_ms = e0.elapsed_time(e1) / steps
+                               extra_times=(region_ms,), run=region, do_warmup=False, own=own)
+    own_ev_ms = ev["ms"] / steps
     # the evaluation: one fused launch per rank, one all-reduce of (sum, count)
     gt = torch.Generator().manual_seed(1 + 1000 * rank)
     t_rot = rr.symmetric_orthogonalization(torch.randn(rows, 9, generator=gt).to(dev))
@@ -768,9 +804,32 @@ def main():
 
     with torch.cuda.stream(stream):           # a graph replays on the CURRENT stream: entered before the clock starts
         e0.record(stream); e1.record(stream)  # (torch creates an event's handle at its first record: not inside the region either)
-        own_clock = {}
+        own_clock, ev = {}, {}
+
+        def region_ms():                      # read ONCE: the job's MAX and this rank's own report are the same reading
+            ev["ms"] = e0.elapsed_time(e1)
+            return ev["ms"]
+
         out, (wall, ev_ms) = run_skeleton(rank, world, args.steps, args.warmup, rows, step, synchronize, dist, dev, config,
-                                          extra_times=(lambda: e0.elapsed_time(e1),), run=region, do_warmup=False, own=own_clock)
+                                          extra_times=(region_ms,), run=region, do_warmup=False, own=own_clock)
+    if args.dump_outputs is not None and rank == 0:       # what the last timed step wrote, before anything else is launched
+        dump_rows(args.dump_outputs, "rotations", outs[(args.steps - 1) % NBUF])
+    if rank == 0:
+        out.update({"ms_per_step_events": ev_ms / args.steps,             # HIP events on the launch stream (ms_per_step: the host clock)
+                    "value_events": rows * world * args.steps / (ev_ms * 1e-3),
+                    "pre_timing": pre})
+
+    def finish():
+        if rank == 0:
+            real_stdout.write(json.dumps(out) + "\n")
+            real_stdout.flush()
+        if dist is not None:
+            dist.destroy_process_group()
+
+    if not args.full:
+        finish()
+        return
+    with torch.cuda.stream(stream):
         # per-launch spread (median and min): a second, untimed pass of 20 eager launches with an event
         # between every two of them
         marks = [torch.cuda.Event(enable_timing=True) for _ in range(21)]
@@ -784,7 +843,7 @@ def main():
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     # every rank's device and its OWN clocks (wall / ev_ms above are the job's: MAX over ranks), gathered with one all-reduce
     props = torch.cuda.get_device_properties(dev)
-    own_wall_ms, own_ev_ms = own_clock["wall_s"] * 1e3 / args.steps, e0.elapsed_time(e1) / args.steps
+    own_wall_ms, own_ev_ms = own_clock["wall_s"] * 1e3 / args.steps, ev["ms"] / args.steps
     reports = gather_rank_reports(rank_report_row(dev.index, getattr(props, "gcnArchName", props.name), props.multi_processor_count,
                                                   [own_wall_ms, own_ev_ms]),
                                   rank, world, dist, dev, names=("ms_per_step", "ms_per_step_events"))
@@ -814,8 +873,6 @@ def main():
             except (OSError, ValueError):
                 traffic = None
         out.update({
-            "ms_per_step_events": ev_ms / args.steps,             # HIP events on the launch stream (ms_per_step: the host clock of the contract)
-            "value_events": rows * world * args.steps / (ev_ms * 1e-3),
             "mean_angle_error_deg": mean_angle,
             "mean_angle_error_delta_vs_ref_deg": delta,
             "roofline": {"bound": "hbm", "kernel": k1_kernel, "achieved": achieved, "peak": HBM_PEAK_GBS,
@@ -834,7 +891,6 @@ def main():
                                             "not measured in this run" % traffic_from) if traffic is not None else None,
                          "bytes_per_launch_algorithmic": BYTES_PER_PROJECTION * rows,
                          "avg_launch_us": per_launch_s * 1e6},
-            "pre_timing": pre,
             # one entry per rank: the device it bound to and its own clocks (ms_per_step / ms_per_step_events above: MAX over ranks)
             "devices_seen": reports,
             "ms_per_step_events_by_rank": spread(reports, "ms_per_step_events"),
@@ -872,13 +928,9 @@ def main():
     if dist is not None and world > 1 and not args.no_secondary and args.config == 2:
         c5 = config5_leg(lib, rr, dist, dev, rank, world, args.steps, args.warmup,
                          rows=2_000_000 if args.rows == ROWS_DEFAULT else 2 * args.rows)
-    if rank == 0:
-        if c5 is not None:
-            out.setdefault("secondary", {})["config5"] = c5
-        real_stdout.write(json.dumps(out) + "\n")
-        real_stdout.flush()
-    if dist is not None:
-        dist.destroy_process_group()
+    if rank == 0 and c5 is not None:
+        out.setdefault("secondary", {})["config5"] = c5
+    finish()
 
 
 if __name__ == "__main__":

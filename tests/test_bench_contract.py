@@ -12,7 +12,8 @@ pytestmark = pytest.mark.gpu
 
 
 def _run_bench(*extra, env=None):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "3", "--cpu-rows", "20000", *extra]
+    """A --full run: the headline and everything beside it."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "30", "--warmup", "3", "--cpu-rows", "20000", *extra]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -67,6 +68,35 @@ def test_bench_json_contract(mode):
         assert pt["launches"] == 3 + 1 + 30 + pt["replays"] * 25                      # what ran untimed in front of the region, all of it
 
 
+def test_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run -- no --full -- sets up, warms up, times the K steps and prints the headline, nothing measured beside it; with
+    --dump-outputs it writes what the last timed step computed.  Nine steps over eight buffer pairs: the last one projected buffer 0
+    again, rank 0's seeded CPU draw (bench.first_buffer), which the test draws too."""
+    import numpy as np
+    import bench
+    from conftest import orth_err
+    from oracle import so3_oracle as so
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "9", "--warmup", "2", "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["metric"] == bench.METRIC and d["unit"] == "projections/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 9 and d["warmup"] == 2 and d["n_gpus"] == 1 and d["value"] > 1e7
+    assert abs(d["value"] - 1_000_000 * 9 / (d["ms_per_step"] * 9 * 1e-3)) / d["value"] < 1e-6
+    for key in ("roofline", "cpu_baseline", "secondary", "sustained", "mean_angle_error_deg", "devices_seen"):
+        assert key not in d, key
+    assert sorted(os.listdir(tmp_path)) == ["rotations.npy"]                  # 36 MB: the whole output, no sample
+    r = np.load(tmp_path / "rotations.npy")
+    assert r.shape == (1_000_000, 3, 3) and r.dtype == np.float32
+    assert orth_err(r).max() < 1e-5
+    x = bench.first_buffer(0, 1_000_000).numpy()
+    idx = np.sort(np.random.default_rng(3).choice(1_000_000, 4096, replace=False))
+    err = np.abs(r[idx] - so.symmetric_orthogonalization_np(x[idx])).reshape(len(idx), -1).max(1)
+    assert np.median(err) < 5e-7 and np.quantile(err, 0.95) < 1e-5, (np.median(err), err.max())
+
+
 def test_bench_under_an_initialised_process_group_rccl_one_rank():
     """The N > 1 path of bench.py with one rank, in a fresh child process: RCCL comes up (backend "nccl" on the GPU),
     the K launches are captured into a hipGraph while the process group (and its watchdog thread) exists, and the
@@ -93,7 +123,7 @@ def test_bench_with_two_ranks_sharing_the_device():
     for rank in range(2):
         env = dict(os.environ, SO3_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE="2",
                    LOCAL_RANK="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "30", "--warmup", "3", "--rows", "500000"]
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "30", "--warmup", "3", "--rows", "500000"]
         procs.append(subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=ROOT, env=env))
     outs = [p.communicate(timeout=600) for p in procs]
     assert all(p.returncode == 0 for p in procs), [o[1][-1500:] for o in outs]
@@ -116,7 +146,7 @@ def test_bench_gpus_2_starts_its_own_ranks():
     ranks are mapped onto cuda:0 (SO3_BENCH_SHARE_DEVICE) and the process group is gloo (RCCL refuses two ranks on one device)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(SO3_BENCH_BACKEND="gloo", SO3_BENCH_SHARE_DEVICE="1")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "30", "--warmup", "3", "--rows", "500000"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "30", "--warmup", "3", "--rows", "500000"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -171,7 +201,7 @@ def test_bench_under_torch_distributed_run_as_the_driver_spells_it():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(SO3_BENCH_BACKEND="gloo", SO3_BENCH_SHARE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--rows", "250000"]
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "20", "--warmup", "5", "--rows", "250000"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2500:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]

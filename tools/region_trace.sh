@@ -4,7 +4,7 @@ set -e
 export TMPDIR=/tmp
 out=gpurun_out/region_trace
 rm -rf $out; mkdir -p $out
-rocprofv3 --kernel-trace --output-format csv -d $out -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $out/line.json 2> $out/log.txt
+rocprofv3 --kernel-trace --output-format csv -d $out -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $out/line.json 2> $out/log.txt
 python3 - <<'PY'
 import csv, glob
 f = sorted(glob.glob("gpurun_out/region_trace/*/*kernel_trace.csv"))[-1]

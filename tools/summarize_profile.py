@@ -28,7 +28,7 @@ kt = list(csv.DictReader(open(one("kt/*/*kernel_trace.csv"))))
 k1 = [r for r in kt if KEY in r["Kernel_Name"]]
 d = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in k1]
 summary = {
-    "command": "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 1000 --warmup 50 --no-cpu-baseline --no-secondary "
+    "command": "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 1000 --warmup 50 --no-cpu-baseline --no-secondary "
                "(50 warm-up launches, the 1000-launch graph once untimed, short-graph clock warm-up, the timed replay, one launch for the parity metric)",
     "kernel": k1[0]["Kernel_Name"][:120], "dispatches": len(d),
     "avg_us": statistics.mean(d), "median_us": statistics.median(d), "min_us": min(d), "max_us": max(d),
@@ -56,7 +56,7 @@ traffic = {
     "correction": "gfx950: FETCH_SIZE reports half of a wide coalesced streaming read -> doubled; WRITE_SIZE exact",
     "hbm_read_bytes_per_launch": 2 * fetch_kb * 1024, "hbm_write_bytes_per_launch": write_kb * 1024,
     "hbm_bytes_per_launch": (2 * fetch_kb + write_kb) * 1024, "algorithmic_bytes_per_launch": 72_000_000,
-    "source": f"profiles/{tag}: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --steps 20 --warmup 5",
+    "source": f"profiles/{tag}: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --full --steps 20 --warmup 5",
 }
 json.dump(traffic, open(os.path.join(root, "k1_pmc_traffic.json"), "w"), indent=1)
 json.dump(traffic, open(os.path.join(root, f"{tag}_k1_pmc_traffic.json"), "w"), indent=1)
