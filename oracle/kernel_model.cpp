@@ -176,3 +176,16 @@ extern "C" void model_fast_path_counters(long long *out2, int reset) {
     out2[1] = so3::host_counters().refinements;
     if (reset) so3::host_counters() = so3::HostCounters{};
 }
+
+// so3_rows.h's float64 acos (K4, the fused K1+K4 and every float64 metric kernel compute their angles with it), elementwise
+extern "C" void model_acos_f64(const double *c, double *out, int64_t n) {
+    for (int64_t i = 0; i < n; ++i) out[i] = so3::acos_f64(c[i]);
+}
+
+// the reduction workspace's slot encoding (so3_rows.h: slot_encode / slot_decode), elementwise
+extern "C" void model_slot_encode(const double *v, unsigned long long *s, int64_t n) {
+    for (int64_t i = 0; i < n; ++i) s[i] = so3::slot_encode(v[i]);
+}
+extern "C" void model_slot_decode(const unsigned long long *s, double *v, int64_t n) {
+    for (int64_t i = 0; i < n; ++i) v[i] = so3::slot_decode(s[i]);
+}

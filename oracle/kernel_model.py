@@ -163,3 +163,26 @@ def fast_path_counters(reset=True):
     out = np.zeros(2, np.int64)
     lib().model_fast_path_counters(_p(out), ctypes.c_int(1 if reset else 0))
     return int(out[0]), int(out[1])
+
+
+def acos_f64(c):
+    """so3_rows.h's float64 acos, elementwise (the kernels' own polynomial, not libm's)."""
+    c = np.ascontiguousarray(c, np.float64)
+    out = np.empty_like(c)
+    lib().model_acos_f64(_p(c), _p(out), ctypes.c_int64(c.size))
+    return out
+
+
+def slot_encode(v):
+    """so3_rows.h's encoding of a float64 partial in a reduction workspace slot (0 = "not here yet"), elementwise: uint64."""
+    v = np.ascontiguousarray(v, np.float64)
+    s = np.empty(v.shape, np.uint64)
+    lib().model_slot_encode(_p(v), _p(s), ctypes.c_int64(v.size))
+    return s
+
+
+def slot_decode(s):
+    s = np.ascontiguousarray(s, np.uint64)
+    v = np.empty(s.shape, np.float64)
+    lib().model_slot_decode(_p(s), _p(v), ctypes.c_int64(s.size))
+    return v

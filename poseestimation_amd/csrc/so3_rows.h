@@ -216,10 +216,19 @@ __device__ __forceinline__ double coherent_f64(const double *p) {         // oth
     return __longlong_as_double(__hip_atomic_load(reinterpret_cast<const long long *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
 
-// A slot holds its partial's bit pattern PLUS ONE: 0, what a slot holds when nobody has written it, then stands for "not here yet" -- no sum of
-// angles or norms is the NaN 0xFFFF...F -- and the workgroup that sums the slots can tell a partial that has not arrived from a partial of 0.0.
-__device__ __forceinline__ unsigned long long slot_encode(double v) { return static_cast<unsigned long long>(__double_as_longlong(v)) + 1ull; }
-__device__ __forceinline__ double slot_decode(unsigned long long s) { return __longlong_as_double(static_cast<long long>(s - 1ull)); }
+#endif  // !SO3_HOST_MODEL
+
+// A slot holds its partial's bit pattern PLUS ONE: 0, what a slot holds when nobody has written it, then stands for "not here yet", and the
+// workgroup that sums the slots can tell a partial that has not arrived from a partial of 0.0.  A NaN partial is stored as the canonical quiet
+// NaN 0x7FF8...0: a float64 partial CAN be 0xFFFF...F (a row of 0xFF bytes keeps its payload through -, fma, sqrt and +, and the NaN 0x7FFF...F
+// comes out of a subtraction with its sign flipped), and that plus one is 0 -- the summing workgroup would poll the slot until it gave up.
+// (Host-visible: oracle/kernel_model.cpp checks the encoding on the CPU.)
+__device__ __forceinline__ unsigned long long slot_encode(double v) {
+    return (v != v ? 0x7ff8000000000000ull : __builtin_bit_cast(unsigned long long, v)) + 1ull;
+}
+__device__ __forceinline__ double slot_decode(unsigned long long s) { return __builtin_bit_cast(double, s - 1ull); }
+
+#ifndef SO3_HOST_MODEL
 __device__ __forceinline__ void slot_publish(ReduceWs *ws, unsigned slot, double v) {           // performed at the memory side (agent scope), not waited for
     __hip_atomic_store(reinterpret_cast<unsigned long long *>(&ws->part[slot]), slot_encode(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -949,28 +958,35 @@ struct OpFrobLoss : OpBase {
     }
 };
 
-// acos in float64 to 1.4e-14 rad (the metric is compared at 1e-9 degrees): |c| <= 1/2: pi/2 - asin(c); otherwise through
-// asin(sqrt((1 - |c|)/2)).  asin(x) = x + x z g(z), z = x^2 <= 1/4, g a degree-9 polynomial (Chebyshev fit).  A third of the
-// device library's acos in instructions: the float64 work of K4 and of the fused K1+K4 is what holds their clocks down.
+#endif  // !SO3_HOST_MODEL
+
+// acos in float64 to 3.6e-15 rad, and to 7e-15 relative for c > 1/2 (small angles stay accurate relative to their size): |c| <= 1/2:
+// pi/2 - asin(c); otherwise through asin(sqrt((1 - |c|)/2)).  asin(x) = x + x z g(z), z = x^2 <= 1/4, g a degree-9 polynomial: the
+// minimax fit of g on [0, 1/4] weighted by z^1.2 (tools/fit_acos_f64.py; weight z^1 is the relative error of the angle for c > 1/2,
+// z^1.5 its absolute error -- 1.2 keeps both well inside the bounds).  The unweighted Chebyshev fit before it was off by 1.4e-14 rad
+// (1.3e-14 relative) next to c = +-1/2.  A third of the device library's acos in instructions: the float64 work of K4 and of the fused
+// K1+K4 is what holds their clocks down.  Host-visible (oracle/kernel_model.cpp sweeps it against long double acos on the CPU).
 __device__ __forceinline__ double acos_f64(double c) {
     const double a = __builtin_fabs(c);
     const bool small = a <= 0.5;
     const double z = small ? c * c : (1.0 - a) * 0.5;
     const double x = small ? c : __builtin_sqrt(z);
-    double g = 2.80174951579700952e-02;
-    g = __builtin_fma(g, z, -3.06358547004551354e-03);
-    g = __builtin_fma(g, z, 1.57334373966823808e-02);
-    g = __builtin_fma(g, z, 1.31733845957499804e-02);
-    g = __builtin_fma(g, z, 1.74436241846820592e-02);
-    g = __builtin_fma(g, z, 2.23658829849630453e-02);
-    g = __builtin_fma(g, z, 3.03821915977370988e-02);
-    g = __builtin_fma(g, z, 4.46428522253018087e-02);
-    g = __builtin_fma(g, z, 7.50000000378114595e-02);
-    g = __builtin_fma(g, z, 1.66666666666618946e-01);
+    double g = 3.21826565586824237e-02;
+    g = __builtin_fma(g, z, -8.16772289330672599e-03);
+    g = __builtin_fma(g, z, 1.83839466589421074e-02);
+    g = __builtin_fma(g, z, 1.24141922603476871e-02);
+    g = __builtin_fma(g, z, 1.75744015881670532e-02);
+    g = __builtin_fma(g, z, 2.23520318074619528e-02);
+    g = __builtin_fma(g, z, 3.03830761694763654e-02);
+    g = __builtin_fma(g, z, 4.46428202860340434e-02);
+    g = __builtin_fma(g, z, 7.50000006048157641e-02);
+    g = __builtin_fma(g, z, 1.66666666663105478e-01);
     const double r = __builtin_fma(x * z, g, x);           // asin(x)
     const double big = c > 0.0 ? r + r : __builtin_fma(-2.0, r, 3.14159265358979323846);
     return small ? 1.57079632679489661923 - r : big;       // NaN in -> NaN out (comparisons false, arithmetic propagates)
 }
+
+#ifndef SO3_HOST_MODEL
 
 // K4: theta = acos(clamp((tr(R1^T R2) - 1)/2)) in float64 on float32 data (rotation_representation.py:230-242).
 template <bool WANT_DEG, bool WANT_SUM>

@@ -341,3 +341,63 @@ def test_first_eigenvector_is_final_on_all_but_a_few_gaussian_rows(km):
     km.project_quat(rng.standard_normal((n, 9)).astype(np.float32))
     rows, adjugates = km.fast_path_counters()
     assert rows / n < 2.0e-3 and adjugates < 1.2 * rows, (rows / n, adjugates)           # 1.6e-3, 1.04 measured
+
+
+def _acos_sweep_cosines():
+    """2e7 cosines over [-1, 1] (a uniform grid, then dense neighbourhoods of +-1/2, where the kernel's acos changes branch, and of +-1,
+    where the angle is small or next to pi), in chunks of 2e6."""
+    n = 2_000_000
+    for k in range(9):
+        yield np.linspace(-1.0, 1.0, n) + (k - 4) * (1.0 / (9 * (n - 1)))       # nine interleaved grids, step 1.1e-7 between them
+    j = np.arange(-n // 4, n // 4, dtype=np.float64)
+    yield np.concatenate((0.5 + j * 2.0**-40, -0.5 + j * 2.0**-40, 0.5 + j * 2.0**-30, -0.5 + j * 2.0**-30))
+    k = np.arange(n // 4, dtype=np.float64)
+    geo = np.geomspace(2.0**-53, 0.5, n // 4)
+    yield np.concatenate((1.0 - k * 2.0**-52, -1.0 + k * 2.0**-53, 1.0 - geo, -1.0 + geo))
+
+
+def test_acos_f64_against_long_double_on_the_host(km):
+    """so3_rows.h's acos_f64 -- every float64 angle the library returns, K4's and the fused K1+K4's degrees on float32 data included --
+    against long double acos: <= 1.5e-14 rad absolute everywhere, <= 1e-14 relative for c > 1/2 (small angles stay accurate relative to
+    their size), 0 and pi exactly at +-1, NaN for NaN.  tests/test_gpu_float64_metrics.py runs the same function through the device."""
+    assert np.finfo(np.longdouble).eps < 1e-18, "needs an extended-precision long double for the reference"
+    worst_abs = worst_rel = 0.0
+    count = 0
+    for c in _acos_sweep_cosines():
+        c = np.clip(c, -1.0, 1.0)
+        got = km.acos_f64(c)
+        ref = np.arccos(c.astype(np.longdouble))
+        err = np.abs(got.astype(np.longdouble) - ref).astype(np.float64)
+        worst_abs = max(worst_abs, float(err.max()))
+        big = (c > 0.5) & (c < 1.0)
+        if big.any():
+            worst_rel = max(worst_rel, float((err[big] / ref[big].astype(np.float64)).max()))
+        count += c.size
+    assert count >= 20_000_000
+    assert worst_abs <= 1.5e-14 and worst_rel <= 1e-14, (worst_abs, worst_rel)
+    ends = km.acos_f64(np.array([1.0, -1.0, 0.0, -0.0, np.nan]))
+    assert ends[0] == 0.0 and ends[1] == np.pi and ends[2] == ends[3] == np.float64(np.pi / 2) and np.isnan(ends[4])
+
+
+def test_reduction_slot_encoding_round_trips_and_never_reads_as_empty(km):
+    """The workspace slots of the reducing kernels (so3_rows.h: slot_encode / slot_decode) hold a partial's bits plus one, 0 meaning
+    "not here yet".  Ordinary values come back bit for bit, every NaN comes back a NaN, and no value at all encodes to 0 -- the NaN
+    0xFFFF...F, which a float64 row of 0xFF bytes produces, once did (the summing workgroup then polled the slot for 0.1 s)."""
+    rng = np.random.default_rng(52)
+    bits = rng.integers(0, 2**64, 1_000_000, dtype=np.uint64, endpoint=False)
+    special = np.array([0.0, -0.0, 1.0, -1.0, 5e-324, -5e-324, 2.2250738585072014e-308, np.finfo(np.float64).max, -np.finfo(np.float64).max,
+                        np.inf, -np.inf, np.pi], np.float64)
+    v = np.concatenate((bits.view(np.float64), special))
+    ordinary = ~np.isnan(v)
+    s = km.slot_encode(v)
+    assert not (s == 0).any()
+    back = km.slot_decode(s)
+    assert np.array_equal(back[ordinary].view(np.uint64), v[ordinary].view(np.uint64))
+    # NaN payloads: both signs, quiet and signalling, the extremes of the payload field and random ones in between
+    payload = np.concatenate((np.array([1, 2**51 - 1, 2**51, 2**52 - 1], np.uint64), rng.integers(1, 2**52, 100_000, dtype=np.uint64)))
+    nan_bits = np.concatenate((np.uint64(0x7FF0000000000000) | payload, np.uint64(0xFFF0000000000000) | payload))
+    nans = nan_bits.view(np.float64)
+    assert np.isnan(nans).all()
+    s = km.slot_encode(nans)
+    assert not (s == 0).any()
+    assert np.isnan(km.slot_decode(s)).all()
