@@ -37,7 +37,8 @@ extern "C" {
 #define SO3PROJ_VERSION 210          /* 0.2.0: the reducing entry points exist once (*_v2: workspace nullable, a flags word), the float64 ones
                                         included (so3_angle_error_v2_f64, so3_frob_loss_v2_f64: round 4 had changed their arguments under the old
                                         names); so3_angle_stats's workspace is zero-filled once by the caller.  0.2.1 (210) ADDS the metrics'
-                                        backward (so3_angle_bwd_f32 / _f64), so3_geodesic_eps_f64 and two flags; nothing of 200 changed its
+                                        backward (so3_angle_bwd_f32 / _f64), so3_geodesic_eps_f64, two flags and the cloud backwards
+                                        (so3_kabsch_bwd_f32, so3_rotate_clouds_bwd_f32); nothing of 200 changed its
                                         arguments, but the float64 entries now reject flag bits they do not know.  A binding checks so3_version(). */
 #define SO3_ERR_INVALID (-1)
 
@@ -294,6 +295,17 @@ int so3_expmap_bwd_f32(const float *X, const float *G, float *dX, int64_t B, voi
 int so3_rotate_clouds_f32(const float *P, const float *R, float *out, int transposed, int64_t B, int32_t N, void *stream);
 int so3_pc_normalize_f32(const float *P, float *out, float *centroid, float *scale, int64_t B, int32_t N, void *stream);
 
+/* so3_rotate_clouds_bwd_f32 (a7b, added in 210): the backward of so3_rotate_clouds_f32, i.e. the gradient the reference's
+ * autograd gives through the bmm of point_cloud/main.py:176-181 (and the transpose at :183) to pc1 and gt_rmat:
+ *     dP_bi = R_b^T g_bi,    dR_b = sum_i g_bi p_bi^T,
+ *   G        in   B*N*3 float32 upstream gradient in the forward's output layout ((B,N,3), or (B,3,N) with transposed != 0)
+ *   dP       out  optional B*N*3 float32 (B,N,3);  dR  out optional B*9 float32 (N == 0 writes dR = 0)
+ * P is read only for dR, R only for dP: R must be non-NULL when dP is asked for, P when dR is (and N > 0), G when N > 0.
+ * Limits as so3_rotate_clouds_f32.
+ */
+int so3_rotate_clouds_bwd_f32(const float *P, const float *R, const float *G, float *dP, float *dR, int transposed,
+                              int64_t B, int32_t N, void *stream);
+
 /* ---- next row f6: the ADD-L1 losses that consume calculate_T_pred's output, with their gradient ----------------
  * Replaces Iterative/loss.py:10-26 (compute_ADD_L1_loss), :29-48 (compute_disentangled_ADD_L1_loss) and :51-70
  * (transform_pts), called at Iterative/main.py:94-95,150-151,196-197 right after calculate_T_pred, plus the autograd
@@ -345,6 +357,21 @@ int so3_angle_stats(const double *deg, const int32_t *cls, int32_t ncls, double 
  */
 int so3_kabsch_f32(const float *P, const float *Q, float *R, float *H, int64_t B, int32_t N,
                    void *stream);
+
+/* ---- K5b: Kabsch backward (added in 210) ----------------------------------------------------------------
+ * The gradient the reference's autograd gives through symmetric_orthogonalization(bmm(Q^T, P))
+ * (rotation_representation.py:192-206 after the pairing rule of point_cloud/main.py:176-181), given the forward's H:
+ *     dH = K2(H, gR) + gH,    dQ_bi = dH_b p_bi,    dP_bi = dH_b^T q_bi.
+ * K2 is so3_project_bwd_f32's closed form, with its singular denominators clamped (a planar cloud's H is still
+ * fine; a collinear or all-zero cloud gets a finite gradient where autograd's is Inf / NaN).
+ *   P, Q     in   B*N*3 float32 (as for so3_kabsch_f32; dQ reads only P, dP reads only Q)
+ *   H        in   B*9 float32, the H so3_kabsch_f32 returned for P, Q
+ *   gR, gH   in   optional B*9 float32 upstream gradients of R and H (NULL: zero)
+ *   dP, dQ   out  optional B*N*3 float32 (NULL: not computed; a one-sided call reads half the bytes)
+ * Limits and NULL rules as so3_kabsch_f32: H always, P and Q when N > 0.  One launch, no atomics.
+ */
+int so3_kabsch_bwd_f32(const float *P, const float *Q, const float *H, const float *gR, const float *gH,
+                       float *dP, float *dQ, int64_t B, int32_t N, void *stream);
 
 /* ---- next row: on-device pair synthesis for Kabsch ------------------------------
  * so3_rotations_axis_angle_f32: the arithmetic of the reference's sampler, point_cloud/prepare.py:21-49

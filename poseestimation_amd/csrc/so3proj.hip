@@ -683,6 +683,85 @@ __global__ __launch_bounds__(kBlock) void k_kabsch(const float *__restrict__ P, 
     }
 }
 
+// ---- K5b: Kabsch backward ---------------------------------------------------------------------------------------
+// Forward H = sum_i q_i p_i^T, R = proj(H).  Given gR and gH (either may be null):
+//     dH = K2(H, gR) + gH,   dQ_i = dH p_i,   dP_i = dH^T q_i.
+// k_kabsch's skeleton turned round: the K2 body runs once per lane (lane j: the wave's j-th cloud; idle lanes take an
+// identity H and a zero gR) BEFORE the point loop, then each cloud's dH is broadcast from its lane (readlane, j is
+// wave-uniform) and the cloud is streamed.  dQ needs only P and dP only Q: a one-sided gradient reads half the bytes.
+template <bool WANT_DP, bool WANT_DQ>
+__global__ __launch_bounds__(kBlock) void k_kabsch_bwd(const float *__restrict__ P, const float *__restrict__ Q,
+                                                       const float *__restrict__ H, const float *__restrict__ gR,
+                                                       const float *__restrict__ gH, float *__restrict__ dP, float *__restrict__ dQ,
+                                                       int64_t B, int32_t N, int clouds_per_wave) {
+    const int lane = threadIdx.x & 63;
+    const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t wave = static_cast<int64_t>(blockIdx.x) * (kBlock / 64) + wave_in_block;
+    const int64_t c0 = wave * clouds_per_wave;
+    if (c0 >= B) return;
+    const int nc = static_cast<int>(min<int64_t>(clouds_per_wave, B - c0));
+    const bool active = lane < nc;
+    float dh[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) dh[i] = 0.f;
+    if (gR != nullptr) {
+        float h[9], g[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            h[i] = active ? H[(c0 + lane) * 9 + i] : ((i & 3) == 0 ? 1.f : 0.f);
+            g[i] = active ? gR[(c0 + lane) * 9 + i] : 0.f;
+        }
+        so3::project_backward_rows<float>(h, g, dh);
+    }
+    if (gH != nullptr) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) dh[i] += active ? gH[(c0 + lane) * 9 + i] : 0.f;
+    }
+    const unsigned cloud_bytes = static_cast<unsigned>(N) * 12u;
+    for (int j = 0; j < nc; ++j) {
+        float d[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) d[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dh[i]), j));
+        const int64_t base = (c0 + j) * N * 3;
+        so3::rsrc_t rp, rq, rdp, rdq;
+        if (WANT_DQ) {
+            rp = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(P) + base, 0, cloud_bytes, so3::kRsrcFlags);
+            rdq = __builtin_amdgcn_make_buffer_rsrc(dQ + base, 0, cloud_bytes, so3::kRsrcFlags);
+        }
+        if (WANT_DP) {
+            rq = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(Q) + base, 0, cloud_bytes, so3::kRsrcFlags);
+            rdp = __builtin_amdgcn_make_buffer_rsrc(dP + base, 0, cloud_bytes, so3::kRsrcFlags);
+        }
+        for (int i0 = 0; i0 < N; i0 += 64 * kKabschUnroll) {
+            u32x3 pp[kKabschUnroll], qq[kKabschUnroll];
+#pragma unroll
+            for (int u = 0; u < kKabschUnroll; ++u) {
+                const int off = (i0 + 64 * u + lane) * 12;
+                if (WANT_DQ) pp[u] = __builtin_amdgcn_raw_buffer_load_b96(rp, off, 0, so3::kStreamNt);
+                if (WANT_DP) qq[u] = __builtin_amdgcn_raw_buffer_load_b96(rq, off, 0, so3::kStreamNt);
+            }
+#pragma unroll
+            for (int u = 0; u < kKabschUnroll; ++u) {
+                const int off = (i0 + 64 * u + lane) * 12;       // lanes past the cloud's end: the range check drops the store
+                if (WANT_DQ) {
+                    const float px = __uint_as_float(pp[u].x), py = __uint_as_float(pp[u].y), pz = __uint_as_float(pp[u].z);
+                    const float x = fmaf(d[2], pz, fmaf(d[1], py, d[0] * px));
+                    const float y = fmaf(d[5], pz, fmaf(d[4], py, d[3] * px));
+                    const float z = fmaf(d[8], pz, fmaf(d[7], py, d[6] * px));
+                    __builtin_amdgcn_raw_buffer_store_b96(u32x3{__float_as_uint(x), __float_as_uint(y), __float_as_uint(z)}, rdq, off, 0, so3::kStreamNt);
+                }
+                if (WANT_DP) {
+                    const float qx = __uint_as_float(qq[u].x), qy = __uint_as_float(qq[u].y), qz = __uint_as_float(qq[u].z);
+                    const float x = fmaf(d[6], qz, fmaf(d[3], qy, d[0] * qx));
+                    const float y = fmaf(d[7], qz, fmaf(d[4], qy, d[1] * qx));
+                    const float z = fmaf(d[8], qz, fmaf(d[5], qy, d[2] * qx));
+                    __builtin_amdgcn_raw_buffer_store_b96(u32x3{__float_as_uint(x), __float_as_uint(y), __float_as_uint(z)}, rdp, off, 0, so3::kStreamNt);
+                }
+            }
+        }
+    }
+}
+
 // ---- next row f4: on-device pair synthesis for Kabsch (point_cloud/prepare.py:21-49, point_cloud/main.py:173-181) --
 // (a) the reference's rotation sampler as a kernel: quaternion (cos t, axis sin t) -> matrix, given the random draws;
 // (b) Kabsch with the second cloud synthesised on the fly, q_i = R_gt p_i + sigma n_i, so only P is read from HBM.
@@ -862,6 +941,91 @@ __global__ __launch_bounds__(kBlock) void k_rotate_clouds(const float *__restric
                 }
             }
         }
+    }
+}
+
+// a7b: the pairing rule's backward.  Forward q_i = R p_i; given G in the forward's output layout ((B,N,3), or (B,3,N) when
+// TRANSPOSED):  dP_i = R^T g_i,  dR = sum_i g_i p_i^T.  G is read once; P only for dR, which is accumulated as k_kabsch
+// accumulates H (lane j keeps cloud j's sum, the wave stores them at the end).  N == 0 still writes dR = 0.
+template <bool TRANSPOSED, bool WANT_DP, bool WANT_DR>
+__global__ __launch_bounds__(kBlock) void k_rotate_clouds_bwd(const float *__restrict__ P, const float *__restrict__ R,
+                                                              const float *__restrict__ G, float *__restrict__ dP,
+                                                              float *__restrict__ dR, int64_t B, int32_t N, int per_wave) {
+    const int lane = threadIdx.x & 63;
+    const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t wave = static_cast<int64_t>(blockIdx.x) * (kBlock / 64) + wave_in_block;
+    const int64_t c0 = wave * per_wave;
+    if (c0 >= B) return;
+    const int nc = static_cast<int>(min<int64_t>(per_wave, B - c0));
+    const unsigned cloud_bytes = static_cast<unsigned>(N) * 12u;
+    const unsigned row_bytes = static_cast<unsigned>(N) * 4u;
+    float dr[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) dr[i] = 0.f;
+    for (int j = 0; j < nc; ++j) {
+        float r[9];
+        if (WANT_DP) {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) r[i] = R[(c0 + j) * 9 + i];             // wave-uniform: scalar loads
+        }
+        const int64_t base = (c0 + j) * N * 3;
+        float *gb = const_cast<float *>(G) + base;
+        const so3::rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc(gb, 0, cloud_bytes, so3::kRsrcFlags);
+        const so3::rsrc_t rgx = __builtin_amdgcn_make_buffer_rsrc(gb, 0, row_bytes, so3::kRsrcFlags);
+        const so3::rsrc_t rgy = __builtin_amdgcn_make_buffer_rsrc(gb + N, 0, row_bytes, so3::kRsrcFlags);
+        const so3::rsrc_t rgz = __builtin_amdgcn_make_buffer_rsrc(gb + 2 * static_cast<int64_t>(N), 0, row_bytes, so3::kRsrcFlags);
+        so3::rsrc_t rp, rdp;
+        if (WANT_DR) rp = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(P) + base, 0, cloud_bytes, so3::kRsrcFlags);
+        if (WANT_DP) rdp = __builtin_amdgcn_make_buffer_rsrc(dP + base, 0, cloud_bytes, so3::kRsrcFlags);
+        float acc[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) acc[i] = 0.f;
+        for (int i0 = 0; i0 < N; i0 += 64 * kCloudUnroll) {
+            f32x3 gg[kCloudUnroll];
+            u32x3 pp[kCloudUnroll];
+#pragma unroll
+            for (int u = 0; u < kCloudUnroll; ++u) {
+                const int i = i0 + 64 * u + lane;                 // lanes past the cloud's end read zeros
+                if (TRANSPOSED) {
+                    gg[u].x = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rgx, i * 4, 0, so3::kStreamNt));
+                    gg[u].y = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rgy, i * 4, 0, so3::kStreamNt));
+                    gg[u].z = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rgz, i * 4, 0, so3::kStreamNt));
+                } else {
+                    const u32x3 v = __builtin_amdgcn_raw_buffer_load_b96(rg, i * 12, 0, so3::kStreamNt);
+                    gg[u] = f32x3{__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z)};
+                }
+                if (WANT_DR) pp[u] = __builtin_amdgcn_raw_buffer_load_b96(rp, i * 12, 0, so3::kStreamNt);
+            }
+#pragma unroll
+            for (int u = 0; u < kCloudUnroll; ++u) {
+                const float gx = gg[u].x, gy = gg[u].y, gz = gg[u].z;
+                if (WANT_DP) {
+                    const float x = fmaf(r[6], gz, fmaf(r[3], gy, r[0] * gx));
+                    const float y = fmaf(r[7], gz, fmaf(r[4], gy, r[1] * gx));
+                    const float z = fmaf(r[8], gz, fmaf(r[5], gy, r[2] * gx));
+                    __builtin_amdgcn_raw_buffer_store_b96(u32x3{__float_as_uint(x), __float_as_uint(y), __float_as_uint(z)}, rdp,
+                                                          (i0 + 64 * u + lane) * 12, 0, so3::kStreamNt);
+                }
+                if (WANT_DR) {
+                    const float px = __uint_as_float(pp[u].x), py = __uint_as_float(pp[u].y), pz = __uint_as_float(pp[u].z);
+                    acc[0] = fmaf(gx, px, acc[0]); acc[1] = fmaf(gx, py, acc[1]); acc[2] = fmaf(gx, pz, acc[2]);
+                    acc[3] = fmaf(gy, px, acc[3]); acc[4] = fmaf(gy, py, acc[4]); acc[5] = fmaf(gy, pz, acc[5]);
+                    acc[6] = fmaf(gz, px, acc[6]); acc[7] = fmaf(gz, py, acc[7]); acc[8] = fmaf(gz, pz, acc[8]);
+                }
+            }
+        }
+        if (WANT_DR) {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) {
+                const float tot = wave_allsum(acc[i]);
+                dr[i] = (lane == j) ? tot : dr[i];
+            }
+        }
+    }
+    if (WANT_DR && lane < nc) {
+        float *out = dR + (c0 + lane) * 9;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) out[i] = dr[i];
     }
 }
 
@@ -2766,6 +2930,56 @@ int so3_kabsch_f32(const float *P, const float *Q, float *R, float *H, int64_t B
     SO3_CHECK_ARGS(blocks <= 2147483647, "so3_kabsch_f32: B too large");
     hipLaunchKernelGGL(k_kabsch, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s, P, Q, R, H, B, N, static_cast<int>(cpw));
     return check_launch("so3_kabsch_f32");
+}
+
+int so3_kabsch_bwd_f32(const float *P, const float *Q, const float *H, const float *gR, const float *gH, float *dP, float *dQ,
+                       int64_t B, int32_t N, void *stream) {
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 40) && N >= 0 && N <= 150000000, "so3_kabsch_bwd_f32: B/N");
+    if (B == 0) return 0;
+    SO3_CHECK_ARGS(H != nullptr && (N == 0 || (P != nullptr && Q != nullptr)), "so3_kabsch_bwd_f32: null pointer");
+    if (N == 0 || (dP == nullptr && dQ == nullptr)) return 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int64_t cpw = B / (static_cast<int64_t>(device_cus()) * 16);          // k_kabsch's launch shape
+    if (cpw < 1) cpw = 1;
+    if (cpw > 64) cpw = 64;
+    const int64_t waves = (B + cpw - 1) / cpw;
+    const int64_t blocks = (waves + (kBlock / 64) - 1) / (kBlock / 64);
+    SO3_CHECK_ARGS(blocks <= 2147483647, "so3_kabsch_bwd_f32: B too large");
+    const dim3 grid(static_cast<unsigned>(blocks)), block(kBlock);
+    const int c = static_cast<int>(cpw);
+    if (dP != nullptr && dQ != nullptr) hipLaunchKernelGGL((k_kabsch_bwd<true, true>), grid, block, 0, s, P, Q, H, gR, gH, dP, dQ, B, N, c);
+    else if (dP != nullptr) hipLaunchKernelGGL((k_kabsch_bwd<true, false>), grid, block, 0, s, P, Q, H, gR, gH, dP, dQ, B, N, c);
+    else hipLaunchKernelGGL((k_kabsch_bwd<false, true>), grid, block, 0, s, P, Q, H, gR, gH, dP, dQ, B, N, c);
+    return check_launch("so3_kabsch_bwd_f32");
+}
+
+int so3_rotate_clouds_bwd_f32(const float *P, const float *R, const float *G, float *dP, float *dR, int transposed, int64_t B, int32_t N,
+                              void *stream) {
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 0 && N <= 150000000, "so3_rotate_clouds_bwd_f32: B/N");
+    if (B == 0) return 0;
+    if (N == 0) dP = nullptr;                                      // (N == 0: dR = 0 is the only output)
+    SO3_CHECK_ARGS((dP == nullptr || R != nullptr) && (N == 0 || (G != nullptr && (dR == nullptr || P != nullptr))),
+                   "so3_rotate_clouds_bwd_f32: null pointer");                 // R for dP, P for dR, G for either
+    if (dR == nullptr && dP == nullptr) return 0;
+    int64_t per_wave = B / (static_cast<int64_t>(device_cus()) * 16);
+    if (per_wave < 1) per_wave = 1;
+    if (per_wave > 64) per_wave = 64;
+    const int64_t waves = (B + per_wave - 1) / per_wave;
+    const dim3 grid(static_cast<unsigned>((waves + (kBlock / 64) - 1) / (kBlock / 64))), block(kBlock);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int pw = static_cast<int>(per_wave);
+#define SO3_ROT_BWD(T, WP, WR) hipLaunchKernelGGL((k_rotate_clouds_bwd<T, WP, WR>), grid, block, 0, s, P, R, G, dP, dR, B, N, pw)
+    if (transposed) {
+        if (dP != nullptr && dR != nullptr) SO3_ROT_BWD(true, true, true);
+        else if (dP != nullptr) SO3_ROT_BWD(true, true, false);
+        else SO3_ROT_BWD(true, false, true);
+    } else {
+        if (dP != nullptr && dR != nullptr) SO3_ROT_BWD(false, true, true);
+        else if (dP != nullptr) SO3_ROT_BWD(false, true, false);
+        else SO3_ROT_BWD(false, false, true);
+    }
+#undef SO3_ROT_BWD
+    return check_launch("so3_rotate_clouds_bwd_f32");
 }
 
 }  // extern "C"

@@ -905,11 +905,8 @@ class FrobeniusHeadStep:
 # --------------------------------------------------------------------------------------------
 # K5: Kabsch
 # --------------------------------------------------------------------------------------------
-def kabsch_rotation(P: torch.Tensor, Q: torch.Tensor, return_h: bool = False):
-    """R_b = argmin_R sum_i |R p_bi - q_bi|^2 over SO(3) = proj(sum_i q_bi p_bi^T).
-
-    P, Q: (B, N, 3) float32 clouds as in point_cloud/main.py:171-181 (q = R p, no translation).
-    Equivalent to symmetric_orthogonalization(torch.bmm(Q.transpose(1, 2), P)) in one launch."""
+def _kabsch_call(P, Q, want_h):
+    """K5 on float32 copies of the clouds: (p, q, R, H or None).  Both the plain call and the graph node run exactly this."""
     dev = _require_device(P, Q)
     if P.dim() != 3 or P.shape[-1] != 3 or P.shape != Q.shape:
         raise RuntimeError(f"kabsch_rotation: expected two (B, N, 3) tensors, got {tuple(P.shape)} and {tuple(Q.shape)}")
@@ -917,19 +914,67 @@ def kabsch_rotation(P: torch.Tensor, Q: torch.Tensor, return_h: bool = False):
     q = Q.detach().contiguous().float()
     b, n, _ = p.shape
     r = torch.empty((b, 3, 3), dtype=torch.float32, device=dev)
-    h = torch.empty((b, 3, 3), dtype=torch.float32, device=dev) if return_h else None
+    h = torch.empty((b, 3, 3), dtype=torch.float32, device=dev) if want_h else None
     with _on_device(dev):
         _check(_libh().so3_kabsch_f32(_ptr(p), _ptr(q), _ptr(r), _ptr(h), b, n, _stream(dev)), "so3_kabsch_f32")
+    return p, q, r, h
+
+
+class _Kabsch(torch.autograd.Function):
+    """kabsch_rotation as a graph node: the reference's expression symmetric_orthogonalization(bmm(Q^T, P)) is differentiable.
+    Forward asks K5 for H as well and keeps it; backward is K5b (so3_kabsch_bwd_f32): dH = K2(H, gR) + gH, dQ = dH p, dP = dH^T q."""
+
+    @staticmethod
+    def forward(ctx, P, Q, return_h):
+        p, q, r, h = _kabsch_call(P, Q, True)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(p, q, h)
+        ctx.meta = ((P.shape, P.dtype), (Q.shape, Q.dtype))
+        return (r, h) if return_h else r
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_r, grad_h=None):
+        p, q, h = ctx.saved_tensors
+        (shape_p, dtype_p), (shape_q, dtype_q) = ctx.meta
+        need_p, need_q = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if (grad_r is None and grad_h is None) or not (need_p or need_q):
+            return None, None, None
+        dev = p.device
+        gr = None if grad_r is None else grad_r.reshape(-1, 9).float().contiguous()
+        gh = None if grad_h is None else grad_h.reshape(-1, 9).float().contiguous()
+        dp = torch.empty_like(p) if need_p else None
+        dq = torch.empty_like(q) if need_q else None
+        b, n, _ = p.shape
+        with _on_device(dev):
+            _check(_libh().so3_kabsch_bwd_f32(_ptr(p), _ptr(q), _ptr(h), _ptr(gr), _ptr(gh), _ptr(dp), _ptr(dq), b, n, _stream(dev)),
+                   "so3_kabsch_bwd_f32")
+        if dp is not None:
+            dp = (dp if dtype_p is torch.float32 else dp.to(dtype_p)).view(shape_p)
+        if dq is not None:
+            dq = (dq if dtype_q is torch.float32 else dq.to(dtype_q)).view(shape_q)
+        return dp, dq, None
+
+
+def kabsch_rotation(P: torch.Tensor, Q: torch.Tensor, return_h: bool = False):
+    """R_b = argmin_R sum_i |R p_bi - q_bi|^2 over SO(3) = proj(sum_i q_bi p_bi^T).
+
+    P, Q: (B, N, 3) float32 clouds as in point_cloud/main.py:171-181 (q = R p, no translation).
+    Equivalent to symmetric_orthogonalization(torch.bmm(Q.transpose(1, 2), P)) in one launch, and differentiable like
+    that expression with respect to both clouds (K5b, so3_kabsch_bwd_f32); with return_h=True, H = bmm(Q^T, P) is a
+    differentiable output too.  Gradients come back in each argument's dtype; where H has a vanishing singular-value
+    gap (collinear or empty clouds) K2's clamp keeps them finite where the reference's autograd gives Inf / NaN."""
+    if _wants_grad(P, Q):
+        _require_device(P, Q)
+        return _Kabsch.apply(P, Q, return_h)
+    _, _, r, h = _kabsch_call(P, Q, return_h)
     return (r, h) if return_h else r
 
 
 # --------------------------------------------------------------------------------------------
 # row a7: the cloud side of the point-cloud path
 # --------------------------------------------------------------------------------------------
-def rotate_point_clouds(pc: torch.Tensor, R: torch.Tensor, transposed: bool = False) -> torch.Tensor:
-    """q_bi = R_b p_bi for every point of every cloud: the pairing rule of point_cloud/main.py:173-181 (expand the
-    rotation to all points, bmm, view) in one launch.  pc: (B,N,3), R: (B,3,3).  Returns (B,N,3), or with
-    `transposed` the contiguous (B,3,N) tensor the reference obtains from `.transpose(1, 2)` at :183."""
+def _rotate_call(pc, R, transposed):
     dev = _require_device(pc, R)
     if pc.dim() != 3 or pc.shape[-1] != 3 or R.numel() != pc.shape[0] * 9:
         raise RuntimeError(f"rotate_point_clouds: expected (B, N, 3) and (B, 3, 3), got {tuple(pc.shape)} and {tuple(R.shape)}")
@@ -939,7 +984,51 @@ def rotate_point_clouds(pc: torch.Tensor, R: torch.Tensor, transposed: bool = Fa
     out = torch.empty((b, 3, n) if transposed else (b, n, 3), dtype=torch.float32, device=dev)
     with _on_device(dev):
         _check(_libh().so3_rotate_clouds_f32(_ptr(p), _ptr(r), _ptr(out), 1 if transposed else 0, b, n, _stream(dev)), "so3_rotate_clouds_f32")
-    return out
+    return p, r, out
+
+
+class _RotateClouds(torch.autograd.Function):
+    """rotate_point_clouds as a graph node (the reference's bmm is differentiable): backward is a7b, so3_rotate_clouds_bwd_f32,
+    dpc = R^T g and dR = sum_i g p^T, reading g in the forward's output layout."""
+
+    @staticmethod
+    def forward(ctx, pc, R, transposed):
+        p, r, out = _rotate_call(pc, R, transposed)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(p if ctx.needs_input_grad[1] else None, r if ctx.needs_input_grad[0] else None)
+        ctx.meta = ((pc.shape, pc.dtype), (R.shape, R.dtype), bool(transposed), p.shape[0], p.shape[1], p.device)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        p, r = ctx.saved_tensors
+        (shape_p, dtype_p), (shape_r, dtype_r), transposed, b, n, dev = ctx.meta
+        need_p, need_r = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if grad_out is None or not (need_p or need_r):
+            return None, None, None
+        g = grad_out.float().contiguous()
+        dp = torch.empty((b, n, 3), dtype=torch.float32, device=dev) if need_p else None
+        dr = torch.empty((b, 9), dtype=torch.float32, device=dev) if need_r else None
+        with _on_device(dev):
+            _check(_libh().so3_rotate_clouds_bwd_f32(_ptr(p), _ptr(r), _ptr(g), _ptr(dp), _ptr(dr), 1 if transposed else 0, b, n, _stream(dev)),
+                   "so3_rotate_clouds_bwd_f32")
+        if dp is not None:
+            dp = (dp if dtype_p is torch.float32 else dp.to(dtype_p)).view(shape_p)
+        if dr is not None:
+            dr = (dr if dtype_r is torch.float32 else dr.to(dtype_r)).view(shape_r)
+        return dp, dr, None
+
+
+def rotate_point_clouds(pc: torch.Tensor, R: torch.Tensor, transposed: bool = False) -> torch.Tensor:
+    """q_bi = R_b p_bi for every point of every cloud: the pairing rule of point_cloud/main.py:173-181 (expand the
+    rotation to all points, bmm, view) in one launch.  pc: (B,N,3), R: (B,3,3).  Returns (B,N,3), or with
+    `transposed` the contiguous (B,3,N) tensor the reference obtains from `.transpose(1, 2)` at :183.
+    Differentiable with respect to pc and R, like the reference's bmm (a7b, so3_rotate_clouds_bwd_f32)."""
+    if _wants_grad(pc, R):
+        _require_device(pc, R)
+        return _RotateClouds.apply(pc, R, transposed)
+    return _rotate_call(pc, R, transposed)[2]
 
 
 def pc_normalize(pc: torch.Tensor):
@@ -947,6 +1036,9 @@ def pc_normalize(pc: torch.Tensor):
     pc: (N,3) as the reference takes it, or a (B,N,3) batch.  Returns (pc, centroid, scale) like the reference
     (centroid (3,) / (B,3); scale 0-dim / (B,)), float32 on the device."""
     dev = _require_device(pc)
+    if _wants_grad(pc):
+        _warn_once("pc_normalize", "pc_normalize is data preparation (numpy in the reference, point_cloud/prepare.py:51-56): its outputs "
+                                   "carry no gradient although the cloud requires grad.")
     single = pc.dim() == 2
     p = (pc.unsqueeze(0) if single else pc).detach().contiguous().float()
     if p.dim() != 3 or p.shape[-1] != 3 or p.shape[1] < 1:
@@ -973,6 +1065,10 @@ def get_sampled_rotation_matrices_by_axisAngle(batch: int, device="cuda", genera
 
 def rotations_from_axis_angle_draws(theta: torch.Tensor, axis: torch.Tensor) -> torch.Tensor:
     dev = _require_device(theta, axis)
+    if _wants_grad(theta, axis):
+        _warn_once("rotations_from_axis_angle_draws",
+                   "rotations_from_axis_angle_draws (the sampler of get_sampled_rotation_matrices_by_axisAngle) draws targets: its rotations "
+                   "carry no gradient although a draw requires grad.")
     t = theta.detach().reshape(-1).contiguous().float()
     a = axis.detach().reshape(-1, 3).contiguous().float()
     if a.shape[0] != t.shape[0]:
@@ -989,6 +1085,11 @@ def kabsch_rotation_synthetic(P: torch.Tensor, R_gt: torch.Tensor, sigma: float 
     dev = _require_device(P, R_gt)
     if P.dim() != 3 or P.shape[-1] != 3 or R_gt.shape[0] != P.shape[0]:
         raise RuntimeError("kabsch_rotation_synthetic: expected P (B,N,3) and R_gt (B,3,3)")
+    if _wants_grad(P, R_gt):
+        _warn_once("kabsch_rotation_synthetic",
+                   "kabsch_rotation_synthetic is not differentiable (its second cloud exists only inside the kernel): R and H carry no "
+                   "gradient although an argument requires grad.  kabsch_rotation(P, rotate_point_clouds(P, R_gt) + noise) is the "
+                   "differentiable spelling.")
     p = P.detach().contiguous().float()
     g = R_gt.detach().reshape(-1, 9).contiguous().float()
     b, n, _ = p.shape

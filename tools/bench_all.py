@@ -146,6 +146,15 @@ def main():
     qc = [torch.rand(b, npts, 3, device=dev) - 0.5 for _ in range(2)]
     rk = torch.empty(b, 9, device=dev)
     timeit("K5 so3_kabsch_f32", lambda i: lib.so3_kabsch_f32(p(pc[i % 2]), p(qc[i % 2]), p(rk), None, b, npts, st), b * (2 * npts * 12 + 36), iters=10, warm=2)
+    hk = torch.empty(b, 9, device=dev)
+    lib.so3_kabsch_f32(p(pc[0]), p(qc[0]), p(rk), p(hk), b, npts, st)
+    gkr, gkh = torch.randn(b, 9, device=dev), torch.randn(b, 9, device=dev)
+    dpc, dqc = torch.empty(b, npts, 3, device=dev), torch.empty(b, npts, 3, device=dev)
+    timeit("K5b so3_kabsch_bwd_f32 (dP and dQ)", lambda i: lib.so3_kabsch_bwd_f32(p(pc[i % 2]), p(qc[i % 2]), p(hk), p(gkr), p(gkh), p(dpc), p(dqc), b, npts, st),
+           b * (48 * npts + 108), iters=10, warm=2)
+    timeit("K5b so3_kabsch_bwd_f32 (dQ only)", lambda i: lib.so3_kabsch_bwd_f32(p(pc[i % 2]), p(qc[i % 2]), p(hk), p(gkr), p(gkh), None, p(dqc), b, npts, st),
+           b * (24 * npts + 108), iters=10, warm=2)
+    del hk, gkr, gkh, dqc
     rg = rr.get_sampled_rotation_matrices_by_axisAngle(b, dev).reshape(b, 9).contiguous()
     timeit("f4 so3_kabsch_synth_f32 (sigma=0: P only)", lambda i: lib.so3_kabsch_synth_f32(p(pc[i % 2]), p(rg), ctypes.c_float(0.0), 1, p(rk), None, b, npts, st), b * (npts * 12 + 72), iters=10, warm=2)
     timeit("f4 so3_kabsch_synth_f32 (sigma=0.01, device RNG)", lambda i: lib.so3_kabsch_synth_f32(p(pc[i % 2]), p(rg), ctypes.c_float(0.01), 1, p(rk), None, b, npts, st), b * (npts * 12 + 72), iters=10, warm=2)
@@ -160,7 +169,12 @@ def main():
     timeit("a7 so3_rotate_clouds_f32", lambda i: lib.so3_rotate_clouds_f32(p(pc[i % 2]), p(rg), p(qo), 0, b, npts, st), b * (npts * 24 + 36), iters=10, warm=2)
     timeit("a7 so3_rotate_clouds_f32 (transposed out)", lambda i: lib.so3_rotate_clouds_f32(p(pc[i % 2]), p(rg), p(qo), 1, b, npts, st), b * (npts * 24 + 36), iters=10, warm=2)
     timeit("a7 so3_pc_normalize_f32", lambda i: lib.so3_pc_normalize_f32(p(pc[i % 2]), p(qo), None, None, b, npts, st), b * (npts * 24), iters=10, warm=2)
-    del pc, tg, tq, dtq, qo
+    drg = torch.empty(b, 9, device=dev)            # qo: the upstream gradient (either layout: same bytes); dpc: dP
+    timeit("a7b so3_rotate_clouds_bwd_f32 (dP and dR)", lambda i: lib.so3_rotate_clouds_bwd_f32(p(pc[i % 2]), p(rg), p(qo), p(dpc), p(drg), 0, b, npts, st),
+           b * (36 * npts + 72), iters=10, warm=2)
+    timeit("a7b so3_rotate_clouds_bwd_f32 (transposed G, dP and dR)",
+           lambda i: lib.so3_rotate_clouds_bwd_f32(p(pc[i % 2]), p(rg), p(qo), p(dpc), p(drg), 1, b, npts, st), b * (36 * npts + 72), iters=10, warm=2)
+    del pc, tg, tq, dtq, qo, dpc, drg
     torch.cuda.empty_cache()
     print("--- config #4: B = 512, bf16 storage, fused head + loss + backward ---")
     b = 512

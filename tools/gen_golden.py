@@ -294,7 +294,64 @@ def g15_metric_gradients():
     save("g15_metric_gradients.npz", **out)
 
 
+def g16_cloud_gradients():
+    """Autograd through the cloud side.  Kabsch: the reference's symmetric_orthogonalization (rotation_representation.py:192-206,
+    torch.svd's autograd) on torch.bmm(Q^T, P), for 12 clouds of 48 points -- 6 noisy pairs q = R p + 0.01 n, 4 independent pairs (det
+    flips among them) and 2 planar clouds (z = 0, q = R p exactly: rank-2 H) --, losses (R*gR).sum() and (R*gR).sum() + (H*gH).sum(),
+    float32 and float64.  Rotation: the four pairing statements of point_cloud/main.py:176-183 replayed verbatim with requires_grad on
+    pc1 and gt_rmat, a random upstream on pc_out and on gg (the transposed layout), float32 and float64."""
+    torch.manual_seed(16)
+    np.random.seed(16)
+    b, n = 12, 48
+    p = torch.rand(b, n, 3) - 0.5
+    p[10:, :, 2] = 0.0                                                    # planar clouds
+    r_gt = sample_rot(b)
+    q = torch.bmm(r_gt, p.transpose(1, 2)).transpose(1, 2).contiguous()
+    q[:6] += 0.01 * torch.randn(6, n, 3)
+    q[6:10] = torch.rand(4, n, 3) - 0.5                                   # independent pairs
+    for c in (8, 9):                                                      # two of them mirrored where needed: det(H) < 0 (K1's flip)
+        if torch.det(q[c].T @ p[c]) > 0:
+            q[c, :, 0] = -q[c, :, 0]
+    g_r, g_h = torch.randn(b, 3, 3), torch.randn(b, 3, 3)
+    out = {"p": p, "q": q, "g_r": g_r, "g_h": g_h}
+    for dt_tag, dt in (("f32", torch.float32), ("f64", torch.float64)):
+        for case in ("r", "rh"):
+            pa = p.to(dt).clone().requires_grad_(True)
+            qa = q.to(dt).clone().requires_grad_(True)
+            h = torch.bmm(qa.transpose(1, 2), pa)
+            r = rr.symmetric_orthogonalization(h)
+            loss = (r * g_r.to(dt)).sum()
+            if case == "rh":
+                loss = loss + (h * g_h.to(dt)).sum()
+            loss.backward()
+            key = "kabsch_%s_%s" % (case, dt_tag)
+            out[key + "_dp"], out[key + "_dq"] = pa.grad, qa.grad
+            if case == "r":
+                out["kabsch_%s_r" % dt_tag], out["kabsch_%s_h" % dt_tag] = r.detach(), h.detach()
+    batch, point_num = 4, 48
+    pc = torch.rand(batch, point_num, 3) - 0.5
+    rot = sample_rot(batch)
+    u_out, u_gg = torch.randn(batch, point_num, 3), torch.randn(batch, 3, point_num)
+    out.update(pc1=pc, gt_rmat=rot, u_out=u_out, u_gg=u_gg)
+    for dt_tag, dt in (("f32", torch.float32), ("f64", torch.float64)):
+        for layout, up in (("out", u_out), ("gg", u_gg)):
+            pc1 = pc.to(dt).clone().requires_grad_(True)
+            gt_rmat = rot.to(dt).clone().requires_grad_(True)
+            gt_rmats = gt_rmat.contiguous().view(batch, 1, 3, 3).expand(batch, point_num, 3, 3).contiguous().view(-1, 3, 3)   # :176-177
+            pc2 = torch.bmm(gt_rmats, pc1.view(-1, 3, 1))                                                                      # :180
+            pc_out = pc2.view(batch, point_num, 3)                                                                             # :181
+            gg = pc_out.transpose(1, 2)                                                                                        # :183
+            y = pc_out if layout == "out" else gg
+            (y * up.to(dt)).sum().backward()
+            key = "rot_%s_%s" % (layout, dt_tag)
+            out[key + "_dpc"], out[key + "_dr"] = pc1.grad, gt_rmat.grad
+            out[key + "_y"] = y.detach().contiguous()
+    save("g16_cloud_gradients.npz", **out)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "g16":
+        return g16_cloud_gradients()
     if len(sys.argv) > 1 and sys.argv[1] == "g15":
         return g15_metric_gradients()
     if len(sys.argv) > 1 and sys.argv[1] == "g14":
