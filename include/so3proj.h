@@ -160,6 +160,34 @@ int so3_angle_error_v2(const float *R1, const float *R2, double *deg, double *su
 int so3_project_angle_error_v2_f32(const float *M, const float *Rtrue, float *R, double *deg, double *sum_count,
                                    int32_t *range_flag, void *workspace, unsigned flags, int64_t B, void *stream);
 
+/* ---- K4s / K3s: the metric and the loss up to a symmetry group (added in 210) ------------------------------------
+ * For objects whose shape a rotation leaves unchanged (ModelNet10-SO(3)'s bathtub, table: 3D-Pose/test_per_class.py:188) the
+ * ground truth is defined up to the group.  The group acts on the PREDICTION from the right, as 3D-Pose/loss.py:14-24
+ * (rotate_by_180: R_guess @ Rx(pi), ...): a row's candidates are Rpred_b S_k.
+ *   S          in   num_classes*K*9 float32: class c's rotations S_{c,0} = I, S_{c,1}, ..., S_{c,K-1} (a class with fewer elements
+ *                   padded with the identity).  Orthogonality is the caller's to check (the Python layer does, in float64).
+ *   class_id   in   B int32 class of each row: required when num_classes > 1, NULL for one class.  An id outside [0, num_classes)
+ *                   gives the row NaN (angle, loss) and index -1.
+ *   index      out  optional B int32: the smallest k attaining the row's minimum (k* = 0 wherever the identity is among the best)
+ * Limits: 1 <= K <= 64, num_classes >= 1, num_classes * K <= 256; B = 0 is a no-op.
+ * so3_sym_angle_error_f32: deg_b = min_k angle(Rpred_b S_k, Rtrue_b), float64 degrees (radians with SO3_RADIANS) on float32 data.
+ *   k = 0 is so3_angle_error_v2's arithmetic bit for bit; a further candidate's trace is sum_lj S_lj M_lj in float64 with
+ *   M = Rpred^T Rtrue.  With the table {I} the result equals so3_angle_error_v2's.
+ *   flags_out  out optional 1 int32, zeroed by the call: bit 0 = some identity cosine outside [-1.1, 1.1] (the reference's raise),
+ *                  bit 1 = some class id out of range.
+ * so3_sym_frob_loss_f32: loss = mean_b min_k ||Rtrue_b - Rpred_b S_k||_F (not squared) and the gradient of the selected branch
+ *   at unit upstream scale: dRpred = -(Rtrue - Rpred S_k*) S_k*^T / (B d), dRtrue = (Rtrue - Rpred S_k*) / (B d), 0 at d = 0.
+ *   The selection compares float32 traces of M; the winner's distance and gradient come from Rtrue - Rpred S_k* directly.  With
+ *   the table {I} it is so3_frob_loss_v2_f32.
+ *   dRpred, dRtrue  out optional B*9 float32;  loss_sum out 1 double;  loss_mean out optional 1 float;
+ *   workspace  as so3_frob_loss_v2_f32 (used above 1024 rows; NULL: a memset and atomics instead).  flags: none defined (0).
+ */
+int so3_sym_angle_error_f32(const float *Rpred, const float *Rtrue, const float *S, const int32_t *class_id, int32_t num_classes,
+                            int32_t K, double *deg, int32_t *index, int32_t *flags_out, unsigned flags, int64_t B, void *stream);
+int so3_sym_frob_loss_f32(const float *Rpred, const float *Rtrue, const float *S, const int32_t *class_id, int32_t num_classes,
+                          int32_t K, float *dRpred, float *dRtrue, int32_t *index, double *loss_sum, float *loss_mean,
+                          void *workspace, unsigned flags, int64_t B, void *stream);
+
 /* Diagnostic: K1 one row per thread (the same arithmetic, bit for bit, as so3_project_fwd_f32) plus, per row, the device's own
  * verdict: hard[b] = 1 where the quaternion fast path did not certify its result and the row was redone by the Jacobi path.
  * For tests that search for inputs the certificate wrongly accepts (tests/test_gpu_parity.py); not a production entry point. */

@@ -60,6 +60,8 @@ SYMBOLS = {
     "so3_rotate_clouds_bwd_f32": (_INT, [_P, _P, _P, _P, _P, _INT, _I64, _I32, _P]),
     "so3_rotations_axis_angle_f32": (_INT, [_P, _P, _P, _I64, _P]),
     "so3_kabsch_synth_f32": (_INT, [_P, _P, ctypes.c_float, ctypes.c_uint32, _P, _P, _I64, _I32, _P]),
+    "so3_sym_angle_error_f32": (_INT, [_P, _P, _P, _P, _I32, _I32, _P, _P, _P, _U32, _I64, _P]),
+    "so3_sym_frob_loss_f32": (_INT, [_P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _U32, _I64, _P]),
 }
 
 ABI_VERSION = 210                                 # include/so3proj.h: SO3PROJ_VERSION this binding's argument lists belong to

@@ -1030,6 +1030,195 @@ struct OpAngle : OpBase {
     }
 };
 
+// ---- K4s / K3s: the metric and the loss up to a symmetry group (so3_sym_angle_error_f32, so3_sym_frob_loss_f32) ----------------
+// A table of rotations S_0 = I, S_1, ..., S_{K-1} per class -- float32 (C, K, 9), a class with fewer elements padded with the identity --
+// acts on the PREDICTION from the right, as 3D-Pose/loss.py:14-24 (R_guess @ Rx): a row's candidates are R_pred S_k.  The best candidate
+// wins, ties go to the smallest k, so padding never shows.  tr((P S)^T T) = sum_lj S_lj M_lj with M = P^T T: nine FMAs per candidate.
+// One class: every lane reads the same entries (scalar loads).  Several: the row's class id rides along as a third input (one int32 per
+// row) and a lane reads its class's entries through the vector cache -- a table is at most 256 x 36 B = 9 KB, resident after the first
+// rounds -- instead of a staged LDS copy, which the engine's one-workgroup-per-CU slot layout has no room to spare for.
+// A class id outside [0, C) makes the row's result NaN and its index -1.
+template <bool MULTI> using SymTab = typename std::conditional<MULTI, const float *, const __attribute__((address_space(4))) float *>::type;
+struct SymTableArgs {
+    const float *table = nullptr;
+    int K = 1, C = 1;
+    // the row's candidates (class 0 for a single-class table or a bad id); `bad`: the id is outside [0, C)
+    // (the single-class table is read through the constant address space: wave-uniform addresses of memory nobody writes during the
+    // launch, which the compiler turns into scalar loads instead of a vector load per candidate that every iteration waited for)
+    template <bool MULTI, class T>
+    __device__ __forceinline__ const SymTab<MULTI> row_table(const T (&c)[1], bool exists, bool &bad) const {
+        if constexpr (!MULTI) {
+            bad = false;
+            return (SymTab<MULTI>)(reinterpret_cast<uintptr_t>(table));
+        } else {
+            const int cls = __float_as_int(c[0]);
+            bad = exists && static_cast<unsigned>(cls) >= static_cast<unsigned>(C);
+            return table + (bad ? 0 : cls) * (K * 9);
+        }
+    }
+};
+// M = P^T T, M_lj = sum_i P_il T_ij, in F (float64 for the metric, float32 for the loss's selection)
+template <class F> __device__ __forceinline__ void pt_times_t(const float (&p)[9], const float (&t)[9], F (&m)[9]) {
+#pragma unroll
+    for (int l = 0; l < 3; ++l)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            F acc = static_cast<F>(p[l]) * static_cast<F>(t[j]);
+            acc = __builtin_elementwise_fma(static_cast<F>(p[3 + l]), static_cast<F>(t[3 + j]), acc);
+            m[l * 3 + j] = __builtin_elementwise_fma(static_cast<F>(p[6 + l]), static_cast<F>(t[6 + j]), acc);
+        }
+}
+__device__ __forceinline__ void store_row_i32(int32_t *base, const RowCtx<1> &ctx, int v) {
+    if (base != nullptr && ctx.exists[0])
+        __builtin_amdgcn_raw_buffer_store_b32(static_cast<unsigned>(v), row_rsrc<4>(base, ctx.unit[0], true), ctx.lane * 4, 0, 0);
+}
+
+// K4s: theta_b = min_k angle(P_b S_k, T_b) in float64 degrees and the smallest k attaining it.  The candidates' traces go through M in
+// float64 and are compared on the clamped cosine (acos is decreasing), one acos per row at the end; where the identity wins, its angle is K4's
+// own arithmetic (OpAngle, bit for bit).
+// flags_out (zeroed by the host) gets bit 0 where the identity candidate's cosine is outside [-1.1, 1.1] (angle_error's raise), bit 1 for a
+// class id out of range: one vector atomic per wave that saw one.
+template <bool MULTI>
+struct OpSymAngle : OpBase {
+    static constexpr int kIn0 = 4, kIn1 = 4, kIn2 = MULTI ? 4 : 0, kOut0 = 0, kOut1 = 0;
+    static constexpr int kIn2N = 1;
+    SymTableArgs sym;
+    double *deg = nullptr;
+    int32_t *index = nullptr, *flags_out = nullptr;
+    double unit_scale = 1.0;
+    template <class T, int NPL>
+    __device__ __forceinline__ void compute(Rows<T, OpSymAngle> &rows, RowCtx<NPL> &ctx) const {
+        static_assert(NPL == 1, "one row per lane: the candidates' loop is a dependent chain of compares");
+        const float (&a)[9] = rows.a;
+        const float (&b)[9] = rows.b;
+        double tr = 0.0;                                     // candidate 0: OpAngle's arithmetic, operation for operation
+#pragma unroll
+        for (int i = 0; i < 9; ++i) tr = fma(static_cast<double>(a[i]), static_cast<double>(b[i]), tr);
+        const double c_raw = (tr - 1.0) * 0.5;
+        const bool bad_range = ctx.exists[0] && (c_raw < -1.1 || c_raw > 1.1);
+        double best = fmin(fmax(c_raw, -1.0), 1.0);
+        if (c_raw != c_raw) best = c_raw;                    // a NaN row stays NaN (no candidate compares greater) at k = 0
+        bool bad_cls;
+        const SymTab<MULTI> tab = sym.row_table<MULTI>(rows.c, ctx.exists[0], bad_cls);
+        int kb = 0;
+        if (sym.K > 1) {
+            // the selection compares every candidate, the identity included, through M: equal table entries (the padding) then give
+            // equal cosines and tie exactly, where the identity's direct trace above may differ from them in the last bit
+            double m[9];
+            pt_times_t(a, b, m);
+            auto cosine = [&](int k) {
+                double t = 0.0;
+#pragma unroll
+                for (int i = 0; i < 9; ++i) t = fma(static_cast<double>(tab[k * 9 + i]), m[i], t);
+                return fmin(fmax((t - 1.0) * 0.5, -1.0), 1.0);
+            };
+            double sel = cosine(0);
+#pragma unroll 4
+            for (int k = 1; k < sym.K; ++k) {
+                const double c = cosine(k);
+                if (c > sel) { sel = c; kb = k; }
+            }
+            if (kb != 0) best = sel;
+        }
+        double ang = acos_f64(best) * unit_scale;
+        if (bad_cls) { ang = __longlong_as_double(0x7ff8000000000000ll); kb = -1; }
+        if (ctx.exists[0]) {
+            const u32x2 bits = __builtin_bit_cast(u32x2, ang);
+            __builtin_amdgcn_raw_buffer_store_b64(bits, row_rsrc<8>(deg, ctx.unit[0], true), ctx.lane * 8, 0, 0);
+        }
+        store_row_i32(index, ctx, kb);
+        if (__builtin_expect(wave_any(bad_range || bad_cls), 0)) {
+            const int f = (wave_any(bad_range) ? 1 : 0) | (wave_any(bad_cls) ? 2 : 0);
+            if (flags_out != nullptr && lane_id_now() == 0) atomicOr(flags_out, f);
+        }
+    }
+};
+
+// K3s: loss_b = min_k ||T_b - P_b S_k||_F, the smallest minimising k, and the gradient of the selected branch at unit upstream scale,
+// dP = -(T - P S_k*) S_k*^T / (B d), dT = (T - P S_k*) / (B d), 0 at d = 0.  The selection runs on the float32 traces of M (||P S|| = ||P||
+// for an orthogonal S, so the largest trace is the smallest distance); the winner's distance and gradient are computed directly from
+// T - P S_k*, and for k* = 0 from T - P, OpFrobLoss's arithmetic.
+template <bool MULTI, bool WANT_DP, bool WANT_DT>
+struct OpSymFrobLoss : OpBase {
+    static constexpr int kIn0 = 4, kIn1 = 4, kIn2 = MULTI ? 4 : 0, kOut0 = WANT_DP ? 4 : 0, kOut1 = WANT_DT ? 4 : 0;
+    static constexpr int kIn2N = 1;
+    static constexpr bool kReduce = true;
+    SymTableArgs sym;
+    int32_t *index = nullptr;
+    double *loss_sum = nullptr;
+    float *loss_mean = nullptr;
+    float inv_b = 0.f;
+    double inv_b_f64 = 0.0;
+    template <class T, int NPL>
+    __device__ __forceinline__ void compute(Rows<T, OpSymFrobLoss> &rows, RowCtx<NPL> &ctx) const {
+        static_assert(NPL == 1, "one row per lane");
+        typedef Tr<float> R;
+        const float (&p)[9] = rows.a;
+        const float (&t)[9] = rows.b;
+        bool bad_cls;
+        const SymTab<MULTI> tab = sym.row_table<MULTI>(rows.c, ctx.exists[0], bad_cls);
+        int kb = 0;
+        float q[9];                                          // P S_k*
+#pragma unroll
+        for (int i = 0; i < 9; ++i) q[i] = p[i];
+        float s[9];                                          // S_k*
+        if (sym.K > 1) {
+            float m[9];
+            pt_times_t(p, t, m);
+            float best = 0.f;
+#pragma unroll
+            for (int i = 0; i < 9; ++i) best = fmaf(tab[i], m[i], best);
+#pragma unroll 4
+            for (int k = 1; k < sym.K; ++k) {
+                float tr = 0.f;
+#pragma unroll
+                for (int i = 0; i < 9; ++i) tr = fmaf(tab[k * 9 + i], m[i], tr);
+                if (tr > best) { best = tr; kb = k; }
+            }
+#pragma unroll
+            for (int i = 0; i < 9; ++i) s[i] = tab[kb * 9 + i];
+            if (kb != 0) {
+#pragma unroll
+                for (int i = 0; i < 3; ++i)
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) q[i * 3 + j] = fmaf(p[i * 3 + 2], s[6 + j], fmaf(p[i * 3 + 1], s[3 + j], p[i * 3] * s[j]));
+            }
+        }
+        float g[9];                                          // P S - T
+        float n2 = 0.f;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) { g[i] = q[i] - t[i]; n2 = R::fma(g[i], g[i], n2); }
+        const float inv = R::rsq(R::max(n2, 1e-37f));
+        const float nan = __int_as_float(0x7fc00000);
+        const float nrm = bad_cls ? nan : n2 * inv;
+        if (ctx.exists[0]) ctx.acc += static_cast<double>(nrm);
+        const float gs = bad_cls ? nan : (n2 > 0.f ? inv * inv_b : 0.f);
+        if constexpr (WANT_DT) {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) rows.o1[i] = -(g[i] * gs);
+        }
+        if constexpr (WANT_DP) {
+            if (kb != 0) {                                   // (P S - T) S^T
+                float h[9];
+#pragma unroll
+                for (int i = 0; i < 3; ++i)
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) h[i * 3 + j] = fmaf(g[i * 3 + 2], s[j * 3 + 2], fmaf(g[i * 3 + 1], s[j * 3 + 1], g[i * 3] * s[j * 3]));
+#pragma unroll
+                for (int i = 0; i < 9; ++i) g[i] = h[i];
+            }
+#pragma unroll
+            for (int i = 0; i < 9; ++i) rows.o0[i] = g[i] * gs;
+        }
+        store_row_i32(index, ctx, bad_cls ? -1 : kb);
+    }
+    __device__ __forceinline__ void finish(double total, bool) const { atomicAdd(loss_sum, total); }
+    __device__ __forceinline__ void finish_total(double total, bool) const {
+        *loss_sum = total;
+        if (loss_mean != nullptr) *loss_mean = static_cast<float>(total * inv_b_f64);
+    }
+};
+
 // The REDUCED forms of the metric -- sum_b acos(clamp((tr(R1_b^T R2_b) - 1)/2)), what `angle_error(...).mean()` (3D-Pose/main.py:62) and
 // the (sum, count) pair of the multi-GPU layer need -- without float64 arithmetic on every row.  The reference casts both
 // rotations to float64 before the product (rotation_representation.py:232-233); reproducing that costs 18 v_cvt_f64_f32, 9 float64

@@ -1402,6 +1402,58 @@ __global__ __launch_bounds__(kBlock) void k_op_rows(Op op, int64_t B) {
     for (int i = 0; i < Op::kOut0N; ++i) o[i] = rows.o0[i];
 }
 
+// ---- K4s / K3s one row per thread: a batch of up to kSmallBatch rows (one workgroup) and the remainder (< 64 rows) or unaligned input
+// of the streaming kernels.  The arithmetic is the engine operation's own (compute<float, 1>).  Every thread runs the operation (idle ones
+// on identities, exists = false), so its wave-wide votes see whole waves.  A wave's rows are one 64-row unit of the pointers it was given
+// (blockDim is a multiple of 64).  `mode` (operations with a reduction): 1 = this launch is the whole batch, its one workgroup writes the
+// loss and the mean; 2 = publish into the workspace's slot blockIdx.x (the engine launch behind it sums); 3 = add to *loss_sum.
+template <class Op>
+__global__ __launch_bounds__(kSmallBatch) void k_sym_rows(Op op, int64_t B, int mode, so3::ReduceWs *ws) {
+    __shared__ double red[kSmallBatch / 64];
+    so3::RowCtx<1> ctx{};
+    ctx.lane = static_cast<int>(threadIdx.x & 63);
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+    for (int64_t row0 = static_cast<int64_t>(blockIdx.x) * blockDim.x; row0 < B; row0 += stride) {
+        const int64_t row = row0 + threadIdx.x;
+        const bool active = row < B;
+        so3::Rows<float, Op> rows;
+        const float *a = static_cast<const float *>(op.in0) + row * 9, *b = static_cast<const float *>(op.in1) + row * 9;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            rows.a[i] = active ? a[i] : ((i & 3) == 0 ? 1.f : 0.f);
+            rows.b[i] = active ? b[i] : ((i & 3) == 0 ? 1.f : 0.f);
+        }
+        if constexpr (Op::kIn2 != 0) rows.c[0] = __int_as_float(active ? static_cast<const int32_t *>(op.in2)[row] : 0);
+        ctx.unit[0] = row >> 6;
+        ctx.exists[0] = active;
+        op.template compute<float, 1>(rows, ctx);
+        if (active) {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) {
+                if constexpr (Op::kOut0 != 0) static_cast<float *>(op.out0)[row * 9 + i] = rows.o0[i];
+                if constexpr (Op::kOut1 != 0) static_cast<float *>(op.out1)[row * 9 + i] = rows.o1[i];
+            }
+        }
+    }
+    if constexpr (Op::kReduce) {
+        const double v = wave_sum(ctx.acc);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double total = 0.0;
+            for (int w = 0; w < static_cast<int>(blockDim.x >> 6); ++w) total += red[w];
+            if (mode == 1) {
+                *op.loss_sum = total;
+                if (op.loss_mean != nullptr) *op.loss_mean = static_cast<float>(total * op.inv_b_f64);
+            } else if (mode == 2) {
+                publish_partial(ws, total, false);
+            } else {
+                atomicAdd(op.loss_sum, total);
+            }
+        }
+    }
+}
+
 // ---- SE(3) update, one row per thread: remainder and unaligned input of the streaming kernels -----------------
 template <bool BWD>
 __global__ __launch_bounds__(kBlock) void k_se3_rows(const float *__restrict__ out12, const float *__restrict__ Tinit,
@@ -2982,4 +3034,115 @@ int so3_rotate_clouds_bwd_f32(const float *P, const float *R, const float *G, fl
     return check_launch("so3_rotate_clouds_bwd_f32");
 }
 
+// ---- K4s / K3s: the metric and the loss up to a symmetry group ------------------------------------------------------------------
+// Arguments both entries share.  `ENTRY` names the entry in so3_last_error().
+#define SO3_SYM_CHECK(ENTRY) do { \
+        SO3_CHECK_ARGS(B >= 0 && B <= SO3_MAX_B, ENTRY ": B"); \
+        SO3_CHECK_ARGS(K >= 1 && K <= 64, ENTRY ": K must be in [1, 64]"); \
+        SO3_CHECK_ARGS(num_classes >= 1, ENTRY ": num_classes must be >= 1"); \
+        SO3_CHECK_ARGS(static_cast<int64_t>(num_classes) * K <= 256, ENTRY ": num_classes * K must be <= 256"); \
+        SO3_CHECK_ARGS((class_id != nullptr) == (num_classes > 1), ENTRY ": class_id must be given exactly when num_classes > 1"); \
+        SO3_CHECK_ARGS(S != nullptr, ENTRY ": S is null"); \
+    } while (0)
+
 }  // extern "C"
+
+template <bool MULTI>
+static void sym_angle_launch(so3::OpSymAngle<MULTI> op, int64_t B, hipStream_t s) {
+    const int64_t nunits = stream_units(B, {op.in0, op.in1, op.in2, op.deg, op.index});
+    if (nunits > 0) launch_rows<1, 4, 1024>(op, nunits, s);
+    const int64_t done = nunits * so3::kUnitRows, rest = B - done;
+    if (rest > 0) {
+        so3::OpSymAngle<MULTI> t = op;
+        t.in0 = static_cast<const float *>(op.in0) + done * 9;
+        t.in1 = static_cast<const float *>(op.in1) + done * 9;
+        if (MULTI) t.in2 = static_cast<const int32_t *>(op.in2) + done;
+        t.deg = op.deg + done;
+        t.index = advance(op.index, done);
+        hipLaunchKernelGGL((k_sym_rows<so3::OpSymAngle<MULTI>>), dim3(persistent_grid(rest)), dim3(kBlock), 0, s, t, rest, 0, nullptr);
+    }
+}
+
+extern "C" {
+
+int so3_sym_angle_error_f32(const float *Rpred, const float *Rtrue, const float *S, const int32_t *class_id, int32_t num_classes, int32_t K,
+                            double *deg, int32_t *index, int32_t *flags_out, unsigned flags, int64_t B, void *stream) {
+    SO3_CHECK_ARGS((flags & ~static_cast<unsigned>(SO3_RADIANS)) == 0, "so3_sym_angle_error_f32: unknown flag");
+    SO3_SYM_CHECK("so3_sym_angle_error_f32");
+    if (B == 0) return 0;
+    SO3_CHECK_ARGS(Rpred != nullptr && Rtrue != nullptr && deg != nullptr, "so3_sym_angle_error_f32: null pointer");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (flags_out != nullptr) {
+        hipError_t e = hipMemsetAsync(flags_out, 0, sizeof(int32_t), s);
+        if (e != hipSuccess) return fail((int)e, "so3_sym_angle_error_f32: memset");
+    }
+#define SYM_OP(MULTI) do { so3::OpSymAngle<MULTI> op; op.in0 = Rpred; op.in1 = Rtrue; op.in2 = class_id; op.sym.table = S; op.sym.K = K; \
+                           op.sym.C = num_classes; op.deg = deg; op.index = index; op.flags_out = flags_out; \
+                           op.unit_scale = (flags & SO3_RADIANS) ? 1.0 : 57.295779513082320876798154814105; sym_angle_launch<MULTI>(op, B, s); } while (0)
+    if (num_classes > 1) SYM_OP(true); else SYM_OP(false);
+#undef SYM_OP
+    return check_launch("so3_sym_angle_error_f32");
+}
+
+}  // extern "C"
+
+template <bool MULTI, bool DP, bool DT>
+static void sym_loss_launch(so3::OpSymFrobLoss<MULTI, DP, DT> op, int64_t B, void *workspace, hipStream_t s, int *err) {
+    typedef so3::OpSymFrobLoss<MULTI, DP, DT> Op;
+    if (B <= kSmallBatch) {                              // one workgroup, one launch: the kernel writes loss_sum and the mean itself
+        hipLaunchKernelGGL((k_sym_rows<Op>), dim3(1), dim3(static_cast<unsigned>((B + 63) / 64 * 64)), 0, s, op, B, 1, nullptr);
+        return;
+    }
+    const int64_t nunits = stream_units(B, {op.in0, op.in1, op.in2, op.out0, op.out1, op.index});
+    const int64_t done = nunits * so3::kUnitRows, rest = B - done;
+    const unsigned tile_wgs = rest > 0 ? persistent_grid(rest) : 0u;
+    so3::ReduceWs *ws = use_workspace(workspace, nunits, tile_wgs) ? static_cast<so3::ReduceWs *>(workspace) : nullptr;
+    if (ws == nullptr) {
+        hipError_t e = hipMemsetAsync(op.loss_sum, 0, sizeof(double), s);
+        if (e != hipSuccess) { *err = (int)e; return; }
+    }
+    if (rest > 0) {
+        Op t = op;
+        t.in0 = static_cast<const float *>(op.in0) + done * 9;
+        t.in1 = static_cast<const float *>(op.in1) + done * 9;
+        if (MULTI) t.in2 = static_cast<const int32_t *>(op.in2) + done;
+        t.out0 = advance(static_cast<float *>(op.out0), done * 9);
+        t.out1 = advance(static_cast<float *>(op.out1), done * 9);
+        t.index = advance(op.index, done);
+        hipLaunchKernelGGL((k_sym_rows<Op>), dim3(tile_wgs), dim3(kBlock), 0, s, t, rest, ws != nullptr ? 2 : 3, ws);
+    }
+    if (nunits > 0) {
+        op.ws = ws;
+        op.ws_slot0 = tile_wgs;
+        launch_rows<1, 4, 1024>(op, nunits, s);
+    }
+    if (ws == nullptr && op.loss_mean != nullptr) k_mean_from_sum<<<1, 1, 0, s>>>(op.loss_sum, op.loss_mean, op.inv_b_f64);
+}
+
+extern "C" {
+
+int so3_sym_frob_loss_f32(const float *Rpred, const float *Rtrue, const float *S, const int32_t *class_id, int32_t num_classes, int32_t K,
+                          float *dRpred, float *dRtrue, int32_t *index, double *loss_sum, float *loss_mean, void *workspace, unsigned flags,
+                          int64_t B, void *stream) {
+    SO3_CHECK_ARGS(flags == 0, "so3_sym_frob_loss_f32: unknown flag (none is defined for it)");
+    SO3_SYM_CHECK("so3_sym_frob_loss_f32");
+    if (B == 0) return 0;
+    SO3_CHECK_ARGS(Rpred != nullptr && Rtrue != nullptr && loss_sum != nullptr, "so3_sym_frob_loss_f32: null pointer");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int err = 0;
+#define SYM_OP(MULTI, DP, DT) do { so3::OpSymFrobLoss<MULTI, DP, DT> op; op.in0 = Rpred; op.in1 = Rtrue; op.in2 = class_id; op.out0 = dRpred; \
+                                   op.out1 = dRtrue; op.sym.table = S; op.sym.K = K; op.sym.C = num_classes; op.index = index; \
+                                   op.loss_sum = loss_sum; op.loss_mean = loss_mean; op.inv_b = 1.0f / static_cast<float>(B); \
+                                   op.inv_b_f64 = 1.0 / static_cast<double>(B); sym_loss_launch(op, B, workspace, s, &err); } while (0)
+#define SYM_PICK(MULTI) do { if (dRpred && dRtrue) SYM_OP(MULTI, true, true); else if (dRpred) SYM_OP(MULTI, true, false); \
+                             else if (dRtrue) SYM_OP(MULTI, false, true); else SYM_OP(MULTI, false, false); } while (0)
+    if (num_classes > 1) SYM_PICK(true); else SYM_PICK(false);
+#undef SYM_PICK
+#undef SYM_OP
+    if (err != 0) return fail(err, "so3_sym_frob_loss_f32: memset");
+    return check_launch("so3_sym_frob_loss_f32");
+}
+#undef SO3_SYM_CHECK
+
+}  // extern "C"
+

@@ -98,6 +98,20 @@ def main():
     timeit("K3' f64 so3_frob_loss_v2_f64 (loss + dRpred, workspace: one launch)", lambda i: lib.so3_frob_loss_v2_f64(p(r64[i % 2]), p(r64[1 - i % 2]), p(g64), p(ls), p(lm64), p(ws), 0, n, st), 216 * n)
     timeit("K4' geodesic(R1, R2, 'mean') so3_geodesic_eps_f32 (workspace: one launch)", lambda i: lib.so3_geodesic_eps_f32(p(r[i % NB]), p(rt[i % NB]), None, p(ls), p(lm), 1, ctypes.c_float(1e-7), p(ws), n, st), 72 * n)
     timeit("K4' geodesic(R1, R2, 'mean') so3_geodesic_eps_f32 (no workspace: memset + kernel + mean)", lambda i: lib.so3_geodesic_eps_f32(p(r[i % NB]), p(rt[i % NB]), None, p(ls), p(lm), 1, ctypes.c_float(1e-7), None, n, st), 72 * n)
+    # K4s / K3s: the metric and the loss up to a symmetry group, single-class tables of K = 1, 4, 24 and ten classes of K = 1 .. 8 (padded to 8)
+    idx = torch.empty(n, dtype=torch.int32, device=dev)
+    cls10 = torch.randint(0, 10, (n,), device=dev, dtype=torch.int32)
+    sym_tables = [("K=%d" % k, rr.SymmetryTable(rr.cyclic_symmetry(k, "y")), None) for k in (1, 4, 24)]
+    sym_tables.append(("10 classes, K=1..8", rr.SymmetryTable([rr.cyclic_symmetry(k, "z") for k in range(1, 9)] + [rr.cyclic_symmetry(2, "x")] * 2), cls10))
+    for tag, tab, cl in sym_tables:
+        sd, cp, extra = tab._on(dev), (p(cl) if cl is not None else None), (4 * n if cl is not None else 0)
+        timeit("K4s so3_sym_angle_error_f32 (%s, deg + index + flags)" % tag,
+               lambda i: lib.so3_sym_angle_error_f32(p(r[i % NB]), p(rt[i % NB]), p(sd), cp, tab.num_classes, tab.K, p(deg), p(idx), p(fl), 0, n, st),
+               84 * n + extra)
+        timeit("K3s so3_sym_frob_loss_f32 (%s, loss + dRpred + dRtrue + mean, workspace)" % tag,
+               lambda i: lib.so3_sym_frob_loss_f32(p(r[i % NB]), p(rt[i % NB]), p(sd), cp, tab.num_classes, tab.K, p(dm[i % NB]), p(g[i % NB]), None,
+                                                   p(ls), p(lm), p(ws), 0, n, st),
+               144 * n + extra)
     del r64, g64
     # K4b: the metrics' backward (round 6): dR1 / dR2 of geodesic(..., 'mean') from a 0-dim upstream gradient, of the per-row form from a
     # per-row one, and angle_error's float64 spelling

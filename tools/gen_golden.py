@@ -349,7 +349,88 @@ def g16_cloud_gradients():
     save("g16_cloud_gradients.npz", **out)
 
 
+def g17_symmetry():
+    """Symmetry-aware angle error and Frobenius loss.  The group acts on the prediction from the right, as rotate_by_180
+    (3D-Pose/loss.py:14-24: R_guess @ Rx(pi), Ry(pi), Rz(pi); spatialmath is not installed, so the flips are written as the diagonal
+    matrices they are).  Three tables: rotate_by_180's {I, Rx, Ry, Rz}, C_4 about y, and three classes {I}, C_2(z), C_4(y) padded with
+    the identity.  Every candidate R_pred @ S_k is formed in float64 from float32 R_pred and the float32-rounded table; the reference's
+    angle_error runs on it, and loss_frobenius (3D-Pose/loss.py:7-11) on each row for the per-candidate distances.  The loss of the
+    selected branches and its autograd gradients are the reference's loss_frobenius over the batch, in float64.  Rows 0..3 of each table
+    are exact ties (integer matrices), the next four 'nearly' rotations of G3's kind (1.05 I: clamped, no raise); bad_* are rows on
+    which angle_error raises (1.5 I) beside rows on which it does not."""
+    torch.manual_seed(17)
+    eye = np.eye(3)
+    flip = np.stack([eye, np.diag([1.0, -1, -1]), np.diag([-1.0, 1, -1]), np.diag([-1.0, -1, 1])])
+    ry = lambda c, s_: np.array([[c, 0.0, s_], [0.0, 1.0, 0.0], [-s_, 0.0, c]])
+    c4y = np.stack([ry(1, 0), ry(0, 1), ry(-1, 0), ry(0, -1)])
+    c2z = np.stack([eye, np.diag([-1.0, -1, 1]), eye, eye])
+    tables = {"flip": flip[None], "c4y": c4y[None], "multi": np.stack([np.stack([eye] * 4), c2z, c4y])}
+    rz90 = np.array([[0.0, -1, 0], [1, 0, 0], [0, 0, 1]])
+    ties = {"flip": [(eye, rz90, 0), (rz90 @ flip[1], eye, 0), (flip[1], eye, 0), (rz90, rz90.T, 0)],
+            "c4y": [(flip[1], eye, 0), (rz90, rz90.T, 0), (eye, flip[3], 0), (c4y[1], c4y[3], 0)],
+            "multi": [(flip[1], eye, 1), (flip[1], eye, 2), (eye, rz90, 0), (c4y[1], c4y[3], 2)]}
+    out = {}
+    n_rand = 160
+    for tag, table in tables.items():
+        s32 = torch.from_numpy(table).float()                                   # (C, K, 3, 3): what the device holds
+        c, k = s32.shape[:2]
+        t_rand = rr.symmetric_orthogonalization(torch.randn(n_rand, 9))
+        p_rand = rr.symmetric_orthogonalization(torch.randn(n_rand, 9))
+        # a third of the random rows are near a symmetric copy of the target: the best candidate is then not the identity
+        cls_rand = torch.randint(0, c, (n_rand,), dtype=torch.int32)
+        near = torch.arange(n_rand) % 3 == 0
+        j = torch.randint(0, k, (n_rand,))
+        s_pick = s32[cls_rand.long(), j]
+        noise = rr.symmetric_orthogonalization(torch.eye(3).reshape(1, 9) + 0.05 * torch.randn(n_rand, 9))
+        p_near = torch.bmm(torch.bmm(t_rand, noise), s_pick.transpose(1, 2))
+        p_rand = torch.where(near[:, None, None], p_near, p_rand).float()
+        tie_p = torch.tensor(np.stack([a for a, _, _ in ties[tag]])).float()
+        tie_t = torch.tensor(np.stack([b for _, b, _ in ties[tag]])).float()
+        tie_c = torch.tensor([cc for _, _, cc in ties[tag]], dtype=torch.int32)
+        nearly_p = 1.05 * torch.eye(3).repeat(4, 1, 1)
+        nearly_t = rr.symmetric_orthogonalization(torch.randn(4, 9)) * 0 + torch.eye(3)
+        nearly_c = torch.arange(4, dtype=torch.int32) % c
+        p = torch.cat([tie_p, nearly_p, p_rand]).contiguous()
+        t = torch.cat([tie_t, nearly_t, t_rand.float()]).contiguous()
+        cls = torch.cat([tie_c, nearly_c, cls_rand]) if c > 1 else torch.zeros(p.shape[0], dtype=torch.int32)
+        b = p.shape[0]
+        s_row = s32[cls.long()].double()                                        # (B, K, 3, 3)
+        deg_all = np.zeros((b, k))
+        dist_all = np.zeros((b, k))
+        for kk in range(k):
+            cand = torch.bmm(p.double(), s_row[:, kk])                          # float64 product of float32 values
+            deg_all[:, kk] = rr.angle_error(cand, t).numpy()
+            for row in range(b):
+                dist_all[row, kk] = float(loss_frobenius(t[row:row + 1].double(), cand[row:row + 1]))
+        idx = np.argmin(deg_all, axis=1)
+        loss_idx = np.argmin(dist_all, axis=1)
+        pa = p.double().clone().requires_grad_(True)
+        ta = t.double().clone().requires_grad_(True)
+        s_sel = s_row[torch.arange(b), torch.from_numpy(loss_idx)]
+        loss = loss_frobenius(ta, torch.bmm(pa, s_sel))                         # call order of 3D-Pose/main.py:85 (R, out)
+        loss.backward()
+        out.update({tag + "_S": s32, tag + "_p": p, tag + "_t": t, tag + "_cls": cls, tag + "_deg_all": deg_all,
+                    tag + "_deg": deg_all.min(axis=1), tag + "_idx": idx.astype(np.int32), tag + "_dist_all": dist_all,
+                    tag + "_loss_idx": loss_idx.astype(np.int32), tag + "_loss": loss.detach(), tag + "_dp": pa.grad, tag + "_dt": ta.grad})
+    bad_p = torch.eye(3).repeat(6, 1, 1)
+    bad_p[1] = 1.5 * torch.eye(3)                   # cos 1.75: raises
+    bad_p[3] = 1.05 * torch.eye(3)                  # cos 1.075: clamped, no raise
+    bad_p[4] = -0.5 * torch.eye(3)                  # cos -1.25: raises
+    bad_t = torch.eye(3).repeat(6, 1, 1)
+    raises = []
+    for row in range(6):
+        try:
+            rr.angle_error(bad_p[row:row + 1], bad_t[row:row + 1])
+            raises.append(False)
+        except ValueError:
+            raises.append(True)
+    out.update(bad_p=bad_p, bad_t=bad_t, bad_raises=np.array(raises))
+    save("g17_symmetry.npz", **out)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "g17":
+        return g17_symmetry()
     if len(sys.argv) > 1 and sys.argv[1] == "g16":
         return g16_cloud_gradients()
     if len(sys.argv) > 1 and sys.argv[1] == "g15":
