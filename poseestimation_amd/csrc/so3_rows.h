@@ -837,6 +837,36 @@ struct OpProjectBwd : OpBase {
     }
 };
 
+// One Frobenius-loss row, the same arithmetic on every route (K3, K3', K3s on the engine; the tile and one-workgroup kernels of
+// so3proj.hip): from g = R - Rtrue, nrm = ||g|| and gs = 1/(B ||g||), 0 for g = 0; the caller's gradient is g * gs, with g as this
+// leaves it.  A row whose n2 is below 2^-100 (every |g_i| < 2^-50) is first scaled by 2^100 -- exact -- and its n2 formed again:
+// below that its squares may be subnormal (rounded, or flushed), and v_rsq_f32 flushes a subnormal argument to 0 (gs = inf).  Scaled,
+// any nonzero g has n2 >= 2^-98 and |g_i| < 2^50.  A select, not a branch; a row with n2 >= 2^-100 keeps s = 1, and the bits it had.
+template <class T>
+struct FrobRow {
+    T nrm, gs;
+};
+template <class T>
+__device__ __forceinline__ FrobRow<T> frob_row(T (&g)[9], float inv_b) {
+    typedef Tr<T> R;
+    T n2 = R::splat(0.f);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) n2 = R::fma(g[i], g[i], n2);
+    const typename R::mask tiny = R::gt(R::splat(0x1p-100f), n2);
+    const T s = R::sel(tiny, R::splat(0x1p100f), R::splat(1.f));
+    T m2 = R::splat(0.f);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        g[i] = g[i] * s;
+        m2 = R::fma(g[i], g[i], m2);
+    }
+    const T inv = R::rsq(R::max(m2, R::splat(1e-37f)));       // (the clamp holds only for g = 0: nrm = 0, not 0 * inf)
+    FrobRow<T> o;
+    o.nrm = (m2 * inv) * R::sel(tiny, R::splat(0x1p-100f), R::splat(1.f));
+    o.gs = R::sel(R::gt(m2, R::splat(0.f)), inv * R::splat(inv_b), R::splat(0.f));   // zero difference -> zero gradient
+    return o;
+}
+
 // K3: head + Frobenius loss + backward in one pass (3D-Pose/main.py:60,85,90).  out0 = dM, out1 = R (each optional).
 template <int M_BYTES, bool WANT_DM, bool WANT_R>
 struct OpFrobHead : OpBase {
@@ -873,21 +903,15 @@ struct OpFrobHead : OpBase {
         late_in1<T, OpFrobHead, NPL>(ctx, rows.b);                // Rtrue: only now
         if (__builtin_expect(base >= 0, 0)) park_words<T, NPL, kParkCap, kParkWords, false, 9>(ctx, base, h.hard, 9, t);
         T g[9];
-        T n2 = R::splat(0.f);
 #pragma unroll
-        for (int i = 0; i < 9; ++i) {
-            g[i] = r[i] - t[i];                           // d||Rtrue - R||/dR = (R - Rtrue)/||.||
-            n2 = R::fma(g[i], g[i], n2);
-        }
-        const T inv = R::rsq(R::max(n2, R::splat(1e-37f)));
-        const T nrm = n2 * inv;
+        for (int i = 0; i < 9; ++i) g[i] = r[i] - t[i];   // d||Rtrue - R||/dR = (R - Rtrue)/||.||
+        const FrobRow<T> fr = frob_row<T>(g, inv_b);
 #pragma unroll
         for (int k = 0; k < NPL; ++k)                     // (a parked row's loss is added when it is redone)
-            if (ctx.exists[k] && !(base >= 0 && R::lane_of(h.hard, k))) ctx.acc += static_cast<double>(R::get(nrm, k));
+            if (ctx.exists[k] && !(base >= 0 && R::lane_of(h.hard, k))) ctx.acc += static_cast<double>(R::get(fr.nrm, k));
         if (WANT_DM) {
-            const T gs = R::sel(R::gt(n2, R::splat(0.f)), inv * R::splat(inv_b), R::splat(0.f));   // zero difference -> zero gradient
 #pragma unroll
-            for (int i = 0; i < 9; ++i) g[i] = g[i] * gs;
+            for (int i = 0; i < 9; ++i) g[i] = g[i] * fr.gs;
             backward_given_rotation<T>(m, r, g, h, dm);
         }
     }
@@ -900,17 +924,15 @@ struct OpFrobHead : OpBase {
         const long long row = parked_row<kParkCap, kParkWords>(ctx.park, e);
         const SignedSvd<float> f = signed_svd<WANT_DM, float>(m);
         rotation_from(f, r);
-        float n2 = 0.f;
 #pragma unroll
-        for (int i = 0; i < 9; ++i) { g[i] = r[i] - t[i]; n2 = fmaf(g[i], g[i], n2); }
-        const float inv = hw::rsq(fmaxf(n2, 1e-37f));
-        if (valid) ctx.acc += static_cast<double>(n2 * inv);
+        for (int i = 0; i < 9; ++i) g[i] = r[i] - t[i];
+        const FrobRow<float> fr = frob_row<float>(g, inv_b);
+        if (valid) ctx.acc += static_cast<double>(fr.nrm);
         if (WANT_R && valid) overwrite_row<4, 9>(out1, row, r);
         if (WANT_DM) {
-            const float gs = n2 > 0.f ? inv * inv_b : 0.f;
             float dm[9];
 #pragma unroll
-            for (int i = 0; i < 9; ++i) g[i] = g[i] * gs;
+            for (int i = 0; i < 9; ++i) g[i] = g[i] * fr.gs;
             project_backward(f, g, dm);
             if (valid) overwrite_row<M_BYTES, 9>(out0, row, dm);
         }
@@ -937,17 +959,14 @@ struct OpFrobLoss : OpBase {
         const T (&p)[9] = rows.a;
         const T (&t)[9] = rows.b;
         T (&g)[9] = rows.o0;
-        T n2 = R::splat(0.f);
 #pragma unroll
-        for (int i = 0; i < 9; ++i) { g[i] = p[i] - t[i]; n2 = R::fma(g[i], g[i], n2); }
-        const T inv = R::rsq(R::max(n2, R::splat(1e-37f)));
-        const T nrm = n2 * inv;
+        for (int i = 0; i < 9; ++i) g[i] = p[i] - t[i];
+        const FrobRow<T> fr = frob_row<T>(g, inv_b);
 #pragma unroll
         for (int k = 0; k < NPL; ++k)
-            if (ctx.exists[k]) ctx.acc += static_cast<double>(R::get(nrm, k));
-        const T gs = R::sel(R::gt(n2, R::splat(0.f)), inv * R::splat(inv_b), R::splat(0.f));
+            if (ctx.exists[k]) ctx.acc += static_cast<double>(R::get(fr.nrm, k));
 #pragma unroll
-        for (int i = 0; i < 9; ++i) g[i] = g[i] * gs;
+        for (int i = 0; i < 9; ++i) g[i] = g[i] * fr.gs;
     }
     float *loss_mean = nullptr;
     double inv_b_f64 = 0.0;
@@ -1152,7 +1171,6 @@ struct OpSymFrobLoss : OpBase {
     template <class T, int NPL>
     __device__ __forceinline__ void compute(Rows<T, OpSymFrobLoss> &rows, RowCtx<NPL> &ctx) const {
         static_assert(NPL == 1, "one row per lane");
-        typedef Tr<float> R;
         const float (&p)[9] = rows.a;
         const float (&t)[9] = rows.b;
         bool bad_cls;
@@ -1184,15 +1202,14 @@ struct OpSymFrobLoss : OpBase {
                     for (int j = 0; j < 3; ++j) q[i * 3 + j] = fmaf(p[i * 3 + 2], s[6 + j], fmaf(p[i * 3 + 1], s[3 + j], p[i * 3] * s[j]));
             }
         }
-        float g[9];                                          // P S - T
-        float n2 = 0.f;
+        float g[9];                                          // P S - T (times 2^100 for a tiny row: frob_row)
 #pragma unroll
-        for (int i = 0; i < 9; ++i) { g[i] = q[i] - t[i]; n2 = R::fma(g[i], g[i], n2); }
-        const float inv = R::rsq(R::max(n2, 1e-37f));
+        for (int i = 0; i < 9; ++i) g[i] = q[i] - t[i];
+        const FrobRow<float> fr = frob_row<float>(g, inv_b);
         const float nan = __int_as_float(0x7fc00000);
-        const float nrm = bad_cls ? nan : n2 * inv;
+        const float nrm = bad_cls ? nan : fr.nrm;
         if (ctx.exists[0]) ctx.acc += static_cast<double>(nrm);
-        const float gs = bad_cls ? nan : (n2 > 0.f ? inv * inv_b : 0.f);
+        const float gs = bad_cls ? nan : fr.gs;
         if constexpr (WANT_DT) {
 #pragma unroll
             for (int i = 0; i < 9; ++i) rows.o1[i] = -(g[i] * gs);

@@ -195,18 +195,13 @@ __global__ __launch_bounds__(kBlock) void k_frob_fwd_bwd(const void *__restrict_
         lane_get(tile_t, active, t);
         so3::HardRows<float> hard;
         so3::project_rotation_frames<WANT_DM, float>(m, r, hard);
-        float n2 = 0.f;
 #pragma unroll
-        for (int i = 0; i < 9; ++i) {
-            g[i] = r[i] - t[i];                       // d||Rtrue - R||/dR = (R - Rtrue)/||.||
-            n2 = fmaf(g[i], g[i], n2);
-        }
-        const float nrm = n2 * __builtin_amdgcn_rsqf(fmaxf(n2, 1e-37f));
-        const float gs = (n2 > 0.f) ? inv_b * __builtin_amdgcn_rsqf(n2) : 0.f;    // zero difference -> zero gradient
-        if (active) acc += static_cast<double>(nrm);
+        for (int i = 0; i < 9; ++i) g[i] = r[i] - t[i];   // d||Rtrue - R||/dR = (R - Rtrue)/||.||
+        const so3::FrobRow<float> fr = so3::frob_row<float>(g, inv_b);      // the engine's arithmetic (so3_rows.h)
+        if (active) acc += static_cast<double>(fr.nrm);
         if (WANT_DM) {
 #pragma unroll
-            for (int i = 0; i < 9; ++i) g[i] *= gs;
+            for (int i = 0; i < 9; ++i) g[i] *= fr.gs;
             so3::backward_given_rotation<float>(m, r, g, hard, dm);
             lane_put(tile_m, dm);
         }
@@ -232,7 +227,8 @@ constexpr int kSmallBatch = 1024;
 template <bool BF16, bool WANT_R, bool WANT_DM>
 __global__ __launch_bounds__(kSmallBatch) void k_frob_small(const void *__restrict__ M, const float *__restrict__ Rtrue,
                                                             float *__restrict__ R, void *__restrict__ dM,
-                                                            double *__restrict__ loss_sum, float *__restrict__ loss_mean, int B, float inv_b) {
+                                                            double *__restrict__ loss_sum, float *__restrict__ loss_mean, int B, float inv_b,
+                                                            bool add) {
     __shared__ double red[kSmallBatch / 64];
     const int b = threadIdx.x;
     const bool active = b < B;
@@ -251,17 +247,13 @@ __global__ __launch_bounds__(kSmallBatch) void k_frob_small(const void *__restri
     }
     so3::HardRows<float> hard;
     so3::project_rotation_frames<WANT_DM, float>(m, r, hard);
-    float n2 = 0.f;
 #pragma unroll
-    for (int i = 0; i < 9; ++i) {
-        g[i] = r[i] - t[i];
-        n2 = fmaf(g[i], g[i], n2);
-    }
-    const float nrm = n2 * __builtin_amdgcn_rsqf(fmaxf(n2, 1e-37f));
-    const float gs = (n2 > 0.f) ? inv_b * __builtin_amdgcn_rsqf(n2) : 0.f;        // zero difference -> zero gradient
+    for (int i = 0; i < 9; ++i) g[i] = r[i] - t[i];
+    const so3::FrobRow<float> fr = so3::frob_row<float>(g, inv_b);
+    const float nrm = fr.nrm;
     if (WANT_DM) {
 #pragma unroll
-        for (int i = 0; i < 9; ++i) g[i] *= gs;
+        for (int i = 0; i < 9; ++i) g[i] *= fr.gs;
         so3::backward_given_rotation<float>(m, r, g, hard, dm);
     }
     if (active) {
@@ -280,7 +272,7 @@ __global__ __launch_bounds__(kSmallBatch) void k_frob_small(const void *__restri
     if (threadIdx.x == 0) {
         double total = 0.0;
         for (int w = 0; w < static_cast<int>(blockDim.x >> 6); ++w) total += red[w];
-        if (loss_sum != nullptr) *loss_sum = total;
+        if (loss_sum != nullptr) *loss_sum = add ? *loss_sum + total : total;        // SO3_PREZEROED: added to, as the atomics do
         if (loss_mean != nullptr) *loss_mean = static_cast<float>(total * (1.0 / static_cast<double>(B)));   // float64 sum / B, rounded once
     }
 }
@@ -308,16 +300,14 @@ __global__ __launch_bounds__(kBlock) void k_frob_loss(const float *__restrict__ 
         const bool active = static_cast<int>(threadIdx.x) < n;
         lane_get(tile_p, active, p);
         lane_get(tile_t, active, t);
-        float n2 = 0.f;
 #pragma unroll
-        for (int i = 0; i < 9; ++i) { g[i] = p[i] - t[i]; n2 = fmaf(g[i], g[i], n2); }
-        const float nrm = n2 * __builtin_amdgcn_rsqf(fmaxf(n2, 1e-37f));
-        if (active) acc += static_cast<double>(nrm);
+        for (int i = 0; i < 9; ++i) g[i] = p[i] - t[i];
+        const so3::FrobRow<float> fr = so3::frob_row<float>(g, inv_b);
+        if (active) acc += static_cast<double>(fr.nrm);
         __syncthreads();
         if (WANT_GRAD) {
-            const float gs = (n2 > 0.f) ? inv_b * __builtin_amdgcn_rsqf(n2) : 0.f;     // zero difference -> zero gradient
 #pragma unroll
-            for (int i = 0; i < 9; ++i) g[i] *= gs;
+            for (int i = 0; i < 9; ++i) g[i] *= fr.gs;
             lane_put(tile_p, g);
             __syncthreads();
             tile_out<false, VEC>(dRpred, first, n, tile_p);
@@ -336,22 +326,18 @@ __global__ __launch_bounds__(kBlock) void k_frob_loss(const float *__restrict__ 
 template <bool WANT_GRAD>
 __global__ __launch_bounds__(kSmallBatch) void k_frob_loss_small(const float *__restrict__ Rpred, const float *__restrict__ Rtrue,
                                                                  float *__restrict__ dRpred, double *__restrict__ loss_sum,
-                                                                 float *__restrict__ loss_mean, int B, float inv_b) {
+                                                                 float *__restrict__ loss_mean, int B, float inv_b, bool add) {
     __shared__ double red[kSmallBatch / 64];
     const int b = threadIdx.x;
     const bool active = b < B;
     float g[9];
-    float n2 = 0.f;
 #pragma unroll
-    for (int i = 0; i < 9; ++i) {
-        g[i] = active ? Rpred[b * 9 + i] - Rtrue[b * 9 + i] : 0.f;
-        n2 = fmaf(g[i], g[i], n2);
-    }
-    const float nrm = n2 * __builtin_amdgcn_rsqf(fmaxf(n2, 1e-37f));
+    for (int i = 0; i < 9; ++i) g[i] = active ? Rpred[b * 9 + i] - Rtrue[b * 9 + i] : 0.f;
+    const so3::FrobRow<float> fr = so3::frob_row<float>(g, inv_b);
+    const float nrm = fr.nrm;
     if (WANT_GRAD && active) {
-        const float gs = (n2 > 0.f) ? inv_b * __builtin_amdgcn_rsqf(n2) : 0.f;     // zero difference -> zero gradient
 #pragma unroll
-        for (int i = 0; i < 9; ++i) dRpred[b * 9 + i] = g[i] * gs;
+        for (int i = 0; i < 9; ++i) dRpred[b * 9 + i] = g[i] * fr.gs;
     }
     const double v = wave_sum(active ? static_cast<double>(nrm) : 0.0);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
@@ -359,7 +345,7 @@ __global__ __launch_bounds__(kSmallBatch) void k_frob_loss_small(const float *__
     if (threadIdx.x == 0) {
         double total = 0.0;
         for (int w = 0; w < static_cast<int>(blockDim.x >> 6); ++w) total += red[w];
-        *loss_sum = total;
+        *loss_sum = add ? *loss_sum + total : total;
         if (loss_mean != nullptr) *loss_mean = static_cast<float>(total * (1.0 / static_cast<double>(B)));
     }
 }
@@ -442,13 +428,14 @@ __global__ __launch_bounds__(kBlock) void k_angle_error(const float *__restrict_
 
 // Batches of up to kSmallBatch rows (the per-batch metric of a training loop, 3D-Pose/main.py:60-62: B = 512) are
 // launch-latency-bound, and the accumulators' initialisation was a launch of its own.  One workgroup, one row per thread:
-// the kernel writes (sum, count) and the range flag with plain stores -- one launch, no atomics.  PROJECT: the first
+// the kernel writes (sum, count) and the range flag with plain stores (with SO3_PREZEROED it adds to the sum and ORs the flag, as the
+// atomics do) -- one launch, no atomics.  PROJECT: the first
 // operand is the head's input M and the angle is taken of its projection (the fused evaluation step).
 template <bool PROJECT, bool WANT_R, bool WANT_DEG>
 __global__ __launch_bounds__(kSmallBatch) void k_angle_small(const float *__restrict__ A, const float *__restrict__ Bm,
                                                              float *__restrict__ R, double *__restrict__ deg,
                                                              double *__restrict__ sum_count, int32_t *__restrict__ range_flag,
-                                                             double unit, int B) {
+                                                             double unit, int B, bool add) {
     __shared__ double red[kSmallBatch / 64];
     __shared__ int red_bad[kSmallBatch / 64];
     const int b = threadIdx.x;
@@ -493,8 +480,8 @@ __global__ __launch_bounds__(kSmallBatch) void k_angle_small(const float *__rest
         double total = 0.0;
         int flag = 0;
         for (int w = 0; w < static_cast<int>(blockDim.x >> 6); ++w) { total += red[w]; flag |= red_bad[w]; }
-        if (sum_count) { sum_count[0] = total; sum_count[1] = static_cast<double>(B); }
-        if (range_flag) *range_flag = flag;
+        if (sum_count) { sum_count[0] = add ? sum_count[0] + total : total; sum_count[1] = static_cast<double>(B); }   // add: SO3_PREZEROED
+        if (range_flag) *range_flag = add ? (*range_flag | flag) : flag;
     }
 }
 
@@ -2308,7 +2295,7 @@ int frob(const void *M, const float *Rtrue, float *R, void *dM, double *loss_sum
         SO3_CHECK_ARGS(M != nullptr && Rtrue != nullptr, "so3_frob_fwd_bwd: null pointer");
         const dim3 grid(1), block(static_cast<unsigned>((B + 63) / 64 * 64));
         const float inv = 1.0f / static_cast<float>(B);
-#define SMALL(WR, WD) hipLaunchKernelGGL((k_frob_small<BF16, WR, WD>), grid, block, 0, s, M, Rtrue, R, dM, loss_sum, loss_mean, static_cast<int>(B), inv)
+#define SMALL(WR, WD) hipLaunchKernelGGL((k_frob_small<BF16, WR, WD>), grid, block, 0, s, M, Rtrue, R, dM, loss_sum, loss_mean, static_cast<int>(B), inv, prezeroed)
         if (R && dM) SMALL(true, true); else if (R) SMALL(true, false); else if (dM) SMALL(false, true); else SMALL(false, false);
 #undef SMALL
         return check_launch("so3_frob_fwd_bwd");
@@ -2443,8 +2430,8 @@ int so3_frob_loss_v2_f32(const float *Rpred, const float *Rtrue, float *dRpred, 
         SO3_CHECK_ARGS(Rpred != nullptr && Rtrue != nullptr, "so3_frob_loss_f32: null pointer");
         const dim3 grid(1), block(static_cast<unsigned>((B + 63) / 64 * 64));
         const float inv = 1.0f / static_cast<float>(B);
-        if (dRpred) hipLaunchKernelGGL((k_frob_loss_small<true>), grid, block, 0, s, Rpred, Rtrue, dRpred, loss_sum, loss_mean, static_cast<int>(B), inv);
-        else hipLaunchKernelGGL((k_frob_loss_small<false>), grid, block, 0, s, Rpred, Rtrue, dRpred, loss_sum, loss_mean, static_cast<int>(B), inv);
+        if (dRpred) hipLaunchKernelGGL((k_frob_loss_small<true>), grid, block, 0, s, Rpred, Rtrue, dRpred, loss_sum, loss_mean, static_cast<int>(B), inv, prezeroed);
+        else hipLaunchKernelGGL((k_frob_loss_small<false>), grid, block, 0, s, Rpred, Rtrue, dRpred, loss_sum, loss_mean, static_cast<int>(B), inv, prezeroed);
         return check_launch("so3_frob_loss_f32");
     }
     const int64_t nunits = B > 0 ? stream_units(B, {Rpred, Rtrue, dRpred}) : 0;
@@ -2493,8 +2480,8 @@ int so3_angle_error_v2(const float *R1, const float *R2, double *deg, double *su
     if (B > 0 && B <= kSmallBatch && (sum_count || range_flag)) {       // one workgroup: the accumulators need no launch of their own
         SO3_CHECK_ARGS(R1 != nullptr && R2 != nullptr, "so3_angle_error: null pointer");
         const dim3 grid(1), block(static_cast<unsigned>((B + 63) / 64 * 64));
-        if (deg) hipLaunchKernelGGL((k_angle_small<false, false, true>), grid, block, 0, s, R1, R2, nullptr, deg, sum_count, range_flag, unit, static_cast<int>(B));
-        else hipLaunchKernelGGL((k_angle_small<false, false, false>), grid, block, 0, s, R1, R2, nullptr, deg, sum_count, range_flag, unit, static_cast<int>(B));
+        if (deg) hipLaunchKernelGGL((k_angle_small<false, false, true>), grid, block, 0, s, R1, R2, nullptr, deg, sum_count, range_flag, unit, static_cast<int>(B), prezeroed);
+        else hipLaunchKernelGGL((k_angle_small<false, false, false>), grid, block, 0, s, R1, R2, nullptr, deg, sum_count, range_flag, unit, static_cast<int>(B), prezeroed);
         return check_launch("so3_angle_error");
     }
     const int64_t nunits = B > 0 ? stream_units(B, {R1, R2, deg}) : 0;
@@ -2538,7 +2525,7 @@ int so3_project_angle_error_v2_f32(const float *M, const float *Rtrue, float *R,
     if (B > 0 && B <= kSmallBatch && (sum_count || range_flag)) {       // one workgroup, one launch
         SO3_CHECK_ARGS(M != nullptr && Rtrue != nullptr, "so3_project_angle_error_f32: null pointer");
         const dim3 grid(1), block(static_cast<unsigned>((B + 63) / 64 * 64));
-#define SMALL(WR, WD) hipLaunchKernelGGL((k_angle_small<true, WR, WD>), grid, block, 0, s, M, Rtrue, R, deg, sum_count, range_flag, unit, static_cast<int>(B))
+#define SMALL(WR, WD) hipLaunchKernelGGL((k_angle_small<true, WR, WD>), grid, block, 0, s, M, Rtrue, R, deg, sum_count, range_flag, unit, static_cast<int>(B), prezeroed)
         if (R && deg) SMALL(true, true); else if (R) SMALL(true, false); else if (deg) SMALL(false, true); else SMALL(false, false);
 #undef SMALL
         return check_launch("so3_project_angle_error_f32");
