@@ -312,6 +312,39 @@ int so3_ortho5d_bwd_f32(const float *X, const float *G, float *dX, int64_t B, vo
 int so3_expmap_fwd_f32(const float *X, float *R, int64_t B, void *stream);
 int so3_expmap_bwd_f32(const float *X, const float *G, float *dX, int64_t B, void *stream);
 
+/* ---- inverse maps (added in 210): rotation matrix -> quaternion, rotation vector, Euler angles; log(R1^T R2) ----
+ * The inverses of the quat, expmap and euler heads above.  R in B*9 float32, documented as rotation matrices: nothing is
+ * validated on the device, a NaN row gives a NaN row, no input hangs or faults.
+ *   mat_to_quat    Q out B*4 (w,x,y,z), the order so3_quat_fwd_f32 reads; unit norm, w >= 0.  Shepperd's method on the
+ *                  largest of (tr, r0, r4, r8), branch-free.
+ *   logmap         V out B*3, the rotation vector, |v| <= float32(pi) (norm of the float32 result, checked in float64): through the quaternion, theta = 2 atan2(n, w),
+ *                  v = (theta / n)(x,y,z) -- no acos of the trace and no (R - R^T) / (2 sin theta), so the axis survives
+ *                  next to pi.  Inverse of so3_expmap_fwd_f32 (whose clamp theta^2 >= 1e-4 moves R by less than 1e-7).
+ *   mat_to_euler   E out B*3 = (e0, e1, e2) in the euler head's convention (e2 the middle angle):
+ *                  (s3, c3) = (r2, r0) / |(r2, r0)| = sincos(e1), e0 = atan2(s3 r3 - c3 r5, c3 r8 - s3 r6),
+ *                  e2 = atan2(clamp(-r1, -1, 1), |(r2, r0)|), clamped to the float32 just below pi/2: asin(-r1) for a
+ *                  rotation, taken through the two entries that still hold cos(e2) next to gimbal lock (a float32 r1
+ *                  rounds to 1 below cos(e2) = 3.5e-4, and asin(-r1) alone then misses R by up to that much).
+ *                  At exact gimbal lock e1 = 0.  |e2| <= pi/2.
+ *   relative_log   V out B*3 = log(R1^T R2) in one launch; |v| is the geodesic angle between R1 and R2.
+ * GRADIENT CONVENTION.  Every backward returns the TANGENT-SPACE gradient at R: for an inverse map f and the incoming
+ * gradient g (G in, shaped like the forward's output) let w = (d f(R exp(hat delta)) / d delta)^T g; then
+ *     dR = 1/2 R hat(w)        (dR out B*9 float32),
+ * whose inner product with a tangent direction R hat(delta) is w . delta.  It does not depend on the branch the forward
+ * took, is bounded for the log map up to theta = pi, and equals the tangent projection R skew(R^T G) of any off-manifold
+ * autograd gradient G.  Every head of this library moves R along tangent directions, so chaining through a head is
+ * exact.  The Euler gradient carries 1 / cos(e2); cos(e2) is clamped from below at 1e-6 (finite at gimbal lock).
+ * so3_relative_log_bwd_f32 writes dR1 and dR2 in one launch; either may be NULL (not both).
+ */
+int so3_mat_to_quat_fwd_f32(const float *R, float *Q, int64_t B, void *stream);
+int so3_mat_to_quat_bwd_f32(const float *R, const float *G, float *dR, int64_t B, void *stream);
+int so3_logmap_fwd_f32(const float *R, float *V, int64_t B, void *stream);
+int so3_logmap_bwd_f32(const float *R, const float *G, float *dR, int64_t B, void *stream);
+int so3_mat_to_euler_fwd_f32(const float *R, float *E, int64_t B, void *stream);
+int so3_mat_to_euler_bwd_f32(const float *R, const float *G, float *dR, int64_t B, void *stream);
+int so3_relative_log_fwd_f32(const float *R1, const float *R2, float *V, int64_t B, void *stream);
+int so3_relative_log_bwd_f32(const float *R1, const float *R2, const float *G, float *dR1, float *dR2, int64_t B, void *stream);
+
 /* ---- row a7: the cloud side of the point-cloud path -------------------------------------
  * so3_rotate_clouds_f32 replaces the pairing rule of the training loop, point_cloud/main.py:173-181
  *   (expand gt_rmat to every point, bmm, view) and, with transposed != 0, the `.transpose(1, 2)` at :183 as well:

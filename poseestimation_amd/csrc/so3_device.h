@@ -133,6 +133,8 @@ template <> struct Tr<float> {
     static __device__ __forceinline__ float sin(float x) { return sinf(x); }                     // full-range libm forms
     static __device__ __forceinline__ float cos(float x) { return cosf(x); }
     static __device__ __forceinline__ void sincos(float x, float &s, float &c) { sincosf(x, &s, &c); }   // one range reduction
+    static __device__ __forceinline__ float atan_unit(float s);                                  // atan(z) / z, s = z^2 in [0, 1] (below)
+    static __device__ __forceinline__ float atan2(float y, float x);
     // exponent that brings x into [0.5, 1), clamped so that 2^e stays finite (denormal input)
     static __device__ __forceinline__ int neg_frexp_exp(float x) { using namespace hw; return min(-hw::frexp_exp(x), 126); }
     static __device__ __forceinline__ float ldexp(float x, int e) { return ldexpf(x, e); }
@@ -173,6 +175,8 @@ template <> struct Tr<f32x2> {
         s = f32x2{s0, s1};
         c = f32x2{c0, c1};
     }
+    static __device__ __forceinline__ f32x2 atan_unit(f32x2 s);
+    static __device__ __forceinline__ f32x2 atan2(f32x2 y, f32x2 x);
     static __device__ __forceinline__ i32x2 neg_frexp_exp(f32x2 x) {
         using namespace hw;
         return i32x2{min(-hw::frexp_exp(x.x), 126), min(-hw::frexp_exp(x.y), 126)};
@@ -231,6 +235,40 @@ template <> struct Tr<double> {           // one matrix per lane in float64 (so3
     static __device__ __forceinline__ bool lane_of(bool m, int) { return m; }
     static __device__ __forceinline__ bool mnot(bool m) { return !m; }
 };
+
+// ---- atan / atan2 in float32 arithmetic, branch-free (the inverse maps of so3_rows.h) ---------------------------------------
+// atan(z) = z p(z^2) on [0, 1], p the degree-8 minimax polynomial of tools/fit_atan_f32.py (relative error 1.5e-8 before rounding);
+// its constant term rounds to 1, so atan(z) / z -> 1 exactly as z -> 0 (the log map's theta / n needs that).
+constexpr float kPiF = 3.14159274f, kHalfPiF = 1.57079637f;
+template <class T> __device__ __forceinline__ T atan_unit_poly(T s) {
+    typedef Tr<T> R;
+    T p = R::splat(2.849886327e-03f);
+    p = R::fma(p, s, R::splat(-1.606861582e-02f));
+    p = R::fma(p, s, R::splat(4.269149797e-02f));
+    p = R::fma(p, s, R::splat(-7.504292743e-02f));
+    p = R::fma(p, s, R::splat(1.064093319e-01f));
+    p = R::fma(p, s, R::splat(-1.420364425e-01f));
+    p = R::fma(p, s, R::splat(1.999261937e-01f));
+    p = R::fma(p, s, R::splat(-3.333307334e-01f));
+    return R::fma(p, s, R::splat(1.f));
+}
+// The usual folding: t = min(|y|, |x|) / max(|y|, |x|) in [0, 1]; pi/2 - a where |y| > |x|; pi - a where x < 0; the sign of y.
+// atan2(0, 0) = 0 (either sign of x's zero); a NaN argument gives NaN; the result lies in [-float32(pi), float32(pi)].
+template <class T> __device__ __forceinline__ T atan2_folded(T y, T x) {
+    typedef Tr<T> R;
+    const T ax = R::abs(x), ay = R::abs(y);
+    const typename R::mask swap = R::gt(ay, ax);
+    const T hi = R::sel(swap, ay, ax), lo = R::sel(swap, ax, ay);
+    const T t = R::sel(R::le(hi, R::splat(0.f)), R::splat(0.f), lo * R::rcp(hi));
+    T a = t * atan_unit_poly<T>(t * t);
+    a = R::sel(swap, R::splat(kHalfPiF) - a, a);
+    a = R::sel(R::gt(R::splat(0.f), x), R::splat(kPiF) - a, a);
+    return R::copysign(a, y);
+}
+__device__ __forceinline__ float Tr<float>::atan_unit(float s) { return atan_unit_poly<float>(s); }
+__device__ __forceinline__ float Tr<float>::atan2(float y, float x) { return atan2_folded<float>(y, x); }
+__device__ __forceinline__ f32x2 Tr<f32x2>::atan_unit(f32x2 s) { return atan_unit_poly<f32x2>(s); }
+__device__ __forceinline__ f32x2 Tr<f32x2>::atan2(f32x2 y, f32x2 x) { return atan2_folded<f32x2>(y, x); }
 
 // ---- 3-vectors over T -----------------------------------------------------------------------------
 template <class T> struct V3 {

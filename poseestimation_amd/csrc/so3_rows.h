@@ -1810,4 +1810,225 @@ struct OpSe3UpdateBwd : OpBase {
     }
 };
 
+// ---- the inverse maps: rotation matrix -> quaternion / rotation vector / Euler angles, and log(R1^T R2) -------------------------
+// (so3_mat_to_quat_*, so3_logmap_*, so3_mat_to_euler_*, so3_relative_log_*: the inverses of OpQuat, OpExpMap and OpEuler above.)
+// Inputs are rotation matrices; nothing is validated, a NaN row gives a NaN row, and there is no loop and no divergent branch.
+//
+// GRADIENT CONVENTION (include/so3proj.h): every backward returns the TANGENT-SPACE gradient at R.  For an inverse map f and an
+// incoming g let  w = (d f(R exp(hat delta)) / d delta)^T g;  the kernel returns  dR = 1/2 R hat(w),  whose inner product with a
+// tangent direction R hat(delta) is w . delta.  It does not depend on the branch the forward took, it is bounded for the log map up to
+// theta = pi, and it equals the projection R skew(R^T G) of any off-manifold autograd gradient G.  Every head of this library moves R
+// along tangent directions, so chaining through a head is exact.
+constexpr float kEulerMaxMiddle = 1.57079625f;   // the float32 below pi/2 (float32(pi/2) lies above it): |e2| <= pi/2 in any arithmetic
+constexpr float kEulerMinCos = 1e-6f;            // floor of cos(e2) in the Euler gradient's 1 / c2: finite at gimbal lock
+
+// dR = 1/2 R hat(w): row i of R crossed with w
+template <class T> __device__ __forceinline__ void tangent_gradient(const T (&r)[9], V3<T> w, T (&d)[9]) {
+    const V3<T> h = scale<T>(w, Tr<T>::splat(0.5f));
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const V3<T> c = cross<T>(mk<T>(r[3 * i], r[3 * i + 1], r[3 * i + 2]), h);
+        d[3 * i] = c.x; d[3 * i + 1] = c.y; d[3 * i + 2] = c.z;
+    }
+}
+
+// Shepperd's method.  The largest of (tr, r0, r4, r8) names the component formed as 1/2 sqrt(1 + ...) = d; the other three are
+// off-diagonal sums and differences over 4 d.  All four candidates times their 4 d are (radicand, three sums / differences): the
+// candidate is picked with R::sel and the ONE normalisation that follows is the square root and the division (for a rotation the
+// picked 4-vector has norm 2 sqrt(radicand) >= 2).  Then w >= 0.
+template <class T> __device__ __forceinline__ void mat_to_quat(const T (&r)[9], T (&q)[4]) {
+    typedef Tr<T> R;
+    typedef typename R::mask mask;
+    const T one = R::splat(1.f);
+    const T tr = r[0] + r[4] + r[8];
+    const T a0 = r[7] - r[5], a1 = r[2] - r[6], a2 = r[3] - r[1];
+    const T s01 = r[1] + r[3], s02 = r[2] + r[6], s12 = r[5] + r[7];
+    const T m48 = R::max(r[4], r[8]);
+    const mask ct = R::ge(tr, R::max(r[0], m48)), c0 = R::ge(r[0], m48), c4 = R::ge(r[4], r[8]);
+    const T d1 = one + r[0] - r[4] - r[8], d2 = one - r[0] + r[4] - r[8], d3 = one - r[0] - r[4] + r[8];
+    const T w = R::sel(ct, one + tr, R::sel(c0, a0, R::sel(c4, a1, a2)));
+    const T x = R::sel(ct, a0, R::sel(c0, d1, R::sel(c4, s01, s02)));
+    const T y = R::sel(ct, a1, R::sel(c0, s01, R::sel(c4, d2, s12)));
+    const T z = R::sel(ct, a2, R::sel(c0, s02, R::sel(c4, s12, d3)));
+    const T inv = R::rsq(R::fma(z, z, R::fma(y, y, R::fma(x, x, w * w))));
+    const T k = R::sel(R::gt(R::splat(0.f), w), -inv, inv);
+    q[0] = w * k; q[1] = x * k; q[2] = y * k; q[3] = z * k;
+}
+
+// |v| <= float32(pi), exactly: the roundings of (theta / n) u can carry a row at theta = pi a few 1e-7 past it.  The norm is taken in
+// float64 (exact to 1e-16 for float32 components); a row beyond float32(pi) is scaled back by pi32 / |v| in float64 and each component
+// rounded TOWARD ZERO, so the result's norm cannot exceed the bound.  Rows inside are untouched (no systematic clamp of theta).
+__device__ __forceinline__ float round_toward_zero(double x) {
+    float f = static_cast<float>(x);
+    if (__builtin_fabs(static_cast<double>(f)) > __builtin_fabs(x)) f = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, f) - 1u);
+    return f;
+}
+template <class T> __device__ __forceinline__ void bound_rotation_vector(V3<T> &v) {
+    typedef Tr<T> R;
+#pragma unroll
+    for (int k = 0; k < R::kLanes; ++k) {
+        const double x = R::get(v.x, k), y = R::get(v.y, k), z = R::get(v.z, k);
+        const double m2 = __builtin_fma(z, z, __builtin_fma(y, y, x * x));
+        constexpr double kPi32 = 3.1415927410125732;          // float32(pi) as a double
+        if (m2 > kPi32 * kPi32) {
+            const double s = kPi32 / __builtin_sqrt(m2);
+            R::set(v.x, k, round_toward_zero(x * s));
+            R::set(v.y, k, round_toward_zero(y * s));
+            R::set(v.z, k, round_toward_zero(z * s));
+        }
+    }
+}
+
+// Unit quaternion with w >= 0 -> rotation vector v = (theta / n) u,  u = (x, y, z), n = |u|, theta = 2 atan2(n, w), without acos of the
+// trace and without (R - R^T) / (2 sin theta).  With t = min(n, w) / max(n, w) and atan t = t p(t^2):
+//     n <= w (theta <= pi/2):  theta / n = 2 p(t^2) / w       -- the series in n / w, exact at n = 0;
+//     n >  w:                  theta = pi - 2 t p(t^2),  theta / n = theta / n  (n > 0.7).
+// Returns theta / n; theta itself is (theta / n) n.
+template <class T> __device__ __forceinline__ T quat_log(const T (&q)[4], V3<T> &v, T &n) {
+    typedef Tr<T> R;
+    const V3<T> u = mk<T>(q[1], q[2], q[3]);
+    n = R::sqrt(dot(u, u));
+    const typename R::mask far = R::gt(n, q[0]);
+    const T id = R::rcp(R::sel(far, n, q[0]));
+    const T t = R::sel(far, q[0], n) * id;
+    const T p = R::atan_unit(t * t);
+    const T two_p = p + p;
+    const T k = R::sel(far, R::fma(-two_p, t, R::splat(kPiF)), two_p) * id;
+    v = scale<T>(u, k);
+    bound_rotation_vector<T>(v);
+    return k;
+}
+// w = J_r^-T(v) g = g - 1/2 v x g + c v x (v x g),   c = 1/theta^2 - (1 + cos theta) / (2 theta sin theta) = (1 - (theta/2) cot(theta/2)) / theta^2
+// with cot(theta/2) = w / n of the quaternion (no division by sin theta: bounded up to pi); theta^2 <= 1: 1/12 + theta^2/720 + ...
+// `vxg` and `vxvxg` return the two cross products (so3_relative_log_bwd needs them for the other argument too).
+template <class T> __device__ __forceinline__ T log_jacobian_c(T qw, T n, T theta) {
+    typedef Tr<T> R;
+    const T t2 = theta * theta;
+    const T series = R::fma(t2, R::fma(t2, R::fma(t2, R::fma(t2, R::splat(1.f / 47900160.f), R::splat(1.f / 1209600.f)),
+                            R::splat(1.f / 30240.f)), R::splat(1.f / 720.f)), R::splat(1.f / 12.f));
+    const T closed = R::fma(R::splat(-0.5f) * theta, qw * R::rcp(n), R::splat(1.f)) * R::rcp(t2);
+    return R::sel(R::le(t2, R::splat(1.f)), series, closed);
+}
+
+// R (B,9) -> q = (w, x, y, z) (B,4);  backward: in1 = g (B,4), out0 = dR (B,9).   dq/ddelta = 1/2 [-u^T ; w I + hat(u)].
+template <bool BWD> struct OpMatToQuat : OpBase {
+    static constexpr int kIn0 = 4, kIn1 = BWD ? 4 : 0, kOut0 = 4, kOut1 = 0;
+    static constexpr int kIn1N = 4, kOut0N = BWD ? 9 : 4;
+    template <class T, int NPL>
+    __device__ __forceinline__ void compute(Rows<T, OpMatToQuat> &rows, RowCtx<NPL> &) const {
+        typedef Tr<T> R;
+        T q[4];
+        mat_to_quat<T>(rows.a, q);
+        if constexpr (!BWD) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) rows.o0[i] = q[i];
+        } else {
+            const T (&g)[4] = rows.b;
+            const V3<T> u = mk<T>(q[1], q[2], q[3]), gv = mk<T>(g[1], g[2], g[3]);
+            // w = 1/2 (-g_w u + w g_v - u x g_v)
+            const V3<T> w = scale<T>(axpy<T>(-g[0], u, axpy<T>(q[0], gv, cross<T>(gv, u))), R::splat(0.5f));
+            tangent_gradient<T>(rows.a, w, rows.o0);
+        }
+    }
+};
+
+// R (B,9) -> v (B,3), |v| <= float32(pi);  backward: in1 = g (B,3), out0 = dR (B,9).   dv/ddelta = J_r^-1(v).
+template <bool BWD> struct OpLogMap : OpBase {
+    static constexpr int kIn0 = 4, kIn1 = BWD ? 4 : 0, kOut0 = 4, kOut1 = 0;
+    static constexpr int kIn1N = 3, kOut0N = BWD ? 9 : 3;
+    template <class T, int NPL>
+    __device__ __forceinline__ void compute(Rows<T, OpLogMap> &rows, RowCtx<NPL> &) const {
+        typedef Tr<T> R;
+        T q[4], n;
+        V3<T> v;
+        mat_to_quat<T>(rows.a, q);
+        const T k = quat_log<T>(q, v, n);
+        if constexpr (!BWD) {
+            rows.o0[0] = v.x; rows.o0[1] = v.y; rows.o0[2] = v.z;
+        } else {
+            const V3<T> g = mk<T>(rows.b[0], rows.b[1], rows.b[2]);
+            const T c = log_jacobian_c<T>(q[0], n, k * n);
+            const V3<T> vg = cross<T>(v, g);
+            const V3<T> w = axpy<T>(c, cross<T>(v, vg), axpy<T>(R::splat(-0.5f), vg, g));
+            tangent_gradient<T>(rows.a, w, rows.o0);
+        }
+    }
+};
+
+// R (B,9) -> (e0, e1, e2) (B,3) in OpEuler's convention (e2 the middle angle, R = X(e0) Z(e2) Y(e1)):
+//     e2 = asin(clamp(-r1, -1, 1)),  (s3, c3) = (r2, r0) / |(r2, r0)| = sincos(e1)  ((0, 1) at exact gimbal lock: e1 = 0),
+//     e0 = atan2(s3 r3 - c3 r5, c3 r8 - s3 r6)      -- well conditioned at gimbal lock, where atan2(r7, r4) is 0 / 0.
+// The arc sine is taken as atan2(s2, c2) with c2 = |(r2, r0)|, which is sqrt(1 - r1^2) for a rotation: next to gimbal lock a float32
+// r1 no longer holds c2 (r1 = 1 - c2^2 / 2 rounds to 1 below c2 = 3.5e-4) and asin(-r1) alone misses R by up to that much;
+// r0 and r2 still carry it to full relative precision.
+// backward: in1 = g (B,3), out0 = dR (B,9).  With p = (delta_x c3 + delta_z s3) / c2:
+//     de0 = p,  de1 = delta_y + s2 p,  de2 = c3 delta_z - s3 delta_x;       c2 is clamped from below at kEulerMinCos.
+template <bool BWD> struct OpMatToEuler : OpBase {
+    static constexpr int kIn0 = 4, kIn1 = BWD ? 4 : 0, kOut0 = 4, kOut1 = 0;
+    static constexpr int kIn1N = 3, kOut0N = BWD ? 9 : 3;
+    template <class T, int NPL>
+    __device__ __forceinline__ void compute(Rows<T, OpMatToEuler> &rows, RowCtx<NPL> &) const {
+        typedef Tr<T> R;
+        const T (&r)[9] = rows.a;
+        const T one = R::splat(1.f), zero = R::splat(0.f);
+        const T s2 = R::clamp(-r[1], R::splat(-1.f), one);
+        const T h = R::fma(r[2], r[2], r[0] * r[0]);
+        const typename R::mask lock = R::le(h, zero);
+        const T ih = R::rsq(h);
+        const T c3 = R::sel(lock, one, r[0] * ih), s3 = R::sel(lock, zero, r[2] * ih);
+        if constexpr (!BWD) {
+            const T c2 = R::sqrt(h);
+            rows.o0[0] = R::atan2(R::fma(s3, r[3], -(c3 * r[5])), R::fma(c3, r[8], -(s3 * r[6])));
+            rows.o0[1] = R::atan2(s3, c3);
+            const T e2 = R::atan2(s2, c2), top = R::splat(kEulerMaxMiddle);                 // (selects, not med3: a NaN stays a NaN)
+            rows.o0[2] = R::sel(R::gt(e2, top), top, R::sel(R::gt(-top, e2), -top, e2));
+        } else {
+            const T (&g)[3] = rows.b;
+            const T ic = R::rcp(R::max(h * ih, R::splat(kEulerMinCos)));          // (h rsq(h) = sqrt(h); NaN at h = 0 falls to the floor)
+            const T p = R::fma(g[1], s2, g[0]) * ic;
+            const V3<T> w = mk<T>(R::fma(c3, p, -(s3 * g[2])), g[1], R::fma(s3, p, c3 * g[2]));
+            tangent_gradient<T>(r, w, rows.o0);
+        }
+    }
+};
+
+// v = log(R1^T R2) (B,3) in one pass: in0 = R1, in1 = R2, out0 = v; |v| is the geodesic angle.
+// backward: in2 = g (B,3), out0 = dR2, out1 = dR1 (BOTH).  With D = R1^T R2 = exp(hat v), which commutes with J_r^-1(v):
+//     w2 = J_r^-T(v) g = g - 1/2 v x g + c v x (v x g),      w1 = -D w2 = -J_r^-1(v) g = -(g + 1/2 v x g + c v x (v x g)),
+//     dR2 = 1/2 R2 hat(w2),  dR1 = 1/2 R1 hat(w1).
+// One gradient alone: log(R1^T R2) = -log(R2^T R1), so the host swaps the rotations and sets gsign = -1 for dR1.
+template <bool BWD, bool BOTH> struct OpRelLog : OpBase {
+    static_assert(BWD || !BOTH, "the forward has one output");
+    static constexpr int kIn0 = 4, kIn1 = 4, kIn2 = BWD ? 4 : 0, kOut0 = 4, kOut1 = BOTH ? 4 : 0;
+    static constexpr int kIn2N = 3, kOut0N = BWD ? 9 : 3;
+    float gsign = 1.f;
+    template <class T, int NPL>
+    __device__ __forceinline__ void compute(Rows<T, OpRelLog> &rows, RowCtx<NPL> &) const {
+        typedef Tr<T> R;
+        const T (&a)[9] = rows.a;
+        const T (&b)[9] = rows.b;
+        T d[9], q[4], n;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) d[3 * i + j] = R::fma(a[6 + i], b[6 + j], R::fma(a[3 + i], b[3 + j], a[i] * b[j]));
+        V3<T> v;
+        mat_to_quat<T>(d, q);
+        const T k = quat_log<T>(q, v, n);
+        if constexpr (!BWD) {
+            rows.o0[0] = v.x; rows.o0[1] = v.y; rows.o0[2] = v.z;
+        } else {
+            const V3<T> g = scale<T>(mk<T>(rows.c[0], rows.c[1], rows.c[2]), R::splat(gsign));
+            const T c = log_jacobian_c<T>(q[0], n, k * n);
+            const V3<T> vg = cross<T>(v, g);
+            const V3<T> even = axpy<T>(c, cross<T>(v, vg), g);
+            tangent_gradient<T>(b, axpy<T>(R::splat(-0.5f), vg, even), rows.o0);
+            if constexpr (BOTH) {
+                const V3<T> w1 = axpy<T>(R::splat(-0.5f), vg, scale<T>(even, R::splat(-1.f)));
+                tangent_gradient<T>(a, w1, rows.o1);
+            }
+        }
+    }
+};
+
 }  // namespace so3

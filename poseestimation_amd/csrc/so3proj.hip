@@ -1383,10 +1383,20 @@ __global__ __launch_bounds__(kBlock) void k_op_rows(Op op, int64_t B) {
 #pragma unroll
         for (int i = 0; i < Op::kIn1N; ++i) rows.b[i] = b[i];
     }
+    if constexpr (Op::kIn2 != 0) {
+        const float *c = static_cast<const float *>(op.in2) + row * Op::kIn2N;
+#pragma unroll
+        for (int i = 0; i < Op::kIn2N; ++i) rows.c[i] = c[i];
+    }
     op.template compute<float, 1>(rows, ctx);
     float *o = static_cast<float *>(op.out0) + row * Op::kOut0N;
 #pragma unroll
     for (int i = 0; i < Op::kOut0N; ++i) o[i] = rows.o0[i];
+    if constexpr (Op::kOut1 != 0) {
+        float *o1 = static_cast<float *>(op.out1) + row * Op::kOut1N;
+#pragma unroll
+        for (int i = 0; i < Op::kOut1N; ++i) o1[i] = rows.o1[i];
+    }
 }
 
 // ---- K4s / K3s one row per thread: a batch of up to kSmallBatch rows (one workgroup) and the remainder (< 64 rows) or unaligned input
@@ -2129,6 +2139,12 @@ inline unsigned persistent_grid(int64_t B) { const unsigned t = grid_for(B); ret
 #define SO3_K4B_BLOCK 256
 #endif
 
+#ifndef SO3_INV_NPL                  // the inverse maps' launch shape (so3_mat_to_quat_*, so3_logmap_*, so3_mat_to_euler_*, so3_relative_log_*)
+#define SO3_INV_NPL 2
+#define SO3_INV_WPS 4
+#define SO3_RELLOG_BWD_WPS 3
+#endif
+
 #define SO3_CHECK_ARGS(cond, name) \
     do { if (!(cond)) return fail(SO3_ERR_INVALID, name); } while (0)
 #define SO3_MAX_B (INT64_C(2147483647) * kBlock)
@@ -2198,18 +2214,20 @@ inline int64_t stream_units(int64_t B, std::initializer_list<const void *> ptrs)
     return B / so3::kUnitRows;
 }
 
-// A float32 row operation with one or two inputs and one output: whole units on the streaming engine, the rest
+// A float32 row operation with up to three inputs and up to two outputs: whole units on the streaming engine, the rest
 // (and everything when a pointer is not 16-byte aligned) one row per thread.
 template <int NPL, int WPS, int BLOCK, class Op>
 int run_row_op(Op op, int64_t B, hipStream_t s, const char *what) {
-    const int64_t nunits = stream_units(B, {op.in0, op.in1, op.out0});
+    const int64_t nunits = stream_units(B, {op.in0, op.in1, op.in2, op.out0, op.out1});
     if (nunits > 0) launch_rows<NPL, WPS, BLOCK>(op, nunits, s);
     const int64_t done = nunits * so3::kUnitRows, rest = B - done;
     if (rest > 0) {
         Op t = op;
         t.in0 = static_cast<const float *>(op.in0) + done * Op::kIn0N;
         if (Op::kIn1 != 0) t.in1 = static_cast<const float *>(op.in1) + done * Op::kIn1N;
+        if (Op::kIn2 != 0) t.in2 = static_cast<const float *>(op.in2) + done * Op::kIn2N;
         t.out0 = static_cast<float *>(op.out0) + done * Op::kOut0N;
+        if (Op::kOut1 != 0) t.out1 = static_cast<float *>(op.out1) + done * Op::kOut1N;
         hipLaunchKernelGGL((k_op_rows<Op>), dim3(grid_for(rest)), dim3(kBlock), 0, s, t, rest);
     }
     return check_launch(what);
@@ -2813,6 +2831,51 @@ SO3_DEFINE_HEAD(euler, OpEuler)
 SO3_DEFINE_HEAD(ortho5d, OpOrtho5d)
 SO3_DEFINE_HEAD(expmap, OpExpMap)
 #undef SO3_DEFINE_HEAD
+
+// The inverse maps (include/so3proj.h, "inverse maps"): R (B,9) -> W numbers per row, and the tangent-space gradient back.
+#define SO3_DEFINE_INVERSE(NAME, OP)                                                                                \
+    int so3_##NAME##_fwd_f32(const float *R, float *Y, int64_t B, void *stream) {                                    \
+        SO3_CHECK_ARGS(B >= 0 && B <= SO3_MAX_B, "so3_" #NAME "_fwd_f32: B");                                        \
+        if (B == 0) return 0;                                                                                        \
+        SO3_CHECK_ARGS(R != nullptr && Y != nullptr, "so3_" #NAME "_fwd_f32: null pointer");                         \
+        so3::OP<false> op; op.in0 = R; op.out0 = Y;                                                                  \
+        return run_row_op<SO3_INV_NPL, SO3_INV_WPS, 256>(op, B, static_cast<hipStream_t>(stream), "so3_" #NAME "_fwd_f32"); \
+    }                                                                                                                \
+    int so3_##NAME##_bwd_f32(const float *R, const float *G, float *dR, int64_t B, void *stream) {                   \
+        SO3_CHECK_ARGS(B >= 0 && B <= SO3_MAX_B, "so3_" #NAME "_bwd_f32: B");                                        \
+        if (B == 0) return 0;                                                                                        \
+        SO3_CHECK_ARGS(R != nullptr && G != nullptr && dR != nullptr, "so3_" #NAME "_bwd_f32: null pointer");        \
+        so3::OP<true> op; op.in0 = R; op.in1 = G; op.out0 = dR;                                                      \
+        return run_row_op<SO3_INV_NPL, SO3_INV_WPS, 256>(op, B, static_cast<hipStream_t>(stream), "so3_" #NAME "_bwd_f32"); \
+    }
+SO3_DEFINE_INVERSE(mat_to_quat, OpMatToQuat)
+SO3_DEFINE_INVERSE(logmap, OpLogMap)
+SO3_DEFINE_INVERSE(mat_to_euler, OpMatToEuler)
+#undef SO3_DEFINE_INVERSE
+
+int so3_relative_log_fwd_f32(const float *R1, const float *R2, float *V, int64_t B, void *stream) {
+    SO3_CHECK_ARGS(B >= 0 && B <= SO3_MAX_B, "so3_relative_log_fwd_f32: B");
+    if (B == 0) return 0;
+    SO3_CHECK_ARGS(R1 != nullptr && R2 != nullptr && V != nullptr, "so3_relative_log_fwd_f32: null pointer");
+    so3::OpRelLog<false, false> op; op.in0 = R1; op.in1 = R2; op.out0 = V;
+    return run_row_op<SO3_INV_NPL, SO3_INV_WPS, 256>(op, B, static_cast<hipStream_t>(stream), "so3_relative_log_fwd_f32");
+}
+
+int so3_relative_log_bwd_f32(const float *R1, const float *R2, const float *G, float *dR1, float *dR2, int64_t B, void *stream) {
+    SO3_CHECK_ARGS(B >= 0 && B <= SO3_MAX_B, "so3_relative_log_bwd_f32: B");
+    if (B == 0) return 0;
+    SO3_CHECK_ARGS(R1 != nullptr && R2 != nullptr && G != nullptr && (dR1 != nullptr || dR2 != nullptr), "so3_relative_log_bwd_f32: null pointer");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (dR1 != nullptr && dR2 != nullptr) {
+        so3::OpRelLog<true, true> op; op.in0 = R1; op.in1 = R2; op.in2 = G; op.out0 = dR2; op.out1 = dR1;
+        return run_row_op<SO3_INV_NPL, SO3_RELLOG_BWD_WPS, 256>(op, B, s, "so3_relative_log_bwd_f32");
+    }
+    // one gradient alone: log(R1^T R2) = -log(R2^T R1), so dR1 is the second argument's gradient of the swapped pair under -g
+    so3::OpRelLog<true, false> op; op.in2 = G;
+    if (dR2 != nullptr) { op.in0 = R1; op.in1 = R2; op.out0 = dR2; }
+    else { op.in0 = R2; op.in1 = R1; op.out0 = dR1; op.gsign = -1.f; }
+    return run_row_op<SO3_INV_NPL, SO3_RELLOG_BWD_WPS, 256>(op, B, s, "so3_relative_log_bwd_f32");
+}
 
 int so3_add_l1_f32(const float *Tgt, const float *Tpred, const float *points, float *dists, double *loss_sum, float *dTpred,
                    float grad_scale, int64_t B, int32_t N, void *stream) {

@@ -1613,3 +1613,150 @@ head_dimensions = {"SVD": 9, "6D": 6, "5D": 5, "Quat": 4, "Euler": 3, "Direct": 
 head_functions = {"SVD": symmetric_orthogonalization, "6D": compute_rotation_matrix_from_ortho6d,
                   "5D": compute_rotation_matrix_from_ortho5d, "Quat": compute_rotation_matrix_from_quaternion,
                   "quat": compute_rotation_matrix_from_quaternion, "Euler": compute_rotation_matrix_from_euler}
+
+
+# --------------------------------------------------------------------------------------------
+# inverse maps: rotation matrix -> quaternion / rotation vector / Euler angles / 6D, and log(R1^T R2)
+# --------------------------------------------------------------------------------------------
+# GRADIENT CONVENTION (include/so3proj.h).  The backward of every inverse map returns the TANGENT-SPACE gradient at R: with
+# w = (d f(R exp(hat delta)) / d delta)^T g it is dR = 1/2 R hat(w).  It does not depend on the branch the forward took, it is bounded
+# for the log map up to theta = pi, and it equals the tangent projection R skew(R^T G) of any off-manifold autograd gradient G.
+# Every head of this package moves R along tangent directions, so chaining an inverse map behind a head is exact.
+EULER_GIMBAL_COS_FLOOR = 1e-6        # csrc: kEulerMinCos -- cos(e2) is clamped from below at this in matrix_to_euler's gradient
+
+
+def _check_rotations(r: torch.Tensor, name: str) -> None:
+    if not ((r.dim() == 3 and r.shape[1:] == (3, 3)) or (r.dim() == 2 and r.shape[1] == 9)):
+        raise RuntimeError("%s expects (B,3,3) or (B,9) rotation matrices, got %s" % (name, tuple(r.shape)))
+    if r.dtype not in (torch.float32, torch.float16, torch.bfloat16, torch.float64):
+        raise TypeError("%s: unsupported dtype %s (inputs: float32, float16, bfloat16, float64)" % (name, r.dtype))
+
+
+def _rotation_blocks(r: torch.Tensor, name: str) -> torch.Tensor:
+    """(B,3,3) or (B,9) of any supported dtype -> contiguous float32 (B,9) (detached)."""
+    _check_rotations(r, name)
+    return r.detach().reshape(-1, 9).contiguous().float()
+
+
+def _make_inverse(symbol: str, width: int, name: str):
+    """autograd.Function over so3_<symbol>_fwd_f32 / _bwd_f32 for a (B,3,3) -> (B, width) inverse map."""
+
+    class _Inverse(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, r_in):
+            dev = _require_device(r_in)
+            r = _rotation_blocks(r_in, name)
+            b = r.shape[0]
+            y = torch.empty((b, width), dtype=torch.float32, device=dev)
+            with _on_device(dev):
+                _check(getattr(_lib.load(), "so3_%s_fwd_f32" % symbol)(_ptr(r), _ptr(y), b, _stream(dev)), "so3_%s_fwd_f32" % symbol)
+            ctx.save_for_backward(r)
+            ctx.in_dtype, ctx.in_shape = r_in.dtype, r_in.shape
+            return y
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_y):
+            (r,) = ctx.saved_tensors
+            dev = r.device
+            g = grad_y.reshape(-1, width).contiguous().float()
+            dr = torch.empty_like(r)
+            with _on_device(dev):
+                _check(getattr(_lib.load(), "so3_%s_bwd_f32" % symbol)(_ptr(r), _ptr(g), _ptr(dr), r.shape[0], _stream(dev)), "so3_%s_bwd_f32" % symbol)
+            return dr.to(ctx.in_dtype).view(ctx.in_shape)
+
+    _Inverse.__name__ = "_Inverse_" + symbol
+    return _Inverse
+
+
+_MatToQuat = _make_inverse("mat_to_quat", 4, "matrix_to_quaternion")
+_LogMap = _make_inverse("logmap", 3, "so3_log_map")
+_MatToEuler = _make_inverse("mat_to_euler", 3, "matrix_to_euler")
+
+
+def matrix_to_quaternion(R: torch.Tensor) -> torch.Tensor:
+    """(B,3,3) or (B,9) rotation matrices -> (B,4) float32 unit quaternions (w,x,y,z) with w >= 0, the order
+    compute_rotation_matrix_from_quaternion reads.  Shepperd's method on the largest of (tr, r0, r4, r8), branch-free.
+    Differentiable: the backward returns the tangent-space gradient 1/2 R hat(w), w = (dq/ddelta)^T g,
+    dq/ddelta = 1/2 [-(x,y,z)^T ; w I + hat(x,y,z)] (see the convention above), cast back to R's dtype and shape.
+    Nothing is validated on the device: a NaN row gives a NaN row."""
+    return _MatToQuat.apply(R)
+
+
+def so3_log_map(R: torch.Tensor) -> torch.Tensor:
+    """(B,3,3) or (B,9) rotation matrices -> (B,3) float32 rotation vectors, |v| <= float32(pi): the inverse of so3_exp_map /
+    vec_3d_to_SO3.  Through the quaternion (theta = 2 atan2(|xyz|, w)), so the axis survives next to theta = pi, where acos of the
+    trace and (R - R^T) / (2 sin theta) lose it.  Differentiable: tangent-space gradient 1/2 R hat(J_r^-T(v) g), bounded up to pi."""
+    return _LogMap.apply(R)
+
+
+def matrix_to_euler(R: torch.Tensor) -> torch.Tensor:
+    """(B,3,3) or (B,9) rotation matrices -> (B,3) float32 Euler angles in compute_rotation_matrix_from_euler's convention
+    (e[:,2] is the middle angle, |e[:,2]| <= pi/2): (s3, c3) = (r2, r0) / |(r2, r0)| = sincos(e1), e0 = atan2(s3 r3 - c3 r5, c3 r8 - s3 r6),
+    which keeps forward(inverse(R)) within rounding of R at gimbal lock, and e2 = atan2(clamp(-r1, -1, 1), |(r2, r0)|), clamped to the
+    float32 just below pi/2 -- asin(-r1) for a rotation, computed from the two entries that still hold cos(e2) next to gimbal lock, where
+    a float32 r1 has rounded to +-1.  At exact gimbal lock e1 = 0.
+    Differentiable (tangent-space gradient); the Jacobian carries 1 / cos(e2), and cos(e2) is clamped from below at
+    EULER_GIMBAL_COS_FLOOR, so the gradient is finite everywhere."""
+    return _MatToEuler.apply(R)
+
+
+def matrix_to_ortho6d(R: torch.Tensor) -> torch.Tensor:
+    """(B,3,3) or (B,9) rotation matrices -> (B,6) float32: the first two columns, in the layout the 6D head reads
+    (compute_rotation_matrix_from_ortho6d).  Plain indexing, differentiated by torch's own autograd."""
+    _require_device(R)
+    _check_rotations(R, "matrix_to_ortho6d")
+    m = R.reshape(-1, 3, 3).float()
+    return torch.cat((m[:, :, 0], m[:, :, 1]), 1)
+
+
+class _RelativeLog(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, r1_in, r2_in):
+        dev = _require_device(r1_in, r2_in)
+        r1 = _rotation_blocks(r1_in, "relative_rotation_vector")
+        r2 = _rotation_blocks(r2_in, "relative_rotation_vector")
+        if r1.shape != r2.shape:
+            raise RuntimeError("relative_rotation_vector: batch sizes differ (%d, %d)" % (r1.shape[0], r2.shape[0]))
+        b = r1.shape[0]
+        v = torch.empty((b, 3), dtype=torch.float32, device=dev)
+        with _on_device(dev):
+            _check(_lib.load().so3_relative_log_fwd_f32(_ptr(r1), _ptr(r2), _ptr(v), b, _stream(dev)), "so3_relative_log_fwd_f32")
+        ctx.save_for_backward(r1, r2)
+        ctx.meta = (r1_in.dtype, r1_in.shape, r2_in.dtype, r2_in.shape)
+        return v
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_v):
+        r1, r2 = ctx.saved_tensors
+        dev = r1.device
+        g = grad_v.reshape(-1, 3).contiguous().float()
+        d1 = torch.empty_like(r1) if ctx.needs_input_grad[0] else None
+        d2 = torch.empty_like(r2) if ctx.needs_input_grad[1] else None
+        if d1 is None and d2 is None:
+            return None, None
+        with _on_device(dev):
+            _check(_lib.load().so3_relative_log_bwd_f32(_ptr(r1), _ptr(r2), _ptr(g), _ptr(d1), _ptr(d2), r1.shape[0], _stream(dev)),
+                   "so3_relative_log_bwd_f32")
+        dt1, sh1, dt2, sh2 = ctx.meta
+        return (d1.to(dt1).view(sh1) if d1 is not None else None, d2.to(dt2).view(sh2) if d2 is not None else None)
+
+
+def relative_rotation_vector(R1: torch.Tensor, R2: torch.Tensor) -> torch.Tensor:
+    """log(R1^T R2) as (B,3) float32 rotation vectors in one launch; the row norm is the geodesic angle between R1 and R2.
+    Differentiable in both arguments with one backward launch (tangent-space gradients at R1 and at R2)."""
+    return _RelativeLog.apply(R1, R2)
+
+
+def _matrix_to_svd9(R: torch.Tensor) -> torch.Tensor:
+    _require_device(R)
+    _check_rotations(R, 'inverse_head_functions["SVD"]')
+    return R.reshape(-1, 9).float()
+
+
+# The inverse of every head: head_functions[key] (transform_output["3D"][1] for "3D") applied to inverse_head_functions[key](R) gives
+# back R.  "5D" is deliberately absent: the head maps five numbers onto three degrees of freedom through a stereographic un-projection,
+# and this package defines no canonical preimage for it (matrix_to_ortho6d gives the 6D one).
+inverse_head_functions = {"SVD": _matrix_to_svd9, "6D": matrix_to_ortho6d, "Quat": matrix_to_quaternion, "quat": matrix_to_quaternion,
+                          "Euler": matrix_to_euler, "3D": so3_log_map}

@@ -139,6 +139,21 @@ def main():
         timeit("f5 so3_%s_fwd_f32" % name, lambda i: fwd(p(xh[i % NB]), p(r[i % NB]), n, st), (4 * w + 36) * n)
         timeit("f5 so3_%s_bwd_f32" % name, lambda i: bwd(p(xh[i % NB]), p(g[i % NB]), p(dh), n, st), (8 * w + 36) * n)
         del xh, dh
+    # the inverse maps: rotation -> quaternion / rotation vector / Euler angles, log(R1^T R2), and their tangent-space gradients
+    for name, w in (("mat_to_quat", 4), ("logmap", 3), ("mat_to_euler", 3)):
+        yh = torch.empty(n, w, device=dev)
+        gh = [torch.randn(n, w, device=dev) for _ in range(NB)]
+        fwd, bwd = getattr(lib, "so3_%s_fwd_f32" % name), getattr(lib, "so3_%s_bwd_f32" % name)
+        timeit("inv so3_%s_fwd_f32" % name, lambda i: fwd(p(rt[i % NB]), p(yh), n, st), (36 + 4 * w) * n)
+        timeit("inv so3_%s_bwd_f32" % name, lambda i: bwd(p(rt[i % NB]), p(gh[i % NB]), p(dm[i % NB]), n, st), (72 + 4 * w) * n)
+        del yh, gh
+    v3 = torch.empty(n, 3, device=dev)
+    g3 = [torch.randn(n, 3, device=dev) for _ in range(NB)]
+    dm2 = torch.empty(n, 9, device=dev)                # dR2 (the rotation buffers r[] are read again below)
+    timeit("inv so3_relative_log_fwd_f32", lambda i: lib.so3_relative_log_fwd_f32(p(rt[i % NB]), p(rt[(i + 1) % NB]), p(v3), n, st), 84 * n)
+    timeit("inv so3_relative_log_bwd_f32 (dR1 + dR2)",
+           lambda i: lib.so3_relative_log_bwd_f32(p(rt[i % NB]), p(rt[(i + 1) % NB]), p(g3[i % NB]), p(dm[i % NB]), p(dm2), n, st), 156 * n)
+    del v3, g3, dm2
     o12 = [torch.randn(n, 12, device=dev) for _ in range(3)]
     ti = [torch.eye(4, device=dev).repeat(n, 1, 1).contiguous() + 0.1 * torch.randn(n, 4, 4, device=dev) for _ in range(3)]
     tp = torch.empty(n, 16, device=dev); g16 = torch.randn(n, 16, device=dev); do12 = torch.empty(n, 12, device=dev)

@@ -428,7 +428,103 @@ def g17_symmetry():
     save("g17_symmetry.npz", **out)
 
 
+def g18_inverse_maps():
+    """The inverse maps (matrix -> quaternion / rotation vector / Euler angles, log(R1^T R2)): about 4 000 float32 rotations made in
+    float64 and then rounded, with the float64 answers for each row.  Families (`family`, names in `family_names`): uniform random;
+    theta in [0, 1e-3]; theta in [pi - 1e-3, pi]; theta exactly 0 and exactly pi about random and about coordinate axes; the 24
+    axis-aligned rotations; |e2| within 1e-3 of pi/2 and exactly pi/2; rows where two of (tr, r0, r4, r8) tie (rotations about a
+    coordinate axis: two equal diagonal entries; half turns about (s, s, t) and (0, s, t): r0 = r4, tr = r0).
+    Answers: scipy's Rotation.as_quat (reordered to (w,x,y,z), w >= 0) and as_rotvec of the NEAREST rotation (from_matrix projects the
+    rounded matrix), the Euler triple of compute_rotation_matrix_from_euler's convention by the definition in float64
+    (e2 = asin(clamp(-r1)), e1 = atan2(r2, r0), e0 = atan2(s3 r3 - c3 r5, c3 r8 - s3 r6), atan2(0, 0) = 0), and log(R1^T R2) for the
+    shuffled pairing `perm`.  The reference's forward maps (compute_rotation_matrix_from_quaternion, so3_exp_map,
+    compute_rotation_matrix_from_euler, run in float64, stored as float32) applied to those answers are kept for every fourth row
+    (`fwd_rows`).  `g` is a fixed upstream gradient (its first three columns serve the three-vectors).
+    The rows exempt from a signed value comparison (|w| < 1e-3, pi - theta < 1e-3, | |e2| - pi/2 | < 1e-2) stay below 25 %."""
+    from scipy.spatial.transform import Rotation
+
+    rng = np.random.default_rng(18)
+    fam_names, mats, fam = [], [], []
+
+    def add(name, m):
+        m = np.asarray(m, np.float64).reshape(-1, 3, 3)
+        if name not in fam_names:
+            fam_names.append(name)
+        mats.append(m)
+        fam.append(np.full(len(m), fam_names.index(name)))
+
+    def unit(n):
+        a = rng.standard_normal((n, 3))
+        return a / np.linalg.norm(a, axis=1, keepdims=True)
+
+    def euler_matrix(e):
+        return rr.compute_rotation_matrix_from_euler(torch.as_tensor(np.asarray(e, np.float64))).numpy()
+
+    add("random", Rotation.random(2400, random_state=18).as_matrix())
+    add("theta_small", Rotation.from_rotvec(unit(300) * rng.uniform(0.0, 1e-3, (300, 1))).as_matrix())
+    add("theta_near_pi", Rotation.from_rotvec(unit(300) * (np.pi - rng.uniform(0.0, 1e-3, (300, 1)))).as_matrix())
+    add("theta_zero", np.tile(np.eye(3), (8, 1, 1)))
+    ax = unit(100)
+    add("theta_pi_random_axis", 2.0 * ax[:, :, None] * ax[:, None, :] - np.eye(3))
+    add("theta_pi_coordinate_axis", [np.diag(d) for d in ([1., -1., -1.], [-1., 1., -1.], [-1., -1., 1.])])
+    axis_aligned = []
+    for perm in ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0)):
+        for signs in ((1, 1, 1), (1, 1, -1), (1, -1, 1), (1, -1, -1), (-1, 1, 1), (-1, 1, -1), (-1, -1, 1), (-1, -1, -1)):
+            m = np.zeros((3, 3))
+            for i in range(3):
+                m[i, perm[i]] = signs[i]
+            if np.linalg.det(m) > 0:
+                axis_aligned.append(m)
+    assert len(axis_aligned) == 24
+    add("axis_aligned", axis_aligned)
+    e = rng.uniform(-np.pi, np.pi, (250, 3))
+    e[:, 2] = rng.choice([-1.0, 1.0], 250) * (np.pi / 2 - rng.uniform(0.0, 1e-3, 250))
+    add("gimbal_near", euler_matrix(e))
+    e = rng.uniform(-np.pi, np.pi, (50, 3))
+    e[:, 2] = rng.choice([-1.0, 1.0], 50) * (np.pi / 2)
+    add("gimbal_exact", euler_matrix(e))
+    ang = rng.uniform(-np.pi, np.pi, 150)
+    add("tie_diagonal", Rotation.from_rotvec(np.eye(3)[np.arange(150) % 3] * ang[:, None]).as_matrix())
+    s_ = np.cos(rng.uniform(0.0, np.pi, 60))
+    half = []
+    for k, s0 in enumerate(s_):
+        a = np.array([s0, s0, 1.0]) if k % 2 == 0 else np.array([0.0, s0, 1.0])
+        a = np.roll(a, k % 3) / np.linalg.norm(a)
+        half.append(2.0 * np.outer(a, a) - np.eye(3))
+    add("tie_half_turn", half)
+
+    r = np.concatenate(mats).astype(np.float32)
+    family = np.concatenate(fam).astype(np.int16)
+    n = len(r)
+    near = Rotation.from_matrix(r.astype(np.float64))            # the nearest rotation of each rounded matrix
+    q = near.as_quat()[:, [3, 0, 1, 2]]
+    q = np.where(q[:, :1] < 0, -q, q)
+    v = near.as_rotvec()
+    m = near.as_matrix().reshape(n, 9)
+    e2 = np.arcsin(np.clip(-m[:, 1], -1.0, 1.0))
+    e1 = np.arctan2(m[:, 2], m[:, 0])
+    s3, c3 = np.sin(e1), np.cos(e1)
+    e0 = np.arctan2(s3 * m[:, 3] - c3 * m[:, 5], c3 * m[:, 8] - s3 * m[:, 6])
+    euler = np.stack([e0, e1, e2], 1)
+    perm = rng.permutation(n)
+    rel = (near.inv() * near[perm]).as_rotvec()
+    fwd_rows = np.arange(0, n, 4)
+    f32 = lambda t: t.numpy().astype(np.float32)
+    r_from_quat = f32(rr.compute_rotation_matrix_from_quaternion(torch.as_tensor(q[fwd_rows])))
+    r_from_rotvec = f32(rr.so3_exp_map(torch.as_tensor(v[fwd_rows])))
+    r_from_euler = f32(rr.compute_rotation_matrix_from_euler(torch.as_tensor(euler[fwd_rows])))
+    theta = np.linalg.norm(v, axis=1)
+    exempt = (np.abs(q[:, 0]) < 1e-3) | (np.pi - theta < 1e-3) | (np.abs(np.abs(e2) - np.pi / 2) < 1e-2)
+    assert exempt.mean() < 0.25, exempt.mean()
+    print("g18: %d rows, %.1f %% exempt from a signed comparison" % (n, 100 * exempt.mean()))
+    save("g18_inverse_maps.npz", r=r, family=family, family_names=np.array(fam_names), quat=q, rotvec=v, euler=euler, perm=perm.astype(np.int32),
+         rel_rotvec=rel, fwd_rows=fwd_rows.astype(np.int32), r_from_quat=r_from_quat, r_from_rotvec=r_from_rotvec, r_from_euler=r_from_euler,
+         g=rng.standard_normal((n, 4)).astype(np.float32))
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "g18":
+        return g18_inverse_maps()
     if len(sys.argv) > 1 and sys.argv[1] == "g17":
         return g17_symmetry()
     if len(sys.argv) > 1 and sys.argv[1] == "g16":
