@@ -388,6 +388,32 @@ int so3_add_l1_f32(const float *Tgt, const float *Tpred, const float *points, fl
 int so3_add_l1_disentangled_f32(const float *Tpred, const float *Tgt, const float *points, double *loss_sum,
                                 float *dTpred, float grad_scale, int64_t B, int32_t N, void *stream);
 
+/* ---- the ADD and ADD-S pose metrics, the ADD-S loss's gradient and the model diameter ---------------------------
+ * The numbers a 6-D pose is reported in (Hinterstoisser et al. 2012; PoseCNN's ADD-S); the reference has no such metric.
+ * With x_i = R_gt p_i + t_gt and y_j = R_pred p_j + t_pred over the N points of sample b:
+ *   so3_add_l2_f32:  ADD_b = (1/N) sum_i |x_i - y_i|_2.  Arguments exactly as so3_add_l1_f32; in dTpred d|e| = e/|e|,
+ *     0 where e = 0.
+ *   so3_add_s_fwd_f32:  ADDS_b = (1/N) sum_i min_j |x_i - y_j|_2 (the outer sum over the true pose, not symmetric).
+ *     point_dist out B*N float32: min_j |x_i - y_j| per point (the work buffer of the row sums: required)
+ *     nearest    out optional B*N int32: the argmin j (the first of equal candidates)
+ *     dists      out optional B float32: ADDS_b;  loss_sum out optional double[1] = sum_b ADDS_b (written, not added to)
+ *   so3_add_s_bwd_f32:  the selected branch's gradient through `nearest` (an index outside [0, N) is clamped):
+ *     dTpred out B*16 float32 = grad_scale * grad_rows[b] * dADDS_b/dTpred (grad_rows NULL: 1), bottom row 0
+ *   so3_cloud_diameter_f32:  diam_b = max_ij |p_i - p_j|_2;  work: B*N float32 scratch (per-point maxima), diam: B float32
+ * Both clouds are posed by the same code and a distance is formed from coordinate differences (never |x|^2 + |y|^2 - 2 x.y),
+ * so Tpred == Tgt gives exactly 0 and nearest[i] == i where the points are distinct.  The ADD-S and diameter entries use no
+ * atomics: two runs give the same bits.  They are N^2 arithmetic per cloud (compute bound), 1 <= N <= SO3_ADD_S_MAX_N -- so that
+ * B*N stays below 2^51 and the 32-bit point and tile indices cannot overflow.
+ */
+#define SO3_ADD_S_MAX_N 1048576
+int so3_add_l2_f32(const float *Tgt, const float *Tpred, const float *points, float *dists, double *loss_sum,
+                   float *dTpred, float grad_scale, int64_t B, int32_t N, void *stream);
+int so3_add_s_fwd_f32(const float *Tgt, const float *Tpred, const float *points, float *point_dist, int32_t *nearest,
+                      float *dists, double *loss_sum, int64_t B, int32_t N, void *stream);
+int so3_add_s_bwd_f32(const float *Tgt, const float *Tpred, const float *points, const int32_t *nearest,
+                      const float *grad_rows, float grad_scale, float *dTpred, int64_t B, int32_t N, void *stream);
+int so3_cloud_diameter_f32(const float *points, float *work, float *diam, int64_t B, int32_t N, void *stream);
+
 /* ---- next row: per-class evaluation statistics on K4's angles ----------------------
  * Replaces the host-side numpy block of 3D-Pose/test_per_class.py:174-216 (np.mean / np.median / np.std / np.max
  * and the accuracy thresholds (x < 30|15|7.5).sum()/len(x)), which the reference feeds one sample at a time.

@@ -57,6 +57,10 @@ SYMBOLS = {
     "so3_pc_normalize_f32": (_INT, [_P, _P, _P, _P, _I64, _I32, _P]),
     "so3_add_l1_f32": (_INT, [_P, _P, _P, _P, _P, _P, ctypes.c_float, _I64, _I32, _P]),
     "so3_add_l1_disentangled_f32": (_INT, [_P, _P, _P, _P, _P, ctypes.c_float, _I64, _I32, _P]),
+    "so3_add_l2_f32": (_INT, [_P, _P, _P, _P, _P, _P, ctypes.c_float, _I64, _I32, _P]),
+    "so3_add_s_fwd_f32": (_INT, [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P]),
+    "so3_add_s_bwd_f32": (_INT, [_P, _P, _P, _P, _P, ctypes.c_float, _P, _I64, _I32, _P]),
+    "so3_cloud_diameter_f32": (_INT, [_P, _P, _P, _I64, _I32, _P]),
     "so3_angle_stats_workspace_bytes": (ctypes.c_size_t, []),
     "so3_angle_stats": (_INT, [_P, _P, _I32, _P, _P, _I64, _P]),
     "so3_kabsch_f32": (_INT, [_P, _P, _P, _P, _I64, _I32, _P]),
@@ -68,6 +72,7 @@ SYMBOLS = {
     "so3_sym_frob_loss_f32": (_INT, [_P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _U32, _I64, _P]),
 }
 
+ADD_S_MAX_N = 1 << 20                             # include/so3proj.h: SO3_ADD_S_MAX_N
 ABI_VERSION = 210                                 # include/so3proj.h: SO3PROJ_VERSION this binding's argument lists belong to
 
 _lock = threading.Lock()

@@ -1077,4 +1077,26 @@ template <> __device__ __forceinline__ void project_backward_rows<double>(const 
     project_backward(f, g, dm);
 }
 
+// ---- ADD / ADD-S / cloud diameter (so3proj.hip: k_add_s, k_add_s_bwd, k_add_l1<.., L2>; tests/host_model/add_metrics.cpp) ----------
+// The arithmetic that is part of the metrics' definition: both clouds are posed by pose_point (one fmaf order), a distance is formed
+// from coordinate differences (pair_dist2), and the square root is taken once per point, after the minimum.
+// m = the top three rows of a row-major 4x4 pose: m[4c .. 4c+2] = row c of R, m[4c+3] = t_c.
+__device__ __forceinline__ void pose_point(const float (&m)[12], float px, float py, float pz, float &x, float &y, float &z) {
+    x = __builtin_fmaf(m[0], px, __builtin_fmaf(m[1], py, __builtin_fmaf(m[2], pz, m[3])));
+    y = __builtin_fmaf(m[4], px, __builtin_fmaf(m[5], py, __builtin_fmaf(m[6], pz, m[7])));
+    z = __builtin_fmaf(m[8], px, __builtin_fmaf(m[9], py, __builtin_fmaf(m[10], pz, m[11])));
+}
+__device__ __forceinline__ float pair_dist2(float dx, float dy, float dz) {                // 1 multiply, 2 FMAs
+    return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+}
+// One pair of the N^2 loop: 3 subtracts, pair_dist2, one min (ADD-S) or max (diameter).  The first of equal candidates keeps the index.
+template <bool WANT_INDEX, bool DIAMETER>
+__device__ __forceinline__ void add_s_pair(float x, float y, float z, float qx, float qy, float qz, int j, float &best, int &idx) {
+    const float d2 = pair_dist2(x - qx, y - qy, z - qz);
+    if (WANT_INDEX) idx = d2 < best ? j : idx;
+    best = DIAMETER ? __builtin_fmaxf(best, d2) : __builtin_fminf(best, d2);
+}
+// 1 / |e| for the unit direction u = e / |e|, 0 where e = 0 (d2 = |e|^2 as pair_dist2 gives it)
+__device__ __forceinline__ float unit_scale(float d2) { return d2 > 0.f ? hw::rcp(hw::sqrt(d2)) : 0.f; }
+
 }  // namespace so3

@@ -7,6 +7,7 @@
 // nine floats out of LDS at a 9-dword stride (odd stride -> conflict-free ds_read_b32 / ds_write_b32).
 #include <hip/hip_runtime.h>
 #include <cxxabi.h>
+#include <algorithm>
 #include <stdlib.h>
 #include <string>
 #include <stdint.h>
@@ -1098,7 +1099,9 @@ __device__ __forceinline__ float sgn_of(float d) { return __builtin_amdgcn_fmed3
 
 // kAddUnroll = 12-byte loads in flight per lane: 16 for large clouds (12 KB per wave, what K5 has with two arrays),
 // fewer for small ones, whose zero-filled slots would only cost arithmetic.
-template <bool DISENT, int kAddUnroll>
+// L2 = compute_ADD_loss (the ADD metric): the same pass with |d|_2 in place of the L1 sum and u = d / |d| (0 where d = 0) in place of
+// the signs; dist_b = mean_i |d_i|, k = scale / N.  Its zero-filled slots are masked, so they contribute exactly zero.
+template <bool DISENT, int kAddUnroll, bool L2 = false>
 __global__ __launch_bounds__(kBlock) void k_add_l1(const float *__restrict__ Tgt, const float *__restrict__ Tpred,
                                                    const float *__restrict__ pts, float *__restrict__ dists,
                                                    double *__restrict__ loss_sum, float *__restrict__ dT, float grad_scale,
@@ -1142,15 +1145,24 @@ __global__ __launch_bounds__(kBlock) void k_add_l1(const float *__restrict__ Tgt
                 const float dx = fmaf(dr[0], px, fmaf(dr[1], py, fmaf(dr[2], pz, ax)));
                 const float dy = fmaf(dr[3], px, fmaf(dr[4], py, fmaf(dr[5], pz, ay)));
                 const float dz = fmaf(dr[6], px, fmaf(dr[7], py, fmaf(dr[8], pz, az)));
-                acc[0] += fabsf(dx) + fabsf(dy) + fabsf(dz);
-                const float sx = sgn_of(dx), sy = sgn_of(dy), sz = sgn_of(dz);
+                float sx, sy, sz;
+                if (L2) {
+                    const bool in = i0 + 64 * u + lane < N;
+                    const float d2 = so3::pair_dist2(dx, dy, dz);
+                    const float inv = in ? so3::unit_scale(d2) : 0.f;
+                    acc[0] += in ? so3::hw::sqrt(d2) : 0.f;
+                    sx = dx * inv; sy = dy * inv; sz = dz * inv;
+                } else {
+                    acc[0] += fabsf(dx) + fabsf(dy) + fabsf(dz);
+                    sx = sgn_of(dx); sy = sgn_of(dy); sz = sgn_of(dz);
+                }
                 acc[1] = fmaf(sx, px, acc[1]); acc[2] = fmaf(sx, py, acc[2]); acc[3] = fmaf(sx, pz, acc[3]);
                 acc[4] = fmaf(sy, px, acc[4]); acc[5] = fmaf(sy, py, acc[5]); acc[6] = fmaf(sy, pz, acc[6]);
                 acc[7] = fmaf(sz, px, acc[7]); acc[8] = fmaf(sz, py, acc[8]); acc[9] = fmaf(sz, pz, acc[9]);
                 acc[10] += sx; acc[11] += sy; acc[12] += sz;
             }
         }
-        if (!DISENT) {      // take the zero-filled slots back out (they saw d = dt exactly)
+        if (!DISENT && !L2) {      // take the zero-filled slots back out (they saw d = dt exactly)
             acc[0] = fmaf(-npad, fabsf(ax) + fabsf(ay) + fabsf(az), acc[0]);
             acc[10] = fmaf(-npad, sgn_of(ax), acc[10]);
             acc[11] = fmaf(-npad, sgn_of(ay), acc[11]);
@@ -1166,7 +1178,8 @@ __global__ __launch_bounds__(kBlock) void k_add_l1(const float *__restrict__ Tgt
     }
     // lane j < nc finishes sample c0 + j
     const bool active = lane < nc;
-    const float dist = keep[0] * inv3n;
+    const float inv_n = L2 ? 1.0f / static_cast<float>(N) : inv3n;
+    const float dist = keep[0] * inv_n;
     double part[3] = {0.0, 0.0, 0.0};
     if (active) {
         const int64_t b = c0 + lane;
@@ -1177,7 +1190,7 @@ __global__ __launch_bounds__(kBlock) void k_add_l1(const float *__restrict__ Tgt
         }
         if (dists != nullptr) dists[b] = dist;
         if (dT != nullptr) {
-            const float k = -grad_scale * inv3n, kt = -grad_scale * (1.0f / 3.0f);
+            const float k = -grad_scale * inv_n, kt = -grad_scale * (1.0f / 3.0f);
             float *o = dT + b * 16;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
@@ -1201,6 +1214,166 @@ __global__ __launch_bounds__(kBlock) void k_add_l1(const float *__restrict__ Tgt
             for (int w = 0; w < kBlock / 64; ++w) tot += red[w][threadIdx.x];
             atomicAdd(loss_sum + threadIdx.x, tot);
         }
+    }
+}
+
+// ---- ADD-S and the cloud diameter: the N^2 kernel -----------------------------------------------------------------------------------
+// ADDS_b = (1/N) sum_i min_j |x_i - y_j|,  x = T_gt p (outer cloud), y = T_pred p (inner cloud);  diam_b = max_ij |p_i - p_j|.
+// One work item = kBlock * U outer points of one cloud (a cloud is split over workgroups when B is small); a lane keeps U outer points
+// in registers.  The inner cloud goes through LDS in tiles of kAddsTile float4 (posed once per work item by the same pose_point as the
+// outer points), and every lane reads the same float4 per step -- one ds_read_b128 broadcast feeds U pairs.  A tile's tail is padded
+// to the unroll with copies of its last point: a copy never beats the original (strict <, the minimum and the maximum are unchanged).
+// The per-point result sqrt(best) goes to point_dist (B,N); k_add_s_rows finishes the rows in a fixed order.  No atomics anywhere.
+constexpr int kAddsTile = 1024;         // 16 KB of LDS per workgroup
+constexpr int kAddsUnroll = 8;
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) f32x4 lds_f32x4;
+template <bool WANT_INDEX, bool DIAMETER, int U>
+__global__ __launch_bounds__(kBlock) void k_add_s(const float *__restrict__ Tgt, const float *__restrict__ Tpred, const float *__restrict__ pts,
+                                                  float *__restrict__ point_dist, int32_t *__restrict__ nearest, int64_t B, int32_t N,
+                                                  int32_t chunks) {
+    __shared__ float4 tile[kAddsTile];
+    const int tid = threadIdx.x;
+    const int64_t items = B * chunks;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t b = item / chunks;
+        const int i_base = static_cast<int>(item - b * chunks) * (kBlock * U);
+        const float *cloud = pts + b * N * 3;
+        float mg[12], mp[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) {                       // wave-uniform: scalar loads
+            mg[k] = DIAMETER ? 0.f : Tgt[b * 16 + k];
+            mp[k] = DIAMETER ? 0.f : Tpred[b * 16 + k];
+        }
+        float x[U], y[U], z[U], best[U];
+        int idx[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = min(i_base + u * kBlock + tid, N - 1);             // a slot beyond the cloud repeats its last point; not stored
+            const float px = cloud[i * 3 + 0], py = cloud[i * 3 + 1], pz = cloud[i * 3 + 2];
+            if (DIAMETER) { x[u] = px; y[u] = py; z[u] = pz; }
+            else so3::pose_point(mg, px, py, pz, x[u], y[u], z[u]);
+            best[u] = DIAMETER ? 0.f : __builtin_huge_valf();
+            idx[u] = 0;
+        }
+        for (int t0 = 0; t0 < N; t0 += kAddsTile) {
+            const int cnt = min(kAddsTile, N - t0);
+            const int cntp = (cnt + kAddsUnroll - 1) / kAddsUnroll * kAddsUnroll;      // <= kAddsTile
+            __syncthreads();                                                         // the previous tile has been read
+            for (int k = tid; k < cntp; k += kBlock) {
+                const int j = t0 + min(k, cnt - 1);
+                const float px = cloud[j * 3 + 0], py = cloud[j * 3 + 1], pz = cloud[j * 3 + 2];
+                float4 q;
+                if (DIAMETER) { q.x = px; q.y = py; q.z = pz; }
+                else so3::pose_point(mp, px, py, pz, q.x, q.y, q.z);
+                q.w = 0.f;
+                tile[k] = q;
+            }
+            __syncthreads();
+            for (int k = 0; k < cntp; k += kAddsUnroll) {
+#pragma unroll
+                for (int kk = 0; kk < kAddsUnroll; ++kk) {
+                    // the same address in every lane: a broadcast.  Volatile keeps the unused fourth dword in the load: one ds_read_b128
+                    // (4 LDS cycles) where the compiler would pick ds_read_b96 (8), which the one-point-per-lane variant cannot hide
+                    const f32x4 q = *(const volatile lds_f32x4 *)(&tile[k + kk]);
+#pragma unroll
+                    for (int u = 0; u < U; ++u)
+                        so3::add_s_pair<WANT_INDEX, DIAMETER>(x[u], y[u], z[u], q.x, q.y, q.z, t0 + k + kk, best[u], idx[u]);
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = i_base + u * kBlock + tid;
+            if (i < N) {
+                point_dist[b * N + i] = so3::hw::sqrt(best[u]);
+                if (WANT_INDEX) nearest[b * N + i] = min(idx[u], N - 1);
+            }
+        }
+    }
+}
+
+// The rows of k_add_s's (B,N) result, one wave per sample at a time, in a fixed order: lane-strided float64 partial sums (or float
+// maxima), a butterfly, out[b] = float(sum / N) (or the maximum).  With ONE workgroup it also leaves sum_b out[b] in total[0].
+template <bool MAX>
+__global__ __launch_bounds__(kBlock) void k_add_s_rows(const float *__restrict__ work, float *__restrict__ out, double *__restrict__ total,
+                                                       int64_t B, int32_t N) {
+    __shared__ double red[4];
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = static_cast<int64_t>(blockIdx.x) * (kBlock / 64) + (threadIdx.x >> 6);
+    const int64_t nwaves = static_cast<int64_t>(gridDim.x) * (kBlock / 64);
+    double mine = 0.0;
+    for (int64_t b = wave; b < B; b += nwaves) {
+        const float *row = work + b * N;
+        float r;
+        if (MAX) {
+            float m = 0.f;
+            for (int i = lane; i < N; i += 64) m = fmaxf(m, row[i]);
+            r = wave_allmax(m);
+        } else {
+            double acc = 0.0;
+            for (int i = lane; i < N; i += 64) acc += static_cast<double>(row[i]);
+            r = static_cast<float>(wave_sum(acc) / static_cast<double>(N));          // the butterfly leaves the same bits in every lane
+        }
+        if (out != nullptr && lane == 0) out[b] = r;
+        mine += static_cast<double>(r);
+    }
+    if (total != nullptr) {                    // gridDim.x == 1
+        const double t = block_sum(lane == 0 ? mine : 0.0, red);
+        if (threadIdx.x == 0) total[0] = t;
+    }
+}
+
+// sum_b v[b] in float64 by one workgroup, in a fixed order
+__global__ __launch_bounds__(kBlock) void k_sum_f32_to_f64(const float *__restrict__ v, double *__restrict__ total, int64_t B) {
+    __shared__ double red[4];
+    double acc = 0.0;
+    for (int64_t b = threadIdx.x; b < B; b += kBlock) acc += static_cast<double>(v[b]);
+    const double t = block_sum(acc, red);
+    if (threadIdx.x == 0) total[0] = t;
+}
+
+// ADD-S backward through the stored indices: with e_i = x_i - y_nn(i), u_i = e_i / |e_i| (0 where e_i = 0),
+// dL/dR_pred = -k sum_i u_i p_nn(i)^T,  dL/dt_pred = -k sum_i u_i,  k = grad_scale * grad_rows[b] / N.  One pass over (B,N), one wave per
+// sample at a time (the k_add_l1 skeleton); an index outside [0, N) is clamped, so a bad index buffer cannot read out of bounds.
+__global__ __launch_bounds__(kBlock) void k_add_s_bwd(const float *__restrict__ Tgt, const float *__restrict__ Tpred, const float *__restrict__ pts,
+                                                      const int32_t *__restrict__ nearest, const float *__restrict__ grad_rows, float grad_scale,
+                                                      float *__restrict__ dT, int64_t B, int32_t N) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = static_cast<int64_t>(blockIdx.x) * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t nwaves = static_cast<int64_t>(gridDim.x) * (kBlock / 64);
+    for (int64_t b = wave; b < B; b += nwaves) {
+        float mg[12], mp[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) { mg[k] = Tgt[b * 16 + k]; mp[k] = Tpred[b * 16 + k]; }
+        const float *cloud = pts + b * N * 3;
+        const int32_t *nn = nearest + b * N;
+        float acc[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) acc[k] = 0.f;
+        for (int i0 = 0; i0 < N; i0 += 64) {
+            const bool in = i0 + lane < N;
+            const int i = min(i0 + lane, N - 1);
+            const int j = min(max(nn[i], 0), N - 1);
+            float ex, ey, ez, qx, qy, qz;
+            so3::pose_point(mg, cloud[i * 3 + 0], cloud[i * 3 + 1], cloud[i * 3 + 2], ex, ey, ez);
+            const float px = cloud[j * 3 + 0], py = cloud[j * 3 + 1], pz = cloud[j * 3 + 2];
+            so3::pose_point(mp, px, py, pz, qx, qy, qz);
+            ex -= qx; ey -= qy; ez -= qz;
+            const float inv = in ? so3::unit_scale(so3::pair_dist2(ex, ey, ez)) : 0.f;
+            const float ux = ex * inv, uy = ey * inv, uz = ez * inv;
+            acc[0] = fmaf(ux, px, acc[0]); acc[1] = fmaf(ux, py, acc[1]); acc[2] = fmaf(ux, pz, acc[2]); acc[3] += ux;
+            acc[4] = fmaf(uy, px, acc[4]); acc[5] = fmaf(uy, py, acc[5]); acc[6] = fmaf(uy, pz, acc[6]); acc[7] += uy;
+            acc[8] = fmaf(uz, px, acc[8]); acc[9] = fmaf(uz, py, acc[9]); acc[10] = fmaf(uz, pz, acc[10]); acc[11] += uz;
+        }
+        const float k = -grad_scale * (grad_rows != nullptr ? grad_rows[b] : 1.f) / static_cast<float>(N);
+        float mine = 0.f;                                    // lane l < 12 keeps entry l of the top three rows
+#pragma unroll
+        for (int e = 0; e < 12; ++e) {
+            const float tot = wave_allsum(acc[e]);
+            mine = lane == e ? tot : mine;
+        }
+        if (lane < 16) dT[b * 16 + lane] = lane < 12 ? k * mine : 0.f;
     }
 }
 
@@ -2364,7 +2537,7 @@ int frob(const void *M, const float *Rtrue, float *R, void *dM, double *loss_sum
 // C ABI
 // =====================================================================================================
 namespace {
-template <bool DISENT>
+template <bool DISENT, bool L2 = false>
 int launch_add_l1(const float *Tgt, const float *Tpred, const float *points, float *dists, double *loss_sum, float *dTpred,
                   float grad_scale, int64_t B, int32_t N, hipStream_t s, const char *what) {
     if (loss_sum != nullptr) {
@@ -2379,9 +2552,33 @@ int launch_add_l1(const float *Tgt, const float *Tpred, const float *points, flo
     const int64_t blocks = (waves + (kBlock / 64) - 1) / (kBlock / 64);
     const dim3 grid(static_cast<unsigned>(blocks)), block(kBlock);
     const int pw = static_cast<int>(per_wave);
-    if (N > 512) hipLaunchKernelGGL((k_add_l1<DISENT, 16>), grid, block, 0, s, Tgt, Tpred, points, dists, loss_sum, dTpred, grad_scale, B, N, pw);
-    else if (N > 128) hipLaunchKernelGGL((k_add_l1<DISENT, 8>), grid, block, 0, s, Tgt, Tpred, points, dists, loss_sum, dTpred, grad_scale, B, N, pw);
-    else hipLaunchKernelGGL((k_add_l1<DISENT, 2>), grid, block, 0, s, Tgt, Tpred, points, dists, loss_sum, dTpred, grad_scale, B, N, pw);
+    if (N > 512) hipLaunchKernelGGL((k_add_l1<DISENT, 16, L2>), grid, block, 0, s, Tgt, Tpred, points, dists, loss_sum, dTpred, grad_scale, B, N, pw);
+    else if (N > 128) hipLaunchKernelGGL((k_add_l1<DISENT, 8, L2>), grid, block, 0, s, Tgt, Tpred, points, dists, loss_sum, dTpred, grad_scale, B, N, pw);
+    else hipLaunchKernelGGL((k_add_l1<DISENT, 2, L2>), grid, block, 0, s, Tgt, Tpred, points, dists, loss_sum, dTpred, grad_scale, B, N, pw);
+    return check_launch(what);
+}
+
+// k_add_s over B clouds, then its rows: U outer points per lane, fewer when the batch alone would not cover the CUs twice.
+template <bool DIAMETER>
+int launch_add_s(const float *Tgt, const float *Tpred, const float *points, float *point_dist, int32_t *nearest, float *rows, double *total,
+                 int64_t B, int32_t N, hipStream_t s, const char *what) {
+    const int64_t cus = device_cus();
+    int u = 4;
+    while (u > 1 && B * ((N + kBlock * u - 1) / (kBlock * u)) < 2 * cus) u >>= 1;
+    const int32_t chunks = (N + kBlock * u - 1) / (kBlock * u);
+    const dim3 grid(static_cast<unsigned>(std::min<int64_t>(B * chunks, cus * 64))), block(kBlock);
+#define ADDS(WI, UU) hipLaunchKernelGGL((k_add_s<(WI) && !DIAMETER, DIAMETER, UU>), grid, block, 0, s, Tgt, Tpred, points, point_dist, nearest, B, N, chunks)
+#define ADDS_U(WI) do { if (u == 4) ADDS(WI, 4); else if (u == 2) ADDS(WI, 2); else ADDS(WI, 1); } while (0)
+    if (!DIAMETER && nearest != nullptr) ADDS_U(true); else ADDS_U(false);
+#undef ADDS_U
+#undef ADDS
+    if (rows != nullptr) {
+        const int64_t blocks = std::min<int64_t>((B + kBlock / 64 - 1) / (kBlock / 64), cus * 8);
+        hipLaunchKernelGGL((k_add_s_rows<DIAMETER>), dim3(static_cast<unsigned>(blocks)), block, 0, s, point_dist, rows, static_cast<double *>(nullptr), B, N);
+        if (total != nullptr) hipLaunchKernelGGL(k_sum_f32_to_f64, dim3(1), block, 0, s, rows, total, B);
+    } else if (total != nullptr) {            // no per-sample buffer to go through: one workgroup finishes rows and batch
+        hipLaunchKernelGGL((k_add_s_rows<DIAMETER>), dim3(1), block, 0, s, point_dist, static_cast<float *>(nullptr), total, B, N);
+    }
     return check_launch(what);
 }
 }  // namespace
@@ -2882,6 +3079,47 @@ int so3_add_l1_f32(const float *Tgt, const float *Tpred, const float *points, fl
     SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= 150000000, "so3_add_l1_f32: B/N");
     SO3_CHECK_ARGS(B == 0 || (Tgt != nullptr && Tpred != nullptr && points != nullptr), "so3_add_l1_f32: null pointer");
     return launch_add_l1<false>(Tgt, Tpred, points, dists, loss_sum, dTpred, grad_scale, B, N, static_cast<hipStream_t>(stream), "so3_add_l1_f32");
+}
+
+int so3_add_l2_f32(const float *Tgt, const float *Tpred, const float *points, float *dists, double *loss_sum, float *dTpred,
+                   float grad_scale, int64_t B, int32_t N, void *stream) {
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= 150000000, "so3_add_l2_f32: B/N");
+    SO3_CHECK_ARGS(B == 0 || (Tgt != nullptr && Tpred != nullptr && points != nullptr), "so3_add_l2_f32: null pointer");
+    return launch_add_l1<false, true>(Tgt, Tpred, points, dists, loss_sum, dTpred, grad_scale, B, N, static_cast<hipStream_t>(stream), "so3_add_l2_f32");
+}
+
+int so3_add_s_fwd_f32(const float *Tgt, const float *Tpred, const float *points, float *point_dist, int32_t *nearest, float *dists,
+                      double *loss_sum, int64_t B, int32_t N, void *stream) {
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N, "so3_add_s_fwd_f32: B/N");
+    SO3_CHECK_ARGS(B == 0 || (Tgt != nullptr && Tpred != nullptr && points != nullptr && point_dist != nullptr), "so3_add_s_fwd_f32: null pointer");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (B == 0) {
+        if (loss_sum != nullptr) {
+            const hipError_t e = hipMemsetAsync(loss_sum, 0, sizeof(double), s);
+            if (e != hipSuccess) return fail(static_cast<int>(e), "so3_add_s_fwd_f32");
+        }
+        return 0;
+    }
+    return launch_add_s<false>(Tgt, Tpred, points, point_dist, nearest, dists, loss_sum, B, N, s, "so3_add_s_fwd_f32");
+}
+
+int so3_add_s_bwd_f32(const float *Tgt, const float *Tpred, const float *points, const int32_t *nearest, const float *grad_rows,
+                      float grad_scale, float *dTpred, int64_t B, int32_t N, void *stream) {
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N, "so3_add_s_bwd_f32: B/N");
+    SO3_CHECK_ARGS(B == 0 || (Tgt != nullptr && Tpred != nullptr && points != nullptr && nearest != nullptr && dTpred != nullptr),
+                   "so3_add_s_bwd_f32: null pointer");
+    if (B == 0) return 0;
+    const int64_t blocks = std::min<int64_t>((B + kBlock / 64 - 1) / (kBlock / 64), static_cast<int64_t>(device_cus()) * 8);
+    hipLaunchKernelGGL(k_add_s_bwd, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), Tgt, Tpred, points,
+                       nearest, grad_rows, grad_scale, dTpred, B, N);
+    return check_launch("so3_add_s_bwd_f32");
+}
+
+int so3_cloud_diameter_f32(const float *points, float *work, float *diam, int64_t B, int32_t N, void *stream) {
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N, "so3_cloud_diameter_f32: B/N");
+    SO3_CHECK_ARGS(B == 0 || (points != nullptr && work != nullptr && diam != nullptr), "so3_cloud_diameter_f32: null pointer");
+    if (B == 0) return 0;
+    return launch_add_s<true>(nullptr, nullptr, points, work, nullptr, diam, nullptr, B, N, static_cast<hipStream_t>(stream), "so3_cloud_diameter_f32");
 }
 
 int so3_add_l1_disentangled_f32(const float *Tpred, const float *Tgt, const float *points, double *loss_sum, float *dTpred,

@@ -1444,6 +1444,130 @@ def compute_disentangled_ADD_L1_loss(T_CO_pred: torch.Tensor, T_CO_gt: torch.Ten
 
 
 # --------------------------------------------------------------------------------------------
+# the ADD / ADD-S pose metrics, the ADD-S loss and the model diameter
+# --------------------------------------------------------------------------------------------
+def _add_metric_points(name, t_gt, points):
+    """(N,3) model points are broadcast to the batch (the copy is negligible beside the N^2 work); a ground-truth pose or points
+    that require grad are constants here."""
+    if _wants_grad(t_gt, points):
+        _warn_once(name + "_constants", name + " is differentiable with respect to TCO_pred only: the ground-truth pose and the model "
+                                               "points carry no gradient although one of them requires grad.")
+    if isinstance(points, torch.Tensor) and points.dim() == 2:
+        points = points.unsqueeze(0).expand(len(t_gt), -1, -1)
+    return points
+
+
+class _AddL2(torch.autograd.Function):
+    """compute_ADD_loss and its gradient w.r.t. the predicted pose, one launch (so3_add_l2_f32)."""
+
+    @staticmethod
+    def forward(ctx, t_gt, t_pred, points, use_batch_mean):
+        dev, b, n, tg, tp, pts = _add_l1_args(t_gt, t_pred, points)
+        want_grad = t_pred.requires_grad
+        dt = torch.empty((b, 4, 4), dtype=torch.float32, device=dev) if want_grad else None
+        dists = None if use_batch_mean else torch.empty((b,), dtype=torch.float32, device=dev)
+        loss_sum = torch.empty((1,), dtype=torch.float64, device=dev) if use_batch_mean else None
+        scale = 1.0 / max(b, 1) if use_batch_mean else 1.0
+        with _on_device(dev):
+            _check(_libh().so3_add_l2_f32(_ptr(tg), _ptr(tp), _ptr(pts), _ptr(dists), _ptr(loss_sum), _ptr(dt), scale, b, n,
+                                          _stream(dev)), "so3_add_l2_f32")
+        ctx.dt, ctx.per_sample, ctx.in_dtype = dt, not use_batch_mean, t_pred.dtype
+        if use_batch_mean:
+            return loss_sum.to(torch.float32).mul_(1.0 / max(b, 1)).squeeze(0)
+        return dists
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        if ctx.dt is None:
+            return None, None, None, None
+        g = grad_out.reshape(-1, 1, 1) if ctx.per_sample else grad_out
+        return None, (ctx.dt * g).to(ctx.in_dtype), None, None
+
+
+class _AddS(torch.autograd.Function):
+    """compute_ADD_S_loss: the N^2 forward (so3_add_s_fwd_f32) keeps the argmin indices; the backward is one pass through them
+    (so3_add_s_bwd_f32)."""
+
+    @staticmethod
+    def forward(ctx, t_gt, t_pred, points, use_batch_mean, return_nearest):
+        dev, b, n, tg, tp, pts = _add_l1_args(t_gt, t_pred, points)
+        if n > _lib.ADD_S_MAX_N:
+            raise RuntimeError(f"compute_ADD_S_loss: at most {_lib.ADD_S_MAX_N} points per cloud, got {n}")
+        want_grad = t_pred.requires_grad
+        point_dist = torch.empty((b, n), dtype=torch.float32, device=dev)
+        nearest = torch.empty((b, n), dtype=torch.int32, device=dev) if (want_grad or return_nearest) else None
+        dists = torch.empty((b,), dtype=torch.float32, device=dev)
+        loss_sum = torch.empty((1,), dtype=torch.float64, device=dev) if use_batch_mean else None
+        with _on_device(dev):
+            _check(_libh().so3_add_s_fwd_f32(_ptr(tg), _ptr(tp), _ptr(pts), _ptr(point_dist), _ptr(nearest), _ptr(dists), _ptr(loss_sum),
+                                             b, n, _stream(dev)), "so3_add_s_fwd_f32")
+        if want_grad:
+            ctx.save_for_backward(tg, tp, pts, nearest)
+        ctx.meta = (want_grad, not use_batch_mean, t_pred.dtype, b, n)
+        out = loss_sum.to(torch.float32).mul_(1.0 / max(b, 1)).squeeze(0) if use_batch_mean else dists
+        if return_nearest:
+            ctx.mark_non_differentiable(nearest)
+            return out, nearest
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out, *unused):
+        want_grad, per_sample, in_dtype, b, n = ctx.meta
+        if not want_grad:
+            return None, None, None, None, None
+        tg, tp, pts, nearest = ctx.saved_tensors
+        dev = tp.device
+        g = grad_out.detach().contiguous().float()
+        dt = torch.empty((b, 4, 4), dtype=torch.float32, device=dev)
+        if per_sample:
+            rows = g.reshape(-1)
+        else:                                              # the batch mean: one upstream scalar for every row, kept on the device
+            rows = (g.reshape(1) * (1.0 / max(b, 1))).expand(b).contiguous()
+        with _on_device(dev):
+            _check(_libh().so3_add_s_bwd_f32(_ptr(tg), _ptr(tp), _ptr(pts), _ptr(nearest), _ptr(rows), 1.0, _ptr(dt), b, n,
+                                             _stream(dev)), "so3_add_s_bwd_f32")
+        return None, dt.to(in_dtype), None, None, None
+
+
+def compute_ADD_loss(TCO_gt: torch.Tensor, TCO_pred: torch.Tensor, points: torch.Tensor, use_batch_mean: bool = True) -> torch.Tensor:
+    """The ADD metric: mean over the model points of |T_gt p - T_pred p|_2 (and over the batch; use_batch_mean=False gives (B,)).
+    points: (B,N,3), or (N,3) for one model shared by the batch.  Differentiable w.r.t. TCO_pred."""
+    points = _add_metric_points("compute_ADD_loss", TCO_gt, points)
+    return _AddL2.apply(TCO_gt, TCO_pred, points, bool(use_batch_mean))
+
+
+def compute_ADD_S_loss(TCO_gt: torch.Tensor, TCO_pred: torch.Tensor, points: torch.Tensor, use_batch_mean: bool = True,
+                       return_nearest: bool = False):
+    """The ADD-S metric (PoseCNN / Hinterstoisser convention): mean over the points under the TRUE pose of the distance to the
+    closest point under the ESTIMATED pose -- for symmetric objects, or objects whose symmetry is unknown.  use_batch_mean=False
+    gives the (B,) metric; return_nearest=True also returns the (B,N) int32 argmin indices.  points: (B,N,3) or (N,3).
+    Differentiable w.r.t. TCO_pred through the stored indices (the selected branch's gradient).  N^2 work per cloud, nothing of
+    that size is materialised."""
+    points = _add_metric_points("compute_ADD_S_loss", TCO_gt, points)
+    return _AddS.apply(TCO_gt, TCO_pred, points, bool(use_batch_mean), bool(return_nearest))
+
+
+def cloud_diameter(points: torch.Tensor) -> torch.Tensor:
+    """max_ij |p_i - p_j|_2 per cloud, the scale of the acceptance threshold "ADD(-S) < 0.1 diameter": (B,) float32 for (B,N,3), a
+    0-dim tensor for (N,3).  Not differentiable."""
+    dev = _require_device(points)
+    if _wants_grad(points):
+        _warn_once("cloud_diameter", "cloud_diameter is an evaluation call: its result carries no gradient although the cloud requires grad.")
+    single = points.dim() == 2
+    p = (points.unsqueeze(0) if single else points).detach().contiguous().float()
+    if p.dim() != 3 or p.shape[-1] != 3 or p.shape[1] < 1 or p.shape[1] > _lib.ADD_S_MAX_N:
+        raise RuntimeError(f"cloud_diameter: expected (N, 3) or (B, N, 3) with 1 <= N <= {_lib.ADD_S_MAX_N}, got {tuple(points.shape)}")
+    b, n, _ = p.shape
+    work = torch.empty((b, n), dtype=torch.float32, device=dev)
+    diam = torch.empty((b,), dtype=torch.float32, device=dev)
+    with _on_device(dev):
+        _check(_libh().so3_cloud_diameter_f32(_ptr(p), _ptr(work), _ptr(diam), b, n, _stream(dev)), "so3_cloud_diameter_f32")
+    return diam[0] if single else diam
+
+
+# --------------------------------------------------------------------------------------------
 # next row f3: per-class evaluation statistics
 # --------------------------------------------------------------------------------------------
 STAT_FIELDS = ("count", "mean", "std", "max", "median", "acc30", "acc15", "acc7.5")

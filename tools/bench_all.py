@@ -194,6 +194,7 @@ def main():
     sc = ctypes.c_float(1.0 / b)
     timeit("f6 so3_add_l1_f32 (loss + dTpred)", lambda i: lib.so3_add_l1_f32(p(tg), p(tq), p(pc[i % 2]), None, p(l3), p(dtq), sc, b, npts, st), b * (npts * 12 + 192), iters=10, warm=2)
     timeit("f6 so3_add_l1_disentangled_f32 (loss + dTpred)", lambda i: lib.so3_add_l1_disentangled_f32(p(tq), p(tg), p(pc[i % 2]), p(l3), p(dtq), sc, b, npts, st), b * (npts * 12 + 192), iters=10, warm=2)
+    timeit("ADD so3_add_l2_f32 (loss + dTpred)", lambda i: lib.so3_add_l2_f32(p(tg), p(tq), p(pc[i % 2]), None, p(l3), p(dtq), sc, b, npts, st), b * (npts * 12 + 192), iters=10, warm=2)
     qo = torch.empty(b, npts, 3, device=dev)
     timeit("a7 so3_rotate_clouds_f32", lambda i: lib.so3_rotate_clouds_f32(p(pc[i % 2]), p(rg), p(qo), 0, b, npts, st), b * (npts * 24 + 36), iters=10, warm=2)
     timeit("a7 so3_rotate_clouds_f32 (transposed out)", lambda i: lib.so3_rotate_clouds_f32(p(pc[i % 2]), p(rg), p(qo), 1, b, npts, st), b * (npts * 24 + 36), iters=10, warm=2)
@@ -205,6 +206,18 @@ def main():
            lambda i: lib.so3_rotate_clouds_bwd_f32(p(pc[i % 2]), p(rg), p(qo), p(dpc), p(drg), 1, b, npts, st), b * (36 * npts + 72), iters=10, warm=2)
     del pc, tg, tq, dtq, qo, dpc, drg
     torch.cuda.empty_cache()
+    print("--- ADD-S / diameter: B = 256 clouds of N = 1024 points (N^2 pairs per cloud: compute bound; GB/s = inputs and outputs only) ---")
+    b, npts = 256, 1024
+    pa_ = torch.randn(b, npts, 3, device=dev)
+    tg = torch.eye(4, device=dev).repeat(b, 1, 1).contiguous(); tg[:, :3, :3] = rr.get_sampled_rotation_matrices_by_axisAngle(b, dev)
+    tq = tg.clone(); tq[:, :3, :3] = rr.get_sampled_rotation_matrices_by_axisAngle(b, dev); tq[:, :3, 3] += 0.1 * torch.randn(b, 3, device=dev)
+    pd = torch.empty(b, npts, device=dev); nn = torch.empty(b, npts, dtype=torch.int32, device=dev); ds = torch.empty(b, device=dev)
+    dtq = torch.empty(b, 16, device=dev); l1 = torch.empty(1, dtype=torch.float64, device=dev)
+    timeit("ADD-S so3_add_s_fwd_f32 (rows)", lambda i: lib.so3_add_s_fwd_f32(p(tg), p(tq), p(pa_), p(pd), None, p(ds), None, b, npts, st), b * (npts * 20 + 132))
+    timeit("ADD-S so3_add_s_fwd_f32 (rows + nearest + loss_sum)", lambda i: lib.so3_add_s_fwd_f32(p(tg), p(tq), p(pa_), p(pd), p(nn), p(ds), p(l1), b, npts, st), b * (npts * 24 + 132))
+    timeit("ADD-S so3_add_s_bwd_f32", lambda i: lib.so3_add_s_bwd_f32(p(tg), p(tq), p(pa_), p(nn), p(ds), ctypes.c_float(1.0), p(dtq), b, npts, st), b * (npts * 28 + 192))
+    timeit("diameter so3_cloud_diameter_f32", lambda i: lib.so3_cloud_diameter_f32(p(pa_), p(pd), p(ds), b, npts, st), b * (npts * 20 + 4))
+    del pa_, tg, tq, pd, nn, ds, dtq
     print("--- config #4: B = 512, bf16 storage, fused head + loss + backward ---")
     b = 512
     x4 = torch.randn(b, 9, device=dev).bfloat16(); r4 = torch.empty(b, 9, device=dev); d4 = torch.empty(b, 9, device=dev, dtype=torch.bfloat16)

@@ -522,7 +522,90 @@ def g18_inverse_maps():
          g=rng.standard_normal((n, 4)).astype(np.float32))
 
 
+def g19_add_metrics():
+    """ADD, ADD-S, per-point distances, nearest indices, diameters and the gradients w.r.t. the estimated pose: float32 inputs, float64
+    answers from tests/add_metrics_ref.py (the reference has no evaluation metric for Iterative/; the definitions are the
+    literature's).  Clouds are normalised to the unit sphere; fixed seeds."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import add_metrics_ref as ref
+    from scipy.spatial.transform import Rotation
+    rng = np.random.default_rng(19)
+
+    def haar(b):
+        return Rotation.random(b, random_state=rng).as_matrix()
+
+    def poses(rot, t):
+        T = np.tile(np.eye(4), (len(rot), 1, 1))
+        T[:, :3, :3], T[:, :3, 3] = rot, t
+        return T.astype(np.float32)
+
+    def unit_sphere(p):                                   # centred on the bounding sphere's proxy (the mean), largest radius 1
+        p = p - p.mean(1, keepdims=True)
+        r = np.linalg.norm(p, axis=-1).max(1)
+        return (p / np.where(r > 0, r, 1.0)[:, None, None]).astype(np.float32)
+
+    def cloud(b, n):
+        return unit_sphere(rng.standard_normal((b, n, 3)))
+
+    def near(T, err):
+        """T with a rotation error of `err` rad about a random axis and a translation error of `err`."""
+        b = len(T)
+        ax = rng.standard_normal((b, 3))
+        ax /= np.linalg.norm(ax, axis=1, keepdims=True)
+        dt = rng.standard_normal((b, 3))
+        dt *= err / np.linalg.norm(dt, axis=1, keepdims=True)
+        rot = Rotation.from_rotvec(ax * err).as_matrix() @ T[:, :3, :3].astype(np.float64)
+        return poses(rot, T[:, :3, 3].astype(np.float64) + dt)
+
+    plan = []                                             # (family, n, tgt, tpred, pts)
+    tr = lambda b: rng.standard_normal((b, 3)) * 0.3 + np.array([0.0, 0.0, 2.0])
+    for n in ref.SIZES:
+        t = tr(2)                                         # Haar rotations; the translations differ a little (not at N = 1: ADD-S <= diameter = 0)
+        plan.append(("haar", n, poses(haar(2), t), poses(haar(2), t + (0.05 * rng.standard_normal((2, 3)) if n > 1 else 0.0)), cloud(2, n)))
+    for n in (64, 256, 1000):
+        tg = poses(haar(1), tr(1))
+        plan.append(("small_error", n, tg, near(tg, 1e-3), cloud(1, n)))
+    for n in (1, 3, 100, 256):
+        tg = poses(haar(1), tr(1))
+        plan.append(("identical", n, tg, tg.copy(), cloud(1, n)))
+    half_turn = np.diag([-1.0, -1.0, 1.0])
+    for n in (64, 100, 256):                              # p and (-x, -y, z): an exact 2-fold symmetry in float32
+        h = rng.standard_normal((1, n // 2, 3))
+        h[..., 2] -= h[..., 2].mean()
+        h = (h / np.linalg.norm(h, axis=-1).max()).astype(np.float32)
+        pts = np.concatenate([h, h * np.array([-1, -1, 1], np.float32)], 1)
+        tg = poses(haar(1), tr(1))
+        tp = poses(tg[:, :3, :3].astype(np.float64) @ half_turn, tg[:, :3, 3].astype(np.float64))     # exact: sign flips of two columns
+        plan.append(("twofold", n, tg, tp, pts))
+    for n in (3, 100):
+        d = rng.standard_normal(3)
+        pts = unit_sphere(rng.standard_normal((1, n, 1)) * (d / np.linalg.norm(d)))
+        plan.append(("collinear", n, poses(haar(1), tr(1)), poses(haar(1), tr(1)), pts))
+    for n in (64, 100):
+        pts = cloud(1, n)
+        pts[:, n // 2:] = pts[:, :n - n // 2]              # every point of the first half appears twice
+        tg = poses(haar(1), tr(1))
+        plan.append(("duplicated", n, tg, near(tg, 0.05), pts))
+
+    out = {k: [] for k in ref.PER_CLOUD + ref.PER_POINT}
+    fam, ns, bs = [], [], []
+    for family, n, tg, tp, pts in plan:
+        assert pts.shape[1] == n and pts.dtype == np.float32 and np.linalg.norm(pts, axis=-1).max() <= 1 + 1e-6
+        ans = ref.answers(tg, tp, pts)
+        ans.update(tgt=tg, tpred=tp, pts=pts)
+        for k in ref.PER_CLOUD:
+            out[k].append(ans[k])
+        for k in ref.PER_POINT:
+            out[k].append(ans[k].reshape((-1,) + ans[k].shape[2:]))
+        fam.append(ref.FAMILIES.index(family)); ns.append(n); bs.append(len(tg))
+        print("g19 %-12s N=%4d  ADD %.3e  ADD-S %.3e  diam %.4f" % (family, n, ans["add"][0], ans["adds"][0], ans["diam"][0]))
+    save("g19_add_metrics.npz", family_names=np.array(ref.FAMILIES), case_family=np.array(fam, np.int32), case_n=np.array(ns, np.int32),
+         case_b=np.array(bs, np.int32), **{k: np.concatenate(v) for k, v in out.items()})
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "g19":
+        return g19_add_metrics()
     if len(sys.argv) > 1 and sys.argv[1] == "g18":
         return g18_inverse_maps()
     if len(sys.argv) > 1 and sys.argv[1] == "g17":
@@ -554,6 +637,7 @@ def main():
     g11_add_l1()
     g12_clouds()
     g13_dtype_fidelity()
+    g19_add_metrics()
     # ---- G1: config #1, 256 Gaussian rows ------------------------------------------------------
     torch.manual_seed(0)
     x = torch.randn(256, 9)
