@@ -460,6 +460,38 @@ int so3_kabsch_f32(const float *P, const float *Q, float *R, float *H, int64_t B
 int so3_kabsch_bwd_f32(const float *P, const float *Q, const float *H, const float *gR, const float *gH,
                        float *dP, float *dQ, int64_t B, int32_t N, void *stream);
 
+/* ---- K5c / K5d: rigid_align, the weighted and centred Kabsch giving a pose (added in 210) -------------------
+ * For every cloud b, with weights w_i >= 0 (all ones when w is NULL):
+ *     W = sum w_i,   pbar = sum w_i p_i / W,   qbar = sum w_i q_i / W,
+ *     H = sum w_i (q_i - qbar)(p_i - pbar)^T        (not divided by W: the projection is scale-free)
+ *     R = proj_SO(3)(H),   t = qbar - R pbar        = argmin over (R, t) of sum w_i |R p_i + t - q_i|^2.
+ * W == 0 (all weights zero, or N == 0): pbar = qbar = 0, H = 0, R = I, t = 0, and every gradient is 0; nothing divides
+ * by W unguarded.  Negative weights are undefined and not checked.  NaN in -> NaN out, and a point of weight 0 must
+ * still be finite (0 * Inf is NaN).
+ * One pass over the clouds.  The sums are taken relative to a pivot, the cloud's FIRST point pair (p_0, q_0), whatever
+ * its weight, so that float32 keeps its digits however far from the origin the clouds lie: R is as accurate as for
+ * centred clouds, t to eps * |qbar|.  That assumes the pivot lies within the cloud's extent: padding a cloud with
+ * junk is fine, putting junk far outside the cloud FIRST is not.
+ *   P, Q   in   B*N*3 float32, as for so3_kabsch_f32
+ *   w      in   optional B*N float32
+ *   R, t   out  B*9, B*3 float32
+ *   H      out  optional B*9 float32
+ *   stats  out  optional B*7 float32: pbar (3), qbar (3), W -- what the backward needs besides H and R
+ * so3_rigid_align_bwd_f32: given the forward's H, R and stats, and upstream gradients gR, gt, gH (each optional: zero),
+ * with a_i = p_i - pbar, c_i = q_i - qbar, u = R^T gt:
+ *     dH = K2(H, gR - gt pbar^T) + gH
+ *     dQ_i = w_i dH a_i + (w_i / W) gt,   dP_i = w_i dH^T c_i - (w_i / W) u,   dw_i = c_i^T dH a_i + (gt . c_i - u . a_i) / W.
+ *   dP, dQ out optional B*N*3 float32, dw out optional B*N float32 (NULL: not computed; dQ alone reads only P and w, dP
+ *   alone only Q and w).  w may be NULL (all ones), and dw may still be asked for.  K2's clamp applies where H has a
+ *   vanishing singular-value gap, as for so3_kabsch_bwd_f32.  One launch each, no atomics, no host synchronisation.
+ * Limits as so3_kabsch_f32; R and t (forward), H, R and stats (backward) always, P and Q when N > 0.
+ */
+int so3_rigid_align_f32(const float *P, const float *Q, const float *w, float *R, float *t, float *H, float *stats,
+                        int64_t B, int32_t N, void *stream);
+int so3_rigid_align_bwd_f32(const float *P, const float *Q, const float *w, const float *H, const float *R,
+                            const float *stats, const float *gR, const float *gt, const float *gH, float *dP, float *dQ,
+                            float *dw, int64_t B, int32_t N, void *stream);
+
 /* ---- next row: on-device pair synthesis for Kabsch ------------------------------
  * so3_rotations_axis_angle_f32: the arithmetic of the reference's sampler, point_cloud/prepare.py:21-49
  *   (normalize_vector :12-18, quaternion (cos theta, axis sin theta) -> matrix :27-47), given the random

@@ -1099,4 +1099,90 @@ __device__ __forceinline__ void add_s_pair(float x, float y, float z, float qx, 
 // 1 / |e| for the unit direction u = e / |e|, 0 where e = 0 (d2 = |e|^2 as pair_dist2 gives it)
 __device__ __forceinline__ float unit_scale(float d2) { return d2 > 0.f ? hw::rcp(hw::sqrt(d2)) : 0.f; }
 
+// ---- rigid_align: weighted, centred Kabsch (so3proj.hip: k_rigid_align, k_rigid_align_bwd; tests/host_model/rigid_align.cpp) --------
+// THE PIVOT RULE.  A cloud's sums are taken of coordinates relative to a per-cloud pivot, its FIRST point pair (p_0, q_0), whatever
+// that point's weight:  a_i = p_i - p_0,  c_i = q_i - q_0.  The one-pass centred covariance then cancels as (cloud extent / cloud
+// radius)^2 instead of (distance from the origin / radius)^2, as long as the pivot lies within the cloud's extent -- which holds for
+// any point of it, masked ones included, unless the masked tail is junk far outside (10 x the radius costs two digits of the 7).
+// Sixteen sums per cloud:  s[0] = W = sum w,  s[1..3] = sum w a,  s[4..6] = sum w c,  s[7 + 3r + k] = sum w c_r a_k.
+constexpr int kAlignSums = 16;
+__device__ __forceinline__ void align_accumulate(float w, float ax, float ay, float az, float cx, float cy, float cz, float (&s)[kAlignSums]) {
+    const float wx = w * cx, wy = w * cy, wz = w * cz;
+    s[0] += w;
+    s[1] = __builtin_fmaf(w, ax, s[1]); s[2] = __builtin_fmaf(w, ay, s[2]); s[3] = __builtin_fmaf(w, az, s[3]);
+    s[4] += wx; s[5] += wy; s[6] += wz;
+    s[7] = __builtin_fmaf(wx, ax, s[7]);   s[8] = __builtin_fmaf(wx, ay, s[8]);   s[9] = __builtin_fmaf(wx, az, s[9]);
+    s[10] = __builtin_fmaf(wy, ax, s[10]); s[11] = __builtin_fmaf(wy, ay, s[11]); s[12] = __builtin_fmaf(wy, az, s[12]);
+    s[13] = __builtin_fmaf(wz, ax, s[13]); s[14] = __builtin_fmaf(wz, ay, s[14]); s[15] = __builtin_fmaf(wz, az, s[15]);
+}
+// 1 / W, 0 for W == 0 (an empty or fully masked cloud: centroids 0, H = 0, every gradient 0).  NaN stays NaN.
+__device__ __forceinline__ float align_inv_weight(float W) { return W != 0.f ? hw::rcp(W) : 0.f; }
+// The sixteen sums -> H = sum w c a^T - (sum w c)(sum w a)^T / W (row-major, not divided by W) and stats = (pbar, qbar, W).
+__device__ __forceinline__ void align_finish(const float (&s)[kAlignSums], const float (&p0)[3], const float (&q0)[3], float (&h)[9], float (&stats)[7]) {
+    const float inv = align_inv_weight(s[0]);
+    const float ma[3] = {s[1] * inv, s[2] * inv, s[3] * inv};
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) h[3 * r + k] = __builtin_fmaf(-s[4 + r], ma[k], s[7 + 3 * r + k]);
+    }
+    const bool live = s[0] != 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        stats[k] = live ? p0[k] + ma[k] : 0.f;
+        stats[3 + k] = live ? __builtin_fmaf(s[4 + k], inv, q0[k]) : 0.f;
+    }
+    stats[6] = s[0];
+}
+// t = qbar - R pbar
+__device__ __forceinline__ void align_translation(const float (&r)[9], const float (&stats)[7], float (&t)[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        t[c] = stats[3 + c] - __builtin_fmaf(r[3 * c + 2], stats[2], __builtin_fmaf(r[3 * c + 1], stats[1], r[3 * c] * stats[0]));
+}
+// Backward, per cloud and before K2: the gradient that reaches R, gR' = gR - g_t pbar^T (t = qbar - R pbar depends on R).
+__device__ __forceinline__ void align_rotation_grad(const float (&gt)[3], const float (&stats)[7], float (&g)[9]) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) g[3 * r + k] = __builtin_fmaf(-gt[r], stats[k], g[3 * r + k]);
+    }
+}
+// Backward, per cloud and after K2: the constants of the point loop,  k = (dH (9), pbar, qbar, g_t / W, u / W)  with u = R^T g_t.
+// A cloud of W == 0 gets dH = 0, g_t / W = 0 and u / W = 0: its gradients are 0 by definition.
+constexpr int kAlignBwdConsts = 21;
+__device__ __forceinline__ void align_bwd_consts(const float (&dh)[9], const float (&r)[9], const float (&gt)[3], const float (&stats)[7],
+                                                 float (&k)[kAlignBwdConsts]) {
+    const float inv = align_inv_weight(stats[6]);
+    const bool live = stats[6] != 0.f;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) k[i] = live ? dh[i] : 0.f;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) k[9 + i] = stats[i];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        k[15 + c] = gt[c] * inv;
+        k[18 + c] = __builtin_fmaf(r[6 + c], gt[2], __builtin_fmaf(r[3 + c], gt[1], r[c] * gt[0])) * inv;
+    }
+}
+// Backward, per point, with a = p - pbar, c = q - qbar:
+//     dQ_i = w (dH a + g_t / W),   dP_i = w (dH^T c - u / W),   dw_i = c^T dH a + (g_t . c - u . a) / W.
+__device__ __forceinline__ void align_bwd_dq(const float (&k)[kAlignBwdConsts], float w, float ax, float ay, float az, float &x, float &y, float &z) {
+    x = w * __builtin_fmaf(k[2], az, __builtin_fmaf(k[1], ay, __builtin_fmaf(k[0], ax, k[15])));
+    y = w * __builtin_fmaf(k[5], az, __builtin_fmaf(k[4], ay, __builtin_fmaf(k[3], ax, k[16])));
+    z = w * __builtin_fmaf(k[8], az, __builtin_fmaf(k[7], ay, __builtin_fmaf(k[6], ax, k[17])));
+}
+__device__ __forceinline__ void align_bwd_dp(const float (&k)[kAlignBwdConsts], float w, float cx, float cy, float cz, float &x, float &y, float &z) {
+    x = w * __builtin_fmaf(k[6], cz, __builtin_fmaf(k[3], cy, __builtin_fmaf(k[0], cx, -k[18])));
+    y = w * __builtin_fmaf(k[7], cz, __builtin_fmaf(k[4], cy, __builtin_fmaf(k[1], cx, -k[19])));
+    z = w * __builtin_fmaf(k[8], cz, __builtin_fmaf(k[5], cy, __builtin_fmaf(k[2], cx, -k[20])));
+}
+__device__ __forceinline__ float align_bwd_dw(const float (&k)[kAlignBwdConsts], float ax, float ay, float az, float cx, float cy, float cz) {
+    const float x = __builtin_fmaf(k[2], az, __builtin_fmaf(k[1], ay, __builtin_fmaf(k[0], ax, k[15])));      // dH a + g_t / W
+    const float y = __builtin_fmaf(k[5], az, __builtin_fmaf(k[4], ay, __builtin_fmaf(k[3], ax, k[16])));
+    const float z = __builtin_fmaf(k[8], az, __builtin_fmaf(k[7], ay, __builtin_fmaf(k[6], ax, k[17])));
+    const float ua = __builtin_fmaf(k[20], az, __builtin_fmaf(k[19], ay, k[18] * ax));
+    return __builtin_fmaf(cz, z, __builtin_fmaf(cy, y, __builtin_fmaf(cx, x, -ua)));
+}
+
 }  // namespace so3

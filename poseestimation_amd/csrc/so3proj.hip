@@ -750,6 +750,186 @@ __global__ __launch_bounds__(kBlock) void k_kabsch_bwd(const float *__restrict__
     }
 }
 
+// ---- K5c: rigid_align, the weighted and centred Kabsch giving a pose (R | t) -------------------------------------------
+//     W = sum w_i,  pbar = sum w_i p_i / W,  qbar = sum w_i q_i / W,  H = sum w_i (q_i - qbar)(p_i - pbar)^T,
+//     R = proj(H),  t = qbar - R pbar.
+// k_kabsch's skeleton with a third, coalesced b32 stream for the weights.  ONE pass over the clouds: the sums are taken
+// relative to the cloud's first point pair (so3_device.h: the pivot rule), sixteen of them instead of nine, and
+// align_finish turns them into H and the centroids -- on every lane alike (the sums are wave-uniform after wave_allsum);
+// lane j keeps cloud j's H, centroids and W.  Lanes past the cloud's end read zeros from the descriptor: a zero weight
+// (WEIGHTED), or the index test (unweighted), keeps their pivot-shifted coordinates out of the sums.
+template <bool WEIGHTED>
+__global__ __launch_bounds__(kBlock) void k_rigid_align(const float *__restrict__ P, const float *__restrict__ Q, const float *__restrict__ Wt,
+                                                        float *__restrict__ R, float *__restrict__ T, float *__restrict__ H,
+                                                        float *__restrict__ S, int64_t B, int32_t N, int clouds_per_wave) {
+    const int lane = threadIdx.x & 63;
+    const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t wave = static_cast<int64_t>(blockIdx.x) * (kBlock / 64) + wave_in_block;
+    const int64_t c0 = wave * clouds_per_wave;
+    if (c0 >= B) return;
+    const int nc = static_cast<int>(min<int64_t>(clouds_per_wave, B - c0));
+    float h[9], st[7];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) h[i] = (i & 3) == 0 ? 1.f : 0.f;
+#pragma unroll
+    for (int i = 0; i < 7; ++i) st[i] = 0.f;
+    const unsigned cloud_bytes = static_cast<unsigned>(N) * 12u;
+    for (int j = 0; j < nc; ++j) {
+        const float *pc = P + (c0 + j) * N * 3, *qc = Q + (c0 + j) * N * 3;
+        const so3::rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(pc), 0, cloud_bytes, so3::kRsrcFlags);
+        const so3::rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(qc), 0, cloud_bytes, so3::kRsrcFlags);
+        so3::rsrc_t rw;
+        if (WEIGHTED) rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(Wt) + (c0 + j) * N, 0, static_cast<unsigned>(N) * 4u, so3::kRsrcFlags);
+        float p0[3] = {0.f, 0.f, 0.f}, q0[3] = {0.f, 0.f, 0.f};               // the pivot: wave-uniform addresses
+        if (N > 0) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { p0[k] = pc[k]; q0[k] = qc[k]; }
+        }
+        float acc[so3::kAlignSums];
+#pragma unroll
+        for (int i = 0; i < so3::kAlignSums; ++i) acc[i] = 0.f;
+        for (int i0 = 0; i0 < N; i0 += 64 * kKabschUnroll) {
+            u32x3 pp[kKabschUnroll], qq[kKabschUnroll];
+            float ww[kKabschUnroll];
+#pragma unroll
+            for (int u = 0; u < kKabschUnroll; ++u) {
+                const int i = i0 + 64 * u + lane;
+                pp[u] = __builtin_amdgcn_raw_buffer_load_b96(rp, i * 12, 0, so3::kStreamNt);
+                qq[u] = __builtin_amdgcn_raw_buffer_load_b96(rq, i * 12, 0, so3::kStreamNt);
+                if (WEIGHTED) ww[u] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rw, i * 4, 0, so3::kStreamNt));
+                else ww[u] = i < N ? 1.f : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < kKabschUnroll; ++u)
+                so3::align_accumulate(ww[u], __uint_as_float(pp[u].x) - p0[0], __uint_as_float(pp[u].y) - p0[1], __uint_as_float(pp[u].z) - p0[2],
+                                      __uint_as_float(qq[u].x) - q0[0], __uint_as_float(qq[u].y) - q0[1], __uint_as_float(qq[u].z) - q0[2], acc);
+        }
+#pragma unroll
+        for (int i = 0; i < so3::kAlignSums; ++i) acc[i] = wave_allsum(acc[i]);
+        float hj[9], sj[7];
+        so3::align_finish(acc, p0, q0, hj, sj);
+#pragma unroll
+        for (int i = 0; i < 9; ++i) h[i] = (lane == j) ? hj[i] : h[i];
+#pragma unroll
+        for (int i = 0; i < 7; ++i) st[i] = (lane == j) ? sj[i] : st[i];
+    }
+    const bool active = lane < nc;
+    float r[9], t[3];
+    so3::project_rotation<float>(h, r);
+    so3::align_translation(r, st, t);
+    if (active) {
+        const int64_t c = c0 + lane;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) R[c * 9 + i] = r[i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) T[c * 3 + i] = t[i];
+        if (H != nullptr) {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) H[c * 9 + i] = h[i];
+        }
+        if (S != nullptr) {
+#pragma unroll
+            for (int i = 0; i < 7; ++i) S[c * 7 + i] = st[i];
+        }
+    }
+}
+
+// ---- K5d: rigid_align backward ----------------------------------------------------------------------------------------
+// Given gR, g_t, gH (each may be null).  With a_i = p_i - pbar, c_i = q_i - qbar, u = R^T g_t:
+//     gR' = gR - g_t pbar^T        (t = qbar - R pbar depends on R)
+//     dH  = K2(H, gR') + gH
+//     dQ_i = w_i dH a_i + (w_i / W) g_t,   dP_i = w_i dH^T c_i - (w_i / W) u,   dw_i = c_i^T dH a_i + (g_t . c_i - u . a_i) / W.
+// Why one pass suffices.  H depends on q_i directly, dH_i = w_i (dq_i) a_i^T, and through qbar: -(sum_j w_j a_j)^T-terms,
+// d(qbar) (sum_j w_j a_j)^T -- but sum_j w_j a_j = sum_j w_j p_j - W pbar = 0, and likewise sum_j w_j c_j = 0 kills the
+// pbar-terms; the w_i-derivative of H is c_i a_i^T plus the same two vanishing centroid terms.  What is left of the centroids
+// is t's own dependence: d(qbar)/d(q_i) = w_i / W, d(qbar)/d(w_i) = c_i / W, d(pbar)/d(w_i) = a_i / W, with dL/d(qbar) = g_t
+// and dL/d(pbar) = -R^T g_t = -u.  So every per-point gradient needs only per-cloud constants known before the point loop.
+// k_kabsch_bwd's skeleton: K2 once per lane, the cloud's 21 constants broadcast from its lane, then one stream over the
+// cloud.  dQ alone reads only P (and w), dP alone only Q (and w); dw reads both.  Wt may be null (all ones).
+template <bool WANT_DP, bool WANT_DQ, bool WANT_DW>
+__global__ __launch_bounds__(kBlock) void k_rigid_align_bwd(const float *__restrict__ P, const float *__restrict__ Q, const float *__restrict__ Wt,
+                                                            const float *__restrict__ H, const float *__restrict__ R, const float *__restrict__ S,
+                                                            const float *__restrict__ gR, const float *__restrict__ gT, const float *__restrict__ gH,
+                                                            float *__restrict__ dP, float *__restrict__ dQ, float *__restrict__ dW,
+                                                            int64_t B, int32_t N, int clouds_per_wave) {
+    constexpr bool NEED_P = WANT_DQ || WANT_DW, NEED_Q = WANT_DP || WANT_DW;
+    const int lane = threadIdx.x & 63;
+    const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t wave = static_cast<int64_t>(blockIdx.x) * (kBlock / 64) + wave_in_block;
+    const int64_t c0 = wave * clouds_per_wave;
+    if (c0 >= B) return;
+    const int nc = static_cast<int>(min<int64_t>(clouds_per_wave, B - c0));
+    const bool active = lane < nc;
+    const int64_t c = c0 + lane;
+    float kk[so3::kAlignBwdConsts];
+    {
+        float st[7], r[9], gt[3], dh[9];
+#pragma unroll
+        for (int i = 0; i < 7; ++i) st[i] = active ? S[c * 7 + i] : 0.f;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) { r[i] = active ? R[c * 9 + i] : 0.f; dh[i] = 0.f; }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) gt[i] = (active && gT != nullptr) ? gT[c * 3 + i] : 0.f;
+        if (gR != nullptr || gT != nullptr) {
+            float h[9], g[9];
+#pragma unroll
+            for (int i = 0; i < 9; ++i) {
+                h[i] = active ? H[c * 9 + i] : ((i & 3) == 0 ? 1.f : 0.f);
+                g[i] = (active && gR != nullptr) ? gR[c * 9 + i] : 0.f;
+            }
+            so3::align_rotation_grad(gt, st, g);
+            so3::project_backward_rows<float>(h, g, dh);
+        }
+        if (gH != nullptr) {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) dh[i] += active ? gH[c * 9 + i] : 0.f;
+        }
+        so3::align_bwd_consts(dh, r, gt, st, kk);
+    }
+    const unsigned cloud_bytes = static_cast<unsigned>(N) * 12u;
+    for (int j = 0; j < nc; ++j) {
+        float k[so3::kAlignBwdConsts];
+#pragma unroll
+        for (int i = 0; i < so3::kAlignBwdConsts; ++i) k[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(kk[i]), j));
+        const int64_t base = (c0 + j) * N * 3;
+        so3::rsrc_t rp, rq, rw, rdp, rdq, rdw;
+        if (NEED_P) rp = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(P) + base, 0, cloud_bytes, so3::kRsrcFlags);
+        if (NEED_Q) rq = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(Q) + base, 0, cloud_bytes, so3::kRsrcFlags);
+        if (Wt != nullptr) rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(Wt) + (c0 + j) * N, 0, static_cast<unsigned>(N) * 4u, so3::kRsrcFlags);
+        if (WANT_DP) rdp = __builtin_amdgcn_make_buffer_rsrc(dP + base, 0, cloud_bytes, so3::kRsrcFlags);
+        if (WANT_DQ) rdq = __builtin_amdgcn_make_buffer_rsrc(dQ + base, 0, cloud_bytes, so3::kRsrcFlags);
+        if (WANT_DW) rdw = __builtin_amdgcn_make_buffer_rsrc(dW + (c0 + j) * N, 0, static_cast<unsigned>(N) * 4u, so3::kRsrcFlags);
+        for (int i0 = 0; i0 < N; i0 += 64 * kKabschUnroll) {
+            u32x3 pp[kKabschUnroll], qq[kKabschUnroll];
+            float ww[kKabschUnroll];
+#pragma unroll
+            for (int u = 0; u < kKabschUnroll; ++u) {
+                const int i = i0 + 64 * u + lane;
+                if (NEED_P) pp[u] = __builtin_amdgcn_raw_buffer_load_b96(rp, i * 12, 0, so3::kStreamNt);
+                if (NEED_Q) qq[u] = __builtin_amdgcn_raw_buffer_load_b96(rq, i * 12, 0, so3::kStreamNt);
+                if (WANT_DP || WANT_DQ) ww[u] = Wt != nullptr ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rw, i * 4, 0, so3::kStreamNt)) : 1.f;
+            }
+#pragma unroll
+            for (int u = 0; u < kKabschUnroll; ++u) {
+                const int i = i0 + 64 * u + lane;                  // lanes past the cloud's end: the range check drops the stores
+                float ax = 0.f, ay = 0.f, az = 0.f, cx = 0.f, cy = 0.f, cz = 0.f, x, y, z;
+                if (NEED_P) { ax = __uint_as_float(pp[u].x) - k[9]; ay = __uint_as_float(pp[u].y) - k[10]; az = __uint_as_float(pp[u].z) - k[11]; }
+                if (NEED_Q) { cx = __uint_as_float(qq[u].x) - k[12]; cy = __uint_as_float(qq[u].y) - k[13]; cz = __uint_as_float(qq[u].z) - k[14]; }
+                if (WANT_DQ) {
+                    so3::align_bwd_dq(k, ww[u], ax, ay, az, x, y, z);
+                    __builtin_amdgcn_raw_buffer_store_b96(u32x3{__float_as_uint(x), __float_as_uint(y), __float_as_uint(z)}, rdq, i * 12, 0, so3::kStreamNt);
+                }
+                if (WANT_DP) {
+                    so3::align_bwd_dp(k, ww[u], cx, cy, cz, x, y, z);
+                    __builtin_amdgcn_raw_buffer_store_b96(u32x3{__float_as_uint(x), __float_as_uint(y), __float_as_uint(z)}, rdp, i * 12, 0, so3::kStreamNt);
+                }
+                if (WANT_DW)
+                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(so3::align_bwd_dw(k, ax, ay, az, cx, cy, cz)), rdw, i * 4, 0, so3::kStreamNt);
+            }
+        }
+    }
+}
+
 // ---- next row f4: on-device pair synthesis for Kabsch (point_cloud/prepare.py:21-49, point_cloud/main.py:173-181) --
 // (a) the reference's rotation sampler as a kernel: quaternion (cos t, axis sin t) -> matrix, given the random draws;
 // (b) Kabsch with the second cloud synthesised on the fly, q_i = R_gt p_i + sigma n_i, so only P is read from HBM.
@@ -3291,6 +3471,57 @@ int so3_kabsch_bwd_f32(const float *P, const float *Q, const float *H, const flo
     else if (dP != nullptr) hipLaunchKernelGGL((k_kabsch_bwd<true, false>), grid, block, 0, s, P, Q, H, gR, gH, dP, dQ, B, N, c);
     else hipLaunchKernelGGL((k_kabsch_bwd<false, true>), grid, block, 0, s, P, Q, H, gR, gH, dP, dQ, B, N, c);
     return check_launch("so3_kabsch_bwd_f32");
+}
+
+// k_kabsch's launch shape: enough waves to fill the CUs x 16 waves, at most 64 clouds per wave (one per lane for the SVD)
+static int64_t kabsch_shape(int64_t B, int64_t &cpw) {
+    cpw = B / (static_cast<int64_t>(device_cus()) * 16);
+    if (cpw < 1) cpw = 1;
+    if (cpw > 64) cpw = 64;
+    const int64_t waves = (B + cpw - 1) / cpw;
+    return (waves + (kBlock / 64) - 1) / (kBlock / 64);
+}
+
+int so3_rigid_align_f32(const float *P, const float *Q, const float *w, float *R, float *t, float *H, float *stats, int64_t B, int32_t N,
+                        void *stream) {
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 40) && N >= 0 && N <= 150000000, "so3_rigid_align_f32: B/N");
+    if (B == 0) return 0;
+    SO3_CHECK_ARGS(R != nullptr && t != nullptr && (N == 0 || (P != nullptr && Q != nullptr)), "so3_rigid_align_f32: null pointer");
+    int64_t cpw;
+    const int64_t blocks = kabsch_shape(B, cpw);
+    SO3_CHECK_ARGS(blocks <= 2147483647, "so3_rigid_align_f32: B too large");
+    hipLaunchKernelGGL((w != nullptr ? k_rigid_align<true> : k_rigid_align<false>), dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0,
+                       static_cast<hipStream_t>(stream), P, Q, w, R, t, H, stats, B, N, static_cast<int>(cpw));
+    return check_launch("so3_rigid_align_f32");
+}
+
+int so3_rigid_align_bwd_f32(const float *P, const float *Q, const float *w, const float *H, const float *R, const float *stats,
+                            const float *gR, const float *gt, const float *gH, float *dP, float *dQ, float *dw, int64_t B, int32_t N,
+                            void *stream) {
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 40) && N >= 0 && N <= 150000000, "so3_rigid_align_bwd_f32: B/N");
+    if (B == 0) return 0;
+    SO3_CHECK_ARGS(H != nullptr && R != nullptr && stats != nullptr && (N == 0 || (P != nullptr && Q != nullptr)),
+                   "so3_rigid_align_bwd_f32: null pointer");
+    if (N == 0 || (dP == nullptr && dQ == nullptr && dw == nullptr)) return 0;
+    int64_t cpw;
+    const int64_t blocks = kabsch_shape(B, cpw);
+    SO3_CHECK_ARGS(blocks <= 2147483647, "so3_rigid_align_bwd_f32: B too large");
+    const dim3 grid(static_cast<unsigned>(blocks)), block(kBlock);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int c = static_cast<int>(cpw);
+#define SO3_ALIGN_BWD(DP, DQ, DW) \
+    hipLaunchKernelGGL((k_rigid_align_bwd<DP, DQ, DW>), grid, block, 0, s, P, Q, w, H, R, stats, gR, gt, gH, dP, dQ, dw, B, N, c)
+    switch ((dP != nullptr ? 4 : 0) | (dQ != nullptr ? 2 : 0) | (dw != nullptr ? 1 : 0)) {
+        case 7: SO3_ALIGN_BWD(true, true, true); break;
+        case 6: SO3_ALIGN_BWD(true, true, false); break;
+        case 5: SO3_ALIGN_BWD(true, false, true); break;
+        case 4: SO3_ALIGN_BWD(true, false, false); break;
+        case 3: SO3_ALIGN_BWD(false, true, true); break;
+        case 2: SO3_ALIGN_BWD(false, true, false); break;
+        default: SO3_ALIGN_BWD(false, false, true); break;
+    }
+#undef SO3_ALIGN_BWD
+    return check_launch("so3_rigid_align_bwd_f32");
 }
 
 int so3_rotate_clouds_bwd_f32(const float *P, const float *R, const float *G, float *dP, float *dR, int transposed, int64_t B, int32_t N,

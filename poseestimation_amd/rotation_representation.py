@@ -1182,6 +1182,88 @@ def kabsch_rotation(P: torch.Tensor, Q: torch.Tensor, return_h: bool = False):
 
 
 # --------------------------------------------------------------------------------------------
+# K5c / K5d: rigid_align, the weighted and centred Kabsch giving a pose
+# --------------------------------------------------------------------------------------------
+def _rigid_align_call(P, Q, weights, want_h, want_stats):
+    """K5c on float32 copies: (p, q, w or None, R, t, H or None, stats or None).  The plain call and the graph node run exactly this."""
+    dev = _require_device(P, Q) if weights is None else _require_device(P, Q, weights)
+    if P.dim() != 3 or P.shape[-1] != 3 or P.shape != Q.shape or (weights is not None and weights.shape != P.shape[:2]):
+        raise RuntimeError("rigid_align: expected two (B, N, 3) tensors and weights of None or (B, N), got %s, %s and %s"
+                           % (tuple(P.shape), tuple(Q.shape), None if weights is None else tuple(weights.shape)))
+    p = P.detach().contiguous().float()
+    q = Q.detach().contiguous().float()
+    w = None if weights is None else weights.detach().contiguous().float()
+    b, n, _ = p.shape
+    r = torch.empty((b, 3, 3), dtype=torch.float32, device=dev)
+    t = torch.empty((b, 3), dtype=torch.float32, device=dev)
+    h = torch.empty((b, 3, 3), dtype=torch.float32, device=dev) if want_h else None
+    stats = torch.empty((b, 7), dtype=torch.float32, device=dev) if want_stats else None
+    with _on_device(dev):
+        _check(_libh().so3_rigid_align_f32(_ptr(p), _ptr(q), _ptr(w), _ptr(r), _ptr(t), _ptr(h), _ptr(stats), b, n, _stream(dev)),
+               "so3_rigid_align_f32")
+    return p, q, w, r, t, h, stats
+
+
+class _RigidAlign(torch.autograd.Function):
+    """rigid_align as a graph node.  Forward keeps H, R and the per-cloud (pbar, qbar, W); backward is one launch of K5d
+    (so3_rigid_align_bwd_f32) that writes only the gradients autograd asks for."""
+
+    @staticmethod
+    def forward(ctx, P, Q, weights, return_h):
+        p, q, w, r, t, h, stats = _rigid_align_call(P, Q, weights, True, True)
+        ctx.set_materialize_grads(False)
+        ctx.has_w = w is not None
+        ctx.save_for_backward(p, q, h, r, stats, *((w,) if w is not None else ()))
+        ctx.meta = tuple((x.shape, x.dtype) if x is not None else None for x in (P, Q, weights))
+        return (r, t, h) if return_h else (r, t)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_r, grad_t, grad_h=None):
+        p, q, h, r, stats = ctx.saved_tensors[:5]
+        w = ctx.saved_tensors[5] if ctx.has_w else None
+        need = [ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_w and ctx.needs_input_grad[2]]
+        if (grad_r is None and grad_t is None and grad_h is None) or not any(need):
+            return None, None, None, None
+        dev = p.device
+        b, n, _ = p.shape
+        gr = None if grad_r is None else grad_r.reshape(-1, 9).float().contiguous()
+        gt = None if grad_t is None else grad_t.reshape(-1, 3).float().contiguous()
+        gh = None if grad_h is None else grad_h.reshape(-1, 9).float().contiguous()
+        outs = [torch.empty_like(p) if need[0] else None, torch.empty_like(q) if need[1] else None, torch.empty_like(w) if need[2] else None]
+        with _on_device(dev):
+            _check(_libh().so3_rigid_align_bwd_f32(_ptr(p), _ptr(q), _ptr(w), _ptr(h), _ptr(r), _ptr(stats), _ptr(gr), _ptr(gt), _ptr(gh),
+                                                   _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), b, n, _stream(dev)), "so3_rigid_align_bwd_f32")
+        for i, d in enumerate(outs):
+            if d is not None:
+                shape, dtype = ctx.meta[i]
+                outs[i] = (d if dtype is torch.float32 else d.to(dtype)).view(shape)
+        return outs[0], outs[1], outs[2], None
+
+
+def rigid_align(P: torch.Tensor, Q: torch.Tensor, weights: torch.Tensor = None, return_h: bool = False):
+    """The pose (R, t) that best maps cloud P onto cloud Q: argmin over SO(3) x R^3 of sum_i w_i |R p_i + t - q_i|^2.
+
+    P, Q: (B, N, 3) corresponding points; weights: None (all ones) or (B, N), w_i >= 0 -- confidences, or a 0/1 mask over
+    clouds padded to a common N.  Returns R (B, 3, 3) and t (B, 3) in float32; with return_h=True also the weighted,
+    centred covariance H = sum_i w_i (q_i - qbar)(p_i - pbar)^T (not divided by sum w), R = proj_SO(3)(H), t = qbar - R pbar.
+    One launch (so3_rigid_align_f32) and one pass over the clouds; differentiable in P, Q and weights through R, t and H
+    with one more launch (so3_rigid_align_bwd_f32); gradients come back in each argument's dtype.  No host synchronisation:
+    the call and its backward can be captured in a graph.
+
+    A cloud whose weights are all zero (or N == 0) gets R = I, t = 0, H = 0 and zero gradients.  Negative weights are
+    undefined and NOT checked (a check would cost a synchronisation).  NaN in gives NaN out; points of weight 0 must be
+    finite.  The sums are taken relative to each cloud's first point pair, so the clouds may lie anywhere in space -- as long
+    as that first point lies within the cloud's extent, whatever its weight: pad at the END.  Where H has a vanishing
+    singular-value gap (collinear or coincident points) R is still a rotation and K2's clamp keeps the gradients finite,
+    as kabsch_rotation documents."""
+    if _wants_grad(P, Q) or (weights is not None and _wants_grad(weights)):
+        return _RigidAlign.apply(P, Q, weights, return_h)
+    _, _, _, r, t, h, _ = _rigid_align_call(P, Q, weights, return_h, False)
+    return (r, t, h) if return_h else (r, t)
+
+
+# --------------------------------------------------------------------------------------------
 # row a7: the cloud side of the point-cloud path
 # --------------------------------------------------------------------------------------------
 def _rotate_call(pc, R, transposed):

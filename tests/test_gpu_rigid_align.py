@@ -1,0 +1,371 @@
+"""rigid_align on the GPU: G20 through the Python surface and through the raw C ABI at the bounds of tests/test_rigid_align_host.py
+(4 x the float32 host model's error; see its docstring), exact recovery near and far from the origin, masking, the launch shapes,
+consistency with kabsch_rotation, the plumbing, and the speed conditions against the compositions the feature replaces."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import rigid_align_ref as ref
+import test_rigid_align_host as host
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def dev():
+    from poseestimation_amd import _lib
+    _lib.load()
+    assert torch.cuda.is_available()
+    return torch.device("cuda:0")
+
+
+@pytest.fixture(scope="module")
+def g20_cases():
+    return ref.cases(ref.g20())
+
+
+@pytest.fixture(scope="module")
+def g20_grads(g20_cases):
+    return [ref.case_grads(c) for c in g20_cases]
+
+
+def _d(a, dev):
+    return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+
+
+def _ptr(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def abi_run(c, dev, which=("dP", "dQ", "dw")):
+    """One case through the raw C ABI: the forward with H and stats, then one backward writing the gradients `which` names."""
+    from poseestimation_amd import _lib
+    lib = _lib.load()
+    b, n = c["b"], c["n"]
+    P, Q, w, gR, gt, gH = (_d(c[k], dev) for k in ("P", "Q", "w", "gR", "gt", "gH"))
+    out = {"R": torch.full((b, 3, 3), np.nan, device=dev), "t": torch.full((b, 3), np.nan, device=dev), "H": torch.full((b, 3, 3), np.nan, device=dev),
+           "stats": torch.full((b, 7), np.nan, device=dev)}
+    grads = {"dP": torch.full((b, n, 3), np.nan, device=dev), "dQ": torch.full((b, n, 3), np.nan, device=dev), "dw": torch.full((b, n), np.nan, device=dev)}
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _lib.check(lib.so3_rigid_align_f32(_ptr(P), _ptr(Q), _ptr(w), _ptr(out["R"]), _ptr(out["t"]), _ptr(out["H"]), _ptr(out["stats"]), b, n, st),
+               "so3_rigid_align_f32")
+    _lib.check(lib.so3_rigid_align_bwd_f32(_ptr(P), _ptr(Q), _ptr(w), _ptr(out["H"]), _ptr(out["R"]), _ptr(out["stats"]), _ptr(gR), _ptr(gt), _ptr(gH),
+                                           *[_ptr(grads[k]) if k in which else None for k in ("dP", "dQ", "dw")], b, n, st), "so3_rigid_align_bwd_f32")
+    for k in ("dP", "dQ", "dw"):                       # a gradient that was not asked for is not written
+        if k not in which:
+            assert torch.isnan(grads[k]).all(), k
+    out.update(grads)
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+def surface_run(c, dev, which=("dP", "dQ", "dw")):
+    """One case through rigid_align(..., return_h=True) and autograd, with only the arguments `which` names requiring grad."""
+    import poseestimation_amd as pa
+    P, Q, w, gR, gt, gH = (_d(c[k], dev) for k in ("P", "Q", "w", "gR", "gt", "gH"))
+    args = {"dP": P, "dQ": Q, "dw": w}
+    wanted = [k for k in which if args[k] is not None]
+    for k in wanted:
+        args[k].requires_grad_(True)
+    R, t, H = pa.rigid_align(P, Q, w, return_h=True)
+    assert R.shape == (c["b"], 3, 3) and t.shape == (c["b"], 3) and H.shape == (c["b"], 3, 3) and R.dtype == torch.float32
+    out = {"R": R.detach().cpu().numpy(), "t": t.detach().cpu().numpy(), "H": H.detach().cpu().numpy()}
+    if wanted:
+        grads = torch.autograd.grad((R * gR).sum() + (t * gt).sum() + (H * gH).sum(), [args[k] for k in wanted])
+        out.update({k: g.cpu().numpy() for k, g in zip(wanted, grads)})
+    r2, t2 = pa.rigid_align(P.detach(), Q.detach(), None if w is None else w.detach())      # the plain call: the same kernel, the same bits
+    assert torch.equal(r2, R.detach()) and torch.equal(t2, t.detach())
+    return out, tuple(wanted)
+
+
+# ---- 4. G20 parity ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("which", host.SUBSETS, ids=lambda s: "+".join(s))
+def test_g20_through_the_c_abi(dev, g20_cases, g20_grads, which):
+    host.check_against_g20(g20_cases, g20_grads, lambda c: abi_run(c, dev, which), "abi[%s]" % "+".join(which), which)
+
+
+@pytest.mark.parametrize("which", host.SUBSETS, ids=lambda s: "+".join(s))
+def test_g20_through_the_python_surface(dev, g20_cases, g20_grads, which):
+    bnd = host.bounds()
+    for c, g in zip(g20_cases, g20_grads):
+        got, wanted = surface_run(c, dev, which)
+        f = host.figures(c, got, g, wanted)
+        print("surface[%s] %-10s %-6s N=%4d off %5.1f  " % ("+".join(which), c["family"], c["weights"], c["n"], c["offset"])
+              + "  ".join("%s %.2e" % kv for kv in f.items()))
+        for k, v in f.items():
+            assert v <= bnd[k], (c["family"], c["weights"], c["n"], c["offset"], k, v, bnd[k])
+
+
+# ---- 5. exact recovery --------------------------------------------------------------------------------------------------------
+def _ball(b, n, rng):
+    """Unit-radius clouds; three points are a jittered equilateral triangle in a random plane, so that R stays well determined."""
+    from scipy.spatial.transform import Rotation
+    if n == 3:
+        ang = 2 * np.pi * (np.arange(3) / 3.0)[None] + rng.uniform(-0.2, 0.2, (b, 3))
+        tri = np.stack([np.cos(ang), np.sin(ang), np.zeros_like(ang)], -1) * rng.uniform(0.8, 1.0, (b, 3, 1))
+        return np.einsum("bij,bnj->bni", Rotation.random(b, random_state=rng).as_matrix(), tri)
+    d = rng.standard_normal((b, n, 3))
+    return d / np.linalg.norm(d, axis=-1, keepdims=True) * rng.uniform(0, 1, (b, n, 1)) ** (1 / 3)
+
+
+def _pairs(b, n, offset, seed, sigma=0.0):
+    """float32 (P, Q) with Q = R0 P + t0 (+ noise) formed in float64, and the float64 (R0, t0)."""
+    from scipy.spatial.transform import Rotation
+    rng = np.random.default_rng(seed)
+    P = _ball(b, n, rng) + offset
+    R0 = Rotation.random(b, random_state=rng).as_matrix()
+    t0 = max(offset, 1.0) * rng.uniform(-1, 1, (b, 3))
+    Q = np.einsum("bij,bnj->bni", R0, P) + t0[:, None] + sigma * rng.standard_normal((b, n, 3))
+    return P.astype(np.float32), Q.astype(np.float32), R0, t0
+
+
+@pytest.mark.parametrize("n", [3, 100, 1024])
+@pytest.mark.parametrize("offset", [0.0, 100.0])
+def test_exact_recovery(dev, n, offset):
+    """rigid_align(P, R0 P + t0) = (R0, t0) at B = 64.  The float64 restatement of the same float32 inputs is matched at the SAME
+    bounds centred and 100 units out (the textbook one-pass form misses by 1e-2 there).  Against (R0, t0) itself the bound grows by
+    what rounding Q to float32 did to the exact answer -- |R64 - R0|, measured in float64 from the inputs alone, nothing at offset
+    0 and up to ~1e-5 for three points 170 units out."""
+    import poseestimation_amd as pa
+    b = 64
+    P, Q, R0, t0 = _pairs(b, n, offset, seed=500 + n)
+    R, t = pa.rigid_align(_d(P, dev), _d(Q, dev))
+    R, t = R.cpu().numpy().astype(np.float64), t.cpu().numpy().astype(np.float64)
+    want = ref.answers(P, Q, None)
+    scale = np.maximum(1.0, np.abs(want["stats"][:, :6]).max(1))
+    e_r, e_t = np.abs(R - want["R"]).max(), (np.abs(t - want["t"]).max(1) / scale).max()
+    in_r, in_t = np.abs(want["R"] - R0).max(), (np.abs(want["t"] - t0).max(1) / scale).max()
+    print("recovery N=%d offset %g: vs float64 dR %.2e dt %.2e; input rounding dR %.2e dt %.2e" % (n, offset, e_r, e_t, in_r, in_t))
+    assert e_r <= host.R_TOL and e_t <= host.T_TOL
+    assert np.abs(R - R0).max() <= host.R_TOL + in_r and (np.abs(t - t0).max(1) / scale).max() <= host.T_TOL + in_t
+    if offset == 0.0:
+        assert in_r <= host.R_TOL and in_t <= host.T_TOL          # centred, the inputs' rounding is below the bounds: (R0, t0) itself
+
+
+# ---- 6. masking ---------------------------------------------------------------------------------------------------------------
+def test_masked_tail_equals_the_truncated_call(dev):
+    import poseestimation_amd as pa
+    b, n, keep = 8, 200, 137
+    P, Q, _, _ = _pairs(b, n, 10.0, seed=61, sigma=0.01)
+    rng = np.random.default_rng(62)
+    P[:, keep:] = 10.0 + rng.uniform(-10, 10, (b, n - keep, 3))
+    Q[:, keep:] = rng.uniform(-10, 10, (b, n - keep, 3))
+    w = np.zeros((b, n), np.float32)
+    w[:, :keep] = 1
+    Pd, Qd, wd = _d(P, dev).requires_grad_(True), _d(Q, dev).requires_grad_(True), _d(w, dev).requires_grad_(True)
+    R, t = pa.rigid_align(Pd, Qd, wd)
+    Rt, tt = pa.rigid_align(_d(P[:, :keep], dev), _d(Q[:, :keep], dev))
+    scale = max(1.0, float(np.abs(P[:, :keep]).max()), float(np.abs(Q[:, :keep]).max()))
+    assert (R - Rt).abs().max().item() <= 2 * host.R_TOL and (t - tt).abs().max().item() / scale <= 2 * host.T_TOL      # two results, each within the bound
+    dP, dQ, dw = torch.autograd.grad(R.sum() + t.sum(), [Pd, Qd, wd])
+    assert (dP[:, keep:] == 0).all() and (dQ[:, keep:] == 0).all()
+    assert dP[:, :keep].abs().max() > 0 and torch.isfinite(dw).all()
+
+
+def test_all_zero_weights_and_empty_shapes(dev):
+    import poseestimation_amd as pa
+    eye = torch.eye(3, device=dev)
+    P = torch.randn(5, 70, 3, device=dev, requires_grad=True)
+    Q = torch.randn(5, 70, 3, device=dev, requires_grad=True)
+    w = torch.zeros(5, 70, device=dev, requires_grad=True)
+    R, t, H = pa.rigid_align(P, Q, w, return_h=True)
+    assert (R == eye).all() and (t == 0).all() and (H == 0).all()
+    grads = torch.autograd.grad(R.sum() + t.sum() + H.sum(), [P, Q, w])
+    assert all((g == 0).all() for g in grads)
+    P0 = torch.zeros(4, 0, 3, device=dev, requires_grad=True)                    # N == 0
+    R, t, H = pa.rigid_align(P0, P0.detach(), return_h=True)
+    assert (R == eye).all() and (t == 0).all() and (H == 0).all()
+    (g,) = torch.autograd.grad(R.sum() + t.sum(), [P0])
+    assert g.shape == (4, 0, 3)
+    R, t = pa.rigid_align(torch.zeros(0, 9, 3, device=dev), torch.zeros(0, 9, 3, device=dev), torch.zeros(0, 9, device=dev))      # B == 0
+    assert R.shape == (0, 3, 3) and t.shape == (0, 3)
+    torch.cuda.synchronize()
+    with pytest.raises(RuntimeError, match=r"\(2, 5, 3\).*\(2, 6, 3\)"):
+        pa.rigid_align(torch.zeros(2, 5, 3, device=dev), torch.zeros(2, 6, 3, device=dev))
+    with pytest.raises(RuntimeError, match=r"\(2, 4\)"):
+        pa.rigid_align(torch.zeros(2, 5, 3, device=dev), torch.zeros(2, 5, 3, device=dev), torch.zeros(2, 4, device=dev))
+
+
+# ---- 7. launch shape ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("many", [True, False], ids=["several-clouds-per-wave", "one-cloud"])
+def test_launch_shapes_against_float64(dev, many):
+    """B = 2 * 16 * CUs + 37 at N = 8: two clouds per wave and a ragged last wave; and B = 1."""
+    import poseestimation_amd as pa
+    b = 2 * 16 * torch.cuda.get_device_properties(dev).multi_processor_count + 37 if many else 1
+    P, Q, _, _ = _pairs(b, 8, 10.0, seed=71, sigma=0.01)
+    w = np.random.default_rng(72).uniform(0.05, 1.0, (b, 8)).astype(np.float32)
+    Pd, Qd, wd = _d(P, dev).requires_grad_(True), _d(Q, dev).requires_grad_(True), _d(w, dev).requires_grad_(True)
+    R, t, H = pa.rigid_align(Pd, Qd, wd, return_h=True)
+    g = torch.Generator().manual_seed(73)
+    gR, gt, gH = torch.randn(b, 3, 3, generator=g), torch.randn(b, 3, generator=g), torch.randn(b, 3, 3, generator=g)
+    grads = torch.autograd.grad((R * gR.to(dev)).sum() + (t * gt.to(dev)).sum() + (H * gH.to(dev)).sum(), [Pd, Qd, wd])
+    want = ref.answers(P, Q, w)
+    s = np.linalg.svd(want["H"], compute_uv=False)
+    ok = (s[:, 1] + s[:, 2]) / s[:, 0] >= 0.1                                     # as G20: clouds whose rotation is well determined
+    assert ok.mean() > 0.5
+    scale = np.maximum(1.0, np.abs(want["stats"][:, :6]).max(1))
+    assert np.abs(R.detach().cpu().numpy() - want["R"])[ok].max() <= host.R_TOL
+    assert (np.abs(t.detach().cpu().numpy() - want["t"]).max(1) / scale)[ok].max() <= host.T_TOL
+    hden = np.abs(want["H"]).reshape(b, -1).max(1)
+    assert (np.abs(H.detach().cpu().numpy() - want["H"]).reshape(b, -1).max(1) / hden).max() <= host.H_TOL
+    T = lambda a: torch.as_tensor(a, dtype=torch.float64)
+    for got, ref_g, tol in zip(grads, ref.grads64(T(P), T(Q), T(w), gR.double(), gt.double(), gH.double()), (host.DP_TOL, host.DQ_TOL, host.DW_TOL)):
+        err = (got.cpu().double() - ref_g).abs().reshape(b, -1).amax(1) / ref_g.abs().reshape(b, -1).amax(1).clamp(min=1.0)
+        assert err[torch.from_numpy(ok)].max().item() <= tol
+
+
+# ---- 8. consistency with the existing op ------------------------------------------------------------------------------------------
+def test_agrees_with_kabsch_rotation_on_centred_clouds(dev):
+    import poseestimation_amd as pa
+    P, Q, _, _ = _pairs(32, 300, 5.0, seed=81, sigma=0.01)
+    Pc = (P.astype(np.float64) - P.astype(np.float64).mean(1, keepdims=True)).astype(np.float32)
+    Qc = (Q.astype(np.float64) - Q.astype(np.float64).mean(1, keepdims=True)).astype(np.float32)
+    R, t = pa.rigid_align(_d(Pc, dev), _d(Qc, dev))
+    Rk = pa.kabsch_rotation(_d(Pc, dev), _d(Qc, dev))
+    assert (R - Rk).abs().max().item() <= 2 * host.R_TOL
+    assert t.abs().max().item() <= host.T_TOL
+
+
+# ---- 9. plumbing --------------------------------------------------------------------------------------------------------------
+def test_views_dtypes_and_a_side_stream(dev):
+    import poseestimation_amd as pa
+    P, Q, _, _ = _pairs(6, 130, 0.0, seed=91, sigma=0.01)
+    w = np.random.default_rng(92).uniform(0.05, 1.0, (6, 130)).astype(np.float32)
+    Pd, Qd, wd = _d(P, dev), _d(Q, dev), _d(w, dev)
+    R, t = pa.rigid_align(Pd, Qd, wd)
+    wide = torch.zeros(6, 130, 6, device=dev)
+    wide[..., ::2] = Pd
+    Rv, tv = pa.rigid_align(wide[..., ::2], Qd.transpose(0, 1).contiguous().transpose(0, 1), wd.t().contiguous().t())      # non-contiguous views
+    assert torch.equal(Rv, R) and torch.equal(tv, t)
+    for dtype, tol in ((torch.float64, 0.0), (torch.bfloat16, None)):
+        a, b, c = (x.to(dtype).requires_grad_(True) for x in (Pd, Qd, wd))
+        Rd, td = pa.rigid_align(a, b, c)
+        assert Rd.dtype == torch.float32 and td.dtype == torch.float32
+        grads = torch.autograd.grad(Rd.sum() + td.sum(), [a, b, c])
+        assert all(g.dtype == dtype and g.shape == x.shape and torch.isfinite(g).all() for g, x in zip(grads, (a, b, c)))
+        if tol == 0.0:
+            assert torch.equal(Rd, R) and torch.equal(td, t)                       # float32 values widened: the same float32 math
+        else:                                                                      # bf16: the float32 call on the same (rounded) values
+            R16, t16 = pa.rigid_align(a.detach().float(), b.detach().float(), c.detach().float())
+            assert torch.equal(Rd, R16) and torch.equal(td, t16)
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        a = Pd.clone().requires_grad_(True)
+        Rs, ts = pa.rigid_align(a, Qd, wd)
+        (gs,) = torch.autograd.grad(Rs.sum() + ts.sum(), [a])
+    side.synchronize()
+    a = Pd.clone().requires_grad_(True)
+    Rm, tm = pa.rigid_align(a, Qd, wd)
+    (gm,) = torch.autograd.grad(Rm.sum() + tm.sum(), [a])
+    assert torch.equal(Rs, R) and torch.equal(ts, t) and torch.equal(gs, gm)
+
+
+def test_training_step_through_add_loss(dev):
+    """rigid_align -> compute_ADD_loss on the assembled (B,4,4) pose -> backward: a finite, non-zero gradient reaches the weights."""
+    import poseestimation_amd as pa
+    b, n = 16, 256
+    P, Q, R0, t0 = _pairs(b, n, 2.0, seed=95, sigma=0.02)
+    Pd, Qd = _d(P, dev), _d(Q, dev)
+    logits = torch.randn(b, n, device=dev, requires_grad=True)
+    R, t = pa.rigid_align(Pd, Qd, torch.sigmoid(logits))
+    bottom = torch.tensor([0.0, 0.0, 0.0, 1.0], device=dev).expand(b, 1, 4)
+    T_pred = torch.cat([torch.cat([R, t[:, :, None]], 2), bottom], 1)
+    T_gt = torch.eye(4, device=dev).repeat(b, 1, 1)
+    T_gt[:, :3, :3], T_gt[:, :3, 3] = torch.from_numpy(R0).float().to(dev), torch.from_numpy(t0).float().to(dev)
+    loss = pa.compute_ADD_loss(T_gt, T_pred, Pd)
+    loss.backward()
+    assert torch.isfinite(loss) and loss.item() < 0.05
+    assert torch.isfinite(logits.grad).all() and logits.grad.abs().max().item() > 0
+
+
+def test_forward_and_backward_replay_from_a_graph(dev):
+    import poseestimation_amd as pa
+    P, Q, _, _ = _pairs(40, 100, 10.0, seed=97, sigma=0.01)
+    w = np.random.default_rng(98).uniform(0.05, 1.0, (40, 100)).astype(np.float32)
+    Pd, Qd, wd = _d(P, dev).requires_grad_(True), _d(Q, dev).requires_grad_(True), _d(w, dev).requires_grad_(True)
+
+    def step():
+        R, t, H = pa.rigid_align(Pd, Qd, wd, return_h=True)
+        return (R, t, H) + torch.autograd.grad(R.sum() + (t * t).sum() + H.sum(), [Pd, Qd, wd])
+
+    eager = [x.detach().clone() for x in step()]
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        step()                                                                     # warm-up on the capture stream
+    torch.cuda.current_stream(dev).wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        captured = step()
+    for x in captured:
+        x.detach().zero_()
+    graph.replay()
+    torch.cuda.synchronize()
+    for a, b in zip(eager, captured):
+        assert torch.equal(a, b.detach())
+
+
+# ---- 10. the speed conditions -------------------------------------------------------------------------------------------------
+def _median_ms(fn):
+    for _ in range(5):
+        fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(20):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        times.append(e0.elapsed_time(e1))
+    return float(np.median(times))
+
+
+def test_rigid_align_is_not_slower_than_the_compositions(dev):
+    """B = 4096, N = 1024, HIP events, 5 warm-ups, median of 20, same process.  Unweighted: against centring with torch and
+    kabsch_rotation, the spelling available before rigid_align.  Weighted forward + backward: against the torch-composed weighted chain
+    around kabsch_rotation.  No margin: the compositions move at least four times the bytes."""
+    import poseestimation_amd as pa
+    from conftest import REPORT_LINES
+    b, n = 4096, 1024
+    g = torch.Generator().manual_seed(101)
+    P = (torch.rand(b, n, 3, generator=g) - 0.5).to(dev)
+    rot = torch.tensor([[np.cos(0.7), -np.sin(0.7), 0.0], [np.sin(0.7), np.cos(0.7), 0.0], [0.0, 0.0, 1.0]], dtype=torch.float32, device=dev)
+    Q = P @ rot.t() + 3.0 + 0.01 * torch.randn(b, n, 3, generator=g).to(dev)
+    w = torch.rand(b, n, generator=g).to(dev) + 0.05
+
+    def composed(P, Q):
+        pbar, qbar = P.mean(1), Q.mean(1)
+        R = pa.kabsch_rotation(P - pbar[:, None], Q - qbar[:, None])
+        return R, qbar - torch.einsum("bij,bj->bi", R, pbar)
+
+    def composed_weighted(P, Q, w):
+        W = w.sum(1, keepdim=True)
+        pbar, qbar = (w[:, :, None] * P).sum(1) / W, (w[:, :, None] * Q).sum(1) / W
+        R = pa.kabsch_rotation(P - pbar[:, None], w[:, :, None] * (Q - qbar[:, None]))
+        return R, qbar - torch.einsum("bij,bj->bi", R, pbar)
+
+    with torch.no_grad():
+        ours = _median_ms(lambda: pa.rigid_align(P, Q))
+        theirs = _median_ms(lambda: composed(P, Q))
+        (R, t), (Rc, tc) = pa.rigid_align(P, Q), composed(P, Q)
+    assert (R - Rc).abs().max().item() < 1e-4 and (t - tc).abs().max().item() < 1e-4      # the same quantity (not an accuracy check)
+    line = "rigid_align B=4096 N=1024 unweighted: %.4f ms, mean + centre + kabsch_rotation %.4f ms (x%.1f)" % (ours, theirs, theirs / ours)
+    print(line)
+    REPORT_LINES.append(line)
+
+    Pg, Qg, wg = (x.clone().requires_grad_(True) for x in (P, Q, w))
+
+    def train(fn):
+        R, t = fn(Pg, Qg, wg)
+        torch.autograd.grad(R.sum() + t.sum(), [Pg, Qg, wg])
+
+    ours_w = _median_ms(lambda: train(pa.rigid_align))
+    theirs_w = _median_ms(lambda: train(composed_weighted))
+    line = "rigid_align B=4096 N=1024 weighted forward + backward: %.4f ms, torch-composed chain %.4f ms (x%.1f)" % (ours_w, theirs_w, theirs_w / ours_w)
+    print(line)
+    REPORT_LINES.append(line)
+    assert ours <= theirs, (ours, theirs)
+    assert ours_w <= theirs_w, (ours_w, theirs_w)

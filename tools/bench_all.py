@@ -183,7 +183,20 @@ def main():
            b * (48 * npts + 108), iters=10, warm=2)
     timeit("K5b so3_kabsch_bwd_f32 (dQ only)", lambda i: lib.so3_kabsch_bwd_f32(p(pc[i % 2]), p(qc[i % 2]), p(hk), p(gkr), p(gkh), None, p(dqc), b, npts, st),
            b * (24 * npts + 108), iters=10, warm=2)
-    del hk, gkr, gkh, dqc
+    # K5c / K5d: rigid_align, the weighted and centred Kabsch giving (R, t) -- K5's bytes unweighted, 4/3 of them weighted
+    wk = [torch.rand(b, npts, device=dev) + 0.05 for _ in range(2)]
+    tk, sk, dwk = torch.empty(b, 3, device=dev), torch.empty(b, 7, device=dev), torch.empty(b, npts, device=dev)
+    ra, rab = lib.so3_rigid_align_f32, lib.so3_rigid_align_bwd_f32
+    timeit("K5c so3_rigid_align_f32 (unweighted)", lambda i: ra(p(pc[i % 2]), p(qc[i % 2]), None, p(rk), p(tk), None, None, b, npts, st),
+           b * (2 * npts * 12 + 48), iters=10, warm=2)
+    timeit("K5c so3_rigid_align_f32 (weighted)", lambda i: ra(p(pc[i % 2]), p(qc[i % 2]), p(wk[i % 2]), p(rk), p(tk), None, None, b, npts, st),
+           b * (npts * 28 + 48), iters=10, warm=2)
+    ra(p(pc[0]), p(qc[0]), p(wk[0]), p(rk), p(tk), p(hk), p(sk), b, npts, st)
+    gtk = torch.randn(b, 3, device=dev)
+    timeit("K5d so3_rigid_align_bwd_f32 (dP, dQ and dw)",
+           lambda i: rab(p(pc[0]), p(qc[0]), p(wk[0]), p(hk), p(rk), p(sk), p(gkr), p(gtk), p(gkh), p(dpc), p(dqc), p(dwk), b, npts, st),
+           b * (56 * npts + 196), iters=10, warm=2)
+    del hk, gkr, gkh, dqc, wk, tk, sk, dwk, gtk
     rg = rr.get_sampled_rotation_matrices_by_axisAngle(b, dev).reshape(b, 9).contiguous()
     timeit("f4 so3_kabsch_synth_f32 (sigma=0: P only)", lambda i: lib.so3_kabsch_synth_f32(p(pc[i % 2]), p(rg), ctypes.c_float(0.0), 1, p(rk), None, b, npts, st), b * (npts * 12 + 72), iters=10, warm=2)
     timeit("f4 so3_kabsch_synth_f32 (sigma=0.01, device RNG)", lambda i: lib.so3_kabsch_synth_f32(p(pc[i % 2]), p(rg), ctypes.c_float(0.01), 1, p(rk), None, b, npts, st), b * (npts * 12 + 72), iters=10, warm=2)

@@ -603,7 +603,105 @@ def g19_add_metrics():
          case_b=np.array(bs, np.int32), **{k: np.concatenate(v) for k, v in out.items()})
 
 
+def g20_rigid_align():
+    """rigid_align: float32 clouds, weights and upstream gradients, float64 answers (R, t, H, centroids) from tests/rigid_align_ref.py
+    (the reference has no registration layer: the definition is the weighted Kabsch / Umeyama solution without scale).  Clouds of
+    unit radius, Q = R_gt P + t_gt + sigma * noise with Haar R_gt; fixed seeds.  The per-point gradients are not stored (they
+    would triple the file): both test files compute them from the stored inputs with ref.grads64."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import rigid_align_ref as ref
+    from scipy.spatial.transform import Rotation
+    rng = np.random.default_rng(20)
+
+    def ball(n):                                           # n points in the unit ball
+        d = rng.standard_normal((n, 3))
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        return d * rng.uniform(0, 1, (n, 1)) ** (1 / 3)
+
+    def weights(kind, n):
+        """(w as stored, the number of real points): the mask keeps at least three points, so that R stays unique."""
+        if kind in ("none", "ones"):
+            return np.ones(n), n
+        if kind == "random":
+            return rng.uniform(0.05, 1.0, n), n
+        if kind == "zero":
+            return np.zeros(n), n
+        valid = min(n, max(3, n // 2))
+        return (np.arange(n) < valid).astype(np.float64), valid
+
+    def well_conditioned(p, q, w):
+        """Is the rotation well determined?  (s2 + s3) / s1 >= 0.1 for the float64 H's singular values: a nearly collinear triple
+        is a degenerate cloud in all but name, and its R amplifies any rounding of H by s1 / (s2 + s3)."""
+        h = ref.answers(p[None].astype(np.float32), q[None].astype(np.float32), w[None].astype(np.float32))["H"][0]
+        s = np.linalg.svd(h, compute_uv=False)
+        return s[0] > 0 and (s[1] + s[2]) / s[0] >= 0.1
+
+    def haar_cloud(n, kind, offset, sigma):
+        while True:
+            p, q, w = draw_cloud(n, kind, offset, sigma)
+            if n < 3 or kind == "zero" or well_conditioned(p, q, w):
+                return p, q, w
+
+    def draw_cloud(n, kind, offset, sigma):
+        w, valid = weights(kind, n)
+        p = ball(n) + offset
+        t_gt = max(offset, 1.0) * rng.uniform(-1, 1, 3)
+        q = p @ Rotation.random(random_state=rng).as_matrix().T + t_gt + sigma * rng.standard_normal((n, 3))
+        if valid < n:                                      # the masked tail: finite junk up to 10 x the radius around the clouds
+            p[valid:] = offset + rng.uniform(-10, 10, (n - valid, 3))
+            q[valid:] = q[:valid].mean(0) + rng.uniform(-10, 10, (n - valid, 3))
+        return p, q, w
+
+    plan = []                                              # (family, kind, n, offset, check, [(p, q, w, sigma), ...])
+    for n in ref.SIZES:
+        if n in ref.SMALL_SIZES:
+            combos = [(k, o) for k in ref.WEIGHTS for o in ref.OFFSETS]
+        else:                                              # a covering selection: every kind and every offset at every large size
+            i = ref.SIZES.index(n)
+            combos = [("none", 100.0), ("random", ref.OFFSETS[i % 3]), ("mask", ref.OFFSETS[(i + 1) % 3]), ("ones", ref.OFFSETS[(i + 2) % 3]),
+                      ("zero", 10.0)]
+        for kind, off in combos:
+            sig = ref.SIGMAS if n in ref.SMALL_SIZES else (ref.SIGMAS[(ref.WEIGHTS.index(kind) + n) % 2],)
+            check = ref.ZERO if kind == "zero" else ref.PROPERTIES if n < 3 else ref.FULL
+            plan.append(("haar", kind, n, off, check, [haar_cloud(n, kind, off, s) + (s,) for s in sig]))
+    for n, off in ((64, 0.0), (65, 10.0)):                 # Q = diag(1, 1, -1) P (about the offset): the best R is not the reflection
+        p = ball(n)
+        plan.append(("reflected", "none", n, off, ref.PROPERTIES, [(p + off, p * np.array([1.0, 1.0, -1.0]) + off, np.ones(n), 0.0)]))
+    for n, off in ((3, 0.0), (65, 10.0)):
+        d = rng.standard_normal(3)
+        p = rng.uniform(-1, 1, (n, 1)) * (d / np.linalg.norm(d)) + off
+        q = (p - off) @ Rotation.random(random_state=rng).as_matrix().T + off
+        plan.append(("collinear", "random", n, off, ref.PROPERTIES, [(p, q, rng.uniform(0.05, 1.0, n), 0.0)]))
+    for n, off in ((3, 0.0), (64, 100.0)):
+        p, q = np.tile(ball(1) + off, (n, 1)), np.tile(ball(1) - off, (n, 1))
+        plan.append(("coincident", "none", n, off, ref.PROPERTIES, [(p, q, np.ones(n), 0.0)]))
+
+    out = {k: [] for k in ref.PER_CLOUD + ref.PER_POINT}
+    meta = {k: [] for k in ref.PER_CASE}
+    for family, kind, n, off, check, clouds in plan:
+        b = len(clouds)
+        P = np.stack([c[0] for c in clouds]).astype(np.float32)
+        Q = np.stack([c[1] for c in clouds]).astype(np.float32)
+        w = np.stack([c[2] for c in clouds]).astype(np.float32)
+        ans = ref.answers(P, Q, w)
+        ans.update(P=P, Q=Q, w=w, sigma=np.array([c[3] for c in clouds]), gR=rng.standard_normal((b, 3, 3)).astype(np.float32),
+                   gt=rng.standard_normal((b, 3)).astype(np.float32), gH=rng.standard_normal((b, 3, 3)).astype(np.float32))
+        for k in ref.PER_CLOUD:
+            out[k].append(ans[k])
+        for k in ref.PER_POINT:
+            out[k].append(ans[k].reshape((-1,) + ans[k].shape[2:]))
+        for k, v in zip(ref.PER_CASE, (ref.FAMILIES.index(family), n, b, ref.WEIGHTS.index(kind), off, check)):
+            meta[k].append(v)
+    print("g20: %d cases, %d clouds, %d points" % (len(plan), sum(meta["b"]), sum(len(x) for x in out["P"])))
+    save("g20_rigid_align.npz", family_names=np.array(ref.FAMILIES), weight_names=np.array(ref.WEIGHTS),
+         case_family=np.array(meta["family"], np.int32), case_n=np.array(meta["n"], np.int32), case_b=np.array(meta["b"], np.int32),
+         case_weights=np.array(meta["weights"], np.int32), case_offset=np.array(meta["offset"]), case_check=np.array(meta["check"], np.int32),
+         **{k: np.concatenate(v) for k, v in out.items()})
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "g20":
+        return g20_rigid_align()
     if len(sys.argv) > 1 and sys.argv[1] == "g19":
         return g19_add_metrics()
     if len(sys.argv) > 1 and sys.argv[1] == "g18":
@@ -638,6 +736,7 @@ def main():
     g12_clouds()
     g13_dtype_fidelity()
     g19_add_metrics()
+    g20_rigid_align()
     # ---- G1: config #1, 256 Gaussian rows ------------------------------------------------------
     torch.manual_seed(0)
     x = torch.randn(256, 9)
