@@ -492,6 +492,45 @@ int so3_rigid_align_bwd_f32(const float *P, const float *Q, const float *w, cons
                             const float *stats, const float *gR, const float *gt, const float *gH, float *dP, float *dQ,
                             float *dw, int64_t B, int32_t N, void *stream);
 
+/* ---- nearest neighbours between two clouds, and ICP (iterative closest point) on top of them (added in 210) ----
+ * so3_nearest_f32: for every point x_i of cloud b (N points) the closest of the M points of its target cloud,
+ *     dist[b][i] = min_j |x_i - y_j|_2,   nearest[b][i] = the argmin j (the first of equal candidates).
+ *   X        in   B*N*3 float32
+ *   Y        in   the targets; y_stride = floats between two clouds' targets: 0 for ONE target shared by the batch
+ *                 (M*3 float32), otherwise >= 3*M (B*M*3 float32 packed: 3*M)
+ *   dist     out  B*N float32 (required);  nearest out optional B*N int32
+ *   Distances come from coordinate differences (never |x|^2 + |y|^2 - 2 x.y): a point of X that is also in Y gets exactly 0.
+ * so3_icp_f32: `iterations` ICP iterations from the pose T_init, without early exit.  One iteration from (R_k, t_k):
+ *     x_i = R_k p_i + t_k;   j(i), d_i as so3_nearest_f32(x, Q);   w'_i = w_i * [d_i <= max_distance];
+ *     (R_k+1, t_k+1) = so3_rigid_align_f32's answer for the pairs (p_i, q_j(i)) with weights w' -- from the UNPOSED p_i, so
+ *     the result is an absolute pose and no composition error builds up; the pivot of the sums is (p_0, q_0), the first
+ *     source and the first target point;
+ *     rmse[k][b] = sqrt(sum w' d^2 / sum w'),   inliers[k][b] = #{i : w'_i > 0}   -- both at the pose the iteration started from.
+ *   sum w' == 0 leaves the pose as it was, with rmse 0 and inliers 0.  iterations == 0 returns the initial pose (and, when
+ *   asked for, nearest and dist of a search at that pose).
+ *   P        in   B*N*3 float32, the source clouds;   Q, q_stride: the targets, as Y, y_stride above (M points)
+ *   w        in   optional B*N float32 weights >= 0 (NULL: all ones)
+ *   T_init   in   optional B*12 float32: per cloud the rows (R | t) of the initial pose, [4c .. 4c+2] = row c of R,
+ *                 [4c+3] = t_c (NULL: the identity)
+ *   max_distance  < 0: no trimming
+ *   R, t     out  B*9, B*3 float32: the pose after the last iteration
+ *   rmse     out  optional iterations*B float32;   inliers out optional iterations*B int32
+ *   nearest, dist  out optional B*N int32 / float32: the LAST iteration's search (at the pose that iteration started from)
+ *   workspace     caller-owned, so3_icp_workspace_bytes(B, N) bytes (0 for B or N out of range), 16-byte aligned.  It needs
+ *                 no zero-fill: the call writes every word before it reads it.
+ * An iteration is two launches on the caller's stream; nothing synchronises with the host and nothing uses atomics, so a
+ * call can be captured in a graph and the same inputs give the same bits.  1 <= N, M <= SO3_ADD_S_MAX_N,
+ * 0 <= iterations <= SO3_ICP_MAX_ITERATIONS.  Not differentiable: for gradients call so3_rigid_align_f32 / _bwd_f32 on
+ * the returned correspondences.
+ */
+#define SO3_ICP_MAX_ITERATIONS 1000
+int so3_nearest_f32(const float *X, const float *Y, int64_t y_stride, float *dist, int32_t *nearest, int64_t B, int32_t N,
+                    int32_t M, void *stream);
+size_t so3_icp_workspace_bytes(int64_t B, int32_t N);
+int so3_icp_f32(const float *P, const float *Q, int64_t q_stride, const float *w, const float *T_init, float max_distance,
+                int32_t iterations, float *R, float *t, float *rmse, int32_t *inliers, int32_t *nearest, float *dist,
+                void *workspace, int64_t B, int32_t N, int32_t M, void *stream);
+
 /* ---- next row: on-device pair synthesis for Kabsch ------------------------------
  * so3_rotations_axis_angle_f32: the arithmetic of the reference's sampler, point_cloud/prepare.py:21-49
  *   (normalize_vector :12-18, quaternion (cos theta, axis sin theta) -> matrix :27-47), given the random

@@ -67,6 +67,9 @@ SYMBOLS = {
     "so3_kabsch_bwd_f32": (_INT, [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P]),
     "so3_rigid_align_f32": (_INT, [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P]),
     "so3_rigid_align_bwd_f32": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P]),
+    "so3_nearest_f32": (_INT, [_P, _P, _I64, _P, _P, _I64, _I32, _I32, _P]),
+    "so3_icp_workspace_bytes": (ctypes.c_size_t, [_I64, _I32]),
+    "so3_icp_f32": (_INT, [_P, _P, _I64, _P, _P, ctypes.c_float, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P]),
     "so3_rotate_clouds_bwd_f32": (_INT, [_P, _P, _P, _P, _P, _INT, _I64, _I32, _P]),
     "so3_rotations_axis_angle_f32": (_INT, [_P, _P, _P, _I64, _P]),
     "so3_kabsch_synth_f32": (_INT, [_P, _P, ctypes.c_float, ctypes.c_uint32, _P, _P, _I64, _I32, _P]),

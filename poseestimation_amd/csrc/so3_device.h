@@ -1185,4 +1185,59 @@ __device__ __forceinline__ float align_bwd_dw(const float (&k)[kAlignBwdConsts],
     return __builtin_fmaf(cz, z, __builtin_fmaf(cy, y, __builtin_fmaf(cx, x, -ua)));
 }
 
+// ---- ICP: nearest neighbours between two clouds fused with rigid_align's sums (so3proj.hip: k_icp_step, k_icp_finish;
+// tests/host_model/icp.cpp) ---------------------------------------------------------------------------------------------------------
+// One iteration from the pose m:  x_i = m p_i,  j(i) = argmin_j |x_i - q_j| (add_s_pair: coordinate differences, the first of equal
+// candidates),  w'_i = w_i [d_i <= max_distance],  and the next pose is rigid_align's answer for the pairs (p_i, q_j(i)) with weights w',
+// from the UNPOSED p_i, relative to the pivot (p_0, q_0) = the first source and the first target point.  Besides rigid_align's sixteen
+// sums a work item keeps  s[16] = sum w' d^2  and  s[17] = #{w' > 0}  (a float count: exact below 2^24 points).
+constexpr int kIcpSums = kAlignSums + 2;
+constexpr int kIcpRecord = 20;                   // floats per partial record in the workspace: the sums, padded to five float4
+constexpr int kIcpBlock = 256;                   // lanes per work item (so3proj.hip: kBlock)
+// The points one lane keeps (U in {4, 2, 1}): fewer when the batch alone would not cover the compute units twice.  k_add_s's rule.
+inline int icp_points_per_lane(int64_t B, int32_t N, int64_t cus) {
+    int u = 4;
+    while (u > 1 && B * ((N + kIcpBlock * u - 1) / (kIcpBlock * u)) < 2 * cus) u >>= 1;
+    return u;
+}
+// One source point's share of a work item's sums.  d2 = |x_i - q_j(i)|^2 as the search left it, d its square root; w is 0 for a slot
+// past the cloud's end.  Returns nothing: the trimmed weight only lives here.
+template <bool TRIMMED>
+__device__ __forceinline__ void icp_accumulate(float w, float d2, float d, float max_distance, float ax, float ay, float az, float cx, float cy,
+                                               float cz, float (&s)[kIcpSums]) {
+    if (TRIMMED) w = d <= max_distance ? w : 0.f;
+    float a[kAlignSums];
+#pragma unroll
+    for (int i = 0; i < kAlignSums; ++i) a[i] = s[i];
+    align_accumulate(w, ax, ay, az, cx, cy, cz, a);
+#pragma unroll
+    for (int i = 0; i < kAlignSums; ++i) s[i] = a[i];
+    s[16] = __builtin_fmaf(w, d2, s[16]);
+    s[17] += w > 0.f ? 1.f : 0.f;
+}
+// A cloud's summed record -> the next pose, rmse and the inlier count.  No inlier weight (s[0] == 0): the pose stays as it was, rmse 0.
+// `prev` is the pose the iteration started from, `next` the pose the following step reads (rows of R | t, as pose_point takes them).
+__device__ __forceinline__ void icp_finish(const float (&s)[kIcpSums], const float (&p0)[3], const float (&q0)[3], const float (&prev)[12],
+                                           float (&next)[12], float &rmse, float &inliers) {
+    float a[kAlignSums], h[9], st[7], r[9], t[3];
+#pragma unroll
+    for (int i = 0; i < kAlignSums; ++i) a[i] = s[i];
+    const bool live = s[0] != 0.f;
+    align_finish(a, p0, q0, h, st);
+    if (!live) {                                                // keep the projection away from H = 0: its result is not used
+#pragma unroll
+        for (int i = 0; i < 9; ++i) h[i] = (i & 3) == 0 ? 1.f : 0.f;
+    }
+    project_rotation<float>(h, r);
+    align_translation(r, st, t);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) next[4 * c + k] = live ? r[3 * c + k] : prev[4 * c + k];
+        next[4 * c + 3] = live ? t[c] : prev[4 * c + 3];
+    }
+    rmse = live ? hw::sqrt(s[16] * align_inv_weight(s[0])) : 0.f;
+    inliers = s[17];
+}
+
 }  // namespace so3

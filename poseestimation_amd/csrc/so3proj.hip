@@ -1557,6 +1557,164 @@ __global__ __launch_bounds__(kBlock) void k_add_s_bwd(const float *__restrict__ 
     }
 }
 
+// ---- ICP: nearest neighbours between two clouds, fused with rigid_align's sums ------------------------------------------------------
+// k_icp_step is k_add_s's skeleton over two DIFFERENT clouds: one work item = kBlock * U source points of one cloud, the target cloud
+// (M points, its own or one shared by the batch) goes through LDS raw in tiles of kAddsTile float4, every lane reads the same float4
+// per step.  The source points are posed by the current pose (pose == nullptr: the identity, nothing is multiplied); distances come
+// from coordinate differences.  SUMS = false is nearest_neighbors: dist and nearest are all it writes.  SUMS = true is one ICP
+// iteration's first half: after the search a lane gathers q_j(i) (12 B per point, an L2 hit), trims its weight and adds the point to
+// rigid_align's sixteen pivot-relative sums (of the UNPOSED p_i), sum w' d^2 and the inlier count; wave_allsum, the four waves
+// combined through LDS in wave order, one record per work item to rec[b][chunk][.].  k_icp_finish adds a cloud's records in chunk
+// order and writes the next pose.  No atomics anywhere: the same inputs give the same bits.
+template <bool WEIGHTED, bool TRIMMED, bool SUMS, int U>
+__global__ __launch_bounds__(kBlock) void k_icp_step(const float *__restrict__ P, const float *__restrict__ Q, int64_t q_stride,
+                                                     const float *__restrict__ Wt, const float *__restrict__ pose, float max_distance,
+                                                     float *__restrict__ rec, float *__restrict__ dist, int32_t *__restrict__ nearest,
+                                                     int64_t B, int32_t N, int32_t M, int32_t chunks) {
+    static_assert(kBlock == so3::kIcpBlock, "the host model's chunking");
+    __shared__ float4 tile[kAddsTile];
+    float (*red)[so3::kIcpRecord] = reinterpret_cast<float (*)[so3::kIcpRecord]>(tile);      // the waves' sums reuse the tile once it has been read
+    const int tid = threadIdx.x;
+    const int64_t items = B * chunks;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t b = item / chunks;
+        const int chunk = static_cast<int>(item - b * chunks);
+        const int i_base = chunk * (kBlock * U);
+        const float *src = P + b * N * 3, *tgt = Q + b * q_stride;
+        float m[12];
+        if (pose != nullptr) {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) m[k] = pose[b * 12 + k];          // wave-uniform: scalar loads
+        }
+        float x[U], y[U], z[U], best[U];
+        int idx[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = min(i_base + u * kBlock + tid, N - 1);             // a slot beyond the cloud repeats its last point; weight 0, not stored
+            const float px = src[i * 3 + 0], py = src[i * 3 + 1], pz = src[i * 3 + 2];
+            if (pose != nullptr) so3::pose_point(m, px, py, pz, x[u], y[u], z[u]);
+            else { x[u] = px; y[u] = py; z[u] = pz; }
+            best[u] = __builtin_huge_valf();
+            idx[u] = 0;
+        }
+        for (int t0 = 0; t0 < M; t0 += kAddsTile) {
+            const int cnt = min(kAddsTile, M - t0);
+            const int cntp = (cnt + kAddsUnroll - 1) / kAddsUnroll * kAddsUnroll;      // <= kAddsTile
+            __syncthreads();                                                         // the previous tile (and the waves' sums in it) has been read
+            for (int k = tid; k < cntp; k += kBlock) {
+                const int j = t0 + min(k, cnt - 1);
+                float4 q;
+                q.x = tgt[j * 3 + 0]; q.y = tgt[j * 3 + 1]; q.z = tgt[j * 3 + 2]; q.w = 0.f;
+                tile[k] = q;
+            }
+            __syncthreads();
+            for (int k = 0; k < cntp; k += kAddsUnroll) {
+#pragma unroll
+                for (int kk = 0; kk < kAddsUnroll; ++kk) {
+                    const f32x4 q = *(const volatile lds_f32x4 *)(&tile[k + kk]);     // k_add_s: the ds_read_b128 broadcast
+#pragma unroll
+                    for (int u = 0; u < U; ++u)
+                        so3::add_s_pair<true, false>(x[u], y[u], z[u], q.x, q.y, q.z, t0 + k + kk, best[u], idx[u]);
+                }
+            }
+        }
+        float acc[so3::kIcpSums];
+        float p0[3], q0[3];
+        if (SUMS) {
+#pragma unroll
+            for (int k = 0; k < so3::kIcpSums; ++k) acc[k] = 0.f;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { p0[k] = src[k]; q0[k] = tgt[k]; }             // the pivot: wave-uniform addresses
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = i_base + u * kBlock + tid;
+            const bool in = i < N;
+            const int j = min(idx[u], M - 1);
+            const float d = so3::hw::sqrt(best[u]);
+            if (in) {
+                if (dist != nullptr) dist[b * N + i] = d;
+                if (nearest != nullptr) nearest[b * N + i] = j;
+            }
+            if (SUMS) {
+                const int ic = min(i, N - 1);
+                const float w = in ? (WEIGHTED ? Wt[b * N + ic] : 1.f) : 0.f;
+                so3::icp_accumulate<TRIMMED>(w, best[u], d, max_distance, src[ic * 3 + 0] - p0[0], src[ic * 3 + 1] - p0[1], src[ic * 3 + 2] - p0[2],
+                                             tgt[j * 3 + 0] - q0[0], tgt[j * 3 + 1] - q0[1], tgt[j * 3 + 2] - q0[2], acc);
+            }
+        }
+        if (SUMS) {
+            const int lane = tid & 63, wave = tid >> 6;
+            float mine = 0.f;                                    // lane k < kIcpSums keeps sum k of its wave
+#pragma unroll
+            for (int k = 0; k < so3::kIcpSums; ++k) {
+                const float tot = wave_allsum(acc[k]);
+                mine = lane == k ? tot : mine;
+            }
+            __syncthreads();                                     // every wave has left the last tile
+            if (lane < so3::kIcpRecord) red[wave][lane] = lane < so3::kIcpSums ? mine : 0.f;
+            __syncthreads();
+            if (tid < so3::kIcpRecord) {
+                float v = red[0][tid];
+#pragma unroll
+                for (int wv = 1; wv < kBlock / 64; ++wv) v += red[wv][tid];          // in wave order
+                rec[(b * chunks + chunk) * so3::kIcpRecord + tid] = v;
+            }
+        }
+    }
+}
+
+// One wave per cloud.  Lane k < kIcpRecord adds entry k of the cloud's records in chunk order; the sums are then broadcast and every
+// lane finishes the same cloud (icp_finish: align_finish, the projection, align_translation), lane 0..11 write the next pose.
+// prev == nullptr: the iteration started from the identity.  R, t (the caller's results) are written when given: the last iteration.
+__global__ __launch_bounds__(kBlock) void k_icp_finish(const float *__restrict__ P, const float *__restrict__ Q, int64_t q_stride,
+                                                       const float *__restrict__ rec, const float *__restrict__ prev, float *__restrict__ next,
+                                                       float *__restrict__ R, float *__restrict__ T, float *__restrict__ rmse,
+                                                       int32_t *__restrict__ inliers, int64_t B, int32_t N, int32_t chunks) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = static_cast<int64_t>(blockIdx.x) * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t nwaves = static_cast<int64_t>(gridDim.x) * (kBlock / 64);
+    for (int64_t b = wave; b < B; b += nwaves) {
+        const float *r = rec + b * chunks * so3::kIcpRecord;
+        float v = 0.f;
+        if (lane < so3::kIcpRecord) {
+            for (int c = 0; c < chunks; ++c) v += r[c * so3::kIcpRecord + lane];
+        }
+        float s[so3::kIcpSums], p0[3], q0[3], mp[12], mn[12], e, cnt;
+#pragma unroll
+        for (int k = 0; k < so3::kIcpSums; ++k) s[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k));
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { p0[k] = P[b * N * 3 + k]; q0[k] = Q[b * q_stride + k]; }
+#pragma unroll
+        for (int k = 0; k < 12; ++k) mp[k] = prev != nullptr ? prev[b * 12 + k] : ((k % 5) == 0 ? 1.f : 0.f);
+        so3::icp_finish(s, p0, q0, mp, mn, e, cnt);
+        float out = 0.f;
+#pragma unroll
+        for (int k = 0; k < 12; ++k) out = lane == k ? mn[k] : out;
+        if (lane < 12) {
+            next[b * 12 + lane] = out;
+            if (R != nullptr) {
+                const int c = lane >> 2, k = lane & 3;
+                if (k < 3) R[b * 9 + 3 * c + k] = out; else T[b * 3 + c] = out;
+            }
+        }
+        if (lane == 0) {
+            if (rmse != nullptr) rmse[b] = e;
+            if (inliers != nullptr) inliers[b] = static_cast<int32_t>(cnt);
+        }
+    }
+}
+
+// iterations == 0: the initial pose is the result
+__global__ __launch_bounds__(kBlock) void k_icp_initial_pose(const float *__restrict__ init, float *__restrict__ R, float *__restrict__ T, int64_t B) {
+    const int64_t e = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (e >= B * 12) return;
+    const int64_t b = e / 12;
+    const int k = static_cast<int>(e - b * 12), c = k >> 2, j = k & 3;
+    const float v = init != nullptr ? init[e] : ((k % 5) == 0 ? 1.f : 0.f);
+    if (j < 3) R[b * 9 + 3 * c + j] = v; else T[b * 3 + c] = v;
+}
+
 // ---- float64 head and backward (the reference's functions accept double tensors): the same templates over
 // T = double, one row per thread with plain loads -- a convenience path, not a benchmark configuration.
 // Four fixed sweeps, then sweeps until the wave-wide residual is below 1e-14 (at most six more).
@@ -2761,6 +2919,31 @@ int launch_add_s(const float *Tgt, const float *Tpred, const float *points, floa
     }
     return check_launch(what);
 }
+
+// k_icp_step over B clouds at k_add_s's launch shape.  The instantiation's name goes to so3_last_kernel.
+thread_local char g_icp_kernel[64] = "";
+int32_t icp_chunks(int64_t B, int32_t N, int &u) {
+    u = so3::icp_points_per_lane(B, N, device_cus());
+    return (N + kBlock * u - 1) / (kBlock * u);
+}
+template <bool SUMS>
+void launch_icp_step(const float *P, const float *Q, int64_t q_stride, const float *w, const float *pose, float max_distance, float *rec,
+                     float *dist, int32_t *nearest, int64_t B, int32_t N, int32_t M, int u, int32_t chunks, hipStream_t s) {
+    const dim3 grid(static_cast<unsigned>(std::min<int64_t>(B * chunks, static_cast<int64_t>(device_cus()) * 64))), block(kBlock);
+    const bool weighted = SUMS && w != nullptr, trimmed = SUMS && max_distance >= 0.f;
+    snprintf(g_icp_kernel, sizeof g_icp_kernel, "k_icp_step<%s, %s, %s, %d>", weighted ? "true" : "false", trimmed ? "true" : "false",
+             SUMS ? "true" : "false", u);
+    g_last_kernel = g_icp_kernel;
+#define ICP(WW, TT, UU) hipLaunchKernelGGL((k_icp_step<(WW) && SUMS, (TT) && SUMS, SUMS, UU>), grid, block, 0, s, P, Q, q_stride, w, pose, max_distance, \
+                                           rec, dist, nearest, B, N, M, chunks)
+#define ICP_U(WW, TT) do { if (u == 4) ICP(WW, TT, 4); else if (u == 2) ICP(WW, TT, 2); else ICP(WW, TT, 1); } while (0)
+    if (weighted && trimmed) ICP_U(true, true);
+    else if (weighted) ICP_U(true, false);
+    else if (trimmed) ICP_U(false, true);
+    else ICP_U(false, false);
+#undef ICP_U
+#undef ICP
+}
 }  // namespace
 
 // ---- K4b: the metrics' backward (include/so3proj.h) ------------------------------------------------------------------
@@ -3300,6 +3483,57 @@ int so3_cloud_diameter_f32(const float *points, float *work, float *diam, int64_
     SO3_CHECK_ARGS(B == 0 || (points != nullptr && work != nullptr && diam != nullptr), "so3_cloud_diameter_f32: null pointer");
     if (B == 0) return 0;
     return launch_add_s<true>(nullptr, nullptr, points, work, nullptr, diam, nullptr, B, N, static_cast<hipStream_t>(stream), "so3_cloud_diameter_f32");
+}
+
+int so3_nearest_f32(const float *X, const float *Y, int64_t y_stride, float *dist, int32_t *nearest, int64_t B, int32_t N, int32_t M,
+                    void *stream) {
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && M >= 1 && M <= SO3_ADD_S_MAX_N, "so3_nearest_f32: B/N");
+    if (B == 0) return 0;
+    SO3_CHECK_ARGS(y_stride == 0 || y_stride >= static_cast<int64_t>(M) * 3, "so3_nearest_f32: y_stride");
+    SO3_CHECK_ARGS(X != nullptr && Y != nullptr && dist != nullptr, "so3_nearest_f32: null pointer");
+    int u;
+    const int32_t chunks = icp_chunks(B, N, u);
+    launch_icp_step<false>(X, Y, y_stride, nullptr, nullptr, -1.f, nullptr, dist, nearest, B, N, M, u, chunks, static_cast<hipStream_t>(stream));
+    return check_launch("so3_nearest_f32");
+}
+
+size_t so3_icp_workspace_bytes(int64_t B, int32_t N) {
+    if (B < 0 || B > (INT64_C(1) << 31) || N < 1 || N > SO3_ADD_S_MAX_N) return 0;
+    // two pose buffers and one record per work item at the smallest work item (U = 1), whatever the device
+    return static_cast<size_t>(B) * (2 * 12 + static_cast<size_t>((N + kBlock - 1) / kBlock) * so3::kIcpRecord) * sizeof(float);
+}
+
+int so3_icp_f32(const float *P, const float *Q, int64_t q_stride, const float *w, const float *T_init, float max_distance, int32_t iterations,
+                float *R, float *t, float *rmse, int32_t *inliers, int32_t *nearest, float *dist, void *workspace, int64_t B, int32_t N,
+                int32_t M, void *stream) {
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && M >= 1 && M <= SO3_ADD_S_MAX_N, "so3_icp_f32: B/N");
+    SO3_CHECK_ARGS(iterations >= 0 && iterations <= SO3_ICP_MAX_ITERATIONS, "so3_icp_f32: iterations");
+    if (B == 0) return 0;
+    SO3_CHECK_ARGS(q_stride == 0 || q_stride >= static_cast<int64_t>(M) * 3, "so3_icp_f32: q_stride");
+    SO3_CHECK_ARGS(P != nullptr && Q != nullptr && R != nullptr && t != nullptr && (iterations == 0 || workspace != nullptr), "so3_icp_f32: null pointer");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 block(kBlock);
+    int u;
+    const int32_t chunks = icp_chunks(B, N, u);
+    if (iterations == 0) {
+        hipLaunchKernelGGL(k_icp_initial_pose, dim3(static_cast<unsigned>((B * 12 + kBlock - 1) / kBlock)), block, 0, s, T_init, R, t, B);
+        if (nearest != nullptr || dist != nullptr)           // the search at the initial pose, so that the outputs are defined
+            launch_icp_step<false>(P, Q, q_stride, nullptr, T_init, -1.f, nullptr, dist, nearest, B, N, M, u, chunks, s);
+        return check_launch("so3_icp_f32");
+    }
+    float *poses[2] = {static_cast<float *>(workspace), static_cast<float *>(workspace) + B * 12};
+    float *rec = static_cast<float *>(workspace) + B * 24;
+    const int64_t fin_blocks = std::min<int64_t>((B + kBlock / 64 - 1) / (kBlock / 64), static_cast<int64_t>(device_cus()) * 16);
+    const float *cur = T_init;
+    for (int32_t k = 0; k < iterations; ++k) {
+        const bool last = k + 1 == iterations;
+        float *next = poses[k & 1];
+        launch_icp_step<true>(P, Q, q_stride, w, cur, max_distance, rec, last ? dist : nullptr, last ? nearest : nullptr, B, N, M, u, chunks, s);
+        hipLaunchKernelGGL(k_icp_finish, dim3(static_cast<unsigned>(fin_blocks)), block, 0, s, P, Q, q_stride, rec, cur, next, last ? R : nullptr,
+                           last ? t : nullptr, rmse != nullptr ? rmse + k * B : nullptr, inliers != nullptr ? inliers + k * B : nullptr, B, N, chunks);
+        cur = next;
+    }
+    return check_launch("so3_icp_f32");
 }
 
 int so3_add_l1_disentangled_f32(const float *Tpred, const float *Tgt, const float *points, double *loss_sum, float *dTpred,

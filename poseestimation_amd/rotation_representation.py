@@ -1264,6 +1264,99 @@ def rigid_align(P: torch.Tensor, Q: torch.Tensor, weights: torch.Tensor = None, 
 
 
 # --------------------------------------------------------------------------------------------
+# nearest neighbours between two clouds, and ICP on top of them
+# --------------------------------------------------------------------------------------------
+def _cloud_pair(name, X, Y):
+    """float32 copies of a source (B,N,3) and a target (B,M,3) or shared (M,3), and the target's stride in floats (0: shared)."""
+    dev = _require_device(X, Y)
+    ok = X.dim() == 3 and X.shape[-1] == 3 and Y.dim() in (2, 3) and Y.shape[-1] == 3 and (Y.dim() == 2 or Y.shape[0] == X.shape[0])
+    if not ok or not 1 <= X.shape[1] <= _lib.ADD_S_MAX_N or not 1 <= Y.shape[-2] <= _lib.ADD_S_MAX_N:
+        raise RuntimeError("%s: expected a source (B, N, 3) and a target (B, M, 3) or (M, 3) with 1 <= N, M <= %d, got %s and %s"
+                           % (name, _lib.ADD_S_MAX_N, tuple(X.shape), tuple(Y.shape)))
+    x = X.detach().contiguous().float()
+    y = Y.detach().contiguous().float()
+    m = y.shape[-2]
+    return dev, x, y, (0 if y.dim() == 2 else 3 * m), x.shape[0], x.shape[1], m
+
+
+def nearest_neighbors(X: torch.Tensor, Y: torch.Tensor):
+    """For every point of X its closest point of Y: (dist, idx) with dist (B,N) float32 = min_j |x_i - y_j|_2 and idx (B,N) int64 the
+    argmin (the first of equal candidates).  X: (B,N,3); Y: (B,M,3), or (M,3) for one target shared by the batch.  N and M are
+    independent.  One launch (so3_nearest_f32), N * M arithmetic per cloud and nothing of that size in memory; distances come from
+    coordinate differences, so a point that is in both clouds gets exactly 0.  An evaluation call: not differentiable."""
+    dev, x, y, stride, b, n, m = _cloud_pair("nearest_neighbors", X, Y)
+    if _wants_grad(X, Y):
+        _warn_once("nearest_neighbors", "nearest_neighbors is an evaluation call: dist carries no gradient although an argument requires grad.  "
+                                        "(X - Y.gather(...)).norm() on the returned indices is the differentiable spelling.")
+    dist = torch.empty((b, n), dtype=torch.float32, device=dev)
+    idx = torch.empty((b, n), dtype=torch.int32, device=dev)
+    with _on_device(dev):
+        _check(_libh().so3_nearest_f32(_ptr(x), _ptr(y), stride, _ptr(dist), _ptr(idx), b, n, m, _stream(dev)), "so3_nearest_f32")
+    return dist, idx.long()
+
+
+def icp_align(P: torch.Tensor, Q: torch.Tensor, R_init: torch.Tensor = None, t_init: torch.Tensor = None, iterations: int = 10,
+              max_distance: float = None, weights: torch.Tensor = None, return_info: bool = False):
+    """Point-to-point ICP (iterative closest point): the pose (R, t) that registers the source clouds P onto the target clouds Q when
+    the correspondences are NOT known.  P: (B,N,3); Q: (B,M,3), or (M,3) for one target shared by the batch; N and M are independent.
+    Returns R (B,3,3) and t (B,3) in float32.
+
+    One iteration, from the pose (R_k, t_k): x_i = R_k p_i + t_k; j(i) = the point of Q closest to x_i and d_i its distance;
+    w'_i = w_i * [d_i <= max_distance] (all of w_i when max_distance is None; w_i = 1 when weights is None); (R_k+1, t_k+1) =
+    rigid_align's answer for the pairs (p_i, q_j(i)) with weights w'.  The pose is solved from the unposed p_i every time, so it is
+    an absolute pose and no composition error builds up.  A cloud without inlier weight keeps its pose.
+
+    R_init (B,3,3) and t_init (B,3) give the initial pose (default: the identity).  Exactly `iterations` iterations run, without an
+    early exit -- a converged cloud repeats its fixed point --, so nothing synchronises with the host and the call can be captured
+    in a graph; the same inputs give the same bits.  iterations=0 returns the initial pose.  weights: None or (B,N), w_i >= 0.
+
+    return_info=True also returns a dict: "rmse" (iterations,B) float32 = sqrt(sum w' d^2 / sum w') and "inliers" (iterations,B)
+    int64 = #{w'_i > 0}, both measured at the pose the iteration STARTED from (0 and 0 where there was no inlier), and "nearest"
+    (B,N) int64, "dist" (B,N) float32 of the last iteration's search.
+
+    Not differentiable (the search is piecewise constant).  For gradients, differentiate the last step on the correspondences:
+        R, t, info = icp_align(P, Q, ..., return_info=True)
+        R, t = rigid_align(P, Q.gather(1, info["nearest"][..., None].expand(-1, -1, 3)), w)     # w: weights * (info["dist"] <= max_distance)"""
+    dev, p, q, stride, b, n, m = _cloud_pair("icp_align", P, Q)
+    extra = [x for x in (R_init, t_init, weights) if x is not None]
+    if extra:
+        _require_device(p, *extra)
+    iterations = int(iterations)
+    if iterations < 0:
+        raise RuntimeError("icp_align: iterations must be >= 0, got %d" % iterations)
+    if (R_init is not None and tuple(R_init.shape) != (b, 3, 3)) or (t_init is not None and tuple(t_init.shape) != (b, 3)) or \
+            (weights is not None and tuple(weights.shape) != (b, n)):
+        raise RuntimeError("icp_align: expected R_init (B, 3, 3), t_init (B, 3) and weights (B, N) for B = %d, N = %d, got %s"
+                           % (b, n, [None if x is None else tuple(x.shape) for x in (R_init, t_init, weights)]))
+    if _wants_grad(P, Q, R_init, t_init, weights):
+        _warn_once("icp_align", "icp_align is not differentiable: R and t carry no gradient although an argument requires grad.  Call "
+                                "rigid_align on the returned correspondences (see the docstring) for a differentiable last step.")
+    t0 = None
+    if R_init is not None or t_init is not None:
+        r0 = R_init.detach().float() if R_init is not None else torch.eye(3, dtype=torch.float32, device=dev).expand(b, 3, 3)
+        tt = t_init.detach().float() if t_init is not None else torch.zeros((b, 3), dtype=torch.float32, device=dev)
+        t0 = torch.cat([r0, tt[:, :, None]], 2).contiguous()                       # (B, 3, 4): the rows (R | t)
+    w = None if weights is None else weights.detach().contiguous().float()
+    r = torch.empty((b, 3, 3), dtype=torch.float32, device=dev)
+    t = torch.empty((b, 3), dtype=torch.float32, device=dev)
+    rmse = inl = nearest = dist = None
+    if return_info:
+        rmse = torch.empty((iterations, b), dtype=torch.float32, device=dev)
+        inl = torch.empty((iterations, b), dtype=torch.int32, device=dev)
+        nearest = torch.empty((b, n), dtype=torch.int32, device=dev)
+        dist = torch.empty((b, n), dtype=torch.float32, device=dev)
+    lib = _libh()
+    work = torch.empty((max(int(lib.so3_icp_workspace_bytes(b, n)) // 4, 1),), dtype=torch.float32, device=dev)
+    with _on_device(dev):
+        _check(lib.so3_icp_f32(_ptr(p), _ptr(q), stride, _ptr(w), _ptr(t0), -1.0 if max_distance is None else float(max_distance), iterations,
+                               _ptr(r), _ptr(t), _ptr(rmse), _ptr(inl), _ptr(nearest), _ptr(dist), _ptr(work), b, n, m, _stream(dev)),
+               "so3_icp_f32")
+    if return_info:
+        return r, t, {"rmse": rmse, "inliers": inl.long(), "nearest": nearest.long(), "dist": dist}
+    return r, t
+
+
+# --------------------------------------------------------------------------------------------
 # row a7: the cloud side of the point-cloud path
 # --------------------------------------------------------------------------------------------
 def _rotate_call(pc, R, transposed):

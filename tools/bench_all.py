@@ -197,6 +197,18 @@ def main():
            lambda i: rab(p(pc[0]), p(qc[0]), p(wk[0]), p(hk), p(rk), p(sk), p(gkr), p(gtk), p(gkh), p(dpc), p(dqc), p(dwk), b, npts, st),
            b * (56 * npts + 196), iters=10, warm=2)
     del hk, gkr, gkh, dqc, wk, tk, sk, dwk, gtk
+    # nearest neighbours between two clouds and ICP on top of them: N * M pairs per cloud (compute bound; the bytes are the clouds')
+    bi, ni = 256, 1024
+    xi, yi = torch.rand(bi, ni, 3, device=dev), torch.rand(bi, ni, 3, device=dev)
+    di, nni = torch.empty(bi, ni, device=dev), torch.empty(bi, ni, dtype=torch.int32, device=dev)
+    ri, ti = torch.empty(bi, 9, device=dev), torch.empty(bi, 3, device=dev)
+    wsi = torch.empty(lib.so3_icp_workspace_bytes(bi, ni) // 4, device=dev)
+    timeit("so3_nearest_f32 (256 x 1024 x 1024)", lambda i: lib.so3_nearest_f32(p(xi), p(yi), 3 * ni, p(di), p(nni), bi, ni, ni, st), bi * ni * 32, iters=10, warm=2)
+    for its in (1, 10):
+        timeit("so3_icp_f32 (256 x 1024 x 1024, %d iteration%s)" % (its, "" if its == 1 else "s"),
+               lambda i: lib.so3_icp_f32(p(xi), p(yi), 3 * ni, None, None, ctypes.c_float(-1.0), its, p(ri), p(ti), None, None, None, None, p(wsi), bi, ni, ni, st),
+               its * bi * ni * 24, iters=10, warm=2)
+    del xi, yi, di, nni, ri, ti, wsi
     rg = rr.get_sampled_rotation_matrices_by_axisAngle(b, dev).reshape(b, 9).contiguous()
     timeit("f4 so3_kabsch_synth_f32 (sigma=0: P only)", lambda i: lib.so3_kabsch_synth_f32(p(pc[i % 2]), p(rg), ctypes.c_float(0.0), 1, p(rk), None, b, npts, st), b * (npts * 12 + 72), iters=10, warm=2)
     timeit("f4 so3_kabsch_synth_f32 (sigma=0.01, device RNG)", lambda i: lib.so3_kabsch_synth_f32(p(pc[i % 2]), p(rg), ctypes.c_float(0.01), 1, p(rk), None, b, npts, st), b * (npts * 12 + 72), iters=10, warm=2)

@@ -699,7 +699,188 @@ def g20_rigid_align():
          **{k: np.concatenate(v) for k, v in out.items()})
 
 
+def g21_icp():
+    """nearest_neighbors and icp_align: float32 clouds, initial poses and weights, float64 answers from tests/icp_ref.py (the reference
+    has no registration layer: the definition is brute-force closest points and rigid_align's pose, restated there).  Clouds of unit
+    radius; fixed seeds.  What the generator asserts about its own cases is what the tests rely on: the trimming margin of every
+    trimmed step, exact convergence of the exact cases within 10 float64 iterations, settled correspondences of the noisy ones."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import icp_ref as ref
+    from scipy.spatial.transform import Rotation
+    rng = np.random.default_rng(21)
+
+    def ball(n):
+        d = rng.standard_normal((n, 3))
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        return d * rng.uniform(0, 1, (n, 1)) ** (1 / 3)
+
+    def spaced_ball(n, spacing, quantum=None):
+        """n points of the unit ball, no two closer than `spacing`; with `quantum`, coordinates are integer multiples of it."""
+        pts = []
+        while len(pts) < n:
+            c = ball(1)[0] * 0.98
+            if quantum is not None:
+                c = np.round(c / quantum) * quantum
+            if all(np.linalg.norm(c - o) >= spacing for o in pts):
+                pts.append(c)
+        return np.array(pts)
+
+    def small_motion(deg, shift):
+        axis = rng.standard_normal(3)
+        axis /= np.linalg.norm(axis)
+        d = rng.standard_normal(3)
+        return (Rotation.from_rotvec(axis * np.deg2rad(rng.uniform(0.25 * deg, deg))).as_matrix(),
+                d / np.linalg.norm(d) * rng.uniform(0.25 * shift, shift))
+
+    cases = []
+
+    def add(kind, name, P, Q, w=None, R0=None, t0=None, iterations=0, max_distance=None, weights="none", offset=0.0, check=ref.FULL, **answers):
+        f32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+        cases.append(dict(kind=kind, name=name, P=f32(P), Q=f32(Q), w=f32(w), R0=f32(R0), t0=f32(t0), iterations=iterations,
+                          max_distance=max_distance, weights=weights, offset=offset, check=check, shared=np.ndim(Q) == 2, **answers))
+        return cases[-1]
+
+    # ---- search -------------------------------------------------------------------------------------------------------------
+    for n, m in ref.SIZES:
+        for shared in (False, True):
+            b = 2 if shared or (n, m) in ref.SMALL_SIZES else 1
+            c = add("search", "search %dx%d %s" % (n, m, "shared" if shared else "own"), np.stack([ball(n) for _ in range(b)]),
+                    ball(m) if shared else np.stack([ball(m) for _ in range(b)]))
+            c["dist"], c["nearest"] = ref.nearest64(c["P"], c["Q"])
+    Y = ball(300)
+    Y[150:200] = Y[50:100]                                                    # duplicated target points: the first one is the answer
+    pick = np.concatenate([rng.permutation(300)[:80], np.arange(150, 200, 2), [299, 0]])
+    c = add("search", "subset with duplicates", np.stack([Y[pick], Y[pick[::-1]]]), Y)
+    c["dist"], c["nearest"] = ref.nearest64(c["P"], c["Q"])
+    first = np.where((pick >= 150) & (pick < 200), pick - 100, pick)
+    assert (c["dist"] == 0).all() and (c["nearest"][0] == first).all() and (c["nearest"][1] == first[::-1]).all()
+
+    # ---- single steps ---------------------------------------------------------------------------------------------------------
+    def step_case(n, m, weights, trimmed, offset, axis, shared=False, b=1, empty=False):
+        P, Q, W, R0, T0 = [], [], [], [], []
+        identity = weights == "none" and offset == 0.0 and not trimmed           # these start from the default pose
+        q_shared = ball(m) + offset * np.eye(3)[axis]
+        for _ in range(b):
+            q = q_shared if shared else ball(m) + offset * np.eye(3)[axis]
+            if identity:
+                r_gt, t_gt = small_motion(3.0, 0.03)
+            else:
+                r_gt, t_gt = Rotation.random(random_state=rng).as_matrix(), max(offset, 1.0) * rng.uniform(-1, 1, 3)
+            src = q[rng.permutation(m)[:n]] + 0.03 * rng.standard_normal((n, 3))
+            P.append((src - t_gt) @ r_gt)                                        # p = R_gt^T (q + noise - t_gt)
+            dr, dt = small_motion(3.0, 0.03)
+            R0.append(r_gt @ dr)
+            T0.append(t_gt + dt)
+            W.append(None if weights == "none" else rng.uniform(0.05, 1.0, n) if weights == "random" else (rng.uniform(0, 1, n) < 0.7).astype(np.float64))
+            Q.append(q)
+        c = add("step", "step %dx%d %s %s off %g%s" % (n, m, weights, "trimmed" if trimmed else "all", offset, " shared" if shared else ""),
+                np.stack(P), q_shared if shared else np.stack(Q), None if weights == "none" else np.stack(W),
+                None if identity else np.stack(R0), None if identity else np.stack(T0), iterations=1, weights=weights, offset=offset)
+        R0_, t0_ = (np.broadcast_to(np.eye(3), (b, 3, 3)), np.zeros((b, 3))) if identity else (c["R0"].astype(np.float64), c["t0"].astype(np.float64))
+        d, idx = ref.nearest64(ref.pose_points(c["P"], R0_, t0_), c["Q"])
+        if trimmed or empty:
+            flat = np.sort(d.reshape(-1))
+            md = None
+            if empty:
+                md = 0.5 * flat[0]
+            else:
+                for k in range(max(1, int(0.6 * len(flat))), len(flat)):
+                    if flat[k] - flat[k - 1] > 4 * ref.MARGIN:
+                        md = 0.5 * (flat[k] + flat[k - 1])
+                        break
+                if md is None:
+                    md = flat[-1] + 0.01
+            assert np.abs(d - md).min() > ref.MARGIN and md > ref.MARGIN, (c["name"], md)
+            c["max_distance"] = float(np.float32(md))
+            assert np.abs(d - c["max_distance"]).min() > ref.MARGIN
+        ans = ref.icp64(c["P"], c["Q"], None if identity else c["R0"], None if identity else c["t0"], 1, c["max_distance"], c["w"])
+        s = ref.step_from(c["P"], c["Q"], idx, d, R0_, t0_, c["w"], c["max_distance"])
+        sv = np.linalg.svd(s["H"], compute_uv=False)
+        good = (s["wp"] > 0).sum(1).min() >= 3 and (sv[:, 0] > 0).all() and ((sv[:, 1] + sv[:, 2]) / np.maximum(sv[:, 0], 1e-300)).min() >= 0.1
+        c["check"] = ref.FULL if good or empty else ref.PROPERTIES
+        if empty:
+            assert (ans["inliers"] == 0).all() and (ans["rmse"] == 0).all() and np.array_equal(ans["R"], R0_) and np.array_equal(ans["t"], t0_)
+        c.update({k: ans[k] for k in ("R", "t", "rmse", "inliers", "nearest", "dist")})
+        return c
+
+    for n, m in ref.SMALL_SIZES:
+        for wk in ref.WEIGHTS:
+            for trimmed in (False, True):
+                for ax, off in enumerate(ref.OFFSETS):
+                    step_case(n, m, wk, trimmed, off, ax, b=2)
+    for i, (n, m) in enumerate(ref.SIZES[2:]):                                    # a covering selection at the large sizes
+        for j, (wk, trimmed) in enumerate((("none", False), ("random", True), ("mask", True), ("random", False))):
+            step_case(n, m, wk, trimmed, ref.OFFSETS[(i + j) % 3] if j else 0.0, (i + j) % 3)
+    step_case(257, 1025, "random", True, 10.0, 1, shared=True, b=2)
+    step_case(255, 1023, "mask", False, 0.0, 0, empty=True)
+    step_case(3, 7, "none", False, 10.0, 2, empty=True, b=2)
+
+    # ---- convergence: Q = T_gt (P permuted) EXACTLY in float32 ----------------------------------------------------------------
+    # P on the lattice 25 * 2^-14, R_gt = Rz Rx of the (3, 4, 5) triangle (entries are multiples of 1/25), t_gt on 2^-14: every
+    # coordinate of Q is an integer multiple of 2^-14 below 4, exact in float32, so the float64 fixed point is T_gt itself.
+    c5, s5 = 3.0 / 5.0, 4.0 / 5.0
+    rz5, rx5 = np.array([[c5, -s5, 0], [s5, c5, 0], [0, 0, 1.0]]), np.array([[1.0, 0, 0], [0, c5, -s5], [0, s5, c5]])
+    r_exact = [rz5 @ rx5, (rz5 @ rx5).T, rx5 @ rz5, (rx5 @ rz5).T]
+
+    def registration(name, kind, exact, extra, sigma, seed_tries=20):
+        n, b = 300, 4
+        for _ in range(seed_tries):
+            P, Q, R0, T0, RG, TG, PERM = [], [], [], [], [], [], []
+            for cloud in range(b):
+                p = spaced_ball(n, 0.12, 25 * 2.0**-14 if exact else None)
+                r_gt = r_exact[cloud] if exact else Rotation.random(random_state=rng).as_matrix()
+                t_gt = np.round(rng.uniform(-0.5, 0.5, 3) * 2**14) / 2**14
+                slots = rng.permutation(n + extra)
+                q = np.zeros((n + extra, 3))
+                if exact:                                  # integers throughout: R_gt = R25 / 25 and p = 25 k 2^-14 give R_gt p = (R25 k) 2^-14
+                    image = (np.round(p * 2.0**14 / 25) @ np.round(25 * r_gt).T) * 2.0**-14 + t_gt
+                else:
+                    image = p @ r_gt.T + t_gt + sigma * rng.standard_normal((n, 3))
+                q[slots[:n]] = image
+                d = rng.standard_normal((extra, 3))
+                q[slots[n:]] = (t_gt + d / np.linalg.norm(d, axis=1, keepdims=True) * rng.uniform(1.5, 2.0, (extra, 1))).astype(np.float32)      # beyond max_distance
+                dr, dt = small_motion(2.0, 0.02)
+                P.append(p); Q.append(q); R0.append(r_gt @ dr); T0.append(t_gt + dt); RG.append(r_gt); TG.append(t_gt); PERM.append(slots[:n])
+            c = dict(P=np.stack(P).astype(np.float32), Q=np.stack(Q).astype(np.float32), R0=np.stack(R0).astype(np.float32), t0=np.stack(T0).astype(np.float32))
+            md = 0.2 if extra else None
+            ans = ref.icp64(c["P"], c["Q"], c["R0"], c["t0"], 20, md, None)
+            perm = np.stack(PERM)
+            if exact:
+                assert np.array_equal(c["P"].astype(np.float64), np.stack(P)) and np.array_equal(c["Q"].astype(np.float64), np.stack(Q))
+                ok = (ans["rmse"][9:] < 1e-12).all() and np.array_equal(ans["nearest"], perm)
+            else:                                          # the correspondences have settled by iteration 10 and are far from a tie
+                early = ref.icp64(c["P"], c["Q"], c["R0"], c["t0"], 10, md, None)
+                ok = np.array_equal(early["nearest"], ans["nearest"]) and ref.runner_up_gap(c["P"], c["Q"], ans["R"], ans["t"]) > 1e-3
+            if ok:
+                break
+        else:
+            raise AssertionError("no seed converged for " + name)
+        add(kind, name, c["P"], c["Q"], None, c["R0"], c["t0"], iterations=20, max_distance=md, Rgt=np.stack(RG), tgt=np.stack(TG), perm=perm,
+            **{k: ans[k] for k in ("R", "t", "rmse", "inliers", "nearest", "dist")})
+        print("g21 %-28s rmse %s" % (name, " ".join("%.1e" % v for v in ans["rmse"][:6, 0])))
+
+    registration("converge exact", "converge", True, 0, 0.0)
+    registration("converge exact superset", "converge", True, 40, 0.0)
+    registration("noise", "noise", False, 0, 0.01)
+    registration("noise superset", "noise", False, 40, 0.01)
+
+    arrays = {}
+    for i, c in enumerate(cases):
+        for k in ref.ARRAYS:
+            if c.get(k) is not None and not (c["kind"] == "step" and k in ("dist", "nearest")):      # a step is checked from what the call returns
+                arrays["c%d_%s" % (i, k)] = c[k].astype(np.int32) if k in ("nearest", "perm", "inliers") else c[k]
+    wn = list(ref.WEIGHTS)
+    print("g21: %d cases" % len(cases))
+    save("g21_icp.npz", kind_names=np.array(ref.KINDS), weight_names=np.array(wn), case_kind=np.array([ref.KINDS.index(c["kind"]) for c in cases], np.int32),
+         case_name=np.array([c["name"] for c in cases]), case_weights=np.array([wn.index(c["weights"]) for c in cases], np.int32),
+         case_offset=np.array([c["offset"] for c in cases]), case_iterations=np.array([c["iterations"] for c in cases], np.int32),
+         case_max_distance=np.array([-1.0 if c["max_distance"] is None else c["max_distance"] for c in cases]),
+         case_shared=np.array([c["shared"] for c in cases]), case_check=np.array([c["check"] for c in cases], np.int32), **arrays)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "g21":
+        return g21_icp()
     if len(sys.argv) > 1 and sys.argv[1] == "g20":
         return g20_rigid_align()
     if len(sys.argv) > 1 and sys.argv[1] == "g19":
@@ -737,6 +918,7 @@ def main():
     g13_dtype_fidelity()
     g19_add_metrics()
     g20_rigid_align()
+    g21_icp()
     # ---- G1: config #1, 256 Gaussian rows ------------------------------------------------------
     torch.manual_seed(0)
     x = torch.randn(256, 9)
