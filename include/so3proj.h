@@ -531,6 +531,45 @@ int so3_icp_f32(const float *P, const float *Q, int64_t q_stride, const float *w
                 int32_t iterations, float *R, float *t, float *rmse, int32_t *inliers, int32_t *nearest, float *dist,
                 void *workspace, int64_t B, int32_t N, int32_t M, void *stream);
 
+/* ---- PointNet++ sampling and grouping: farthest-point sampling and ball query (added in 210) ----
+ * The reference's point_cloud/pointnet_utils.py: farthest_point_sample (:53-74, a Python loop of npoint iterations) and
+ * query_ball_point (:77-97, a (B,S,N) index tensor sorted along N), each as one launch.
+ *
+ * THE ARITHMETIC IS A DEFINITION.  Farthest-point sampling is a chain: an argmax that rounds differently changes every later
+ * index, and on the reference's own workload the best and the runner-up come within 6e-7 of each other (relative).  So:
+ *     d(j, c) = ((dx * dx) + (dy * dy)) + (dz * dz),   dx = x_j - c_x, dy = y_j - c_y, dz = z_j - c_z,
+ *   every operation rounded to float32 on its own, no fused multiply-add;
+ *     dist_j starts at 1e10f and is updated by   if (d < dist_j) dist_j = d;
+ *     the next index is the argmax of dist, the LOWEST index among equal values.
+ *   This is index for index what the reference's loop computes in float32 on the CPU from the same start.
+ *   Ball membership is   !(d(j, c) > radius * radius)   with the same d and the product rounded to float32.
+ *   KNOWN DIFFERENCE from the reference: its query_ball_point takes d from the expanded form |a|^2 + |b|^2 - 2 a.b
+ *   (square_distance, :12-31), so a point within rounding of the sphere (| d - r^2 | of the order 1e-6 r^2 .. 1e-5 r^2 for
+ *   clouds of unit radius) can fall on the other side.  It is the only difference.
+ *   Non-finite coordinates give unspecified indices, but every index stays in [0, N] and the kernels terminate.
+ *
+ * so3_fps_f32: out[b][0] = start[b];  out[b][i + 1] = the argmax above after the update with centre out[b][i].
+ *   xyz      in   B*N*3 float32
+ *   start    in   B int32, each in [0, N) (a value outside is clamped into the range)
+ *   out      out  B*npoint int32
+ *   1 <= N <= SO3_FPS_MAX_N, 1 <= npoint <= SO3_FPS_MAX_N.  npoint > N is legal: once every point has been taken every dist
+ *   is 0 and the rule gives index 0.  One workgroup per cloud and all npoint iterations in one launch (the points and their
+ *   running minima stay in registers); no atomics, no workspace.
+ * so3_ball_query_f32: for centre s of cloud b the first `width` = min(nsample, N) indices j, ascending, of the points inside
+ *   the ball; the remaining slots repeat the first hit; a centre WITHOUT a hit gets N in every slot (as the reference does:
+ *   an index one past the cloud -- look at count before gathering).
+ *   xyz      in   B*N*3 float32;   centres in B*S*3 float32
+ *   idx      out  B*S*width int32
+ *   count    out  optional B*S int32: the points in the ball, NOT clipped to nsample (asking for it scans the whole cloud;
+ *                 without it a centre's scan stops once its row is full)
+ *   1 <= N, S <= SO3_ADD_S_MAX_N, 1 <= nsample.  One wave per centre, no atomics, no workspace.
+ * Neither call synchronises with the host; both can be captured in a graph and give the same bits from call to call.
+ */
+#define SO3_FPS_MAX_N 16384
+int so3_fps_f32(const float *xyz, const int32_t *start, int32_t *out, int64_t B, int32_t N, int32_t npoint, void *stream);
+int so3_ball_query_f32(const float *xyz, const float *centres, float radius, int32_t nsample, int32_t *idx, int32_t *count,
+                       int64_t B, int32_t N, int32_t S, void *stream);
+
 /* ---- next row: on-device pair synthesis for Kabsch ------------------------------
  * so3_rotations_axis_angle_f32: the arithmetic of the reference's sampler, point_cloud/prepare.py:21-49
  *   (normalize_vector :12-18, quaternion (cos theta, axis sin theta) -> matrix :27-47), given the random

@@ -70,6 +70,8 @@ SYMBOLS = {
     "so3_nearest_f32": (_INT, [_P, _P, _I64, _P, _P, _I64, _I32, _I32, _P]),
     "so3_icp_workspace_bytes": (ctypes.c_size_t, [_I64, _I32]),
     "so3_icp_f32": (_INT, [_P, _P, _I64, _P, _P, ctypes.c_float, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P]),
+    "so3_fps_f32": (_INT, [_P, _P, _P, _I64, _I32, _I32, _P]),
+    "so3_ball_query_f32": (_INT, [_P, _P, ctypes.c_float, _I32, _P, _P, _I64, _I32, _I32, _P]),
     "so3_rotate_clouds_bwd_f32": (_INT, [_P, _P, _P, _P, _P, _INT, _I64, _I32, _P]),
     "so3_rotations_axis_angle_f32": (_INT, [_P, _P, _P, _I64, _P]),
     "so3_kabsch_synth_f32": (_INT, [_P, _P, ctypes.c_float, ctypes.c_uint32, _P, _P, _I64, _I32, _P]),
@@ -78,6 +80,7 @@ SYMBOLS = {
 }
 
 ADD_S_MAX_N = 1 << 20                             # include/so3proj.h: SO3_ADD_S_MAX_N
+FPS_MAX_N = 16384                                 # include/so3proj.h: SO3_FPS_MAX_N
 ABI_VERSION = 210                                 # include/so3proj.h: SO3PROJ_VERSION this binding's argument lists belong to
 
 _lock = threading.Lock()

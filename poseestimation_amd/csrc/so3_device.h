@@ -1240,4 +1240,44 @@ __device__ __forceinline__ void icp_finish(const float (&s)[kIcpSums], const flo
     inliers = s[17];
 }
 
+// ---- PointNet++ sampling and grouping: farthest-point sampling and ball query (so3proj.hip: k_fps, k_ball_query;
+// tests/host_model/pointnet.cpp) -------------------------------------------------------------------------------------------------
+// Farthest-point sampling is a chain: one argmax that rounds differently changes every later index.  Its arithmetic is therefore a
+// DEFINITION (include/so3proj.h), not an approximation with a tolerance:
+//     d = ((dx * dx) + (dy * dy)) + (dz * dz),  dx = x_j - c_x, ...  -- every operation rounded to float32 on its own, NO contraction;
+//     the running minimum starts at kFpsInit and is updated by  if (d < dist) dist = d;
+//     the next centre is the argmax of the running minimum, the LOWEST index among equal values.
+// A ball's membership test is  !(d > radius * radius)  on the same d, the product rounded to float32.
+// A running minimum is never negative and never NaN (a NaN d fails d < dist), so its bit pattern orders as the value does and
+// (bits << 32) | (0xFFFFFFFF - j) makes "largest distance, lowest index" one unsigned maximum.  A slot without a point carries
+// key 0, which loses against every point's key (j < 2^32 - 1).
+#pragma clang fp contract(off)
+constexpr float kFpsInit = 1e10f;
+constexpr int kFpsMaxN = 16384;                  // include/so3proj.h: SO3_FPS_MAX_N
+__device__ __forceinline__ float pointnet_dist2(float x, float y, float z, float cx, float cy, float cz) {
+    const float dx = x - cx, dy = y - cy, dz = z - cz;
+    const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
+    const float xy = xx + yy;
+    return xy + zz;
+}
+__device__ __forceinline__ float ball_radius2(float radius) { return radius * radius; }
+#pragma clang fp contract(fast)
+__device__ __forceinline__ void fps_update(float d, float &dist) {
+    if (d < dist) dist = d;
+}
+__device__ __forceinline__ unsigned long long fps_key(float dist, int j) {
+    unsigned int bits;
+    __builtin_memcpy(&bits, &dist, 4);
+    return (static_cast<unsigned long long>(bits) << 32) | (0xFFFFFFFFu - static_cast<unsigned int>(j));
+}
+__device__ __forceinline__ int fps_key_index(unsigned long long key) { return static_cast<int>(0xFFFFFFFFu - static_cast<unsigned int>(key)); }
+__device__ __forceinline__ bool ball_member(float d, float r2) { return !(d > r2); }
+// k_fps<PPL, BLOCK>: the points one lane keeps and the lanes of the workgroup that serves a cloud of N points.  Point j lives in
+// slot j / BLOCK of lane j % BLOCK.
+inline void fps_shape(int N, int &ppl, int &block) {
+    block = N <= 2048 ? 256 : 1024;
+    ppl = 1;
+    while (ppl * block < N) ppl <<= 1;           // 256 x {1, 2, 4, 8}, 1024 x {4, 8, 16}
+}
+
 }  // namespace so3

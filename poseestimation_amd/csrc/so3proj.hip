@@ -1715,6 +1715,139 @@ __global__ __launch_bounds__(kBlock) void k_icp_initial_pose(const float *__rest
     if (j < 3) R[b * 9 + 3 * c + j] = v; else T[b * 3 + c] = v;
 }
 
+// ---- PointNet++ sampling and grouping: farthest-point sampling and ball query ----------------------------------------------------
+// The maximum of a 64-bit key over the wave, in every lane (wave_allmax's partners).
+__device__ __forceinline__ unsigned long long key_max(unsigned long long a, unsigned int lo, unsigned int hi) {
+    const unsigned long long b = (static_cast<unsigned long long>(hi) << 32) | lo;
+    return b > a ? b : a;
+}
+template <int STEPS>                    // STEPS = 6: the whole wave; fewer: aligned groups of 2^STEPS lanes (STEPS <= 4)
+__device__ __forceinline__ unsigned long long wave_allmax_key(unsigned long long k) {
+#define SO3_KEY_STEP(MOVE) k = key_max(k, __float_as_uint(MOVE(__uint_as_float(static_cast<unsigned int>(k)))), \
+                                       __float_as_uint(MOVE(__uint_as_float(static_cast<unsigned int>(k >> 32)))))
+    if (STEPS >= 1) SO3_KEY_STEP(dpp_xor1);
+    if (STEPS >= 2) SO3_KEY_STEP(dpp_xor2);
+    if (STEPS >= 3) SO3_KEY_STEP(dpp_half_mirror);
+    if (STEPS >= 4) SO3_KEY_STEP(dpp_mirror);
+#undef SO3_KEY_STEP
+    if (STEPS >= 5) k = key_max(k, __shfl_xor(static_cast<unsigned int>(k), 16, 64), __shfl_xor(static_cast<unsigned int>(k >> 32), 16, 64));
+    if (STEPS >= 6) k = key_max(k, __shfl_xor(static_cast<unsigned int>(k), 32, 64), __shfl_xor(static_cast<unsigned int>(k >> 32), 32, 64));
+    return k;
+}
+
+// k_fps<PPL, BLOCK>: one workgroup per cloud, all npoint iterations in one launch.  Point j lives in slot j / BLOCK of lane
+// j % BLOCK, with its running minimum, for the whole launch.  One iteration: every lane updates its minima with the current centre
+// (so3::pointnet_dist2, fps_update) and keeps its largest minimum and that point's slot, which give its key (so3::fps_key: largest
+// minimum, lowest index); the wave's maximum (wave_allmax_key) is unique to one lane, which writes the key and its point's coordinates to
+// the wave's LDS slot; one barrier; every wave reduces the slots redundantly and reads the winner's coordinates from the winner's slot, so the
+// next centre never comes from global memory.  The slots are double-buffered by the parity of a counter that runs on across the
+// clouds a workgroup serves: a wave can only be one barrier ahead of another, so it writes the buffer nobody is still reading.
+// Loop bounds and barriers are uniform across the workgroup.  No atomics, no workspace, no scratch.
+constexpr int kFpsMaxGrid = 4096;        // workgroups of a launch; a larger batch is strided over
+template <int PPL, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void k_fps(const float *__restrict__ xyz, const int32_t *__restrict__ start, int32_t *__restrict__ out,
+                                               int64_t B, int32_t N, int32_t npoint) {
+    constexpr int kWaves = BLOCK / 64;
+    constexpr int kSlotSteps = kWaves == 16 ? 4 : 2;
+    static_assert(kWaves == 4 || kWaves == 16, "the slots are reduced within a DPP row");
+    __shared__ unsigned long long slot_key[2][kWaves];
+    __shared__ float4 slot_xyz[2][kWaves];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    unsigned int turn = 0;
+    for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
+        const float *src = xyz + b * N * 3;
+        float x[PPL], y[PPL], z[PPL], dist[PPL];
+#pragma unroll
+        for (int u = 0; u < PPL; ++u) {
+            const int j = u * BLOCK + tid, jc = min(j, N - 1);
+            x[u] = src[jc * 3 + 0]; y[u] = src[jc * 3 + 1]; z[u] = src[jc * 3 + 2];
+            dist[u] = j < N ? so3::kFpsInit : -1.f;                         // a slot beyond the cloud: no d is below -1, and no point's minimum is
+        }
+        int cur = min(max(start[b], 0), N - 1);                             // workgroup-uniform
+        float cx = src[cur * 3 + 0], cy = src[cur * 3 + 1], cz = src[cur * 3 + 2];
+        asm volatile("" : "+v"(cx), "+v"(cy), "+v"(cz));                    // values, not addresses: otherwise the loop reads its centre through one
+        for (int i = 0; i < npoint; ++i) {                                  // flat load whose pointer is this global one or the LDS slot's
+            if (tid == 0) out[b * npoint + i] = cur;
+            if (i + 1 == npoint) break;
+            float bestd = -1.f;                                             // the lane's largest minimum and its slot: the lowest slot (= the
+            int bu = 0;                                                     // lowest j of this lane) among equal values
+#pragma unroll
+            for (int u = 0; u < PPL; ++u) {
+                so3::fps_update(so3::pointnet_dist2(x[u], y[u], z[u], cx, cy, cz), dist[u]);
+                const bool up = dist[u] > bestd;
+                bestd = up ? dist[u] : bestd;
+                bu = up ? u : bu;
+            }
+            const unsigned long long best = bestd < 0.f ? 0ull : so3::fps_key(bestd, bu * BLOCK + tid);      // 0: a lane without a point
+            const unsigned long long top = wave_allmax_key<6>(best);
+            const int par = turn & 1;
+            ++turn;
+            if (top != 0 ? best == top : lane == 0) {                      // one lane: a point's key is unique
+                float bx = x[0], by = y[0], bz = z[0];
+#pragma unroll
+                for (int u = 1; u < PPL; ++u) {
+                    const bool mine = u == bu;
+                    bx = mine ? x[u] : bx; by = mine ? y[u] : by; bz = mine ? z[u] : bz;
+                }
+                slot_key[par][wave] = top;
+                slot_xyz[par][wave] = make_float4(bx, by, bz, 0.f);
+            }
+            __syncthreads();
+            const unsigned long long win = wave_allmax_key<kSlotSteps>(slot_key[par][lane & (kWaves - 1)]);
+            cur = so3::fps_key_index(win);
+            const float4 c = slot_xyz[par][(cur & (BLOCK - 1)) >> 6];       // the wave that holds point cur
+            cx = c.x; cy = c.y; cz = c.z;
+        }
+    }
+}
+
+// k_ball_query<COUNT>: one wave per centre, the cloud scanned 64 points per step in ascending j, kBallUnroll steps' loads in flight.
+// The cloud is read straight from global memory (12 B per lane, a wave's 768 B contiguous; every centre of a cloud reads the same
+// 12 * N bytes, which stay in L2): waves that have filled their row leave early, which tiles shared through LDS by a workgroup
+// would not allow.  Membership gives a ballot; a lane's slot is count + popcount(mask below it), so stores ascend by construction.
+// COUNT = true scans the whole cloud and writes the number of points in the ball.
+constexpr int kBallUnroll = 4;
+template <bool COUNT>
+__global__ __launch_bounds__(kBlock) void k_ball_query(const float *__restrict__ xyz, const float *__restrict__ centres, float radius,
+                                                       int32_t width, int32_t *__restrict__ idx, int32_t *__restrict__ count,
+                                                       int64_t B, int32_t N, int32_t S) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = static_cast<int64_t>(blockIdx.x) * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t nwaves = static_cast<int64_t>(gridDim.x) * (kBlock / 64);
+    const float r2 = so3::ball_radius2(radius);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int64_t item = wave; item < B * S; item += nwaves) {
+        const int64_t b = item / S;
+        const float *src = xyz + b * N * 3;
+        const float cx = centres[item * 3 + 0], cy = centres[item * 3 + 1], cz = centres[item * 3 + 2];      // wave-uniform
+        int32_t *row = idx + item * width;
+        int found = 0, first = N;
+        for (int j0 = 0; j0 < N; j0 += 64 * kBallUnroll) {
+            float x[kBallUnroll], y[kBallUnroll], z[kBallUnroll];
+#pragma unroll
+            for (int k = 0; k < kBallUnroll; ++k) {
+                const int j = min(j0 + 64 * k + lane, N - 1);
+                x[k] = src[j * 3 + 0]; y[k] = src[j * 3 + 1]; z[k] = src[j * 3 + 2];
+            }
+#pragma unroll
+            for (int k = 0; k < kBallUnroll; ++k) {
+                const int j = j0 + 64 * k + lane;
+                const bool in = j < N && so3::ball_member(so3::pointnet_dist2(x[k], y[k], z[k], cx, cy, cz), r2);
+                const unsigned long long mask = __builtin_amdgcn_ballot_w64(in);
+                if (mask != 0) {                                           // wave-uniform
+                    if (found == 0) first = j0 + 64 * k + __builtin_ctzll(mask);
+                    const int at = found + __builtin_popcountll(mask & below);
+                    if (in && at < width) row[at] = j;
+                    found += __builtin_popcountll(mask);
+                }
+            }
+            if (!COUNT && found >= width) break;
+        }
+        for (int k = min(found, width) + lane; k < width; k += 64) row[k] = first;
+        if (COUNT && lane == 0) count[item] = found;
+    }
+}
+
 // ---- float64 head and backward (the reference's functions accept double tensors): the same templates over
 // T = double, one row per thread with plain loads -- a convenience path, not a benchmark configuration.
 // Four fixed sweeps, then sweeps until the wave-wide residual is below 1e-14 (at most six more).
@@ -3534,6 +3667,49 @@ int so3_icp_f32(const float *P, const float *Q, int64_t q_stride, const float *w
         cur = next;
     }
     return check_launch("so3_icp_f32");
+}
+
+int so3_fps_f32(const float *xyz, const int32_t *start, int32_t *out, int64_t B, int32_t N, int32_t npoint, void *stream) {
+    static_assert(SO3_FPS_MAX_N == so3::kFpsMaxN, "the header's limit is the dispatch's");
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_FPS_MAX_N && npoint >= 1 && npoint <= SO3_FPS_MAX_N, "so3_fps_f32: B/N/npoint");
+    if (B == 0) return 0;
+    SO3_CHECK_ARGS(xyz != nullptr && start != nullptr && out != nullptr, "so3_fps_f32: null pointer");
+    int ppl, block;
+    so3::fps_shape(N, ppl, block);
+    static thread_local char name[32];
+    snprintf(name, sizeof name, "k_fps<%d, %d>", ppl, block);
+    g_last_kernel = name;
+    const dim3 grid(static_cast<unsigned>(std::min<int64_t>(B, kFpsMaxGrid)));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+#define FPS(PP, BB) hipLaunchKernelGGL((k_fps<PP, BB>), grid, dim3(BB), 0, s, xyz, start, out, B, N, npoint)
+    switch (block * 100 + ppl) {
+        case 25601: FPS(1, 256); break;
+        case 25602: FPS(2, 256); break;
+        case 25604: FPS(4, 256); break;
+        case 25608: FPS(8, 256); break;
+        case 102404: FPS(4, 1024); break;
+        case 102408: FPS(8, 1024); break;
+        case 102416: FPS(16, 1024); break;
+        default: return fail(SO3_ERR_INVALID, "so3_fps_f32: no kernel for this N");
+    }
+#undef FPS
+    return check_launch("so3_fps_f32");
+}
+
+int so3_ball_query_f32(const float *xyz, const float *centres, float radius, int32_t nsample, int32_t *idx, int32_t *count, int64_t B,
+                       int32_t N, int32_t S, void *stream) {
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && S >= 1 && S <= SO3_ADD_S_MAX_N && nsample >= 1,
+                   "so3_ball_query_f32: B/N/S/nsample");
+    if (B == 0) return 0;
+    SO3_CHECK_ARGS(xyz != nullptr && centres != nullptr && idx != nullptr, "so3_ball_query_f32: null pointer");
+    const int32_t width = std::min(nsample, N);
+    const int64_t blocks = (B * S + kBlock / 64 - 1) / (kBlock / 64);
+    const dim3 grid(static_cast<unsigned>(std::min<int64_t>(blocks, static_cast<int64_t>(device_cus()) * 32))), block(kBlock);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    g_last_kernel = count != nullptr ? "k_ball_query<true>" : "k_ball_query<false>";
+    if (count != nullptr) hipLaunchKernelGGL(k_ball_query<true>, grid, block, 0, s, xyz, centres, radius, width, idx, count, B, N, S);
+    else hipLaunchKernelGGL(k_ball_query<false>, grid, block, 0, s, xyz, centres, radius, width, idx, count, B, N, S);
+    return check_launch("so3_ball_query_f32");
 }
 
 int so3_add_l1_disentangled_f32(const float *Tpred, const float *Tgt, const float *points, double *loss_sum, float *dTpred,

@@ -1357,6 +1357,112 @@ def icp_align(P: torch.Tensor, Q: torch.Tensor, R_init: torch.Tensor = None, t_i
 
 
 # --------------------------------------------------------------------------------------------
+# PointNet++ sampling and grouping (reference: point_cloud/pointnet_utils.py)
+# --------------------------------------------------------------------------------------------
+def _cloud_f32(name, what, x, width=3):
+    """A contiguous float32 copy (or the tensor itself) of a (B, N, 3) cloud on the device."""
+    dev = _require_device(x)
+    if x.dim() != 3 or x.shape[-1] != width or x.shape[1] < 1:
+        raise RuntimeError("%s: expected %s of shape (B, N, %d) with N >= 1, got %s" % (name, what, width, tuple(x.shape)))
+    return dev, x.detach().contiguous().float()
+
+
+def farthest_point_sample(xyz: torch.Tensor, npoint: int, start=None) -> torch.Tensor:
+    """point_cloud/pointnet_utils.py:53-74 in one launch: (B, npoint) int64 indices of the farthest-point sample of xyz (B, N, 3).
+    out[:, 0] is the first index; every further index is the point farthest from all chosen so far, the lowest index among equals.
+
+    start=None draws the first index with torch.randint(0, N, (B,)) as the reference does (on the device).  An int, or a (B,)
+    integer tensor, fixes it; an index outside [0, N) raises a RuntimeError.  An int or a CPU tensor is checked on the host; a
+    DEVICE tensor is checked by reading one flag back, which synchronises -- except while the stream is being captured into a graph,
+    where the kernel clamps the index into range instead.  With start=None or an int nothing synchronises with the host.
+
+    The arithmetic is a definition (include/so3proj.h): d = ((dx * dx) + (dy * dy)) + (dz * dz) in float32 without fused
+    multiply-add, a running minimum from 1e10, the argmax with the lowest index among equal values.  It equals the reference's loop
+    on the CPU index for index from the same start.  1 <= N <= FPS_MAX_N (16384), 1 <= npoint <= FPS_MAX_N; npoint > N gives index 0
+    once every point is taken.  One workgroup per cloud (so3_fps_f32).  Other float dtypes are converted to float32.  The
+    indices carry no gradient, as the reference's."""
+    dev, x = _cloud_f32("farthest_point_sample", "xyz", xyz)
+    b, n = x.shape[0], x.shape[1]
+    npoint = int(npoint)
+    if n > _lib.FPS_MAX_N or not 1 <= npoint <= _lib.FPS_MAX_N:
+        raise RuntimeError("farthest_point_sample: expected 1 <= N <= %d and 1 <= npoint <= %d, got N = %d, npoint = %d"
+                           % (_lib.FPS_MAX_N, _lib.FPS_MAX_N, n, npoint))
+    if start is None:
+        first = torch.randint(0, n, (b,), device=dev, dtype=torch.int32)
+    elif isinstance(start, torch.Tensor):
+        if start.dim() != 1 or start.shape[0] != b or start.dtype.is_floating_point or start.dtype in (torch.bool, torch.complex64, torch.complex128):
+            raise RuntimeError("farthest_point_sample: start must be an int or an integer tensor of shape (%d,), got %s %s"
+                               % (b, start.dtype, tuple(start.shape)))
+        if b and not (start.is_cuda and _capturing(dev)) and bool(((start < 0) | (start >= n)).any()):
+            raise RuntimeError("farthest_point_sample: start index outside [0, %d)" % n)
+        first = start.detach().to(device=dev, dtype=torch.int32).contiguous()
+    else:
+        if not 0 <= int(start) < n:
+            raise RuntimeError("farthest_point_sample: start index %d outside [0, %d)" % (int(start), n))
+        first = torch.full((b,), int(start), device=dev, dtype=torch.int32)
+    out = torch.empty((b, npoint), dtype=torch.int32, device=dev)
+    with _on_device(dev):
+        _check(_libh().so3_fps_f32(_ptr(x), _ptr(first), _ptr(out), b, n, npoint, _stream(dev)), "so3_fps_f32")
+    return out.long()
+
+
+def query_ball_point(radius: float, nsample: int, xyz: torch.Tensor, new_xyz: torch.Tensor, return_counts: bool = False):
+    """point_cloud/pointnet_utils.py:77-97 in one launch, without the (B, S, N) tensors and the sort: for every centre new_xyz[b, s]
+    the first nsample indices j, in ascending j, of the points of xyz[b] with |new_xyz_s - xyz_j|^2 <= radius^2; the remaining slots
+    repeat the first hit.  xyz: (B, N, 3), new_xyz: (B, S, 3); the result is (B, S, min(nsample, N)) int64.
+
+    A centre WITHOUT a hit gets N in every slot, as the reference does -- an index one past the cloud, which index_points would
+    refuse.  return_counts=True also returns a (B, S) int64 count of the points in each ball, NOT clipped to nsample: look there
+    (count == 0) before gathering when centres may be empty.  Centres that are cloud points (sample_and_group's) always hit themselves.
+
+    The distance comes from coordinate differences, d = ((dx * dx) + (dy * dy)) + (dz * dz) in float32, and the test is
+    not (d > radius * radius) (include/so3proj.h).  The reference expands |a|^2 + |b|^2 - 2 a.b, so a point within rounding of the
+    sphere can fall on the other side there; that is the only difference.  One wave per centre (so3_ball_query_f32); without
+    return_counts a centre's scan stops once its row is full.  Nothing synchronises with the host.  No gradient, as the reference's."""
+    dev, x = _cloud_f32("query_ball_point", "xyz", xyz)
+    _, c = _cloud_f32("query_ball_point", "new_xyz", new_xyz)
+    _require_device(x, c)
+    b, n, s = x.shape[0], x.shape[1], c.shape[1]
+    nsample = int(nsample)
+    if c.shape[0] != b or n > _lib.ADD_S_MAX_N or s > _lib.ADD_S_MAX_N or nsample < 1:
+        raise RuntimeError("query_ball_point: expected xyz (B, N, 3) and new_xyz (B, S, 3) with 1 <= N, S <= %d and nsample >= 1, got %s, %s "
+                           "and nsample = %d" % (_lib.ADD_S_MAX_N, tuple(xyz.shape), tuple(new_xyz.shape), nsample))
+    idx = torch.empty((b, s, min(nsample, n)), dtype=torch.int32, device=dev)
+    count = torch.empty((b, s), dtype=torch.int32, device=dev) if return_counts else None
+    with _on_device(dev):
+        _check(_libh().so3_ball_query_f32(_ptr(x), _ptr(c), float(radius), min(nsample, 2**31 - 1), _ptr(idx), _ptr(count), b, n, s, _stream(dev)),
+               "so3_ball_query_f32")
+    return (idx.long(), count.long()) if return_counts else idx.long()
+
+
+def index_points(points: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """point_cloud/pointnet_utils.py:34-50: points (B, N, C) gathered by idx (B, S) -> (B, S, C) or (B, S, K) -> (B, S, K, C).
+    Plain torch indexing on the tensors' device, differentiable in points."""
+    if points.dim() != 3 or idx.dim() not in (2, 3) or idx.shape[0] != points.shape[0]:
+        raise RuntimeError("index_points: expected points (B, N, C) and idx (B, S) or (B, S, K), got %s and %s" % (tuple(points.shape), tuple(idx.shape)))
+    batch = torch.arange(points.shape[0], dtype=torch.long, device=points.device).view(-1, *([1] * (idx.dim() - 1)))
+    return points[batch, idx.long(), :]
+
+
+def sample_and_group(npoint: int, radius: float, nsample: int, xyz: torch.Tensor, points: torch.Tensor, returnfps: bool = False, start=None):
+    """point_cloud/pointnet_utils.py:100-128, a set-abstraction layer's sampling and grouping: farthest_point_sample (from `start`),
+    the sampled centres new_xyz (B, npoint, 3), query_ball_point around them, and new_points (B, npoint, K, 3 + D) = the grouped
+    coordinates relative to their centre, concatenated with the grouped features of points (B, N, D) (points=None: the coordinates
+    alone); K = min(nsample, N).  Returns (new_xyz, new_points), with returnfps=True (new_xyz, new_points, grouped_xyz, fps_idx).
+    new_points is differentiable in xyz and points through the gathers; the indices carry no gradient."""
+    fps_idx = farthest_point_sample(xyz, npoint, start)
+    new_xyz = index_points(xyz, fps_idx)
+    idx = query_ball_point(radius, nsample, xyz, new_xyz)
+    grouped_xyz = index_points(xyz, idx)
+    new_points = grouped_xyz - new_xyz[:, :, None, :]
+    if points is not None:
+        new_points = torch.cat([new_points, index_points(points, idx)], dim=-1)
+    if returnfps:
+        return new_xyz, new_points, grouped_xyz, fps_idx
+    return new_xyz, new_points
+
+
+# --------------------------------------------------------------------------------------------
 # row a7: the cloud side of the point-cloud path
 # --------------------------------------------------------------------------------------------
 def _rotate_call(pc, R, transposed):

@@ -209,6 +209,22 @@ def main():
                lambda i: lib.so3_icp_f32(p(xi), p(yi), 3 * ni, None, None, ctypes.c_float(-1.0), its, p(ri), p(ti), None, None, None, None, p(wsi), bi, ni, ni, st),
                its * bi * ni * 24, iters=10, warm=2)
     del xi, yi, di, nni, ri, ti, wsi
+    # PointNet++ sampling and grouping at the reference model's first level: a chain of 511 dependent argmaxes per cloud (one workgroup
+    # each: latency bound, most compute units idle at B = 32), and one wave per centre over the cloud (the bytes are the index rows')
+    bf, nf, sf, kf = 32, 1024, 512, 64
+    xf = torch.rand(bf, nf, 3, device=dev) - 0.5
+    xf = xf / (xf.amax(1) - xf.amin(1)).norm(dim=-1)[:, None, None]                     # pc_normalize's scale
+    s0 = torch.zeros(bf, dtype=torch.int32, device=dev)
+    of = torch.empty(bf, sf, dtype=torch.int32, device=dev)
+    timeit("pointnet: so3_fps_f32 (32 x 1024 -> 512)", lambda i: lib.so3_fps_f32(p(xf), p(s0), p(of), bf, nf, sf, st), bf * (nf * 12 + sf * 4), iters=10, warm=2)
+    _lib.check(lib.so3_fps_f32(p(xf), p(s0), p(of), bf, nf, sf, st), "so3_fps_f32")        # the centres, whether or not the line above ran
+    cf = torch.gather(xf, 1, of.long()[..., None].expand(-1, -1, 3)).contiguous()
+    gi, gc = torch.empty(bf, sf, kf, dtype=torch.int32, device=dev), torch.empty(bf, sf, dtype=torch.int32, device=dev)
+    timeit("pointnet: so3_ball_query_f32 (32 x 1024, 512 centres, r=0.2, K=64)", lambda i: lib.so3_ball_query_f32(p(xf), p(cf), ctypes.c_float(0.2), kf, p(gi), None, bf, nf, sf, st),
+           bf * sf * kf * 4, iters=10, warm=2)
+    timeit("pointnet: so3_ball_query_f32 (the same, with counts)", lambda i: lib.so3_ball_query_f32(p(xf), p(cf), ctypes.c_float(0.2), kf, p(gi), p(gc), bf, nf, sf, st),
+           bf * sf * (kf + 1) * 4, iters=10, warm=2)
+    del xf, s0, of, cf, gi, gc
     rg = rr.get_sampled_rotation_matrices_by_axisAngle(b, dev).reshape(b, 9).contiguous()
     timeit("f4 so3_kabsch_synth_f32 (sigma=0: P only)", lambda i: lib.so3_kabsch_synth_f32(p(pc[i % 2]), p(rg), ctypes.c_float(0.0), 1, p(rk), None, b, npts, st), b * (npts * 12 + 72), iters=10, warm=2)
     timeit("f4 so3_kabsch_synth_f32 (sigma=0.01, device RNG)", lambda i: lib.so3_kabsch_synth_f32(p(pc[i % 2]), p(rg), ctypes.c_float(0.01), 1, p(rk), None, b, npts, st), b * (npts * 12 + 72), iters=10, warm=2)

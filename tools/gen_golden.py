@@ -878,7 +878,61 @@ def g21_icp():
          case_shared=np.array([c["shared"] for c in cases]), case_check=np.array([c["check"] for c in cases], np.int32), **arrays)
 
 
+def g22_pointnet(seed=24):
+    """farthest_point_sample and query_ball_point (point_cloud/pointnet_utils.py:53-97), the reference's own functions on the CPU in
+    float32, at the reference model's settings: clouds normalised by pc_normalize, level one 1024 -> 512 centres with (r, K) = (0.1, 32)
+    and (0.2, 64), level two 512 -> 128 centres (of level one's centres) with (0.4, 64) and (0.8, 128), and an odd-sized 3 x 300 -> 77.
+    torch is seeded and centroids[:, 0] is the recorded start.  Every ball-query case stores near_boundary (tests/pointnet_ref.py);
+    the generator asserts that the reference differs from the float64 restatement only inside that mask and that the mask covers at
+    most 1 % of a case's rows.  (Seeds 22 and 23 put 4 and 3 of level two's 256 rows into the mask: 1.6 % and 1.2 %; 24 is the first
+    seed that meets the cap in every case.)"""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import pointnet_ref as ref
+    names = ["square_distance", "index_points", "farthest_point_sample", "query_ball_point"]
+    fns = functions_from(os.path.join(REF, "point_cloud", "pointnet_utils.py"), names)
+    for f in fns:                                                 # the functions call each other by name
+        f.__globals__.update(dict(zip(names, fns)))
+    _, index_points, farthest_point_sample, query_ball_point = fns
+    (pc_normalize,) = functions_from(os.path.join(REF, "point_cloud", "prepare.py"), ["pc_normalize"])
+    rng = np.random.RandomState(seed)
+    torch.manual_seed(seed)
+
+    def clouds(b, n):
+        raw = (rng.rand(b, n, 3) - 0.5) * np.array([1.0, 0.8, 0.6]) + np.array([0.3, -1.0, 2.0])
+        return torch.tensor(np.stack([pc_normalize(c)[0] for c in raw])).float()
+
+    arrays = {}
+    level = {1024: clouds(2, 1024), 300: clouds(3, 300)}
+    arrays["cloud0"], arrays["cloud2"] = level[1024], level[300]
+    fps_idx = {}
+    for k, (b, n, npoint) in enumerate(ref.FPS_CASES):
+        idx = farthest_point_sample(level[n], npoint)
+        assert idx.shape == (b, npoint) and int(idx.max()) < n
+        assert np.array_equal(ref.fps(level[n].numpy(), npoint, idx[:, 0].numpy()), idx.numpy()), "the restatement is not the reference's sequence"
+        fps_idx[n] = idx
+        arrays["fps%d_idx" % k] = idx.numpy().astype(np.uint16)
+        if n == 1024:
+            level[512] = index_points(level[1024], idx)             # level two's cloud: level one's centres
+    centres = {1024: level[512], 512: index_points(level[512], fps_idx[512])}
+    for k, (n, s, radius, nsample) in enumerate(ref.BALL_CASES):
+        xyz, c = level[n], centres[n]
+        assert c.shape == (2, s, 3)
+        idx = query_ball_point(radius, nsample, xyz, c).numpy()
+        want, _ = ref.ball_query(radius, nsample, xyz.numpy(), c.numpy(), np.float64)
+        near = ref.near_boundary(radius, xyz.numpy(), c.numpy())
+        differ = (idx != want).any(-1)
+        assert not (differ & ~near).any(), "the reference differs from the float64 restatement outside the boundary mask"
+        assert near.mean() <= ref.BOUNDARY_CAP, (k, near.mean())
+        ref.row_properties(idx, n)
+        print("g22 ball N=%d S=%d r=%g K=%d: %d rows near the boundary (%.2f %%), %d differ" % (n, s, radius, nsample, near.sum(), 100 * near.mean(), differ.sum()))
+        arrays["ball%d_idx" % k] = idx.astype(np.uint16)
+        arrays["ball%d_near" % k] = near
+    save("g22_pointnet.npz", **arrays)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "g22":
+        return g22_pointnet()
     if len(sys.argv) > 1 and sys.argv[1] == "g21":
         return g21_icp()
     if len(sys.argv) > 1 and sys.argv[1] == "g20":
@@ -919,6 +973,7 @@ def main():
     g19_add_metrics()
     g20_rigid_align()
     g21_icp()
+    g22_pointnet()
     # ---- G1: config #1, 256 Gaussian rows ------------------------------------------------------
     torch.manual_seed(0)
     x = torch.randn(256, 9)
