@@ -1062,6 +1062,74 @@ __global__ __launch_bounds__(kBlock) void k_kabsch_synth(const float *__restrict
     }
 }
 
+// Clouds of a few points (N <= kSynthFew): the same skeleton, one point per lane, with q = R_gt p + sigma n formed in float64 -- the noise
+// included: log, sqrt, cospi / sinpi on the same six uniforms -- and rounded to float32 ONCE.  H = sum q p^T of so few terms has no slack to
+// hide the roundings of q's three products where they cancel (a q_a of 1e-4 from products of 0.3 carries 3e-8, three hundred times
+// u |q_a|); with q correctly rounded, |dH_ab| <= 2 N u sum_i |q_ia| |p_ib| holds for every N.  Eight points a cloud: the cost does not matter.
+constexpr int kSynthFew = 8;
+__device__ __forceinline__ double synth_unit_double(unsigned h) { return static_cast<double>(h >> 9) * (1.0 / 8388608.0); }   // [0, 1)
+template <bool NOISE>
+__global__ __launch_bounds__(kBlock) void k_kabsch_synth_few(const float *__restrict__ P, const float *__restrict__ Rgt, float sigma,
+                                                             unsigned seed, float *__restrict__ R, float *__restrict__ H, int64_t B,
+                                                             int32_t N, int clouds_per_wave) {
+    const int lane = threadIdx.x & 63;
+    const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t wave = static_cast<int64_t>(blockIdx.x) * (kBlock / 64) + wave_in_block;
+    const int64_t c0 = wave * clouds_per_wave;
+    if (c0 >= B) return;
+    const int nc = static_cast<int>(min<int64_t>(clouds_per_wave, B - c0));
+    float h[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) h[i] = (i & 3) == 0 ? 1.f : 0.f;
+    const unsigned cloud_bytes = static_cast<unsigned>(N) * 12u;
+    for (int j = 0; j < nc; ++j) {
+        const so3::rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(P) + (c0 + j) * N * 3, 0, cloud_bytes, so3::kRsrcFlags);
+        const u32x3 pp = __builtin_amdgcn_raw_buffer_load_b96(rp, lane * 12, 0, so3::kStreamNt);     // lanes past the cloud's end: zeros
+        const float p[3] = {__uint_as_float(pp.x), __uint_as_float(pp.y), __uint_as_float(pp.z)};
+        double nz[3] = {0.0, 0.0, 0.0};
+        if constexpr (NOISE) {          // point `lane` < 64 is point a of pair `lane` (synth_normal3x2): (r_A cos, r_A sin)(u_A), r_C cos(u_C)
+            const unsigned cloud_key = synth_cloud_key(seed, static_cast<unsigned>(c0 + j));
+            const unsigned h0 = mix32(cloud_key ^ (static_cast<unsigned>(lane) * 0x9e3779b9u + 0xc2b2ae35u));
+            unsigned h1 = h0 + 0x27d4eb2fu; h1 ^= h1 >> 16; h1 *= 0x7feb352du; h1 ^= h1 >> 15;
+            unsigned h2 = h0 ^ 0x165667b1u; h2 ^= h2 >> 15; h2 *= 0x2c1b3c6du; h2 ^= h2 >> 16;
+            unsigned h3 = h0 + 0x9e3779b1u; h3 ^= h3 >> 17; h3 *= 0x297a2d39u; h3 ^= h3 >> 14;
+            unsigned h4 = h0 ^ 0x85ebca77u; h4 ^= h4 >> 14; h4 *= 0xc2b2ae3du; h4 ^= h4 >> 17;
+            const unsigned low = ((h0 & 0xffu) << 24) | ((h1 & 0xffu) << 16) | ((h2 & 0xffu) << 8) | (h3 & 0xffu);
+            const double ra = sqrt(-2.0 * log(1.0 - synth_unit_double(h0))), rc = sqrt(-2.0 * log(1.0 - synth_unit_double(h4)));
+            const double ta = 2.0 * synth_unit_double(h1), tc = 2.0 * synth_unit_double(low);        // half turns
+            nz[0] = ra * cospi(ta); nz[1] = ra * sinpi(ta); nz[2] = rc * cospi(tc);
+        }
+        float q[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float *g = Rgt + (c0 + j) * 9 + 3 * a;                         // wave-uniform: scalar loads
+            double s = static_cast<double>(g[0]) * p[0];                          // products of two floats are exact in float64
+            s = fma(static_cast<double>(g[1]), static_cast<double>(p[1]), s);
+            s = fma(static_cast<double>(g[2]), static_cast<double>(p[2]), s);
+            if constexpr (NOISE) s = fma(static_cast<double>(sigma), nz[a], s);
+            q[a] = static_cast<float>(s);
+        }
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            const float tot = wave_allsum(q[i / 3] * p[i % 3]);
+            h[i] = (lane == j) ? tot : h[i];
+        }
+    }
+    const bool active = lane < nc;
+    float r[9];
+    so3::project_rotation<float>(h, r);
+    if (active) {
+        float *out = R + (c0 + lane) * 9;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) out[i] = r[i];
+        if (H != nullptr) {
+            float *ho = H + (c0 + lane) * 9;
+#pragma unroll
+            for (int i = 0; i < 9; ++i) ho[i] = h[i];
+        }
+    }
+}
+
 // ---- row a7 (cloud side of the Kabsch / PointNet path) ----------------------------------------------------------
 // (a) the training loop's pairing rule, point_cloud/main.py:173-181: q_i = R_b p_i for every point of cloud b, written
 //     either as (B,N,3) or already transposed to the (B,3,N) layout the network consumes (`gg = pc_out.transpose(1,2)`);
@@ -1224,7 +1292,9 @@ __global__ __launch_bounds__(kBlock) void k_pc_normalize(const float *__restrict
         const so3::rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(P) + (c0 + j) * N * 3, 0, cloud_bytes, so3::kRsrcFlags);
         const so3::rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(out + (c0 + j) * N * 3, 0, cloud_bytes, so3::kRsrcFlags);
         // pass 1: bounding box.  Out-of-range lanes read zeros, which must not enter the box: they are masked by index.
-        float hi[3] = {-inf, -inf, -inf}, lo[3] = {inf, inf, inf};
+        // fmaxf / fminf drop a NaN operand where numpy's max / min (prepare.py:52) hand it on: the last NaN coordinate a lane has seen
+        // on an axis is kept beside the box (a select; a zero-filled slot is no NaN) and given back to the box after the wave's reduction.
+        float hi[3] = {-inf, -inf, -inf}, lo[3] = {inf, inf, inf}, bad[3] = {0.f, 0.f, 0.f};
         u32x3 pp[kU];
         for (int i0 = 0; i0 < N; i0 += 64 * kU) {
 #pragma unroll
@@ -1235,12 +1305,15 @@ __global__ __launch_bounds__(kBlock) void k_pc_normalize(const float *__restrict
                 const float px = __uint_as_float(pp[u].x), py = __uint_as_float(pp[u].y), pz = __uint_as_float(pp[u].z);
                 hi[0] = fmaxf(hi[0], in ? px : -inf); hi[1] = fmaxf(hi[1], in ? py : -inf); hi[2] = fmaxf(hi[2], in ? pz : -inf);
                 lo[0] = fminf(lo[0], in ? px : inf);  lo[1] = fminf(lo[1], in ? py : inf);  lo[2] = fminf(lo[2], in ? pz : inf);
+                bad[0] = px != px ? px : bad[0]; bad[1] = py != py ? py : bad[1]; bad[2] = pz != pz ? pz : bad[2];
             }
         }
         float c[3], ext2 = 0.f;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const float mx = wave_allmax(hi[k]), mn = -wave_allmax(-lo[k]);
+            const bool nan_k = so3::hw::any_lane(bad[k] != bad[k]);    // wave-uniform: a select on the scalar unit's condition, no branch
+            const float nan = __builtin_nanf("");
+            const float mx = nan_k ? nan : wave_allmax(hi[k]), mn = nan_k ? nan : -wave_allmax(-lo[k]);
             c[k] = (mx + mn) * 0.5f;                                   // prepare.py:52
             const float e = (mx - c[k]) - (mn - c[k]);                 // :54 on the centred cloud
             ext2 = fmaf(e, e, ext2);
@@ -3841,8 +3914,12 @@ int so3_kabsch_synth_f32(const float *P, const float *Rgt, float sigma, uint32_t
     if (cpw > 64) cpw = 64;
     const int64_t waves = (B + cpw - 1) / cpw;
     const int64_t blocks = (waves + (kBlock / 64) - 1) / (kBlock / 64);
-    hipLaunchKernelGGL((sigma != 0.f ? k_kabsch_synth<true> : k_kabsch_synth<false>), dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), P, Rgt, sigma,
-                       seed, R, H, B, N, static_cast<int>(cpw));
+    if (N <= kSynthFew)      // a few points a cloud: q rounded once (k_kabsch_synth_few)
+        hipLaunchKernelGGL((sigma != 0.f ? k_kabsch_synth_few<true> : k_kabsch_synth_few<false>), dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0,
+                           static_cast<hipStream_t>(stream), P, Rgt, sigma, seed, R, H, B, N, static_cast<int>(cpw));
+    else
+        hipLaunchKernelGGL((sigma != 0.f ? k_kabsch_synth<true> : k_kabsch_synth<false>), dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), P, Rgt, sigma,
+                           seed, R, H, B, N, static_cast<int>(cpw));
     return check_launch("so3_kabsch_synth_f32");
 }
 
