@@ -283,7 +283,7 @@ int so3_se3_update_bwd_f32(const float *out12, const float *Tinit, const float *
  * Replaces rotation_representation.py:21-36 (compute_rotation_matrix_from_ortho6d; duplicate at :174-189),
  * the reference's main comparison head (transform_output['6D'], Comparison/models.py:19).
  *   X in B*6 float32;  R out B*9 float32;  G in B*9 float32 (dL/dR);  dX out B*6 float32.
- * No epsilon in the norms, as in the reference: a zero or parallel pair gives Inf/NaN.
+ * No epsilon in the norms, as in the reference: a zero or parallel pair gives Inf/NaN.  Input range: see the heads below.
  */
 int so3_ortho6d_fwd_f32(const float *X, float *R, int64_t B, void *stream);
 int so3_ortho6d_bwd_f32(const float *X, const float *G, float *dX, int64_t B, void *stream);
@@ -302,6 +302,25 @@ int so3_ortho6d_bwd_f32(const float *X, const float *G, float *dX, int64_t B, vo
  * gets from autograd through the same formulas).  Degenerate input behaves like the reference's float32 graph
  * (zero 5D tail or zero 6D halves: Inf/NaN), except that an exactly-zero quaternion gives the clamped
  * gradient G-terms/1e-8 where autograd yields NaN.
+ *
+ * INPUT RANGE OF THE HEADS (tests/heads_ref.py; pinned by tests/test_heads_host.py and tests/test_gpu_heads.py).
+ * Inside it every row agrees with the float64 evaluation of the same float32 input within  C u cond,  u = 2^-24,
+ * C <= 43 (forward) and <= 31 (backward, in the gradient's own unit: see heads_ref), on the device as on the host:
+ *   quat     |q| = 0 and 1e-25 <= |q| <= 1e18.  |q| <= 1e-8 (|q| = 0 too) divides by the constant 1e-8f; q = 0 gives
+ *            R = I and a zero gradient.  ABOVE: once |q|^2 overflows (|q| >= 1.9e19) 1/|q| is 0: R = I, gradient 0.
+ *   euler    every finite angle (tested to 1e6; sin / cos are the full-range forms, cond = 1).
+ *   expmap   every finite v with finite |v|^2; cond = max(1, |v|).  A row within 4 u of |v|^2 = 1e-4 may take
+ *            either side of the clamp in its gradient (the forward is continuous there).
+ *   ortho6d  each half with 1e-30 <= |.| <= 1e30, independently (the range tested); cond = 1 / sin(a, b).  Both halves
+ *            are prescaled by an exact power of two, so neither |a|^2 nor |a x b|^2 = |b|^2 sin^2 overflows or falls
+ *            among the subnormals (which v_rsq_f32 reads as 0).  The gradient is of size |G| / (|a| sin), |G| / (|b| sin).
+ *            Nothing is promised for subnormal halves or components of 2^127 and above (there the scale itself is
+ *            subnormal).  A zero half or parallel halves: Inf / NaN.
+ *   ortho5d  X[2:5] and X[0:2] with 1e-10 <= |.| <= 1e10 each (the magnitudes tested); cond = 1 / sin of the
+ *            un-projected pair.  BELOW (s = |v|^2 = 0): R[0] = R[3] = 0, every other slot NaN.  ABOVE (s = inf):
+ *            every slot NaN.
+ * Between the range and those magnitudes a squared norm is subnormal and nothing is promised about the values.
+ * In every case the damage stays in its row: a NaN, an inf or an out-of-range row changes no other row.
  */
 int so3_quat_fwd_f32(const float *X, float *R, int64_t B, void *stream);
 int so3_quat_bwd_f32(const float *X, const float *G, float *dX, int64_t B, void *stream);

@@ -181,7 +181,7 @@ def sample_rotations_axis_angle_np(rng, batch):
     theta = rng.uniform(-1.0, 1.0, batch) * np.pi                   # :23
     sin = np.sin(theta)                                             # :24
     axis = rng.standard_normal((batch, 3))                          # :25
-    axis = axis / np.maximum(np.linalg.norm(axis, axis=1, keepdims=True), 1e-8)   # :26 / :12-18
+    axis = axis / np.maximum(np.linalg.norm(axis, axis=1, keepdims=True), float(np.float32(1e-8)))   # :26 / :12-18
     qw = np.cos(theta)                                              # :27
     qx, qy, qz = axis[:, 0] * sin, axis[:, 1] * sin, axis[:, 2] * sin   # :28-30
     xx, yy, zz = qx * qx, qy * qy, qz * qz
@@ -197,7 +197,7 @@ def rotations_from_draws_np(theta, axis):
     """The arithmetic of the reference sampler (point_cloud/prepare.py:24-47) for given draws theta (B,), axis (B,3)."""
     theta = np.asarray(theta, np.float64)
     axis = np.asarray(axis, np.float64)
-    axis = axis / np.maximum(np.linalg.norm(axis, axis=1, keepdims=True), 1e-8)
+    axis = axis / np.maximum(np.linalg.norm(axis, axis=1, keepdims=True), float(np.float32(1e-8)))
     sin, qw = np.sin(theta), np.cos(theta)
     qx, qy, qz = axis[:, 0] * sin, axis[:, 1] * sin, axis[:, 2] * sin
     xx, yy, zz, xy, xz, yz = qx * qx, qy * qy, qz * qz, qx * qy, qx * qz, qy * qz
@@ -377,10 +377,13 @@ def ortho6d_backward_np(poses, g):
 # next row f5: the other heads of the dispatch tables.  Restated op for op with torch (float64 by default) so
 # that the backward is autograd through the same graph the reference differentiates -- no closed forms here.
 # --------------------------------------------------------------------------------------------
+QUAT_MIN_NORM = float(np.float32(1e-8))    # the reference's torch.FloatTensor([1e-8]) (rotation_representation.py:47, prepare.py:15): 1.0000000117e-8
+
+
 def quat_torch(q):
     """(B,4) (w,x,y,z) -> (B,3,3); rotation_representation.py:39-50 (normalize_vector) and :137-171."""
     mag = torch.sqrt(q.pow(2).sum(1))                                            # :46
-    mag = torch.max(mag, torch.tensor([1e-8], dtype=q.dtype))                    # :47
+    mag = torch.max(mag, torch.tensor([QUAT_MIN_NORM], dtype=q.dtype))           # :47  (a FloatTensor: float32(1e-8), in any dtype)
     n = q / mag.view(-1, 1)                                                      # :48-49
     w, x, y, z = n[:, 0:1], n[:, 1:2], n[:, 2:3], n[:, 3:4]                      # :148-151
     xx, yy, zz, xy, xz, yz, xw, yw, zw = x * x, y * y, z * z, x * y, x * z, y * z, x * w, y * w, z * w   # :154-162

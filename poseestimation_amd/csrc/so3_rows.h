@@ -1520,8 +1520,18 @@ struct OpAngleBwd : OpBase {
 
 // ---- next row f2: the 6D Gram-Schmidt head (rotation_representation.py:21-36) --------------------------------
 // x = a/|a|,  z = (x x b)/|x x b|,  y = z x x,  R = [x y z] (columns); a, b = the two halves of the 6-vector.
-template <class T> __device__ __forceinline__ void ortho6d_forward(V3<T> a, V3<T> b, T (&r)[9]) {
+// Both squared norms are taken of vectors prescaled by an exact power of two (largest |component| in [0.5, 1), as signed_svd does):
+// |a|^2 and |x x b|^2 = |b|^2 sin^2 then neither overflow nor fall among the subnormals, which v_rsq_f32 reads as 0 -- halves of 1e-18
+// at a sine of 0.1 gave inf / NaN on the device (5.8e-39) and finite rows on the host.  x, y, z are the same bits as without it.
+template <class T> __device__ __forceinline__ V3<T> pow2_prescaled(V3<T> v, T &sc) {
     typedef Tr<T> R;
+    sc = R::ldexp(R::splat(1.f), R::neg_frexp_exp(R::max(R::max(R::abs(v.x), R::abs(v.y)), R::abs(v.z))));
+    return scale<T>(v, sc);
+}
+template <class T> __device__ __forceinline__ void ortho6d_forward(V3<T> a_in, V3<T> b_in, T (&r)[9]) {
+    typedef Tr<T> R;
+    T sa, sb;
+    const V3<T> a = pow2_prescaled<T>(a_in, sa), b = pow2_prescaled<T>(b_in, sb);
     const V3<T> x = scale<T>(a, R::rsq(dot(a, a)));
     const V3<T> w = cross<T>(x, b);
     const V3<T> z = scale<T>(w, R::rsq(dot(w, w)));
@@ -1533,11 +1543,14 @@ template <class T> __device__ __forceinline__ void ortho6d_forward(V3<T> a, V3<T
 // G = dL/dR (row-major)  ->  dL/da, dL/db
 template <class T> __device__ __forceinline__ void ortho6d_backward(V3<T> a, V3<T> b, const T (&g)[9], V3<T> &ga, V3<T> &gb) {
     typedef Tr<T> R;
-    const T ia = R::rsq(dot(a, a));
-    const V3<T> x = scale<T>(a, ia);
-    const V3<T> w = cross<T>(x, b);
-    const T iw = R::rsq(dot(w, w));
-    const V3<T> z = scale<T>(w, iw);
+    T sa, sb;
+    const V3<T> as = pow2_prescaled<T>(a, sa), bs = pow2_prescaled<T>(b, sb);
+    const T ias = R::rsq(dot(as, as));
+    const V3<T> x = scale<T>(as, ias);
+    const V3<T> ws = cross<T>(x, bs);                    // (x x b) sb
+    const T iws = R::rsq(dot(ws, ws));
+    const V3<T> z = scale<T>(ws, iws);
+    const T ia = ias * sa, iw = iws * sb;               // 1 / |a|, 1 / |x x b|
     const V3<T> gx = mk<T>(g[0], g[3], g[6]), gy = mk<T>(g[1], g[4], g[7]), gz = mk<T>(g[2], g[5], g[8]);   // columns of G
     // y = z x x :  gz += x x gy ,  gx += gy x z
     const V3<T> gzt = axpy<T>(R::splat(1.f), cross<T>(x, gy), gz);

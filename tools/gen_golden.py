@@ -930,7 +930,53 @@ def g22_pointnet(seed=24):
     save("g22_pointnet.npz", **arrays)
 
 
+def g23_head_edges():
+    """The forward heads at their edges (tests/heads_ref.py: every family, every fourth row -- 32 of 128): the reference's own float32
+    outputs and autograd gradients, float64 too where the reference's code keeps float64 (not the 5D head: float32 zeros, :82; not
+    calculate_T_pred: .float(), utility.py:123).  Shows that oracle/so3_oracle.py's float64 restatement takes the reference's clamps
+    (max(|q|, 1e-8), clamp(|v|^2, 1e-4)) at the edges G10's randn rows never reach."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+    import heads_ref as hr
+    heads = {"quat": rr.compute_rotation_matrix_from_quaternion, "euler": rr.compute_rotation_matrix_from_euler,
+             "ortho5d": rr.compute_rotation_matrix_from_ortho5d, "expmap": rr.vec_3d_to_SO3, "ortho6d": rr.compute_rotation_matrix_from_ortho6d}
+    out = {}
+    for name, fn in heads.items():
+        d = hr.data(name)
+        rows = np.arange(0, len(d["x"]), 4)
+        x, g = torch.as_tensor(d["x"][rows].copy()), torch.as_tensor(d["g"][rows].copy()).view(-1, 3, 3)
+        xf = x.clone().requires_grad_(True)
+        r = fn(xf)
+        r.backward(g)
+        out.update({name + "_rows": rows.astype(np.int32), name + "_x": x, name + "_r": r.detach().reshape(-1, 9), name + "_dx": xf.grad})
+        if name != "ortho5d":
+            xd = x.double().requires_grad_(True)
+            rd = fn(xd)
+            rd.backward(g.double())
+            assert rd.dtype == torch.float64
+            out.update({name + "_r_f64": rd.detach().reshape(-1, 9), name + "_dx_f64": xd.grad})
+
+    def combine(R, tx, ty, tz, device="cpu"):                 # see g8_se3_update
+        T = torch.ones((R.shape[0], 4, 4))
+        T[:, :3, :3] = R
+        T[:, 0, 3], T[:, 1, 3], T[:, 2, 3] = tx, ty, tz
+        T[:, 3, :3] = 0
+        return T
+    calc, scene = functions_from(os.path.join(REF, "Iterative", "utility.py"), ["calculate_T_pred", "get_scene_parameters"])
+    calc.__globals__.update(symmetric_orthogonalization=rr.symmetric_orthogonalization, combine=combine, get_scene_parameters=scene)
+    d = hr.data("se3_update")
+    rows = np.arange(0, len(d["x"]), 4)
+    o = torch.as_tensor(d["x"][rows].copy()).requires_grad_(True)
+    tp = calc(o, torch.as_tensor(d["t"][rows].copy()).view(-1, 4, 4), "cpu")
+    tp.backward(torch.as_tensor(d["g"][rows].copy()).view(-1, 4, 4))
+    assert abs(scene()[0] - hr.FX) < 1e-9 and abs(scene()[1] - hr.FY) < 1e-9
+    out.update(se3_update_rows=rows.astype(np.int32), se3_update_x=o.detach(), se3_update_r=tp.detach().reshape(-1, 16), se3_update_dx=o.grad)
+    save("g23_head_edges.npz", **out)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "g23":
+        return g23_head_edges()
     if len(sys.argv) > 1 and sys.argv[1] == "g22":
         return g22_pointnet()
     if len(sys.argv) > 1 and sys.argv[1] == "g21":
@@ -974,6 +1020,7 @@ def main():
     g20_rigid_align()
     g21_icp()
     g22_pointnet()
+    g23_head_edges()
     # ---- G1: config #1, 256 Gaussian rows ------------------------------------------------------
     torch.manual_seed(0)
     x = torch.randn(256, 9)
