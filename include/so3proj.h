@@ -589,6 +589,61 @@ int so3_fps_f32(const float *xyz, const int32_t *start, int32_t *out, int64_t B,
 int so3_ball_query_f32(const float *xyz, const float *centres, float radius, int32_t nsample, int32_t *idx, int32_t *count,
                        int64_t B, int32_t N, int32_t S, void *stream);
 
+/* ---- PointNet++ feature propagation: the three nearest known points and their interpolation (added in 210) ----
+ * The non-GEMM half of the reference's PointNetFeaturePropagation.forward (point_cloud/pointnet_utils.py:283-293): a (B,N,S)
+ * distance tensor, a full sort along S to keep three columns, five element-wise launches for the weights, a (B,N,3,D) gather,
+ * a product and a sum -- here one launch for the search, one for the interpolation and one for its backward.
+ *
+ * THE ARITHMETIC IS A DEFINITION.
+ *   d(n, s) is the d(j, c) of the sampling section above between unknown point n and known point s:
+ *       ((dx * dx) + (dy * dy)) + (dz * dz) from coordinate differences, every operation rounded to float32 on its own, no
+ *       fused multiply-add.
+ *   The neighbours of n are the three smallest under the order "smaller d first, among equal d the LOWER index first",
+ *   written in that order.
+ *   S < 3 is legal: the min(3, S) real neighbours come first; the remaining slots repeat slot 0's index with dist2 = +inf and
+ *   weight 0.
+ *   The weights:  r_k = 1.0f / (d_k + 1e-8f)  (r_k = 0 for a padded slot);   w_k = r_k / ((r_0 + r_1) + r_2).
+ *       Every addition and every division is an IEEE-754 operation rounded to float32 on its own (the library is built without
+ *       fast-math: the divisions are correctly rounded divisions, not reciprocal approximations).  S == 1 gives exactly 1.
+ *   The interpolation, in this order:  out = fma(w_2, f_2, fma(w_1, f_1, w_0 * f_0)), f_k = feat[idx_k][c]: one rounded
+ *       product and two fused multiply-adds, each rounded once.
+ *   The backward:  grad_feat[b][s][c] = sum of w(n,k) * grad_out[b][n][c] over all (n, k) with idx[b][n][k] == s, accumulated
+ *       in ASCENDING (n, k) from 0 by  acc = fma(w, g, acc).  The order is part of the definition.
+ *   KNOWN DIFFERENCE from the reference: it takes d from the expanded form |a|^2 + |b|^2 - 2 a.b (square_distance, :12-31).
+ *   Two known points whose distances to n differ by a few 1e-7 (unit-radius clouds) can swap there, and a true distance of 0 --
+ *   every second row where the known points are a subset of the unknown ones, as in the model's fp1 and fp2 -- comes out as
+ *   +-1e-7 of cancellation noise, which 1 / (d + 1e-8) turns into arbitrary, even negative, weights.  Here a coincident point
+ *   has d == 0 exactly and weight 1 - O(1e-8 / d_1).
+ *   A d that overflows float32 and non-finite coordinates give unspecified neighbours and weights, but every index stays in
+ *   [0, S) and the kernels terminate.
+ *
+ * so3_three_nn_f32:
+ *   unknown  in   B*N*3 float32;   known in B*S*3 float32
+ *   dist2    out  B*N*3 float32: d of the three neighbours, ascending
+ *   idx      out  B*N*3 int32
+ *   weight   out  optional B*N*3 float32
+ *   1 <= N, S <= SO3_ADD_S_MAX_N.  The known cloud goes through on-chip memory in tiles; a launch with few unknown points splits
+ *   every point's scan over four waves and merges their lists on (d, idx) -- the result does not depend on the split.
+ * so3_three_interpolate_f32 / so3_three_interpolate_bwd_f32: both layouts are contiguous;
+ *   channels_first == 0:  feat (B,S,D) -> out (B,N,D);   grad_out (B,N,D) -> grad_feat (B,S,D)   (the reference's internal layout)
+ *   channels_first != 0:  feat (B,D,S) -> out (B,D,N);   grad_out (B,D,N) -> grad_feat (B,D,S)   (what the layer receives and
+ *                         what its Conv1d takes)
+ *   idx      in   B*N*3 int32, each in [0, S).  An index outside is the CALLER'S ERROR; it is clamped into the range by the
+ *                 forward and by the backward alike, so it cannot make a kernel touch memory outside the buffers.
+ *   weight   in   B*N*3 float32 (any values: the weights need not come from so3_three_nn_f32)
+ *   1 <= D <= SO3_THREE_MAX_D.  The backward writes EVERY element of grad_feat (0 for a known point nobody selected); there is
+ *   no gradient with respect to weight, idx or the coordinates.
+ * None of the three uses atomics, a workspace or a memset, none synchronises with the host; all can be captured in a graph
+ * and give the same bits from call to call.  B == 0 is a no-op whatever the pointers.
+ */
+#define SO3_THREE_MAX_D 65536
+int so3_three_nn_f32(const float *unknown, const float *known, float *dist2, int32_t *idx, float *weight, int64_t B, int32_t N,
+                     int32_t S, void *stream);
+int so3_three_interpolate_f32(const float *feat, const int32_t *idx, const float *weight, float *out, int32_t channels_first,
+                              int64_t B, int32_t N, int32_t S, int32_t D, void *stream);
+int so3_three_interpolate_bwd_f32(const float *grad_out, const int32_t *idx, const float *weight, float *grad_feat,
+                                  int32_t channels_first, int64_t B, int32_t N, int32_t S, int32_t D, void *stream);
+
 /* ---- next row: on-device pair synthesis for Kabsch ------------------------------
  * so3_rotations_axis_angle_f32: the arithmetic of the reference's sampler, point_cloud/prepare.py:21-49
  *   (normalize_vector :12-18, quaternion (cos theta, axis sin theta) -> matrix :27-47), given the random

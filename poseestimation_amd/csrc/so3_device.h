@@ -1280,4 +1280,80 @@ inline void fps_shape(int N, int &ppl, int &block) {
     while (ppl * block < N) ppl <<= 1;           // 256 x {1, 2, 4, 8}, 1024 x {4, 8, 16}
 }
 
+// ---- PointNet++ feature propagation: the three nearest known points and the inverse-distance interpolation (so3proj.hip:
+// k_three_nn, k_three_interp, k_three_interp_bwd_*; tests/host_model/three_nn.cpp) --------------------------------------------------
+// The search's arithmetic is a DEFINITION (include/so3proj.h): d(n, s) = pointnet_dist2 above; the result is the three smallest under
+// "smaller d first, among equal d the lower index first".  A list is three (d, j) pairs sorted that way; it starts as three
+// (+inf, kThreeNnNone) entries, which lose against every real candidate with a finite d.  three_nn_put<false> is the scan's update:
+// candidates arrive in ascending j, so the strict < alone gives the tie rule.  three_nn_put<true> compares (d, j) lexicographically:
+// the merge of lists that were scanned over different slices of the known cloud.  A NaN d fails every <, so it never enters a list
+// and the lists stay sorted.  The top three under a total order do not depend on how the candidates were split or merged.
+constexpr int kThreeNnNone = 0x7fffffff;
+template <bool LEX>
+__device__ __forceinline__ void three_nn_put(float d, int j, float (&D)[3], int (&J)[3]) {
+    const bool c0 = d < D[0] || (LEX && d == D[0] && j < J[0]);
+    const bool c1 = d < D[1] || (LEX && d == D[1] && j < J[1]);
+    const bool c2 = d < D[2] || (LEX && d == D[2] && j < J[2]);
+    D[2] = c1 ? D[1] : (c2 ? d : D[2]);
+    J[2] = c1 ? J[1] : (c2 ? j : J[2]);
+    D[1] = c0 ? D[0] : (c1 ? d : D[1]);
+    J[1] = c0 ? J[0] : (c1 ? j : J[1]);
+    D[0] = c0 ? d : D[0];
+    J[0] = c0 ? j : J[0];
+}
+// What is written for a finished list: slot k < min(3, S) keeps its neighbour (an index that never got a candidate -- non-finite
+// coordinates only -- is clamped into the cloud); the slots past S repeat slot 0's index with d = +inf.
+__device__ __forceinline__ void three_nn_finish(int32_t S, float (&D)[3], int (&J)[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const bool real = k < S;
+        J[k] = real ? (J[k] < S - 1 ? J[k] : S - 1) : J[0];
+        D[k] = real ? D[k] : __builtin_huge_valf();
+    }
+}
+// The inverse-distance weights, every operation rounded to float32 on its own (contraction off; the library is built without
+// fast-math, so the divisions are IEEE-754 correctly rounded divisions, not reciprocal approximations; the host model's are too):
+//     r_k = 1.0f / (d_k + 1e-8f)  for k < min(3, S),  r_k = 0 for a padded slot;   w_k = r_k / ((r_0 + r_1) + r_2).
+// S == 1: w_0 = r_0 / ((r_0 + 0) + 0) = 1 exactly.
+#pragma clang fp contract(off)
+__device__ __forceinline__ void three_nn_weights(int32_t S, const float (&D)[3], float (&W)[3]) {
+    const float r0 = 1.0f / (D[0] + 1e-8f);
+    const float r1 = S > 1 ? 1.0f / (D[1] + 1e-8f) : 0.f;
+    const float r2 = S > 2 ? 1.0f / (D[2] + 1e-8f) : 0.f;
+    const float r01 = r0 + r1;
+    const float sum = r01 + r2;
+    W[0] = r0 / sum;
+    W[1] = r1 / sum;
+    W[2] = r2 / sum;
+}
+// The interpolation's fixed order: one rounded product, then two fused multiply-adds (each rounds once):
+//     out = fma(w_2, f_2, fma(w_1, f_1, w_0 * f_0)).
+// The backward's running sum takes its hits in ascending (n, k) through  acc = fma(w, g, acc).
+__device__ __forceinline__ float three_interp(float w0, float w1, float w2, float f0, float f1, float f2) {
+    const float p0 = w0 * f0;
+#ifdef SO3_HOST_MODEL
+    return std::fmaf(w2, f2, std::fmaf(w1, f1, p0));
+#else
+    return __builtin_fmaf(w2, f2, __builtin_fmaf(w1, f1, p0));
+#endif
+}
+__device__ __forceinline__ float three_interp_bwd_add(float w, float g, float acc) {
+#ifdef SO3_HOST_MODEL
+    return std::fmaf(w, g, acc);
+#else
+    return __builtin_fmaf(w, g, acc);
+#endif
+}
+#pragma clang fp contract(fast)
+// k_three_nn<WPP, WEIGHT>: the waves that share an unknown point's scan.  One wave per 64 points leaves most of the chip idle at the
+// model's sizes (32 x 1024 points are 512 waves for 1024 SIMDs), so a launch with few work items splits every point's scan over four
+// waves, which merge their lists through LDS (DESIGN.md section 7f holds the measurement).  A short known cloud is not worth the merge.
+constexpr int kThreeNnTile = 1024;                // known points per LDS tile (so3proj.hip: kAddsTile)
+constexpr int kThreeNnSplitItems = 1024;          // fewer work items of 256 points than this: four waves per point
+constexpr int kThreeNnSplitS = 64;                // ... when the known cloud has at least this many points
+constexpr int kThreeBwdChannels = 256;            // k_three_interp_bwd_cl: the channels of one pass (four per lane)
+inline int three_nn_waves_per_point(int64_t B, int32_t N, int32_t S) {
+    return (S >= kThreeNnSplitS && B * ((N + kIcpBlock - 1) / kIcpBlock) < kThreeNnSplitItems) ? 4 : 1;
+}
+
 }  // namespace so3

@@ -1921,6 +1921,245 @@ __global__ __launch_bounds__(kBlock) void k_ball_query(const float *__restrict__
     }
 }
 
+// ---- PointNet++ feature propagation: three nearest known points, inverse-distance interpolation and its backward -------------------
+constexpr int kThreeMaxGrid = 8192;      // workgroups of a launch; more work items are strided over
+
+// k_three_nn<WPP, WEIGHT>: k_icp_step<false>'s skeleton with a sorted top three per lane.  One work item = kBlock / WPP unknown points
+// of one cloud; the known cloud goes through LDS in tiles of kAddsTile float4 and every lane of a wave reads the same float4 per step.
+// Thread tid keeps point tid % (kBlock / WPP) and scans slice tid / (kBlock / WPP): the tile's blocks of kAddsUnroll entries are dealt
+// to the WPP slices in turn, so a wave's lanes share their slice and the LDS read stays a broadcast.  A tile's tail is padded with
+// x = +inf, whose d is +inf (or NaN) and never enters a list.  Slices 1.. hand their lists to slice 0 through LDS, which merges them
+// lexicographically on (d, j) (so3::three_nn_put<true>), finishes the row and writes it.  No atomics, no workspace, no scratch.
+template <int WPP, bool WEIGHT>
+__global__ __launch_bounds__(kBlock) void k_three_nn(const float *__restrict__ unknown, const float *__restrict__ known, float *__restrict__ dist2,
+                                                     int32_t *__restrict__ idx, float *__restrict__ weight, int64_t B, int32_t N, int32_t S,
+                                                     int32_t chunks) {
+    static_assert(kAddsTile == so3::kThreeNnTile && kBlock == so3::kIcpBlock, "the dispatch's constants");
+    constexpr int kPts = kBlock / WPP;
+    __shared__ float4 tile[kAddsTile];
+    __shared__ float part_d[WPP > 1 ? WPP - 1 : 1][3][kPts];
+    __shared__ int part_j[WPP > 1 ? WPP - 1 : 1][3][kPts];
+    const int tid = threadIdx.x, pt = tid % kPts, slice = tid / kPts;
+    const int64_t items = B * chunks;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t b = item / chunks;
+        const int i = static_cast<int>(item - b * chunks) * kPts + pt;
+        const float *src = unknown + b * N * 3, *tgt = known + b * S * 3;
+        const int ic = min(i, N - 1);                                              // a slot beyond the cloud repeats its last point; not stored
+        const float x = src[ic * 3 + 0], y = src[ic * 3 + 1], z = src[ic * 3 + 2];
+        float D[3] = {__builtin_huge_valf(), __builtin_huge_valf(), __builtin_huge_valf()};
+        int J[3] = {so3::kThreeNnNone, so3::kThreeNnNone, so3::kThreeNnNone};
+        for (int t0 = 0; t0 < S; t0 += kAddsTile) {
+            const int cnt = min(kAddsTile, S - t0);
+            const int cntp = (cnt + kAddsUnroll - 1) / kAddsUnroll * kAddsUnroll;      // <= kAddsTile
+            __syncthreads();                                                         // the previous tile has been read
+            for (int k = tid; k < cntp; k += kBlock) {
+                const int j = t0 + min(k, cnt - 1);
+                float4 q;
+                q.x = k < cnt ? tgt[j * 3 + 0] : __builtin_huge_valf(); q.y = tgt[j * 3 + 1]; q.z = tgt[j * 3 + 2]; q.w = 0.f;
+                tile[k] = q;
+            }
+            __syncthreads();
+            for (int k = slice * kAddsUnroll; k < cntp; k += WPP * kAddsUnroll) {
+#pragma unroll
+                for (int kk = 0; kk < kAddsUnroll; ++kk) {
+                    const f32x4 q = *(const volatile lds_f32x4 *)(&tile[k + kk]);     // k_add_s: the ds_read_b128 broadcast
+                    so3::three_nn_put<false>(so3::pointnet_dist2(q.x, q.y, q.z, x, y, z), t0 + k + kk, D, J);
+                }
+            }
+        }
+        if (WPP > 1) {
+            if (slice > 0) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) { part_d[slice - 1][k][pt] = D[k]; part_j[slice - 1][k][pt] = J[k]; }
+            }
+            __syncthreads();                                                         // the next write to part comes two barriers later
+            if (slice > 0) continue;
+#pragma unroll
+            for (int w = 0; w < WPP - 1; ++w) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) so3::three_nn_put<true>(part_d[w][k][pt], part_j[w][k][pt], D, J);
+            }
+        }
+        so3::three_nn_finish(S, D, J);
+        if (i < N) {
+            const int64_t at = (b * N + i) * 3;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { dist2[at + k] = D[k]; idx[at + k] = J[k]; }
+            if (WEIGHT) {
+                float W[3];
+                so3::three_nn_weights(S, D, W);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) weight[at + k] = W[k];
+            }
+        }
+    }
+}
+
+// k_three_interp<CF>: out = fma(w2, f2, fma(w1, f1, w0 * f0)) (so3::three_interp).  An index outside [0, S) is clamped, so a bad index
+// buffer cannot read out of bounds.
+// CF = false, (B,S,D) -> (B,N,D): a group of gw = min(64, D rounded up to a power of two) lanes per unknown point, 64 / gw points per
+//   wave; the lanes run over the channels, so the three feature rows are read and the output row is written contiguously.
+// CF = true, (B,D,S) -> (B,D,N): one work item = kBlock unknown points x kThreeCfChannels channels of one cloud; a lane keeps its
+//   point's indices and weights and walks the channels, so every store is contiguous over n and every load is a gather inside one
+//   feature row of S floats.
+constexpr int kThreeCfChannels = 16;
+template <bool CF>
+__global__ __launch_bounds__(kBlock) void k_three_interp(const float *__restrict__ feat, const int32_t *__restrict__ idx, const float *__restrict__ weight,
+                                                         float *__restrict__ out, int64_t B, int32_t N, int32_t S, int32_t D, int32_t gw) {
+    if (!CF) {
+        const int lane = threadIdx.x & 63, sub = lane / gw, c0 = lane % gw, rpw = 64 / gw;
+        const int64_t wave = static_cast<int64_t>(blockIdx.x) * (kBlock / 64) + (threadIdx.x >> 6);
+        const int64_t nwaves = static_cast<int64_t>(gridDim.x) * (kBlock / 64), rows = B * N;
+        for (int64_t row0 = wave * rpw; row0 < rows; row0 += nwaves * rpw) {
+            const int64_t row = row0 + sub;
+            if (row >= rows) continue;
+            const float *f = feat + row / N * S * D;
+            const int64_t i0 = min(max(idx[row * 3 + 0], 0), S - 1), i1 = min(max(idx[row * 3 + 1], 0), S - 1), i2 = min(max(idx[row * 3 + 2], 0), S - 1);
+            const float w0 = weight[row * 3 + 0], w1 = weight[row * 3 + 1], w2 = weight[row * 3 + 2];
+            for (int c = c0; c < D; c += gw) out[row * D + c] = so3::three_interp(w0, w1, w2, f[i0 * D + c], f[i1 * D + c], f[i2 * D + c]);
+        }
+    } else {
+        const int nchunks = (N + kBlock - 1) / kBlock, cchunks = (D + kThreeCfChannels - 1) / kThreeCfChannels;
+        const int64_t items = B * nchunks * cchunks;
+        for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+            const int64_t b = item / (static_cast<int64_t>(nchunks) * cchunks);
+            const int rest = static_cast<int>(item - b * nchunks * cchunks);
+            const int n = rest % nchunks * kBlock + static_cast<int>(threadIdx.x), cbase = rest / nchunks * kThreeCfChannels;
+            if (n >= N) continue;
+            const int64_t row = b * N + n;
+            const int i0 = min(max(idx[row * 3 + 0], 0), S - 1), i1 = min(max(idx[row * 3 + 1], 0), S - 1), i2 = min(max(idx[row * 3 + 2], 0), S - 1);
+            const float w0 = weight[row * 3 + 0], w1 = weight[row * 3 + 1], w2 = weight[row * 3 + 2];
+            const int cend = min(cbase + kThreeCfChannels, D);
+            for (int c = cbase; c < cend; ++c) {
+                const float *f = feat + (b * D + c) * S;
+                out[(b * D + c) * N + n] = so3::three_interp(w0, w1, w2, f[i0], f[i1], f[i2]);
+            }
+        }
+    }
+}
+
+// The backward as a gather: grad_feat[b][s][c] = sum of w(n,k) * grad_out[b][n][c] over the (n, k) with idx[b][n][k] == s, taken in
+// ascending (n, k) through acc = fma(w, g, acc) (so3::three_interp_bwd_add).  A wave owns known points; it scans the cloud's 3N
+// indices (clamped into [0, S) as the forward clamps them) 64 at a time from LDS, takes the ballot of idx == s and walks the set bits
+// upwards.  Every element of grad_feat is written once, zeros included: no atomics, no memset, no workspace, the same bits every call.
+// k_three_interp_bwd_cl, (B,N,D) -> (B,S,D): one work item = kThreeBwdS known points of one cloud, kThreeBwdS / 4 per wave; the lanes
+//   run over the channels, four per lane (so3::kThreeBwdChannels per pass, further passes scan again), so a hit reads a contiguous row
+//   of grad_out.  Indices and weights go through LDS in tiles of kThreeBwdTile unknown points.
+constexpr int kThreeBwdS = 16;
+constexpr int kThreeBwdTile = 1024;
+__global__ __launch_bounds__(kBlock) void k_three_interp_bwd_cl(const float *__restrict__ grad_out, const int32_t *__restrict__ idx,
+                                                                const float *__restrict__ weight, float *__restrict__ grad_feat, int64_t B, int32_t N,
+                                                                int32_t S, int32_t D) {
+    constexpr int kPerWave = kThreeBwdS / (kBlock / 64), kPerLane = so3::kThreeBwdChannels / 64;
+    __shared__ int32_t t_idx[3 * kThreeBwdTile];
+    __shared__ float t_w[3 * kThreeBwdTile];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int groups = (S + kThreeBwdS - 1) / kThreeBwdS;
+    const int64_t items = B * groups;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t b = item / groups;
+        const int s0 = static_cast<int>(item - b * groups) * kThreeBwdS + wave * kPerWave;
+        const int32_t *ib = idx + b * N * 3;
+        const float *wb = weight + b * N * 3, *gb = grad_out + b * N * D;
+        for (int c0 = 0; c0 < D; c0 += so3::kThreeBwdChannels) {
+            float acc[kPerWave][kPerLane];
+#pragma unroll
+            for (int u = 0; u < kPerWave; ++u)
+#pragma unroll
+                for (int q = 0; q < kPerLane; ++q) acc[u][q] = 0.f;
+            for (int n0 = 0; n0 < N; n0 += kThreeBwdTile) {
+                const int cnt = 3 * min(kThreeBwdTile, N - n0), cntp = (cnt + 63) / 64 * 64;
+                __syncthreads();                                                     // the previous tile has been read
+                for (int k = tid; k < cntp; k += kBlock) {
+                    const int64_t e = static_cast<int64_t>(n0) * 3 + min(k, cnt - 1);
+                    t_idx[k] = k < cnt ? min(max(ib[e], 0), S - 1) : -1;
+                    t_w[k] = wb[e];
+                }
+                __syncthreads();
+#pragma unroll
+                for (int u = 0; u < kPerWave; ++u) {
+                    const int s = s0 + u;                                            // s >= S matches nothing: the indices are clamped
+                    for (int k = 0; k < cntp; k += 64) {
+                        unsigned long long mask = __builtin_amdgcn_ballot_w64(t_idx[k + lane] == s);
+                        while (mask != 0) {                                          // wave-uniform
+                            const int e = k + __builtin_ctzll(mask);
+                            mask &= mask - 1;
+                            const float w = t_w[e];
+                            const float *g = gb + static_cast<int64_t>(n0 + e / 3) * D + c0 + lane;
+#pragma unroll
+                            for (int q = 0; q < kPerLane; ++q)
+                                if (c0 + lane + 64 * q < D) acc[u][q] = so3::three_interp_bwd_add(w, g[64 * q], acc[u][q]);
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < kPerWave; ++u)
+#pragma unroll
+                for (int q = 0; q < kPerLane; ++q)
+                    if (s0 + u < S && c0 + lane + 64 * q < D) grad_feat[(b * S + s0 + u) * D + c0 + lane + 64 * q] = acc[u][q];
+        }
+    }
+}
+
+// k_three_interp_bwd_cf, (B,D,N) -> (B,D,S): one work item = 64 known points x 64 channels of one cloud, sixteen known points per wave,
+//   a lane per channel.  grad_out is contiguous over n, so a tile of 64 unknown points x 64 channels is read row by row (lanes over n)
+//   and stored transposed in LDS (stride 65: no bank conflicts either way); a hit then reads its row with the lanes over the channels.
+//   The sums leave through the same LDS array, transposed back, so the stores to grad_feat are contiguous over s.
+__global__ __launch_bounds__(kBlock) void k_three_interp_bwd_cf(const float *__restrict__ grad_out, const int32_t *__restrict__ idx,
+                                                                const float *__restrict__ weight, float *__restrict__ grad_feat, int64_t B, int32_t N,
+                                                                int32_t S, int32_t D) {
+    constexpr int kPerWave = 64 / (kBlock / 64);
+    __shared__ float gt[64][65];
+    __shared__ int32_t t_idx[192];
+    __shared__ float t_w[192];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int sgroups = (S + 63) / 64, cgroups = (D + 63) / 64;
+    const int64_t items = B * sgroups * cgroups;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t b = item / (static_cast<int64_t>(sgroups) * cgroups);
+        const int rest = static_cast<int>(item - b * sgroups * cgroups);
+        const int sbase = rest % sgroups * 64, c0 = rest / sgroups * 64;
+        const int32_t *ib = idx + b * N * 3;
+        const float *wb = weight + b * N * 3;
+        float acc[kPerWave];
+#pragma unroll
+        for (int u = 0; u < kPerWave; ++u) acc[u] = 0.f;
+        for (int n0 = 0; n0 < N; n0 += 64) {
+            const int cnt = min(64, N - n0);
+            __syncthreads();                                                         // the previous tile (or the previous item's sums) has been read
+            for (int r = wave; r < 64; r += kBlock / 64)
+                gt[lane][r] = (c0 + r < D && lane < cnt) ? grad_out[(b * D + c0 + r) * N + n0 + lane] : 0.f;
+            if (tid < 192) {
+                const int64_t e = static_cast<int64_t>(n0) * 3 + min(tid, 3 * cnt - 1);
+                t_idx[tid] = tid < 3 * cnt ? min(max(ib[e], 0), S - 1) : -1;
+                t_w[tid] = wb[e];
+            }
+            __syncthreads();
+#pragma unroll
+            for (int u = 0; u < kPerWave; ++u) {
+                const int s = sbase + wave * kPerWave + u;
+#pragma unroll
+                for (int k = 0; k < 192; k += 64) {
+                    unsigned long long mask = __builtin_amdgcn_ballot_w64(t_idx[k + lane] == s);
+                    while (mask != 0) {                                              // wave-uniform
+                        const int e = k + __builtin_ctzll(mask);
+                        mask &= mask - 1;
+                        acc[u] = so3::three_interp_bwd_add(t_w[e], gt[e / 3][lane], acc[u]);
+                    }
+                }
+            }
+        }
+        __syncthreads();                                                             // the last tile has been read
+#pragma unroll
+        for (int u = 0; u < kPerWave; ++u) gt[wave * kPerWave + u][lane] = acc[u];
+        __syncthreads();
+        for (int r = wave; r < 64; r += kBlock / 64)
+            if (c0 + r < D && sbase + lane < S) grad_feat[(b * D + c0 + r) * S + sbase + lane] = gt[lane][r];
+    }
+}
+
 // ---- float64 head and backward (the reference's functions accept double tensors): the same templates over
 // T = double, one row per thread with plain loads -- a convenience path, not a benchmark configuration.
 // Four fixed sweeps, then sweeps until the wave-wide residual is below 1e-14 (at most six more).
@@ -3783,6 +4022,63 @@ int so3_ball_query_f32(const float *xyz, const float *centres, float radius, int
     if (count != nullptr) hipLaunchKernelGGL(k_ball_query<true>, grid, block, 0, s, xyz, centres, radius, width, idx, count, B, N, S);
     else hipLaunchKernelGGL(k_ball_query<false>, grid, block, 0, s, xyz, centres, radius, width, idx, count, B, N, S);
     return check_launch("so3_ball_query_f32");
+}
+
+int so3_three_nn_f32(const float *unknown, const float *known, float *dist2, int32_t *idx, float *weight, int64_t B, int32_t N, int32_t S,
+                     void *stream) {
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && S >= 1 && S <= SO3_ADD_S_MAX_N, "so3_three_nn_f32: B/N/S");
+    if (B == 0) return 0;
+    SO3_CHECK_ARGS(unknown != nullptr && known != nullptr && dist2 != nullptr && idx != nullptr, "so3_three_nn_f32: null pointer");
+    const int wpp = so3::three_nn_waves_per_point(B, N, S);
+    const int32_t chunks = (N + kBlock / wpp - 1) / (kBlock / wpp);
+    const dim3 grid(static_cast<unsigned>(std::min<int64_t>(B * chunks, kThreeMaxGrid))), block(kBlock);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool wt = weight != nullptr;
+    g_last_kernel = wpp == 4 ? (wt ? "k_three_nn<4, true>" : "k_three_nn<4, false>") : (wt ? "k_three_nn<1, true>" : "k_three_nn<1, false>");
+#define NN3(WW, TT) hipLaunchKernelGGL((k_three_nn<WW, TT>), grid, block, 0, s, unknown, known, dist2, idx, weight, B, N, S, chunks)
+    if (wpp == 4) { if (wt) NN3(4, true); else NN3(4, false); }
+    else { if (wt) NN3(1, true); else NN3(1, false); }
+#undef NN3
+    return check_launch("so3_three_nn_f32");
+}
+
+int so3_three_interpolate_f32(const float *feat, const int32_t *idx, const float *weight, float *out, int32_t channels_first, int64_t B,
+                              int32_t N, int32_t S, int32_t D, void *stream) {
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && S >= 1 && S <= SO3_ADD_S_MAX_N && D >= 1 && D <= SO3_THREE_MAX_D,
+                   "so3_three_interpolate_f32: B/N/S/D");
+    if (B == 0) return 0;
+    SO3_CHECK_ARGS(feat != nullptr && idx != nullptr && weight != nullptr && out != nullptr, "so3_three_interpolate_f32: null pointer");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int32_t gw = 64;
+    while (gw > 1 && gw / 2 >= D) gw >>= 1;
+    int64_t blocks;
+    if (channels_first) {
+        g_last_kernel = "k_three_interp<true>";
+        blocks = B * ((N + kBlock - 1) / kBlock) * ((D + kThreeCfChannels - 1) / kThreeCfChannels);
+    } else {
+        g_last_kernel = "k_three_interp<false>";
+        const int64_t rows_per_block = (kBlock / 64) * (64 / gw);
+        blocks = (B * N + rows_per_block - 1) / rows_per_block;
+    }
+    const dim3 grid(static_cast<unsigned>(std::min<int64_t>(blocks, kThreeMaxGrid))), block(kBlock);
+    if (channels_first) hipLaunchKernelGGL(k_three_interp<true>, grid, block, 0, s, feat, idx, weight, out, B, N, S, D, gw);
+    else hipLaunchKernelGGL(k_three_interp<false>, grid, block, 0, s, feat, idx, weight, out, B, N, S, D, gw);
+    return check_launch("so3_three_interpolate_f32");
+}
+
+int so3_three_interpolate_bwd_f32(const float *grad_out, const int32_t *idx, const float *weight, float *grad_feat, int32_t channels_first,
+                                  int64_t B, int32_t N, int32_t S, int32_t D, void *stream) {
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && S >= 1 && S <= SO3_ADD_S_MAX_N && D >= 1 && D <= SO3_THREE_MAX_D,
+                   "so3_three_interpolate_bwd_f32: B/N/S/D");
+    if (B == 0) return 0;
+    SO3_CHECK_ARGS(grad_out != nullptr && idx != nullptr && weight != nullptr && grad_feat != nullptr, "so3_three_interpolate_bwd_f32: null pointer");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t blocks = channels_first ? B * ((S + 63) / 64) * ((D + 63) / 64) : B * ((S + kThreeBwdS - 1) / kThreeBwdS);
+    const dim3 grid(static_cast<unsigned>(std::min<int64_t>(blocks, kThreeMaxGrid))), block(kBlock);
+    g_last_kernel = channels_first ? "k_three_interp_bwd_cf" : "k_three_interp_bwd_cl";
+    if (channels_first) hipLaunchKernelGGL(k_three_interp_bwd_cf, grid, block, 0, s, grad_out, idx, weight, grad_feat, B, N, S, D);
+    else hipLaunchKernelGGL(k_three_interp_bwd_cl, grid, block, 0, s, grad_out, idx, weight, grad_feat, B, N, S, D);
+    return check_launch("so3_three_interpolate_bwd_f32");
 }
 
 int so3_add_l1_disentangled_f32(const float *Tpred, const float *Tgt, const float *points, double *loss_sum, float *dTpred,

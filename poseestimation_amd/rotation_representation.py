@@ -1463,6 +1463,136 @@ def sample_and_group(npoint: int, radius: float, nsample: int, xyz: torch.Tensor
 
 
 # --------------------------------------------------------------------------------------------
+# PointNet++ feature propagation (reference: point_cloud/pointnet_utils.py:266-300, PointNetFeaturePropagation.forward)
+# --------------------------------------------------------------------------------------------
+def three_nn(xyz1: torch.Tensor, xyz2: torch.Tensor, return_weights: bool = False):
+    """For every point of xyz1 (B, N, 3) the three nearest points of xyz2 (B, S, 3): (dist2, idx) with dist2 (B, N, 3) float32 the
+    squared distances in ascending order and idx (B, N, 3) int64; with return_weights=True also weight (B, N, 3) float32, the
+    normalised inverse-distance weights of point_cloud/pointnet_utils.py:290-292.  One launch (so3_three_nn_f32) instead of the
+    (B, N, S) distance tensor and its full sort.
+
+    The arithmetic is a definition (include/so3proj.h): d = ((dx * dx) + (dy * dy)) + (dz * dz) from coordinate differences in
+    float32 without fused multiply-add, the three smallest with the lower index first among equal d; r_k = 1 / (d_k + 1e-8),
+    w_k = r_k / ((r_0 + r_1) + r_2).  A point of xyz1 that is also in xyz2 gets d = 0 exactly and (almost) all the weight, where the
+    reference's expanded form returns rounding noise.  S < 3 is legal: the missing slots repeat slot 0's index with dist2 = +inf and
+    weight 0 (S == 1: weight exactly 1, the reference's `repeat` branch).  1 <= N, S <= ADD_S_MAX_N.  Other float dtypes are converted
+    to float32.  Nothing synchronises with the host.  The outputs carry no gradient (nor do the CUDA PointNet++ ops'); a cloud that
+    requires grad is warned about once."""
+    dev, x = _cloud_f32("three_nn", "xyz1", xyz1)
+    _, y = _cloud_f32("three_nn", "xyz2", xyz2)
+    _require_device(x, y)
+    b, n, s = x.shape[0], x.shape[1], y.shape[1]
+    if y.shape[0] != b or n > _lib.ADD_S_MAX_N or s > _lib.ADD_S_MAX_N:
+        raise RuntimeError("three_nn: expected xyz1 (B, N, 3) and xyz2 (B, S, 3) with 1 <= N, S <= %d, got %s and %s"
+                           % (_lib.ADD_S_MAX_N, tuple(xyz1.shape), tuple(xyz2.shape)))
+    if _wants_grad(xyz1, xyz2):
+        _warn_once("three_nn", "three_nn is not differentiable: distances, indices and weights carry no gradient although a cloud requires "
+                               "grad (the reference's autograd reaches xyz through square_distance; nothing in its models sits upstream of xyz).")
+    dist2 = torch.empty((b, n, 3), dtype=torch.float32, device=dev)
+    idx = torch.empty((b, n, 3), dtype=torch.int32, device=dev)
+    weight = torch.empty((b, n, 3), dtype=torch.float32, device=dev) if return_weights else None
+    with _on_device(dev):
+        _check(_libh().so3_three_nn_f32(_ptr(x), _ptr(y), _ptr(dist2), _ptr(idx), _ptr(weight), b, n, s, _stream(dev)), "so3_three_nn_f32")
+    return (dist2, idx.long(), weight) if return_weights else (dist2, idx.long())
+
+
+def _three_args(name, points2, idx, weight, channels_first):
+    """Checked, contiguous float32 / int32 operands of the interpolation and (B, N, S, D)."""
+    dev = _require_device(points2, idx, weight)
+    ok = points2.dim() == 3 and idx.dim() == 3 and idx.shape[-1] == 3 and idx.shape == weight.shape and idx.shape[0] == points2.shape[0]
+    if not ok or not points2.dtype.is_floating_point or not weight.dtype.is_floating_point or idx.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError("%s: expected points2 %s (float), idx (B, N, 3) (int32 or int64) and weight (B, N, 3) (float), got %s %s, %s %s and %s %s"
+                           % (name, "(B, D, S)" if channels_first else "(B, S, D)", points2.dtype, tuple(points2.shape), idx.dtype, tuple(idx.shape),
+                              weight.dtype, tuple(weight.shape)))
+    b, n = idx.shape[0], idx.shape[1]
+    d, s = (points2.shape[1], points2.shape[2]) if channels_first else (points2.shape[2], points2.shape[1])
+    if not (1 <= n <= _lib.ADD_S_MAX_N and 1 <= s <= _lib.ADD_S_MAX_N and 1 <= d <= _lib.THREE_MAX_D):
+        raise RuntimeError("%s: expected 1 <= N, S <= %d and 1 <= D <= %d, got N = %d, S = %d, D = %d" % (name, _lib.ADD_S_MAX_N, _lib.THREE_MAX_D, n, s, d))
+    return dev, idx.detach().contiguous().int(), weight.detach().contiguous().float(), b, n, s, d
+
+
+class _ThreeInterpolate(torch.autograd.Function):
+    """three_interpolate as a graph node: backward is one launch of so3_three_interpolate_bwd_f32, a gather over the stored indices in
+    a fixed order (no atomics: the same bits from call to call), reading grad_out in the forward's output layout."""
+
+    @staticmethod
+    def forward(ctx, points2, idx32, w32, channels_first, dims):
+        b, n, s, d = dims
+        dev = points2.device
+        f = points2.detach().contiguous().float()
+        out = torch.empty((b, d, n) if channels_first else (b, n, d), dtype=torch.float32, device=dev)
+        with _on_device(dev):
+            _check(_libh().so3_three_interpolate_f32(_ptr(f), _ptr(idx32), _ptr(w32), _ptr(out), 1 if channels_first else 0, b, n, s, d, _stream(dev)),
+                   "so3_three_interpolate_f32")
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(idx32, w32)
+        ctx.meta = (bool(channels_first), dims, points2.dtype, dev)
+        return out if points2.dtype is torch.float32 else out.to(points2.dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        idx32, w32 = ctx.saved_tensors
+        channels_first, (b, n, s, d), dtype, dev = ctx.meta
+        if grad_out is None or not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        g = grad_out.float().contiguous()
+        grad = torch.empty((b, d, s) if channels_first else (b, s, d), dtype=torch.float32, device=dev)
+        with _on_device(dev):
+            _check(_libh().so3_three_interpolate_bwd_f32(_ptr(g), _ptr(idx32), _ptr(w32), _ptr(grad), 1 if channels_first else 0, b, n, s, d,
+                                                         _stream(dev)), "so3_three_interpolate_bwd_f32")
+        return (grad if dtype is torch.float32 else grad.to(dtype)), None, None, None, None
+
+
+def three_interpolate(points2: torch.Tensor, idx: torch.Tensor, weight: torch.Tensor, channels_first: bool = False) -> torch.Tensor:
+    """point_cloud/pointnet_utils.py:293 without the (B, N, 3, D) gather: out[b, n, c] = sum_k weight[b, n, k] * points2[b, idx[b, n, k], c].
+    points2 is (B, S, D) and the result (B, N, D); with channels_first=True points2 is (B, D, S) and the result (B, D, N), the layout a
+    PointNetFeaturePropagation layer receives and its Conv1d takes, so no permute().contiguous() is needed on either side.  idx and
+    weight are (B, N, 3), as three_nn returns them (int64 or int32 indices; any weights).
+
+    The order is fixed (include/so3proj.h): fma(w_2, f_2, fma(w_1, f_1, w_0 * f_0)) in float32.  Differentiable in points2: the
+    backward is one launch that sums, for every known point, its hits in ascending (n, k) -- no atomics, the same bits from call to
+    call; a known point nobody selected gets exactly 0.  Double backward is refused.  There is no gradient to weight or idx: a weight
+    that requires grad is warned about once.
+
+    EVERY INDEX MUST LIE IN [0, S).  The indices are not validated (three_nn's always are in range); the kernels clamp an index outside
+    into the range, forward and backward alike, so a bad index gives a wrong value, never an access outside the tensors."""
+    dev, idx32, w32, b, n, s, d = _three_args("three_interpolate", points2, idx, weight, channels_first)
+    if _wants_grad(weight):
+        _warn_once("three_interpolate", "three_interpolate is differentiable with respect to points2 only: weight carries no gradient although it "
+                                        "requires grad.")
+    if b == 0:
+        return points2.new_zeros((0, d, n) if channels_first else (0, n, d))
+    return _ThreeInterpolate.apply(points2, idx32, w32, bool(channels_first), (b, n, s, d))
+
+
+def interpolate_features(xyz1: torch.Tensor, xyz2: torch.Tensor, points2: torch.Tensor, channels_first: bool = False) -> torch.Tensor:
+    """point_cloud/pointnet_utils.py:283-293 in two launches: the features points2 of the known points xyz2 (B, S, 3) carried to the
+    points xyz1 (B, N, 3) by inverse-distance weighting over the three nearest known points; three_nn(..., return_weights=True)
+    followed by three_interpolate.  The clouds are (B, ., 3) in both layouts; channels_first only says how points2 and the result are laid out:
+    (B, S, D) -> (B, N, D), or (B, D, S) -> (B, D, N).  Differentiable in points2."""
+    _, idx, weight = three_nn(xyz1, xyz2, return_weights=True)
+    return three_interpolate(points2, idx, weight, channels_first)
+
+
+def propagate_features(xyz1: torch.Tensor, xyz2: torch.Tensor, points1, points2: torch.Tensor) -> torch.Tensor:
+    """PointNetFeaturePropagation.forward up to its MLP (point_cloud/pointnet_utils.py:276-301), in the layer's own channel-first
+    layout: xyz1 (B, 3, N), xyz2 (B, 3, S), points1 (B, D1, N) or None, points2 (B, D2, S) -> (B, D1 + D2, N), points1 first.  The
+    interpolated half is interpolate_features(..., channels_first=True), S == 1 included (every point then takes the one known feature
+    with weight 1); the concatenation is plain torch.  Differentiable in points1 and points2."""
+    _require_device(xyz1, xyz2, points2)
+    if xyz1.dim() != 3 or xyz2.dim() != 3 or xyz1.shape[1] != 3 or xyz2.shape[1] != 3:
+        raise RuntimeError("propagate_features: expected xyz1 (B, 3, N) and xyz2 (B, 3, S), got %s and %s" % (tuple(xyz1.shape), tuple(xyz2.shape)))
+    out = interpolate_features(xyz1.transpose(1, 2), xyz2.transpose(1, 2), points2, channels_first=True)
+    if points1 is None:
+        return out
+    _require_device(points1)
+    if points1.dim() != 3 or points1.shape[0] != out.shape[0] or points1.shape[2] != out.shape[2]:
+        raise RuntimeError("propagate_features: expected points1 (B, D1, N) with N = %d, got %s" % (out.shape[2], tuple(points1.shape)))
+    return torch.cat([points1, out], dim=1)
+
+
+# --------------------------------------------------------------------------------------------
 # row a7: the cloud side of the point-cloud path
 # --------------------------------------------------------------------------------------------
 def _rotate_call(pc, R, transposed):

@@ -225,6 +225,25 @@ def main():
     timeit("pointnet: so3_ball_query_f32 (the same, with counts)", lambda i: lib.so3_ball_query_f32(p(xf), p(cf), ctypes.c_float(0.2), kf, p(gi), p(gc), bf, nf, sf, st),
            bf * sf * (kf + 1) * 4, iters=10, warm=2)
     del xf, s0, of, cf, gi, gc
+    # feature propagation: the reference model's first and second propagation levels, both layouts
+    for bt, nt, stn, dt in ((32, 1024, 512, 128), (32, 512, 128, 256)):
+        shape = "%d x %d <- %d" % (bt, nt, stn)
+        x1, x2 = torch.rand(bt, nt, 3, device=dev) - 0.5, torch.rand(bt, stn, 3, device=dev) - 0.5
+        d3, i3, w3 = torch.empty(bt, nt, 3, device=dev), torch.empty(bt, nt, 3, dtype=torch.int32, device=dev), torch.empty(bt, nt, 3, device=dev)
+        timeit("three_nn: so3_three_nn_f32 (%s, with weights)" % shape, lambda i: lib.so3_three_nn_f32(p(x1), p(x2), p(d3), p(i3), p(w3), bt, nt, stn, st),
+               bt * (nt * 48 + stn * 12), iters=20, warm=3)
+        timeit("three_nn: so3_three_nn_f32 (%s, without)" % shape, lambda i: lib.so3_three_nn_f32(p(x1), p(x2), p(d3), p(i3), None, bt, nt, stn, st),
+               bt * (nt * 36 + stn * 12), iters=20, warm=3)
+        _lib.check(lib.so3_three_nn_f32(p(x1), p(x2), p(d3), p(i3), p(w3), bt, nt, stn, st), "so3_three_nn_f32")
+        ft, gt = torch.randn(bt, stn * dt, device=dev), torch.randn(bt, nt * dt, device=dev)
+        ot, gf = torch.empty_like(gt), torch.empty_like(ft)
+        moved = bt * ((nt + stn) * dt * 4 + nt * 24)
+        for cfl, lay in ((0, "(B,S,D)"), (1, "(B,D,S)")):
+            timeit("three_nn: so3_three_interpolate_f32 (%s, D=%d, %s)" % (shape, dt, lay),
+                   lambda i: lib.so3_three_interpolate_f32(p(ft), p(i3), p(w3), p(ot), cfl, bt, nt, stn, dt, st), moved, iters=20, warm=3)
+            timeit("three_nn: so3_three_interpolate_bwd_f32 (%s, D=%d, %s)" % (shape, dt, lay),
+                   lambda i: lib.so3_three_interpolate_bwd_f32(p(gt), p(i3), p(w3), p(gf), cfl, bt, nt, stn, dt, st), moved, iters=20, warm=3)
+        del x1, x2, d3, i3, w3, ft, gt, ot, gf
     rg = rr.get_sampled_rotation_matrices_by_axisAngle(b, dev).reshape(b, 9).contiguous()
     timeit("f4 so3_kabsch_synth_f32 (sigma=0: P only)", lambda i: lib.so3_kabsch_synth_f32(p(pc[i % 2]), p(rg), ctypes.c_float(0.0), 1, p(rk), None, b, npts, st), b * (npts * 12 + 72), iters=10, warm=2)
     timeit("f4 so3_kabsch_synth_f32 (sigma=0.01, device RNG)", lambda i: lib.so3_kabsch_synth_f32(p(pc[i % 2]), p(rg), ctypes.c_float(0.01), 1, p(rk), None, b, npts, st), b * (npts * 12 + 72), iters=10, warm=2)

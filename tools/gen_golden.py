@@ -930,6 +930,91 @@ def g22_pointnet(seed=24):
     save("g22_pointnet.npz", **arrays)
 
 
+def g24_three_nn(seed=24):
+    """three_nn and three_interpolate: the reference's own statements on the CPU in float32 -- the `if S == 1: ... else: ...` of
+    PointNetFeaturePropagation.forward (point_cloud/pointnet_utils.py:283-293: square_distance, sort, the weight lines, index_points),
+    taken out of the method with `ast` and executed, nothing retyped -- on anisotropic Gaussian clouds, D = 16, torch seeded.  The
+    clouds go through pc_normalize (centred on their bounding box and scaled by its diagonal: radius at most 0.5) and are then scaled
+    to radius 1, the scale near_tie's and near_zero's thresholds are stated for: at pc_normalize's own scale no cloud of 512 known
+    points can meet the near_zero cap (a bounding box of diagonal 1 holds at most 0.19 of volume, so more than 1.1 % of uniformly
+    placed unknown points lie within 0.01 of a known one; a Gaussian cloud at that scale puts 1.8 % of the rows near a tie).
+    Cases (tests/three_nn_ref.py: CASES): disjoint clouds at 2 x 1024 <- 512, 2 x 512 <- 128 and 3 x 300 <- 77 (unknown and known
+    points drawn and normalised together, then split); `subset` at 2 x 1024 <- 512, case 0's unknown cloud with the known points
+    chosen from it by the reference's farthest_point_sample, as the model's fp1 has them; 2 x 128 <- 1.  Every case stores near_tie and
+    near_zero (float64); the generator asserts that the reference's indices differ from the restatement's only inside near_tie, that
+    near_tie covers at most 1 % of a case's rows and, for the disjoint cases, that near_tie | near_zero does.  ref_dev is the largest
+    |reference - float64 restatement| of the interpolated features outside both masks.  The subset case's values are NOT stored: half its
+    rows have a true distance of 0, where the reference's expanded form is cancellation noise; the number of rows with a negative
+    reference weight is recorded instead."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import three_nn_ref as ref
+    path = os.path.join(REF, "point_cloud", "pointnet_utils.py")
+    names = ["square_distance", "index_points", "farthest_point_sample"]
+    fns = functions_from(path, names)
+    for f in fns:
+        f.__globals__.update(dict(zip(names, fns)))
+    square_distance, index_points, farthest_point_sample = fns
+    (pc_normalize,) = functions_from(os.path.join(REF, "point_cloud", "prepare.py"), ["pc_normalize"])
+    with open(path) as fh:
+        tree = ast.parse(fh.read(), filename=path)
+    layer = next(n for n in tree.body if isinstance(n, ast.ClassDef) and n.name == "PointNetFeaturePropagation")
+    forward = next(n for n in layer.body if isinstance(n, ast.FunctionDef) and n.name == "forward")
+    branch = next(n for n in forward.body if isinstance(n, ast.If) and isinstance(n.test, ast.Compare) and getattr(n.test.left, "id", "") == "S")
+    assert (branch.lineno, branch.end_lineno) == (283, 293)
+    code = compile(ast.Module(body=[branch], type_ignores=[]), path, "exec")
+
+    def reference(xyz1, xyz2, points2):
+        ns = {"torch": torch, "square_distance": square_distance, "index_points": index_points, "xyz1": xyz1, "xyz2": xyz2, "points2": points2,
+              "B": xyz1.shape[0], "N": xyz1.shape[1], "S": xyz2.shape[1]}
+        exec(code, ns)
+        return ns["interpolated_points"], ns.get("idx"), ns.get("weight")
+
+    rng = np.random.RandomState(seed)
+    torch.manual_seed(seed)
+
+    def clouds(b, n):
+        raw = rng.randn(b, n, 3) * np.array([1.0, 0.8, 0.6]) + np.array([0.3, -1.0, 2.0])
+        pc = np.stack([pc_normalize(c)[0] for c in raw])
+        return torch.tensor(pc / np.linalg.norm(pc, axis=-1).max(1)[:, None, None]).float()
+
+    arrays = {}
+    for k, (kind, b, n, s) in enumerate(ref.CASES):
+        if kind == "subset":
+            xyz1, feat = arrays["xyz1_0"], arrays["feat_0"]
+            fps = farthest_point_sample(xyz1, s)
+            xyz2 = index_points(xyz1, fps)
+            arrays["fps_%d" % k] = fps.numpy().astype(np.uint16)
+        else:
+            both = clouds(b, n + s)
+            xyz1, xyz2 = both[:, :n].contiguous(), both[:, n:].contiguous()
+            feat = torch.randn(b, s, ref.D_FIXTURE)
+            arrays["xyz1_%d" % k], arrays["xyz2_%d" % k], arrays["feat_%d" % k] = xyz1, xyz2, feat
+        out, idx, weight = reference(xyz1, xyz2, feat)
+        assert out.shape == (b, n, ref.D_FIXTURE) and out.dtype == torch.float32
+        d3, want, w = ref.three_nn(xyz1.numpy(), xyz2.numpy())
+        tie, zero = ref.masks(xyz1.numpy(), xyz2.numpy())
+        ref_idx = np.zeros((b, n, 3), np.int64) if idx is None else idx.numpy()
+        differ = (ref_idx != want).any(-1)
+        assert not (differ & ~tie).any(), "the reference's indices differ from the restatement's outside near_tie"
+        assert tie.mean() <= ref.MASK_CAP, (k, tie.mean())
+        arrays["ref_idx_%d" % k], arrays["near_tie_%d" % k], arrays["near_zero_%d" % k] = ref_idx.astype(np.uint16), tie, zero
+        line = "g24 %s %dx%d<-%d: near_tie %.2f %%, near_zero %.2f %%, either %.2f %%, %d rows differ" % (
+            kind, b, n, s, 100 * tie.mean(), 100 * zero.mean(), 100 * (tie | zero).mean(), differ.sum())
+        if kind == "subset":
+            negative = int((weight < 0).any(-1).sum())
+            arrays["ref_negative_weights_%d" % k] = np.int64(negative)
+            line += "; the reference has a negative weight in %d of %d rows" % (negative, b * n)
+        else:
+            if kind == "disjoint":
+                assert (tie | zero).mean() <= ref.MASK_CAP, (k, (tie | zero).mean())
+            keep = ~(tie | zero)
+            dev = float(np.abs(out.numpy().astype(np.float64) - ref.interpolate(feat.numpy(), want, w)[0])[keep].max())
+            arrays["ref_out_%d" % k], arrays["ref_dev_%d" % k] = out, np.float64(dev)
+            line += "; ref_dev %.3g" % dev
+        print(line)
+    save("g24_three_nn.npz", **arrays)
+
+
 def g23_head_edges():
     """The forward heads at their edges (tests/heads_ref.py: every family, every fourth row -- 32 of 128): the reference's own float32
     outputs and autograd gradients, float64 too where the reference's code keeps float64 (not the 5D head: float32 zeros, :82; not
@@ -975,6 +1060,8 @@ def g23_head_edges():
 
 
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "g24":
+        return g24_three_nn()
     if len(sys.argv) > 1 and sys.argv[1] == "g23":
         return g23_head_edges()
     if len(sys.argv) > 1 and sys.argv[1] == "g22":
