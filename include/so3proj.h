@@ -65,6 +65,36 @@ const char *so3_last_kernel(void);
 int so3_project_fwd_f32(const float *M, float *R, uint8_t *flip, int64_t B, void *stream);
 int so3_project_fwd_bf16(const void *M, float *R, uint8_t *flip, int64_t B, void *stream);
 
+/* K1 over n independent buffer pairs in ONE launch of the streaming engine: R[i] = the rotations of M[i], B[i] rows each.
+ *   1 <= n <= 8; every B[i] a positive multiple of 64; every M[i], R[i] non-NULL and 4-byte aligned; the rounds of all segments
+ *   together fit 32 bits (2^31 - 4096 units of 64 rows).  Anything else returns SO3_ERR_INVALID and launches nothing.
+ *   The three arrays are host memory and are read before the call returns.  The segments run concurrently inside the kernel: no
+ *   R[i] may overlap another R[j] or any M[j] (the caller's contract, as for separate launches on separate streams).
+ * Every row goes through the arithmetic of so3_project_fwd_f32, paired with the same neighbour row: the results are bit-identical
+ * to n separate calls; with n = 1 it IS that call's launch.  What it saves is the launch boundary: the tail of one segment overlaps
+ * the fill of the next inside the kernel. */
+int so3_project_fwd_segments_f32(const float *const *M, float *const *R, const int64_t *B, int n, void *stream);
+
+/* Capture-time fusion of adjacent K1 calls.  While a stream is being CAPTURED into a graph, a call of so3_project_fwd_f32 / _bf16
+ * with flip == NULL, B a multiple of 64 and 4-byte aligned pointers may add no kernel node of its own: it is folded, as one more
+ * segment, into the node that the SAME thread's previous such call created, when that node is the stream's only capture
+ * dependency (nothing was captured on the stream in between, and nothing else must precede the call), both calls are the same
+ * instantiation, the node holds fewer than 8 segments, and the new call's buffers are hazard-free against the node's (input
+ * overlaps no earlier output; output overlaps no earlier output or input).  Results are the same bits; a replay runs one persistent
+ * launch per run of up to 8 calls and a profiler sees one dispatch for it.  Eager (uncaptured) calls are never fused.
+ *   so3_capture_fusion(enable)      sets the process-wide switch (default: on) and returns the previous setting.  A caller that
+ *                                   edits the kernel-node parameters of a captured graph itself switches it off before capturing.
+ *   so3_capture_fused_launches()    how many calls THIS thread has folded into an earlier node so far. */
+int so3_capture_fusion(int enable);
+int64_t so3_capture_fused_launches(void);
+/* The fusion decision alone, for tests (no device, no pointer is dereferenced): would a call (M, R, B rows, elem_bytes = 4 for
+ * float32 / 2 for bfloat16 input) be folded into a recorded node of rec_n segments (rec_M, rec_R, rec_B, rec_elem_bytes), given
+ * whether the capture is the same, how many capture dependencies the stream has and whether the first is the recorded node?
+ * Returns 1 / 0, or SO3_ERR_INVALID for a malformed record. */
+int so3_capture_fusion_would_fuse(const void *const *rec_M, void *const *rec_R, const int64_t *rec_B, int rec_n, int rec_elem_bytes,
+                                  int same_capture, int ndeps, int dep_is_recorded_node, int elem_bytes, const void *M, const void *R,
+                                  int64_t B);
+
 /* ---- K2: backward of K1 ---------------------------------------------------------------------------
  * dM_b = U' Bm V^T with the signed SVD M = U' diag(s') V^T (U', V in SO(3)), A = U'^T G V,
  * Bm_ij = (A_ij - A_ji)/(s'_i + s'_j), Bm_ii = 0.  The SVD is recomputed from M (nothing else is

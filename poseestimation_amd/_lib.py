@@ -22,6 +22,10 @@ SYMBOLS = {
     "so3_last_kernel": (ctypes.c_char_p, []),
     "so3_project_fwd_f32": (_INT, [_P, _P, _P, _I64, _P]),
     "so3_project_fwd_bf16": (_INT, [_P, _P, _P, _I64, _P]),
+    "so3_project_fwd_segments_f32": (_INT, [_P, _P, _P, _INT, _P]),
+    "so3_capture_fusion": (_INT, [_INT]),
+    "so3_capture_fused_launches": (_I64, []),
+    "so3_capture_fusion_would_fuse": (_INT, [_P, _P, _P, _INT, _INT, _INT, _INT, _INT, _INT, _P, _P, _I64]),
     "so3_project_bwd_f32": (_INT, [_P, _P, _P, _I64, _P]),
     "so3_project_bwd_bf16": (_INT, [_P, _P, _P, _I64, _P]),
     "so3_project_fwd_f64": (_INT, [_P, _P, _P, _I64, _P]),

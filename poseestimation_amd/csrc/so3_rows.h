@@ -338,6 +338,7 @@ template <int NPL> struct RowCtx {
     bool flag;              // per-lane sticky flag (K4: cosine out of range)
     const char *img1;       // LDS image of the second input's block (operations with kLateIn1 read their rows from it themselves)
     char *slot;             // the wave's LDS slot: free between take_rows and put_rows (the inputs have left, the outputs are not staged yet)
+    int seg;                // wave-uniform: the segment the round belongs to (Op::kSegmented; 0 otherwise)
     int dense;              // wave-uniform (K1): 1 = the wave's last round was dense in hard rows, 2 = so were earlier ones and the shortcut was refused
     float *park;            // Op::kParkWords > 0: the workgroup's list of parked hard rows (LDS, see park_hard_rows) ...
     unsigned *park_count;   // ... and how many it holds
@@ -345,6 +346,27 @@ template <int NPL> struct RowCtx {
 };
 
 #ifndef SO3_HOST_MODEL
+// ---- a launch over several buffer pairs (Op::kSegmented) ------------------------------------------------------------------
+// The table travels in the kernel arguments (no device allocation, no workspace).  Rounds are numbered across the concatenation of
+// the segments: segment k owns rounds [first, first + ceil(units / NPL)), so a round never straddles two segments and a segment's odd
+// tail keeps its phantom unit (cut off by the descriptor's range check, as in a launch of its own).  With one segment the table
+// describes the plain launch.  The lookup is wave-uniform: a wave keeps the segment of its current round and the segment of the
+// round it is fetching in scalar registers and moves them on as its round numbers grow; the table is read with scalar loads.
+constexpr int kMaxSegments = 8;
+struct RowSegment {
+    const void *in;
+    void *out;
+    int first;              // the segment's first round in the launch's numbering
+    int units;              // its units of 64 rows
+};
+template <bool SEGMENTED> struct SegCursor {};
+template <> struct SegCursor<true> {
+    int idx, first, end, units;         // rounds [first, end) belong to segment idx
+    const void *in;
+    void *out;
+};
+constexpr int kParkedSegShift = 56;     // a parked row's segment rides in the spare high bits of its 64-bit row number
+
 // ---- the engine ----------------------------------------------------------------------------------------
 // Op provides: kIn0, kIn1, kIn2, kOut0, kOut1 (element bytes, 0 = absent), pointers in0, in1, in2, out0, out1,
 //   kIn0N .. kOut1N (elements per row, 9 unless overridden),
@@ -403,7 +425,38 @@ void k_rows(Op op, int64_t nunits, unsigned long long *__restrict__ stamps) {
     // of this round exist" went through v_cmp_*_i64 on the vector unit every round.  (2^31 rounds of 128 rows are 10 TB of float32 rows;
     // the host refuses a batch beyond that, stream_units.)  Units and rows stay 64-bit where they become addresses.
     constexpr int kFixed = Op::kFixedRounds;
-    const int nrounds_all = static_cast<int>((nunits + NPL - 1) / NPL);
+    constexpr bool kSeg = Op::kSegmented;
+    static_assert(!kSeg || (Op::kIn1 == 0 && Op::kIn2 == 0 && Op::kOut1 == 0), "a segment is one input and one output");
+    // kSegmented: `cur` is the segment of round t, `nxt` the segment of the round whose loads were issued last (scalars).  A table
+    // entry is read in ONE batch of scalar loads that is waited for on the spot (the empty asm pins the values): left to itself the
+    // compiler reads the fields one dependent round trip at a time -- at the head of the kernel each of them a cold miss, a
+    // microsecond and a half per launch in all -- and leaves a load pending across the loop's back edge, where waiting for it (scalar
+    // loads return out of order: lgkmcnt(0)) also waits for the LDS writes in front of every round's loads.
+    SegCursor<kSeg> cur, nxt;
+    int nseg_ = 1, nrounds_all_;
+    auto seg_load = [&](SegCursor<kSeg> &c, int i) {
+        if constexpr (kSeg) {
+            int first = op.seg[i].first, units = op.seg[i].units;
+            const void *in = op.seg[i].in;
+            void *out = op.seg[i].out;
+            asm volatile("" : "+s"(first), "+s"(units), "+s"(in), "+s"(out));
+            c.idx = i;
+            c.first = first;
+            c.units = units;
+            c.end = first + (units + NPL - 1) / NPL;
+            c.in = in;
+            c.out = out;
+        }
+    };
+    if constexpr (kSeg) {
+        nseg_ = op.nseg;
+        nrounds_all_ = op.total_rounds;
+        asm volatile("" : "+s"(nseg_), "+s"(nrounds_all_));
+        seg_load(nxt, 0);
+    } else {
+        nrounds_all_ = static_cast<int>((nunits + NPL - 1) / NPL);
+    }
+    const int nseg = nseg_, nrounds_all = nrounds_all_;
     const int stride = kFixed > 0 ? 1 : static_cast<int>(gridDim.x) * kWaves;
     const int wave_id = static_cast<int>(blockIdx.x) * kWaves + wave_in_block;
     int t = kFixed > 0 ? wave_id * kFixed : wave_id;
@@ -415,6 +468,7 @@ void k_rows(Op op, int64_t nunits, unsigned long long *__restrict__ stamps) {
     ctx.flag = false;
     ctx.img1 = nullptr;
     ctx.slot = nullptr;
+    ctx.seg = 0;
     ctx.dense = 0;
     ctx.park = park;
     ctx.park_count = &park_count;
@@ -426,8 +480,14 @@ void k_rows(Op op, int64_t nunits, unsigned long long *__restrict__ stamps) {
     ctx.n_pi = 0;
     if (t < nrounds) {
         const int nunits32 = static_cast<int>(nunits);
-        auto units_of = [&](int tr) -> int {                // how many of round tr's NPL units exist (0 past the end)
-            const int left = nunits32 - tr * NPL;
+        auto seg_seek = [&](SegCursor<kSeg> &c, int tr) {   // forward only; past the last round the cursor stays on the last segment
+            if constexpr (kSeg)
+                while (tr >= c.end && c.idx + 1 < nseg) seg_load(c, c.idx + 1);
+        };
+        auto units_of = [&](int tr, const SegCursor<kSeg> &c) -> int {     // how many of round tr's NPL units exist (0 past the end)
+            int left;
+            if constexpr (kSeg) left = c.units - (tr - c.first) * NPL;
+            else left = nunits32 - tr * NPL;
             return tr < nrounds ? (left < NPL ? left : NPL) : 0;
         };
         // STAMP builds: wall-clock (100 MHz) begin / end of the arithmetic of the wave's first four rounds
@@ -444,9 +504,15 @@ void k_rows(Op op, int64_t nunits, unsigned long long *__restrict__ stamps) {
         auto take_rows = [&](const char *img, Rows<T, Op> &rows) {
 #pragma unroll
             for (int k = 0; k < NPL; ++k) {
-                ctx.unit[k] = t * NPL + k;
-                ctx.exists[k] = t * NPL + k < nunits32; // wave-uniform; false only for the phantom unit of an odd tail, whose lanes
-            }                                           // work on the zeros the range check returned for it (results dropped)
+                if constexpr (kSeg) {                   // units are numbered within the round's segment
+                    ctx.unit[k] = (t - cur.first) * NPL + k;
+                    ctx.exists[k] = (t - cur.first) * NPL + k < cur.units;
+                } else {
+                    ctx.unit[k] = t * NPL + k;
+                    ctx.exists[k] = t * NPL + k < nunits32; // wave-uniform; false only for the phantom unit of an odd tail, whose lanes
+                }                                           // work on the zeros the range check returned for it (results dropped)
+            }
+            if constexpr (kSeg) ctx.seg = cur.idx;
             I0::template read_rows<T>(img, lane, rows.a);
             if constexpr (Op::kIn1 != 0 && !Op::kLateIn1) I1::template read_rows<T>(img + kIn0B, lane, rows.b);
             if constexpr (Op::kIn2 != 0) I2::template read_rows<T>(img + kIn0B + kIn1B, lane, rows.c);
@@ -464,9 +530,13 @@ void k_rows(Op op, int64_t nunits, unsigned long long *__restrict__ stamps) {
                 if constexpr (Op::kOut0 != 0) O0::from_lds(v0, img, lane);
                 if constexpr (Op::kOut1 != 0) O1::from_lds(v1, img + kOut0B, lane);
                 wave_lds_fence();
-                const int cnt = units_of(t);            // an odd tail's phantom unit is cut off by the descriptor
-                if constexpr (Op::kOut0 != 0) O0::store(O0::rsrc(op.out0, static_cast<int64_t>(t) * NPL, cnt), v0, lane);
-                if constexpr (Op::kOut1 != 0) O1::store(O1::rsrc(op.out1, static_cast<int64_t>(t) * NPL, cnt), v1, lane);
+                const int cnt = units_of(t, cur);       // an odd tail's phantom unit is cut off by the descriptor
+                if constexpr (kSeg) {
+                    O0::store(O0::rsrc(cur.out, static_cast<int64_t>(t - cur.first) * NPL, cnt), v0, lane);
+                } else {
+                    if constexpr (Op::kOut0 != 0) O0::store(O0::rsrc(op.out0, static_cast<int64_t>(t) * NPL, cnt), v0, lane);
+                    if constexpr (Op::kOut1 != 0) O1::store(O1::rsrc(op.out1, static_cast<int64_t>(t) * NPL, cnt), v1, lane);
+                }
             }
         };
         {
@@ -476,11 +546,16 @@ void k_rows(Op op, int64_t nunits, unsigned long long *__restrict__ stamps) {
             // One round is in flight in registers behind the round that sits in LDS.
             f32x4 in0[I0::kLoads], in1[I1::kLoads], in2[I2::kLoads];
             auto issue = [&](int tr) {                      // past the last round the descriptors are empty: the loads
-                const int cnt = units_of(tr);               // return 0 and cost no traffic
-                const int64_t u = static_cast<int64_t>(tr) * NPL;      // (past the end nothing is in range, whatever the base)
-                I0::fetch(in0, I0::rsrc(op.in0, u, cnt), lane);
-                if constexpr (Op::kIn1 != 0) I1::fetch(in1, I1::rsrc(op.in1, u, cnt), lane);
-                if constexpr (Op::kIn2 != 0) I2::fetch(in2, I2::rsrc(op.in2, u, cnt), lane);
+                seg_seek(nxt, tr);                          // return 0 and cost no traffic
+                const int cnt = units_of(tr, nxt);
+                if constexpr (kSeg) {
+                    I0::fetch(in0, I0::rsrc(nxt.in, static_cast<int64_t>(tr - nxt.first) * NPL, cnt), lane);
+                } else {
+                    const int64_t u = static_cast<int64_t>(tr) * NPL;  // (past the end nothing is in range, whatever the base)
+                    I0::fetch(in0, I0::rsrc(op.in0, u, cnt), lane);
+                    if constexpr (Op::kIn1 != 0) I1::fetch(in1, I1::rsrc(op.in1, u, cnt), lane);
+                    if constexpr (Op::kIn2 != 0) I2::fetch(in2, I2::rsrc(op.in2, u, cnt), lane);
+                }
             };
             auto land = [&]() {                             // registers -> the wave's LDS slot (float32 images)
                 I0::to_lds(slot, in0, lane);
@@ -488,6 +563,7 @@ void k_rows(Op op, int64_t nunits, unsigned long long *__restrict__ stamps) {
                 if constexpr (Op::kIn2 != 0) I2::to_lds(slot + kIn0B + kIn1B, in2, lane);
             };
             issue(t);
+            cur = nxt;
             land();
             int held = t + stride;                          // the round the registers hold (>= nrounds: none, empty loads)
             issue(held);
@@ -506,6 +582,7 @@ void k_rows(Op op, int64_t nunits, unsigned long long *__restrict__ stamps) {
                 // stores, so the wait is vmcnt(#stores), never a drain.
                 land();
                 t = held;
+                cur = nxt;                                  // (the segment of the round that has just landed)
                 held += stride;
                 issue(held);
             }
@@ -598,6 +675,9 @@ struct OpBase {
     // kFixedRounds > 0 (experiment builds, SO3_K1_FIXED_ROUNDS): NOT persistent -- wave w takes the kFixedRounds CONSECUTIVE rounds
     // w k, w k + 1, ... and retires; the host launches ceil(rounds / k) waves and the dispatcher back-fills (round 6's A/B)
     static constexpr int kFixedRounds = 0;
+    // kSegmented: the launch runs over up to kMaxSegments buffer pairs listed in the operation's own table (seg, nseg, total_rounds)
+    // instead of in0 / out0 and the kernel's unit count (k_rows; one input, one output)
+    static constexpr bool kSegmented = false;
 #ifndef SO3_HOST_MODEL
     ReduceWs *ws = nullptr;        // reduction workspace (nullptr: atomics onto host-initialised accumulators)
     unsigned ws_slot0 = 0;         // slots below this one were filled by the remainder kernel launched before the engine
@@ -653,7 +733,7 @@ __device__ __forceinline__ void park_words(const RowCtx<NPL> &ctx, int base, typ
 #pragma unroll
             for (int i = 0; i < N; ++i) ctx.park[(w0 + i) * CAP + e] = Tr<T>::get(v[i], k);
             if (ROW) {
-                const long long row = ctx.unit[k] * kUnitRows + lane;
+                const long long row = (ctx.unit[k] * kUnitRows + lane) | (static_cast<long long>(ctx.seg) << kParkedSegShift);
                 ctx.park[WORDS * CAP + e] = __int_as_float(static_cast<int>(row & 0xffffffffll));
                 ctx.park[(WORDS + 1) * CAP + e] = __int_as_float(static_cast<int>(row >> 32));
             }
@@ -770,7 +850,22 @@ struct OpProject : OpBase {
     static constexpr int kIn0 = IN_BYTES, kIn1 = 0, kOut0 = 4, kOut1 = 0;
     static constexpr int kFixedRounds = SO3_K1_FIXED_ROUNDS;
     static constexpr int kParkWords = 9, kParkCap = SO3_PARK_CAP1;          // 512 entries: 22 KB of LDS per workgroup
-    uint8_t *flip = nullptr;
+    static constexpr bool kSegmented = true;
+    uint8_t *flip = nullptr;                     // (flags are numbered within the segment: launches with flags have one)
+    RowSegment seg[kMaxSegments] = {};
+    int nseg = 0, total_rounds = 0;
+    // Host side: append a buffer pair of `units` units (NPL units per round); returns false when the table is full.
+    template <int NPL> __host__ bool add_segment(const void *in, void *out, int64_t units) {
+        if (nseg >= kMaxSegments) return false;
+        seg[nseg].in = in;
+        seg[nseg].out = out;
+        seg[nseg].first = total_rounds;
+        seg[nseg].units = static_cast<int>(units);
+        total_rounds += static_cast<int>((units + NPL - 1) / NPL);
+        if (nseg == 0) { in0 = in; out0 = out; }
+        ++nseg;
+        return true;
+    }
     template <class T, int NPL>
     __device__ __forceinline__ void compute(Rows<T, OpProject> &rows, RowCtx<NPL> &ctx) const {
         typedef Tr<T> R;
@@ -794,7 +889,9 @@ struct OpProject : OpBase {
         float m[9], r[9];
         parked_words<kParkCap, 9>(ctx.park, e, 0, m);
         rotation_from(signed_svd<false, float>(m), r);
-        if (valid) overwrite_row<4, 9>(out0, parked_row<kParkCap, kParkWords>(ctx.park, e), r);
+        const long long tagged = parked_row<kParkCap, kParkWords>(ctx.park, e);          // segment << kParkedSegShift | row within the segment
+        void *out = seg[static_cast<int>(tagged >> kParkedSegShift) & (kMaxSegments - 1)].out;
+        if (valid) overwrite_row<4, 9>(out, tagged & ((1ll << kParkedSegShift) - 1), r);
     }
 };
 

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <cxxabi.h>
 #include <algorithm>
+#include <atomic>
 #include <stdlib.h>
 #include <string>
 #include <stdint.h>
@@ -3143,18 +3144,25 @@ const char *rows_kernel_name(hipStream_t s) {
     return name.c_str();
 }
 
+// The grid of a launch of `rounds` rounds: a wave per round up to the CUs' wave slots.
 template <int NPL, int WPS, int BLOCK, class Op>
-void launch_rows(const Op &op, int64_t nunits, hipStream_t s) {
+unsigned rows_grid(int64_t rounds) {
     constexpr int kWaves = BLOCK / 64;
-    g_last_kernel = rows_kernel_name<Op, NPL, WPS, BLOCK>(s);
-    const int64_t rounds = (nunits + NPL - 1) / NPL;
     const int64_t want = (rounds + kWaves - 1) / kWaves;
     int64_t cap = static_cast<int64_t>(device_cus()) * 4 * WPS / kWaves;          // CUs x 4 SIMDs x WPS wave slots
     if (Op::kFixedRounds > 0) {                                                    // not persistent: a wave per k consecutive rounds, back-filled
         const int64_t waves = (rounds + Op::kFixedRounds - 1) / Op::kFixedRounds;
         cap = (waves + kWaves - 1) / kWaves;
     }
-    const dim3 grid(static_cast<unsigned>(want < cap ? want : cap)), block(BLOCK);
+    return static_cast<unsigned>(want < cap ? want : cap);
+}
+
+// `rounds` < 0: the rounds of one array of nunits units; a segmented operation (Op::kSegmented) passes its table's total.
+template <int NPL, int WPS, int BLOCK, class Op>
+void launch_rows(const Op &op, int64_t nunits, hipStream_t s, int64_t rounds = -1) {
+    g_last_kernel = rows_kernel_name<Op, NPL, WPS, BLOCK>(s);
+    if (rounds < 0) rounds = (nunits + NPL - 1) / NPL;
+    const dim3 grid(rows_grid<NPL, WPS, BLOCK, Op>(rounds)), block(BLOCK);
     hipLaunchKernelGGL((so3::k_rows<Op, NPL, WPS, BLOCK, false>), grid, block, 0, s, op, nunits, nullptr);
 }
 
@@ -3194,6 +3202,104 @@ inline const void *advance_bytes(const void *p, int64_t bytes) { return p ? stat
 inline void *advance_bytes(void *p, int64_t bytes) { return p ? static_cast<char *>(p) + bytes : nullptr; }
 
 // ---- K1 --------------------------------------------------------------------------------------------
+// The buffer pairs of one launch of K1's engine kernel as the host keeps them (so3::OpProject's segment table is built from it).
+struct K1Run {
+    const void *in[so3::kMaxSegments];
+    float *out[so3::kMaxSegments];
+    int64_t rows[so3::kMaxSegments];          // whole units each
+    int n = 0;
+    int elem_bytes = 4;                       // of the input: 4 = float32, 2 = bfloat16 (different kernels)
+};
+constexpr int64_t kMaxRounds32 = (INT64_C(1) << 30) - 2048;      // what stream_units admits for one array: round numbers stay 32-bit
+inline int64_t k1_rounds(int64_t rows) { return (rows / so3::kUnitRows + 1) / 2; }
+inline int64_t k1_rounds(const K1Run &run) {
+    int64_t r = 0;
+    for (int i = 0; i < run.n; ++i) r += k1_rounds(run.rows[i]);
+    return r;
+}
+inline bool bytes_overlap(const void *a, int64_t na, const void *b, int64_t nb) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + static_cast<uintptr_t>(nb) && b0 < a0 + static_cast<uintptr_t>(na);
+}
+
+// What this thread's last engine-only K1 call left in the graph being captured: the kernel node and the segments it runs.
+struct K1Captured {
+    unsigned long long capture_id = 0;
+    hipGraphNode_t node = nullptr;
+    K1Run run;
+};
+thread_local K1Captured g_k1_captured;
+thread_local int64_t g_k1_fused = 0;
+std::atomic<int> g_capture_fusion{1};
+
+// May the call (M, R, B rows, elem_bytes) on a stream whose capture is `capture_id` and whose capture dependencies are `ndeps` nodes
+// (the first one `dep0`) be folded into the recorded node?  Pure logic: no runtime call, no pointer is dereferenced.
+//   * same capture, and the recorded node is the stream's ONLY dependency: nothing was captured on this stream since, and whatever must
+//     precede this call is upstream of that node already (anything else would be a second dependency);
+//   * same instantiation, room in the table, round numbers still 32-bit;
+//   * no hazard between the segments, which run concurrently inside the kernel: the new input overlaps no recorded output (read after
+//     write), the new output overlaps no recorded output (write after write) and no recorded input (write after read).
+bool k1_may_fuse(const K1Captured &rec, unsigned long long capture_id, size_t ndeps, hipGraphNode_t dep0, int elem_bytes,
+                 const void *M, const void *R, int64_t B) {
+    if (rec.node == nullptr || rec.run.n < 1 || rec.capture_id != capture_id) return false;
+    if (ndeps != 1 || dep0 != rec.node) return false;
+    if (rec.run.elem_bytes != elem_bytes) return false;
+    if (rec.run.n >= so3::kMaxSegments) return false;
+    if (k1_rounds(rec.run) + k1_rounds(B) > kMaxRounds32) return false;
+    const int64_t in_bytes = B * 9 * elem_bytes, out_bytes = B * 9 * 4;
+    for (int i = 0; i < rec.run.n; ++i) {
+        const int64_t rin = rec.run.rows[i] * 9 * rec.run.elem_bytes, rout = rec.run.rows[i] * 9 * 4;
+        if (bytes_overlap(M, in_bytes, rec.run.out[i], rout)) return false;
+        if (bytes_overlap(R, out_bytes, rec.run.out[i], rout)) return false;
+        if (bytes_overlap(R, out_bytes, rec.run.in[i], rin)) return false;
+    }
+    return true;
+}
+
+template <int EB> so3::OpProject<EB, false> k1_op(const K1Run &run) {
+    so3::OpProject<EB, false> op;
+    for (int i = 0; i < run.n; ++i) op.template add_segment<2>(run.in[i], run.out[i], run.rows[i] / so3::kUnitRows);
+    return op;
+}
+template <int EB> void k1_launch(const K1Run &run, hipStream_t s) {
+    const so3::OpProject<EB, false> op = k1_op<EB>(run);
+    int64_t units = 0;
+    for (int i = 0; i < run.n; ++i) units += run.rows[i] / so3::kUnitRows;
+    launch_rows<2, SO3_WPS_K1, SO3_BLOCK_K1>(op, units, s, op.total_rounds);
+}
+// The recorded kernel node runs `run` from now on: a new argument block and the grid of its rounds.
+template <int EB> hipError_t k1_rewrite_node(hipGraphNode_t node, const K1Run &run, hipStream_t s) {
+    typedef so3::OpProject<EB, false> Op;
+    Op op = k1_op<EB>(run);
+    int64_t units = 0;
+    for (int i = 0; i < run.n; ++i) units += run.rows[i] / so3::kUnitRows;
+    unsigned long long *stamps = nullptr;
+    void *args[3] = {&op, &units, &stamps};
+    hipKernelNodeParams p;
+    memset(&p, 0, sizeof p);
+    p.func = reinterpret_cast<void *>(&so3::k_rows<Op, 2, SO3_WPS_K1, SO3_BLOCK_K1, false>);
+    p.gridDim = dim3(rows_grid<2, SO3_WPS_K1, SO3_BLOCK_K1, Op>(op.total_rounds));
+    p.blockDim = dim3(SO3_BLOCK_K1);
+    p.sharedMemBytes = 0;
+    p.kernelParams = args;
+    p.extra = nullptr;
+    const hipError_t e = hipGraphKernelNodeSetParams(node, &p);
+    if (e == hipSuccess) g_last_kernel = rows_kernel_name<Op, 2, SO3_WPS_K1, SO3_BLOCK_K1>(s);
+    return e;
+}
+
+// The capture state of `s`: true while it is being captured (then id and the stream's capture dependencies are set).
+inline bool capture_state(hipStream_t s, unsigned long long *id, const hipGraphNode_t **deps, size_t *ndeps) {
+    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+    hipGraph_t graph = nullptr;
+    *id = 0; *deps = nullptr; *ndeps = 0;
+    if (hipStreamGetCaptureInfo_v2(s, &status, id, &graph, deps, ndeps) != hipSuccess) {
+        (void)hipGetLastError();              // (a query the runtime refuses is not this call's failure: launch as ever)
+        return false;
+    }
+    return status == hipStreamCaptureStatusActive;
+}
+
 template <bool BF16>
 int project_fwd(const void *M, float *R, uint8_t *flip, int64_t B, void *stream) {
     SO3_CHECK_ARGS(B >= 0 && B <= SO3_MAX_B, "so3_project_fwd: B");
@@ -3205,8 +3311,41 @@ int project_fwd(const void *M, float *R, uint8_t *flip, int64_t B, void *stream)
     if (nunits > 0) {
         // two matrices per lane, three waves per SIMD: against one matrix per lane at four / five / six / eight waves (round 3, the fast
         // path, one device): 14.6-14.9 us against 15.6 / 14.9 / 16.6 (spills) / 18.4
-        if (flip) { so3::OpProject<EB, true> op; op.in0 = M; op.out0 = R; op.flip = flip; launch_rows<2, SO3_WPS_K1, SO3_BLOCK_K1>(op, nunits, s); }
-        else { so3::OpProject<EB, false> op; op.in0 = M; op.out0 = R; launch_rows<2, SO3_WPS_K1, SO3_BLOCK_K1>(op, nunits, s); }
+        if (flip) {
+            so3::OpProject<EB, true> op; op.template add_segment<2>(M, R, nunits); op.flip = flip;
+            launch_rows<2, SO3_WPS_K1, SO3_BLOCK_K1>(op, nunits, s);
+        } else if (nunits * so3::kUnitRows == B && g_capture_fusion.load(std::memory_order_relaxed) != 0) {
+            // Engine only (no flags, no remainder).  Under capture the call may join the kernel node this thread's previous such call
+            // created: adjacent independent launches then replay as ONE persistent launch over several segments, and the tail of one
+            // overlaps the fill of the next inside the kernel instead of draining at a launch boundary.
+            K1Captured &rec = g_k1_captured;
+            unsigned long long id;
+            const hipGraphNode_t *deps;
+            size_t ndeps;
+            const bool capturing = capture_state(s, &id, &deps, &ndeps);
+            if (capturing && k1_may_fuse(rec, id, ndeps, ndeps > 0 ? deps[0] : nullptr, EB, M, R, B)) {
+                K1Run wider = rec.run;
+                wider.in[wider.n] = M; wider.out[wider.n] = R; wider.rows[wider.n] = B; ++wider.n;
+                if (k1_rewrite_node<EB>(rec.node, wider, s) == hipSuccess) {
+                    rec.run = wider;
+                    ++g_k1_fused;
+                    return 0;
+                }
+                (void)hipGetLastError();      // the runtime refused: a node of its own, below
+            }
+            K1Run run;
+            run.in[0] = M; run.out[0] = R; run.rows[0] = B; run.n = 1; run.elem_bytes = EB;
+            k1_launch<EB>(run, s);
+            rec.node = nullptr;
+            if (capturing && capture_state(s, &id, &deps, &ndeps) && ndeps == 1) {       // the node the launch has just created
+                rec.capture_id = id;
+                rec.node = deps[0];
+                rec.run = run;
+            }
+        } else {
+            so3::OpProject<EB, false> op; op.template add_segment<2>(M, R, nunits);
+            launch_rows<2, SO3_WPS_K1, SO3_BLOCK_K1>(op, nunits, s);
+        }
     }
     const int64_t done = nunits * so3::kUnitRows, rest = B - done;
     if (rest > 0) {
@@ -3425,6 +3564,39 @@ int so3_project_fwd_f32(const float *M, float *R, uint8_t *flip, int64_t B, void
 }
 int so3_project_fwd_bf16(const void *M, float *R, uint8_t *flip, int64_t B, void *stream) {
     return project_fwd<true>(M, R, flip, B, stream);
+}
+int so3_project_fwd_segments_f32(const float *const *M, float *const *R, const int64_t *B, int n, void *stream) {
+    SO3_CHECK_ARGS(n >= 1 && n <= so3::kMaxSegments, "so3_project_fwd_segments_f32: n");
+    SO3_CHECK_ARGS(M != nullptr && R != nullptr && B != nullptr, "so3_project_fwd_segments_f32: null pointer");
+    K1Run run;
+    for (int i = 0; i < n; ++i) {
+        SO3_CHECK_ARGS(B[i] > 0 && B[i] % so3::kUnitRows == 0, "so3_project_fwd_segments_f32: B[i] must be a positive multiple of 64");
+        SO3_CHECK_ARGS(M[i] != nullptr && R[i] != nullptr, "so3_project_fwd_segments_f32: null pointer");
+        SO3_CHECK_ARGS(aligned4(M[i]) && aligned4(R[i]), "so3_project_fwd_segments_f32: pointers must be dword aligned");
+        run.in[i] = M[i]; run.out[i] = R[i]; run.rows[i] = B[i];
+        run.n = i + 1;
+        SO3_CHECK_ARGS(k1_rounds(run) <= kMaxRounds32, "so3_project_fwd_segments_f32: too many rows in all");
+    }
+    k1_launch<4>(run, static_cast<hipStream_t>(stream));
+    g_k1_captured.node = nullptr;
+    return check_launch("so3_project_fwd_segments_f32");
+}
+int so3_capture_fusion(int enable) { return g_capture_fusion.exchange(enable != 0 ? 1 : 0); }
+int64_t so3_capture_fused_launches(void) { return g_k1_fused; }
+int so3_capture_fusion_would_fuse(const void *const *rec_M, void *const *rec_R, const int64_t *rec_B, int rec_n, int rec_elem_bytes,
+                                  int same_capture, int ndeps, int dep_is_recorded_node, int elem_bytes, const void *M, const void *R,
+                                  int64_t B) {
+    SO3_CHECK_ARGS(rec_n >= 0 && rec_n <= so3::kMaxSegments && (rec_n == 0 || (rec_M != nullptr && rec_R != nullptr && rec_B != nullptr)),
+                   "so3_capture_fusion_would_fuse: record");
+    int marks[2];                              // two distinct addresses stand for the recorded node and for any other (never dereferenced)
+    K1Captured rec;
+    rec.capture_id = 1;
+    rec.node = rec_n > 0 ? reinterpret_cast<hipGraphNode_t>(&marks[0]) : nullptr;
+    rec.run.n = rec_n;
+    rec.run.elem_bytes = rec_elem_bytes;
+    for (int i = 0; i < rec_n; ++i) { rec.run.in[i] = rec_M[i]; rec.run.out[i] = static_cast<float *>(rec_R[i]); rec.run.rows[i] = rec_B[i]; }
+    return k1_may_fuse(rec, same_capture != 0 ? 1 : 2, static_cast<size_t>(ndeps < 0 ? 0 : ndeps),
+                       reinterpret_cast<hipGraphNode_t>(&marks[dep_is_recorded_node != 0 ? 0 : 1]), elem_bytes, M, R, B) ? 1 : 0;
 }
 int so3_project_bwd_f32(const float *M, const float *G, float *dM, int64_t B, void *stream) {
     return project_bwd<false>(M, G, dM, B, stream);

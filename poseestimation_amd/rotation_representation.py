@@ -369,6 +369,29 @@ def symmetric_orthogonalization_with_flip(x: torch.Tensor):
     return r, flip.bool()
 
 
+def symmetric_orthogonalization_segments(xs):
+    """[(B_i, 9) float32, ...] -> [(B_i, 3, 3), ...]: up to eight independent batches in ONE launch of the streaming engine
+    (so3_project_fwd_segments_f32: every B_i a positive multiple of 64).  The same bits as symmetric_orthogonalization on each;
+    what it saves is the launch boundary between them.  Not differentiable."""
+    import ctypes
+    xs = list(xs)
+    dev = _require_device(*xs)
+    ms = []
+    for x in xs:
+        m = _as_blocks(x.detach())
+        if m.dtype is not torch.float32:
+            raise TypeError(f"symmetric_orthogonalization_segments: float32 input only, got {m.dtype}")
+        ms.append(m)
+    rs = [torch.empty((m.shape[0], 3, 3), dtype=torch.float32, device=dev) for m in ms]
+    n = len(ms)
+    in_ptrs = (ctypes.c_void_p * max(n, 1))(*[m.data_ptr() for m in ms])
+    out_ptrs = (ctypes.c_void_p * max(n, 1))(*[r.data_ptr() for r in rs])
+    rows = (ctypes.c_int64 * max(n, 1))(*[m.shape[0] for m in ms])
+    with _on_device(dev):
+        _check(_libh().so3_project_fwd_segments_f32(in_ptrs, out_ptrs, rows, n, _stream(dev)), "so3_project_fwd_segments_f32")
+    return rs
+
+
 # --------------------------------------------------------------------------------------------
 # K4: metrics
 # --------------------------------------------------------------------------------------------

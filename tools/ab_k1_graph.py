@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """A/B of K1 between builds of the library: per build one hipGraph of 500 launches (1M rows, 8 rotating buffers);
-builds are interleaved, each measured as the mean of 4 timed replays after 2 untimed ones.  usage: ab_k1_graph.py a.so b.so ..."""
+builds are interleaved, each measured as the mean of 4 timed replays after 2 untimed ones.  usage: ab_k1_graph.py a.so b.so ...
+A build given as `path@nofuse` is captured with so3_capture_fusion(0) (the switch is process-wide PER LOADED FILE: to compare one
+build with and without fusion, give it under two file names).  AB_EAGER=n adds, per round and build, the time per launch of n eager
+launches over the same buffers (columns `name/eager`)."""
 import ctypes, sys
 import torch
 
@@ -11,8 +14,12 @@ x = [torch.randn(n, 9, device=dev) for _ in range(NB)]
 r = [torch.empty(n, 9, device=dev) for _ in range(NB)]
 graphs = {}
 side = torch.cuda.Stream()
-for path in sys.argv[1:]:
+EAGER = int(__import__("os").environ.get("AB_EAGER", "0"))
+for spec in sys.argv[1:]:
+    path, _, mode = spec.partition("@")
     lib = ctypes.CDLL(path)
+    if mode == "nofuse":
+        lib.so3_capture_fusion(0)
     lib.so3_project_fwd_f32.restype = ctypes.c_int
     lib.so3_project_fwd_f32.argtypes = [P, P, P, ctypes.c_int64, P]
     g = torch.cuda.CUDAGraph()
@@ -22,7 +29,7 @@ for path in sys.argv[1:]:
             st = P(side.cuda_stream)
             for i in range(K):
                 assert lib.so3_project_fwd_f32(P(x[i % NB].data_ptr()), P(r[i % NB].data_ptr()), None, n, st) == 0
-    graphs[path.split("/")[-1]] = (g, lib)
+    graphs[spec.split("/")[-1]] = (g, lib)
 torch.cuda.synchronize()
 names = list(graphs)
 for rnd in range(int(__import__("os").environ.get("AB_ROUNDS", "4"))):
@@ -39,4 +46,16 @@ for rnd in range(int(__import__("os").environ.get("AB_ROUNDS", "4"))):
             b.record(side)
         torch.cuda.synchronize()
         line.append((name, a.elapsed_time(b) * 1e3 / (4 * K)))
-    print("  ".join("%s %.2f" % (n_, dict(line)[n_]) for n_ in names), flush=True)
+        if EAGER:
+            lib = graphs[name][1]
+            with torch.cuda.stream(side):
+                st = P(side.cuda_stream)
+                for i in range(NB):
+                    lib.so3_project_fwd_f32(P(x[i].data_ptr()), P(r[i].data_ptr()), None, n, st)
+                a.record(side)
+                for i in range(EAGER):
+                    lib.so3_project_fwd_f32(P(x[i % NB].data_ptr()), P(r[i % NB].data_ptr()), None, n, st)
+                b.record(side)
+            torch.cuda.synchronize()
+            line.append((name + "/eager", a.elapsed_time(b) * 1e3 / EAGER))
+    print("  ".join("%s %.2f" % (n_, v) for n_, v in sorted(line, key=lambda kv: (kv[0].endswith("/eager"), names.index(kv[0].split("/eager")[0])))), flush=True)

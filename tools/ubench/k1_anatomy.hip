@@ -55,6 +55,7 @@ void run(const char *what, float **in, float **out, unsigned long long *stamps_d
     // reducing operations add onto a scratch accumulator with one atomic per workgroup (the library's no-workspace path)
     auto mk = [&](int i) {
         Op op; op.in0 = in[i % NBUF]; op.out0 = out[i % NBUF];
+        if constexpr (Op::kSegmented) op.template add_segment<NPL>(in[i % NBUF], out[i % NBUF], nunits);      // K1 reads its buffers from its segment table
         if constexpr (Op::kIn1 != 0) op.in1 = g_rot[(i + 1) % NBUF];
         if constexpr (Op::kOut0 == 0) op.out0 = nullptr;
         if constexpr (Op::kReduce) { op.sum_count = g_acc; op.range_flag = g_flag; op.unit_scale = 57.29577951308232; op.count = (double)ROWS; }
@@ -144,7 +145,7 @@ int main(int argc, char **argv) {
             CHECK(hipMalloc(&g_rot[i], ROWS * 9 * 4));
             float *tmp; CHECK(hipMalloc(&tmp, ROWS * 9 * 4));
             hipLaunchKernelGGL(fill, dim3((ROWS * 9 + 255) / 256), dim3(256), 0, 0, tmp, ROWS * 9, 777u + i);
-            K1 op; op.in0 = tmp; op.out0 = g_rot[i];
+            K1 op; op.add_segment<2>(tmp, g_rot[i], ROWS / 64);
             hipLaunchKernelGGL((so3::k_rows<K1, 2, 3, 256, false>), dim3(768), dim3(256), 0, 0, op, ROWS / 64, nullptr);
             CHECK(hipDeviceSynchronize()); CHECK(hipFree(tmp));
         }
