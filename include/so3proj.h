@@ -674,6 +674,45 @@ int so3_three_interpolate_f32(const float *feat, const int32_t *idx, const float
 int so3_three_interpolate_bwd_f32(const float *grad_out, const int32_t *idx, const float *weight, float *grad_feat,
                                   int32_t channels_first, int64_t B, int32_t N, int32_t S, int32_t D, void *stream);
 
+/* ---- PointNet++ set abstraction: the grouping gather and its backward (added in 210) ----
+ * What every PointNetSetAbstraction / PointNetSetAbstractionMsg forward does between the ball query and its first Conv2d
+ * (point_cloud/pointnet_utils.py:117-124 and :234-242): two advanced-index gathers, a subtraction, a cat and a permute that the
+ * convolution then makes contiguous -- here one launch that writes the layer's own layout, and one backward call that is a gather.
+ *
+ *   xyz (B,N,3), centres (B,S,3) and idx (B,S,K) int32 are always in these layouts.  C = 3 + D; D == 0 is legal, and then feat and
+ *   grad_feat are not read (pass NULL).
+ *   channels_first == 0:  feat (B,N,D);  out / grad_out (B,S,K,C)   (the reference's internal layout)
+ *   channels_first != 0:  feat (B,D,N);  out / grad_out (B,C,K,S)   (what the layer receives, and what its permute(0,3,2,1) hands
+ *                         to Conv2d)
+ *   features_first == 0:  channels 0..2 are the relative coordinates, then the D features   (sample_and_group: cat([xyz_norm, points]))
+ *   features_first != 0:  the D features first, then the three relative coordinates   (the Msg layer: cat([grouped_points, grouped_xyz]))
+ *
+ * THE FORWARD IS A DEFINITION.  A relative coordinate is  xyz[b][idx[b][s][k]][j] - centres[b][s][j],  one float32 subtraction; a
+ *   feature is a copy.
+ * AN INDEX OUTSIDE [0, N) -- so3_ball_query_f32 writes N into every slot of an empty ball; a negative index falls under the same
+ *   rule -- gives 0 IN EVERY CHANNEL of that slot, and the slot takes and gives no gradient: nothing of it reaches grad_xyz, grad_feat
+ *   or grad_centres.  No index can make a kernel read or write outside a buffer.  (The reference's index_points raises an IndexError
+ *   there.)
+ * THE BACKWARD, so3_group_points_bwd_f32:
+ *   grad_xyz[b][n][j] and grad_feat[b][n][d] (feat's layout) are the sums of the matching channel of grad_out over all slots (s, k)
+ *   with idx[b][s][k] == n;  grad_centres[b][s][j] = 0 - (the sum of coordinate channel j over the valid slots k of row (b, s)).
+ *   THE SUMMATION ORDER IS PART OF THE DEFINITION: every sum starts at 0 and takes its terms by plain float32 additions in the
+ *   ascending MEMORY order of grad_out's slots --
+ *       channels_first == 0:  ascending (s, k), s the slow index;      channels_first != 0:  ascending (k, s), k the slow index;
+ *       grad_centres: ascending k in both layouts.
+ *   The order does not depend on B, on the launch's grid or on which outputs are requested.
+ *   Each of grad_xyz, grad_centres and grad_feat is optional (NULL: not computed).  Every element of a requested output is written
+ *   exactly once, 0 for a point nobody selected.  grad_out is read once per 64 points of the cloud (and once more for grad_centres).
+ * 1 <= N, S <= SO3_ADD_S_MAX_N, 1 <= K <= SO3_GROUP_MAX_K, 0 <= D <= SO3_THREE_MAX_D.  Offsets into out and grad_out are 64-bit.
+ * Neither call uses atomics, a workspace or a memset, neither synchronises with the host; both can be captured in a graph and give
+ * the same bits from call to call.  B == 0 is a no-op whatever the pointers.
+ */
+#define SO3_GROUP_MAX_K 65536
+int so3_group_points_f32(const float *xyz, const float *centres, const float *feat, const int32_t *idx, float *out, int32_t features_first,
+                         int32_t channels_first, int64_t B, int32_t N, int32_t S, int32_t K, int32_t D, void *stream);
+int so3_group_points_bwd_f32(const float *grad_out, const int32_t *idx, float *grad_xyz, float *grad_centres, float *grad_feat,
+                             int32_t features_first, int32_t channels_first, int64_t B, int32_t N, int32_t S, int32_t K, int32_t D, void *stream);
+
 /* ---- next row: on-device pair synthesis for Kabsch ------------------------------
  * so3_rotations_axis_angle_f32: the arithmetic of the reference's sampler, point_cloud/prepare.py:21-49
  *   (normalize_vector :12-18, quaternion (cos theta, axis sin theta) -> matrix :27-47), given the random

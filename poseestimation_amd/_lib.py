@@ -79,6 +79,8 @@ SYMBOLS = {
     "so3_three_nn_f32": (_INT, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _P]),
     "so3_three_interpolate_f32": (_INT, [_P, _P, _P, _P, _I32, _I64, _I32, _I32, _I32, _P]),
     "so3_three_interpolate_bwd_f32": (_INT, [_P, _P, _P, _P, _I32, _I64, _I32, _I32, _I32, _P]),
+    "so3_group_points_f32": (_INT, [_P, _P, _P, _P, _P, _I32, _I32, _I64, _I32, _I32, _I32, _I32, _P]),
+    "so3_group_points_bwd_f32": (_INT, [_P, _P, _P, _P, _P, _I32, _I32, _I64, _I32, _I32, _I32, _I32, _P]),
     "so3_rotate_clouds_bwd_f32": (_INT, [_P, _P, _P, _P, _P, _INT, _I64, _I32, _P]),
     "so3_rotations_axis_angle_f32": (_INT, [_P, _P, _P, _I64, _P]),
     "so3_kabsch_synth_f32": (_INT, [_P, _P, ctypes.c_float, ctypes.c_uint32, _P, _P, _I64, _I32, _P]),
@@ -89,6 +91,7 @@ SYMBOLS = {
 ADD_S_MAX_N = 1 << 20                             # include/so3proj.h: SO3_ADD_S_MAX_N
 FPS_MAX_N = 16384                                 # include/so3proj.h: SO3_FPS_MAX_N
 THREE_MAX_D = 65536                               # include/so3proj.h: SO3_THREE_MAX_D
+GROUP_MAX_K = 65536                               # include/so3proj.h: SO3_GROUP_MAX_K
 ABI_VERSION = 210                                 # include/so3proj.h: SO3PROJ_VERSION this binding's argument lists belong to
 
 _lock = threading.Lock()

@@ -1356,4 +1356,28 @@ inline int three_nn_waves_per_point(int64_t B, int32_t N, int32_t S) {
     return (S >= kThreeNnSplitS && B * ((N + kIcpBlock - 1) / kIcpBlock) < kThreeNnSplitItems) ? 4 : 1;
 }
 
+// ---- PointNet++ set abstraction: the grouping gather and its backward (so3proj.hip: k_group_fwd, k_group_bwd, k_group_centres_bwd;
+// tests/host_model/grouping.cpp) ---------------------------------------------------------------------------------------------------
+// The forward is a DEFINITION (include/so3proj.h): a relative coordinate is one float32 subtraction, a feature is a copy, a slot whose
+// index lies outside [0, N) is 0 in every channel.  The backward's sums are plain float32 additions from 0 in the ascending MEMORY
+// order of grad_out's slots: (s, k) channel-last, (k, s) channel-first; grad_centres is minus the sum over ascending k.
+__device__ __forceinline__ bool group_valid(int32_t i, int32_t N) { return static_cast<uint32_t>(i) < static_cast<uint32_t>(N); }
+__device__ __forceinline__ float group_relative(float x, float centre) { return x - centre; }
+__device__ __forceinline__ float group_bwd_add(float acc, float g) { return acc + g; }
+// Output channel c of C = 3 + D: which coordinate (0..2) it is, or -1 for a feature, whose number goes to d.
+__device__ __forceinline__ int group_channel(bool features_first, int32_t D, int32_t c, int32_t &d) {
+    d = features_first ? c : c - 3;
+    return features_first ? (c >= D ? c - D : -1) : (c < 3 ? c : -1);
+}
+// k_group_bwd<CF, CW, R>: a wave's 64 lanes are 64 / CW owner groups x CW channels, and a lane keeps R owners, so a wave owns
+// 64 / CW * R points and a workgroup four times as many.  Up to kGroupNarrowC channels (3 + D <= 8: a first set-abstraction level
+// with up to five features) eight owner groups x eight channels fill the wave and a lane keeps two owners; above, a lane is a channel
+// and keeps sixteen owners.
+constexpr int kGroupNarrowC = 8;
+constexpr int kGroupNarrowTile = 1024, kGroupWideTile = 128;      // slots of grad_out per LDS tile
+constexpr int kGroupNarrowOwners = 64, kGroupWideOwners = 64;     // points per work item
+constexpr int kGroupWideChannels = 64;                            // channels per work item of the wide kernel
+constexpr int kGroupFwdCfChannels = 16;                           // k_group_fwd<true>: channels per work item
+inline bool group_bwd_narrow(int32_t D) { return 3 + D <= kGroupNarrowC; }
+
 }  // namespace so3

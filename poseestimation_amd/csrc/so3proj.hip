@@ -2161,6 +2161,214 @@ __global__ __launch_bounds__(kBlock) void k_three_interp_bwd_cf(const float *__r
     }
 }
 
+// ---- PointNet++ set abstraction: the grouping gather and its backward -------------------------------------------------------------
+// What sample_and_group does between the ball query and the first Conv2d: gather the grouped coordinates and
+// features, subtract the centre, concatenate, in the layout the caller asks for.  A slot whose index lies outside [0, N) -- an empty
+// ball's N, or a negative index -- is 0 in every channel and takes no gradient; no index can make a kernel leave a buffer.
+// k_group_fwd<CF>:
+// CF = false, -> (B,S,K,C): a group of gw = min(64, C rounded up to a power of two) lanes per slot, 64 / gw slots per wave; the
+//   lanes run over the channels, so the point's row is read and the slot's row is written contiguously (k_three_interp<false>).
+// CF = true, -> (B,C,K,S): one work item = kBlock centres x kGroupFwdCfChannels channels of one (cloud, k); a lane keeps its slot's
+//   index and walks the channels, so every store is contiguous over s and every load is a gather inside the cloud's coordinates or
+//   inside one feature row of N floats.
+template <bool CF>
+__global__ __launch_bounds__(kBlock) void k_group_fwd(const float *__restrict__ xyz, const float *__restrict__ centres, const float *__restrict__ feat,
+                                                      const int32_t *__restrict__ idx, float *__restrict__ out, int32_t features_first, int64_t B,
+                                                      int32_t N, int32_t S, int32_t K, int32_t D, int32_t gw) {
+    const int32_t C = 3 + D;
+    const bool ff = features_first != 0;
+    if (!CF) {
+        const int lane = threadIdx.x & 63, sub = lane / gw, c0 = lane % gw, rpw = 64 / gw;
+        const int64_t wave = static_cast<int64_t>(blockIdx.x) * (kBlock / 64) + (threadIdx.x >> 6);
+        const int64_t nwaves = static_cast<int64_t>(gridDim.x) * (kBlock / 64), rows = B * S * K;
+        for (int64_t row0 = wave * rpw; row0 < rows; row0 += nwaves * rpw) {
+            const int64_t row = row0 + sub;
+            if (row >= rows) continue;
+            const int64_t bs = row / K, b = bs / S;
+            const int32_t i = idx[row];
+            const bool ok = so3::group_valid(i, N);
+            const int64_t src = b * N + (ok ? i : 0);
+            for (int32_t c = c0; c < C; c += gw) {
+                int32_t d;
+                const int j = so3::group_channel(ff, D, c, d);
+                float v = 0.f;
+                if (ok) v = j >= 0 ? so3::group_relative(xyz[src * 3 + j], centres[bs * 3 + j]) : feat[src * D + d];
+                out[row * C + c] = v;
+            }
+        }
+    } else {
+        const int schunks = (S + kBlock - 1) / kBlock, cchunks = (C + so3::kGroupFwdCfChannels - 1) / so3::kGroupFwdCfChannels;
+        const int64_t items = B * K * schunks * cchunks;
+        for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+            const int sc = static_cast<int>(item % schunks);
+            int64_t rest = item / schunks;
+            const int32_t k = static_cast<int32_t>(rest % K);
+            rest /= K;
+            const int32_t cbase = static_cast<int32_t>(rest % cchunks) * so3::kGroupFwdCfChannels;
+            const int64_t b = rest / cchunks;
+            const int32_t s = sc * kBlock + static_cast<int32_t>(threadIdx.x);
+            if (s >= S) continue;
+            const int64_t bs = b * S + s;
+            const int32_t i = idx[bs * K + k];
+            const bool ok = so3::group_valid(i, N);
+            const int64_t src = ok ? i : 0;
+            const int32_t cend = min(cbase + so3::kGroupFwdCfChannels, C);
+            for (int32_t c = cbase; c < cend; ++c) {
+                int32_t d;
+                const int j = so3::group_channel(ff, D, c, d);
+                float v = 0.f;
+                if (ok) v = j >= 0 ? so3::group_relative(xyz[(b * N + src) * 3 + j], centres[bs * 3 + j]) : feat[(b * D + d) * N + src];
+                out[((b * C + c) * K + k) * S + s] = v;
+            }
+        }
+    }
+}
+
+// The backward as a gather (k_three_interp_bwd_* above, with the scan shared): grad_xyz[b][n][j] and grad_feat[b][n][d] are the sums
+// of the matching channel of grad_out over the slots that selected n, by plain float32 additions from 0 in the ascending MEMORY order
+// of the slots -- (s, k) channel-last, (k, s) channel-first.  Every requested element is written once, zeros included: no atomics, no
+// memset, no workspace, the same bits every call.
+// k_group_bwd<CF, CW, R>: one work item = 4 * (64 / CW) * R points x CW channels of one cloud.  grad_out streams through LDS in
+//   memory order, T slots x CW channels per tile (channel-first: read with the lanes over the slots and stored transposed, stride
+//   CW + 1, so neither side has bank conflicts), with the tile's indices beside it (invalid ones as -1).  A wave then scans the
+//   indices 64 at a time ONCE for all its owners: idx - (its first owner) against its owner count, one ballot; a step without a hit
+//   costs nothing more.  A hit is walked in ascending order; lane (u, c) adds the slot's channel c to the owner it keeps if the hit is
+//   that owner's (R > 1: one ballot per r, so the accumulator's index is static).
+//   <CF, 8, 2>: 3 + D <= 8, eight owner groups x eight channels per wave.  <CF, 64, 16>: a lane per channel, sixteen owners per lane.
+//   A wave's owners are the points n = w (mod WT), WT the waves that share the cloud, not a run of neighbours: a ball query pads its
+//   rows with their FIRST hit, the lowest index in the ball, so the low indices of a cloud take most of the hits and a wave that owned
+//   points 0..15 would walk many times the average wave's hits, one after the other.  The scan sees idx % WT * 16 + idx / WT.
+//   A work item whose channels hold no requested output is skipped, so a subset of the outputs gives the bits of the whole.
+template <bool CF, int CW, int R>
+__global__ __launch_bounds__(kBlock) void k_group_bwd(const float *__restrict__ grad_out, const int32_t *__restrict__ idx, float *__restrict__ grad_xyz,
+                                                      float *__restrict__ grad_feat, int32_t features_first, int64_t B, int32_t N, int32_t S,
+                                                      int32_t K, int32_t D) {
+    constexpr int T = CW == so3::kGroupNarrowC ? so3::kGroupNarrowTile : so3::kGroupWideTile;
+    constexpr int PW = 64 / CW * R, PG = PW * (kBlock / 64);
+    constexpr int NL = T * CW / kBlock, NI = (T + kBlock - 1) / kBlock;             // loads of one lane per tile: 32 values, 4 or 1 indices
+    static_assert(PG == (CW == so3::kGroupNarrowC ? so3::kGroupNarrowOwners : so3::kGroupWideOwners) && (R & (R - 1)) == 0 && T % 64 == 0 &&
+                      T * CW % kBlock == 0, "so3_device.h");
+    __shared__ float gt[T * (CW + 1)];
+    __shared__ int32_t t_i[T];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int u = lane / CW, cl = lane % CW;
+    const int32_t C = 3 + D;
+    const bool ff = features_first != 0;
+    const int32_t xb = ff ? D : 0, fb = ff ? 0 : 3;              // the first coordinate channel, the first feature channel
+    const int64_t E = static_cast<int64_t>(S) * K;
+    const int ngroups = (N + PG - 1) / PG, cchunks = (C + CW - 1) / CW;
+    const int32_t WT = ngroups * (kBlock / 64);                  // the waves that share a cloud's points: wave w owns the points n = w (mod WT)
+    const int64_t items = B * ngroups * cchunks;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t b = item / (static_cast<int64_t>(ngroups) * cchunks);
+        const int rest = static_cast<int>(item - b * ngroups * cchunks);
+        const int32_t c0 = rest / ngroups * CW, cw = min(CW, C - c0);
+        const bool has_xyz = grad_xyz != nullptr && c0 < xb + 3 && c0 + cw > xb;
+        const bool has_feat = grad_feat != nullptr && c0 < fb + D && c0 + cw > fb;
+        if (!has_xyz && !has_feat) continue;                                         // workgroup-uniform
+        const int32_t nw0 = rest % ngroups * PG + wave * PW;                         // the wave's first owner
+        const int32_t *ib = idx + b * E;
+        const float *gb = grad_out + b * E * C;
+        float acc[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r] = 0.f;
+        // A tile's loads: NL values and NI indices per lane, every address clamped into the buffer (no branch around a load), all in
+        // flight together; the next tile's are issued before the current tile is scanned and wait in registers.
+        float pre[NL];
+        int32_t pi[NI];
+        auto load_tile = [&](int64_t t0) {
+            const int cnt = static_cast<int>(min(static_cast<int64_t>(T), E - t0));
+            const int64_t k0 = CF ? t0 / S : 0;
+            const int32_t s0 = CF ? static_cast<int32_t>(t0 - k0 * S) : 0;                 // s0 + q < S + T: int32
+#pragma unroll
+            for (int m = 0; m < NI; ++m) {
+                const int q = min(tid + m * kBlock, cnt - 1);
+                const int32_t kq = CF ? (s0 + q) / S : 0, sq = s0 + q - kq * S;
+                pi[m] = ib[CF ? static_cast<int64_t>(sq) * K + k0 + kq : t0 + q];
+            }
+#pragma unroll
+            for (int m = 0; m < NL; ++m) {
+                const int q = tid + m * kBlock;
+                const int cc = min(CF ? q / T : q % CW, cw - 1), jj = min(CF ? q % T : q / CW, cnt - 1);
+                pre[m] = gb[CF ? static_cast<int64_t>(c0 + cc) * E + t0 + jj : (t0 + jj) * C + c0 + cc];
+            }
+        };
+        load_tile(0);
+        for (int64_t t0 = 0; t0 < E; t0 += T) {
+            const int cnt = static_cast<int>(min(static_cast<int64_t>(T), E - t0)), cntp = (cnt + 63) / 64 * 64;
+            __syncthreads();                                                         // the previous tile has been read
+#pragma unroll
+            for (int m = 0; m < NI; ++m) {
+                const int q = tid + m * kBlock;
+                if (q < T) t_i[q] = q < cnt && so3::group_valid(pi[m], N) ? pi[m] % WT * PW + pi[m] / WT : -1;   // the point's place among the owners
+            }
+#pragma unroll
+            for (int m = 0; m < NL; ++m) {
+                const int q = tid + m * kBlock;
+                gt[(CF ? q % T : q / CW) * (CW + 1) + (CF ? q / T : q % CW)] = pre[m];   // a clamped load lands in a slot or channel nobody reads
+            }
+            __syncthreads();
+            if (t0 + T < E) load_tile(t0 + T);                                       // workgroup-uniform
+            for (int k0 = 0; k0 < cntp; k0 += 64) {
+                const int32_t v = t_i[k0 + lane] - nw0;
+                const bool in = static_cast<uint32_t>(v) < static_cast<uint32_t>(PW);
+                if (__builtin_amdgcn_ballot_w64(in) == 0) continue;                  // wave-uniform: nobody here owns any of the 64 slots
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    unsigned long long mask = __builtin_amdgcn_ballot_w64(in && (v & (R - 1)) == r);
+                    while (mask != 0) {                                              // wave-uniform
+                        const int e = k0 + __builtin_ctzll(mask);
+                        mask &= mask - 1;
+                        const int32_t vh = (t_i[e] - nw0) / R;
+                        const float g = gt[e * (CW + 1) + cl];
+                        acc[r] = vh == u ? so3::group_bwd_add(acc[r], g) : acc[r];
+                    }
+                }
+            }
+        }
+        const int32_t c = c0 + cl;
+        if (c >= C) continue;                                                        // no barrier follows in this iteration
+        int32_t d;
+        const int j = so3::group_channel(ff, D, c, d);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int64_t n = static_cast<int64_t>((u * R + r) % PW) * WT + (nw0 + u * R + r) / PW;
+            if (n >= N) continue;
+            if (j >= 0) {
+                if (grad_xyz != nullptr) grad_xyz[(b * N + n) * 3 + j] = acc[r];
+            } else if (grad_feat != nullptr) {
+                grad_feat[CF ? (b * D + d) * N + n : (b * N + n) * D + d] = acc[r];
+            }
+        }
+    }
+}
+
+// grad_centres[b][s][j] = 0 - (the sum over ascending k of coordinate channel j of the valid slots of row (b, s)): a thread per centre.
+template <bool CF>
+__global__ __launch_bounds__(kBlock) void k_group_centres_bwd(const float *__restrict__ grad_out, const int32_t *__restrict__ idx,
+                                                              float *__restrict__ grad_centres, int32_t features_first, int64_t B, int32_t N,
+                                                              int32_t S, int32_t K, int32_t D) {
+    const int32_t C = 3 + D, xb = features_first != 0 ? D : 0;
+    const int64_t rows = B * S, step = static_cast<int64_t>(gridDim.x) * kBlock;
+    for (int64_t row = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; row < rows; row += step) {
+        const int64_t b = row / S, s = row - b * S;
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+        const int64_t cs = CF ? static_cast<int64_t>(K) * S : 1;
+#pragma unroll 8
+        for (int32_t k = 0; k < K; ++k) {                                            // no load depends on the index: no branch, the loads overlap
+            const bool ok = so3::group_valid(idx[row * K + k], N);
+            const float *g = CF ? grad_out + ((b * C + xb) * K + k) * S + s : grad_out + (row * K + k) * C + xb;
+            const float g0 = g[0], g1 = g[cs], g2 = g[2 * cs];
+            a0 = ok ? so3::group_bwd_add(a0, g0) : a0;
+            a1 = ok ? so3::group_bwd_add(a1, g1) : a1;
+            a2 = ok ? so3::group_bwd_add(a2, g2) : a2;
+        }
+        grad_centres[row * 3 + 0] = 0.f - a0;
+        grad_centres[row * 3 + 1] = 0.f - a1;
+        grad_centres[row * 3 + 2] = 0.f - a2;
+    }
+}
+
 // ---- float64 head and backward (the reference's functions accept double tensors): the same templates over
 // T = double, one row per thread with plain loads -- a convenience path, not a benchmark configuration.
 // Four fixed sweeps, then sweeps until the wave-wide residual is below 1e-14 (at most six more).
@@ -4251,6 +4459,66 @@ int so3_three_interpolate_bwd_f32(const float *grad_out, const int32_t *idx, con
     if (channels_first) hipLaunchKernelGGL(k_three_interp_bwd_cf, grid, block, 0, s, grad_out, idx, weight, grad_feat, B, N, S, D);
     else hipLaunchKernelGGL(k_three_interp_bwd_cl, grid, block, 0, s, grad_out, idx, weight, grad_feat, B, N, S, D);
     return check_launch("so3_three_interpolate_bwd_f32");
+}
+
+int so3_group_points_f32(const float *xyz, const float *centres, const float *feat, const int32_t *idx, float *out, int32_t features_first,
+                         int32_t channels_first, int64_t B, int32_t N, int32_t S, int32_t K, int32_t D, void *stream) {
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && S >= 1 && S <= SO3_ADD_S_MAX_N && K >= 1 &&
+                       K <= SO3_GROUP_MAX_K && D >= 0 && D <= SO3_THREE_MAX_D,
+                   "so3_group_points_f32: B/N/S/K/D");
+    if (B == 0) return 0;
+    SO3_CHECK_ARGS(xyz != nullptr && centres != nullptr && idx != nullptr && out != nullptr && (D == 0 || feat != nullptr),
+                   "so3_group_points_f32: null pointer");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int32_t C = 3 + D;
+    int32_t gw = 64;
+    while (gw > 1 && gw / 2 >= C) gw >>= 1;
+    int64_t blocks;
+    if (channels_first) {
+        g_last_kernel = "k_group_fwd<true>";
+        blocks = B * K * ((S + kBlock - 1) / kBlock) * ((C + so3::kGroupFwdCfChannels - 1) / so3::kGroupFwdCfChannels);
+    } else {
+        g_last_kernel = "k_group_fwd<false>";
+        const int64_t rows_per_block = (kBlock / 64) * (64 / gw);
+        blocks = (B * S * K + rows_per_block - 1) / rows_per_block;
+    }
+    const dim3 grid(static_cast<unsigned>(std::min<int64_t>(blocks, kThreeMaxGrid))), block(kBlock);
+    if (channels_first) hipLaunchKernelGGL(k_group_fwd<true>, grid, block, 0, s, xyz, centres, feat, idx, out, features_first, B, N, S, K, D, gw);
+    else hipLaunchKernelGGL(k_group_fwd<false>, grid, block, 0, s, xyz, centres, feat, idx, out, features_first, B, N, S, K, D, gw);
+    return check_launch("so3_group_points_f32");
+}
+
+int so3_group_points_bwd_f32(const float *grad_out, const int32_t *idx, float *grad_xyz, float *grad_centres, float *grad_feat,
+                             int32_t features_first, int32_t channels_first, int64_t B, int32_t N, int32_t S, int32_t K, int32_t D, void *stream) {
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && S >= 1 && S <= SO3_ADD_S_MAX_N && K >= 1 &&
+                       K <= SO3_GROUP_MAX_K && D >= 0 && D <= SO3_THREE_MAX_D,
+                   "so3_group_points_bwd_f32: B/N/S/K/D");
+    if (B == 0) return 0;
+    SO3_CHECK_ARGS(grad_out != nullptr && idx != nullptr, "so3_group_points_bwd_f32: null pointer");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 block(kBlock);
+    if (D == 0) grad_feat = nullptr;
+    if (grad_centres != nullptr) {
+        const dim3 grid(static_cast<unsigned>(std::min<int64_t>((B * S + kBlock - 1) / kBlock, kThreeMaxGrid)));
+        g_last_kernel = channels_first ? "k_group_centres_bwd<true>" : "k_group_centres_bwd<false>";
+        if (channels_first) hipLaunchKernelGGL(k_group_centres_bwd<true>, grid, block, 0, s, grad_out, idx, grad_centres, features_first, B, N, S, K, D);
+        else hipLaunchKernelGGL(k_group_centres_bwd<false>, grid, block, 0, s, grad_out, idx, grad_centres, features_first, B, N, S, K, D);
+    }
+    if (grad_xyz != nullptr || grad_feat != nullptr) {
+        const bool narrow = so3::group_bwd_narrow(D);
+        const int owners = narrow ? so3::kGroupNarrowOwners : so3::kGroupWideOwners, cw = narrow ? so3::kGroupNarrowC : so3::kGroupWideChannels;
+        const int64_t blocks = B * ((N + owners - 1) / owners) * ((3 + D + cw - 1) / cw);
+        const dim3 grid(static_cast<unsigned>(std::min<int64_t>(blocks, kThreeMaxGrid)));
+#define GROUP_BWD(CF, CW, R)                                                                                                               \
+    do {                                                                                                                                   \
+        g_last_kernel = "k_group_bwd<" #CF ", " #CW ", " #R ">";                                                                            \
+        hipLaunchKernelGGL((k_group_bwd<CF, CW, R>), grid, block, 0, s, grad_out, idx, grad_xyz, grad_feat, features_first, B, N, S, K, D); \
+    } while (0)
+        if (narrow) { if (channels_first) GROUP_BWD(true, 8, 2); else GROUP_BWD(false, 8, 2); }
+        else { if (channels_first) GROUP_BWD(true, 64, 16); else GROUP_BWD(false, 64, 16); }
+#undef GROUP_BWD
+    }
+    return check_launch("so3_group_points_bwd_f32");
 }
 
 int so3_add_l1_disentangled_f32(const float *Tpred, const float *Tgt, const float *points, double *loss_sum, float *dTpred,

@@ -1485,6 +1485,139 @@ def sample_and_group(npoint: int, radius: float, nsample: int, xyz: torch.Tensor
     return new_xyz, new_points
 
 
+def sample_and_group_all(xyz: torch.Tensor, points: torch.Tensor):
+    """point_cloud/pointnet_utils.py:131-148, the group_all branch of a set-abstraction layer, plain torch: xyz (B, N, 3) and points
+    (B, N, D) or None -> (new_xyz (B, 1, 3) zeros, new_points (B, 1, N, 3 + D)), the coordinates as they are (no centre is subtracted)
+    followed by the features.  Differentiable in xyz and points."""
+    if xyz.dim() != 3 or (points is not None and (points.dim() != 3 or points.shape[:2] != xyz.shape[:2])):
+        raise RuntimeError("sample_and_group_all: expected xyz (B, N, C) and points (B, N, D) or None, got %s and %s"
+                           % (tuple(xyz.shape), None if points is None else tuple(points.shape)))
+    b, n, c = xyz.shape
+    new_xyz = torch.zeros(b, 1, c, device=xyz.device)
+    grouped_xyz = xyz.view(b, 1, n, c) if xyz.is_contiguous() else xyz.reshape(b, 1, n, c)
+    if points is None:
+        return new_xyz, grouped_xyz
+    return new_xyz, torch.cat([grouped_xyz, points.reshape(b, 1, n, -1)], dim=-1)
+
+
+class _GroupPoints(torch.autograd.Function):
+    """group_points as a graph node: backward is one call of so3_group_points_bwd_f32, a gather over the stored indices in a fixed
+    order (no atomics: the same bits from call to call), reading grad_out in the forward's output layout; only the gradients that are
+    needed are requested."""
+
+    @staticmethod
+    def forward(ctx, xyz, new_xyz, points, idx32, channels_first, features_first, dims):
+        b, n, s, k, d = dims
+        dev = xyz.device
+        x, c = xyz.detach().contiguous(), new_xyz.detach().contiguous()
+        f = points.detach().contiguous() if d else None
+        cf, ff = 1 if channels_first else 0, 1 if features_first else 0
+        out = torch.empty((b, 3 + d, k, s) if channels_first else (b, s, k, 3 + d), dtype=torch.float32, device=dev)
+        with _on_device(dev):
+            _check(_libh().so3_group_points_f32(_ptr(x), _ptr(c), _ptr(f), _ptr(idx32), _ptr(out), ff, cf, b, n, s, k, d, _stream(dev)),
+                   "so3_group_points_f32")
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(idx32)
+        ctx.meta = (cf, ff, dims, dev)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (idx32,) = ctx.saved_tensors
+        cf, ff, (b, n, s, k, d), dev = ctx.meta
+        need = ctx.needs_input_grad
+        if grad_out is None or not (need[0] or need[1] or (need[2] and d)):
+            return None, None, None, None, None, None, None
+        _no_double_backward(grad_out)
+        g = grad_out.detach().contiguous()
+        gx = torch.empty((b, n, 3), dtype=torch.float32, device=dev) if need[0] else None
+        gc = torch.empty((b, s, 3), dtype=torch.float32, device=dev) if need[1] else None
+        gf = torch.empty((b, d, n) if cf else (b, n, d), dtype=torch.float32, device=dev) if need[2] and d else None
+        with _on_device(dev):
+            _check(_libh().so3_group_points_bwd_f32(_ptr(g), _ptr(idx32), _ptr(gx), _ptr(gc), _ptr(gf), ff, cf, b, n, s, k, d, _stream(dev)),
+                   "so3_group_points_bwd_f32")
+        return gx, gc, gf, None, None, None, None
+
+
+def group_points(xyz: torch.Tensor, new_xyz: torch.Tensor, points, idx: torch.Tensor, channels_first: bool = False,
+                 features_first: bool = False) -> torch.Tensor:
+    """point_cloud/pointnet_utils.py:117-124 (sample_and_group) and :234-242 (PointNetSetAbstractionMsg.forward) in one launch: the
+    coordinates xyz (B, N, 3) gathered by idx (B, S, K) relative to their centre new_xyz (B, S, 3), concatenated with the gathered
+    features.  points is None, (B, N, D), or (B, D, N) with channels_first=True; the result is (B, S, K, 3 + D), or with
+    channels_first=True (B, 3 + D, K, S), what the layer's permute(0, 3, 2, 1) hands to its Conv2d -- already contiguous.
+    features_first=False is sample_and_group's channel order, cat([xyz_norm, points]); features_first=True the Msg layer's,
+    cat([grouped_points, grouped_xyz]).  idx is int64 or int32, as query_ball_point returns it.
+
+    The forward is a definition (include/so3proj.h): one float32 subtraction per coordinate, a copy per feature.  AN INDEX OUTSIDE
+    [0, N) -- query_ball_point writes N into every slot of an empty ball -- gives 0 in every channel of that slot and takes no
+    gradient, where the reference's index_points raises an IndexError; nothing is read or written outside the tensors.
+
+    Differentiable in xyz, new_xyz and points through ONE backward call (so3_group_points_bwd_f32) that computes only the gradients
+    that are needed: every point sums its hits in the ascending memory order of grad_out's slots -- no atomics, no zero-fill, the same
+    bits from call to call; a point nobody selected gets exactly 0.  A non-contiguous grad_out is copied first.  Double backward is
+    refused.  float32 only.  1 <= N, S <= ADD_S_MAX_N, 1 <= K <= GROUP_MAX_K, D <= THREE_MAX_D."""
+    tensors = (xyz, new_xyz, idx) if points is None else (xyz, new_xyz, points, idx)
+    dev = _require_device(*tensors)
+    ok = xyz.dim() == 3 and new_xyz.dim() == 3 and idx.dim() == 3 and xyz.shape[-1] == 3 and new_xyz.shape[-1] == 3 \
+        and new_xyz.shape[0] == xyz.shape[0] and idx.shape[:2] == new_xyz.shape[:2]
+    if ok and points is not None:
+        ok = points.dim() == 3 and points.shape[0] == xyz.shape[0] and points.shape[2 if channels_first else 1] == xyz.shape[1]
+    if not ok or idx.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError("group_points: expected xyz (B, N, 3), new_xyz (B, S, 3), points %s or None and idx (B, S, K) (int32 or int64), got "
+                           "%s, %s, %s and %s %s" % ("(B, D, N)" if channels_first else "(B, N, D)", tuple(xyz.shape), tuple(new_xyz.shape),
+                                                     None if points is None else tuple(points.shape), idx.dtype, tuple(idx.shape)))
+    if any(t.dtype is not torch.float32 for t in tensors[:-1]):
+        raise RuntimeError("group_points: float32 only, got %s" % ", ".join(str(t.dtype) for t in tensors[:-1]))
+    b, n, s, k = xyz.shape[0], xyz.shape[1], idx.shape[1], idx.shape[2]
+    d = 0 if points is None else points.shape[1 if channels_first else 2]
+    if not (1 <= n <= _lib.ADD_S_MAX_N and 1 <= s <= _lib.ADD_S_MAX_N and 1 <= k <= _lib.GROUP_MAX_K and d <= _lib.THREE_MAX_D):
+        raise RuntimeError("group_points: expected 1 <= N, S <= %d, 1 <= K <= %d and D <= %d, got N = %d, S = %d, K = %d, D = %d"
+                           % (_lib.ADD_S_MAX_N, _lib.GROUP_MAX_K, _lib.THREE_MAX_D, n, s, k, d))
+    if b == 0:
+        return xyz.new_zeros((0, 3 + d, k, s) if channels_first else (0, s, k, 3 + d))
+    idx32 = idx.detach().contiguous().int()
+    return _GroupPoints.apply(xyz, new_xyz, points if d else None, idx32, bool(channels_first), bool(features_first), (b, n, s, k, d))
+
+
+def _abstraction_args(name, xyz, points):
+    _require_device(*((xyz,) if points is None else (xyz, points)))
+    if xyz.dim() != 3 or xyz.shape[1] != 3 or (points is not None and (points.dim() != 3 or points.shape[0] != xyz.shape[0] or points.shape[2] != xyz.shape[2])):
+        raise RuntimeError("%s: expected xyz (B, 3, N) and points (B, D, N) or None, got %s and %s"
+                           % (name, tuple(xyz.shape), None if points is None else tuple(points.shape)))
+    return xyz.transpose(1, 2).contiguous()
+
+
+def set_abstraction_group(npoint: int, radius: float, nsample: int, xyz: torch.Tensor, points, group_all: bool = False, start=None):
+    """PointNetSetAbstraction.forward up to its MLP (point_cloud/pointnet_utils.py:175-185), in the layer's own channel-first layouts:
+    xyz (B, 3, N), points (B, D, N) or None -> (new_xyz (B, 3, S), new_points (B, 3 + D, K, S)), S = npoint, K = min(nsample, N), the
+    relative coordinates first.  Three launches: farthest_point_sample (from `start`), query_ball_point and
+    group_points(..., channels_first=True), whose output is what the first Conv2d takes -- no permute, no copy.  With group_all=True
+    (sample_and_group_all, :131-148) it returns ((B, 3, 1) zeros, (B, 3 + D, N, 1)): the coordinates as they are, then the features.
+    Differentiable in xyz and points."""
+    pts = _abstraction_args("set_abstraction_group", xyz, points)
+    if group_all:
+        new_points = (xyz if points is None else torch.cat([xyz, points], dim=1)).unsqueeze(-1)
+        return torch.zeros(xyz.shape[0], 3, 1, device=xyz.device), new_points
+    fps_idx = farthest_point_sample(pts, npoint, start)
+    new_xyz = index_points(pts, fps_idx)
+    idx = query_ball_point(radius, nsample, pts, new_xyz)
+    return new_xyz.transpose(1, 2), group_points(pts, new_xyz, points, idx, channels_first=True)
+
+
+def set_abstraction_msg_group(npoint: int, radius_list, nsample_list, xyz: torch.Tensor, points, start=None):
+    """PointNetSetAbstractionMsg.forward up to its convolutions (point_cloud/pointnet_utils.py:223-242), in the layer's own layouts:
+    xyz (B, 3, N), points (B, D, N) or None -> (new_xyz (B, 3, S), [(B, D + 3, K_i, S) for every radius]), the features first.  One
+    farthest_point_sample (from `start`), then per radius one query_ball_point and one group_points(..., channels_first=True,
+    features_first=True).  Differentiable in xyz and points."""
+    pts = _abstraction_args("set_abstraction_msg_group", xyz, points)
+    if len(radius_list) != len(nsample_list):
+        raise RuntimeError("set_abstraction_msg_group: %d radii and %d sample counts" % (len(radius_list), len(nsample_list)))
+    new_xyz = index_points(pts, farthest_point_sample(pts, npoint, start))
+    groups = [group_points(pts, new_xyz, points, query_ball_point(radius, nsample, pts, new_xyz), channels_first=True, features_first=True)
+              for radius, nsample in zip(radius_list, nsample_list)]
+    return new_xyz.transpose(1, 2), groups
+
+
 # --------------------------------------------------------------------------------------------
 # PointNet++ feature propagation (reference: point_cloud/pointnet_utils.py:266-300, PointNetFeaturePropagation.forward)
 # --------------------------------------------------------------------------------------------

@@ -244,6 +244,55 @@ def main():
             timeit("three_nn: so3_three_interpolate_bwd_f32 (%s, D=%d, %s)" % (shape, dt, lay),
                    lambda i: lib.so3_three_interpolate_bwd_f32(p(gt), p(i3), p(w3), p(gf), cfl, bt, nt, stn, dt, st), moved, iters=20, warm=3)
         del x1, x2, d3, i3, w3, ft, gt, ot, gf
+    # set-abstraction grouping: the reference model's first level (one of its three radii) and its second level,
+    # both launches in both layouts; then whole Python calls of group_points(channels_first=True) against the torch spelling it replaces
+    for bg, ng, sg, kg, dg, rad in ((32, 1024, 512, 64, 3, 0.2), (32, 512, 128, 128, 320, 0.4)):
+        shape = "%d x %d, %d centres, K=%d, D=%d" % (bg, ng, sg, kg, dg)
+        xg = torch.rand(bg, ng, 3, device=dev) - 0.5
+        s0 = torch.zeros(bg, dtype=torch.int32, device=dev)
+        og = torch.empty(bg, sg, dtype=torch.int32, device=dev)
+        _lib.check(lib.so3_fps_f32(p(xg), p(s0), p(og), bg, ng, sg, st), "so3_fps_f32")
+        cg = torch.gather(xg, 1, og.long()[..., None].expand(-1, -1, 3)).contiguous()
+        ig = torch.empty(bg, sg, kg, dtype=torch.int32, device=dev)
+        _lib.check(lib.so3_ball_query_f32(p(xg), p(cg), ctypes.c_float(rad), kg, p(ig), None, bg, ng, sg, st), "so3_ball_query_f32")
+        fg, cot = torch.randn(bg, ng * dg, device=dev), torch.randn(bg, (3 + dg) * kg * sg, device=dev)
+        outg, gxg, gcg, gfg = torch.empty_like(cot), torch.empty_like(xg), torch.empty_like(cg), torch.empty_like(fg)
+        moved = bg * ((3 + dg) * kg * sg * 4 + sg * kg * 4 + (ng + sg) * 12 + ng * dg * 4)
+        for cfl, lay in ((0, "(B,S,K,C)"), (1, "(B,C,K,S)")):
+            timeit("grouping: so3_group_points_f32 (%s, %s)" % (shape, lay),
+                   lambda i: lib.so3_group_points_f32(p(xg), p(cg), p(fg), p(ig), p(outg), 0, cfl, bg, ng, sg, kg, dg, st), moved, iters=20, warm=3)
+            timeit("grouping: so3_group_points_bwd_f32 (%s, %s, all three)" % (shape, lay),
+                   lambda i: lib.so3_group_points_bwd_f32(p(cot), p(ig), p(gxg), p(gcg), p(gfg), 0, cfl, bg, ng, sg, kg, dg, st), moved, iters=20, warm=3)
+        if not ONLY or ONLY in "grouping: python":
+            import numpy as np
+            leaves = [t.requires_grad_(True) for t in (xg, cg, fg.view(bg, ng, dg), fg.view(bg, ng, dg).transpose(1, 2).contiguous())]
+            il, cot4 = ig.long(), cot.view(bg, 3 + dg, kg, sg)
+
+            def median_ms(fn, warm=3, iters=10 if dg > 64 else 20):
+                times = []
+                for k in range(warm + iters):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(); fn(); e1.record(); e1.synchronize()
+                    times.append(e0.elapsed_time(e1))
+                return float(np.median(times[warm:]))
+
+            def spelled():
+                grouped = rr.index_points(leaves[0], il) - leaves[1][:, :, None, :]
+                return torch.cat([grouped, rr.index_points(leaves[2], il)], dim=-1).permute(0, 3, 2, 1).contiguous()
+
+            def both(fn):
+                for t in leaves: t.grad = None
+                fn().backward(cot4)
+
+            ours = lambda: rr.group_points(leaves[0], leaves[1], leaves[3], il, channels_first=True)
+            with torch.no_grad():
+                of_, tf_ = median_ms(ours), median_ms(spelled)
+            ofb, tfb = median_ms(lambda: both(ours)), median_ms(lambda: both(spelled))
+            print("grouping: python calls (%s): forward %.4f ms, torch spelling %.4f ms (x%.1f); forward + backward %.4f ms, torch %.4f ms (x%.1f)"
+                  % (shape, of_, tf_, tf_ / of_, ofb, tfb, tfb / ofb))
+            del leaves, il, cot4
+        del xg, s0, og, cg, ig, fg, cot, outg, gxg, gcg, gfg
+        torch.cuda.empty_cache()
     rg = rr.get_sampled_rotation_matrices_by_axisAngle(b, dev).reshape(b, 9).contiguous()
     timeit("f4 so3_kabsch_synth_f32 (sigma=0: P only)", lambda i: lib.so3_kabsch_synth_f32(p(pc[i % 2]), p(rg), ctypes.c_float(0.0), 1, p(rk), None, b, npts, st), b * (npts * 12 + 72), iters=10, warm=2)
     timeit("f4 so3_kabsch_synth_f32 (sigma=0.01, device RNG)", lambda i: lib.so3_kabsch_synth_f32(p(pc[i % 2]), p(rg), ctypes.c_float(0.01), 1, p(rk), None, b, npts, st), b * (npts * 12 + 72), iters=10, warm=2)

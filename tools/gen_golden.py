@@ -1015,6 +1015,82 @@ def g24_three_nn(seed=24):
     save("g24_three_nn.npz", **arrays)
 
 
+def g25_grouping(seed=25):
+    """group_points: the reference's own CLASSES on the CPU, torch seeded -- PointNetSetAbstraction (group_all false and true) and
+    PointNetSetAbstractionMsg (two radii) of point_cloud/pointnet_utils.py, constructed with EMPTY MLP lists, so the tensor entering
+    torch.max(., 2) is exactly the permuted grouped tensor (B, C, K, S).  While a forward runs, torch.max and the module's
+    farthest_point_sample and query_ball_point are wrapped to record that tensor T, the FPS indices (their first column is the
+    start), every idx and new_xyz; nothing of the reference is retyped.  Recorded beside them: the reference's own autograd gradients
+    of sum_i (T_i * G_i).sum() with respect to xyz (B, 3, N) and points (B, D, N), G_i = tests/grouping_ref.py: seeded_g(i, T_i.shape)
+    (regenerated by the tests, not stored).  2 x 256 points, 64 centres, D = 5, (r, K) = (0.2, 16) and (0.4, 32) (the single-scale
+    layer takes the second) on pc_normalize'd clouds scaled to radius 1; 2 x 40 points for group_all.  Asserted here: no recorded idx
+    holds N (every centre is a cloud point and hits itself)."""
+    import importlib.util
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import grouping_ref as ref
+    spec = importlib.util.spec_from_file_location("reference_pointnet_utils", os.path.join(REF, "point_cloud", "pointnet_utils.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    (pc_normalize,) = functions_from(os.path.join(REF, "point_cloud", "prepare.py"), ["pc_normalize"])
+    rng = np.random.RandomState(seed)
+    torch.manual_seed(seed)
+
+    def clouds(b, n):
+        raw = rng.randn(b, n, 3) * np.array([1.0, 0.8, 0.6]) + np.array([0.3, -1.0, 2.0])
+        pc = np.stack([pc_normalize(c)[0] for c in raw])
+        return torch.tensor(pc / np.linalg.norm(pc, axis=-1).max(1)[:, None, None]).float()
+
+    def run(layer, xyz, points):
+        """-> (new_xyz (B, 3, S), [T_i], [fps], [idx_i], grad_xyz (B, 3, N), grad_points (B, D, N))"""
+        rec = {"t": [], "fps": [], "idx": []}
+        real_max, real_fps, real_ball = torch.max, mod.farthest_point_sample, mod.query_ball_point
+
+        def max_(x, *a, **k):
+            if x.dim() == 4:                        # the layer's own call; farthest_point_sample's argmax is (B, N)
+                rec["t"].append(x)
+            return real_max(x, *a, **k)
+
+        def fps_(*a, **k):
+            rec["fps"].append(real_fps(*a, **k))
+            return rec["fps"][-1]
+
+        def ball_(*a, **k):
+            rec["idx"].append(real_ball(*a, **k).clone())
+            return rec["idx"][-1].clone()
+
+        x, p = xyz.transpose(1, 2).contiguous().requires_grad_(True), points.transpose(1, 2).contiguous().requires_grad_(True)
+        torch.max, mod.farthest_point_sample, mod.query_ball_point = max_, fps_, ball_
+        try:
+            new_xyz, _ = layer(x, p)
+        finally:
+            torch.max, mod.farthest_point_sample, mod.query_ball_point = real_max, real_fps, real_ball
+        sum((t * torch.tensor(ref.seeded_g(i, tuple(t.shape)))).sum() for i, t in enumerate(rec["t"])).backward()
+        return new_xyz.detach(), [t.detach() for t in rec["t"]], rec["fps"], rec["idx"], x.grad, p.grad
+
+    n, s, d = ref.N_FIXTURE, ref.S_FIXTURE, ref.D_FIXTURE
+    xyz, points = clouds(2, n), torch.randn(2, n, d)
+    arrays = {"xyz": xyz, "points": points}
+    (r0, k0), (r1, k1) = ref.RADII
+    layers = {"sa": mod.PointNetSetAbstraction(s, r1, k1, 3 + d, [], False), "msg": mod.PointNetSetAbstractionMsg(s, [r0, r1], [k0, k1], d, [[], []])}
+    for tag, layer in layers.items():
+        new_xyz, ts, fps, idxs, gx, gp = run(layer, xyz, points)
+        assert len(fps) == 1 and len(ts) == len(idxs) == (1 if tag == "sa" else 2)
+        arrays["fps_" + tag], arrays["new_xyz_" + tag] = fps[0].numpy().astype(np.uint16), new_xyz
+        arrays["grad_xyz_" + tag], arrays["grad_points_" + tag] = gx, gp
+        for i, (t, idx) in enumerate(zip(ts, idxs)):
+            assert t.shape == (2, 3 + d, idx.shape[2], s) and t.dtype == torch.float32
+            assert int(idx.max()) < n and int(idx.min()) >= 0, "a recorded idx holds N"
+            arrays["t_%s_%d" % (tag, i)], arrays["idx_%s_%d" % (tag, i)] = t.contiguous(), idx.numpy().astype(np.uint16)
+            print("g25 %s radius %d: K = %d, %.1f %% of the slots are padding" % (
+                tag, i, idx.shape[2], 100 * float((idx[:, :, 1:] == idx[:, :, :1]).float().mean())))
+    xyz_all, points_all = clouds(2, ref.N_ALL), torch.randn(2, ref.N_ALL, d)
+    new_xyz, ts, fps, idxs, gx, gp = run(mod.PointNetSetAbstraction(None, None, None, 3 + d, [], True), xyz_all, points_all)
+    assert not fps and not idxs and len(ts) == 1 and ts[0].shape == (2, 3 + d, ref.N_ALL, 1)
+    arrays.update(xyz_all=xyz_all, points_all=points_all, new_xyz_all=new_xyz, t_all=ts[0].contiguous(), grad_xyz_all=gx, grad_points_all=gp)
+    save("g25_grouping.npz", **arrays)
+    assert os.path.getsize(os.path.join(OUT, "g25_grouping.npz")) <= 512 * 1024
+
+
 def g23_head_edges():
     """The forward heads at their edges (tests/heads_ref.py: every family, every fourth row -- 32 of 128): the reference's own float32
     outputs and autograd gradients, float64 too where the reference's code keeps float64 (not the 5D head: float32 zeros, :82; not
@@ -1060,6 +1136,8 @@ def g23_head_edges():
 
 
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "g25":
+        return g25_grouping()
     if len(sys.argv) > 1 and sys.argv[1] == "g24":
         return g24_three_nn()
     if len(sys.argv) > 1 and sys.argv[1] == "g23":
