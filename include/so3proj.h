@@ -218,6 +218,41 @@ int so3_sym_frob_loss_f32(const float *Rpred, const float *Rtrue, const float *S
                           int32_t K, float *dRpred, float *dRtrue, int32_t *index, double *loss_sum, float *loss_mean,
                           void *workspace, unsigned flags, int64_t B, void *stream);
 
+/* ---- ADD, ADD-L1 and MSSD up to a symmetry group ---------------------------------------------------------------------
+ * The point-based scores of a full pose (so3_add_l2_f32, so3_add_l1_f32) minimised over a discrete symmetry group: the training
+ * loss min_k ADD(T_gt, T_pred S_k) and, with a maximum over the points, BOP's MSSD (maximum symmetry-aware surface distance).
+ * O(N K) per sample.  S, class_id, num_classes, K: the table of so3_sym_angle_error_f32, same layout and limits; the group acts on
+ * the PREDICTION from the right and only rotations about the model origin are supported (no translation part; MSPD, which needs
+ * camera intrinsics, is out of scope).  Tgt, Tpred, points as so3_add_l1_f32.
+ * The arithmetic is part of the definition (poseestimation_amd/csrc/so3_device.h, sym_add_*):
+ *   A_k = Rpred S_k, one float32 fmaf chain per entry in a fixed order; A_0 = Rpred itself, no product
+ *   D_k = Rgt - A_k,  dt = tgt - tpred,  d_i^k = D_k p_i + dt in so3_add_l1_f32's fmaf order; a distance comes from these coordinate
+ *   differences only, so Tpred S_j == Tgt in float32 makes candidate j exactly 0.
+ *   flags (the mode)        statistic of candidate k                        gradient
+ *   SO3_SYM_ADD_L2          (1/N) sum_i |d_i^k|_2                           u = d / |d|, 0 at d = 0;  c = grad_scale / N
+ *   SO3_SYM_ADD_L1          (1/3N) sum_i (|d_x| + |d_y| + |d_z|)            u = sgn(d), sgn(0) = 0;   c = grad_scale / (3N)
+ *   SO3_SYM_ADD_MAX         max_i |d_i^k|_2 (one sqrt, after the maximum)    none: evaluation only (MSSD)
+ *   dists[b] = min_k stat_k;  index[b] = the smallest k attaining it (strict < in ascending k: a NaN candidate never wins, a NaN
+ *   candidate 0 is never beaten).  The gradient is the selected branch's, w.r.t. Tpred only: with G = sum_i u_i p_i^T and
+ *   g_t = sum_i u_i,  dRpred = -c G S_k*^T  (k* = 0: -c G),  dtpred = -c g_t,  bottom row 0.
+ *   dists      out optional B float32;  index out optional B int32
+ *   loss_sum   out optional double[1] = sum_b dists[b], WRITTEN (not added to), summed in a fixed order without atomics: two calls
+ *                  give the same bits.  With dists it is a second small launch over them; without dists ONE workgroup runs the
+ *                  whole call (correct, and slow for a large batch: pass dists).
+ *   dTpred     out optional B*16 float32 at scale grad_scale; must be NULL with SO3_SYM_ADD_MAX (SO3_ERR_INVALID otherwise)
+ * A class id outside [0, num_classes): dists[b] = NaN, index[b] = -1, loss_sum NaN, and the row's twelve gradient entries NaN (as
+ * so3_sym_frob_loss_f32 leaves its row), the bottom row still 0; other rows are untouched by it.
+ * Limits: 0 <= B <= 2^31, 1 <= N <= 150 000 000 (so3_add_l1_f32's: a cloud's 12 N bytes are addressed in 32 bits), the table's
+ * limits above; B = 0 is a no-op.  A sum runs in sweeps of 1024 points -- per lane in index order, the wave's butterfly, the sweeps'
+ * totals in order -- so a row's bits depend on its data and N only, never on B or the launch shape.
+ */
+#define SO3_SYM_ADD_L2 0u
+#define SO3_SYM_ADD_L1 1u
+#define SO3_SYM_ADD_MAX 2u
+int so3_sym_add_f32(const float *Tgt, const float *Tpred, const float *points, const float *S, const int32_t *class_id,
+                    int32_t num_classes, int32_t K, float *dists, int32_t *index, double *loss_sum, float *dTpred,
+                    float grad_scale, unsigned flags, int64_t B, int32_t N, void *stream);
+
 /* Diagnostic: K1 one row per thread (the same arithmetic, bit for bit, as so3_project_fwd_f32) plus, per row, the device's own
  * verdict: hard[b] = 1 where the quaternion fast path did not certify its result and the row was redone by the Jacobi path.
  * For tests that search for inputs the certificate wrongly accepts (tests/test_gpu_parity.py); not a production entry point. */

@@ -86,8 +86,10 @@ SYMBOLS = {
     "so3_kabsch_synth_f32": (_INT, [_P, _P, ctypes.c_float, ctypes.c_uint32, _P, _P, _I64, _I32, _P]),
     "so3_sym_angle_error_f32": (_INT, [_P, _P, _P, _P, _I32, _I32, _P, _P, _P, _U32, _I64, _P]),
     "so3_sym_frob_loss_f32": (_INT, [_P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _U32, _I64, _P]),
+    "so3_sym_add_f32": (_INT, [_P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, ctypes.c_float, _U32, _I64, _I32, _P]),
 }
 
+SYM_ADD_L2, SYM_ADD_L1, SYM_ADD_MAX = 0, 1, 2      # include/so3proj.h: SO3_SYM_ADD_L2, SO3_SYM_ADD_L1, SO3_SYM_ADD_MAX (so3_sym_add_f32's flags)
 ADD_S_MAX_N = 1 << 20                             # include/so3proj.h: SO3_ADD_S_MAX_N
 FPS_MAX_N = 16384                                 # include/so3proj.h: SO3_FPS_MAX_N
 THREE_MAX_D = 65536                               # include/so3proj.h: SO3_THREE_MAX_D

@@ -1099,6 +1099,69 @@ __device__ __forceinline__ void add_s_pair(float x, float y, float z, float qx, 
 // 1 / |e| for the unit direction u = e / |e|, 0 where e = 0 (d2 = |e|^2 as pair_dist2 gives it)
 __device__ __forceinline__ float unit_scale(float d2) { return d2 > 0.f ? hw::rcp(hw::sqrt(d2)) : 0.f; }
 
+// ---- ADD / ADD-L1 / MSSD up to a symmetry group (so3proj.hip: k_sym_add; tests/host_model/sym_add.cpp) -----------------------------
+// The arithmetic that is part of so3_sym_add_f32's definition.  The group acts on the prediction from the right (K4s / K3s): candidate
+// k poses the cloud with A_k = R_pred S_k (A_0 = R_pred itself, no product), one fmaf chain per entry; a residual is
+// d_i^k = (R_gt - A_k) p_i + (t_gt - t_pred) in k_add_l1's fmaf order, and a distance is formed from those coordinate differences only.
+// So T_pred S_j == T_gt in float32 makes candidate j exactly 0.
+// A cloud is walked in sweeps of kSymAddSweep points; within a sweep a lane sums its points in index order, the wave's butterfly follows,
+// and the sweeps' totals are added in order (the maximum needs no order).
+constexpr int kSymAddL2 = 0, kSymAddL1 = 1, kSymAddMax = 2;       // include/so3proj.h: SO3_SYM_ADD_L2, _L1, _MAX
+constexpr int kSymAddSweep = 1024;
+// D_k = R_gt - A_k; s = S_k, row-major
+__device__ __forceinline__ void sym_add_difference(const float (&rg)[9], const float (&rp)[9], const float (&s)[9], int k, float (&d)[9]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const float a = __builtin_fmaf(rp[3 * i + 2], s[6 + j], __builtin_fmaf(rp[3 * i + 1], s[3 + j], rp[3 * i] * s[j]));
+            d[3 * i + j] = rg[3 * i + j] - (k == 0 ? rp[3 * i + j] : a);
+        }
+}
+__device__ __forceinline__ void sym_add_residual(const float (&d)[9], const float (&dt)[3], float px, float py, float pz, float &dx, float &dy,
+                                                 float &dz) {
+    dx = __builtin_fmaf(d[0], px, __builtin_fmaf(d[1], py, __builtin_fmaf(d[2], pz, dt[0])));
+    dy = __builtin_fmaf(d[3], px, __builtin_fmaf(d[4], py, __builtin_fmaf(d[5], pz, dt[1])));
+    dz = __builtin_fmaf(d[6], px, __builtin_fmaf(d[7], py, __builtin_fmaf(d[8], pz, dt[2])));
+}
+// One point's term of the candidate's statistic: |d|_2, |dx| + |dy| + |dz|, or |d|^2 (the square root of MSSD follows the maximum).
+template <int MODE> __device__ __forceinline__ float sym_add_term(float dx, float dy, float dz) {
+    if (MODE == kSymAddL1) return __builtin_fabsf(dx) + __builtin_fabsf(dy) + __builtin_fabsf(dz);
+    const float d2 = pair_dist2(dx, dy, dz);
+    return MODE == kSymAddMax ? d2 : hw::sqrt(d2);
+}
+// (the maximum keeps a NaN as the sum does: v_max_f32 alone would drop it and a NaN pose would score 0)
+template <int MODE> __device__ __forceinline__ float sym_add_join(float acc, float term) {
+    if (MODE == kSymAddMax) return term <= acc ? acc : (acc != acc ? acc : term);
+    return acc + term;
+}
+// The statistic from its sum (or maximum) over the cloud.
+template <int MODE> __device__ __forceinline__ float sym_add_finish(float acc, int32_t n) {
+    if (MODE == kSymAddMax) return hw::sqrt(acc);
+    return acc * (MODE == kSymAddL1 ? 1.0f / (3.0f * static_cast<float>(n)) : 1.0f / static_cast<float>(n));
+}
+// u = d / |d| (0 at d = 0) for ADD, sgn(d) per coordinate (sgn(0) = 0) for ADD-L1
+template <int MODE> __device__ __forceinline__ void sym_add_direction(float dx, float dy, float dz, float &ux, float &uy, float &uz) {
+    if (MODE == kSymAddL1) {
+        ux = dx > 0.f ? 1.f : (dx < 0.f ? -1.f : 0.f);
+        uy = dy > 0.f ? 1.f : (dy < 0.f ? -1.f : 0.f);
+        uz = dz > 0.f ? 1.f : (dz < 0.f ? -1.f : 0.f);
+    } else {
+        const float inv = unit_scale(pair_dist2(dx, dy, dz));
+        ux = dx * inv; uy = dy * inv; uz = dz * inv;
+    }
+}
+// G S_k^T: the chain rule through A_k = R_pred S_k (k = 0: G itself)
+__device__ __forceinline__ void sym_add_rotate_back(const float (&g)[9], const float (&s)[9], int k, float (&out)[9]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const float h = __builtin_fmaf(g[3 * i + 2], s[3 * j + 2], __builtin_fmaf(g[3 * i + 1], s[3 * j + 1], g[3 * i] * s[3 * j]));
+            out[3 * i + j] = k == 0 ? g[3 * i + j] : h;
+        }
+}
+
 // ---- rigid_align: weighted, centred Kabsch (so3proj.hip: k_rigid_align, k_rigid_align_bwd; tests/host_model/rigid_align.cpp) --------
 // THE PIVOT RULE.  A cloud's sums are taken of coordinates relative to a per-cloud pivot, its FIRST point pair (p_0, q_0), whatever
 // that point's weight:  a_i = p_i - p_0,  c_i = q_i - q_0.  The one-pass centred covariance then cancels as (cloud extent / cloud

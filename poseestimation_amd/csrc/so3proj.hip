@@ -1587,6 +1587,136 @@ __global__ __launch_bounds__(kBlock) void k_sum_f32_to_f64(const float *__restri
     if (threadIdx.x == 0) total[0] = t;
 }
 
+// ---- ADD / ADD-L1 / MSSD up to a symmetry group (so3_sym_add_f32) -----------------------------------------------------------------
+// dist_b = min_k stat(T_gt, T_pred S_k), the smallest minimising k, and (GRAD) the selected branch's gradient w.r.t. T_pred, in one
+// launch.  k_add_l1's skeleton: one wave per sample at a time, 12-byte buffer loads, poses and table entries wave-uniform.  A sweep of
+// 64 * kU points is loaded into registers once and every candidate is walked over it in a wave-uniform loop: D_k = R_gt - R_pred S_k
+// from scalar loads, the lanes' partial statistic, one butterfly per candidate; LANE k keeps candidate k's statistic across the sweeps
+// (K <= 64), so no per-lane array is indexed by k.  The minimum and its first index are one more butterfly and a ballot.  The gradient
+// phase recomputes D_k* and runs k_add_l1's twelve sums over the points -- still in registers when the cloud is one sweep, read again
+// (L2) when it is longer.  kU < 16 is only launched for clouds that fit 64 * kU points: a sweep is kSymAddSweep points for every N,
+// so the order of a row's sum depends on N alone.
+// `total` (one workgroup only): sum_b dist_b in float64, in the order the four waves met the rows.
+template <int MODE> __device__ __forceinline__ float sym_add_wave_join(float v) {      // wave_allsum's partners
+    v = so3::sym_add_join<MODE>(v, dpp_xor1(v));
+    v = so3::sym_add_join<MODE>(v, dpp_xor2(v));
+    v = so3::sym_add_join<MODE>(v, dpp_half_mirror(v));
+    v = so3::sym_add_join<MODE>(v, dpp_mirror(v));
+    v = so3::sym_add_join<MODE>(v, __shfl_xor(v, 16, 64));
+    v = so3::sym_add_join<MODE>(v, __shfl_xor(v, 32, 64));
+    return v;
+}
+template <int MODE, bool GRAD, int kU>
+__global__ __launch_bounds__(kBlock) void k_sym_add(const float *__restrict__ Tgt, const float *__restrict__ Tpred, const float *__restrict__ pts,
+                                                    const float *__restrict__ S, const int32_t *__restrict__ class_id, int32_t C, int32_t K,
+                                                    float *__restrict__ dists, int32_t *__restrict__ index, double *__restrict__ total,
+                                                    float *__restrict__ dT, float grad_scale, int64_t B, int32_t N) {
+    static_assert(64 * kU <= so3::kSymAddSweep && !(GRAD && MODE == so3::kSymAddMax), "");
+    __shared__ double red[4];
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = static_cast<int64_t>(blockIdx.x) * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t nwaves = static_cast<int64_t>(gridDim.x) * (kBlock / 64);
+    const unsigned cloud_bytes = static_cast<unsigned>(N) * 12u;
+    const float nan = __int_as_float(0x7fc00000);
+    double mine = 0.0;
+    for (int64_t b = wave; b < B; b += nwaves) {
+        const float *tg = Tgt + b * 16, *tp = Tpred + b * 16;                   // wave-uniform: scalar loads
+        float rg[9], rp[9], dt[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) { rg[3 * c + j] = tg[4 * c + j]; rp[3 * c + j] = tp[4 * c + j]; }
+            dt[c] = tg[4 * c + 3] - tp[4 * c + 3];
+        }
+        const int cls = class_id != nullptr ? class_id[b] : 0;
+        const bool bad = static_cast<unsigned>(cls) >= static_cast<unsigned>(C);
+        const float *tab = S + static_cast<int64_t>(bad ? 0 : cls) * K * 9;
+        const so3::rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(pts) + b * N * 3, 0, cloud_bytes, so3::kRsrcFlags);
+        u32x3 pp[kU];
+        float stat = 0.f;                                                        // lane k: candidate k
+        for (int i0 = 0; i0 < N; i0 += 64 * kU) {
+#pragma unroll
+            for (int u = 0; u < kU; ++u) pp[u] = __builtin_amdgcn_raw_buffer_load_b96(rsrc, (i0 + 64 * u + lane) * 12, 0, 0);
+            for (int k = 0; k < K; ++k) {
+                float s[9], d[9];
+#pragma unroll
+                for (int i = 0; i < 9; ++i) s[i] = tab[k * 9 + i];
+                so3::sym_add_difference(rg, rp, s, k, d);
+                float part = 0.f;
+#pragma unroll
+                for (int u = 0; u < kU; ++u) {
+                    float dx, dy, dz;
+                    so3::sym_add_residual(d, dt, __uint_as_float(pp[u].x), __uint_as_float(pp[u].y), __uint_as_float(pp[u].z), dx, dy, dz);
+                    const float term = so3::sym_add_term<MODE>(dx, dy, dz);
+                    part = so3::sym_add_join<MODE>(part, i0 + 64 * u + lane < N ? term : 0.f);      // a zero-filled slot adds exactly 0
+                }
+                const float tot = sym_add_wave_join<MODE>(part);
+                stat = lane == k ? so3::sym_add_join<MODE>(stat, tot) : stat;
+            }
+        }
+        // min_k by strict < in ascending k: a NaN candidate never wins, a NaN candidate 0 is never beaten
+        const float val = lane < K ? so3::sym_add_finish<MODE>(stat, N) : __builtin_huge_valf();
+        const float v0 = __builtin_amdgcn_readfirstlane(val);
+        float best = -wave_allmax(-val);
+        int kb = __builtin_ctzll(__builtin_amdgcn_ballot_w64(val == best) | (1ull << 63));
+        if (v0 != v0) { best = v0; kb = 0; }
+        if (bad) { best = nan; }
+        if (lane == 0) {
+            if (dists != nullptr) dists[b] = best;
+            if (index != nullptr) index[b] = bad ? -1 : kb;
+        }
+        mine += static_cast<double>(best);
+        if (GRAD) {
+            float s[9], d[9];
+#pragma unroll
+            for (int i = 0; i < 9; ++i) s[i] = tab[kb * 9 + i];
+            so3::sym_add_difference(rg, rp, s, kb, d);
+            float acc[12];
+#pragma unroll
+            for (int i = 0; i < 12; ++i) acc[i] = 0.f;
+            for (int i0 = 0; i0 < N; i0 += 64 * kU) {
+                if (N > 64 * kU) {                                               // more than one sweep: the registers hold the last one
+#pragma unroll
+                    for (int u = 0; u < kU; ++u) pp[u] = __builtin_amdgcn_raw_buffer_load_b96(rsrc, (i0 + 64 * u + lane) * 12, 0, 0);
+                }
+#pragma unroll
+                for (int u = 0; u < kU; ++u) {
+                    const float px = __uint_as_float(pp[u].x), py = __uint_as_float(pp[u].y), pz = __uint_as_float(pp[u].z);
+                    const bool in = i0 + 64 * u + lane < N;
+                    float dx, dy, dz, ux, uy, uz;
+                    so3::sym_add_residual(d, dt, px, py, pz, dx, dy, dz);
+                    so3::sym_add_direction<MODE>(dx, dy, dz, ux, uy, uz);
+                    ux = in ? ux : 0.f; uy = in ? uy : 0.f; uz = in ? uz : 0.f;
+                    acc[0] = fmaf(ux, px, acc[0]); acc[1] = fmaf(ux, py, acc[1]); acc[2] = fmaf(ux, pz, acc[2]);
+                    acc[3] = fmaf(uy, px, acc[3]); acc[4] = fmaf(uy, py, acc[4]); acc[5] = fmaf(uy, pz, acc[5]);
+                    acc[6] = fmaf(uz, px, acc[6]); acc[7] = fmaf(uz, py, acc[7]); acc[8] = fmaf(uz, pz, acc[8]);
+                    acc[9] += ux; acc[10] += uy; acc[11] += uz;
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 12; ++i) acc[i] = wave_allsum(acc[i]);
+            float g[9], gs[9];
+#pragma unroll
+            for (int i = 0; i < 9; ++i) g[i] = acc[i];
+            so3::sym_add_rotate_back(g, s, kb, gs);
+            if (lane == 0) {
+                const float c = bad ? nan : -grad_scale * (MODE == so3::kSymAddL1 ? 1.0f / (3.0f * static_cast<float>(N)) : 1.0f / static_cast<float>(N));
+                float *o = dT + b * 16;
+#pragma unroll
+                for (int r = 0; r < 3; ++r) {
+                    o[4 * r + 0] = c * gs[3 * r + 0]; o[4 * r + 1] = c * gs[3 * r + 1]; o[4 * r + 2] = c * gs[3 * r + 2];
+                    o[4 * r + 3] = c * acc[9 + r];
+                }
+                o[12] = 0.f; o[13] = 0.f; o[14] = 0.f; o[15] = 0.f;
+            }
+        }
+    }
+    if (total != nullptr) {                    // gridDim.x == 1
+        const double t = block_sum(lane == 0 ? mine : 0.0, red);
+        if (threadIdx.x == 0) total[0] = t;
+    }
+}
+
 // ADD-S backward through the stored indices: with e_i = x_i - y_nn(i), u_i = e_i / |e_i| (0 where e_i = 0),
 // dL/dR_pred = -k sum_i u_i p_nn(i)^T,  dL/dt_pred = -k sum_i u_i,  k = grad_scale * grad_rows[b] / N.  One pass over (B,N), one wave per
 // sample at a time (the k_add_l1 skeleton); an index outside [0, N) is clamped, so a bad index buffer cannot read out of bounds.
@@ -3712,6 +3842,27 @@ int launch_add_s(const float *Tgt, const float *Tpred, const float *points, floa
     return check_launch(what);
 }
 
+// k_sym_add over B clouds: a wave per sample at a time, at most eight workgroups per compute unit.  With `rows` the batch total is a
+// second, one-workgroup launch over them; without, one workgroup does the whole call and sums as it goes (k_add_s_rows's rule).
+// The instantiation's name goes to so3_last_kernel.
+thread_local char g_sym_add_kernel[48] = "";
+template <int MODE, bool GRAD>
+void launch_sym_add(const float *Tgt, const float *Tpred, const float *points, const float *S, const int32_t *class_id, int32_t C, int32_t K,
+                    float *rows, int32_t *index, double *total, float *dT, float grad_scale, int64_t B, int32_t N, hipStream_t s) {
+    const bool one_group = rows == nullptr && total != nullptr;
+    const int64_t blocks = one_group ? 1 : std::min<int64_t>((B + kBlock / 64 - 1) / (kBlock / 64), static_cast<int64_t>(device_cus()) * 8);
+    const dim3 grid(static_cast<unsigned>(blocks)), block(kBlock);
+    double *in_kernel = one_group ? total : nullptr;
+    const int u = N > 512 ? 16 : (N > 128 ? 8 : 2);
+    snprintf(g_sym_add_kernel, sizeof g_sym_add_kernel, "k_sym_add<%d, %s, %d>", MODE, GRAD ? "true" : "false", u);
+    g_last_kernel = g_sym_add_kernel;
+#define SYM_ADD(UU) hipLaunchKernelGGL((k_sym_add<MODE, GRAD, UU>), grid, block, 0, s, Tgt, Tpred, points, S, class_id, C, K, rows, index, \
+                                       in_kernel, dT, grad_scale, B, N)
+    if (u == 16) SYM_ADD(16); else if (u == 8) SYM_ADD(8); else SYM_ADD(2);
+#undef SYM_ADD
+    if (rows != nullptr && total != nullptr) hipLaunchKernelGGL(k_sum_f32_to_f64, dim3(1), block, 0, s, rows, total, B);
+}
+
 // k_icp_step over B clouds at k_add_s's launch shape.  The instantiation's name goes to so3_last_kernel.
 thread_local char g_icp_kernel[64] = "";
 int32_t icp_chunks(int64_t B, int32_t N, int &u) {
@@ -4883,6 +5034,27 @@ int so3_sym_frob_loss_f32(const float *Rpred, const float *Rtrue, const float *S
 #undef SYM_OP
     if (err != 0) return fail(err, "so3_sym_frob_loss_f32: memset");
     return check_launch("so3_sym_frob_loss_f32");
+}
+
+int so3_sym_add_f32(const float *Tgt, const float *Tpred, const float *points, const float *S, const int32_t *class_id, int32_t num_classes,
+                    int32_t K, float *dists, int32_t *index, double *loss_sum, float *dTpred, float grad_scale, unsigned flags, int64_t B,
+                    int32_t N, void *stream) {
+    SO3_CHECK_ARGS(flags <= static_cast<unsigned>(SO3_SYM_ADD_MAX), "so3_sym_add_f32: unknown flag (the mode: SO3_SYM_ADD_L2, _L1 or _MAX)");
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= 150000000, "so3_sym_add_f32: B/N");
+    SO3_SYM_CHECK("so3_sym_add_f32");
+    SO3_CHECK_ARGS(flags != static_cast<unsigned>(SO3_SYM_ADD_MAX) || dTpred == nullptr, "so3_sym_add_f32: dTpred must be null with SO3_SYM_ADD_MAX (no gradient)");
+    if (B == 0) return 0;
+    SO3_CHECK_ARGS(Tgt != nullptr && Tpred != nullptr && points != nullptr, "so3_sym_add_f32: null pointer");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+#define SYM_ADD_MODE(M) do { if (dTpred != nullptr) launch_sym_add<M, true>(Tgt, Tpred, points, S, class_id, num_classes, K, dists, index, loss_sum, \
+                                                                              dTpred, grad_scale, B, N, s); \
+                             else launch_sym_add<M, false>(Tgt, Tpred, points, S, class_id, num_classes, K, dists, index, loss_sum, nullptr, \
+                                                           grad_scale, B, N, s); } while (0)
+    if (flags == static_cast<unsigned>(SO3_SYM_ADD_L1)) SYM_ADD_MODE(so3::kSymAddL1);
+    else if (flags == static_cast<unsigned>(SO3_SYM_ADD_L2)) SYM_ADD_MODE(so3::kSymAddL2);
+    else launch_sym_add<so3::kSymAddMax, false>(Tgt, Tpred, points, S, class_id, num_classes, K, dists, index, loss_sum, nullptr, grad_scale, B, N, s);
+#undef SYM_ADD_MODE
+    return check_launch("so3_sym_add_f32");
 }
 #undef SO3_SYM_CHECK
 

@@ -2135,6 +2135,103 @@ def cloud_diameter(points: torch.Tensor) -> torch.Tensor:
 
 
 # --------------------------------------------------------------------------------------------
+# ADD, ADD-L1 and MSSD up to a symmetry group (so3_sym_add_f32)
+# --------------------------------------------------------------------------------------------
+def _sym_add_call(what, mode, t_gt, t_pred, points, table, class_ids, want_rows, want_sum, want_index, want_grad, scale):
+    """One so3_sym_add_f32 launch: (rows, loss_sum, index, dT), each None unless asked for (rows are always taken: they are the
+    work buffer of the batch sum)."""
+    if not isinstance(table, SymmetryTable):
+        raise TypeError(f"{what}: table must be a SymmetryTable, got {type(table).__name__}")
+    dev, b, n, tg, tp, pts = _add_l1_args(t_gt, t_pred, points)
+    cls = None
+    if table.num_classes > 1:
+        if class_ids is None:
+            raise ValueError(f"{what}: a table of {table.num_classes} classes needs class_ids")
+        _require_device(t_pred, class_ids)
+        if class_ids.dtype not in (torch.int32, torch.int64) or class_ids.dim() != 1 or class_ids.shape[0] != b:
+            raise ValueError(f"{what}: class_ids must be int32 or int64 of shape ({b},), got {class_ids.dtype} {tuple(class_ids.shape)}")
+        if class_ids.dtype is torch.int64:            # out-of-range ids stay out of range in int32
+            class_ids = class_ids.clamp(-1, table.num_classes).int()
+        cls = class_ids.contiguous()
+    elif class_ids is not None:
+        raise ValueError(f"{what}: class_ids given for a single-class table")
+    s = table._on(dev)
+    rows = torch.empty((b,), dtype=torch.float32, device=dev) if (want_rows or want_sum) else None
+    loss_sum = torch.empty((1,), dtype=torch.float64, device=dev) if want_sum else None
+    idx = torch.empty((b,), dtype=torch.int32, device=dev) if want_index else None
+    dt = torch.empty((b, 4, 4), dtype=torch.float32, device=dev) if want_grad else None
+    with _on_device(dev):
+        _check(_libh().so3_sym_add_f32(_ptr(tg), _ptr(tp), _ptr(pts), _ptr(s), _ptr(cls), table.num_classes, table.K, _ptr(rows), _ptr(idx),
+                                       _ptr(loss_sum), _ptr(dt), scale, mode, b, n, _stream(dev)), "so3_sym_add_f32")
+    if b == 0 and loss_sum is not None:               # the mean of no rows, as torch's .mean() gives it
+        loss_sum.fill_(float("nan"))
+    return rows, loss_sum, idx, dt
+
+
+class _SymAdd(torch.autograd.Function):
+    """compute_symmetric_ADD_loss / compute_symmetric_ADD_L1_loss: one launch writes the loss and, at unit upstream scale, the selected
+    branch's gradient w.r.t. the predicted pose; backward scales it."""
+
+    @staticmethod
+    def forward(ctx, t_gt, t_pred, points, table, class_ids, use_batch_mean, return_index, mode, what):
+        b = len(t_gt)
+        want_grad = t_pred.requires_grad
+        rows, loss_sum, idx, dt = _sym_add_call(what, mode, t_gt, t_pred, points, table, class_ids, not use_batch_mean, use_batch_mean,
+                                                return_index, want_grad, 1.0 / max(b, 1) if use_batch_mean else 1.0)
+        ctx.dt, ctx.per_sample, ctx.in_dtype = dt, not use_batch_mean, t_pred.dtype
+        out = loss_sum.to(torch.float32).mul_(1.0 / max(b, 1)).squeeze(0) if use_batch_mean else rows
+        if return_index:
+            ctx.mark_non_differentiable(idx)
+            return out, idx
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out, *_):
+        _no_double_backward(grad_out)
+        if ctx.dt is None:
+            return (None,) * 9
+        g = grad_out.reshape(-1, 1, 1) if ctx.per_sample else grad_out
+        return (None, (ctx.dt * g).to(ctx.in_dtype)) + (None,) * 7
+
+
+def compute_symmetric_ADD_loss(TCO_gt: torch.Tensor, TCO_pred: torch.Tensor, points: torch.Tensor, table: SymmetryTable,
+                               class_ids: torch.Tensor = None, use_batch_mean: bool = True, return_index: bool = False):
+    """ADD up to a discrete symmetry group: min_k ADD(T_gt, T_pred S_k), S_k the table's rotations of the row's class acting on the
+    prediction from the right (about the model origin; symmetries with a translation part are not supported) -- the training loss for
+    an object with discrete symmetries, O(N K) per sample.  use_batch_mean=False gives (B,); points: (B,N,3) or a shared (N,3).
+    table / class_ids as in symmetric_angle_error; an id out of range makes the row (and the batch mean) NaN.
+    return_index=True also returns k* (int32 (B,)), the smallest minimising k, -1 for a bad class id.
+    Differentiable w.r.t. TCO_pred only: the selected branch's gradient, written by the forward launch.  No host sync: capturable in a
+    graph once the table is on the device (`table.to(device)`).  A table {I} gives compute_ADD_loss (to rounding)."""
+    points = _add_metric_points("compute_symmetric_ADD_loss", TCO_gt, points)
+    return _SymAdd.apply(TCO_gt, TCO_pred, points, table, class_ids, bool(use_batch_mean), bool(return_index), _lib.SYM_ADD_L2,
+                         "compute_symmetric_ADD_loss")
+
+
+def compute_symmetric_ADD_L1_loss(TCO_gt: torch.Tensor, TCO_pred: torch.Tensor, points: torch.Tensor, table: SymmetryTable,
+                                  class_ids: torch.Tensor = None, use_batch_mean: bool = True, return_index: bool = False):
+    """compute_ADD_L1_loss (Iterative/loss.py:10-26) up to a discrete symmetry group: min_k of the mean over points and coordinates of
+    |T_gt p - T_pred S_k p|.  Arguments, gradient and capture as compute_symmetric_ADD_loss."""
+    points = _add_metric_points("compute_symmetric_ADD_L1_loss", TCO_gt, points)
+    return _SymAdd.apply(TCO_gt, TCO_pred, points, table, class_ids, bool(use_batch_mean), bool(return_index), _lib.SYM_ADD_L1,
+                         "compute_symmetric_ADD_L1_loss")
+
+
+def compute_MSSD(TCO_gt: torch.Tensor, TCO_pred: torch.Tensor, points: torch.Tensor, table: SymmetryTable, class_ids: torch.Tensor = None,
+                 return_index: bool = False):
+    """BOP's maximum symmetry-aware surface distance: min_k max_i |T_gt p_i - T_pred S_k p_i|_2, (B,) float32.  Arguments as
+    compute_symmetric_ADD_loss.  An evaluation metric: no gradient."""
+    if _wants_grad(TCO_gt, TCO_pred, points):
+        _warn_once("compute_MSSD", "compute_MSSD is an evaluation call: its result carries no gradient although an argument requires grad.  "
+                                   "compute_symmetric_ADD_loss is the differentiable symmetric spelling.")
+    if isinstance(points, torch.Tensor) and points.dim() == 2:
+        points = points.unsqueeze(0).expand(len(TCO_gt), -1, -1)
+    rows, _, idx, _ = _sym_add_call("compute_MSSD", _lib.SYM_ADD_MAX, TCO_gt, TCO_pred, points, table, class_ids, True, False,
+                                    bool(return_index), False, 1.0)
+    return (rows, idx) if return_index else rows
+
+
+# --------------------------------------------------------------------------------------------
 # next row f3: per-class evaluation statistics
 # --------------------------------------------------------------------------------------------
 STAT_FIELDS = ("count", "mean", "std", "max", "median", "acc30", "acc15", "acc7.5")

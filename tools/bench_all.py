@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times every C-ABI entry point at the BASELINE.json configs (secondary kernels; bench.py is the headline).
 Each call is launched back-to-back on rotating buffers; reported per call with the algorithmic bytes it moves."""
-import ctypes, os, sys
+import ctypes, math, os, sys
 import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from poseestimation_amd import _lib
@@ -326,7 +326,23 @@ def main():
     timeit("ADD-S so3_add_s_fwd_f32 (rows + nearest + loss_sum)", lambda i: lib.so3_add_s_fwd_f32(p(tg), p(tq), p(pa_), p(pd), p(nn), p(ds), p(l1), b, npts, st), b * (npts * 24 + 132))
     timeit("ADD-S so3_add_s_bwd_f32", lambda i: lib.so3_add_s_bwd_f32(p(tg), p(tq), p(pa_), p(nn), p(ds), ctypes.c_float(1.0), p(dtq), b, npts, st), b * (npts * 28 + 192))
     timeit("diameter so3_cloud_diameter_f32", lambda i: lib.so3_cloud_diameter_f32(p(pa_), p(pd), p(ds), b, npts, st), b * (npts * 20 + 4))
-    del pa_, tg, tq, pd, nn, ds, dtq
+    # ADD up to a symmetry group at the same shape: K = 1 against so3_add_l2_f32 is what the min_k wrapper costs over the plain pass
+    kk = 8
+    th = 2.0 * math.pi * torch.arange(kk, dtype=torch.float64) / kk
+    s8 = torch.zeros(kk, 3, 3, dtype=torch.float64); s8[:, 0, 0] = th.cos(); s8[:, 0, 1] = -th.sin(); s8[:, 1, 0] = th.sin(); s8[:, 1, 1] = th.cos(); s8[:, 2, 2] = 1.0
+    s8 = s8.reshape(kk, 9).float().to(dev).contiguous()
+    ix = torch.empty(b, dtype=torch.int32, device=dev)
+    one = ctypes.c_float(1.0)
+    sym = lambda K, rows, idx, tot, dT, mode: lib.so3_sym_add_f32(p(tg), p(tq), p(pa_), p(s8), None, 1, K, rows, idx, tot, dT, one, mode, b, npts, st)
+    timeit("ADD so3_add_l2_f32 (B=256, rows)", lambda i: lib.so3_add_l2_f32(p(tg), p(tq), p(pa_), p(ds), None, None, one, b, npts, st), b * (npts * 12 + 132))
+    timeit("ADD so3_add_l2_f32 (B=256, rows + dTpred)", lambda i: lib.so3_add_l2_f32(p(tg), p(tq), p(pa_), p(ds), None, p(dtq), one, b, npts, st), b * (npts * 12 + 196))
+    timeit("symADD so3_sym_add_f32 (L2, K=1, rows)", lambda i: sym(1, p(ds), None, None, None, _lib.SYM_ADD_L2), b * (npts * 12 + 132))
+    timeit("symADD so3_sym_add_f32 (L2, K=1, rows + dTpred)", lambda i: sym(1, p(ds), None, None, p(dtq), _lib.SYM_ADD_L2), b * (npts * 12 + 196))
+    timeit("symADD so3_sym_add_f32 (L2, K=8, rows)", lambda i: sym(kk, p(ds), None, None, None, _lib.SYM_ADD_L2), b * (npts * 12 + 132))
+    timeit("symADD so3_sym_add_f32 (L2, K=8, rows + index + loss_sum + dTpred)", lambda i: sym(kk, p(ds), p(ix), p(l1), p(dtq), _lib.SYM_ADD_L2), b * (npts * 12 + 200))
+    timeit("symADD so3_sym_add_f32 (L1, K=8, rows + dTpred)", lambda i: sym(kk, p(ds), None, None, p(dtq), _lib.SYM_ADD_L1), b * (npts * 12 + 196))
+    timeit("symADD so3_sym_add_f32 (MSSD, K=8, rows)", lambda i: sym(kk, p(ds), None, None, None, _lib.SYM_ADD_MAX), b * (npts * 12 + 132))
+    del pa_, tg, tq, pd, nn, ds, dtq, s8, ix
     print("--- config #4: B = 512, bf16 storage, fused head + loss + backward ---")
     b = 512
     x4 = torch.randn(b, 9, device=dev).bfloat16(); r4 = torch.empty(b, 9, device=dev); d4 = torch.empty(b, 9, device=dev, dtype=torch.bfloat16)

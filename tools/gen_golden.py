@@ -603,6 +603,101 @@ def g19_add_metrics():
          case_b=np.array(bs, np.int32), **{k: np.concatenate(v) for k, v in out.items()})
 
 
+def g26_sym_add():
+    """so3_sym_add_f32: ADD, ADD-L1 and MSSD up to a symmetry group.  float32 poses, clouds and tables; float64 answers from
+    tests/sym_add_ref.py for the three modes and EVERY candidate k, and the float64 winner's gradient for the two losses (no reference
+    code exists for these metrics, as for G19: the definitions are the literature's, restated from include/so3proj.h).  Clouds of unit
+    radius, poses about two units from the origin, fixed seeds.  Families: haar (unrelated poses), near_symmetric (T_pred within 1e-2 of
+    T_gt S_j^-1: the winner is j), exact_c4 (T_pred = T_gt S_j^-1 exactly, quarter turns about z), identical_points (a cloud of one
+    repeated point at T_pred = T_gt: d = 0 everywhere)."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import sym_add_ref as ref
+    rng = np.random.default_rng(26)
+    eye = np.eye(3)
+
+    def haar(b):
+        q, r = np.linalg.qr(rng.standard_normal((b, 3, 3)))
+        q = q * np.sign(np.einsum("bii->bi", r))[:, None, :]
+        q[:, :, 0] *= np.linalg.det(q)[:, None]
+        return q
+
+    def cyclic(n, axis):                                  # C_n about a coordinate axis; quarter and half turns exact
+        th = 2.0 * np.pi * np.arange(n) / n
+        c, s_ = np.cos(th), np.sin(th)
+        c[np.abs(c) < 1e-15] = 0.0
+        s_[np.abs(s_) < 1e-15] = 0.0
+        a = np.zeros(3)
+        a["xyz".index(axis)] = 1.0
+        k = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+        return c[:, None, None] * eye + (1.0 - c)[:, None, None] * np.outer(a, a) + s_[:, None, None] * k
+
+    def table(groups):                                    # SymmetryTable's layout: identity first, padded with the identity
+        k = max(len(g) for g in groups)
+        t = np.broadcast_to(eye, (len(groups), k, 3, 3)).copy()
+        for c, g in enumerate(groups):
+            t[c, :len(g)] = g
+        return t.astype(np.float32)
+
+    def poses(rot, t):
+        T = np.tile(np.eye(4), (len(rot), 1, 1))
+        T[:, :3, :3], T[:, :3, 3] = rot, t
+        return T.astype(np.float32)
+
+    def cloud(b, n):
+        p = rng.standard_normal((b, n, 3))
+        if n > 1:
+            p = p - p.mean(1, keepdims=True)
+        return (p / np.linalg.norm(p, axis=-1).max(1)[:, None, None]).astype(np.float32)
+
+    def small_rotation(b, err):
+        v = rng.standard_normal((b, 3))
+        v *= err / np.linalg.norm(v, axis=1, keepdims=True)
+        th = np.linalg.norm(v, axis=1)[:, None, None]
+        k = np.zeros((b, 3, 3))
+        k[:, 0, 1], k[:, 0, 2], k[:, 1, 0], k[:, 1, 2], k[:, 2, 0], k[:, 2, 1] = -v[:, 2], v[:, 1], v[:, 2], -v[:, 0], -v[:, 1], v[:, 0]
+        k = k / th
+        return eye + np.sin(th) * k + (1.0 - np.cos(th)) * (k @ k)
+
+    tr = lambda b: rng.standard_normal((b, 3)) * 0.3 + np.array([0.0, 0.0, 2.0])
+    one = {"c2z": table([cyclic(2, "z")]), "c4y": table([cyclic(4, "y")]), "c7x": table([cyclic(7, "x")]), "i": table([eye[None]])}
+    multi = table([eye[None], cyclic(2, "z"), cyclic(4, "y"), cyclic(6, "x")])
+    plan = []                                             # (family, tgt, tpred, pts, S, cls)
+    for n, tag in ((1, "c2z"), (3, "c4y"), (64, "c7x"), (100, "i"), (1000, "c4y"), (1500, "c2z")):
+        t = tr(2)
+        plan.append(("haar", poses(haar(2), t), poses(haar(2), t + 0.05 * rng.standard_normal((2, 3))), cloud(2, n), one[tag], None))
+    for n in (65, 300):
+        b = 8
+        cls = rng.integers(0, 4, b).astype(np.int32)
+        t = tr(b)
+        plan.append(("haar", poses(haar(b), t), poses(haar(b), t + 0.05 * rng.standard_normal((b, 3))), cloud(b, n), multi, cls))
+    for n, S, cls in ((64, one["c4y"], None), (256, one["c7x"], None), (1100, one["c2z"], None), (100, multi, np.array([0, 1, 2, 3, 3, 2], np.int32))):
+        b = S.shape[1] if cls is None else len(cls)
+        rows = ref.rows_of(S, cls, b)
+        j = np.arange(b) % S.shape[1]
+        rg, t = haar(b), tr(b)
+        rp = small_rotation(b, 1e-2) @ rg @ np.transpose(rows[np.arange(b), j], (0, 2, 1))
+        plan.append(("near_symmetric", poses(rg, t), poses(rp, t + 1e-3 * rng.standard_normal((b, 3))), cloud(b, n), S, cls))
+    c4z = table([cyclic(4, "z")])
+    for n in (1, 100, 1030):
+        tg = poses(haar(4), tr(4))
+        tp = tg.copy()
+        tp[:, :3, :3] = np.einsum("bil,bjl->bij", tg[:, :3, :3], c4z[0])          # T_gt S_j^-1: signed column permutations, exact in float32
+        plan.append(("exact_c4", tg, tp, cloud(4, n), c4z, None))
+    for n in (5, 200):
+        tg = poses(haar(1), tr(1))
+        plan.append(("identical_points", tg, tg.copy(), np.repeat(cloud(1, 1), n, axis=1), one["c4y"], None))
+
+    out, fam = {}, []
+    for i, (family, tg, tp, pts, S, cls) in enumerate(plan):
+        assert pts.dtype == np.float32 and S.dtype == np.float32 and np.linalg.norm(pts, axis=-1).max() <= 1 + 1e-6
+        ans = ref.answers(tg, tp, pts, S, cls)
+        ans.update(tgt=tg, tpred=tp, pts=pts, S=S, cls=np.zeros(0, np.int32) if cls is None else cls)
+        out.update({"%d_%s" % (i, k): ans[k] for k in ref.PER_CASE})
+        fam.append(ref.FAMILIES.index(family))
+        print("g26 %-16s B=%d N=%4d C=%d K=%d  ADD %s" % (family, len(tg), pts.shape[1], S.shape[0], S.shape[1], np.round(ans["stat_l2"][0], 4)))
+    save("g26_sym_add.npz", family_names=np.array(ref.FAMILIES), case_family=np.array(fam, np.int32), **out)
+
+
 def g20_rigid_align():
     """rigid_align: float32 clouds, weights and upstream gradients, float64 answers (R, t, H, centroids) from tests/rigid_align_ref.py
     (the reference has no registration layer: the definition is the weighted Kabsch / Umeyama solution without scale).  Clouds of
@@ -1136,6 +1231,8 @@ def g23_head_edges():
 
 
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "g26":
+        return g26_sym_add()
     if len(sys.argv) > 1 and sys.argv[1] == "g25":
         return g25_grouping()
     if len(sys.argv) > 1 and sys.argv[1] == "g24":
@@ -1182,6 +1279,7 @@ def main():
     g12_clouds()
     g13_dtype_fidelity()
     g19_add_metrics()
+    g26_sym_add()
     g20_rigid_align()
     g21_icp()
     g22_pointnet()
