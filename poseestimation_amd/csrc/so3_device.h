@@ -1263,6 +1263,13 @@ inline int icp_points_per_lane(int64_t B, int32_t N, int64_t cus) {
     while (u > 1 && B * ((N + kIcpBlock * u - 1) / (kIcpBlock * u)) < 2 * cus) u >>= 1;
     return u;
 }
+// The launch shape of the kernels that give a cloud to a lane or a wave's turn (k_kabsch and its kin, k_add_l1, k_rotate_clouds,
+// k_pc_normalize): enough waves for sixteen per compute unit, at most 64 clouds per wave (one per lane for the SVD), four waves per block.
+inline int clouds_per_wave(int64_t B, int64_t cus) {
+    const int64_t c = B / (cus * 16);
+    return static_cast<int>(c < 1 ? 1 : (c > 64 ? 64 : c));
+}
+inline int64_t cloud_blocks(int64_t B, int per_wave) { return ((B + per_wave - 1) / per_wave + kIcpBlock / 64 - 1) / (kIcpBlock / 64); }
 // One source point's share of a work item's sums.  d2 = |x_i - q_j(i)|^2 as the search left it, d its square root; w is 0 for a slot
 // past the cloud's end.  Returns nothing: the trimmed weight only lives here.
 template <bool TRIMMED>

@@ -18,6 +18,7 @@
 
 #include "../../include/so3proj.h"
 #include "so3_device.h"
+#include "so3_dispatch.h"
 #include "so3_rows.h"
 
 namespace {
@@ -3402,7 +3403,8 @@ __global__ __launch_bounds__(kStatBlock) void k_stats_collect(const double *__re
 }
 
 inline unsigned grid_for(int64_t B) { return static_cast<unsigned>((B + kBlock - 1) / kBlock); }
-inline unsigned persistent_grid(int64_t B) { const unsigned t = grid_for(B); return t < 2048u ? t : 2048u; }
+inline unsigned capped_grid(int64_t B, unsigned cap) { const unsigned t = grid_for(B); return t < cap ? t : cap; }
+inline unsigned persistent_grid(int64_t B) { return capped_grid(B, 2048u); }
 
 // Resident waves per SIMD the two-input kernels K2 / K3 / K1+K4 are built for (K1 runs at 3): their rare Jacobi branch keeps the frames
 // live across the backward (190-216 VGPRs).  Round 4 measured what three waves would buy with that branch out of the loop
@@ -3457,10 +3459,35 @@ inline int device_cus() {
     return cus[dev];
 }
 
+using so3::with_flags;
+using so3::with_value;
+using so3::kernel_label;
+constexpr double kDegPerRad = 57.295779513082320876798154814105;      // 180/pi
+
+// A wave per row at a time: the workgroups B rows need, at most per_cu per compute unit.
+inline unsigned wave_rows_grid(int64_t B, int per_cu) {
+    return static_cast<unsigned>(std::min<int64_t>((B + kBlock / 64 - 1) / (kBlock / 64), static_cast<int64_t>(device_cus()) * per_cu));
+}
+// The cloud kernels' launch shape on this device (so3::clouds_per_wave).
+struct CloudShape { int per_wave; int64_t blocks; };
+inline CloudShape cloud_shape(int64_t B) {
+    const int per_wave = so3::clouds_per_wave(B, device_cus());
+    return {per_wave, so3::cloud_blocks(B, per_wave)};
+}
+// Zero `bytes` at p in stream order; `what` names the call in so3_last_error() when the runtime refuses.
+inline int zero_async(void *p, size_t bytes, hipStream_t s, const char *what) {
+    const hipError_t e = hipMemsetAsync(p, 0, bytes, s);
+    return e == hipSuccess ? 0 : fail(static_cast<int>(e), what);
+}
+
 // Launch an operation on the streaming engine: NPL matrices per lane, WPS resident waves per SIMD, BLOCK threads.
 // The name of a k_rows instantiation as a profiler prints it: the runtime's own (mangled) name of the kernel behind the host
 // stub, demangled, without the "void " in front and the parameter list behind.
 thread_local const char *g_last_kernel = "";
+thread_local char g_kernel_label[64] = "";        // so3_last_kernel() of the launchers outside the engine: kernel_label writes it
+template <class... Args> inline void name_kernel(const char *name, Args... args) {
+    g_last_kernel = kernel_label(g_kernel_label, sizeof g_kernel_label, name, args...);
+}
 template <class Op, int NPL, int WPS, int BLOCK>
 const char *rows_kernel_name(hipStream_t s) {
     static const std::string name = [s] {
@@ -3515,15 +3542,21 @@ inline int64_t stream_units(int64_t B, std::initializer_list<const void *> ptrs)
     if (B / so3::kUnitRows > 0x7fffffff - 4096) return 0;      // the engine numbers its rounds in 32 bits (1.3e11 rows: 5 TB of float32 input)
     return B / so3::kUnitRows;
 }
+// A call's rows between the two: nunits whole units = rows [0, done) on the engine, the last `rest` rows on the tile kernels.
+struct Split {
+    int64_t nunits, done, rest;
+    Split(int64_t B, std::initializer_list<const void *> ptrs)
+        : nunits(B > 0 ? stream_units(B, ptrs) : 0), done(nunits * so3::kUnitRows), rest(B - done) {}
+};
 
 // A float32 row operation with up to three inputs and up to two outputs: whole units on the streaming engine, the rest
 // (and everything when a pointer is not 16-byte aligned) one row per thread.
 template <int NPL, int WPS, int BLOCK, class Op>
 int run_row_op(Op op, int64_t B, hipStream_t s, const char *what) {
-    const int64_t nunits = stream_units(B, {op.in0, op.in1, op.in2, op.out0, op.out1});
-    if (nunits > 0) launch_rows<NPL, WPS, BLOCK>(op, nunits, s);
-    const int64_t done = nunits * so3::kUnitRows, rest = B - done;
-    if (rest > 0) {
+    const Split sp(B, {op.in0, op.in1, op.in2, op.out0, op.out1});
+    if (sp.nunits > 0) launch_rows<NPL, WPS, BLOCK>(op, sp.nunits, s);
+    if (sp.rest > 0) {
+        const int64_t done = sp.done, rest = sp.rest;
         Op t = op;
         t.in0 = static_cast<const float *>(op.in0) + done * Op::kIn0N;
         if (Op::kIn1 != 0) t.in1 = static_cast<const float *>(op.in1) + done * Op::kIn1N;
@@ -3645,7 +3678,8 @@ int project_fwd(const void *M, float *R, uint8_t *flip, int64_t B, void *stream)
     SO3_CHECK_ARGS(M != nullptr && R != nullptr, "so3_project_fwd: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
     constexpr int EB = BF16 ? 2 : 4;
-    const int64_t nunits = stream_units(B, {M, R});
+    const Split sp(B, {M, R});
+    const int64_t nunits = sp.nunits, done = sp.done, rest = sp.rest;
     if (nunits > 0) {
         // two matrices per lane, three waves per SIMD: against one matrix per lane at four / five / six / eight waves (round 3, the fast
         // path, one device): 14.6-14.9 us against 15.6 / 14.9 / 16.6 (spills) / 18.4
@@ -3685,17 +3719,14 @@ int project_fwd(const void *M, float *R, uint8_t *flip, int64_t B, void *stream)
             launch_rows<2, SO3_WPS_K1, SO3_BLOCK_K1>(op, nunits, s);
         }
     }
-    const int64_t done = nunits * so3::kUnitRows, rest = B - done;
     if (rest > 0) {
         const void *Mt = advance_bytes(M, done * 9 * EB);
         float *Rt = R + done * 9;
         uint8_t *ft = advance(flip, done);
         const bool vec = (BF16 || aligned16(Mt)) && aligned16(Rt);      // for bf16 input VEC only governs the R store
         const dim3 grid(grid_for(rest)), block(kBlock);
-#define LAUNCH(VE, FL) hipLaunchKernelGGL((k_project_fwd<BF16, VE, FL>), grid, block, 0, s, Mt, Rt, ft, rest)
-        if (vec) { if (flip) LAUNCH(true, true); else LAUNCH(true, false); }
-        else { if (flip) LAUNCH(false, true); else LAUNCH(false, false); }
-#undef LAUNCH
+        with_flags([&](auto VE, auto FL) { hipLaunchKernelGGL((k_project_fwd<BF16, VE(), FL()>), grid, block, 0, s, Mt, Rt, ft, rest); }, vec,
+                   flip != nullptr);
     }
     return check_launch("so3_project_fwd");
 }
@@ -3708,20 +3739,19 @@ int project_bwd(const void *M, const float *G, void *dM, int64_t B, void *stream
     SO3_CHECK_ARGS(M != nullptr && G != nullptr && dM != nullptr, "so3_project_bwd: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
     constexpr int EB = BF16 ? 2 : 4;
-    const int64_t nunits = stream_units(B, {M, G, dM});
-    if (nunits > 0) {
+    const Split sp(B, {M, G, dM});
+    const int64_t done = sp.done, rest = sp.rest;
+    if (sp.nunits > 0) {
         so3::OpProjectBwd<EB> op; op.in0 = M; op.in1 = G; op.out0 = dM;
-        launch_rows<2, SO3_WPS_K2, 256>(op, nunits, s);
+        launch_rows<2, SO3_WPS_K2, 256>(op, sp.nunits, s);
     }
-    const int64_t done = nunits * so3::kUnitRows, rest = B - done;
     if (rest > 0) {
         const void *Mt = advance_bytes(M, done * 9 * EB);
         const float *Gt = G + done * 9;
         void *dt = advance_bytes(dM, done * 9 * EB);
         const bool vec = aligned16(Gt) && (BF16 || (aligned16(Mt) && aligned16(dt)));
         const dim3 grid(grid_for(rest)), block(kBlock);
-        if (vec) hipLaunchKernelGGL((k_project_bwd<BF16, true>), grid, block, 0, s, Mt, Gt, dt, rest);
-        else hipLaunchKernelGGL((k_project_bwd<BF16, false>), grid, block, 0, s, Mt, Gt, dt, rest);
+        with_flags([&](auto VE) { hipLaunchKernelGGL((k_project_bwd<BF16, VE()>), grid, block, 0, s, Mt, Gt, dt, rest); }, vec);
     }
     return check_launch("so3_project_bwd");
 }
@@ -3730,8 +3760,9 @@ int project_bwd(const void *M, const float *G, void *dM, int64_t B, void *stream
 // How a reduction over a large batch is finished.  With a workspace (and whole units on the engine): the remainder kernel,
 // if any, runs FIRST and fills slots [0, tile_wgs); the engine launch then takes tickets and its last workgroup writes the
 // result.  Without: the accumulators are zeroed by a memset / init launch and every workgroup adds to them atomically.
-inline bool use_workspace(void *workspace, int64_t nunits, unsigned tile_wgs) {
-    return workspace != nullptr && nunits > 0 && tile_wgs <= 1024u;        // + at most 1024 engine workgroups <= kMaxPartials
+inline so3::ReduceWs *reduce_workspace(void *workspace, const Split &sp, unsigned tile_wgs) {
+    const bool use = workspace != nullptr && sp.nunits > 0 && tile_wgs <= 1024u;        // + at most 1024 engine workgroups <= kMaxPartials
+    return use ? static_cast<so3::ReduceWs *>(workspace) : nullptr;
 }
 
 template <bool BF16>
@@ -3746,22 +3777,19 @@ int frob(const void *M, const float *Rtrue, float *R, void *dM, double *loss_sum
         SO3_CHECK_ARGS(M != nullptr && Rtrue != nullptr, "so3_frob_fwd_bwd: null pointer");
         const dim3 grid(1), block(static_cast<unsigned>((B + 63) / 64 * 64));
         const float inv = 1.0f / static_cast<float>(B);
-#define SMALL(WR, WD) hipLaunchKernelGGL((k_frob_small<BF16, WR, WD>), grid, block, 0, s, M, Rtrue, R, dM, loss_sum, loss_mean, static_cast<int>(B), inv, prezeroed)
-        if (R && dM) SMALL(true, true); else if (R) SMALL(true, false); else if (dM) SMALL(false, true); else SMALL(false, false);
-#undef SMALL
+        with_flags([&](auto WR, auto WD) {
+            hipLaunchKernelGGL((k_frob_small<BF16, WR(), WD()>), grid, block, 0, s, M, Rtrue, R, dM, loss_sum, loss_mean, static_cast<int>(B), inv, prezeroed);
+        }, R != nullptr, dM != nullptr);
         return check_launch("so3_frob_fwd_bwd");
     }
     constexpr int EB = BF16 ? 2 : 4;
-    const int64_t nunits = B > 0 ? stream_units(B, {M, Rtrue, R, dM}) : 0;
-    const int64_t done = nunits * so3::kUnitRows, rest = B - done;
+    const Split sp(B, {M, Rtrue, R, dM});
+    const int64_t nunits = sp.nunits, done = sp.done, rest = sp.rest;
     const unsigned tile_wgs = rest > 0 ? persistent_grid(rest) : 0u;
-    so3::ReduceWs *ws = use_workspace(workspace, nunits, tile_wgs) ? static_cast<so3::ReduceWs *>(workspace) : nullptr;
-    if (ws == nullptr && !prezeroed) {
-        hipError_t e = hipMemsetAsync(loss_sum, 0, sizeof(double), s);
-        if (e != hipSuccess) return fail((int)e, "so3_frob_fwd_bwd: memset");
-    }
+    so3::ReduceWs *ws = reduce_workspace(workspace, sp, tile_wgs);
+    if (ws == nullptr && !prezeroed) if (int e = zero_async(loss_sum, sizeof(double), s, "so3_frob_fwd_bwd: memset")) return e;
     if (B == 0) {
-        if (loss_mean != nullptr) { hipError_t e = hipMemsetAsync(loss_mean, 0, sizeof(float), s); if (e != hipSuccess) return fail((int)e, "so3_frob_fwd_bwd: memset"); }
+        if (loss_mean != nullptr) if (int e = zero_async(loss_mean, sizeof(float), s, "so3_frob_fwd_bwd: memset")) return e;
         return 0;
     }
     SO3_CHECK_ARGS(M != nullptr && Rtrue != nullptr, "so3_frob_fwd_bwd: null pointer");
@@ -3774,18 +3802,17 @@ int frob(const void *M, const float *Rtrue, float *R, void *dM, double *loss_sum
         bool vec = aligned16(Tt) && (Rt == nullptr || aligned16(Rt));
         if (!BF16) vec = vec && aligned16(Mt) && (dt == nullptr || aligned16(dt));
         const dim3 grid(tile_wgs), block(kBlock);
-#define LAUNCH(VE, WR, WD) hipLaunchKernelGGL((k_frob_fwd_bwd<BF16, VE, WR, WD>), grid, block, 0, s, Mt, Tt, Rt, dt, loss_sum, rest, inv_b, ws)
-#define PICK(VE) do { if (R && dM) LAUNCH(VE, true, true); else if (R) LAUNCH(VE, true, false); else if (dM) LAUNCH(VE, false, true); else LAUNCH(VE, false, false); } while (0)
-        if (vec) PICK(true); else PICK(false);
-#undef PICK
-#undef LAUNCH
+        with_flags([&](auto VE, auto WR, auto WD) {
+            hipLaunchKernelGGL((k_frob_fwd_bwd<BF16, VE(), WR(), WD()>), grid, block, 0, s, Mt, Tt, Rt, dt, loss_sum, rest, inv_b, ws);
+        }, vec, R != nullptr, dM != nullptr);
     }
     if (nunits > 0) {
-#define SLAUNCH(WD, WR) do { so3::OpFrobHead<EB, WD, WR> op; op.in0 = M; op.in1 = Rtrue; op.out0 = dM; op.out1 = R; \
-                             op.loss_sum = loss_sum; op.inv_b = inv_b; op.loss_mean = loss_mean; op.inv_b_f64 = 1.0 / static_cast<double>(B); \
-                             op.ws = ws; op.ws_slot0 = tile_wgs; launch_rows<2, SO3_WPS_K3, SO3_BLOCK_K3>(op, nunits, s); } while (0)
-        if (R && dM) SLAUNCH(true, true); else if (dM) SLAUNCH(true, false); else if (R) SLAUNCH(false, true); else SLAUNCH(false, false);
-#undef SLAUNCH
+        with_flags([&](auto WR, auto WD) {
+            so3::OpFrobHead<EB, WD(), WR()> op; op.in0 = M; op.in1 = Rtrue; op.out0 = dM; op.out1 = R;
+            op.loss_sum = loss_sum; op.inv_b = inv_b; op.loss_mean = loss_mean; op.inv_b_f64 = 1.0 / static_cast<double>(B);
+            op.ws = ws; op.ws_slot0 = tile_wgs;
+            launch_rows<2, SO3_WPS_K3, SO3_BLOCK_K3>(op, nunits, s);
+        }, R != nullptr, dM != nullptr);
     }
     if (ws == nullptr && loss_mean != nullptr) k_mean_from_sum<<<1, 1, 0, s>>>(loss_sum, loss_mean, 1.0 / static_cast<double>(B));
     return check_launch("so3_frob_fwd_bwd");
@@ -3797,24 +3824,19 @@ int frob(const void *M, const float *Rtrue, float *R, void *dM, double *loss_sum
 // C ABI
 // =====================================================================================================
 namespace {
+// The model points a lane of k_add_l1 / k_sym_add keeps in flight.
+inline int add_points_unroll(int32_t N) { return N > 512 ? 16 : (N > 128 ? 8 : 2); }
+
 template <bool DISENT, bool L2 = false>
 int launch_add_l1(const float *Tgt, const float *Tpred, const float *points, float *dists, double *loss_sum, float *dTpred,
                   float grad_scale, int64_t B, int32_t N, hipStream_t s, const char *what) {
-    if (loss_sum != nullptr) {
-        const hipError_t e = hipMemsetAsync(loss_sum, 0, (DISENT ? 3 : 1) * sizeof(double), s);
-        if (e != hipSuccess) return fail(static_cast<int>(e), what);
-    }
+    if (loss_sum != nullptr) if (int e = zero_async(loss_sum, (DISENT ? 3 : 1) * sizeof(double), s, what)) return e;
     if (B == 0) return 0;
-    int64_t per_wave = B / (static_cast<int64_t>(device_cus()) * 16);              // enough waves for 256 CUs x 16, at most 64 samples per wave
-    if (per_wave < 1) per_wave = 1;
-    if (per_wave > 64) per_wave = 64;
-    const int64_t waves = (B + per_wave - 1) / per_wave;
-    const int64_t blocks = (waves + (kBlock / 64) - 1) / (kBlock / 64);
-    const dim3 grid(static_cast<unsigned>(blocks)), block(kBlock);
-    const int pw = static_cast<int>(per_wave);
-    if (N > 512) hipLaunchKernelGGL((k_add_l1<DISENT, 16, L2>), grid, block, 0, s, Tgt, Tpred, points, dists, loss_sum, dTpred, grad_scale, B, N, pw);
-    else if (N > 128) hipLaunchKernelGGL((k_add_l1<DISENT, 8, L2>), grid, block, 0, s, Tgt, Tpred, points, dists, loss_sum, dTpred, grad_scale, B, N, pw);
-    else hipLaunchKernelGGL((k_add_l1<DISENT, 2, L2>), grid, block, 0, s, Tgt, Tpred, points, dists, loss_sum, dTpred, grad_scale, B, N, pw);
+    const CloudShape shape = cloud_shape(B);
+    const dim3 grid(static_cast<unsigned>(shape.blocks)), block(kBlock);
+    with_value<16, 8, 2>(add_points_unroll(N), [&](auto U) {
+        hipLaunchKernelGGL((k_add_l1<DISENT, U(), L2>), grid, block, 0, s, Tgt, Tpred, points, dists, loss_sum, dTpred, grad_scale, B, N, shape.per_wave);
+    });
     return check_launch(what);
 }
 
@@ -3823,18 +3845,17 @@ template <bool DIAMETER>
 int launch_add_s(const float *Tgt, const float *Tpred, const float *points, float *point_dist, int32_t *nearest, float *rows, double *total,
                  int64_t B, int32_t N, hipStream_t s, const char *what) {
     const int64_t cus = device_cus();
-    int u = 4;
-    while (u > 1 && B * ((N + kBlock * u - 1) / (kBlock * u)) < 2 * cus) u >>= 1;
+    const int u = so3::icp_points_per_lane(B, N, cus);
     const int32_t chunks = (N + kBlock * u - 1) / (kBlock * u);
     const dim3 grid(static_cast<unsigned>(std::min<int64_t>(B * chunks, cus * 64))), block(kBlock);
-#define ADDS(WI, UU) hipLaunchKernelGGL((k_add_s<(WI) && !DIAMETER, DIAMETER, UU>), grid, block, 0, s, Tgt, Tpred, points, point_dist, nearest, B, N, chunks)
-#define ADDS_U(WI) do { if (u == 4) ADDS(WI, 4); else if (u == 2) ADDS(WI, 2); else ADDS(WI, 1); } while (0)
-    if (!DIAMETER && nearest != nullptr) ADDS_U(true); else ADDS_U(false);
-#undef ADDS_U
-#undef ADDS
+    with_flags([&](auto WI) {
+        constexpr bool kIndex = WI() && !DIAMETER;             // a diameter has no nearest index: no such instantiation
+        with_value<4, 2, 1>(u, [&](auto U) {
+            hipLaunchKernelGGL((k_add_s<kIndex, DIAMETER, U()>), grid, block, 0, s, Tgt, Tpred, points, point_dist, nearest, B, N, chunks);
+        });
+    }, !DIAMETER && nearest != nullptr);
     if (rows != nullptr) {
-        const int64_t blocks = std::min<int64_t>((B + kBlock / 64 - 1) / (kBlock / 64), cus * 8);
-        hipLaunchKernelGGL((k_add_s_rows<DIAMETER>), dim3(static_cast<unsigned>(blocks)), block, 0, s, point_dist, rows, static_cast<double *>(nullptr), B, N);
+        hipLaunchKernelGGL((k_add_s_rows<DIAMETER>), dim3(wave_rows_grid(B, 8)), block, 0, s, point_dist, rows, static_cast<double *>(nullptr), B, N);
         if (total != nullptr) hipLaunchKernelGGL(k_sum_f32_to_f64, dim3(1), block, 0, s, rows, total, B);
     } else if (total != nullptr) {            // no per-sample buffer to go through: one workgroup finishes rows and batch
         hipLaunchKernelGGL((k_add_s_rows<DIAMETER>), dim3(1), block, 0, s, point_dist, static_cast<float *>(nullptr), total, B, N);
@@ -3845,26 +3866,21 @@ int launch_add_s(const float *Tgt, const float *Tpred, const float *points, floa
 // k_sym_add over B clouds: a wave per sample at a time, at most eight workgroups per compute unit.  With `rows` the batch total is a
 // second, one-workgroup launch over them; without, one workgroup does the whole call and sums as it goes (k_add_s_rows's rule).
 // The instantiation's name goes to so3_last_kernel.
-thread_local char g_sym_add_kernel[48] = "";
 template <int MODE, bool GRAD>
 void launch_sym_add(const float *Tgt, const float *Tpred, const float *points, const float *S, const int32_t *class_id, int32_t C, int32_t K,
                     float *rows, int32_t *index, double *total, float *dT, float grad_scale, int64_t B, int32_t N, hipStream_t s) {
     const bool one_group = rows == nullptr && total != nullptr;
-    const int64_t blocks = one_group ? 1 : std::min<int64_t>((B + kBlock / 64 - 1) / (kBlock / 64), static_cast<int64_t>(device_cus()) * 8);
-    const dim3 grid(static_cast<unsigned>(blocks)), block(kBlock);
+    const dim3 grid(one_group ? 1u : wave_rows_grid(B, 8)), block(kBlock);
     double *in_kernel = one_group ? total : nullptr;
-    const int u = N > 512 ? 16 : (N > 128 ? 8 : 2);
-    snprintf(g_sym_add_kernel, sizeof g_sym_add_kernel, "k_sym_add<%d, %s, %d>", MODE, GRAD ? "true" : "false", u);
-    g_last_kernel = g_sym_add_kernel;
-#define SYM_ADD(UU) hipLaunchKernelGGL((k_sym_add<MODE, GRAD, UU>), grid, block, 0, s, Tgt, Tpred, points, S, class_id, C, K, rows, index, \
-                                       in_kernel, dT, grad_scale, B, N)
-    if (u == 16) SYM_ADD(16); else if (u == 8) SYM_ADD(8); else SYM_ADD(2);
-#undef SYM_ADD
+    with_value<16, 8, 2>(add_points_unroll(N), [&](auto U) {
+        name_kernel("k_sym_add", MODE, GRAD, U);
+        hipLaunchKernelGGL((k_sym_add<MODE, GRAD, U()>), grid, block, 0, s, Tgt, Tpred, points, S, class_id, C, K, rows, index, in_kernel, dT,
+                           grad_scale, B, N);
+    });
     if (rows != nullptr && total != nullptr) hipLaunchKernelGGL(k_sum_f32_to_f64, dim3(1), block, 0, s, rows, total, B);
 }
 
 // k_icp_step over B clouds at k_add_s's launch shape.  The instantiation's name goes to so3_last_kernel.
-thread_local char g_icp_kernel[64] = "";
 int32_t icp_chunks(int64_t B, int32_t N, int &u) {
     u = so3::icp_points_per_lane(B, N, device_cus());
     return (N + kBlock * u - 1) / (kBlock * u);
@@ -3873,19 +3889,14 @@ template <bool SUMS>
 void launch_icp_step(const float *P, const float *Q, int64_t q_stride, const float *w, const float *pose, float max_distance, float *rec,
                      float *dist, int32_t *nearest, int64_t B, int32_t N, int32_t M, int u, int32_t chunks, hipStream_t s) {
     const dim3 grid(static_cast<unsigned>(std::min<int64_t>(B * chunks, static_cast<int64_t>(device_cus()) * 64))), block(kBlock);
-    const bool weighted = SUMS && w != nullptr, trimmed = SUMS && max_distance >= 0.f;
-    snprintf(g_icp_kernel, sizeof g_icp_kernel, "k_icp_step<%s, %s, %s, %d>", weighted ? "true" : "false", trimmed ? "true" : "false",
-             SUMS ? "true" : "false", u);
-    g_last_kernel = g_icp_kernel;
-#define ICP(WW, TT, UU) hipLaunchKernelGGL((k_icp_step<(WW) && SUMS, (TT) && SUMS, SUMS, UU>), grid, block, 0, s, P, Q, q_stride, w, pose, max_distance, \
-                                           rec, dist, nearest, B, N, M, chunks)
-#define ICP_U(WW, TT) do { if (u == 4) ICP(WW, TT, 4); else if (u == 2) ICP(WW, TT, 2); else ICP(WW, TT, 1); } while (0)
-    if (weighted && trimmed) ICP_U(true, true);
-    else if (weighted) ICP_U(true, false);
-    else if (trimmed) ICP_U(false, true);
-    else ICP_U(false, false);
-#undef ICP_U
-#undef ICP
+    with_flags([&](auto WW, auto TT) {
+        constexpr bool kWeighted = WW() && SUMS, kTrimmed = TT() && SUMS;       // the search alone has neither: no such instantiation
+        with_value<4, 2, 1>(u, [&](auto U) {
+            name_kernel("k_icp_step", kWeighted, kTrimmed, SUMS, U);
+            hipLaunchKernelGGL((k_icp_step<kWeighted, kTrimmed, SUMS, U()>), grid, block, 0, s, P, Q, q_stride, w, pose, max_distance, rec, dist,
+                               nearest, B, N, M, chunks);
+        });
+    }, SUMS && w != nullptr, SUMS && max_distance >= 0.f);
 }
 }  // namespace
 
@@ -3898,10 +3909,10 @@ void angle_bwd_launch(const float *R1, const float *R2, const void *grad, double
     op.in0 = R1; op.in1 = R2; op.out0 = d1; op.out1 = d2;
     op.lo = lo; op.hi = hi; op.unit = unit; op.div = div;
     if (GRAD == 0) op.gscalar = grad; else op.in2 = grad;
-    const int64_t nunits = stream_units(B, {R1, R2, GRAD != 0 ? grad : nullptr, d1, d2});
+    const Split sp(B, {R1, R2, GRAD != 0 ? grad : nullptr, d1, d2});
+    const int64_t done = sp.done, rest = sp.rest;
     // light arithmetic, 108-152 B per row: two rows per lane, three waves per SIMD (11 KB of LDS per wave)
-    if (nunits > 0) launch_rows<SO3_K4B_NPL, SO3_K4B_WPS, SO3_K4B_BLOCK>(op, nunits, s);
-    const int64_t done = nunits * so3::kUnitRows, rest = B - done;
+    if (sp.nunits > 0) launch_rows<SO3_K4B_NPL, SO3_K4B_WPS, SO3_K4B_BLOCK>(op, sp.nunits, s);
     if (rest > 0) {
         so3::OpAngleBwd<GRAD, F64MATH, BOTH> t = op;
         t.in0 = R1 + done * 9; t.in1 = R2 + done * 9;
@@ -3984,20 +3995,18 @@ int so3_frob_loss_v2_f32(const float *Rpred, const float *Rtrue, float *dRpred, 
         SO3_CHECK_ARGS(Rpred != nullptr && Rtrue != nullptr, "so3_frob_loss_f32: null pointer");
         const dim3 grid(1), block(static_cast<unsigned>((B + 63) / 64 * 64));
         const float inv = 1.0f / static_cast<float>(B);
-        if (dRpred) hipLaunchKernelGGL((k_frob_loss_small<true>), grid, block, 0, s, Rpred, Rtrue, dRpred, loss_sum, loss_mean, static_cast<int>(B), inv, prezeroed);
-        else hipLaunchKernelGGL((k_frob_loss_small<false>), grid, block, 0, s, Rpred, Rtrue, dRpred, loss_sum, loss_mean, static_cast<int>(B), inv, prezeroed);
+        with_flags([&](auto WG) {
+            hipLaunchKernelGGL((k_frob_loss_small<WG()>), grid, block, 0, s, Rpred, Rtrue, dRpred, loss_sum, loss_mean, static_cast<int>(B), inv, prezeroed);
+        }, dRpred != nullptr);
         return check_launch("so3_frob_loss_f32");
     }
-    const int64_t nunits = B > 0 ? stream_units(B, {Rpred, Rtrue, dRpred}) : 0;
-    const int64_t done = nunits * so3::kUnitRows, rest = B - done;
+    const Split sp(B, {Rpred, Rtrue, dRpred});
+    const int64_t nunits = sp.nunits, done = sp.done, rest = sp.rest;
     const unsigned tile_wgs = rest > 0 ? persistent_grid(rest) : 0u;
-    so3::ReduceWs *ws = use_workspace(workspace, nunits, tile_wgs) ? static_cast<so3::ReduceWs *>(workspace) : nullptr;
-    if (ws == nullptr && !prezeroed) {
-        hipError_t e = hipMemsetAsync(loss_sum, 0, sizeof(double), s);
-        if (e != hipSuccess) return fail((int)e, "so3_frob_loss_f32: memset");
-    }
+    so3::ReduceWs *ws = reduce_workspace(workspace, sp, tile_wgs);
+    if (ws == nullptr && !prezeroed) if (int e = zero_async(loss_sum, sizeof(double), s, "so3_frob_loss_f32: memset")) return e;
     if (B == 0) {
-        if (loss_mean != nullptr) { hipError_t e = hipMemsetAsync(loss_mean, 0, sizeof(float), s); if (e != hipSuccess) return fail((int)e, "so3_frob_loss_f32: memset"); }
+        if (loss_mean != nullptr) if (int e = zero_async(loss_mean, sizeof(float), s, "so3_frob_loss_f32: memset")) return e;
         return 0;
     }
     SO3_CHECK_ARGS(Rpred != nullptr && Rtrue != nullptr, "so3_frob_loss_f32: null pointer");
@@ -4007,17 +4016,16 @@ int so3_frob_loss_v2_f32(const float *Rpred, const float *Rtrue, float *dRpred, 
         float *gt = advance(dRpred, done * 9);
         const bool vec = aligned16(Pt) && aligned16(Tt) && (gt == nullptr || aligned16(gt));
         const dim3 grid(tile_wgs), block(kBlock);
-#define LAUNCH(VE, WG) hipLaunchKernelGGL((k_frob_loss<VE, WG>), grid, block, 0, s, Pt, Tt, gt, loss_sum, rest, inv_b, ws)
-        if (vec) { if (dRpred) LAUNCH(true, true); else LAUNCH(true, false); }
-        else { if (dRpred) LAUNCH(false, true); else LAUNCH(false, false); }
-#undef LAUNCH
+        with_flags([&](auto VE, auto WG) {
+            hipLaunchKernelGGL((k_frob_loss<VE(), WG()>), grid, block, 0, s, Pt, Tt, gt, loss_sum, rest, inv_b, ws);
+        }, vec, dRpred != nullptr);
     }
     if (nunits > 0) {
-#define SLAUNCH(WG) do { so3::OpFrobLoss<WG> op; op.in0 = Rpred; op.in1 = Rtrue; op.out0 = dRpred; op.loss_sum = loss_sum; op.inv_b = inv_b; \
-                         op.loss_mean = loss_mean; op.inv_b_f64 = 1.0 / static_cast<double>(B); op.ws = ws; op.ws_slot0 = tile_wgs; \
-                         launch_rows<1, 4, 1024>(op, nunits, s); } while (0)
-        if (dRpred) SLAUNCH(true); else SLAUNCH(false);
-#undef SLAUNCH
+        with_flags([&](auto WG) {
+            so3::OpFrobLoss<WG()> op; op.in0 = Rpred; op.in1 = Rtrue; op.out0 = dRpred; op.loss_sum = loss_sum; op.inv_b = inv_b;
+            op.loss_mean = loss_mean; op.inv_b_f64 = 1.0 / static_cast<double>(B); op.ws = ws; op.ws_slot0 = tile_wgs;
+            launch_rows<1, 4, 1024>(op, nunits, s);
+        }, dRpred != nullptr);
     }
     if (ws == nullptr && loss_mean != nullptr) k_mean_from_sum<<<1, 1, 0, s>>>(loss_sum, loss_mean, 1.0 / static_cast<double>(B));
     return check_launch("so3_frob_loss_f32");
@@ -4030,18 +4038,19 @@ int so3_angle_error_v2(const float *R1, const float *R2, double *deg, double *su
     const bool radians = (flags & SO3_RADIANS) != 0, prezeroed = (flags & SO3_PREZEROED) != 0;      // (K4 alone is float64 on every row: SO3_EXACT_F64 changes nothing)
     SO3_CHECK_ARGS(B >= 0 && B <= SO3_MAX_B, "so3_angle_error: B");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const double unit = radians ? 1.0 : 57.295779513082320876798154814105;   // 180/pi
+    const double unit = radians ? 1.0 : kDegPerRad;
     if (B > 0 && B <= kSmallBatch && (sum_count || range_flag)) {       // one workgroup: the accumulators need no launch of their own
         SO3_CHECK_ARGS(R1 != nullptr && R2 != nullptr, "so3_angle_error: null pointer");
         const dim3 grid(1), block(static_cast<unsigned>((B + 63) / 64 * 64));
-        if (deg) hipLaunchKernelGGL((k_angle_small<false, false, true>), grid, block, 0, s, R1, R2, nullptr, deg, sum_count, range_flag, unit, static_cast<int>(B), prezeroed);
-        else hipLaunchKernelGGL((k_angle_small<false, false, false>), grid, block, 0, s, R1, R2, nullptr, deg, sum_count, range_flag, unit, static_cast<int>(B), prezeroed);
+        with_flags([&](auto WD) {
+            hipLaunchKernelGGL((k_angle_small<false, false, WD()>), grid, block, 0, s, R1, R2, nullptr, deg, sum_count, range_flag, unit, static_cast<int>(B), prezeroed);
+        }, deg != nullptr);
         return check_launch("so3_angle_error");
     }
-    const int64_t nunits = B > 0 ? stream_units(B, {R1, R2, deg}) : 0;
-    const int64_t done = nunits * so3::kUnitRows, rest = B - done;
+    const Split sp(B, {R1, R2, deg});
+    const int64_t nunits = sp.nunits, done = sp.done, rest = sp.rest;
     const unsigned tile_wgs = rest > 0 ? grid_for(rest) : 0u;
-    so3::ReduceWs *ws = (sum_count || range_flag) && use_workspace(workspace, nunits, tile_wgs) ? static_cast<so3::ReduceWs *>(workspace) : nullptr;
+    so3::ReduceWs *ws = (sum_count || range_flag) ? reduce_workspace(workspace, sp, tile_wgs) : nullptr;
     // without a workspace one tiny launch zeroes the accumulators and writes the row count (instead of two memsets + a store)
     if (ws == nullptr && (sum_count || range_flag) && !(prezeroed && B > 0)) k_angle_init<<<1, 1, 0, s>>>(sum_count, range_flag, static_cast<double>(B));
     if (B == 0) return check_launch("so3_angle_error");
@@ -4053,19 +4062,18 @@ int so3_angle_error_v2(const float *R1, const float *R2, double *deg, double *su
         double *dg = advance(deg, done);
         const bool vec = aligned16(A1) && aligned16(A2);
         const dim3 grid(tile_wgs), block(kBlock);
-#define LAUNCH(VE, WD, WS) hipLaunchKernelGGL((k_angle_error<VE, WD, WS>), grid, block, 0, s, A1, A2, dg, sum_count, range_flag, unit, rest, ws)
-#define PICK(VE) do { if (deg && sum_count) LAUNCH(VE, true, true); else if (deg) LAUNCH(VE, true, false); else if (sum_count) LAUNCH(VE, false, true); else LAUNCH(VE, false, false); } while (0)
-        if (vec) PICK(true); else PICK(false);
-#undef PICK
-#undef LAUNCH
+        with_flags([&](auto VE, auto WD, auto WS) {
+            hipLaunchKernelGGL((k_angle_error<VE(), WD(), WS()>), grid, block, 0, s, A1, A2, dg, sum_count, range_flag, unit, rest, ws);
+        }, vec, deg != nullptr, sum_count != nullptr);
     }
     if (nunits > 0) {
         // 1024-thread workgroups: 256 partials (or, without a workspace, 256 same-address float64 atomics at ~9 ns) at the end
-#define SLAUNCH(WD, WS) do { so3::OpAngle<WD, WS> op; op.in0 = R1; op.in1 = R2; op.deg = deg; op.sum_count = sum_count; \
-                             op.range_flag = range_flag; op.unit_scale = unit; op.count = static_cast<double>(B); op.ws = ws; op.ws_slot0 = tile_wgs; \
-                             op.store_count = store_count; launch_rows<1, 4, 1024>(op, nunits, s); } while (0)
-        if (deg && sum_count) SLAUNCH(true, true); else if (deg) SLAUNCH(true, false); else if (sum_count) SLAUNCH(false, true); else SLAUNCH(false, false);
-#undef SLAUNCH
+        with_flags([&](auto WD, auto WS) {
+            so3::OpAngle<WD(), WS()> op; op.in0 = R1; op.in1 = R2; op.deg = deg; op.sum_count = sum_count;
+            op.range_flag = range_flag; op.unit_scale = unit; op.count = static_cast<double>(B); op.ws = ws; op.ws_slot0 = tile_wgs;
+            op.store_count = store_count;
+            launch_rows<1, 4, 1024>(op, nunits, s);
+        }, deg != nullptr, sum_count != nullptr);
     }
     return check_launch("so3_angle_error");
 }
@@ -4075,19 +4083,19 @@ int so3_project_angle_error_v2_f32(const float *M, const float *Rtrue, float *R,
     const bool radians = (flags & SO3_RADIANS) != 0, prezeroed = (flags & SO3_PREZEROED) != 0, exact = (flags & SO3_EXACT_F64) != 0;
     SO3_CHECK_ARGS(B >= 0 && B <= SO3_MAX_B, "so3_project_angle_error_f32: B");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const double unit = radians ? 1.0 : 57.295779513082320876798154814105;
+    const double unit = radians ? 1.0 : kDegPerRad;
     if (B > 0 && B <= kSmallBatch && (sum_count || range_flag)) {       // one workgroup, one launch
         SO3_CHECK_ARGS(M != nullptr && Rtrue != nullptr, "so3_project_angle_error_f32: null pointer");
         const dim3 grid(1), block(static_cast<unsigned>((B + 63) / 64 * 64));
-#define SMALL(WR, WD) hipLaunchKernelGGL((k_angle_small<true, WR, WD>), grid, block, 0, s, M, Rtrue, R, deg, sum_count, range_flag, unit, static_cast<int>(B), prezeroed)
-        if (R && deg) SMALL(true, true); else if (R) SMALL(true, false); else if (deg) SMALL(false, true); else SMALL(false, false);
-#undef SMALL
+        with_flags([&](auto WR, auto WD) {
+            hipLaunchKernelGGL((k_angle_small<true, WR(), WD()>), grid, block, 0, s, M, Rtrue, R, deg, sum_count, range_flag, unit, static_cast<int>(B), prezeroed);
+        }, R != nullptr, deg != nullptr);
         return check_launch("so3_project_angle_error_f32");
     }
-    const int64_t nunits = B > 0 ? stream_units(B, {M, Rtrue, R, deg}) : 0;
-    const int64_t done = nunits * so3::kUnitRows, rest = B - done;
+    const Split sp(B, {M, Rtrue, R, deg});
+    const int64_t nunits = sp.nunits, done = sp.done, rest = sp.rest;
     const unsigned tile_wgs = rest > 0 ? grid_for(rest) : 0u;
-    so3::ReduceWs *ws = (sum_count || range_flag) && use_workspace(workspace, nunits, tile_wgs) ? static_cast<so3::ReduceWs *>(workspace) : nullptr;
+    so3::ReduceWs *ws = (sum_count || range_flag) ? reduce_workspace(workspace, sp, tile_wgs) : nullptr;
     if (ws == nullptr && (sum_count || range_flag) && !(prezeroed && B > 0)) k_angle_init<<<1, 1, 0, s>>>(sum_count, range_flag, static_cast<double>(B));
     if (B == 0) return check_launch("so3_project_angle_error_f32");
     const bool store_count = prezeroed && ws == nullptr;
@@ -4100,23 +4108,24 @@ int so3_project_angle_error_v2_f32(const float *M, const float *Rtrue, float *R,
         float *Rt = R + done * 9;
         double *dg = advance(deg, done);
         const dim3 grid(tile_wgs), block(kBlock);
-        if (aligned16(Mt) && aligned16(Rt)) hipLaunchKernelGGL((k_project_fwd<false, true, false>), grid, block, 0, s, static_cast<const void *>(Mt), Rt, nullptr, rest);
-        else hipLaunchKernelGGL((k_project_fwd<false, false, false>), grid, block, 0, s, static_cast<const void *>(Mt), Rt, nullptr, rest);
-#define LAUNCH(WD, WS) hipLaunchKernelGGL((k_angle_error<false, WD, WS>), grid, block, 0, s, Rt, Tt, dg, sum_count, range_flag, unit, rest, ws)
-        if (deg && sum_count) LAUNCH(true, true); else if (deg) LAUNCH(true, false); else if (sum_count) LAUNCH(false, true); else LAUNCH(false, false);
-#undef LAUNCH
+        with_flags([&](auto VE) {
+            hipLaunchKernelGGL((k_project_fwd<false, VE(), false>), grid, block, 0, s, static_cast<const void *>(Mt), Rt, nullptr, rest);
+        }, aligned16(Mt) && aligned16(Rt));
+        with_flags([&](auto WD, auto WS) {
+            hipLaunchKernelGGL((k_angle_error<false, WD(), WS()>), grid, block, 0, s, Rt, Tt, dg, sum_count, range_flag, unit, rest, ws);
+        }, deg != nullptr, sum_count != nullptr);
     }
     if (nunits > 0) {
-#define SLAUNCH(WR, WD, WS, F32) do { so3::OpProjectAngle<4, WR, WD, WS, F32> op; op.in0 = M; op.in1 = Rtrue; op.out0 = R; op.deg = deg; \
-                                 op.sum_count = sum_count; op.range_flag = range_flag; op.unit_scale = unit; op.count = static_cast<double>(B); \
-                                 op.ws = ws; op.ws_slot0 = tile_wgs; op.store_count = store_count; launch_rows<2, SO3_WPS_K14, SO3_BLOCK_K14>(op, nunits, s); } while (0)
         // the sum without per-row angles: float32 trace and acos outside the band around +-1 (so3::angle_sum_f32) unless SO3_EXACT_F64
-#define PICKR(WR) do { if (deg && sum_count) SLAUNCH(WR, true, true, false); else if (deg) SLAUNCH(WR, true, false, false); \
-                       else if (sum_count && !exact) SLAUNCH(WR, false, true, true); else if (sum_count) SLAUNCH(WR, false, true, false); \
-                       else SLAUNCH(WR, false, false, false); } while (0)
-        if (R) PICKR(true); else PICKR(false);
-#undef PICKR
-#undef SLAUNCH
+        const bool f32 = sum_count != nullptr && deg == nullptr && !exact;
+        with_flags([&](auto WR, auto WD, auto WS, auto F32) {
+            if constexpr (!F32() || (!WD() && WS())) {        // (F32 exists for the sum alone)
+                so3::OpProjectAngle<4, WR(), WD(), WS(), F32()> op; op.in0 = M; op.in1 = Rtrue; op.out0 = R; op.deg = deg;
+                op.sum_count = sum_count; op.range_flag = range_flag; op.unit_scale = unit; op.count = static_cast<double>(B);
+                op.ws = ws; op.ws_slot0 = tile_wgs; op.store_count = store_count;
+                launch_rows<2, SO3_WPS_K14, SO3_BLOCK_K14>(op, nunits, s);
+            }
+        }, R != nullptr, deg != nullptr, sum_count != nullptr, f32);
     }
     return check_launch("so3_project_angle_error_f32");
 }
@@ -4149,8 +4158,7 @@ int so3_scale_bf16(const void *src, const float *factor, void *dst, int64_t n, v
 static int reduce_how(void *workspace, int64_t B, unsigned *grid) {
     // two workgroups' worth per CU, grid-stride: the ticket at the end is one same-address atomic per workgroup (~12 ns each,
     // serialised at the memory side -- 2048 of them were 7 us on top of a 37-us kernel)
-    const unsigned want = grid_for(B), cap = 2u * static_cast<unsigned>(device_cus());
-    *grid = B <= kSmallBatch ? 1u : (want < cap ? want : cap);
+    *grid = B <= kSmallBatch ? 1u : capped_grid(B, 2u * static_cast<unsigned>(device_cus()));
     return B <= kSmallBatch ? 1 : (workspace != nullptr ? 2 : 0);
 }
 
@@ -4165,12 +4173,12 @@ int so3_angle_error_v2_f64(const double *R1, const double *R2, double *deg, doub
     if (how == 0 && (sum_count || range_flag)) k_angle_init<<<1, 1, 0, s>>>(sum_count, range_flag, static_cast<double>(B));
     if (B == 0) return check_launch("so3_angle_error_v2_f64");
     SO3_CHECK_ARGS(R1 != nullptr && R2 != nullptr, "so3_angle_error_v2_f64: null pointer");
-    const double unit = radians ? 1.0 : 57.295779513082320876798154814105;
+    const double unit = radians ? 1.0 : kDegPerRad;
     const dim3 block(kBlock);
     so3::ReduceWs *ws = static_cast<so3::ReduceWs *>(workspace);
-#define LAUNCH(WD, WS) hipLaunchKernelGGL((k_angle_f64<0, WD, WS>), dim3(grid), block, 0, s, R1, R2, deg, sum_count, range_flag, unit, B, ws, how)
-    if (deg && sum_count) LAUNCH(true, true); else if (deg) LAUNCH(true, false); else if (sum_count) LAUNCH(false, true); else LAUNCH(false, false);
-#undef LAUNCH
+    with_flags([&](auto WD, auto WS) {
+        hipLaunchKernelGGL((k_angle_f64<0, WD(), WS()>), dim3(grid), block, 0, s, R1, R2, deg, sum_count, range_flag, unit, B, ws, how);
+    }, deg != nullptr, sum_count != nullptr);
     return check_launch("so3_angle_error_v2_f64");
 }
 
@@ -4179,8 +4187,7 @@ int so3_geodesic_f64(const double *R1, const double *R2, double *theta, int64_t 
     if (B == 0) return 0;
     SO3_CHECK_ARGS(R1 != nullptr && R2 != nullptr && theta != nullptr, "so3_geodesic_f64: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const unsigned want = grid_for(B);
-    hipLaunchKernelGGL((k_angle_f64<1, true, false>), dim3(want < 2048u ? want : 2048u), dim3(kBlock), 0, s, R1, R2, theta, nullptr, nullptr, 1.0, B, nullptr, 0);
+    hipLaunchKernelGGL((k_angle_f64<1, true, false>), dim3(capped_grid(B, 2048u)), dim3(kBlock), 0, s, R1, R2, theta, nullptr, nullptr, 1.0, B, nullptr, 0);
     return check_launch("so3_geodesic_f64");
 }
 
@@ -4193,10 +4200,9 @@ int so3_frob_loss_v2_f64(const double *Rpred, const double *Rtrue, double *dRpre
     unsigned grid = 1;
     const int how = B > 0 ? reduce_how(workspace, B, &grid) : 0;
     if (how == 0) {
-        hipError_t e = hipMemsetAsync(loss_sum, 0, sizeof(double), s);
-        if (e != hipSuccess) return fail((int)e, "so3_frob_loss_v2_f64: memset");
+        if (int e = zero_async(loss_sum, sizeof(double), s, "so3_frob_loss_v2_f64: memset")) return e;
         if (B == 0) {
-            if (loss_mean != nullptr) { e = hipMemsetAsync(loss_mean, 0, sizeof(double), s); if (e != hipSuccess) return fail((int)e, "so3_frob_loss_v2_f64: memset"); }
+            if (loss_mean != nullptr) if (int e = zero_async(loss_mean, sizeof(double), s, "so3_frob_loss_v2_f64: memset")) return e;
             return 0;
         }
     }
@@ -4204,8 +4210,9 @@ int so3_frob_loss_v2_f64(const double *Rpred, const double *Rtrue, double *dRpre
     const double inv_b = 1.0 / static_cast<double>(B);
     const dim3 block(kBlock);
     so3::ReduceWs *ws = static_cast<so3::ReduceWs *>(workspace);
-    if (dRpred) hipLaunchKernelGGL((k_frob_loss_f64<true>), dim3(grid), block, 0, s, Rpred, Rtrue, dRpred, loss_sum, loss_mean, B, inv_b, ws, how);
-    else hipLaunchKernelGGL((k_frob_loss_f64<false>), dim3(grid), block, 0, s, Rpred, Rtrue, dRpred, loss_sum, loss_mean, B, inv_b, ws, how);
+    with_flags([&](auto WG) {
+        hipLaunchKernelGGL((k_frob_loss_f64<WG()>), dim3(grid), block, 0, s, Rpred, Rtrue, dRpred, loss_sum, loss_mean, B, inv_b, ws, how);
+    }, dRpred != nullptr);
     if (how == 0 && loss_mean != nullptr) k_mean_from_sum_f64<<<1, 1, 0, s>>>(loss_sum, loss_mean, inv_b);
     return check_launch("so3_frob_loss_v2_f64");
 }
@@ -4214,15 +4221,12 @@ static int geodesic_f32(const float *R1, const float *R2, float *theta, double *
                         void *stream, const char *what) {
     SO3_CHECK_ARGS(B >= 0 && B <= SO3_MAX_B && eps >= 0.f && eps < 1.f, what);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int64_t nunits = B > 0 ? stream_units(B, {R1, R2, theta}) : 0;
-    const int64_t done = nunits * so3::kUnitRows, rest = B - done;
+    const Split sp(B, {R1, R2, theta});
+    const int64_t nunits = sp.nunits, done = sp.done, rest = sp.rest;
     const unsigned tile_wgs = rest > 0 ? grid_for(rest) : 0u;
     // with a workspace: ONE launch (two with a remainder) -- the last workgroup writes the sum and the reduced result
-    so3::ReduceWs *ws = sum != nullptr && use_workspace(workspace, nunits, tile_wgs) ? static_cast<so3::ReduceWs *>(workspace) : nullptr;
-    if (sum != nullptr && ws == nullptr) {
-        const hipError_t e = hipMemsetAsync(sum, 0, sizeof(double), s);
-        if (e != hipSuccess) return fail(static_cast<int>(e), what);
-    }
+    so3::ReduceWs *ws = sum != nullptr ? reduce_workspace(workspace, sp, tile_wgs) : nullptr;
+    if (sum != nullptr && ws == nullptr) if (int e = zero_async(sum, sizeof(double), s, what)) return e;
     const double scale = mean ? 1.0 / static_cast<double>(B) : 1.0;
     if (B > 0) {
         SO3_CHECK_ARGS(R1 != nullptr && R2 != nullptr && (theta != nullptr || sum != nullptr), what);
@@ -4230,8 +4234,9 @@ static int geodesic_f32(const float *R1, const float *R2, float *theta, double *
         if (rest > 0) {                                       // (first: its partials are in the workspace when the engine's last workgroup sums)
             const float *A1 = R1 + done * 9, *A2 = R2 + done * 9;
             const dim3 grid(tile_wgs), block(kBlock);
-            if (aligned16(A1) && aligned16(A2)) hipLaunchKernelGGL((k_geodesic_f32<true>), grid, block, 0, s, A1, A2, advance(theta, done), sum, lo, hi, rest, ws);
-            else hipLaunchKernelGGL((k_geodesic_f32<false>), grid, block, 0, s, A1, A2, advance(theta, done), sum, lo, hi, rest, ws);
+            with_flags([&](auto VE) {
+                hipLaunchKernelGGL((k_geodesic_f32<VE()>), grid, block, 0, s, A1, A2, advance(theta, done), sum, lo, hi, rest, ws);
+            }, aligned16(A1) && aligned16(A2));
         }
         if (nunits > 0) {
             if (sum) {
@@ -4268,7 +4273,7 @@ int so3_angle_bwd_f32(const float *R1, const float *R2, const void *grad, double
     const bool f64 = (flags & SO3_F64_MATH) != 0, scalar = (flags & SO3_GRAD_SCALAR) != 0;
     SO3_CHECK_ARGS((reinterpret_cast<uintptr_t>(grad) & (f64 ? 7u : 3u)) == 0, "so3_angle_bwd_f32: grad is not aligned to its element");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const double unit = (flags & SO3_RADIANS) != 0 ? 1.0 : 57.295779513082320876798154814105;
+    const double unit = (flags & SO3_RADIANS) != 0 ? 1.0 : kDegPerRad;
     // the clamp's bounds in the arithmetic of the spelling (torch.clamp's scalars on a float32 tensor are float32)
     const double lo = f64 ? -1.0 + eps : static_cast<double>(-1.f + static_cast<float>(eps));
     const double hi = f64 ? 1.0 - eps : static_cast<double>(1.f - static_cast<float>(eps));
@@ -4276,12 +4281,10 @@ int so3_angle_bwd_f32(const float *R1, const float *R2, const void *grad, double
     const bool both = dR1 != nullptr && dR2 != nullptr;
     const float *A = dR1 != nullptr ? R1 : R2, *Bm = dR1 != nullptr ? R2 : R1;
     float *d1 = dR1 != nullptr ? dR1 : dR2, *d2 = both ? dR2 : nullptr;
-#define GO(GR, F6, BO) angle_bwd_launch<GR, F6, BO>(A, Bm, grad, grad_div, unit, lo, hi, d1, d2, B, s)
-#define PICK(F6, PER) do { if (scalar) { if (both) GO(0, F6, true); else GO(0, F6, false); } \
-                           else { if (both) GO(PER, F6, true); else GO(PER, F6, false); } } while (0)
-    if (f64) PICK(true, 2); else PICK(false, 1);
-#undef PICK
-#undef GO
+    with_flags([&](auto F6, auto SC, auto BO) {
+        constexpr int kGrad = SC() ? 0 : (F6() ? 2 : 1);          // the upstream gradient: one scalar, or per row in float32 / float64
+        angle_bwd_launch<kGrad, F6(), BO()>(A, Bm, grad, grad_div, unit, lo, hi, d1, d2, B, s);
+    }, f64, scalar, both);
     return check_launch("so3_angle_bwd_f32");
 }
 
@@ -4293,9 +4296,8 @@ int so3_angle_bwd_f64(const double *R1, const double *R2, const double *grad, do
     if (B == 0) return 0;
     SO3_CHECK_ARGS(R1 != nullptr && R2 != nullptr && grad != nullptr && (dR1 != nullptr || dR2 != nullptr), "so3_angle_bwd_f64: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const double unit = (flags & SO3_RADIANS) != 0 ? 1.0 : 57.295779513082320876798154814105;
-    const unsigned want = grid_for(B);
-    hipLaunchKernelGGL(k_angle_bwd_f64, dim3(want < 2048u ? want : 2048u), dim3(kBlock), 0, s, R1, R2, grad, (flags & SO3_GRAD_SCALAR) != 0, grad_div,
+    const double unit = (flags & SO3_RADIANS) != 0 ? 1.0 : kDegPerRad;
+    hipLaunchKernelGGL(k_angle_bwd_f64, dim3(capped_grid(B, 2048u)), dim3(kBlock), 0, s, R1, R2, grad, (flags & SO3_GRAD_SCALAR) != 0, grad_div,
                        unit, -1.0 + eps, 1.0 - eps, dR1, dR2, B);
     return check_launch("so3_angle_bwd_f64");
 }
@@ -4305,17 +4307,14 @@ int so3_geodesic_eps_f64(const double *R1, const double *R2, double *theta, doub
     SO3_CHECK_ARGS(B >= 0 && B <= SO3_MAX_B && eps >= 0.0 && eps < 1.0, "so3_geodesic_eps_f64: B / eps");
     SO3_CHECK_ARGS(result == nullptr || sum != nullptr, "so3_geodesic_eps_f64: result needs the scratch `sum`");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (sum != nullptr) {
-        const hipError_t e = hipMemsetAsync(sum, 0, sizeof(double), s);
-        if (e != hipSuccess) return fail(static_cast<int>(e), "so3_geodesic_eps_f64: memset");
-    }
+    if (sum != nullptr) if (int e = zero_async(sum, sizeof(double), s, "so3_geodesic_eps_f64: memset")) return e;
     if (B > 0) {
         SO3_CHECK_ARGS(R1 != nullptr && R2 != nullptr && (theta != nullptr || sum != nullptr), "so3_geodesic_eps_f64: null pointer");
-        const unsigned want = grid_for(B);
-        const dim3 grid(want < 2048u ? want : 2048u), block(kBlock);
-        if (theta && sum) hipLaunchKernelGGL((k_angle_f64<2, true, true>), grid, block, 0, s, R1, R2, theta, sum, nullptr, 1.0, B, nullptr, 0, -1.0 + eps, 1.0 - eps);
-        else if (theta) hipLaunchKernelGGL((k_angle_f64<2, true, false>), grid, block, 0, s, R1, R2, theta, sum, nullptr, 1.0, B, nullptr, 0, -1.0 + eps, 1.0 - eps);
-        else hipLaunchKernelGGL((k_angle_f64<2, false, true>), grid, block, 0, s, R1, R2, theta, sum, nullptr, 1.0, B, nullptr, 0, -1.0 + eps, 1.0 - eps);
+        const dim3 grid(capped_grid(B, 2048u)), block(kBlock);
+        with_flags([&](auto WD, auto WS) {
+            if constexpr (WD() || WS())                         // (neither output: refused above)
+                hipLaunchKernelGGL((k_angle_f64<2, WD(), WS()>), grid, block, 0, s, R1, R2, theta, sum, nullptr, 1.0, B, nullptr, 0, -1.0 + eps, 1.0 - eps);
+        }, theta != nullptr, sum != nullptr);
     }
     // (torch's mean of an empty tensor is NaN, its sum 0)
     if (result != nullptr) k_mean_from_sum_f64<<<1, 1, 0, s>>>(sum, result, mean ? 1.0 / static_cast<double>(B) : 1.0);
@@ -4327,9 +4326,9 @@ int so3_ortho6d_fwd_f32(const float *X, float *R, int64_t B, void *stream) {
     if (B == 0) return 0;
     SO3_CHECK_ARGS(X != nullptr && R != nullptr, "so3_ortho6d_fwd_f32: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int64_t nunits = stream_units(B, {X, R});
-    if (nunits > 0) { so3::OpOrtho6d op; op.in0 = X; op.out0 = R; launch_rows<2, 4, 256>(op, nunits, s); }
-    const int64_t done = nunits * so3::kUnitRows, rest = B - done;
+    const Split sp(B, {X, R});
+    const int64_t done = sp.done, rest = sp.rest;
+    if (sp.nunits > 0) { so3::OpOrtho6d op; op.in0 = X; op.out0 = R; launch_rows<2, 4, 256>(op, sp.nunits, s); }
     if (rest > 0) hipLaunchKernelGGL((k_ortho6d_rows<false>), dim3(grid_for(rest)), dim3(kBlock), 0, s, X + done * 6, nullptr, R + done * 9, rest);
     return check_launch("so3_ortho6d_fwd_f32");
 }
@@ -4339,9 +4338,9 @@ int so3_ortho6d_bwd_f32(const float *X, const float *G, float *dX, int64_t B, vo
     if (B == 0) return 0;
     SO3_CHECK_ARGS(X != nullptr && G != nullptr && dX != nullptr, "so3_ortho6d_bwd_f32: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int64_t nunits = stream_units(B, {X, G, dX});
-    if (nunits > 0) { so3::OpOrtho6dBwd op; op.in0 = X; op.in1 = G; op.out0 = dX; launch_rows<2, 4, 256>(op, nunits, s); }
-    const int64_t done = nunits * so3::kUnitRows, rest = B - done;
+    const Split sp(B, {X, G, dX});
+    const int64_t done = sp.done, rest = sp.rest;
+    if (sp.nunits > 0) { so3::OpOrtho6dBwd op; op.in0 = X; op.in1 = G; op.out0 = dX; launch_rows<2, 4, 256>(op, sp.nunits, s); }
     if (rest > 0) hipLaunchKernelGGL((k_ortho6d_rows<true>), dim3(grid_for(rest)), dim3(kBlock), 0, s, X + done * 6, G + done * 9, dX + done * 6, rest);
     return check_launch("so3_ortho6d_bwd_f32");
 }
@@ -4433,10 +4432,7 @@ int so3_add_s_fwd_f32(const float *Tgt, const float *Tpred, const float *points,
     SO3_CHECK_ARGS(B == 0 || (Tgt != nullptr && Tpred != nullptr && points != nullptr && point_dist != nullptr), "so3_add_s_fwd_f32: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (B == 0) {
-        if (loss_sum != nullptr) {
-            const hipError_t e = hipMemsetAsync(loss_sum, 0, sizeof(double), s);
-            if (e != hipSuccess) return fail(static_cast<int>(e), "so3_add_s_fwd_f32");
-        }
+        if (loss_sum != nullptr) if (int e = zero_async(loss_sum, sizeof(double), s, "so3_add_s_fwd_f32")) return e;
         return 0;
     }
     return launch_add_s<false>(Tgt, Tpred, points, point_dist, nearest, dists, loss_sum, B, N, s, "so3_add_s_fwd_f32");
@@ -4448,8 +4444,7 @@ int so3_add_s_bwd_f32(const float *Tgt, const float *Tpred, const float *points,
     SO3_CHECK_ARGS(B == 0 || (Tgt != nullptr && Tpred != nullptr && points != nullptr && nearest != nullptr && dTpred != nullptr),
                    "so3_add_s_bwd_f32: null pointer");
     if (B == 0) return 0;
-    const int64_t blocks = std::min<int64_t>((B + kBlock / 64 - 1) / (kBlock / 64), static_cast<int64_t>(device_cus()) * 8);
-    hipLaunchKernelGGL(k_add_s_bwd, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), Tgt, Tpred, points,
+    hipLaunchKernelGGL(k_add_s_bwd, dim3(wave_rows_grid(B, 8)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), Tgt, Tpred, points,
                        nearest, grad_rows, grad_scale, dTpred, B, N);
     return check_launch("so3_add_s_bwd_f32");
 }
@@ -4499,13 +4494,13 @@ int so3_icp_f32(const float *P, const float *Q, int64_t q_stride, const float *w
     }
     float *poses[2] = {static_cast<float *>(workspace), static_cast<float *>(workspace) + B * 12};
     float *rec = static_cast<float *>(workspace) + B * 24;
-    const int64_t fin_blocks = std::min<int64_t>((B + kBlock / 64 - 1) / (kBlock / 64), static_cast<int64_t>(device_cus()) * 16);
+    const unsigned fin_blocks = wave_rows_grid(B, 16);
     const float *cur = T_init;
     for (int32_t k = 0; k < iterations; ++k) {
         const bool last = k + 1 == iterations;
         float *next = poses[k & 1];
         launch_icp_step<true>(P, Q, q_stride, w, cur, max_distance, rec, last ? dist : nullptr, last ? nearest : nullptr, B, N, M, u, chunks, s);
-        hipLaunchKernelGGL(k_icp_finish, dim3(static_cast<unsigned>(fin_blocks)), block, 0, s, P, Q, q_stride, rec, cur, next, last ? R : nullptr,
+        hipLaunchKernelGGL(k_icp_finish, dim3(fin_blocks), block, 0, s, P, Q, q_stride, rec, cur, next, last ? R : nullptr,
                            last ? t : nullptr, rmse != nullptr ? rmse + k * B : nullptr, inliers != nullptr ? inliers + k * B : nullptr, B, N, chunks);
         cur = next;
     }
@@ -4519,23 +4514,17 @@ int so3_fps_f32(const float *xyz, const int32_t *start, int32_t *out, int64_t B,
     SO3_CHECK_ARGS(xyz != nullptr && start != nullptr && out != nullptr, "so3_fps_f32: null pointer");
     int ppl, block;
     so3::fps_shape(N, ppl, block);
-    static thread_local char name[32];
-    snprintf(name, sizeof name, "k_fps<%d, %d>", ppl, block);
-    g_last_kernel = name;
     const dim3 grid(static_cast<unsigned>(std::min<int64_t>(B, kFpsMaxGrid)));
     hipStream_t s = static_cast<hipStream_t>(stream);
-#define FPS(PP, BB) hipLaunchKernelGGL((k_fps<PP, BB>), grid, dim3(BB), 0, s, xyz, start, out, B, N, npoint)
-    switch (block * 100 + ppl) {
-        case 25601: FPS(1, 256); break;
-        case 25602: FPS(2, 256); break;
-        case 25604: FPS(4, 256); break;
-        case 25608: FPS(8, 256); break;
-        case 102404: FPS(4, 1024); break;
-        case 102408: FPS(8, 1024); break;
-        case 102416: FPS(16, 1024); break;
-        default: return fail(SO3_ERR_INVALID, "so3_fps_f32: no kernel for this N");
-    }
-#undef FPS
+    auto launch = [&](auto PP, auto BB) {
+        name_kernel("k_fps", PP, BB);
+        hipLaunchKernelGGL((k_fps<PP(), BB()>), grid, dim3(BB()), 0, s, xyz, start, out, B, N, npoint);
+    };
+    // the shapes so3::fps_shape hands out: up to eight points per lane of 256, then four to sixteen of 1024
+    const bool found = block == 256    ? with_value<1, 2, 4, 8>(ppl, [&](auto PP) { launch(PP, std::integral_constant<int, 256>{}); })
+                       : block == 1024 ? with_value<4, 8, 16>(ppl, [&](auto PP) { launch(PP, std::integral_constant<int, 1024>{}); })
+                                       : false;
+    if (!found) return fail(SO3_ERR_INVALID, "so3_fps_f32: no kernel for this N");
     return check_launch("so3_fps_f32");
 }
 
@@ -4546,12 +4535,12 @@ int so3_ball_query_f32(const float *xyz, const float *centres, float radius, int
     if (B == 0) return 0;
     SO3_CHECK_ARGS(xyz != nullptr && centres != nullptr && idx != nullptr, "so3_ball_query_f32: null pointer");
     const int32_t width = std::min(nsample, N);
-    const int64_t blocks = (B * S + kBlock / 64 - 1) / (kBlock / 64);
-    const dim3 grid(static_cast<unsigned>(std::min<int64_t>(blocks, static_cast<int64_t>(device_cus()) * 32))), block(kBlock);
+    const dim3 grid(wave_rows_grid(B * S, 32)), block(kBlock);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    g_last_kernel = count != nullptr ? "k_ball_query<true>" : "k_ball_query<false>";
-    if (count != nullptr) hipLaunchKernelGGL(k_ball_query<true>, grid, block, 0, s, xyz, centres, radius, width, idx, count, B, N, S);
-    else hipLaunchKernelGGL(k_ball_query<false>, grid, block, 0, s, xyz, centres, radius, width, idx, count, B, N, S);
+    with_flags([&](auto COUNT) {
+        name_kernel("k_ball_query", COUNT);
+        hipLaunchKernelGGL(k_ball_query<COUNT()>, grid, block, 0, s, xyz, centres, radius, width, idx, count, B, N, S);
+    }, count != nullptr);
     return check_launch("so3_ball_query_f32");
 }
 
@@ -4564,12 +4553,13 @@ int so3_three_nn_f32(const float *unknown, const float *known, float *dist2, int
     const int32_t chunks = (N + kBlock / wpp - 1) / (kBlock / wpp);
     const dim3 grid(static_cast<unsigned>(std::min<int64_t>(B * chunks, kThreeMaxGrid))), block(kBlock);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool wt = weight != nullptr;
-    g_last_kernel = wpp == 4 ? (wt ? "k_three_nn<4, true>" : "k_three_nn<4, false>") : (wt ? "k_three_nn<1, true>" : "k_three_nn<1, false>");
-#define NN3(WW, TT) hipLaunchKernelGGL((k_three_nn<WW, TT>), grid, block, 0, s, unknown, known, dist2, idx, weight, B, N, S, chunks)
-    if (wpp == 4) { if (wt) NN3(4, true); else NN3(4, false); }
-    else { if (wt) NN3(1, true); else NN3(1, false); }
-#undef NN3
+    with_flags([&](auto WEIGHT) {
+        constexpr bool kWeight = WEIGHT();
+        with_value<4, 1>(wpp, [&](auto WPP) {
+            name_kernel("k_three_nn", WPP, kWeight);
+            hipLaunchKernelGGL((k_three_nn<WPP(), kWeight>), grid, block, 0, s, unknown, known, dist2, idx, weight, B, N, S, chunks);
+        });
+    }, weight != nullptr);
     return check_launch("so3_three_nn_f32");
 }
 
@@ -4584,16 +4574,16 @@ int so3_three_interpolate_f32(const float *feat, const int32_t *idx, const float
     while (gw > 1 && gw / 2 >= D) gw >>= 1;
     int64_t blocks;
     if (channels_first) {
-        g_last_kernel = "k_three_interp<true>";
         blocks = B * ((N + kBlock - 1) / kBlock) * ((D + kThreeCfChannels - 1) / kThreeCfChannels);
     } else {
-        g_last_kernel = "k_three_interp<false>";
         const int64_t rows_per_block = (kBlock / 64) * (64 / gw);
         blocks = (B * N + rows_per_block - 1) / rows_per_block;
     }
     const dim3 grid(static_cast<unsigned>(std::min<int64_t>(blocks, kThreeMaxGrid))), block(kBlock);
-    if (channels_first) hipLaunchKernelGGL(k_three_interp<true>, grid, block, 0, s, feat, idx, weight, out, B, N, S, D, gw);
-    else hipLaunchKernelGGL(k_three_interp<false>, grid, block, 0, s, feat, idx, weight, out, B, N, S, D, gw);
+    with_flags([&](auto CF) {
+        name_kernel("k_three_interp", CF);
+        hipLaunchKernelGGL(k_three_interp<CF()>, grid, block, 0, s, feat, idx, weight, out, B, N, S, D, gw);
+    }, channels_first != 0);
     return check_launch("so3_three_interpolate_f32");
 }
 
@@ -4626,16 +4616,16 @@ int so3_group_points_f32(const float *xyz, const float *centres, const float *fe
     while (gw > 1 && gw / 2 >= C) gw >>= 1;
     int64_t blocks;
     if (channels_first) {
-        g_last_kernel = "k_group_fwd<true>";
         blocks = B * K * ((S + kBlock - 1) / kBlock) * ((C + so3::kGroupFwdCfChannels - 1) / so3::kGroupFwdCfChannels);
     } else {
-        g_last_kernel = "k_group_fwd<false>";
         const int64_t rows_per_block = (kBlock / 64) * (64 / gw);
         blocks = (B * S * K + rows_per_block - 1) / rows_per_block;
     }
     const dim3 grid(static_cast<unsigned>(std::min<int64_t>(blocks, kThreeMaxGrid))), block(kBlock);
-    if (channels_first) hipLaunchKernelGGL(k_group_fwd<true>, grid, block, 0, s, xyz, centres, feat, idx, out, features_first, B, N, S, K, D, gw);
-    else hipLaunchKernelGGL(k_group_fwd<false>, grid, block, 0, s, xyz, centres, feat, idx, out, features_first, B, N, S, K, D, gw);
+    with_flags([&](auto CF) {
+        name_kernel("k_group_fwd", CF);
+        hipLaunchKernelGGL(k_group_fwd<CF()>, grid, block, 0, s, xyz, centres, feat, idx, out, features_first, B, N, S, K, D, gw);
+    }, channels_first != 0);
     return check_launch("so3_group_points_f32");
 }
 
@@ -4651,23 +4641,22 @@ int so3_group_points_bwd_f32(const float *grad_out, const int32_t *idx, float *g
     if (D == 0) grad_feat = nullptr;
     if (grad_centres != nullptr) {
         const dim3 grid(static_cast<unsigned>(std::min<int64_t>((B * S + kBlock - 1) / kBlock, kThreeMaxGrid)));
-        g_last_kernel = channels_first ? "k_group_centres_bwd<true>" : "k_group_centres_bwd<false>";
-        if (channels_first) hipLaunchKernelGGL(k_group_centres_bwd<true>, grid, block, 0, s, grad_out, idx, grad_centres, features_first, B, N, S, K, D);
-        else hipLaunchKernelGGL(k_group_centres_bwd<false>, grid, block, 0, s, grad_out, idx, grad_centres, features_first, B, N, S, K, D);
+        with_flags([&](auto CF) {
+            name_kernel("k_group_centres_bwd", CF);
+            hipLaunchKernelGGL(k_group_centres_bwd<CF()>, grid, block, 0, s, grad_out, idx, grad_centres, features_first, B, N, S, K, D);
+        }, channels_first != 0);
     }
     if (grad_xyz != nullptr || grad_feat != nullptr) {
         const bool narrow = so3::group_bwd_narrow(D);
         const int owners = narrow ? so3::kGroupNarrowOwners : so3::kGroupWideOwners, cw = narrow ? so3::kGroupNarrowC : so3::kGroupWideChannels;
         const int64_t blocks = B * ((N + owners - 1) / owners) * ((3 + D + cw - 1) / cw);
         const dim3 grid(static_cast<unsigned>(std::min<int64_t>(blocks, kThreeMaxGrid)));
-#define GROUP_BWD(CF, CW, R)                                                                                                               \
-    do {                                                                                                                                   \
-        g_last_kernel = "k_group_bwd<" #CF ", " #CW ", " #R ">";                                                                            \
-        hipLaunchKernelGGL((k_group_bwd<CF, CW, R>), grid, block, 0, s, grad_out, idx, grad_xyz, grad_feat, features_first, B, N, S, K, D); \
-    } while (0)
-        if (narrow) { if (channels_first) GROUP_BWD(true, 8, 2); else GROUP_BWD(false, 8, 2); }
-        else { if (channels_first) GROUP_BWD(true, 64, 16); else GROUP_BWD(false, 64, 16); }
-#undef GROUP_BWD
+        with_flags([&](auto CF, auto NARROW) {
+            // channels per owner group and owners per lane (so3_device.h, k_group_bwd<CF, CW, R>)
+            constexpr int kCw = NARROW() ? so3::kGroupNarrowC : so3::kGroupWideChannels, kR = NARROW() ? 2 : 16;
+            name_kernel("k_group_bwd", CF, kCw, kR);
+            hipLaunchKernelGGL((k_group_bwd<CF(), kCw, kR>), grid, block, 0, s, grad_out, idx, grad_xyz, grad_feat, features_first, B, N, S, K, D);
+        }, channels_first != 0, narrow);
     }
     return check_launch("so3_group_points_bwd_f32");
 }
@@ -4684,14 +4673,10 @@ int so3_rotate_clouds_f32(const float *P, const float *R, float *out, int transp
     SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 0 && N <= 150000000, "so3_rotate_clouds_f32: B/N");
     if (B == 0 || N == 0) return 0;
     SO3_CHECK_ARGS(P != nullptr && R != nullptr && out != nullptr, "so3_rotate_clouds_f32: null pointer");
-    int64_t per_wave = B / (static_cast<int64_t>(device_cus()) * 16);
-    if (per_wave < 1) per_wave = 1;
-    if (per_wave > 64) per_wave = 64;
-    const int64_t waves = (B + per_wave - 1) / per_wave;
-    const dim3 grid(static_cast<unsigned>((waves + (kBlock / 64) - 1) / (kBlock / 64))), block(kBlock);
+    const CloudShape shape = cloud_shape(B);
+    const dim3 grid(static_cast<unsigned>(shape.blocks)), block(kBlock);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (transposed) hipLaunchKernelGGL((k_rotate_clouds<true>), grid, block, 0, s, P, R, out, B, N, static_cast<int>(per_wave));
-    else hipLaunchKernelGGL((k_rotate_clouds<false>), grid, block, 0, s, P, R, out, B, N, static_cast<int>(per_wave));
+    with_flags([&](auto T) { hipLaunchKernelGGL((k_rotate_clouds<T()>), grid, block, 0, s, P, R, out, B, N, shape.per_wave); }, transposed != 0);
     return check_launch("so3_rotate_clouds_f32");
 }
 
@@ -4699,16 +4684,13 @@ int so3_pc_normalize_f32(const float *P, float *out, float *centroid, float *sca
     SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= 150000000, "so3_pc_normalize_f32: B/N");
     if (B == 0) return 0;
     SO3_CHECK_ARGS(P != nullptr && out != nullptr, "so3_pc_normalize_f32: null pointer");
-    int64_t per_wave = B / (static_cast<int64_t>(device_cus()) * 16);
-    if (per_wave < 1) per_wave = 1;
-    if (per_wave > 64) per_wave = 64;
-    const int64_t waves = (B + per_wave - 1) / per_wave;
-    const dim3 grid(static_cast<unsigned>((waves + (kBlock / 64) - 1) / (kBlock / 64))), block(kBlock);
+    const CloudShape shape = cloud_shape(B);
+    const dim3 grid(static_cast<unsigned>(shape.blocks)), block(kBlock);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int pw = static_cast<int>(per_wave);
-    if (N <= 256) hipLaunchKernelGGL((k_pc_normalize<4>), grid, block, 0, s, P, out, centroid, scale, B, N, pw);
-    else if (N <= 1024) hipLaunchKernelGGL((k_pc_normalize<16>), grid, block, 0, s, P, out, centroid, scale, B, N, pw);
-    else hipLaunchKernelGGL((k_pc_normalize<0>), grid, block, 0, s, P, out, centroid, scale, B, N, pw);
+    // the points a lane holds in registers between the two passes (N <= 64 * HOLD), or 0: the cloud is read twice
+    with_value<4, 16, 0>(N <= 256 ? 4 : (N <= 1024 ? 16 : 0), [&](auto HOLD) {
+        hipLaunchKernelGGL((k_pc_normalize<HOLD()>), grid, block, 0, s, P, out, centroid, scale, B, N, shape.per_wave);
+    });
     return check_launch("so3_pc_normalize_f32");
 }
 
@@ -4764,9 +4746,9 @@ int so3_se3_update_f32(const float *out12, const float *Tinit, float *Tpred, flo
     if (B == 0) return 0;
     SO3_CHECK_ARGS(out12 != nullptr && Tinit != nullptr && Tpred != nullptr, "so3_se3_update_f32: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int64_t nunits = stream_units(B, {out12, Tinit, Tpred});
-    if (nunits > 0) { so3::OpSe3Update op; op.in0 = out12; op.in1 = Tinit; op.out0 = Tpred; op.inv_fx = 1.f / fx; op.inv_fy = 1.f / fy; launch_rows<2, 2, 256>(op, nunits, s); }
-    const int64_t done = nunits * so3::kUnitRows, rest = B - done;
+    const Split sp(B, {out12, Tinit, Tpred});
+    const int64_t done = sp.done, rest = sp.rest;
+    if (sp.nunits > 0) { so3::OpSe3Update op; op.in0 = out12; op.in1 = Tinit; op.out0 = Tpred; op.inv_fx = 1.f / fx; op.inv_fy = 1.f / fy; launch_rows<2, 2, 256>(op, sp.nunits, s); }
     if (rest > 0) hipLaunchKernelGGL((k_se3_rows<false>), dim3(grid_for(rest)), dim3(kBlock), 0, s, out12 + done * 12, Tinit + done * 16, nullptr, Tpred + done * 16, 1.f / fx, 1.f / fy, rest);
     return check_launch("so3_se3_update_f32");
 }
@@ -4776,9 +4758,9 @@ int so3_se3_update_bwd_f32(const float *out12, const float *Tinit, const float *
     if (B == 0) return 0;
     SO3_CHECK_ARGS(out12 != nullptr && Tinit != nullptr && G != nullptr && dout12 != nullptr, "so3_se3_update_bwd_f32: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int64_t nunits = stream_units(B, {out12, Tinit, G, dout12});
-    if (nunits > 0) { so3::OpSe3UpdateBwd op; op.in0 = out12; op.in1 = Tinit; op.in2 = G; op.out0 = dout12; op.inv_fx = 1.f / fx; op.inv_fy = 1.f / fy; launch_rows<1, 3, 256>(op, nunits, s); }
-    const int64_t done = nunits * so3::kUnitRows, rest = B - done;
+    const Split sp(B, {out12, Tinit, G, dout12});
+    const int64_t done = sp.done, rest = sp.rest;
+    if (sp.nunits > 0) { so3::OpSe3UpdateBwd op; op.in0 = out12; op.in1 = Tinit; op.in2 = G; op.out0 = dout12; op.inv_fx = 1.f / fx; op.inv_fy = 1.f / fy; launch_rows<1, 3, 256>(op, sp.nunits, s); }
     if (rest > 0) hipLaunchKernelGGL((k_se3_rows<true>), dim3(grid_for(rest)), dim3(kBlock), 0, s, out12 + done * 12, Tinit + done * 16, G + done * 16, dout12 + done * 12, 1.f / fx, 1.f / fy, rest);
     return check_launch("so3_se3_update_bwd_f32");
 }
@@ -4796,17 +4778,15 @@ int so3_kabsch_synth_f32(const float *P, const float *Rgt, float sigma, uint32_t
     SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 0 && N <= 150000000, "so3_kabsch_synth_f32: B/N");
     if (B == 0) return 0;
     SO3_CHECK_ARGS(R != nullptr && Rgt != nullptr && (N == 0 || P != nullptr), "so3_kabsch_synth_f32: null pointer");
-    int64_t cpw = B / (static_cast<int64_t>(device_cus()) * 16);
-    if (cpw < 1) cpw = 1;
-    if (cpw > 64) cpw = 64;
-    const int64_t waves = (B + cpw - 1) / cpw;
-    const int64_t blocks = (waves + (kBlock / 64) - 1) / (kBlock / 64);
-    if (N <= kSynthFew)      // a few points a cloud: q rounded once (k_kabsch_synth_few)
-        hipLaunchKernelGGL((sigma != 0.f ? k_kabsch_synth_few<true> : k_kabsch_synth_few<false>), dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0,
-                           static_cast<hipStream_t>(stream), P, Rgt, sigma, seed, R, H, B, N, static_cast<int>(cpw));
-    else
-        hipLaunchKernelGGL((sigma != 0.f ? k_kabsch_synth<true> : k_kabsch_synth<false>), dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), P, Rgt, sigma,
-                           seed, R, H, B, N, static_cast<int>(cpw));
+    const CloudShape shape = cloud_shape(B);
+    const dim3 grid(static_cast<unsigned>(shape.blocks)), block(kBlock);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    with_flags([&](auto NOISE) {
+        if (N <= kSynthFew)      // a few points a cloud: q rounded once (k_kabsch_synth_few)
+            hipLaunchKernelGGL((k_kabsch_synth_few<NOISE()>), grid, block, 0, s, P, Rgt, sigma, seed, R, H, B, N, shape.per_wave);
+        else
+            hipLaunchKernelGGL((k_kabsch_synth<NOISE()>), grid, block, 0, s, P, Rgt, sigma, seed, R, H, B, N, shape.per_wave);
+    }, sigma != 0.f);
     return check_launch("so3_kabsch_synth_f32");
 }
 
@@ -4815,14 +4795,9 @@ int so3_kabsch_f32(const float *P, const float *Q, float *R, float *H, int64_t B
     if (B == 0) return 0;
     SO3_CHECK_ARGS(R != nullptr && (N == 0 || (P != nullptr && Q != nullptr)), "so3_kabsch_f32: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // enough waves to fill 256 CUs x 16 waves, at most 64 clouds per wave (one per lane for the SVD)
-    int64_t cpw = B / (static_cast<int64_t>(device_cus()) * 16);
-    if (cpw < 1) cpw = 1;
-    if (cpw > 64) cpw = 64;
-    const int64_t waves = (B + cpw - 1) / cpw;
-    const int64_t blocks = (waves + (kBlock / 64) - 1) / (kBlock / 64);
-    SO3_CHECK_ARGS(blocks <= 2147483647, "so3_kabsch_f32: B too large");
-    hipLaunchKernelGGL(k_kabsch, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s, P, Q, R, H, B, N, static_cast<int>(cpw));
+    const CloudShape shape = cloud_shape(B);
+    SO3_CHECK_ARGS(shape.blocks <= 2147483647, "so3_kabsch_f32: B too large");
+    hipLaunchKernelGGL(k_kabsch, dim3(static_cast<unsigned>(shape.blocks)), dim3(kBlock), 0, s, P, Q, R, H, B, N, shape.per_wave);
     return check_launch("so3_kabsch_f32");
 }
 
@@ -4833,27 +4808,14 @@ int so3_kabsch_bwd_f32(const float *P, const float *Q, const float *H, const flo
     SO3_CHECK_ARGS(H != nullptr && (N == 0 || (P != nullptr && Q != nullptr)), "so3_kabsch_bwd_f32: null pointer");
     if (N == 0 || (dP == nullptr && dQ == nullptr)) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int64_t cpw = B / (static_cast<int64_t>(device_cus()) * 16);          // k_kabsch's launch shape
-    if (cpw < 1) cpw = 1;
-    if (cpw > 64) cpw = 64;
-    const int64_t waves = (B + cpw - 1) / cpw;
-    const int64_t blocks = (waves + (kBlock / 64) - 1) / (kBlock / 64);
-    SO3_CHECK_ARGS(blocks <= 2147483647, "so3_kabsch_bwd_f32: B too large");
-    const dim3 grid(static_cast<unsigned>(blocks)), block(kBlock);
-    const int c = static_cast<int>(cpw);
-    if (dP != nullptr && dQ != nullptr) hipLaunchKernelGGL((k_kabsch_bwd<true, true>), grid, block, 0, s, P, Q, H, gR, gH, dP, dQ, B, N, c);
-    else if (dP != nullptr) hipLaunchKernelGGL((k_kabsch_bwd<true, false>), grid, block, 0, s, P, Q, H, gR, gH, dP, dQ, B, N, c);
-    else hipLaunchKernelGGL((k_kabsch_bwd<false, true>), grid, block, 0, s, P, Q, H, gR, gH, dP, dQ, B, N, c);
+    const CloudShape shape = cloud_shape(B);
+    SO3_CHECK_ARGS(shape.blocks <= 2147483647, "so3_kabsch_bwd_f32: B too large");
+    const dim3 grid(static_cast<unsigned>(shape.blocks)), block(kBlock);
+    with_flags([&](auto DP, auto DQ) {
+        if constexpr (DP() || DQ())                              // (no gradient asked for: returned above)
+            hipLaunchKernelGGL((k_kabsch_bwd<DP(), DQ()>), grid, block, 0, s, P, Q, H, gR, gH, dP, dQ, B, N, shape.per_wave);
+    }, dP != nullptr, dQ != nullptr);
     return check_launch("so3_kabsch_bwd_f32");
-}
-
-// k_kabsch's launch shape: enough waves to fill the CUs x 16 waves, at most 64 clouds per wave (one per lane for the SVD)
-static int64_t kabsch_shape(int64_t B, int64_t &cpw) {
-    cpw = B / (static_cast<int64_t>(device_cus()) * 16);
-    if (cpw < 1) cpw = 1;
-    if (cpw > 64) cpw = 64;
-    const int64_t waves = (B + cpw - 1) / cpw;
-    return (waves + (kBlock / 64) - 1) / (kBlock / 64);
 }
 
 int so3_rigid_align_f32(const float *P, const float *Q, const float *w, float *R, float *t, float *H, float *stats, int64_t B, int32_t N,
@@ -4861,11 +4823,12 @@ int so3_rigid_align_f32(const float *P, const float *Q, const float *w, float *R
     SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 40) && N >= 0 && N <= 150000000, "so3_rigid_align_f32: B/N");
     if (B == 0) return 0;
     SO3_CHECK_ARGS(R != nullptr && t != nullptr && (N == 0 || (P != nullptr && Q != nullptr)), "so3_rigid_align_f32: null pointer");
-    int64_t cpw;
-    const int64_t blocks = kabsch_shape(B, cpw);
-    SO3_CHECK_ARGS(blocks <= 2147483647, "so3_rigid_align_f32: B too large");
-    hipLaunchKernelGGL((w != nullptr ? k_rigid_align<true> : k_rigid_align<false>), dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0,
-                       static_cast<hipStream_t>(stream), P, Q, w, R, t, H, stats, B, N, static_cast<int>(cpw));
+    const CloudShape shape = cloud_shape(B);
+    SO3_CHECK_ARGS(shape.blocks <= 2147483647, "so3_rigid_align_f32: B too large");
+    with_flags([&](auto WEIGHTED) {
+        hipLaunchKernelGGL((k_rigid_align<WEIGHTED()>), dim3(static_cast<unsigned>(shape.blocks)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
+                           P, Q, w, R, t, H, stats, B, N, shape.per_wave);
+    }, w != nullptr);
     return check_launch("so3_rigid_align_f32");
 }
 
@@ -4877,24 +4840,15 @@ int so3_rigid_align_bwd_f32(const float *P, const float *Q, const float *w, cons
     SO3_CHECK_ARGS(H != nullptr && R != nullptr && stats != nullptr && (N == 0 || (P != nullptr && Q != nullptr)),
                    "so3_rigid_align_bwd_f32: null pointer");
     if (N == 0 || (dP == nullptr && dQ == nullptr && dw == nullptr)) return 0;
-    int64_t cpw;
-    const int64_t blocks = kabsch_shape(B, cpw);
-    SO3_CHECK_ARGS(blocks <= 2147483647, "so3_rigid_align_bwd_f32: B too large");
-    const dim3 grid(static_cast<unsigned>(blocks)), block(kBlock);
+    const CloudShape shape = cloud_shape(B);
+    SO3_CHECK_ARGS(shape.blocks <= 2147483647, "so3_rigid_align_bwd_f32: B too large");
+    const dim3 grid(static_cast<unsigned>(shape.blocks)), block(kBlock);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int c = static_cast<int>(cpw);
-#define SO3_ALIGN_BWD(DP, DQ, DW) \
-    hipLaunchKernelGGL((k_rigid_align_bwd<DP, DQ, DW>), grid, block, 0, s, P, Q, w, H, R, stats, gR, gt, gH, dP, dQ, dw, B, N, c)
-    switch ((dP != nullptr ? 4 : 0) | (dQ != nullptr ? 2 : 0) | (dw != nullptr ? 1 : 0)) {
-        case 7: SO3_ALIGN_BWD(true, true, true); break;
-        case 6: SO3_ALIGN_BWD(true, true, false); break;
-        case 5: SO3_ALIGN_BWD(true, false, true); break;
-        case 4: SO3_ALIGN_BWD(true, false, false); break;
-        case 3: SO3_ALIGN_BWD(false, true, true); break;
-        case 2: SO3_ALIGN_BWD(false, true, false); break;
-        default: SO3_ALIGN_BWD(false, false, true); break;
-    }
-#undef SO3_ALIGN_BWD
+    with_flags([&](auto DP, auto DQ, auto DW) {
+        if constexpr (DP() || DQ() || DW())                      // (no gradient asked for: returned above)
+            hipLaunchKernelGGL((k_rigid_align_bwd<DP(), DQ(), DW()>), grid, block, 0, s, P, Q, w, H, R, stats, gR, gt, gH, dP, dQ, dw, B, N,
+                               shape.per_wave);
+    }, dP != nullptr, dQ != nullptr, dw != nullptr);
     return check_launch("so3_rigid_align_bwd_f32");
 }
 
@@ -4906,24 +4860,13 @@ int so3_rotate_clouds_bwd_f32(const float *P, const float *R, const float *G, fl
     SO3_CHECK_ARGS((dP == nullptr || R != nullptr) && (N == 0 || (G != nullptr && (dR == nullptr || P != nullptr))),
                    "so3_rotate_clouds_bwd_f32: null pointer");                 // R for dP, P for dR, G for either
     if (dR == nullptr && dP == nullptr) return 0;
-    int64_t per_wave = B / (static_cast<int64_t>(device_cus()) * 16);
-    if (per_wave < 1) per_wave = 1;
-    if (per_wave > 64) per_wave = 64;
-    const int64_t waves = (B + per_wave - 1) / per_wave;
-    const dim3 grid(static_cast<unsigned>((waves + (kBlock / 64) - 1) / (kBlock / 64))), block(kBlock);
+    const CloudShape shape = cloud_shape(B);
+    const dim3 grid(static_cast<unsigned>(shape.blocks)), block(kBlock);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int pw = static_cast<int>(per_wave);
-#define SO3_ROT_BWD(T, WP, WR) hipLaunchKernelGGL((k_rotate_clouds_bwd<T, WP, WR>), grid, block, 0, s, P, R, G, dP, dR, B, N, pw)
-    if (transposed) {
-        if (dP != nullptr && dR != nullptr) SO3_ROT_BWD(true, true, true);
-        else if (dP != nullptr) SO3_ROT_BWD(true, true, false);
-        else SO3_ROT_BWD(true, false, true);
-    } else {
-        if (dP != nullptr && dR != nullptr) SO3_ROT_BWD(false, true, true);
-        else if (dP != nullptr) SO3_ROT_BWD(false, true, false);
-        else SO3_ROT_BWD(false, false, true);
-    }
-#undef SO3_ROT_BWD
+    with_flags([&](auto T, auto WP, auto WR) {
+        if constexpr (WP() || WR())                              // (no gradient asked for: returned above)
+            hipLaunchKernelGGL((k_rotate_clouds_bwd<T(), WP(), WR()>), grid, block, 0, s, P, R, G, dP, dR, B, N, shape.per_wave);
+    }, transposed != 0, dP != nullptr, dR != nullptr);
     return check_launch("so3_rotate_clouds_bwd_f32");
 }
 
@@ -4942,9 +4885,9 @@ int so3_rotate_clouds_bwd_f32(const float *P, const float *R, const float *G, fl
 
 template <bool MULTI>
 static void sym_angle_launch(so3::OpSymAngle<MULTI> op, int64_t B, hipStream_t s) {
-    const int64_t nunits = stream_units(B, {op.in0, op.in1, op.in2, op.deg, op.index});
-    if (nunits > 0) launch_rows<1, 4, 1024>(op, nunits, s);
-    const int64_t done = nunits * so3::kUnitRows, rest = B - done;
+    const Split sp(B, {op.in0, op.in1, op.in2, op.deg, op.index});
+    const int64_t done = sp.done, rest = sp.rest;
+    if (sp.nunits > 0) launch_rows<1, 4, 1024>(op, sp.nunits, s);
     if (rest > 0) {
         so3::OpSymAngle<MULTI> t = op;
         t.in0 = static_cast<const float *>(op.in0) + done * 9;
@@ -4965,35 +4908,30 @@ int so3_sym_angle_error_f32(const float *Rpred, const float *Rtrue, const float 
     if (B == 0) return 0;
     SO3_CHECK_ARGS(Rpred != nullptr && Rtrue != nullptr && deg != nullptr, "so3_sym_angle_error_f32: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (flags_out != nullptr) {
-        hipError_t e = hipMemsetAsync(flags_out, 0, sizeof(int32_t), s);
-        if (e != hipSuccess) return fail((int)e, "so3_sym_angle_error_f32: memset");
-    }
-#define SYM_OP(MULTI) do { so3::OpSymAngle<MULTI> op; op.in0 = Rpred; op.in1 = Rtrue; op.in2 = class_id; op.sym.table = S; op.sym.K = K; \
-                           op.sym.C = num_classes; op.deg = deg; op.index = index; op.flags_out = flags_out; \
-                           op.unit_scale = (flags & SO3_RADIANS) ? 1.0 : 57.295779513082320876798154814105; sym_angle_launch<MULTI>(op, B, s); } while (0)
-    if (num_classes > 1) SYM_OP(true); else SYM_OP(false);
-#undef SYM_OP
+    if (flags_out != nullptr) if (int e = zero_async(flags_out, sizeof(int32_t), s, "so3_sym_angle_error_f32: memset")) return e;
+    with_flags([&](auto MULTI) {
+        so3::OpSymAngle<MULTI()> op; op.in0 = Rpred; op.in1 = Rtrue; op.in2 = class_id; op.sym.table = S; op.sym.K = K;
+        op.sym.C = num_classes; op.deg = deg; op.index = index; op.flags_out = flags_out;
+        op.unit_scale = (flags & SO3_RADIANS) ? 1.0 : kDegPerRad;
+        sym_angle_launch<MULTI()>(op, B, s);
+    }, num_classes > 1);
     return check_launch("so3_sym_angle_error_f32");
 }
 
 }  // extern "C"
 
 template <bool MULTI, bool DP, bool DT>
-static void sym_loss_launch(so3::OpSymFrobLoss<MULTI, DP, DT> op, int64_t B, void *workspace, hipStream_t s, int *err) {
+static int sym_loss_launch(so3::OpSymFrobLoss<MULTI, DP, DT> op, int64_t B, void *workspace, hipStream_t s) {
     typedef so3::OpSymFrobLoss<MULTI, DP, DT> Op;
     if (B <= kSmallBatch) {                              // one workgroup, one launch: the kernel writes loss_sum and the mean itself
         hipLaunchKernelGGL((k_sym_rows<Op>), dim3(1), dim3(static_cast<unsigned>((B + 63) / 64 * 64)), 0, s, op, B, 1, nullptr);
-        return;
+        return 0;
     }
-    const int64_t nunits = stream_units(B, {op.in0, op.in1, op.in2, op.out0, op.out1, op.index});
-    const int64_t done = nunits * so3::kUnitRows, rest = B - done;
+    const Split sp(B, {op.in0, op.in1, op.in2, op.out0, op.out1, op.index});
+    const int64_t nunits = sp.nunits, done = sp.done, rest = sp.rest;
     const unsigned tile_wgs = rest > 0 ? persistent_grid(rest) : 0u;
-    so3::ReduceWs *ws = use_workspace(workspace, nunits, tile_wgs) ? static_cast<so3::ReduceWs *>(workspace) : nullptr;
-    if (ws == nullptr) {
-        hipError_t e = hipMemsetAsync(op.loss_sum, 0, sizeof(double), s);
-        if (e != hipSuccess) { *err = (int)e; return; }
-    }
+    so3::ReduceWs *ws = reduce_workspace(workspace, sp, tile_wgs);
+    if (ws == nullptr) if (int e = zero_async(op.loss_sum, sizeof(double), s, "so3_sym_frob_loss_f32: memset")) return e;
     if (rest > 0) {
         Op t = op;
         t.in0 = static_cast<const float *>(op.in0) + done * 9;
@@ -5010,6 +4948,7 @@ static void sym_loss_launch(so3::OpSymFrobLoss<MULTI, DP, DT> op, int64_t B, voi
         launch_rows<1, 4, 1024>(op, nunits, s);
     }
     if (ws == nullptr && op.loss_mean != nullptr) k_mean_from_sum<<<1, 1, 0, s>>>(op.loss_sum, op.loss_mean, op.inv_b_f64);
+    return 0;
 }
 
 extern "C" {
@@ -5023,16 +4962,14 @@ int so3_sym_frob_loss_f32(const float *Rpred, const float *Rtrue, const float *S
     SO3_CHECK_ARGS(Rpred != nullptr && Rtrue != nullptr && loss_sum != nullptr, "so3_sym_frob_loss_f32: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
     int err = 0;
-#define SYM_OP(MULTI, DP, DT) do { so3::OpSymFrobLoss<MULTI, DP, DT> op; op.in0 = Rpred; op.in1 = Rtrue; op.in2 = class_id; op.out0 = dRpred; \
-                                   op.out1 = dRtrue; op.sym.table = S; op.sym.K = K; op.sym.C = num_classes; op.index = index; \
-                                   op.loss_sum = loss_sum; op.loss_mean = loss_mean; op.inv_b = 1.0f / static_cast<float>(B); \
-                                   op.inv_b_f64 = 1.0 / static_cast<double>(B); sym_loss_launch(op, B, workspace, s, &err); } while (0)
-#define SYM_PICK(MULTI) do { if (dRpred && dRtrue) SYM_OP(MULTI, true, true); else if (dRpred) SYM_OP(MULTI, true, false); \
-                             else if (dRtrue) SYM_OP(MULTI, false, true); else SYM_OP(MULTI, false, false); } while (0)
-    if (num_classes > 1) SYM_PICK(true); else SYM_PICK(false);
-#undef SYM_PICK
-#undef SYM_OP
-    if (err != 0) return fail(err, "so3_sym_frob_loss_f32: memset");
+    with_flags([&](auto MULTI, auto DP, auto DT) {
+        so3::OpSymFrobLoss<MULTI(), DP(), DT()> op; op.in0 = Rpred; op.in1 = Rtrue; op.in2 = class_id; op.out0 = dRpred;
+        op.out1 = dRtrue; op.sym.table = S; op.sym.K = K; op.sym.C = num_classes; op.index = index;
+        op.loss_sum = loss_sum; op.loss_mean = loss_mean; op.inv_b = 1.0f / static_cast<float>(B);
+        op.inv_b_f64 = 1.0 / static_cast<double>(B);
+        err = sym_loss_launch(op, B, workspace, s);
+    }, num_classes > 1, dRpred != nullptr, dRtrue != nullptr);
+    if (err != 0) return err;                           // (the memset's: so3_last_error() is set)
     return check_launch("so3_sym_frob_loss_f32");
 }
 
@@ -5046,14 +4983,14 @@ int so3_sym_add_f32(const float *Tgt, const float *Tpred, const float *points, c
     if (B == 0) return 0;
     SO3_CHECK_ARGS(Tgt != nullptr && Tpred != nullptr && points != nullptr, "so3_sym_add_f32: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
-#define SYM_ADD_MODE(M) do { if (dTpred != nullptr) launch_sym_add<M, true>(Tgt, Tpred, points, S, class_id, num_classes, K, dists, index, loss_sum, \
-                                                                              dTpred, grad_scale, B, N, s); \
-                             else launch_sym_add<M, false>(Tgt, Tpred, points, S, class_id, num_classes, K, dists, index, loss_sum, nullptr, \
-                                                           grad_scale, B, N, s); } while (0)
-    if (flags == static_cast<unsigned>(SO3_SYM_ADD_L1)) SYM_ADD_MODE(so3::kSymAddL1);
-    else if (flags == static_cast<unsigned>(SO3_SYM_ADD_L2)) SYM_ADD_MODE(so3::kSymAddL2);
-    else launch_sym_add<so3::kSymAddMax, false>(Tgt, Tpred, points, S, class_id, num_classes, K, dists, index, loss_sum, nullptr, grad_scale, B, N, s);
-#undef SYM_ADD_MODE
+    static_assert(SO3_SYM_ADD_L2 == so3::kSymAddL2 && SO3_SYM_ADD_L1 == so3::kSymAddL1 && SO3_SYM_ADD_MAX == so3::kSymAddMax, "the flag is the mode");
+    with_value<so3::kSymAddL2, so3::kSymAddL1, so3::kSymAddMax>(static_cast<int>(flags), [&](auto MODE) {
+        constexpr int kMode = MODE();
+        with_flags([&](auto GRAD) {
+            if constexpr (kMode != so3::kSymAddMax || !GRAD())   // (the maximum has no gradient: refused above)
+                launch_sym_add<kMode, GRAD()>(Tgt, Tpred, points, S, class_id, num_classes, K, dists, index, loss_sum, dTpred, grad_scale, B, N, s);
+        }, dTpred != nullptr);
+    });
     return check_launch("so3_sym_add_f32");
 }
 #undef SO3_SYM_CHECK

@@ -116,6 +116,124 @@ def test_argument_validation_without_gpu(built_library):
     assert lib.so3_kabsch_f32(None, None, None, None, 4, -1, None) == -1
 
 
+P = "a valid pointer"            # a row's placeholder for the address of a 64-byte host buffer (never dereferenced: no row gets to a launch)
+INVALID = -1                     # SO3_ERR_INVALID
+# (entry, arguments, return code, so3_last_error() afterwards or None for an accepted call).  Every call returns before its first launch or
+# memset, so the table needs no GPU.
+REJECTED_CALLS = [
+    # a bad B: an engine entry, a reducing entry, a cloud entry, a symmetry entry
+    ("so3_project_fwd_f32", (None, None, None, -1, None), INVALID, "so3_project_fwd: B: invalid argument"),
+    ("so3_frob_fwd_bwd_v2_f32", (P, P, None, None, P, None, None, 0, -1, None), INVALID, "so3_frob_fwd_bwd: B: invalid argument"),
+    ("so3_rotate_clouds_f32", (P, P, P, 0, -1, 8, None), INVALID, "so3_rotate_clouds_f32: B/N: invalid argument"),
+    ("so3_sym_angle_error_f32", (P, P, P, None, 1, 1, P, None, None, 0, -1, None), INVALID, "so3_sym_angle_error_f32: B: invalid argument"),
+    # B / N
+    ("so3_add_l1_f32", (P, P, P, None, None, None, 1.0, 4, 0, None), INVALID, "so3_add_l1_f32: B/N: invalid argument"),
+    ("so3_add_s_fwd_f32", (P, P, P, P, None, None, None, 4, (1 << 20) + 1, None), INVALID, "so3_add_s_fwd_f32: B/N: invalid argument"),
+    ("so3_kabsch_f32", (P, P, P, None, (1 << 40) + 1, 8, None), INVALID, "so3_kabsch_f32: B/N: invalid argument"),
+    ("so3_kabsch_f32", (P, P, P, None, 4, -1, None), INVALID, "so3_kabsch_f32: B/N: invalid argument"),
+    ("so3_fps_f32", (P, P, P, 4, 16384 + 1, 8, None), INVALID, "so3_fps_f32: B/N/npoint: invalid argument"),
+    # unknown flags
+    ("so3_frob_fwd_bwd_v2_f32", (P, P, None, None, P, None, None, 1 << 31, 4, None), INVALID, "so3_frob_fwd_bwd: unknown flag: invalid argument"),
+    ("so3_frob_loss_v2_f32", (P, P, None, P, None, None, 1 << 31, 4, None), INVALID, "so3_frob_loss_f32: unknown flag: invalid argument"),
+    ("so3_angle_error_v2", (P, P, P, None, None, None, 1 << 31, 4, None), INVALID, "so3_angle_error: unknown flag: invalid argument"),
+    ("so3_project_angle_error_v2_f32", (P, P, P, P, None, None, None, 1 << 31, 4, None), INVALID,
+     "so3_project_angle_error_f32: unknown flag: invalid argument"),
+    ("so3_angle_error_v2_f64", (P, P, P, None, None, None, 1 << 31, 4, None), INVALID,
+     "so3_angle_error_v2_f64: unknown flag (SO3_RADIANS only): invalid argument"),
+    ("so3_angle_bwd_f32", (P, P, P, 1.0, 0.0, 1 << 31, P, None, 4, None), INVALID, "so3_angle_bwd_f32: unknown flag: invalid argument"),
+    ("so3_sym_frob_loss_f32", (P, P, P, None, 1, 1, None, None, None, P, None, None, 1, 4, None), INVALID,
+     "so3_sym_frob_loss_f32: unknown flag (none is defined for it): invalid argument"),
+    ("so3_sym_add_f32", (P, P, P, P, None, 1, 1, P, None, None, None, 1.0, 3, 4, 8, None), INVALID,
+     "so3_sym_add_f32: unknown flag (the mode: SO3_SYM_ADD_L2, _L1 or _MAX): invalid argument"),
+    # K and num_classes of the three symmetry entries
+    ("so3_sym_angle_error_f32", (P, P, P, None, 1, 0, P, None, None, 0, 4, None), INVALID,
+     "so3_sym_angle_error_f32: K must be in [1, 64]: invalid argument"),
+    ("so3_sym_angle_error_f32", (P, P, P, None, 0, 1, P, None, None, 0, 4, None), INVALID,
+     "so3_sym_angle_error_f32: num_classes must be >= 1: invalid argument"),
+    ("so3_sym_frob_loss_f32", (P, P, P, None, 1, 65, None, None, None, P, None, None, 0, 4, None), INVALID,
+     "so3_sym_frob_loss_f32: K must be in [1, 64]: invalid argument"),
+    ("so3_sym_frob_loss_f32", (P, P, P, P, 5, 64, None, None, None, P, None, None, 0, 4, None), INVALID,
+     "so3_sym_frob_loss_f32: num_classes * K must be <= 256: invalid argument"),
+    ("so3_sym_frob_loss_f32", (P, P, None, None, 1, 1, None, None, None, P, None, None, 0, 4, None), INVALID,
+     "so3_sym_frob_loss_f32: S is null: invalid argument"),
+    ("so3_sym_add_f32", (P, P, P, P, None, 2, 4, P, None, None, None, 1.0, 0, 4, 8, None), INVALID,
+     "so3_sym_add_f32: class_id must be given exactly when num_classes > 1: invalid argument"),
+    ("so3_sym_add_f32", (P, P, P, P, P, 1, 4, P, None, None, None, 1.0, 0, 4, 8, None), INVALID,
+     "so3_sym_add_f32: class_id must be given exactly when num_classes > 1: invalid argument"),
+    ("so3_sym_add_f32", (P, P, P, P, None, 1, 0, P, None, None, None, 1.0, 0, 4, 8, None), INVALID,
+     "so3_sym_add_f32: K must be in [1, 64]: invalid argument"),
+    ("so3_sym_add_f32", (P, P, P, P, None, 1, 4, P, None, None, P, 1.0, 2, 4, 8, None), INVALID,
+     "so3_sym_add_f32: dTpred must be null with SO3_SYM_ADD_MAX (no gradient): invalid argument"),
+    # null pointers with B > 0, an entry per family
+    ("so3_project_fwd_f32", (None, P, None, 5, None), INVALID, "so3_project_fwd: null pointer: invalid argument"),
+    ("so3_project_bwd_f32", (P, None, P, 5, None), INVALID, "so3_project_bwd: null pointer: invalid argument"),
+    ("so3_frob_fwd_bwd_v2_f32", (None, P, None, None, P, None, None, 0, 5, None), INVALID, "so3_frob_fwd_bwd: null pointer: invalid argument"),
+    ("so3_frob_fwd_bwd_v2_f32", (P, P, None, None, None, None, None, 0, 5, None), INVALID, "so3_frob_fwd_bwd: loss_sum is null: invalid argument"),
+    ("so3_frob_loss_v2_f32", (P, None, None, P, None, None, 0, 5, None), INVALID, "so3_frob_loss_f32: null pointer: invalid argument"),
+    ("so3_angle_error_v2", (None, P, P, P, None, None, 0, 5, None), INVALID, "so3_angle_error: null pointer: invalid argument"),
+    ("so3_geodesic_f32", (P, P, None, 5, None), INVALID, "so3_geodesic_f32: null pointer: invalid argument"),
+    ("so3_angle_bwd_f32", (P, P, P, 1.0, 0.0, 0, None, None, 5, None), INVALID, "so3_angle_bwd_f32: null pointer: invalid argument"),
+    ("so3_angle_bwd_f32", (P, P, P, 0.0, 0.0, 0, P, None, 5, None), INVALID, "so3_angle_bwd_f32: eps / grad_div: invalid argument"),
+    ("so3_ortho6d_fwd_f32", (P, None, 5, None), INVALID, "so3_ortho6d_fwd_f32: null pointer: invalid argument"),
+    ("so3_quat_bwd_f32", (P, None, P, 5, None), INVALID, "so3_quat_bwd_f32: null pointer: invalid argument"),
+    ("so3_logmap_fwd_f32", (None, P, 5, None), INVALID, "so3_logmap_fwd_f32: null pointer: invalid argument"),
+    ("so3_relative_log_bwd_f32", (P, P, P, None, None, 5, None), INVALID, "so3_relative_log_bwd_f32: null pointer: invalid argument"),
+    ("so3_add_l1_f32", (P, P, None, None, None, None, 1.0, 5, 8, None), INVALID, "so3_add_l1_f32: null pointer: invalid argument"),
+    ("so3_add_s_fwd_f32", (P, P, P, None, None, None, None, 5, 8, None), INVALID, "so3_add_s_fwd_f32: null pointer: invalid argument"),
+    ("so3_icp_f32", (P, P, 0, None, None, -1.0, 3, P, P, None, None, None, None, None, 5, 8, 8, None), INVALID,
+     "so3_icp_f32: null pointer: invalid argument"),
+    ("so3_fps_f32", (P, None, P, 5, 8, 4, None), INVALID, "so3_fps_f32: null pointer: invalid argument"),
+    ("so3_three_nn_f32", (P, P, P, None, None, 5, 8, 8, None), INVALID, "so3_three_nn_f32: null pointer: invalid argument"),
+    ("so3_rotate_clouds_bwd_f32", (P, None, P, P, None, 0, 5, 8, None), INVALID, "so3_rotate_clouds_bwd_f32: null pointer: invalid argument"),
+    ("so3_kabsch_bwd_f32", (P, P, None, P, None, P, P, 5, 8, None), INVALID, "so3_kabsch_bwd_f32: null pointer: invalid argument"),
+    ("so3_rigid_align_bwd_f32", (P, P, None, P, P, None, P, None, None, P, None, None, 5, 8, None), INVALID,
+     "so3_rigid_align_bwd_f32: null pointer: invalid argument"),
+    ("so3_sym_angle_error_f32", (P, P, P, None, 1, 4, None, None, None, 0, 5, None), INVALID,
+     "so3_sym_angle_error_f32: null pointer: invalid argument"),
+    ("so3_sym_frob_loss_f32", (P, P, P, None, 1, 4, None, None, None, None, None, None, 0, 5, None), INVALID,
+     "so3_sym_frob_loss_f32: null pointer: invalid argument"),
+    ("so3_sym_add_f32", (P, None, P, P, None, 1, 4, P, None, None, None, 1.0, 0, 5, 8, None), INVALID,
+     "so3_sym_add_f32: null pointer: invalid argument"),
+    # B == 0 is accepted whatever the pointers
+    ("so3_project_fwd_f32", (None, None, None, 0, None), 0, None),
+    ("so3_angle_bwd_f32", (None, None, None, 1.0, 0.0, 0, None, None, 0, None), 0, None),
+    ("so3_kabsch_bwd_f32", (None, None, None, None, None, None, None, 0, 8, None), 0, None),
+    ("so3_rigid_align_bwd_f32", (None,) * 12 + (0, 8, None), 0, None),
+    ("so3_rotate_clouds_bwd_f32", (None, None, None, None, None, 1, 0, 8, None), 0, None),
+    ("so3_fps_f32", (None, None, None, 0, 8, 4, None), 0, None),
+    ("so3_three_nn_f32", (None, None, None, None, None, 0, 8, 8, None), 0, None),
+    ("so3_sym_add_f32", (None, None, None, P, None, 1, 4, None, None, None, None, 1.0, 0, 0, 8, None), 0, None),
+]
+
+
+def test_rejected_calls_keep_their_code_and_message(built_library):
+    """Every row of REJECTED_CALLS: the return code and the exact text of so3_last_error().  On a thread of its own: so3_last_error is
+    thread-local and never cleared, and test_binding_table_matches_header reads it empty on the main thread."""
+    import threading
+    from poseestimation_amd import _lib
+    lib = _lib.load()
+    assert len(REJECTED_CALLS) >= 25
+    failures = []
+
+    def body():
+        buf = ctypes.create_string_buffer(64)
+        p = ctypes.cast(buf, ctypes.c_void_p).value
+        for entry, args, code, text in REJECTED_CALLS:
+            try:
+                assert len(args) == len(_lib.SYMBOLS[entry][1]), "argument count"
+                got = getattr(lib, entry)(*[p if a is P else a for a in args])
+                err = lib.so3_last_error().decode()
+                if got != code or (text is not None and err != text):
+                    failures.append((entry, args, got, err))
+            except Exception as exc:               # noqa: BLE001 -- reported on the main thread
+                failures.append((entry, args, repr(exc)))
+
+    t = threading.Thread(target=body)
+    t.start()
+    t.join()
+    assert not failures, failures
+
+
 def test_cpu_tensor_is_refused_not_silently_computed():
     import poseestimation_amd as pa
     x = torch.randn(4, 9)

@@ -503,6 +503,26 @@ def test_angle_sums_against_fsum(lib, data, idx):
     assert _zeroed(ws)
 
 
+@pytest.mark.parametrize("n", [3, 1088, 1091])
+def test_projected_angle_rows_and_sum_in_one_call(lib, data, n):
+    """K1 + K4 writing the per-row angles AND their sum (OpProjectAngle<4, WR, true, true, false>, with SO3_EXACT_F64 and without: the
+    float32 sum exists for the sum alone), R given and, where no remainder needs it (17 whole units), left out: one workgroup, the
+    engine alone, engine + remainder + workspace finish.  The sum against fsum of the rows the same call wrote."""
+    t, x = data["t"][:n], data["x"][:n]
+    ws, st = _ws(lib), _st()
+    for exact_flag in (EXACT_F64, 0):
+        for with_r in ((True, False) if n % 64 == 0 else (True,)):
+            for w in (ws, None):
+                r = torch.empty(n, 9, device=DEV) if with_r else None
+                deg, sc = _f64(n), _f64(2, 777.0)
+                assert lib.so3_project_angle_error_v2_f32(_p(x), _p(t), _p(r), _p(deg), _p(sc), None, _p(w), exact_flag, n, st) == 0
+                s, cnt = sc.tolist()
+                exact = math.fsum(deg.cpu().numpy().tolist())
+                assert cnt == n
+                assert abs(s - exact) <= _depth(n, w is not None) * U * exact, (n, exact_flag, with_r, w is None, s - exact)
+    assert _zeroed(ws)
+
+
 # ------------------------------------------------------------------------------------------------
 # 7. SO3_PREZEROED accumulating over several calls, one per shard
 # ------------------------------------------------------------------------------------------------

@@ -799,6 +799,30 @@ def test_metric_gradients_on_large_ragged_batches_and_views(rr):
         ga.sum().backward()
 
 
+@pytest.mark.parametrize("n", [3, 1091])
+@pytest.mark.parametrize("name", ["geo_none", "ang"])
+def test_one_metric_gradient_alone_under_a_per_row_upstream(rr, n, name):
+    """K4b with an upstream gradient per row and ONE argument that requires grad (OpAngleBwd<1 or 2, F64MATH, false>): float32 and
+    float64 arithmetic, either argument, 3 rows (the remainder kernel alone) and 17 units plus 3 rows (engine and remainder).  The
+    float64 closed form and the bounds of test_metric_gradients_on_large_ragged_batches_and_views."""
+    from oracle import so3_oracle as so
+    gen = torch.Generator(device=DEV).manual_seed(160 + n)
+    big_a, big_b = _haar_rows(n, gen), _haar_rows(n, gen)
+    w = torch.randn(n, device=DEV, generator=gen)
+    eps, unit, _, _ = METRIC_GRAD_CASES[name]
+    f64_graph = name.startswith("ang")
+    d1, d2, c = so.metric_backward_np(big_a.cpu().numpy(), big_b.cpu().numpy(), w.cpu().numpy(), eps=eps, unit=unit, divisor=1.0,
+                                      clamp_dtype=np.float64 if f64_graph else np.float32)
+    a = big_a.detach().requires_grad_(True)
+    ya = _metric_call(rr, name, a, big_b)
+    ya.backward(w.to(ya.dtype))
+    b = big_b.detach().requires_grad_(True)
+    yb = _metric_call(rr, name, big_a, b)
+    yb.backward(w.to(yb.dtype))
+    metric_grad_check(a.grad.cpu().numpy(), b.grad.cpu().numpy(), d1, d2, c, eps, 1e-15 if f64_graph else 6e-7, 4e-7, (name, n))
+    assert torch.isfinite(a.grad).all() and torch.isfinite(b.grad).all()
+
+
 def test_a_geodesic_loss_trains_the_head_like_the_reference_graph(rr):
     """`lossfunc` = geodesic in the reference's loops (point_cloud/main.py:194-197, UPNA/main.py:56-59): head -> metric -> backward,
     against the same chain in float64 torch (the oracle's port of the head and autograd through the reference's expression)."""

@@ -291,6 +291,30 @@ def test_loss_autograd_shapes_sides_and_determinism(pa):
         assert torch.equal(a, b)
 
 
+@pytest.mark.parametrize("n", [3, 1091])
+@pytest.mark.parametrize("side", ["pred", "true"])
+def test_ten_classes_with_one_gradient_alone(pa, n, side):
+    """Several classes with the gradient of one argument only (OpSymFrobLoss<true, DP, DT> with one of DP, DT): one workgroup (3 rows),
+    and 17 whole units plus 3 rows, where the engine launch, the remainder kernel and the workspace finish all run in one call.
+    check_against_oracle's bound."""
+    table = ten_class_table(pa)
+    gen = torch.Generator().manual_seed(40 + n)
+    t, p = haar(n, gen).float(), haar(n, gen).float()
+    cls = torch.randint(0, 10, (n,), generator=gen).int()
+    S = table_f32(table)
+    o = sym_oracle(p.numpy(), t.numpy(), S, cls.numpy())
+    pg, tg = cuda(p).requires_grad_(side == "pred"), cuda(t).requires_grad_(side == "true")
+    loss = pa.symmetric_loss_frobenius(pg, tg, table, cls.cuda())
+    assert abs(loss.item() - o["loss"]) <= 1e-6 * abs(o["loss"]), (loss.item(), o["loss"])
+    loss.backward()
+    got, ref, other = (pg.grad, o["dp"], tg) if side == "pred" else (tg.grad, o["dt"], pg)
+    assert other.grad is None
+    sure_l = trace_margin(p.numpy(), t.numpy(), S, cls.numpy(), loss=True) >= 1e-5
+    tol = (2e-6 + 4e-7 / o["dist"]) / n
+    err = np.abs(got.cpu().numpy() - ref).max(axis=(1, 2))
+    assert np.all((err <= tol)[sure_l]), (err / tol)[sure_l].max()
+
+
 def test_graph_replay_equals_eager(pa):
     table = ten_class_table(pa).to("cuda")
     gen = torch.Generator().manual_seed(12)
