@@ -3841,6 +3841,7 @@ int launch_add_l1(const float *Tgt, const float *Tpred, const float *points, flo
 }
 
 // k_add_s over B clouds, then its rows: U outer points per lane, fewer when the batch alone would not cover the CUs twice.
+// The instantiation's name goes to so3_last_kernel; the rows' launches leave it there.
 template <bool DIAMETER>
 int launch_add_s(const float *Tgt, const float *Tpred, const float *points, float *point_dist, int32_t *nearest, float *rows, double *total,
                  int64_t B, int32_t N, hipStream_t s, const char *what) {
@@ -3851,6 +3852,7 @@ int launch_add_s(const float *Tgt, const float *Tpred, const float *points, floa
     with_flags([&](auto WI) {
         constexpr bool kIndex = WI() && !DIAMETER;             // a diameter has no nearest index: no such instantiation
         with_value<4, 2, 1>(u, [&](auto U) {
+            name_kernel("k_add_s", kIndex, DIAMETER, U);
             hipLaunchKernelGGL((k_add_s<kIndex, DIAMETER, U()>), grid, block, 0, s, Tgt, Tpred, points, point_dist, nearest, B, N, chunks);
         });
     }, !DIAMETER && nearest != nullptr);

@@ -41,6 +41,11 @@ HOST_CONV_R = 1.645e-7;           CONV_R_TOL = 4 * HOST_CONV_R           # noqa:
 HOST_CONV_T = 5.960e-8;           CONV_T_TOL = 4 * HOST_CONV_T           # noqa: E702
 HOST_CONV_RMSE = 1.625e-7;        CONV_RMSE_TOL = 4 * HOST_CONV_RMSE     # noqa: E702
 ROT_TOL = 6 * R_TOL
+# The host model on the geometry case G4 of tests/search_geometry_ref.py (64 CUs + 37 clouds of 12 points, weighted, trimmed, two
+# iterations), measured in tests/test_search_geometry_host.py: among 16 421 small clouds the worst conditioned that still counts as
+# unique ((s2 + s3) / s1 = 0.16, s3 / s1 = 0.003) is beyond G21's figures, so for that shape R and T are bounded by 4 x these.
+HOST_R_G4 = 9.868e-6;             R_TOL_G4 = 4 * HOST_R_G4               # noqa: E702
+HOST_T_G4 = 5.085e-6;             T_TOL_G4 = 4 * HOST_T_G4               # noqa: E702
 MEASURED = {"search": HOST_SEARCH, "R": HOST_R, "T": HOST_T, "rmse": HOST_RMSE, "conv_R": HOST_CONV_R, "conv_T": HOST_CONV_T,
             "conv_rmse": HOST_CONV_RMSE}
 
@@ -52,6 +57,10 @@ CUS = 256                           # the device the host model stands in for
 def bounds():
     return {"search": SEARCH_TOL, "dist": SEARCH_TOL, "R": R_TOL, "T": T_TOL, "rmse": RMSE_TOL, "conv_R": CONV_R_TOL, "conv_T": CONV_T_TOL,
             "conv_rmse": CONV_RMSE_TOL, "rotation": ROT_TOL, "move_R": R_TOL, "move_T": T_TOL, "rise": RMSE_TOL, "exact": 0.0}
+
+
+def bounds_g4():
+    return dict(bounds(), R=R_TOL_G4, T=T_TOL_G4)
 
 
 # ---- the boundary ---------------------------------------------------------------------------------------------------------
