@@ -615,6 +615,40 @@ int so3_icp_f32(const float *P, const float *Q, int64_t q_stride, const float *w
                 int32_t iterations, float *R, float *t, float *rmse, int32_t *inliers, int32_t *nearest, float *dist,
                 void *workspace, int64_t B, int32_t N, int32_t M, void *stream);
 
+/* ---- Chamfer distance between two ragged clouds, with gradients to both (added in 210) ----
+ * Cloud b uses the first n_b = clip(x_len[b], 0, N) points of X and the first m_b = clip(y_len[b], 0, M) points of Y (NULL: all).
+ *     j(i) = the first argmin over j < m_b of |x_i - y_j|^2,   i(j) = the first argmin over i < n_b of |y_j - x_i|^2
+ *     (so3_nearest_f32's search: coordinate differences, strict < in ascending index; a point in both clouds gets exactly 0),
+ *     e = d^2, or d with SO3_CHAMFER_UNSQUARED (one square root after the minimum),
+ *     rows[b] = (sum_{i<n_b} e_i / n_b,  sum_{j<m_b} e_j / m_b);  with SO3_CHAMFER_SINGLE only the x direction runs and rows[b][1] = 0.
+ *   A cloud with n_b == 0 or m_b == 0 scores (0, 0) and takes no gradient.  A slot past its cloud's length reads dist 0,
+ *   nearest -1 and a gradient row of zeros: every element of every output is written, no buffer needs a zero-fill.
+ * so3_chamfer_fwd_f32: one launch searches both directions, a second adds each cloud's partial sums in a fixed order (float64).
+ *   X, Y           in   B*N*3, B*M*3 float32;   x_len, y_len  in  optional B int32
+ *   dist_x, dist_y out  optional B*N, B*M float32: the per-point e;   nearest_x, nearest_y  out  optional B*N, B*M int32
+ *                       (dist_y and nearest_y must be NULL with SO3_CHAMFER_SINGLE)
+ *   rows           out  B*2 float32 (required)
+ *   work                caller-owned, so3_chamfer_workspace_bytes(B, N, M) bytes (0 out of range), 4-byte aligned, no zero-fill
+ * so3_chamfer_bwd_f32: one launch, both gradients as a gather through the two index arrays the forward left:
+ *     dX[b][i] = scale_x[b] phi(x_i - y_j(i)) + sum_{j < m_b, i(j) = i} scale_y[b] phi(x_i - y_j),   dY the mirror image,
+ *     phi(v) = 2 v, or v / |v| (0 at v = 0) with SO3_CHAMFER_UNSQUARED;
+ *   per coordinate one chain: the own term (a rounded product), then fma(scale, phi, acc) over the hits in ascending index.
+ *   scale_x, scale_y  in  B float32: the upstream gradient of rows[b][0], rows[b][1] times the reduction's 1 / n_b, 1 / m_b.
+ *   With SO3_CHAMFER_SINGLE nearest_y and scale_y must be NULL (dY then holds the x direction's hits alone); otherwise both are
+ *   required.  dX, dY  out  B*N*3, B*M*3 float32, each optional, not both NULL.
+ * Nothing synchronises with the host and nothing uses atomics: a call can be captured in a graph and the same inputs give the
+ * same bits.  1 <= N, M <= SO3_ADD_S_MAX_N, B as so3_nearest_f32 (0: a no-op).
+ */
+#define SO3_CHAMFER_UNSQUARED 1u
+#define SO3_CHAMFER_SINGLE 2u
+size_t so3_chamfer_workspace_bytes(int64_t B, int32_t N, int32_t M);
+int so3_chamfer_fwd_f32(const float *X, const float *Y, const int32_t *x_len, const int32_t *y_len, float *dist_x,
+                        int32_t *nearest_x, float *dist_y, int32_t *nearest_y, float *rows, void *work, uint32_t flags, int64_t B,
+                        int32_t N, int32_t M, void *stream);
+int so3_chamfer_bwd_f32(const float *X, const float *Y, const int32_t *x_len, const int32_t *y_len, const int32_t *nearest_x,
+                        const int32_t *nearest_y, const float *scale_x, const float *scale_y, float *dX, float *dY,
+                        uint32_t flags, int64_t B, int32_t N, int32_t M, void *stream);
+
 /* ---- PointNet++ sampling and grouping: farthest-point sampling and ball query (added in 210) ----
  * The reference's point_cloud/pointnet_utils.py: farthest_point_sample (:53-74, a Python loop of npoint iterations) and
  * query_ball_point (:77-97, a (B,S,N) index tensor sorted along N), each as one launch.

@@ -1450,4 +1450,44 @@ constexpr int kGroupWideChannels = 64;                            // channels pe
 constexpr int kGroupFwdCfChannels = 16;                           // k_group_fwd<true>: channels per work item
 inline bool group_bwd_narrow(int32_t D) { return 3 + D <= kGroupNarrowC; }
 
+// ---- Chamfer distance between two clouds, with gradients to both (so3proj.hip: k_chamfer_fwd, k_chamfer_rows, k_chamfer_bwd;
+// tests/host_model/chamfer.cpp) ------------------------------------------------------------------------------------------------------
+// The arithmetic that is part of so3_chamfer_*_f32's definition.  The search is add_s_pair's (coordinate differences, strict < in
+// ascending index: a point that is in both clouds gets exactly 0); a point's term e is the minimum d^2, or its square root taken once
+// after the minimum.  A work item's partial sum of e is lane-wise in slot order, the wave's butterfly, the four waves in wave order;
+// a cloud's records are added in chunk order in float64.
+// The gradient of one point is ONE fmaf chain per coordinate:  the own term  a * phi(p - q_near(p))  first (one rounded product),
+// then  acc = fma(c, phi(p - q_j), acc)  for the points q_j of the other cloud whose nearest neighbour p is, in ascending j.
+//     phi(v) = 2 v  (squared),   v / |v| with 0 at v = 0  (unsquared: sym_add_direction's rule).
+constexpr int kChamferOwners = 64;               // k_chamfer_bwd: the points a wave owns, one per lane
+constexpr int kChamferScanBlocks = 8;            // ... and the 64-entry blocks of the other cloud's `nearest` it keeps in flight
+// The points one lane of k_chamfer_fwd keeps (U in {4, 2, 1}): k_add_s's rule over the work items of BOTH directions.
+inline int chamfer_points_per_lane(int64_t B, int32_t N, int32_t M, bool single, int64_t cus) {
+    int u = 4;
+    while (u > 1 && B * ((N + kIcpBlock * u - 1) / (kIcpBlock * u) + (single ? 0 : (M + kIcpBlock * u - 1) / (kIcpBlock * u))) < 2 * cus) u >>= 1;
+    return u;
+}
+__device__ __forceinline__ int32_t chamfer_length(const int32_t *lengths, int64_t b, int32_t full) {
+    if (lengths == nullptr) return full;
+    const int32_t n = lengths[b];
+    return n < 0 ? 0 : (n > full ? full : n);
+}
+template <bool SQUARED> __device__ __forceinline__ float chamfer_term(float best) { return SQUARED ? best : hw::sqrt(best); }
+template <bool SQUARED> __device__ __forceinline__ void chamfer_phi(float dx, float dy, float dz, float &ux, float &uy, float &uz) {
+    if (SQUARED) { ux = 2.f * dx; uy = 2.f * dy; uz = 2.f * dz; }
+    else sym_add_direction<kSymAddL2>(dx, dy, dz, ux, uy, uz);
+}
+// the own term: it opens the chain
+template <bool SQUARED> __device__ __forceinline__ void chamfer_own(float a, float dx, float dy, float dz, float (&acc)[3]) {
+    float ux, uy, uz;
+    chamfer_phi<SQUARED>(dx, dy, dz, ux, uy, uz);
+    acc[0] = a * ux; acc[1] = a * uy; acc[2] = a * uz;
+}
+// one hit, its phi already formed
+__device__ __forceinline__ void chamfer_hit(float c, float ux, float uy, float uz, float (&acc)[3]) {
+    acc[0] = __builtin_fmaf(c, ux, acc[0]);
+    acc[1] = __builtin_fmaf(c, uy, acc[1]);
+    acc[2] = __builtin_fmaf(c, uz, acc[2]);
+}
+
 }  // namespace so3

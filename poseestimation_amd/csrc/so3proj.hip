@@ -1920,6 +1920,196 @@ __global__ __launch_bounds__(kBlock) void k_icp_initial_pose(const float *__rest
     if (j < 3) R[b * 9 + 3 * c + j] = v; else T[b * 3 + c] = v;
 }
 
+// ---- Chamfer distance: both searches in one launch, both gradients in one gather ---------------------------------------------------
+// k_chamfer_fwd is k_icp_step<.., SUMS = false, U>'s skeleton over the work items of BOTH directions: a cloud has chunks_x items
+// that search Y for kBlock * U points of X, then chunks_y items that search X for points of Y (chunks_y = 0: x direction only).  The
+// clouds are ragged: a cloud uses its first n_b / m_b points (wave-uniform, scalar loads), the tile loop runs to the target's own
+// length, slots past the source's length read dist 0 and nearest -1.  A work item leaves the sum of its points' terms in rec[item]:
+// lane-wise in slot order, wave_allsum, the four waves in wave order.  k_chamfer_rows adds a cloud's records in chunk order in float64
+// and WRITES rows (B,2) = the two directions' means.  No atomics, no zero-fill.
+template <bool SQUARED, int U>
+__global__ __launch_bounds__(kBlock) void k_chamfer_fwd(const float *__restrict__ X, const float *__restrict__ Y, const int32_t *__restrict__ x_len,
+                                                        const int32_t *__restrict__ y_len, float *__restrict__ dist_x, int32_t *__restrict__ nearest_x,
+                                                        float *__restrict__ dist_y, int32_t *__restrict__ nearest_y, float *__restrict__ rec,
+                                                        int64_t B, int32_t N, int32_t M, int32_t chunks_x, int32_t chunks_y) {
+    static_assert(kBlock == so3::kIcpBlock, "the host model's chunking");
+    __shared__ float4 tile[kAddsTile];
+    float *red = reinterpret_cast<float *>(tile);                  // the waves' sums reuse the tile once it has been read
+    const int tid = threadIdx.x;
+    const int per = chunks_x + chunks_y;
+    const int64_t items = B * per;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t b = item / per;
+        const int c = static_cast<int>(item - b * per);
+        const bool rev = c >= chunks_x;                              // the y direction: Y's points search X
+        const int i_base = (rev ? c - chunks_x : c) * (kBlock * U);
+        const int32_t nb = so3::chamfer_length(x_len, b, N), mb = so3::chamfer_length(y_len, b, M);
+        const int32_t full = rev ? M : N, len_p = rev ? mb : nb, len_q = rev ? nb : mb;
+        const float *src = rev ? Y + b * M * 3 : X + b * N * 3, *tgt = rev ? X + b * N * 3 : Y + b * M * 3;
+        float *dist = rev ? dist_y : dist_x;
+        int32_t *nearest = rev ? nearest_y : nearest_x;
+        const bool live = len_q > 0 && i_base < len_p;              // the same in every lane of the workgroup
+        float x[U], y[U], z[U], best[U];
+        int idx[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) { x[u] = 0.f; y[u] = 0.f; z[u] = 0.f; best[u] = 0.f; idx[u] = 0; }
+        if (live) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int i = min(i_base + u * kBlock + tid, len_p - 1);    // a slot beyond the cloud repeats its last point; not summed, not stored
+                x[u] = src[i * 3 + 0]; y[u] = src[i * 3 + 1]; z[u] = src[i * 3 + 2];
+                best[u] = __builtin_huge_valf();
+            }
+            for (int t0 = 0; t0 < len_q; t0 += kAddsTile) {
+                const int cnt = min(kAddsTile, len_q - t0);
+                const int cntp = (cnt + kAddsUnroll - 1) / kAddsUnroll * kAddsUnroll;      // <= kAddsTile
+                __syncthreads();                                                         // the previous tile (and the waves' sums in it) has been read
+                for (int k = tid; k < cntp; k += kBlock) {
+                    const int j = t0 + min(k, cnt - 1);
+                    float4 q;
+                    q.x = tgt[j * 3 + 0]; q.y = tgt[j * 3 + 1]; q.z = tgt[j * 3 + 2]; q.w = 0.f;
+                    tile[k] = q;
+                }
+                __syncthreads();
+                for (int k = 0; k < cntp; k += kAddsUnroll) {
+#pragma unroll
+                    for (int kk = 0; kk < kAddsUnroll; ++kk) {
+                        const f32x4 q = *(const volatile lds_f32x4 *)(&tile[k + kk]);     // k_add_s: the ds_read_b128 broadcast
+#pragma unroll
+                        for (int u = 0; u < U; ++u)
+                            so3::add_s_pair<true, false>(x[u], y[u], z[u], q.x, q.y, q.z, t0 + k + kk, best[u], idx[u]);
+                    }
+                }
+            }
+        }
+        float mine = 0.f;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = i_base + u * kBlock + tid;
+            const bool valid = live && i < len_p;
+            const float e = valid ? so3::chamfer_term<SQUARED>(best[u]) : 0.f;
+            mine += e;
+            if (i < full) {
+                if (dist != nullptr) dist[b * full + i] = e;
+                if (nearest != nullptr) nearest[b * full + i] = valid ? min(idx[u], len_q - 1) : -1;
+            }
+        }
+        const float tot = wave_allsum(mine);
+        __syncthreads();                                         // every wave has left the last tile
+        if ((tid & 63) == 0) red[tid >> 6] = tot;
+        __syncthreads();
+        if (tid == 0) {
+            float v = red[0];
+#pragma unroll
+            for (int wv = 1; wv < kBlock / 64; ++wv) v += red[wv];          // in wave order
+            rec[item] = v;
+        }
+    }
+}
+
+// rows[b] = (cham_x, cham_y): a thread per (cloud, direction) adds the records in chunk order in float64 and divides by the length.
+// A cloud with an empty side scores 0 in both; without the y items (chunks_y = 0) cham_y is written as 0.
+__global__ __launch_bounds__(kBlock) void k_chamfer_rows(const float *__restrict__ rec, const int32_t *__restrict__ x_len,
+                                                         const int32_t *__restrict__ y_len, float *__restrict__ rows, int64_t B, int32_t N, int32_t M,
+                                                         int32_t chunks_x, int32_t chunks_y) {
+    const int per = chunks_x + chunks_y;
+    for (int64_t t = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; t < 2 * B; t += static_cast<int64_t>(gridDim.x) * kBlock) {
+        const int64_t b = t >> 1;
+        const bool rev = (t & 1) != 0;
+        const int32_t nb = so3::chamfer_length(x_len, b, N), mb = so3::chamfer_length(y_len, b, M);
+        const float *r = rec + b * per + (rev ? chunks_x : 0);
+        const int chunks = rev ? chunks_y : chunks_x;
+        double acc = 0.0;
+        for (int c = 0; c < chunks; ++c) acc += static_cast<double>(r[c]);
+        rows[t] = (nb > 0 && mb > 0 && chunks > 0) ? static_cast<float>(acc / static_cast<double>(rev ? mb : nb)) : 0.f;
+    }
+}
+
+// k_chamfer_bwd: both gradients as a gather.  A wave owns kChamferOwners = 64 consecutive points of one cloud, one per lane, and a
+// work item is the four waves' 256 points; the items of dX come first, then dY's, as in k_chamfer_fwd.  A lane opens its chain with
+// its own term (its neighbour's 12 bytes gathered from L2).  The wave then reads the OTHER direction's `nearest`, 64 entries per
+// block and kChamferScanBlocks blocks in flight, once for all its owners: an entry names one of them when idx - first < owners (one
+// unsigned compare: -1 and every other owner fall out), a ballot collects the block's hits.  The lanes that hold a hit gather their
+// point and form phi against the owner's point (ds_bpermute) side by side; the wave then walks the ballot in ascending order and the
+// owner a hit names takes it with chamfer_hit -- readlane moves, no memory, one statically indexed accumulator per lane.
+// No LDS, no barrier: the waves of a work item do not meet.  Padded slots and clouds with an empty side get a row of zeros.
+template <bool SQUARED>
+__global__ __launch_bounds__(kBlock) void k_chamfer_bwd(const float *__restrict__ X, const float *__restrict__ Y, const int32_t *__restrict__ x_len,
+                                                        const int32_t *__restrict__ y_len, const int32_t *__restrict__ nearest_x,
+                                                        const int32_t *__restrict__ nearest_y, const float *__restrict__ scale_x,
+                                                        const float *__restrict__ scale_y, float *__restrict__ dX, float *__restrict__ dY, int64_t B,
+                                                        int32_t N, int32_t M, int32_t chunks_x, int32_t chunks_y) {
+    static_assert(so3::kChamferOwners == 64 && kBlock % 64 == 0, "one owner per lane");
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int per = chunks_x + chunks_y;
+    const int64_t items = B * per;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t b = item / per;
+        const int c = static_cast<int>(item - b * per);
+        const bool rev = c >= chunks_x;                              // dY: Y's points own, X's points hit
+        const int32_t full = rev ? M : N, qfull = rev ? N : M;
+        const int first = (rev ? c - chunks_x : c) * kBlock + wave * 64;
+        float *out = rev ? dY : dX;
+        if (out == nullptr || first >= full) continue;
+        const int32_t nb = so3::chamfer_length(x_len, b, N), mb = so3::chamfer_length(y_len, b, M);
+        const int32_t len_p = rev ? mb : nb, len_q = rev ? nb : mb;
+        const float *P = rev ? Y + b * M * 3 : X + b * N * 3, *Q = rev ? X + b * N * 3 : Y + b * M * 3;
+        const int32_t *near_own = rev ? nearest_y : nearest_x, *near_hit = rev ? nearest_x : nearest_y;
+        const float *s_own = rev ? scale_y : scale_x, *s_hit = rev ? scale_x : scale_y;
+        const int i = first + lane;
+        float acc[3] = {0.f, 0.f, 0.f};
+        const bool live = len_q > 0 && first < len_p;                // wave-uniform
+        if (live) {
+            const int ic = min(i, len_p - 1);
+            const float px = P[ic * 3 + 0], py = P[ic * 3 + 1], pz = P[ic * 3 + 2];
+            if (s_own != nullptr && near_own != nullptr) {
+                const int j = min(max(near_own[b * full + ic], 0), len_q - 1);
+                so3::chamfer_own<SQUARED>(s_own[b], px - Q[j * 3 + 0], py - Q[j * 3 + 1], pz - Q[j * 3 + 2], acc);
+            }
+            if (s_hit != nullptr && near_hit != nullptr) {
+                const float cb = s_hit[b];
+                const unsigned owners = static_cast<unsigned>(min(64, len_p - first));
+                const int32_t *hits = near_hit + b * qfull;
+                for (int j0 = 0; j0 < len_q; j0 += 64 * so3::kChamferScanBlocks) {
+                    int idx[so3::kChamferScanBlocks];
+#pragma unroll
+                    for (int s = 0; s < so3::kChamferScanBlocks; ++s) {
+                        const int j = j0 + 64 * s + lane;
+                        idx[s] = j < len_q ? hits[j] : -1;
+                    }
+#pragma unroll
+                    for (int s = 0; s < so3::kChamferScanBlocks; ++s) {
+                        const unsigned rel = static_cast<unsigned>(idx[s] - first);
+                        const bool hit = rel < owners;
+                        unsigned long long mask = __ballot(hit);
+                        if (mask == 0) continue;
+                        const int j = min(j0 + 64 * s + lane, len_q - 1);
+                        const int owner = static_cast<int>(rel & 63u);
+                        const float ox = __shfl(px, owner, 64), oy = __shfl(py, owner, 64), oz = __shfl(pz, owner, 64);
+                        float ux = 0.f, uy = 0.f, uz = 0.f;
+                        if (hit) so3::chamfer_phi<SQUARED>(ox - Q[j * 3 + 0], oy - Q[j * 3 + 1], oz - Q[j * 3 + 2], ux, uy, uz);
+                        while (mask != 0) {                                  // ascending j
+                            const int h = __builtin_ctzll(mask);
+                            mask &= mask - 1;
+                            const int o = __builtin_amdgcn_readlane(owner, h);
+                            const float hx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ux), h));
+                            const float hy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(uy), h));
+                            const float hz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(uz), h));
+                            if (lane == o) so3::chamfer_hit(cb, hx, hy, hz, acc);
+                        }
+                    }
+                }
+            }
+        }
+        if (i < full) {
+            const bool keep = live && i < len_p;
+            float *o = out + (b * full + i) * 3;
+            o[0] = keep ? acc[0] : 0.f; o[1] = keep ? acc[1] : 0.f; o[2] = keep ? acc[2] : 0.f;
+        }
+    }
+}
+
 // ---- PointNet++ sampling and grouping: farthest-point sampling and ball query ----------------------------------------------------
 // The maximum of a 64-bit key over the wave, in every lane (wave_allmax's partners).
 __device__ __forceinline__ unsigned long long key_max(unsigned long long a, unsigned int lo, unsigned int hi) {
@@ -3900,6 +4090,15 @@ void launch_icp_step(const float *P, const float *Q, int64_t q_stride, const flo
         });
     }, SUMS && w != nullptr, SUMS && max_distance >= 0.f);
 }
+
+// The work items of one cloud in the Chamfer kernels: `points` points per item, x items first, then the y items (none: x direction only).
+struct ChamferChunks { int32_t x, y; };
+inline ChamferChunks chamfer_chunks(int32_t N, int32_t M, bool single, int points) {
+    return {(N + points - 1) / points, single ? 0 : (M + points - 1) / points};
+}
+inline unsigned chamfer_grid(int64_t B, ChamferChunks ch) {
+    return static_cast<unsigned>(std::min<int64_t>(B * (ch.x + ch.y), static_cast<int64_t>(device_cus()) * 64));
+}
 }  // namespace
 
 // ---- K4b: the metrics' backward (include/so3proj.h) ------------------------------------------------------------------
@@ -4507,6 +4706,61 @@ int so3_icp_f32(const float *P, const float *Q, int64_t q_stride, const float *w
         cur = next;
     }
     return check_launch("so3_icp_f32");
+}
+
+size_t so3_chamfer_workspace_bytes(int64_t B, int32_t N, int32_t M) {
+    if (B < 0 || B > (INT64_C(1) << 31) || N < 1 || N > SO3_ADD_S_MAX_N || M < 1 || M > SO3_ADD_S_MAX_N) return 0;
+    // one float per work item at the smallest work item (U = 1), both directions, whatever the device
+    const ChamferChunks ch = chamfer_chunks(N, M, false, kBlock);
+    return static_cast<size_t>(B) * (static_cast<size_t>(ch.x) + static_cast<size_t>(ch.y)) * sizeof(float);
+}
+
+int so3_chamfer_fwd_f32(const float *X, const float *Y, const int32_t *x_len, const int32_t *y_len, float *dist_x, int32_t *nearest_x,
+                        float *dist_y, int32_t *nearest_y, float *rows, void *work, uint32_t flags, int64_t B, int32_t N, int32_t M,
+                        void *stream) {
+    SO3_CHECK_ARGS((flags & ~static_cast<unsigned>(SO3_CHAMFER_UNSQUARED | SO3_CHAMFER_SINGLE)) == 0, "so3_chamfer_fwd_f32: unknown flag");
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && M >= 1 && M <= SO3_ADD_S_MAX_N,
+                   "so3_chamfer_fwd_f32: B/N/M");
+    if (B == 0) return 0;
+    const bool single = (flags & SO3_CHAMFER_SINGLE) != 0;
+    SO3_CHECK_ARGS(X != nullptr && Y != nullptr && rows != nullptr && work != nullptr, "so3_chamfer_fwd_f32: null pointer");
+    SO3_CHECK_ARGS(!single || (dist_y == nullptr && nearest_y == nullptr), "so3_chamfer_fwd_f32: dist_y / nearest_y with SO3_CHAMFER_SINGLE");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int u = so3::chamfer_points_per_lane(B, N, M, single, device_cus());
+    const ChamferChunks ch = chamfer_chunks(N, M, single, kBlock * u);
+    float *rec = static_cast<float *>(work);
+    with_flags([&](auto SQ) {
+        constexpr bool kSquared = SQ();
+        with_value<4, 2, 1>(u, [&](auto U) {
+            name_kernel("k_chamfer_fwd", kSquared, U);
+            hipLaunchKernelGGL((k_chamfer_fwd<kSquared, U()>),dim3(chamfer_grid(B, ch)), dim3(kBlock), 0, s, X, Y, x_len, y_len, dist_x, nearest_x, dist_y,
+                               nearest_y, rec, B, N, M, ch.x, ch.y);
+        });
+    }, (flags & SO3_CHAMFER_UNSQUARED) == 0);
+    const unsigned rows_grid = static_cast<unsigned>(std::min<int64_t>((2 * B + kBlock - 1) / kBlock, static_cast<int64_t>(device_cus()) * 64));
+    hipLaunchKernelGGL(k_chamfer_rows, dim3(rows_grid), dim3(kBlock), 0, s, rec, x_len, y_len, rows, B, N, M, ch.x, ch.y);
+    return check_launch("so3_chamfer_fwd_f32");
+}
+
+int so3_chamfer_bwd_f32(const float *X, const float *Y, const int32_t *x_len, const int32_t *y_len, const int32_t *nearest_x,
+                        const int32_t *nearest_y, const float *scale_x, const float *scale_y, float *dX, float *dY, uint32_t flags, int64_t B,
+                        int32_t N, int32_t M, void *stream) {
+    SO3_CHECK_ARGS((flags & ~static_cast<unsigned>(SO3_CHAMFER_UNSQUARED | SO3_CHAMFER_SINGLE)) == 0, "so3_chamfer_bwd_f32: unknown flag");
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && M >= 1 && M <= SO3_ADD_S_MAX_N,
+                   "so3_chamfer_bwd_f32: B/N/M");
+    if (B == 0) return 0;
+    const bool single = (flags & SO3_CHAMFER_SINGLE) != 0;
+    SO3_CHECK_ARGS(X != nullptr && Y != nullptr && nearest_x != nullptr && scale_x != nullptr && (dX != nullptr || dY != nullptr),
+                   "so3_chamfer_bwd_f32: null pointer");
+    SO3_CHECK_ARGS(single ? (nearest_y == nullptr && scale_y == nullptr) : (nearest_y != nullptr && scale_y != nullptr),
+                   "so3_chamfer_bwd_f32: nearest_y and scale_y go with both directions, NULL with SO3_CHAMFER_SINGLE");
+    const ChamferChunks ch = chamfer_chunks(N, M, false, kBlock);
+    with_flags([&](auto SQ) {
+        name_kernel("k_chamfer_bwd", SQ);
+        hipLaunchKernelGGL((k_chamfer_bwd<SQ()>), dim3(chamfer_grid(B, ch)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), X, Y, x_len, y_len,
+                           nearest_x, nearest_y, scale_x, scale_y, dX, dY, B, N, M, ch.x, ch.y);
+    }, (flags & SO3_CHAMFER_UNSQUARED) == 0);
+    return check_launch("so3_chamfer_bwd_f32");
 }
 
 int so3_fps_f32(const float *xyz, const int32_t *start, int32_t *out, int64_t B, int32_t N, int32_t npoint, void *stream) {

@@ -1380,6 +1380,127 @@ def icp_align(P: torch.Tensor, Q: torch.Tensor, R_init: torch.Tensor = None, t_i
 
 
 # --------------------------------------------------------------------------------------------
+# the Chamfer distance: a loss between two clouds, differentiable in both
+# --------------------------------------------------------------------------------------------
+def _chamfer_lengths(name, lengths, b, full, dev):
+    """(the lengths as the C ABI takes them: (B,) int32 or None, the per-cloud point counts as float32 (B,) or None for the full length)."""
+    if lengths is None:
+        return None, None
+    _require_device(lengths)
+    if lengths.device != dev or tuple(lengths.shape) != (b,) or lengths.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError("chamfer_distance: expected %s as a (B,) int32 or int64 tensor on %s for B = %d, got %s %s on %s"
+                           % (name, dev, b, tuple(lengths.shape), lengths.dtype, lengths.device))
+    clipped = lengths.detach().clamp(0, full).to(torch.int32).contiguous()
+    return clipped, clipped.to(torch.float32)
+
+
+class _Chamfer(torch.autograd.Function):
+    """chamfer_distance: so3_chamfer_fwd_f32 searches both directions and leaves the (B,2) means; the reductions over them are a few
+    (B,)-sized torch statements.  The backward folds the upstream gradient and those reductions into per-cloud scales on the device
+    and makes one so3_chamfer_bwd_f32 call through the stored indices."""
+
+    @staticmethod
+    def forward(ctx, X, Y, x_lengths, y_lengths, squared, point_reduction, batch_reduction, single, return_nearest):
+        dev = _require_device(X, Y)
+        ok = X.dim() == 3 and X.shape[-1] == 3 and Y.dim() == 3 and Y.shape[-1] == 3 and Y.shape[0] == X.shape[0]
+        if not ok or not 1 <= X.shape[1] <= _lib.ADD_S_MAX_N or not 1 <= Y.shape[1] <= _lib.ADD_S_MAX_N:
+            raise RuntimeError("chamfer_distance: expected a source (B, N, 3) and a target (B, M, 3) with 1 <= N, M <= %d, got %s and %s"
+                               % (_lib.ADD_S_MAX_N, tuple(X.shape), tuple(Y.shape)))
+        x, y = X.detach().contiguous().float(), Y.detach().contiguous().float()
+        b, n, m = x.shape[0], x.shape[1], y.shape[1]
+        xl, nx = _chamfer_lengths("x_lengths", x_lengths, b, n, dev)
+        yl, ny = _chamfer_lengths("y_lengths", y_lengths, b, m, dev)
+        want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        want_grad = want_x or want_y
+        flags = (0 if squared else _lib.CHAMFER_UNSQUARED) | (_lib.CHAMFER_SINGLE if single else 0)
+
+        def buf(rows, dtype, wanted):
+            return torch.empty((b, rows), dtype=dtype, device=dev) if wanted else None
+
+        near_x = buf(n, torch.int32, want_grad or return_nearest)
+        near_y = buf(m, torch.int32, (want_grad or return_nearest) and not single)
+        dist_x = buf(n, torch.float32, return_nearest)
+        dist_y = buf(m, torch.float32, return_nearest and not single)
+        rows = torch.empty((b, 2), dtype=torch.float32, device=dev)
+        lib = _libh()
+        work = torch.empty((max(int(lib.so3_chamfer_workspace_bytes(b, n, m)) // 4, 1),), dtype=torch.float32, device=dev)
+        with _on_device(dev):
+            _check(lib.so3_chamfer_fwd_f32(_ptr(x), _ptr(y), _ptr(xl), _ptr(yl), _ptr(dist_x), _ptr(near_x), _ptr(dist_y), _ptr(near_y), _ptr(rows),
+                                           _ptr(work), flags, b, n, m, _stream(dev)), "so3_chamfer_fwd_f32")
+        cham_x, cham_y = rows[:, 0], rows[:, 1]
+        if point_reduction == "sum":                       # rows holds the means
+            cham_x = cham_x * (float(n) if nx is None else nx)
+            cham_y = cham_y * (float(m) if ny is None else ny)
+        per_cloud = cham_x if single else cham_x + cham_y
+        out = per_cloud.mean() if batch_reduction == "mean" else (per_cloud.sum() if batch_reduction == "sum" else per_cloud.contiguous())
+        if want_grad:
+            ctx.save_for_backward(x, y, xl, yl, near_x, near_y, nx, ny)
+        ctx.meta = (want_x, want_y, flags, point_reduction, batch_reduction, X.dtype, Y.dtype, b, n, m)
+        if not return_nearest:
+            return out
+        extras = (near_x.long(), dist_x) if single else (near_x.long(), dist_x, near_y.long(), dist_y)
+        ctx.mark_non_differentiable(*extras)
+        return (out,) + extras
+
+    @staticmethod
+    def backward(ctx, grad_out, *unused):
+        _no_double_backward(grad_out)
+        want_x, want_y, flags, point_reduction, batch_reduction, x_dtype, y_dtype, b, n, m = ctx.meta
+        if not (want_x or want_y):
+            return (None,) * 9
+        x, y, xl, yl, near_x, near_y, nx, ny = ctx.saved_tensors
+        dev = x.device
+        g = grad_out.detach().float()
+        if batch_reduction is None:
+            g = g.reshape(b)
+        else:                                              # one upstream scalar for every cloud, kept on the device
+            g = (g.reshape(1) * (1.0 / max(b, 1)) if batch_reduction == "mean" else g.reshape(1)).expand(b)
+        if point_reduction == "mean":                      # an empty cloud takes no gradient: the kernel writes its rows as 0
+            scale_x = g * (1.0 / n) if nx is None else g / nx.clamp(min=1.0)
+            scale_y = g * (1.0 / m) if ny is None else g / ny.clamp(min=1.0)
+        else:
+            scale_x = scale_y = g
+        single = bool(flags & _lib.CHAMFER_SINGLE)
+        scale_x = scale_x.contiguous()
+        scale_y = None if single else scale_y.contiguous()
+        dx = torch.empty((b, n, 3), dtype=torch.float32, device=dev) if want_x else None
+        dy = torch.empty((b, m, 3), dtype=torch.float32, device=dev) if want_y else None
+        with _on_device(dev):
+            _check(_libh().so3_chamfer_bwd_f32(_ptr(x), _ptr(y), _ptr(xl), _ptr(yl), _ptr(near_x), _ptr(near_y), _ptr(scale_x), _ptr(scale_y),
+                                               _ptr(dx), _ptr(dy), flags, b, n, m, _stream(dev)), "so3_chamfer_bwd_f32")
+        return (None if dx is None else dx.to(x_dtype), None if dy is None else dy.to(y_dtype)) + (None,) * 7
+
+
+def chamfer_distance(X: torch.Tensor, Y: torch.Tensor, x_lengths: torch.Tensor = None, y_lengths: torch.Tensor = None, squared: bool = True,
+                     point_reduction: str = "mean", batch_reduction: str = "mean", single_directional: bool = False,
+                     return_nearest: bool = False):
+    """The Chamfer distance between the clouds X (B,N,3) and Y (B,M,3), differentiable in BOTH clouds:
+
+        loss_b = mean_{i < n_b} min_{j < m_b} |x_i - y_j|^2  +  mean_{j < m_b} min_{i < n_b} |y_j - x_i|^2.
+
+    x_lengths, y_lengths: optional (B,) int32 / int64 tensors; cloud b uses its first n_b = clip(x_lengths[b], 0, N) and m_b points, a
+    point past the length is neither a source nor a candidate.  A cloud with n_b == 0 or m_b == 0 scores 0 and takes no gradient.
+    squared=False sums the distances instead of their squares (one square root after the minimum; its gradient is the unit direction,
+    0 where the two points coincide).  point_reduction: "mean" or "sum" over a cloud's points; batch_reduction: "mean", "sum" or None
+    for the (B,) rows; single_directional=True keeps the first term alone.
+
+    The searches are nearest_neighbors' (coordinate differences, the first of equal candidates: a point that is in both clouds gets
+    exactly 0) and run in ONE launch; the backward is one launch that gathers both gradients through the stored indices in a fixed
+    order.  No atomics and nothing synchronises with the host: the same inputs give the same bits, and the call captures into a graph.
+
+    return_nearest=True returns (loss, info) with info["nearest_x"] (B,N), info["nearest_y"] (B,M) int64 (-1 in slots past the length)
+    and info["dist_x"], info["dist_y"] float32, the per-point terms (0 in those slots); single_directional leaves the y entries out."""
+    if point_reduction not in ("mean", "sum") or batch_reduction not in ("mean", "sum", None):
+        raise ValueError("chamfer_distance: point_reduction is 'mean' or 'sum' and batch_reduction 'mean', 'sum' or None, got %r and %r"
+                         % (point_reduction, batch_reduction))
+    res = _Chamfer.apply(X, Y, x_lengths, y_lengths, bool(squared), point_reduction, batch_reduction, bool(single_directional), bool(return_nearest))
+    if not return_nearest:
+        return res
+    names = ("nearest_x", "dist_x") if single_directional else ("nearest_x", "dist_x", "nearest_y", "dist_y")
+    return res[0], dict(zip(names, res[1:]))
+
+
+# --------------------------------------------------------------------------------------------
 # PointNet++ sampling and grouping (reference: point_cloud/pointnet_utils.py)
 # --------------------------------------------------------------------------------------------
 def _cloud_f32(name, what, x, width=3):

@@ -208,7 +208,16 @@ def main():
         timeit("so3_icp_f32 (256 x 1024 x 1024, %d iteration%s)" % (its, "" if its == 1 else "s"),
                lambda i: lib.so3_icp_f32(p(xi), p(yi), 3 * ni, None, None, ctypes.c_float(-1.0), its, p(ri), p(ti), None, None, None, None, p(wsi), bi, ni, ni, st),
                its * bi * ni * 24, iters=10, warm=2)
-    del xi, yi, di, nni, ri, ti, wsi
+    # the Chamfer distance at the same shape: both searches in one launch (2 x N * M pairs per cloud), then both gradients in one gather
+    dyi, nyi = torch.empty(bi, ni, device=dev), torch.empty(bi, ni, dtype=torch.int32, device=dev)
+    rwi, sci = torch.empty(bi, 2, device=dev), torch.full((bi,), 1.0 / ni, device=dev)
+    gxi, gyi = torch.empty(bi, ni, 3, device=dev), torch.empty(bi, ni, 3, device=dev)
+    wci = torch.empty(lib.so3_chamfer_workspace_bytes(bi, ni, ni) // 4, device=dev)
+    timeit("so3_chamfer_fwd_f32 (256 x 1024 x 1024, rows + nearest)",
+           lambda i: lib.so3_chamfer_fwd_f32(p(xi), p(yi), None, None, None, p(nni), None, p(nyi), p(rwi), p(wci), 0, bi, ni, ni, st), bi * ni * 32, iters=10, warm=2)
+    timeit("so3_chamfer_bwd_f32 (256 x 1024 x 1024, dX + dY)",
+           lambda i: lib.so3_chamfer_bwd_f32(p(xi), p(yi), None, None, p(nni), p(nyi), p(sci), p(sci), p(gxi), p(gyi), 0, bi, ni, ni, st), bi * ni * 56, iters=10, warm=2)
+    del xi, yi, di, nni, ri, ti, wsi, dyi, nyi, rwi, sci, gxi, gyi, wci
     # PointNet++ sampling and grouping at the reference model's first level: a chain of 511 dependent argmaxes per cloud (one workgroup
     # each: latency bound, most compute units idle at B = 32), and one wave per centre over the cloud (the bytes are the index rows')
     bf, nf, sf, kf = 32, 1024, 512, 64

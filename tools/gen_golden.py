@@ -1230,7 +1230,21 @@ def g23_head_edges():
     save("g23_head_edges.npz", **out)
 
 
+def g27_chamfer():
+    """chamfer_distance: no reference code exists, so the fixture holds the inputs (clouds of unit radius at every work split, ragged
+    lengths with an empty source, an empty target and a one-point target, X inside Y with duplicates, 2500 points whose nearest
+    neighbour is ONE point) and the float64 restatement's indices and rows -- tests/chamfer_ref.py: generate, which asserts that no
+    non-zero nearest distance lies below MIN_DISTANCE."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import chamfer_ref as ref
+    arrays = ref.generate()
+    save("g27_chamfer.npz", **arrays)
+    assert os.path.getsize(os.path.join(OUT, "g27_chamfer.npz")) <= os.path.getsize(os.path.join(OUT, "g21_icp.npz"))
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "g27":
+        return g27_chamfer()
     if len(sys.argv) > 1 and sys.argv[1] == "g26":
         return g26_sym_add()
     if len(sys.argv) > 1 and sys.argv[1] == "g25":
@@ -1282,6 +1296,7 @@ def main():
     g26_sym_add()
     g20_rigid_align()
     g21_icp()
+    g27_chamfer()
     g22_pointnet()
     g23_head_edges()
     # ---- G1: config #1, 256 Gaussian rows ------------------------------------------------------
