@@ -7,7 +7,11 @@ tests/test_chamfer_host.py and tests/test_gpu_chamfer.py share.  TEST INFRASTRUC
     (0, 0) when n_b == 0 or m_b == 0;   a padded slot has dist 0, nearest -1 and a zero gradient row.
     dX[b,i] = a_b phi(x_i - y_j(i)) + sum_{j<m_b, i(j)=i} c_b phi(x_i - y_j),  phi(v) = 2v or v/|v| (0 at 0);  dY the mirror image.
 
-The search is discontinuous, so indices are never compared for equality outside the exact families; the figures are
+The search's and the squared gradient's order of operations is part of the definition (so3_device.h), so search32 and grad32 below
+restate their float32 BITS through tests/f32_exact.py: the host model and the device are held to them by equality -- nearest_x /
+nearest_y in both flavours, the squared dist and the squared dX / dY.  The unsquared terms pass through 1-ulp instructions and rows
+through a butterfly whose shape follows the device, so those stay on the float64 figures, which the exact outputs keep beside the
+equality.  Against FLOAT64 the search is discontinuous, so there indices are never compared outside the exact families; the figures are
   search   e64(point, RETURNED neighbour) - the float64 minimum, over the live points of both directions
   dist     |returned dist - e64(point, returned neighbour)|
   rows     |rows - float64 rows| / |float64 rows|;  a float64 row of exactly 0 must be returned as exactly 0 (else inf)
@@ -18,6 +22,8 @@ The search is discontinuous, so indices are never compared for equality outside 
 import os
 
 import numpy as np
+
+from f32_exact import first_argmin32, fma32, pair_dist2_32
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g27_chamfer.npz")
 SIZES = [(1, 1), (3, 7), (255, 1023), (256, 1024), (257, 1025), (1000, 2500)]
@@ -124,6 +130,102 @@ def grad64(X, Y, x_lengths, y_lengths, nearest_x, nearest_y, scale_x, scale_y, s
             np.add.at(dX[k], i, -t)
             np.add.at(AX[k], i, np.abs(t))
     return dX, dY, AX, AY
+
+
+# ---- the defined float32 bits (so3_device.h: add_s_pair, chamfer_own, chamfer_hit), through tests/f32_exact.py ------------------------
+SEARCH32_PAIRS = 1 << 20                # pairs per numpy pass of search32
+
+
+def _search32(P, Q, pl, ql):
+    """P (b,n,3) searches Q (b,m,3) over the live prefixes pl, ql (b,): d2 (b,n) float32 and the first argmin (b,n), 0 / -1 in the
+    slots past pl and in clouds with an empty side."""
+    b, n, m = P.shape[0], P.shape[1], Q.shape[1]
+    d2, idx = np.zeros((b, n), np.float32), np.full((b, n), -1, np.int64)
+    rows = max(1, SEARCH32_PAIRS // m)                          # a pass is some rows of some clouds, all m candidates of each
+    step = max(1, rows // n)
+    for k in range(0, b, step):
+        q = Q[k:k + step, None, :, :]
+        past = np.arange(m)[None, None, :] >= ql[k:k + step, None, None]
+        for lo in range(0, n, rows):
+            p = P[k:k + step, lo:lo + rows, None, :]
+            d = pair_dist2_32(p[..., 0] - q[..., 0], p[..., 1] - q[..., 1], p[..., 2] - q[..., 2])
+            d[np.broadcast_to(past, d.shape)] = np.inf
+            at = first_argmin32(d)
+            idx[k:k + step, lo:lo + rows], d2[k:k + step, lo:lo + rows] = at, np.take_along_axis(d, at[..., None], -1)[..., 0]
+    dead = (np.arange(n)[None, :] >= pl[:, None]) | (ql[:, None] == 0)
+    d2[dead], idx[dead] = 0, -1
+    return d2, idx
+
+
+def search32(X, Y, x_lengths=None, y_lengths=None, single=False):
+    """The squared flavour's forward, bit for bit: dist_x, nearest_x (and dist_y, nearest_y) as so3_chamfer_fwd_f32 defines them --
+    d^2 = fma(dz, dz, fma(dy, dy, dx * dx)) from float32 coordinate differences, the first of equal candidates, a padded slot 0 / -1.
+    The indices are the unsquared flavour's too (its term is the root of the same minimum)."""
+    X, Y = np.asarray(X, np.float32), np.asarray(Y, np.float32)
+    b, n, m = X.shape[0], X.shape[1], Y.shape[1]
+    nl, ml = lengths_of(x_lengths, b, n), lengths_of(y_lengths, b, m)
+    out = {}
+    out["dist_x"], out["nearest_x"] = _search32(X, Y, nl, ml)
+    if not single:
+        out["dist_y"], out["nearest_y"] = _search32(Y, X, ml, nl)
+    return out
+
+
+def _chain32(P, Q, pl, ql, near_own, near_hit, s_own, s_hit):
+    """One cloud, one side (so3_device.h's chain): acc = s_own * (2 (p_i - q_near_own(i))) as one rounded product (+0 without an own
+    term), then acc = fma(s_hit, 2 (p_i - q_j), acc) over the j < ql with near_hit[j] == i in ascending j.  The r-th hit of every
+    owner is one numpy step."""
+    out = np.zeros_like(P)
+    if pl == 0 or ql == 0:
+        return out
+    acc = np.zeros((pl, 3), np.float32)
+    if s_own is not None:
+        j = np.clip(np.asarray(near_own[:pl], np.int64), 0, ql - 1)
+        acc = np.float32(s_own) * (np.float32(2) * (P[:pl] - Q[j]))
+    if s_hit is not None:
+        owner = np.asarray(near_hit[:ql], np.int64)
+        j = np.flatnonzero((owner >= 0) & (owner < pl))
+        j = j[np.argsort(owner[j], kind="stable")]                     # by owner, ascending j within an owner
+        o = owner[j]
+        rank = np.arange(len(j)) - np.searchsorted(o, o, side="left")  # the hit's place in its owner's chain
+        for r in range(int(rank.max()) + 1 if len(j) else 0):
+            at = rank == r
+            oo, jj = o[at], j[at]
+            acc[oo] = fma32(np.float32(s_hit), np.float32(2) * (P[oo] - Q[jj]), acc[oo])
+    out[:pl] = acc
+    return out
+
+
+def grad32(X, Y, x_lengths, y_lengths, nearest_x, nearest_y, scale_x, scale_y, clouds=None):
+    """The squared flavour's gradients, bit for bit, through the GIVEN indices and the float32 scales: (dX, dY) float32.  scale_y None:
+    the x direction alone (dY's chains then start at +0 and hold the x direction's hits).  clouds: restate these alone (the others 0)."""
+    X, Y = np.asarray(X, np.float32), np.asarray(Y, np.float32)
+    b, n, m = X.shape[0], X.shape[1], Y.shape[1]
+    nl, ml = lengths_of(x_lengths, b, n), lengths_of(y_lengths, b, m)
+    dX, dY = np.zeros_like(X), np.zeros_like(Y)
+    for k in range(b) if clouds is None else clouds:
+        sx, sy = scale_x[k], None if scale_y is None else scale_y[k]
+        iy = None if scale_y is None else nearest_y[k]
+        dX[k] = _chain32(X[k], Y[k], int(nl[k]), int(ml[k]), nearest_x[k], iy, sx, sy)
+        dY[k] = _chain32(Y[k], X[k], int(ml[k]), int(nl[k]), iy, nearest_x[k], sy, sx)
+    return dX, dY
+
+
+def small_last_hit_case(seed=2750):
+    """G27's many-to-one geometry on fresh points (squared, full lengths), with the LAST of the 2500 hits on x_0 made small: y_2499 lies
+    1e-6 from x_0, so its term in dX[0]'s chain is about 1e-7 of the sum of the chain's absolute terms -- a tenth of what the float64
+    figure's bound lets pass -- and still tens of ulps of the running sum.  It sits in the last, partial 64-entry block of the scan."""
+    rng = np.random.default_rng(seed)
+    n, m = 257, 2500
+    d = rng.standard_normal((m, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    Y = d * rng.uniform(2e-3, 9e-3, (m, 1))
+    Y[-1] = d[-1] * 1e-6
+    X = rng.standard_normal((n, 3))
+    X /= np.linalg.norm(X, axis=1, keepdims=True)
+    X[0] = 0
+    return {"name": "many_to_one, the last hit a small one", "family": "fresh", "X": X[None].astype(np.float32), "Y": Y[None].astype(np.float32),
+            "x_lengths": None, "y_lengths": None, "squared": True, "b": 1, "n": n, "m": m}
 
 
 def min_nonzero_distance(X, Y, x_lengths=None, y_lengths=None):

@@ -37,6 +37,7 @@ import functools
 import numpy as np
 
 import icp_ref
+from f32_exact import first_argmin32, pair_dist2_32
 
 CUS = 256                            # the device the CPU file evaluates the rule for
 BLOCK, TILE, UNROLL = 256, 1024, 8
@@ -46,6 +47,7 @@ G6_SIZES = ((1023, 2049), (1024, 1025), (1025, 1024), (2047, 1023), (2049, 2047)
 G7_SIZES = ((255, 1024), (256, 1023), (257, 2049), (1, 9), (2, 1), (9, 7))
 IDS = ["G1", "G2", "G3", "G4", "G5"] + ["G6-%d" % n for n, _ in G6_SIZES] + ["G7-%d" % n for n, _ in G7_SIZES]
 F64_PAIRS = 1 << 29                  # float64 pairs a GPU test checks per case: above it every k-th cloud (G5: every 32nd)
+F32_PAIRS = 1 << 25                  # pairs a GPU test restates in float32 numpy per case (f32_sample; G5 at 256 CUs: every 512th cloud)
 
 
 # ---- the geometry ---------------------------------------------------------------------------------------------------------------
@@ -89,6 +91,38 @@ def f64_sample(b, pairs_per_cloud, budget=F64_PAIRS):
     while (b + k - 1) // k * pairs_per_cloud > budget:
         k *= 2
     return np.arange(0, b, k)
+
+
+# ---- the searches' defined float32 bits ---------------------------------------------------------------------------------------
+def f32_sample(b, pairs_per_cloud, items, cap, budget=F32_PAIRS):
+    """The clouds of a batch whose indices are compared with the float32 restatement: the first, the last and every k-th between, k the
+    smallest power of two that keeps the restated pairs within `budget`.  -> (clouds, k).  Work item i of `items` is served on trip
+    i // cap of the grid and a cloud's items are consecutive, so with items > cap the last cloud is a second-trip one: asserted."""
+    k = 1
+    while True:
+        keep = np.union1d(np.arange(0, b, k), [b - 1])
+        if len(keep) * pairs_per_cloud <= budget:
+            break
+        k *= 2
+    per_cloud = items // b
+    assert items == per_cloud * b and (items <= cap or ((keep + 1) * per_cloud - 1 >= cap).any()), (b, items, cap)
+    return keep, k
+
+
+def nearest32(X, Y, pairs_per_pass=1 << 20):
+    """add_s_pair's search restated with tests/f32_exact.py: X (c,n,3) float32, Y (c,m,3) or one shared (m,3) -> (c,n) the first index
+    of the smallest d^2 = fma(dz, dz, fma(dy, dy, dx * dx)), coordinate differences rounded to float32."""
+    X, Y = np.asarray(X, np.float32), np.asarray(Y, np.float32)
+    c, n, m = X.shape[0], X.shape[1], Y.shape[-2]
+    out = np.empty((c, n), np.int64)
+    rows = max(1, pairs_per_pass // m)
+    step = max(1, rows // n)
+    for k in range(0, c, step):
+        q = Y[None, None] if Y.ndim == 2 else Y[k:k + step, None]
+        for lo in range(0, n, rows):
+            p = X[k:k + step, lo:lo + rows, None, :]
+            out[k:k + step, lo:lo + rows] = first_argmin32(pair_dist2_32(p[..., 0] - q[..., 0], p[..., 1] - q[..., 1], p[..., 2] - q[..., 2]))
+    return out
 
 
 # ---- ADD-S and the diameter: random input ----------------------------------------------------------------------------------------

@@ -2,8 +2,9 @@
 binding table, exports, argument validation, the Python names), the G27 fixture's own consistency, and the kernels' device functions
 compiled for the host (tests/host_model/chamfer.cpp with SO3_HOST_MODEL) on G27.
 
-The figures are tests/chamfer_ref.py's (search, dist, rows, grad, exact); indices are compared for equality only in the exact
-families.  Clouds are of unit radius, and no non-zero nearest distance of the fixture lies below chamfer_ref.MIN_DISTANCE (asserted by
+The figures are tests/chamfer_ref.py's (search, dist, rows, grad, exact), all against float64, where indices are compared for equality
+only in the exact families -- and `bits` (bit_figure), 0 or inf: the indices, the squared d^2 and the squared gradients EQUAL the float32
+restatement of the defined order (chamfer_ref.search32 / grad32), on the host model and on the device.  Clouds are of unit radius, and no non-zero nearest distance of the fixture lies below chamfer_ref.MIN_DISTANCE (asserted by
 the generator and again here: a condition on the inputs that keeps v / |v| away from its singularity).
 
 TOLERANCES.  HOST_* are the largest figures of the float32 host model (at 256 compute units) over G27, measured here; the bound of
@@ -50,7 +51,7 @@ SEARCH_REASONED = 64 * 2.0 ** -24
 
 
 def bounds():
-    return {"search": SEARCH_TOL, "dist": DIST_TOL, "rows": ROWS_TOL, "loss": LOSS_TOL, "grad": GRAD_TOL, "exact": 0.0}
+    return {"search": SEARCH_TOL, "dist": DIST_TOL, "rows": ROWS_TOL, "loss": LOSS_TOL, "grad": GRAD_TOL, "exact": 0.0, "bits": 0.0}
 
 
 # ---- the boundary ---------------------------------------------------------------------------------------------------------
@@ -196,10 +197,45 @@ def test_g27_is_self_consistent(g27_cases):
 
 
 # ---- the checks, shared with tests/test_gpu_chamfer.py -----------------------------------------------------------------------
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+SEARCH32 = {}
+
+
+def expected_search32(c):
+    """ref.search32 of a fixture case, computed once per (geometry, lengths): both flavours, the host model and the device share it."""
+    key = (c["geometry"], c["lengths"])
+    if key not in SEARCH32:
+        SEARCH32[key] = ref.search32(c["X"], c["Y"], c["x_lengths"], c["y_lengths"])
+    return SEARCH32[key]
+
+
+def bit_figure(c, got, single=False):
+    """0 or inf: what the definition fixes down to the bits equals the float32 restatement (chamfer_ref.search32, grad32) -- the
+    indices in both flavours; in the squared one d^2 and, where the gradients came from ref.scales through the C ABI's argument order
+    (the Python surface folds its own scales), dX and dY through the RETURNED indices."""
+    want, wrong = expected_search32(c), []
+    for side in ("x",) if single else ("x", "y"):
+        if not np.array_equal(got["nearest_" + side], want["nearest_" + side]):
+            wrong.append(("nearest_" + side, int((np.asarray(got["nearest_" + side]) != want["nearest_" + side]).sum())))
+        if c["squared"] and not np.array_equal(bits(got["dist_" + side]), bits(want["dist_" + side])):
+            wrong.append(("dist_" + side, int((bits(got["dist_" + side]) != bits(want["dist_" + side])).sum())))
+    if c["squared"] and "scale_x" not in got:
+        sx, sy = ref.scales(c["b"])
+        dX, dY = ref.grad32(c["X"], c["Y"], c["x_lengths"], c["y_lengths"], got["nearest_x"], None if single else got["nearest_y"], sx, None if single else sy)
+        wrong += [(k, int((bits(got[k]) != bits(w)).sum())) for k, w in (("dX", dX), ("dY", dY)) if not np.array_equal(bits(got[k]), bits(w))]
+    if wrong:
+        print("%s: elements whose bits differ from the float32 restatement: %s" % (c["name"], wrong))
+    return np.inf if wrong else 0.0
+
+
 def case_figures(c, got, single=False):
     """The figures of one fixture case for the results `got` of running it forward and backward with ref.scales as the gradient
     scales (or the scale_x, scale_y it carries): dist_x, nearest_x, (dist_y, nearest_y,) rows or loss, dX, dY."""
     f = ref.forward_figures(c["X"], c["Y"], c["x_lengths"], c["y_lengths"], c["squared"], got, single)
+    f["bits"] = bit_figure(c, got, single)
     sx, sy = got.get("scale_x", ref.scales(c["b"])[0]), got.get("scale_y", ref.scales(c["b"])[1])
     if f["exact"] == 0.0:
         f.update(ref.gradient_figures(c["X"], c["Y"], c["x_lengths"], c["y_lengths"], c["squared"], got["nearest_x"],

@@ -1,6 +1,8 @@
 """chamfer_distance on the GPU: G27 through the Python surface and through the raw C ABI with the checks and bounds of
 tests/test_chamfer_host.py (4 x the float32 host model's figures; see its docstring), batch shapes that force each work-item size of
-k_chamfer_fwd against the float64 restatement on the same random input, every reduction, the boundary cases, repeatability, replay
+k_chamfer_fwd against the float64 restatement on the same random input and, in the squared flavour through the C ABI, BIT FOR BIT
+against the float32 restatement of the defined order (chamfer_ref.search32, grad32: indices, d^2 and both gradients; G27's cases get
+the same equality inside check_against_g27, the 2500-hit chain of the many-to-one family among them), every reduction, the boundary cases, repeatability, replay
 from a graph, and the speed condition against the torch spelling."""
 import ctypes
 import itertools
@@ -14,6 +16,8 @@ import test_chamfer_host as host
 
 pytestmark = pytest.mark.gpu
 GUARD = 64                          # elements in front of and behind every raw buffer
+KERNELS = []                        # abi_run: the k_chamfer_fwd instantiation of every forward call, in call order
+F32_PAIRS = 1 << 25                 # pairs the float32 restatement forms per test case
 
 
 @pytest.fixture(scope="module")
@@ -134,6 +138,7 @@ def abi_run(c, dev, single=False):
     sxd, syd = _d(sx, dev), (None if single else _d(sy, dev))
     _lib.check(lib.so3_chamfer_fwd_f32(_ptr(X), _ptr(Y), _ptr(xl), _ptr(yl), _ptr(out["dist_x"]), _ptr(out["nearest_x"]), _ptr(out.get("dist_y")),
                                        _ptr(out.get("nearest_y")), _ptr(out["rows"]), _ptr(work), flags, b, n, m, st), "so3_chamfer_fwd_f32")
+    KERNELS.append(lib.so3_last_kernel().decode())                                          # the forward's instantiation, for the caller
     _lib.check(lib.so3_chamfer_bwd_f32(_ptr(X), _ptr(Y), _ptr(xl), _ptr(yl), _ptr(out["nearest_x"]), _ptr(out.get("nearest_y")), _ptr(sxd), _ptr(syd),
                                        _ptr(out["dX"]), _ptr(out["dY"]), flags, b, n, m, st), "so3_chamfer_bwd_f32")
     assert lib.so3_last_kernel().decode() == "k_chamfer_bwd<%s>" % ("true" if c["squared"] else "false")
@@ -226,6 +231,101 @@ def test_batch_above_the_grid_cap(dev):
     c = _split_case(b, n, m, ragged=True, squared=True)
     assert _split_check(c, dev, long_lengths=False, label="above the cap B=%d" % b) == "k_chamfer_fwd<true, 4>"
     if cus == 256:                      # an MI355X in SPX mode: with this one the shapes of the work splits reach every instantiation
+        assert {_rule(*s, cus) for s in SPLITS} | {4} == {1, 2, 4}
+
+
+# ---- every work split, bit for bit ----------------------------------------------------------------------------------------------
+def _exact_case(b, n, m):
+    """Fresh clouds of unit radius, squared, ragged: the first and the last cloud keep every point (the sizes are tile and chunk edges),
+    the others random lengths >= 1, and from three clouds on cloud 1 has an empty x side."""
+    c = _split_case(b, n, m, ragged=True, squared=True)
+    rng = np.random.default_rng(27500 + 97 * b + n + m)
+    c["x_lengths"], c["y_lengths"] = rng.integers(1, n + 1, b), rng.integers(1, m + 1, b)
+    for k in (0, b - 1):
+        c["x_lengths"][k], c["y_lengths"][k] = n, m
+    if b >= 3:
+        c["x_lengths"][1] = 0
+    return c
+
+
+def _restated_clouds(b, n, m):
+    """The clouds the float32 restatement covers within F32_PAIRS pairs (both directions: 2 N M per cloud): the first, the last and
+    every k-th between, k the smallest power of two that fits.  -> (indices, k)."""
+    k = 1
+    while True:
+        keep = np.union1d(np.arange(0, b, k), [b - 1])
+        if len(keep) * 2 * n * m <= F32_PAIRS:
+            return keep, k
+        k *= 2
+
+
+def _exact_check(c, dev, label, single=False):
+    """so3_chamfer_fwd_f32 / so3_chamfer_bwd_f32 through the raw C ABI (NaN / -2 pre-filled, guarded buffers; each gradient alone gives
+    the bits of both: abi_run) against chamfer_ref.search32 and, through the device's OWN indices and ref.scales' float32 scales,
+    grad32.  Equality of indices and of bit patterns, every slot of every restated cloud."""
+    b, n, m = c["b"], c["n"], c["m"]
+    got = abi_run(c, dev, single)
+    kernel = KERNELS[-1]                                                                     # abi_run's forward into the checked buffers
+    keep, k = _restated_clouds(b, n, m)
+    print("%s: %s, %d of %d clouds restated (every %d%s)" % (label, kernel, len(keep), b, k, "" if k == 1 else ", the first and the last"))
+    sub = lambda a: None if a is None else np.asarray(a)[keep]
+    want = ref.search32(c["X"][keep], c["Y"][keep], sub(c["x_lengths"]), sub(c["y_lengths"]), single)
+    for key, w in want.items():
+        g = got[key][keep]
+        wrong = np.argwhere(g != w) if key.startswith("nearest") else np.argwhere(host.bits(g) != host.bits(w))
+        assert len(wrong) == 0, (label, key, len(wrong), keep[wrong[:4, 0]], wrong[:4, 1], g[tuple(wrong[:4].T)], w[tuple(wrong[:4].T)])
+    if not single:                                  # the unsquared flavour takes the root of the same minimum: its indices are the same
+        l2 = abi_run(dict(c, squared=False), dev)
+        assert KERNELS[-1] == kernel.replace("<true", "<false")
+        for key in ("nearest_x", "nearest_y"):
+            assert np.array_equal(l2[key][keep], want[key]), (label, "unsquared", key)
+    sx, sy = ref.scales(b)
+    dX, dY = ref.grad32(c["X"], c["Y"], c["x_lengths"], c["y_lengths"], got["nearest_x"], None if single else got["nearest_y"], sx, None if single else sy,
+                        clouds=keep)
+    for key, w in (("dX", dX), ("dY", dY)):
+        wrong = np.argwhere(host.bits(got[key][keep]) != host.bits(w[keep]))
+        assert len(wrong) == 0, (label, key, len(wrong), keep[wrong[:4, 0]], wrong[:4, 1:], got[key][keep][tuple(wrong[:4].T)], w[keep][tuple(wrong[:4].T)])
+    return kernel, keep
+
+
+@pytest.mark.parametrize("b,n,m", SPLITS, ids=lambda v: str(v))
+def test_work_splits_bit_for_bit(dev, b, n, m):
+    """The squared flavour on every size of the work-split test: nearest_x / nearest_y equal search32's indices, dist_x / dist_y its
+    d^2 and dX / dY grad32, bit for bit; the instantiation is the one the launcher's rule names.  SO3_CHAMFER_SINGLE on every third."""
+    c = _exact_case(b, n, m)
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    kernel, _ = _exact_check(c, dev, "exact B=%d N=%d M=%d" % (b, n, m))
+    assert kernel == "k_chamfer_fwd<true, %d>" % _rule(b, n, m, cus)
+    if SPLITS.index((b, n, m)) % 3 == 0:
+        _exact_check(c, dev, "exact single B=%d N=%d M=%d" % (b, n, m), single=True)
+
+
+def test_four_points_per_lane_on_multi_tile_clouds_bit_for_bit(dev):
+    """The sizes above reach U = 4 only on clouds of 12 points: the smallest batch whose rule gives U = 4 at (1025, 1023) -- two tiles, the
+    second of one point and seven pads, and x's second work item holding one real point."""
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    b = next(b for b in range(1, 4 * cus) if _rule(b, 1025, 1023, cus) == 4)
+    kernel, _ = _exact_check(_exact_case(b, 1025, 1023), dev, "exact U = 4 B=%d N=1025 M=1023" % b)
+    assert kernel == "k_chamfer_fwd<true, 4>"
+
+
+def test_a_small_last_hit_of_a_long_chain_bit_for_bit(dev):
+    """2500 hits on one owner, the last of them a tenth of what the float64 figure's bound lets pass and tens of ulps of the running sum
+    (tests/test_f32_exact_host.py holds the premise): in the last, partial block of k_chamfer_bwd's scan."""
+    c = ref.small_last_hit_case()
+    _exact_check(c, dev, "exact " + c["name"])
+
+
+def test_batch_above_the_grid_cap_bit_for_bit(dev):
+    """More work items than the grid holds: two items per cloud at U = 4, so the last cloud's items are served on the grid's second
+    trip, and every cloud is restated (k = 1).  With it the exact comparison has run under U = 1, 2 and 4 on an MI355X."""
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    b, n, m = cus * 32 + 1, 12, 12
+    kernel, keep = _exact_check(_exact_case(b, n, m), dev, "exact above the cap B=%d" % b)
+    assert kernel == "k_chamfer_fwd<true, 4>"
+    grid, per = cus * 64, 2                                     # chamfer_grid; chunks_x + chunks_y
+    assert b * per > grid and (keep * per + per - 1 >= grid).any() and len(keep) == b       # a second-trip cloud is among the restated ones
+    if cus == 256:                      # every case above asserts the instantiation its rule names: on an MI355X in SPX mode they are all three
         assert {_rule(*s, cus) for s in SPLITS} | {4} == {1, 2, 4}
 
 

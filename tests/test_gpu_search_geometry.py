@@ -7,6 +7,10 @@ expectations without a GPU.
       written, every canary intact, indices in range; the ICP workspace 16-byte aligned, NaN-filled, guarded behind its stated size;
   (b) every cloud and every point against float64 on the device in slices (above search_geometry_ref.F64_PAIRS pairs every k-th cloud: G5),
       at test_add_metrics_host's and test_icp_host's bounds, unchanged; the instantiation through so3_last_kernel() on every case;
+      and the indices -- so3_nearest_f32's, the first ICP search's (source through pose_point32) and so3_add_s_fwd_f32's (both clouds
+      through it) -- EQUAL to the float32 restatement of the defined order (search_geometry_ref.nearest32 over tests/f32_exact.py), on
+      the first cloud, the last and every k-th between within search_geometry_ref.F32_PAIRS pairs (k printed; G4 and G5: the last
+      cloud is a second-trip one, asserted by f32_sample).  dist keeps its bound: it passes through v_sqrt_f32 (1 ulp);
   (c) the same cloud gives the same bits at U = 1 (batches of <= 64), 2 and 4, in the reversed batch and on the second grid-stride trip;
   (d) the exact lattice families: ties across tiles and in the padding, the last point, identical clouds, the diameter;
   (e) the optional-output spellings at G4;  (f) a NaN and an Inf cloud change no other cloud.
@@ -37,6 +41,7 @@ import pytest
 import torch
 
 import add_metrics_ref as aref
+import f32_exact as fx
 import icp_ref
 import search_geometry_ref as geo
 import test_add_metrics_host as ahost
@@ -200,6 +205,14 @@ def test_add_s_backward_and_diameter_on_every_split(ctx, case_id):
     f = adds_figures(got, tg, tp, pts, rows, keep)
     hold("%s B=%d N=%d U=%d float64 on %d clouds" % (case_id, b, n, c["u_adds"], len(keep)), f, ahost.BOUNDS)
     assert (got["grad"][:, 3] == 0).all()
+    # the defined bits: both clouds through pose_point's fmaf order, pair_dist2, the first of equal candidates -- indices EQUAL
+    keep32, k32 = geo.f32_sample(b, n * n, c["items_adds"], c["cap"])
+    at = torch.as_tensor(keep32, device=ctx.dev)
+    p32 = pts[at].cpu().numpy()
+    want = geo.nearest32(*(fx.pose_point32(t[at].cpu().numpy().reshape(-1, 16)[:, :12], p32) for t in (tg, tp)))
+    wrong = np.argwhere(got["nearest"][at].cpu().numpy() != want)
+    print("%s ADD-S nearest against the float32 restatement: %d clouds (every %d, the first and the last), %d differ" % (case_id, len(keep32), k32, len(wrong)))
+    assert len(wrong) == 0, (case_id, len(wrong), keep32[wrong[:4, 0]], wrong[:4, 1], want[tuple(wrong[:4].T)])
     if n == 1:
         assert (got["diam"] == 0).all() and (got["nearest"] == 0).all()
 
@@ -407,6 +420,17 @@ def test_icp_and_search_on_every_split(ctx, case_id, target):
     hn = _host(near)
     Pk, Qk = (d["Ps"] if shared else d["P"])[keep], d["Qs"] if shared else d["Q"][keep]
     hold(label + " search", ihost.search_figures(Pk, Qk, hn["dist"][keep], hn["nearest"][keep], device=ctx.dev), ihost.bounds())
+    # the defined bits (pair_dist2 from coordinate differences, the first of equal candidates): indices EQUAL the float32 restatement;
+    # a posed case restates two searches, so each takes half the pairs
+    keep32, k32 = geo.f32_sample(b, (2 if posed else 1) * n * m, c["items"], c["cap"])
+    P32, Q32 = (d["Ps"] if shared else d["P"])[keep32], d["Qs"] if shared else d["Q"][keep32]
+
+    def same_indices(what, nearest, X):
+        wrong = np.argwhere(nearest[keep32] != geo.nearest32(X, Q32))
+        print("%s %s against the float32 restatement: %d clouds (every %d, the first and the last), %d differ" % (label, what, len(keep32), k32, len(wrong)))
+        assert len(wrong) == 0, (label, what, len(wrong), keep32[wrong[:4, 0]], wrong[:4, 1])
+
+    same_indices("so3_nearest_f32", hn["nearest"], P32)
     # one iteration, then (G4, G5) two: the second is judged from the pose the first one returned
     one = run_icp(ctx, P, Q, stride, D["w"], D["T0"], md, 1, b, n, m)
     want = "k_icp_step<%s, %s, true, %d>" % (str(weighted).lower(), str(trimmed).lower(), u)
@@ -415,6 +439,8 @@ def test_icp_and_search_on_every_split(ctx, case_id, target):
     hold(label + " iteration 1 of 1", icp_figures(ctx, d, keep, shared, md, h1, start, 0), bnd)
     if not posed:                                            # from the identity nothing is multiplied: the search's own bits
         assert torch.equal(one["dist"], near["dist"]) and torch.equal(one["nearest"], near["nearest"])
+    else:                                                    # the source through pose_point's fmaf order first
+        same_indices("ICP's first search", h1["nearest"], fx.pose_point32(d["T0"][keep32], P32))
     last = one
     if iterations == 2:
         two = run_icp(ctx, P, Q, stride, D["w"], D["T0"], md, 2, b, n, m)

@@ -1,6 +1,9 @@
 """three_nn, three_interpolate, interpolate_features and propagate_features on the GPU.  Distances, indices and weights are compared
 EXACTLY with the numpy restatement of the definition (tests/three_nn_ref.py), indices with the reference's recorded ones outside
-near_tie (G24); interpolation and backward within the bounds derived there -- all through the checks of tests/test_three_nn_host.py, on
+near_tie (G24); interpolation and backward BIT FOR BIT with interpolate32 / backward32, the defined order of fused multiply-adds
+restated through tests/f32_exact.py, in both layouts and on every shape of the lists (D = 257: the channel-last backward's second
+channel pass; N = 1023, 1024, 1025: its LDS tile; S either side of 16 and 64; batches beyond the grid; h = 3N hits and none), and
+beside that within the bounds derived there -- all through the checks of tests/test_three_nn_host.py, on
 its shape lists, through the Python surface and through the raw C ABI into buffers pre-filled with -1 / NaN, with `weight` asked for
 and omitted.  Then autograd, determinism and replay from a graph, the composition, the documented errors and the warn-once, and the
 speed condition against the torch spelling the feature replaces."""
@@ -103,6 +106,7 @@ def abi_fwd(feat, idx, weight, channels_first, dev):
     out = torch.full((b, d, n) if channels_first else (b, n, d), float("nan"), device=dev)
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     _lib.check(lib.so3_three_interpolate_f32(_ptr(f), _ptr(i), _ptr(w), _ptr(out), int(channels_first), b, n, s, d, st), "so3_three_interpolate_f32")
+    assert _last_kernel() == "k_three_interp<%s>" % ("true" if channels_first else "false")
     return out.cpu().numpy()
 
 
@@ -143,9 +147,9 @@ def test_search_shapes_equal_the_restatement_and_reach_every_instantiation(dev):
 @pytest.mark.parametrize("kind", ["surface", "abi"])
 def test_interpolation_shapes_in_both_layouts(dev, kind):
     _, fwd, bwd = _runners(kind, dev)
-    for c in host.interp_shape_cases():
+    for i, c in enumerate(host.interp_shape_cases()):
         for channels_first in (False, True):
-            got, _ = host.check_interp(c["name"], fwd, bwd, c, channels_first)
+            got, _ = host.check_interp(c["name"], fwd, bwd, c, channels_first, host.interp_expected32(i))
             if c["name"] == "an unknown point that is a known point":
                 got = got.transpose(0, 2, 1) if channels_first else got
                 own = c["feat"][0][c["idx"][0, :, 0]]
@@ -192,6 +196,10 @@ def test_gradient_against_autograd_through_the_float64_restatement(dev, channels
     bound = bound.transpose(1, 2) if channels_first else bound
     assert (out.double() - want_out.detach()).abs().max().item() < 1e-5
     assert ((got.double() - want).abs() <= bound).all(), ((got.double() - want).abs().max().item())
+    # autograd's gradient is the C ABI's, bit for bit, and both are the defined order's
+    direct = abi_bwd(grad.contiguous().cpu().numpy(), idx.cpu().numpy(), w.cpu().numpy(), s, channels_first, dev)
+    assert np.array_equal(host.bits(got.cpu().numpy()), host.bits(direct))
+    assert np.array_equal(host.bits(direct), host.bits(ref.backward32(grad.contiguous().cpu().numpy(), idx.cpu().numpy(), w.cpu().numpy(), s, channels_first)))
     with pytest.raises(RuntimeError, match="differentiate twice|double backward"):
         f2 = feat.detach().clone().requires_grad_(True)
         o2 = pa.three_interpolate(f2, idx, w, channels_first)

@@ -272,7 +272,7 @@ def check_forward(name, run_fwd, xyz, centres, feat, idx, channels_first, featur
 
 def check_backward(name, run_bwd, grad, idx, n, d, channels_first, features_first, exact, want32=None, want64=None, subsets=True):
     """run_bwd(grad, idx, n, d, channels_first, features_first, (want_xyz, want_centres, want_feat)) -> (grad_xyz, grad_centres, grad_feat),
-    None where not requested; buffers start as NaN.  exact: the float32 order bit for bit (the host model); otherwise the bound."""
+    None where not requested; buffers start as NaN.  exact: the float32 order bit for bit beside the bound (the host model and the device both run with it)."""
     want32 = ref.backward(grad, idx, n, channels_first, features_first, np.float32) if want32 is None else want32
     want64 = ref.backward(grad, idx, n, channels_first, features_first, np.float64) if want64 is None else want64
     bound = ref.bounds(want64, channels_first)

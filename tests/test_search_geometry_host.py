@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import add_metrics_ref as aref
+import f32_exact as fx
 import icp_ref
 import search_geometry_ref as geo
 import test_add_metrics_host as ahost
@@ -146,7 +147,11 @@ def test_host_add_metrics_at_every_edge(adds_model, case_id):
     c = CASES[case_id]
     tg, tp, pts = geo.adds_inputs(c["b"], c["n_adds"], 600 + geo.IDS.index(case_id))
     case = adds_case(tg.numpy(), tp.numpy(), pts.numpy())
-    f = ahost.figures(case, ahost.host_run(adds_model, case))
+    got = ahost.host_run(adds_model, case)
+    f = ahost.figures(case, got)
+    # the defined bits: both clouds through pose_point's fmaf order, pair_dist2, the first of equal candidates -- indices EQUAL
+    posed = [fx.pose_point32(case[k].reshape(-1, 16)[:, :12], case["pts"]) for k in ("tgt", "tpred")]
+    assert np.array_equal(got["nearest"], geo.nearest32(*posed)), case_id
     print("host %-8s " % case_id + "  ".join("%s %.2e" % kv for kv in f.items()))
     for k, v in f.items():
         assert v <= ahost.BOUNDS[k], (case_id, k, v, ahost.BOUNDS[k])
@@ -181,6 +186,7 @@ def test_host_icp_at_every_edge(icp_model, case_id, shared):
     X = icp_ref.pose_points(case["P"], R0, t0)
     dmin, idx = icp_ref.nearest64(X, case["Q"])
     f = ihost.search_figures(X, case["Q"], got["dist"], got["nearest"], dmin)
+    assert d["R0"] is None and np.array_equal(got["nearest"], geo.nearest32(case["P"], case["Q"])), case_id      # unposed: the raw points' defined bits
     unique = geo.unique_step(icp_ref.step_from(case["P"], case["Q"], idx, dmin, R0, t0, case["w"], None))
     f.update(split_step_figures(case["P"], case["Q"], case["w"], R0, t0, None, got, unique))
     print("host %-8s %-6s " % (case_id, "shared" if shared else "own") + "  ".join("%s %.2e" % kv for kv in f.items()))
@@ -204,6 +210,8 @@ def test_host_icp_on_the_whole_of_g4(icp_model):
         one = ihost.host_run(icp_model, icp_case(c, d, shared, md, 1))
         two = ihost.host_run(icp_model, icp_case(c, d, shared, md, 2))
         assert np.array_equal(two["rmse"][0], one["rmse"][0]) and np.array_equal(two["inliers"][0], one["inliers"][0])
+        T0 = np.concatenate([d["R0"], d["t0"][:, :, None]], 2).reshape(-1, 12)       # the first search: the source through pose_point32, indices EQUAL
+        assert np.array_equal(one["nearest"], geo.nearest32(fx.pose_point32(T0, P), Q)), shared
         for got, (Ra, ta), it in ((one, (R0, t0), 0), (two, (one["R"].astype(np.float64), one["t"].astype(np.float64)), 1)):
             X = icp_ref.pose_points(P, Ra, ta)
             dmin, idx = icp_ref.nearest64(X, Q)

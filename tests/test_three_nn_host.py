@@ -8,10 +8,12 @@ The search's arithmetic is a definition (include/so3proj.h), so distances, indic
   2  its indices equal the ones the reference's own code produced (G24) outside near_tie -- the reference takes its distances from
      |a|^2 + |b|^2 - 2 a.b, so two candidates within 2e-6 can swap there.  The mask may cover at most 1 % of a case's rows (re-asserted
      here: exclusions cannot hide a failure); inside it rows must still be in range, distinct and non-decreasing in dist2;
-  3  interpolated values lie within 8 * 2^-24 * sum_k w_k |f_k| of the float64 restatement, and within ref_dev + that bound of the
-     reference's recorded output outside near_tie | near_zero (not for the subset case: its reference weights are noise);
-  4  the backward lies within (h + 2) * 2^-24 * sum |w g| of the float64 restatement for a known point with h hits, and is exactly 0 for
-     a known point nobody selected.
+  3  interpolated values equal interpolate32 (the defined fma order through tests/f32_exact.py) bit for bit, lie within
+     8 * 2^-24 * sum_k w_k |f_k| of the float64 restatement, and within ref_dev + that bound of the reference's recorded output
+     outside near_tie | near_zero (not for the subset case: its reference weights are noise);
+  4  the backward equals backward32 (fused multiply-adds from +0 in ascending (n, k)) bit for bit, lies within
+     (h + 2) * 2^-24 * sum |w g| of the float64 restatement for a known point with h hits, and is exactly 0 for a known point nobody
+     selected.
 tests/test_gpu_three_nn.py imports the shape lists and the checks and runs them on the device."""
 import ctypes
 import functools
@@ -82,7 +84,8 @@ def interp_shape_cases():
     from them.  D in {1, 3, 63, 64, 65, 257} (257: one above the channel-last backward's 256 channels per pass, and five 64-channel
     groups of the channel-first one); N around the channel-first backward's tile (64) and the channel-last one's (1024); S around the 16
     and 64 known points of a backward work item; batches beyond the grid of every launch; a known point selected by every unknown point in
-    all three slots (h = 3 N hits) beside known points selected by none; an unknown point that is a known point."""
+    all three slots (h = 3 N hits) beside known points selected by none; an unknown point that is a known point; a 600-hit chain whose
+    last hit is far inside the backward's any-order bound (what only the bit comparison sees)."""
     rng = np.random.default_rng(2402)
     out = []
 
@@ -108,6 +111,12 @@ def interp_shape_cases():
     known = np.stack(np.meshgrid(*[np.arange(3.0)] * 3, indexing="ij"), -1).reshape(1, 27, 3) * 0.5      # a grid: every other distance is >= 0.25
     add("an unknown point that is a known point", 1, 27, 27, 6, xyz=(known[:, ::-1], known))
     out[-1]["feat"] = np.ascontiguousarray(rng.uniform(1, 2, (1, 27, 6)), np.float32)
+    # what only the bit comparison sees: a chain of 600 hits whose LAST hit weighs 1e-4 -- at most a fortieth of the backward's any-order
+    # bound (602 * 2^-24 * sum |w g|) and typically forty ulps of the running sum.  Dropping it, or taking it twice, stays inside the
+    # bound and changes the bits (test_the_shape_lists_hold_what_they_promise).  Added last: the cases above keep their random streams.
+    small = rng.uniform(0.25, 1, (1, n, 3))
+    small[0, -1, 2] = 1e-4
+    add("h = 3N hits, the last a small one", 1, n, s, 70, np.zeros((1, n, 3), np.int64), small)
     return out
 
 
@@ -139,6 +148,11 @@ def test_the_shape_lists_hold_what_they_promise():
     hits = {c["name"]: ref.backward(c["grad"], c["idx"], c["weight"], c["feat"].shape[1])[2] for c in interp_shape_cases()}
     h = hits["h = 3N hits and none"]
     assert h[0, 0] == 600 and (h[0, 1:] == 0).all() and (h[1, :2] == 0).all()
+    c = interp_shape_cases()[-1]
+    want, bound, h = ref.backward(c["grad"], c["idx"], c["weight"], c["feat"].shape[1])
+    last = np.abs(np.float64(c["weight"][0, -1, 2]) * c["grad"][0, -1])                 # the last hit of known point 0's chain, per channel
+    assert c["name"].startswith("h = 3N hits, the last") and h[0, 0] == 600 and (last < bound[0, 0] / 10).all()       # far inside the bound ...
+    assert (last > 2 * np.spacing(np.abs(want[0, 0]).astype(np.float32))).mean() > 0.9                                # ... and above the sum's ulp
 
 
 # ---- the boundary ---------------------------------------------------------------------------------------------------------
@@ -253,21 +267,45 @@ def check_nn(name, run_nn, xyz1, xyz2, want=None):
     return d3, idx, w
 
 
-def check_interp(name, run_fwd, run_bwd, c, channels_first):
-    """run_fwd(feat, idx, weight, channels_first) -> out; run_bwd(grad, idx, weight, s, channels_first) -> grad_feat, in the layout asked for."""
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def expected32(c):
+    """(out, grad_feat) of an interpolation case in the DEFINED float32 order, channel-last; the other layout is their transpose (the
+    arithmetic of an element does not depend on the layout)."""
+    return ref.interpolate32(c["feat"], c["idx"], c["weight"]), ref.backward32(c["grad"], c["idx"], c["weight"], c["feat"].shape[1])
+
+
+@functools.lru_cache(maxsize=None)
+def interp_expected32(i):
+    return expected32(interp_shape_cases()[i])
+
+
+def check_interp(name, run_fwd, run_bwd, c, channels_first, want32=None):
+    """run_fwd(feat, idx, weight, channels_first) -> out; run_bwd(grad, idx, weight, s, channels_first) -> grad_feat, in the layout asked
+    for.  Both bit for bit with the float32 restatement of the defined order (want32: expected32's pair, when it is at hand), and
+    beside that within the derived bounds of the float64 restatement."""
     feat, grad = layouts(c, channels_first)
     s = c["feat"].shape[1]
+    out32, grad32 = (a.transpose(0, 2, 1) if channels_first else a for a in (expected32(c) if want32 is None else want32))
     want, bound = ref.interpolate(feat, c["idx"], c["weight"], channels_first)
     got = np.asarray(run_fwd(feat, c["idx"], c["weight"], channels_first))
     assert got.dtype == np.float32 and got.shape == want.shape, name
     assert (np.abs(got - want) <= bound).all(), (name, channels_first, np.abs(got - want).max(), (np.abs(got - want) - bound).max())
+    assert np.array_equal(bits(got), bits(out32)), (name, channels_first, "out", int((bits(got) != bits(out32)).sum()), np.argwhere(bits(got) != bits(out32))[:4])
     want_g, bound_g, hits = ref.backward(grad, c["idx"], c["weight"], s, channels_first)
     got_g = np.asarray(run_bwd(grad, c["idx"], c["weight"], s, channels_first))
     assert got_g.dtype == np.float32 and got_g.shape == want_g.shape, name
     assert (np.abs(got_g - want_g) <= bound_g).all(), (name, channels_first, np.abs(got_g - want_g).max(), (np.abs(got_g - want_g) - bound_g).max())
+    assert np.array_equal(bits(got_g), bits(grad32)), (name, channels_first, "grad_feat", int((bits(got_g) != bits(grad32)).sum()),
+                                                       np.argwhere(bits(got_g) != bits(grad32))[:4])
     untouched = np.broadcast_to((hits == 0)[:, None, :] if channels_first else (hits == 0)[:, :, None], got_g.shape)
     assert (got_g[untouched] == 0).all(), name                                      # exactly 0 (and written: the buffers start as NaN)
     return got, got_g
+
+
+G24_EXPECTED32 = {}
 
 
 def check_against_g24(g24_cases, run_nn, run_fwd, run_bwd):
@@ -280,8 +318,11 @@ def check_against_g24(g24_cases, run_nn, run_fwd, run_bwd):
         ref.row_properties(d3, idx, s)                                                                           # in the mask as well
         rng = np.random.default_rng(2403)
         case = {"feat": c["feat"], "idx": idx, "weight": w, "grad": rng.standard_normal(c["xyz1"].shape[:2] + (ref.D_FIXTURE,)).astype(np.float32)}
+        if c["name"] not in G24_EXPECTED32:                  # computed once: the host model and the device's two routes share it
+            G24_EXPECTED32[c["name"]] = expected32(case)
+        want32 = G24_EXPECTED32[c["name"]]
         for channels_first in (False, True):
-            got, _ = check_interp(c["name"], run_fwd, run_bwd, case, channels_first)                             # 3, 4
+            got, _ = check_interp(c["name"], run_fwd, run_bwd, case, channels_first, want32)                     # 3, 4
             if c["kind"] == "subset":
                 continue                                                                                         # indices only
             got = got.transpose(0, 2, 1) if channels_first else got
@@ -357,9 +398,9 @@ def test_host_model_equals_the_restatement_however_the_scan_is_split(model):
 
 
 def test_host_model_interpolation_and_backward_on_the_shape_lists(model):
-    for c in interp_shape_cases():
+    for i, c in enumerate(interp_shape_cases()):
         for channels_first in (False, True):
-            got, _ = check_interp(c["name"], lambda *a: model_fwd(model, *a), lambda *a: model_bwd(model, *a), c, channels_first)
+            got, _ = check_interp(c["name"], lambda *a: model_fwd(model, *a), lambda *a: model_bwd(model, *a), c, channels_first, interp_expected32(i))
             if c["name"] == "an unknown point that is a known point":
                 got = got.transpose(0, 2, 1) if channels_first else got
                 own = c["feat"][0][c["idx"][0, :, 0]]

@@ -5,16 +5,21 @@ restated in numpy from their DEFINITION (include/so3proj.h), and the fixture's l
     neighbours: the three smallest d, among equal d the lower index first = the first three of a STABLE argsort along s;
                 S < 3: the real neighbours first, the other slots repeat slot 0's index with d = +inf
     weights:    r_k = 1 / (d_k + 1e-8) in float32 (0 for a padded slot), w_k = r_k / ((r_0 + r_1) + r_2)
-These three are exact: the kernels and the host model must reproduce them bit for bit.  The interpolation and its backward are
-evaluated in float64 FROM those float32 d and w, and compared within bounds derived from the kernels' fixed order of operations:
-    out = fma(w2, f2, fma(w1, f1, w0 * f0)): three roundings on float32 inputs, each at most 2^-24 relative of a partial result
-          no larger than sum_k w_k |f_k| -> 3 * 2^-24 * sum_k |w_k f_k| to first order.  INTERP_ULPS = 8 is the issue's constant (two
-          products and two sums, without fused operations); the fused order is inside it.
-    grad_feat[s] = h fused multiply-adds in ascending (n, k): h roundings, each at most 2^-24 of a partial sum no larger than
-          sum |w g| -> h * 2^-24 * sum |w g|; the bound used is (h + 2)."""
+These three are exact: the kernels and the host model must reproduce them bit for bit.  So are the interpolation and its backward, whose
+order of operations is part of the definition (so3_device.h: three_interp, three_interp_bwd_add); interpolate32 and backward32 restate
+them through tests/f32_exact.py's fma32, and the host model and the device are held to those bits:
+    out = fma(w2, f2, fma(w1, f1, w0 * f0)),    grad_feat[s] = h fused multiply-adds from +0 in ascending (n, k).
+The float64 evaluation FROM the float32 d and w stays beside them as the check that the defined order is an accurate one:
+    out:  three roundings on float32 inputs, each at most 2^-24 relative of a partial result no larger than sum_k w_k |f_k|
+          -> 3 * 2^-24 * sum_k |w_k f_k| to first order.  INTERP_ULPS = 8 is the issue's constant (two products and two sums, without
+          fused operations); the fused order is inside it.
+    grad_feat[s]: h roundings, each at most 2^-24 of a partial sum no larger than sum |w g| -> h * 2^-24 * sum |w g|; the bound used
+          is (h + 2)."""
 import os
 
 import numpy as np
+
+from f32_exact import fma32
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g24_three_nn.npz")
 EPS = np.float32(1e-8)
@@ -88,6 +93,33 @@ def backward(grad_out, idx, weight, s, channels_first=False):
             np.add.at(hits[bb], idx[bb, :, k], 1)
     bound = (hits[..., None] + 2) * U * mag
     return (grad.transpose(0, 2, 1), bound.transpose(0, 2, 1), hits) if channels_first else (grad, bound, hits)
+
+
+def interpolate32(feat, idx, weight, channels_first=False):
+    """The DEFINED bits (so3_device.h: three_interp): out = fma(w2, f2, fma(w1, f1, w0 * f0)) in float32, the product rounded on its own.
+    -> float32 (B, N, D), or (B, D, N) with channels_first."""
+    f = np.asarray(feat, np.float32)
+    f = f.transpose(0, 2, 1) if channels_first else f
+    g = np.stack([fb[ib] for fb, ib in zip(f, np.asarray(idx, np.int64))])          # (B, N, 3, D)
+    w = np.asarray(weight, np.float32)[..., None]
+    out = fma32(w[:, :, 2], g[:, :, 2], fma32(w[:, :, 1], g[:, :, 1], w[:, :, 0] * g[:, :, 0]))
+    return np.ascontiguousarray(out.transpose(0, 2, 1)) if channels_first else out
+
+
+def backward32(grad_out, idx, weight, s, channels_first=False):
+    """The DEFINED bits (so3_device.h: three_interp_bwd_add): every known point's running sum starts at +0 and takes its hits in
+    ascending (n, k) through acc = fma(w, g, acc).  One step per (n, k), all clouds and channels at once.
+    -> float32 (B, S, D), or (B, D, S) with channels_first."""
+    g = np.asarray(grad_out, np.float32)
+    g = g.transpose(0, 2, 1) if channels_first else g                              # (B, N, D)
+    idx, w = np.asarray(idx, np.int64), np.asarray(weight, np.float32)
+    b, n, d = g.shape
+    acc, rows = np.zeros((b, s, d), np.float32), np.arange(b)
+    for nn in range(n):
+        for k in range(3):
+            at = idx[:, nn, k]
+            acc[rows, at] = fma32(w[:, nn, k, None], g[:, nn], acc[rows, at])
+    return np.ascontiguousarray(acc.transpose(0, 2, 1)) if channels_first else acc
 
 
 def masks(xyz1, xyz2):
