@@ -501,10 +501,19 @@ int so3_cloud_diameter_f32(const float *points, float *work, float *diam, int64_
 /* ---- next row: per-class evaluation statistics on K4's angles ----------------------
  * Replaces the host-side numpy block of 3D-Pose/test_per_class.py:174-216 (np.mean / np.median / np.std / np.max
  * and the accuracy thresholds (x < 30|15|7.5).sum()/len(x)), which the reference feeds one sample at a time.
- *   deg       in  B float64 angles (degrees), e.g. so3_angle_error's per-row output
+ *   deg       in  B float64 angles (degrees), e.g. so3_angle_error's per-row output: not negative.  -0.0 counts as +0.0 (in the
+ *                 median and the max as in the sums); NEGATIVE angles are outside the contract (they are ordered as 0 but summed
+ *                 as they are); +inf and NaN are answered as numpy answers them, see below
  *   cls       in  optional B int32 class ids in [0, ncls) (NULL: one class); rows with other ids are ignored
  *   stats     out ncls x 8 doubles: count, mean, std (population, as np.std), max, median (EXACT: radix select
- *                 on the float64 bits, the two middle elements averaged as np.median does), acc<30, acc<15, acc<7.5
+ *                 on the float64 bits, the two middle elements averaged as np.median does), acc<30, acc<15, acc<7.5.
+ *                 std is the one-pass sqrt(S2/m - (S1/m)^2) over float64 sums: |std^2 - np.var(x)| <= c D 2^-53 (mean(x^2) + mean(x)^2),
+ *                 D = B / (8 x workgroups) + workgroups + 49 the additions a row's value passes (workgroups = min(ceil(B/2048),
+ *                 CUs)), c = 0.13 (never above 2 and a little) -- about 1e-11 deg^2 at a million rows of tens
+ *                 of degrees: a distribution whose std is below ~1e-7 of its mean gets no correct digit of it (0 where the
+ *                 difference comes out negative).
+ *                 An EMPTY class reports count 0 and NaN in every other field.  A class holding +inf reports mean = max = +inf,
+ *                 std = NaN and numpy's median.
  *   workspace     caller-owned scratch of so3_angle_stats_workspace_bytes() bytes (~10 MB: histograms and a buffer for the
  *                 candidates of the medians), ZERO-FILLED ONCE before its first use -- every call leaves its sums and histograms
  *                 zeroed and re-initialises its control words in its first launch --, used by ONE stream at a time (re-zero it

@@ -2993,8 +2993,9 @@ __global__ __launch_bounds__(kBlock) void k_se3_rows(const float *__restrict__ o
 // The workspace is ZERO-FILLED ONCE by the caller and every call leaves it zeroed (the finishers clear what their class used): round
 // 4's zero-fill launch in front of every call is gone.
 // Exact for every input: an edge bin (zeros, denormals, angles above 512 degrees) is selected on all 64 bits, and if a workgroup's
-// staging overflows (more than 4096 of its rows inside the selected bins: e.g. a million equal angles) the finishing workgroups
-// select over the rows themselves (two sweeps, then from LDS).
+// staging overflows (more than 4096 of its rows inside the selected bins: e.g. two million equal angles -- one million over 256
+// workgroups are exactly 4096 each and fit) the finishing workgroups select over the rows themselves (two sweeps, then from LDS).
+// An empty class reports count 0 and NaN elsewhere; -0.0 counts as +0.0; negative angles are outside the contract (include/so3proj.h).
 // What does NOT pay (measured, tools/stats_anatomy.py): one launch for both passes with the rows kept in registers -- the two grid-wide
 // waits it needs cost what the launch boundary does (a ticket takes 3.5 us from the last workgroup's store to the first reader's
 // load); the candidates' first digit voted by the collecting workgroups into a global sub-histogram -- 74 000 same-address atomics
@@ -3053,7 +3054,8 @@ struct StatWork {
 constexpr unsigned int kStatRegion = 4096;         // candidates one workgroup of k_stats_collect can stage in LDS (48 KB)
 static_assert(kStatRegion * 256u <= kCandCap, "what 256 workgroups can stage fits the buffer");
 
-__device__ __forceinline__ unsigned long long angle_key(double a) { return static_cast<unsigned long long>(__double_as_longlong(a < 0 ? 0.0 : a)); }
+// (a <= 0: -0.0, whose pattern 0x8000... would order above every angle, counts as +0.0 too; negative angles are outside the contract)
+__device__ __forceinline__ unsigned long long angle_key(double a) { return static_cast<unsigned long long>(__double_as_longlong(a <= 0 ? 0.0 : a)); }
 
 #ifdef SO3_STATS_STAMP
 #define STAT_STAMP(w, idx) do { if ((blockIdx.x == 0 || blockIdx.x == 100) && threadIdx.x == 0) (w)->cand[kCandCap - 64 + (blockIdx.x ? 32 : 0) + (idx)] = __builtin_amdgcn_s_memrealtime(); } while (0)
@@ -3479,12 +3481,14 @@ __device__ __forceinline__ void stats_finish_class(int c, const double *__restri
     if (threadIdx.x == 0) {
         const double qnan = __longlong_as_double(0x7ff8000000000000ll);
         double *o = stats + c * kStatFields;
+        // an empty class (m == 0 == n): count 0 and NaN for every other field, as the oracle reports it (0/0 below); a class holding
+        // +inf: mean and max +inf, var = inf - inf = NaN and std NaN, as np.std
         const double mean = sel.acc[0][c] / m;
         o[0] = n;
         o[1] = nan > 0 ? qnan : mean;
         const double var = sel.acc[1][c] / m - mean * mean;
-        o[2] = nan > 0 ? o[1] : sqrt(var > 0 ? var : 0.0);                       // np.std: population standard deviation
-        o[3] = nan > 0 ? o[1] : sel.acc[2][c];
+        o[2] = nan > 0 ? o[1] : sqrt(var < 0 ? 0.0 : var);                       // np.std: population standard deviation (a NaN stays one)
+        o[3] = (nan > 0 || m <= 0) ? qnan : sel.acc[2][c];
         o[4] = (nan > 0 || m <= 0) ? qnan : 0.5 * (middle[0] + middle[1]);
         o[5] = sel.below[0][c] / n; o[6] = sel.below[1][c] / n; o[7] = sel.below[2][c] / n;   // (x < t).sum() / len(x)
     }

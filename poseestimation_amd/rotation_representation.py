@@ -2362,15 +2362,22 @@ _STAT_WORKSPACES = {}
 def angle_error_statistics(angles: torch.Tensor, class_ids: torch.Tensor = None, num_classes: int = 1) -> dict:
     """Device-side replacement of the numpy block in 3D-Pose/test_per_class.py:174-216.
 
-    angles: (B,) degrees (e.g. `angle_error(...)`); class_ids: optional (B,) integer ids in [0, num_classes).
+    angles: (B,) degrees (e.g. `angle_error(...)`), not negative (-0.0 counts as +0.0; negative angles are outside the contract);
+    class_ids: optional (B,) integer ids in [0, num_classes) -- rows with other ids, int64 ids beyond int32 included, are ignored.
     Returns {"count","mean","std","max","median","acc30","acc15","acc7.5"} -> (num_classes,) float64 tensors;
-    median is exact (radix select), std is numpy's population std, acc* are (x < t).sum()/len(x)."""
+    median is exact (radix select), std is numpy's population std by the one-pass formula (include/so3proj.h bounds its error: on a
+    distribution much narrower than its mean no digit of it need be right), acc* are (x < t).sum()/len(x).
+    As numpy: an empty class has count 0 and NaN elsewhere; a class holding a NaN has NaN for mean, std, max and median; a class
+    holding +inf has mean = max = +inf and std = NaN."""
     dev = _require_device(angles)
     a = angles.detach().reshape(-1).contiguous().double()
     c = None
     if class_ids is not None:
         _require_device(class_ids)
-        c = class_ids.detach().reshape(-1).contiguous().to(torch.int32)
+        c = class_ids.detach().reshape(-1)
+        if c.dtype is torch.int64:                    # out-of-range ids stay out of range in int32
+            c = c.clamp(-1, num_classes)
+        c = c.contiguous().to(torch.int32)
         if c.numel() != a.numel():
             raise RuntimeError("angle_error_statistics: angles and class_ids differ in length")
     lib = _libh()

@@ -1737,9 +1737,12 @@ def test_angle_error_statistics_match_numpy(rr, n, ncls):
                                   "every row the same", "all rows inside one bin", "one bin, two classes, NaN in one"])
 def test_angle_error_statistics_far_candidates_and_overflow(rr, case):
     """The exact median where the candidates of a class do not fit the finishing workgroup's LDS (one class of 1M rows: 44 000 rows in its
-    middle 1/16-octave bin -- they move into LDS once the first digit has thinned them out) and where a collecting workgroup's region
-    overflows (ties, a distribution narrower than a bin: the finishing workgroup then selects over the rows themselves, and again
-    moves to LDS when few enough are left): bit-equal to np.median every time."""
+    middle 1/16-octave bin -- they move into LDS once the first digit has thinned them out) and where EVERY row of a class is a
+    candidate (ties, a distribution narrower than a bin): bit-equal to np.median every time.  The name says "overflow", the flag
+    word does not: a million rows over 256 workgroups are two blocks of 1024 pairs each, 4096 rows at the most -- a collecting
+    workgroup's staging area exactly full, not overflowing (bit 0 of StatWork::overflow is asserted against the restatement of the
+    split, tests/angle_stats_ref.py, whatever the device's CU count).  The inputs that do overflow, and select over the rows
+    themselves, are tests/test_gpu_angle_stats.py's staging cases."""
     from oracle import so3_oracle as so
     rng = np.random.default_rng(len(case))
     n, ncls = 1_000_000, 1
@@ -1767,18 +1770,36 @@ def test_angle_error_statistics_far_candidates_and_overflow(rr, case):
     for k in ("count", "max", "median", "acc30", "acc15", "acc7.5"):
         assert np.array_equal(got[k].cpu().numpy(), ref[k], equal_nan=True), (k, got[k], ref[k])
     assert np.allclose(got["mean"].cpu().numpy(), ref["mean"], rtol=0, atol=1e-9, equal_nan=True)
+    work = rr._STAT_WORKSPACES[(torch.cuda.current_device(), torch.cuda.current_stream().cuda_stream)]
+    _check_stat_flags(work, ang, cls, ncls)
 
 
 _STAT_ACC_BYTES = 4 * 64 * 4 * 8                   # StatWork (csrc/so3proj.hip): acc[replicas][classes][4] float64 ...
 _STAT_HIST_AT = _STAT_ACC_BYTES + 16 + 64 * 4      # ... overflow, ticket, 2 spare words, class_cursor[64]; then the histograms
 
 
+def _check_stat_flags(work, ang, cls, ncls):
+    """StatWork::overflow and ticket after a call of the shipped library: every workgroup has drawn its ticket, bit 0 (a collecting
+    workgroup staged more than 4096 rows) is what the split of the rows says (tests/angle_stats_ref.py), bit 2 (a wait timed
+    out) may be either.  Returns bit 0."""
+    import angle_stats_ref as ar
+    torch.cuda.synchronize()
+    overflow, ticket = (int(v) for v in work[_STAT_ACC_BYTES:_STAT_ACC_BYTES + 8].cpu().numpy().view(np.uint32))
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    staged = ar.rows_staged_per_workgroup(len(ang), cus, 0, ar.staged_mask(ang, cls, ncls))
+    assert ticket == ar.grid(len(ang), cus), (ticket, len(ang), cus)
+    assert (overflow & 1) == int(staged.max() > ar.STAT_REGION) and overflow & ~5 == 0, (overflow, int(staged.max()))
+    return overflow & 1
+
+
 def test_angle_error_statistics_leave_their_workspace_zeroed(rr):
     """include/so3proj.h: the caller zero-fills so3_angle_stats's workspace ONCE and every call leaves its counted part zeroed -- sums and
     histograms (all replicas, both bin widths); the control words between them (overflow flag, ticket, cursors: 272 bytes) are
     re-initialised by every call's first launch, and the candidate buffer behind is scratch.  One workspace
-    through few classes (bins of 1/64 octave), many (1/16), the 64-class histograms, NaN rows, an overflowing staging area (every row the
-    same) and back: all zeros after every call, and the answers do not depend on what ran before."""
+    through few classes (bins of 1/64 octave), many (1/16), the 64-class histograms, NaN rows, every row a candidate (every row the
+    same: 300 000 rows are at most 4096 per workgroup, so the staging areas fill and do NOT overflow -- the flag word is asserted;
+    tests/test_gpu_angle_stats.py has the inputs that do) and back: all zeros after every call, and the answers do not depend on
+    what ran before."""
     from oracle import so3_oracle as so
     from poseestimation_amd import _lib
     lib = _lib.load()
@@ -1802,6 +1823,8 @@ def test_angle_error_statistics_leave_their_workspace_zeroed(rr):
         assert lib.so3_angle_stats(a.data_ptr(), c.data_ptr(), ncls, stats.data_ptr(), work.data_ptr(), n, st) == 0
         torch.cuda.synchronize()
         assert int(torch.count_nonzero(work[:_STAT_ACC_BYTES]).item()) == 0 and int(torch.count_nonzero(work[_STAT_HIST_AT:counted]).item()) == 0, (ncls, kind)
+        if kind == "same":
+            _check_stat_flags(work, ang, cls, ncls)
         ref = so.angle_statistics_np(ang, cls, ncls)
         got = stats.cpu().numpy()
         for i, k in enumerate(("count", "mean", "std", "max", "median", "acc30", "acc15", "acc7.5")):
