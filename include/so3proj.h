@@ -658,6 +658,41 @@ int so3_chamfer_bwd_f32(const float *X, const float *Y, const int32_t *x_len, co
                         const int32_t *nearest_y, const float *scale_x, const float *scale_y, float *dX, float *dY,
                         uint32_t flags, int64_t B, int32_t N, int32_t M, void *stream);
 
+/* ---- K nearest neighbours between two ragged clouds, with gradients to both (added in 210) ----
+ * Cloud b uses the first n_b = clip(x_len[b], 0, N) points of X and the first m_b = clip(y_len[b], 0, M) points of Y (NULL: all).
+ * The arithmetic is a definition, not an approximation:
+ *     d(i, j) = ((dx * dx) + (dy * dy)) + (dz * dz) from coordinate differences, every operation rounded to float32 on its own, no
+ *     fused multiply-add (so3_three_nn_f32's and so3_fps_f32's distance);
+ *     row i < n_b holds the r = min(K, m_b) smallest candidates j < m_b, ordered "smaller d first, among equal d the lower j first":
+ *     dist2[b][i][k] = d, idx[b][i][k] = j.
+ *   dist2 = 0 and idx = -1 fill every slot k >= r, every slot of a row i >= n_b, every slot of a cloud with m_b == 0, and a slot that
+ *   never received a candidate (non-finite coordinates only: a NaN or +inf d fails every <).  Every element of both outputs is
+ *   written; no buffer needs a zero-fill.  so3_group_points_f32 reads -1 as an empty slot.
+ *   K = 3 with full lengths and M >= 3 gives so3_three_nn_f32's dist2 and idx bit for bit.  K = 1 gives the first argmin of THIS d,
+ *   which is not necessarily so3_nearest_f32's: that search forms d with fused multiply-adds, and two candidates within rounding of
+ *   each other can change places between the two forms.
+ * so3_knn_f32: one launch.
+ *   X        in   B*N*3 float32;   Y  in  cloud b's target at Y + b*y_stride floats (y_stride 0: one target shared by all clouds,
+ *                 otherwise >= 3*M), as so3_nearest_f32;   x_len, y_len  in  optional B int32
+ *   dist2    out  optional B*N*K float32;   idx  out  B*N*K int32 (required)
+ * so3_knn_bwd_f32: one launch, the gradient of dist2 to both clouds as a gather through idx (per-cloud targets: Y is B*M*3).
+ *   Per coordinate c one chain from +0, the difference one rounded subtraction, the doubling exact:
+ *     dX[b][i][c]: over k = 0 .. r-1 ascending,  acc = fma(g[b][i][k], 2 (x_ic - y_jc), acc)  with j = idx[b][i][k];
+ *     dY[b][j][c]: over the entries (i, k), i < n_b, with idx[b][i][k] == j, in ascending (i, k),  acc = fma(g[b][i][k], 2 (y_jc - x_ic), acc).
+ *   A padded slot (-1) contributes nothing.  idx holds -1 or values in [0, m_b); anything else reads nothing out of bounds (dX clamps
+ *   it into [0, m_b), dY ignores it).  Rows i >= n_b of
+ *   dX and j >= m_b of dY, and both gradients of a cloud with n_b == 0 or m_b == 0, are written as zeros.
+ *   idx, grad_dist2  in  B*N*K;   dX, dY  out  B*N*3, B*M*3 float32, each optional, not both NULL.
+ * Nothing synchronises with the host and nothing uses atomics: a call can be captured in a graph and the same inputs give the
+ * same bits.  1 <= K <= SO3_KNN_MAX_K (K > M is legal), 1 <= N, M <= SO3_ADD_S_MAX_N, B as so3_nearest_f32 (0: a no-op).
+ * B, N, M and K are checked first: B == 0 with a K out of range is an error, B == 0 with NULL pointers is not.
+ */
+#define SO3_KNN_MAX_K 64
+int so3_knn_f32(const float *X, const float *Y, int64_t y_stride, const int32_t *x_len, const int32_t *y_len, float *dist2,
+                int32_t *idx, int32_t K, int64_t B, int32_t N, int32_t M, void *stream);
+int so3_knn_bwd_f32(const float *X, const float *Y, const int32_t *x_len, const int32_t *y_len, const int32_t *idx,
+                    const float *grad_dist2, float *dX, float *dY, int32_t K, int64_t B, int32_t N, int32_t M, void *stream);
+
 /* ---- PointNet++ sampling and grouping: farthest-point sampling and ball query (added in 210) ----
  * The reference's point_cloud/pointnet_utils.py: farthest_point_sample (:53-74, a Python loop of npoint iterations) and
  * query_ball_point (:77-97, a (B,S,N) index tensor sorted along N), each as one launch.

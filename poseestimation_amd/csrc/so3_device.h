@@ -1490,4 +1490,39 @@ __device__ __forceinline__ void chamfer_hit(float c, float ux, float uy, float u
     acc[2] = __builtin_fmaf(c, uz, acc[2]);
 }
 
+// ---- K nearest neighbours between two ragged clouds, with gradients to both (so3proj.hip: k_knn, k_knn_bwd;
+// tests/host_model/knn.cpp) ----------------------------------------------------------------------------------------------------------
+// The arithmetic is a DEFINITION (include/so3proj.h): d = pointnet_dist2, a row holds the min(K, m_b) smallest candidates under
+// "smaller d first, among equal d the lower j first".  The sorted list of ONE query lives across the 64 lanes of a wave: lane k holds
+// entry k, (D, J), and starts as (+inf, kKnnNone).  A candidate (d, j) is offered to all lanes at once; (pD, pJ) is the entry of the
+// lane below (lane 0: pD = -inf, which no d is smaller than).  Candidates arrive in ascending j, so the strict < alone gives the tie
+// rule; a NaN or +inf d fails every < and never enters.  Lanes at and above the first entry larger than d shift up by one, the first
+// of them takes the candidate.
+constexpr int kKnnMaxK = 64;                     // include/so3proj.h: SO3_KNN_MAX_K, the lanes of a wave
+constexpr int kKnnNone = -1;
+__device__ __forceinline__ void knn_insert(float d, int j, float &D, int &J, float pD, int pJ) {
+    const bool c = d < D, cp = d < pD;
+    D = c ? (cp ? pD : d) : D;
+    J = c ? (cp ? pJ : j) : J;
+}
+// What slot k of a finished list writes: its neighbour while k < r = min(K, m_b) (0 for a row past n_b or a cloud without targets) and
+// the slot received a candidate, the index clamped into the cloud; otherwise the padding (0, -1).
+__device__ __forceinline__ void knn_finish(int k, int32_t r, int32_t mb, float &D, int &J) {
+    const bool real = k < r && J >= 0;
+    D = real ? D : 0.f;
+    J = real ? (J < mb - 1 ? J : mb - 1) : kKnnNone;
+}
+// The gradient of dist2 is chamfer_phi<true> and chamfer_hit above: per coordinate ONE chain from +0, acc = fma(g_ik, 2 (p - q), acc),
+// over k ascending for a query and over the entries (i, k) that name it, ascending, for a target.
+// k_knn<Q>: the queries one wave serves side by side against every block of 64 candidates it loads (so3proj.hip; DESIGN.md
+// section 7j holds the measurement behind the rule).  A work item is the four waves' 4 Q consecutive queries of one cloud.
+constexpr int kKnnWideQ = 4, kKnnNarrowQ = 1;
+// Sharing a block among four queries pays once the target is long (the loads and block steps it saves grow with M) and there are
+// enough queries to fill the chip with a quarter of the waves; otherwise one query per wave.
+constexpr int64_t kKnnWideQueries = 16384;        // B * N from which ...
+constexpr int kKnnWideTargets = 2048;             // ... and M from which a wave serves kKnnWideQ queries
+inline int knn_queries_per_wave(int64_t B, int32_t N, int32_t M) {
+    return (M >= kKnnWideTargets && B * N >= kKnnWideQueries) ? kKnnWideQ : kKnnNarrowQ;
+}
+
 }  // namespace so3

@@ -2482,6 +2482,174 @@ __global__ __launch_bounds__(kBlock) void k_three_interp_bwd_cf(const float *__r
     }
 }
 
+// ---- K nearest neighbours: a sorted list across the lanes of a wave, and both gradients in one gather -------------------------------
+// The entry of the lane below (wave_shr:1 DPP); lane 0 keeps `below0`.
+__device__ __forceinline__ float lane_below(float v, float below0) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(below0), __float_as_int(v), 0x138, 0xf, 0xf, false));
+}
+__device__ __forceinline__ int lane_below(int v, int below0) { return __builtin_amdgcn_update_dpp(below0, v, 0x138, 0xf, 0xf, false); }
+
+// k_knn<Q>: one wave serves Q queries of one cloud at a time; a work item is the four waves' 4 Q consecutive queries, and the waves of
+// a work item do not meet (no LDS, no barrier).  Lane k holds entry k of every query's sorted list (so3::knn_insert), so K is a
+// run-time, wave-uniform value.  The wave walks the target in blocks of 64 candidates, one per lane, straight from global memory
+// (coalesced; a cloud's target stays in L2 for all its waves) with the next block's loads in flight; the Q query points are
+// wave-uniform.  Per query a lane forms d and tests d < tau = entry K - 1, a ballot collects the block's hits and the wave inserts
+// them in ascending j, each with one DPP move per list register and no memory access.  A hit is not tested again against the tau an
+// earlier hit of its block lowered: inserting a d >= tau changes no lane below K.  Rows past n_b and clouds without a target skip the
+// scan and write the padding (dist2 0, idx -1); lane k < K stores slot k, a row is one contiguous store.
+template <int Q>
+__global__ __launch_bounds__(kBlock) void k_knn(const float *__restrict__ X, const float *__restrict__ Y, int64_t y_stride, const int32_t *__restrict__ x_len,
+                                                const int32_t *__restrict__ y_len, float *__restrict__ dist2, int32_t *__restrict__ idx, int32_t K,
+                                                int64_t B, int32_t N, int32_t M, int32_t chunks) {
+    static_assert(so3::kKnnMaxK == 64 && kBlock % 64 == 0, "one list entry per lane");
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t items = B * chunks;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t b = item / chunks;
+        const int first = (static_cast<int>(item - b * chunks) * (kBlock / 64) + wave) * Q;          // wave-uniform
+        if (first >= N) continue;
+        const int32_t nb = so3::chamfer_length(x_len, b, N), mb = so3::chamfer_length(y_len, b, M);
+        const float *src = X + b * N * 3, *tgt = Y + b * y_stride;
+        const bool live = mb > 0 && first < nb;
+        float D[Q];
+        int J[Q];
+#pragma unroll
+        for (int q = 0; q < Q; ++q) { D[q] = __builtin_huge_valf(); J[q] = so3::kKnnNone; }
+        if (live) {
+            float qx[Q], qy[Q], qz[Q];
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {
+                const int i = min(first + q, nb - 1);                // a slot beyond the cloud repeats its last point; not stored
+                qx[q] = src[i * 3 + 0]; qy[q] = src[i * 3 + 1]; qz[q] = src[i * 3 + 2];
+            }
+            int jn = min(lane, mb - 1);
+            float nx = tgt[jn * 3 + 0], ny = tgt[jn * 3 + 1], nz = tgt[jn * 3 + 2];
+            for (int j0 = 0; j0 < mb; j0 += 64) {
+                const float cx = nx, cy = ny, cz = nz;
+                jn = min(j0 + 64 + lane, mb - 1);                    // the next block, clamped into the cloud
+                nx = tgt[jn * 3 + 0]; ny = tgt[jn * 3 + 1]; nz = tgt[jn * 3 + 2];
+                const bool valid = j0 + lane < mb;
+#pragma unroll
+                for (int q = 0; q < Q; ++q) {
+                    const float d = so3::pointnet_dist2(cx, cy, cz, qx[q], qy[q], qz[q]);
+                    const float tau = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(D[q]), K - 1));
+                    unsigned long long mask = __ballot(valid && d < tau);
+                    while (mask != 0) {                              // ascending j
+                        const int h = __builtin_ctzll(mask);
+                        mask &= mask - 1;
+                        const float dh = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(d), h));
+                        so3::knn_insert(dh, j0 + h, D[q], J[q], lane_below(D[q], -__builtin_huge_valf()), lane_below(J[q], so3::kKnnNone));
+                    }
+                }
+            }
+        }
+        const int32_t r = min(K, mb);
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            const int i = first + q;
+            if (i >= N) break;
+            so3::knn_finish(lane, live && i < nb ? r : 0, mb, D[q], J[q]);
+            if (lane < K) {
+                const int64_t at = (b * N + i) * K + lane;
+                if (dist2 != nullptr) dist2[at] = D[q];
+                idx[at] = J[q];
+            }
+        }
+    }
+}
+
+// k_knn_bwd: both gradients of dist2 as a gather, one launch; the items of dX come first, then dY's, as in k_chamfer_bwd.
+// dX: a lane per query; its chain takes the slots k < r in ascending k (K gathers of 12 bytes), a padded slot (-1) contributes nothing.
+// dY: k_chamfer_bwd's owner scan.  A wave owns 64 consecutive target points, one per lane, and reads the cloud's n_b * K index entries
+//   64 per block, kChamferScanBlocks blocks in flight: an entry names an owner when idx - first < owners (one unsigned compare: -1 and
+//   every other owner fall out).  The hit lanes gather their query point and the entry's g and form the term against the owner's point
+//   (ds_bpermute); the wave walks the ballot in ascending entry order and the owner takes the hit with chamfer_hit (readlane moves).
+// An index is clamped before it addresses anything; no loop bound depends on the data.  No LDS, no atomics, no zero-fill.
+__global__ __launch_bounds__(kBlock) void k_knn_bwd(const float *__restrict__ X, const float *__restrict__ Y, const int32_t *__restrict__ x_len,
+                                                    const int32_t *__restrict__ y_len, const int32_t *__restrict__ idx, const float *__restrict__ grad,
+                                                    float *__restrict__ dX, float *__restrict__ dY, int32_t K, int64_t B, int32_t N, int32_t M,
+                                                    int32_t chunks_x, int32_t chunks_y) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int per = chunks_x + chunks_y;
+    const int64_t items = B * per;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t b = item / per;
+        const int c = static_cast<int>(item - b * per);
+        const bool rev = c >= chunks_x;                              // dY: Y's points own
+        const int32_t full = rev ? M : N;
+        const int first = (rev ? c - chunks_x : c) * kBlock + wave * 64;
+        float *out = rev ? dY : dX;
+        if (out == nullptr || first >= full) continue;
+        const int32_t nb = so3::chamfer_length(x_len, b, N), mb = so3::chamfer_length(y_len, b, M);
+        const int32_t len_p = rev ? mb : nb;
+        const float *xs = X + b * N * 3, *ys = Y + b * M * 3;
+        const int32_t *rows = idx + b * N * K;
+        const float *gs = grad + b * N * K;
+        const int i = first + lane;
+        float acc[3] = {0.f, 0.f, 0.f};
+        const bool live = nb > 0 && mb > 0 && first < len_p;         // wave-uniform
+        if (live && !rev) {
+            const int ic = min(i, nb - 1);
+            const float px = xs[ic * 3 + 0], py = xs[ic * 3 + 1], pz = xs[ic * 3 + 2];
+            const int32_t r = min(K, mb);
+            for (int k = 0; k < r; ++k) {
+                const int jr = rows[static_cast<int64_t>(ic) * K + k];
+                const int j = min(max(jr, 0), mb - 1);
+                float ux, uy, uz;
+                so3::chamfer_phi<true>(px - ys[j * 3 + 0], py - ys[j * 3 + 1], pz - ys[j * 3 + 2], ux, uy, uz);
+                if (jr >= 0) so3::chamfer_hit(gs[static_cast<int64_t>(ic) * K + k], ux, uy, uz, acc);
+            }
+        }
+        if (live && rev) {
+            const int jc = min(i, mb - 1);
+            const float px = ys[jc * 3 + 0], py = ys[jc * 3 + 1], pz = ys[jc * 3 + 2];
+            const unsigned owners = static_cast<unsigned>(min(64, mb - first));
+            const int64_t entries = static_cast<int64_t>(nb) * K;
+            for (int64_t e0 = 0; e0 < entries; e0 += 64 * so3::kChamferScanBlocks) {
+                int named[so3::kChamferScanBlocks];
+#pragma unroll
+                for (int s = 0; s < so3::kChamferScanBlocks; ++s) {
+                    const int64_t e = e0 + 64 * s + lane;
+                    named[s] = e < entries ? rows[e] : -1;
+                }
+#pragma unroll
+                for (int s = 0; s < so3::kChamferScanBlocks; ++s) {
+                    const unsigned rel = static_cast<unsigned>(named[s] - first);
+                    const bool hit = rel < owners;
+                    unsigned long long mask = __ballot(hit);
+                    if (mask == 0) continue;
+                    const int64_t e = min(e0 + 64 * s + lane, entries - 1);
+                    const int owner = static_cast<int>(rel & 63u);
+                    const float ox = __shfl(px, owner, 64), oy = __shfl(py, owner, 64), oz = __shfl(pz, owner, 64);
+                    float ux = 0.f, uy = 0.f, uz = 0.f, g = 0.f;
+                    if (hit) {
+                        const int q = static_cast<int>(e / K);       // the entry's query point, < n_b
+                        so3::chamfer_phi<true>(ox - xs[q * 3 + 0], oy - xs[q * 3 + 1], oz - xs[q * 3 + 2], ux, uy, uz);
+                        g = gs[e];
+                    }
+                    while (mask != 0) {                              // ascending (i, k)
+                        const int h = __builtin_ctzll(mask);
+                        mask &= mask - 1;
+                        const int o = __builtin_amdgcn_readlane(owner, h);
+                        const float hg = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(g), h));
+                        const float hx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ux), h));
+                        const float hy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(uy), h));
+                        const float hz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(uz), h));
+                        if (lane == o) so3::chamfer_hit(hg, hx, hy, hz, acc);
+                    }
+                }
+            }
+        }
+        if (i < full) {
+            const bool keep = live && i < len_p;
+            float *o = out + (b * full + i) * 3;
+            o[0] = keep ? acc[0] : 0.f; o[1] = keep ? acc[1] : 0.f; o[2] = keep ? acc[2] : 0.f;
+        }
+    }
+}
+
 // ---- PointNet++ set abstraction: the grouping gather and its backward -------------------------------------------------------------
 // What sample_and_group does between the ball query and the first Conv2d: gather the grouped coordinates and
 // features, subtract the centre, concatenate, in the layout the caller asks for.  A slot whose index lies outside [0, N) -- an empty
@@ -4765,6 +4933,38 @@ int so3_chamfer_bwd_f32(const float *X, const float *Y, const int32_t *x_len, co
                            nearest_x, nearest_y, scale_x, scale_y, dX, dY, B, N, M, ch.x, ch.y);
     }, (flags & SO3_CHAMFER_UNSQUARED) == 0);
     return check_launch("so3_chamfer_bwd_f32");
+}
+
+int so3_knn_f32(const float *X, const float *Y, int64_t y_stride, const int32_t *x_len, const int32_t *y_len, float *dist2, int32_t *idx, int32_t K,
+                int64_t B, int32_t N, int32_t M, void *stream) {
+    static_assert(SO3_KNN_MAX_K == so3::kKnnMaxK, "the header's limit is the kernel's");
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && M >= 1 && M <= SO3_ADD_S_MAX_N, "so3_knn_f32: B/N/M");
+    SO3_CHECK_ARGS(K >= 1 && K <= SO3_KNN_MAX_K, "so3_knn_f32: K");
+    if (B == 0) return 0;
+    SO3_CHECK_ARGS(y_stride == 0 || y_stride >= static_cast<int64_t>(M) * 3, "so3_knn_f32: y_stride");
+    SO3_CHECK_ARGS(X != nullptr && Y != nullptr && idx != nullptr, "so3_knn_f32: null pointer");
+    with_value<so3::kKnnWideQ, so3::kKnnNarrowQ>(so3::knn_queries_per_wave(B, N, M), [&](auto QQ) {
+        constexpr int kPer = kBlock / 64 * QQ();
+        const int32_t chunks = (N + kPer - 1) / kPer;
+        name_kernel("k_knn", QQ);
+        hipLaunchKernelGGL((k_knn<QQ()>), dim3(static_cast<unsigned>(std::min<int64_t>(B * chunks, kThreeMaxGrid))), dim3(kBlock), 0,
+                           static_cast<hipStream_t>(stream), X, Y, y_stride, x_len, y_len, dist2, idx, K, B, N, M, chunks);
+    });
+    return check_launch("so3_knn_f32");
+}
+
+int so3_knn_bwd_f32(const float *X, const float *Y, const int32_t *x_len, const int32_t *y_len, const int32_t *idx, const float *grad_dist2,
+                    float *dX, float *dY, int32_t K, int64_t B, int32_t N, int32_t M, void *stream) {
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && M >= 1 && M <= SO3_ADD_S_MAX_N, "so3_knn_bwd_f32: B/N/M");
+    SO3_CHECK_ARGS(K >= 1 && K <= SO3_KNN_MAX_K, "so3_knn_bwd_f32: K");
+    if (B == 0) return 0;
+    SO3_CHECK_ARGS(X != nullptr && Y != nullptr && idx != nullptr && grad_dist2 != nullptr && (dX != nullptr || dY != nullptr),
+                   "so3_knn_bwd_f32: null pointer");
+    const ChamferChunks ch = chamfer_chunks(N, M, false, kBlock);
+    name_kernel("k_knn_bwd");
+    hipLaunchKernelGGL(k_knn_bwd, dim3(chamfer_grid(B, ch)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), X, Y, x_len, y_len, idx, grad_dist2, dX,
+                       dY, K, B, N, M, ch.x, ch.y);
+    return check_launch("so3_knn_bwd_f32");
 }
 
 int so3_fps_f32(const float *xyz, const int32_t *start, int32_t *out, int64_t B, int32_t N, int32_t npoint, void *stream) {

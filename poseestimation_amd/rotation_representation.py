@@ -1501,6 +1501,113 @@ def chamfer_distance(X: torch.Tensor, Y: torch.Tensor, x_lengths: torch.Tensor =
 
 
 # --------------------------------------------------------------------------------------------
+# K nearest neighbours between two clouds, differentiable in both
+# --------------------------------------------------------------------------------------------
+def _knn_lengths(name, lengths, b, full, dev):
+    """The lengths as the C ABI takes them: (B,) int32 clipped to [0, full], or None."""
+    if lengths is None:
+        return None
+    _require_device(lengths)
+    if lengths.device != dev or tuple(lengths.shape) != (b,) or lengths.dtype not in (torch.int32, torch.int64):
+        raise ValueError("knn_points: expected %s as a (B,) int32 or int64 tensor on %s for B = %d, got %s %s on %s"
+                         % (name, dev, b, tuple(lengths.shape), lengths.dtype, lengths.device))
+    return lengths.detach().clamp(0, full).to(torch.int32).contiguous()
+
+
+class _KnnPoints(torch.autograd.Function):
+    """knn_points: one so3_knn_f32 launch; the backward is one so3_knn_bwd_f32 launch that gathers both gradients through the stored
+    int32 indices in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, X, Y, k, x_lengths, y_lengths):
+        dev = _require_device(X, Y)
+        ok = X.dim() == 3 and X.shape[-1] == 3 and Y.dim() in (2, 3) and Y.shape[-1] == 3 and (Y.dim() == 2 or Y.shape[0] == X.shape[0])
+        if not ok or not 1 <= X.shape[1] <= _lib.ADD_S_MAX_N or not 1 <= Y.shape[-2] <= _lib.ADD_S_MAX_N:
+            raise ValueError("knn_points: expected a source (B, N, 3) and a target (B, M, 3) or (M, 3) with 1 <= N, M <= %d, got %s and %s"
+                             % (_lib.ADD_S_MAX_N, tuple(X.shape), tuple(Y.shape)))
+        shared = Y.dim() == 2
+        if shared and ctx.needs_input_grad[1]:
+            raise ValueError("knn_points: a shared (M, 3) target takes no gradient; pass Y.expand(B, M, 3) to differentiate in it")
+        x, y = X.detach().contiguous().float(), Y.detach().contiguous().float()
+        b, n, m = x.shape[0], x.shape[1], y.shape[-2]
+        xl = _knn_lengths("x_lengths", x_lengths, b, n, dev)
+        yl = _knn_lengths("y_lengths", y_lengths, b, m, dev)
+        dist2 = torch.empty((b, n, k), dtype=torch.float32, device=dev)
+        idx = torch.empty((b, n, k), dtype=torch.int32, device=dev)
+        with _on_device(dev):
+            _check(_libh().so3_knn_f32(_ptr(x), _ptr(y), 0 if shared else 3 * m, _ptr(xl), _ptr(yl), _ptr(dist2), _ptr(idx), k, b, n, m, _stream(dev)),
+                   "so3_knn_f32")
+        want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if want_x or want_y:
+            ctx.save_for_backward(x, y, xl, yl, idx)
+        ctx.meta = (want_x, want_y, X.dtype, Y.dtype, k, b, n, m)
+        idx64 = idx.long()
+        ctx.mark_non_differentiable(idx64)
+        return dist2.to(X.dtype), idx64
+
+    @staticmethod
+    def backward(ctx, grad_dist2, unused):
+        _no_double_backward(grad_dist2)
+        want_x, want_y, x_dtype, y_dtype, k, b, n, m = ctx.meta
+        if not (want_x or want_y):
+            return None, None, None, None, None
+        x, y, xl, yl, idx = ctx.saved_tensors
+        dev = x.device
+        if y.dim() == 2:                                   # a shared target: the backward takes per-cloud targets
+            y = y.expand(b, m, 3).contiguous()
+        g = grad_dist2.detach().float().contiguous()
+        dx = torch.empty((b, n, 3), dtype=torch.float32, device=dev) if want_x else None
+        dy = torch.empty((b, m, 3), dtype=torch.float32, device=dev) if want_y else None
+        with _on_device(dev):
+            _check(_libh().so3_knn_bwd_f32(_ptr(x), _ptr(y), _ptr(xl), _ptr(yl), _ptr(idx), _ptr(g), _ptr(dx), _ptr(dy), k, b, n, m, _stream(dev)),
+                   "so3_knn_bwd_f32")
+        return None if dx is None else dx.to(x_dtype), None if dy is None else dy.to(y_dtype), None, None, None
+
+
+def knn_points(X: torch.Tensor, Y: torch.Tensor, K: int, x_lengths: torch.Tensor = None, y_lengths: torch.Tensor = None):
+    """For every point of X (B,N,3) its K nearest points of Y (B,M,3): (dist2, idx) with dist2 (B,N,K) the squared distances in
+    ascending order and idx (B,N,K) int64, among equal distances the lower index first.  1 <= K <= KNN_MAX_K (64); K > M is legal.
+
+    x_lengths, y_lengths: optional (B,) int32 / int64 tensors; cloud b uses its first n_b = clip(x_lengths[b], 0, N) and m_b points.
+    dist2 = 0 and idx = -1 fill the slots k >= min(K, m_b), the rows i >= n_b and every slot of a cloud with m_b == 0 -- what
+    knn_gather and group_points read as an empty slot.
+
+    The arithmetic is a definition (include/so3proj.h): d = ((dx * dx) + (dy * dy)) + (dz * dz) from coordinate differences in
+    float32 without fused multiply-add, three_nn's distance: K = 3 gives three_nn's bits, and a point that is in both clouds gets
+    exactly 0.  One launch (so3_knn_f32): a wave keeps a query's sorted list across its lanes, nothing of size N * M is in memory.
+
+    dist2 is differentiable in BOTH clouds (dist2 and the gradients come back in the clouds' dtypes; the arithmetic is float32):
+    one backward launch gathers both gradients through the stored indices in a fixed order, without atomics -- the same inputs give
+    the same bits.  Nothing synchronises with the host, so the call captures into a graph.  idx carries no gradient; double
+    backward is refused.  Y may be ONE (M,3) target shared by the batch, forward only: a shared target that requires grad raises
+    (expand it to (B,M,3) instead)."""
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= _lib.KNN_MAX_K:
+        raise ValueError("knn_points: expected an int 1 <= K <= %d, got %r" % (_lib.KNN_MAX_K, K))
+    return _KnnPoints.apply(X, Y, K, x_lengths, y_lengths)
+
+
+def knn_gather(points: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """points (B,M,C) gathered by knn_points' idx (B,N,K) -> (B,N,K,C); a slot of -1 gives a row of zeros.  Plain torch on the tensors'
+    device, differentiable in points."""
+    if points.dim() != 3 or idx.dim() != 3 or idx.shape[0] != points.shape[0] or idx.dtype not in (torch.int32, torch.int64):
+        raise ValueError("knn_gather: expected points (B, M, C) and idx (B, N, K) (int32 or int64), got %s and %s %s"
+                         % (tuple(points.shape), idx.dtype, tuple(idx.shape)))
+    b, n, k = idx.shape
+    c = points.shape[2]
+    at = idx.long().clamp(min=0).reshape(b, n * k, 1).expand(b, n * k, c)
+    out = points.gather(1, at).reshape(b, n, k, c)
+    return torch.where((idx >= 0)[..., None], out, torch.zeros((), dtype=out.dtype, device=out.device))
+
+
+def knn_group(K: int, xyz: torch.Tensor, new_xyz: torch.Tensor, points, channels_first: bool = False) -> torch.Tensor:
+    """The kNN alternative to query_ball_point + group_points: the K nearest points of xyz (B,N,3) around every centre new_xyz (B,S,3)
+    (knn_points(new_xyz, xyz, K)), grouped by group_points with its layouts: (B,S,K,3 + D), or with channels_first=True (points then
+    (B,D,N)) (B,3 + D,K,S).  Differentiable in xyz, new_xyz and points through the grouping; the indices carry no gradient."""
+    _, idx = knn_points(new_xyz.detach(), xyz.detach(), K)
+    return group_points(xyz, new_xyz, points, idx, channels_first=channels_first)
+
+
+# --------------------------------------------------------------------------------------------
 # PointNet++ sampling and grouping (reference: point_cloud/pointnet_utils.py)
 # --------------------------------------------------------------------------------------------
 def _cloud_f32(name, what, x, width=3):

@@ -218,6 +218,17 @@ def main():
     timeit("so3_chamfer_bwd_f32 (256 x 1024 x 1024, dX + dY)",
            lambda i: lib.so3_chamfer_bwd_f32(p(xi), p(yi), None, None, p(nni), p(nyi), p(sci), p(sci), p(gxi), p(gyi), 0, bi, ni, ni, st), bi * ni * 56, iters=10, warm=2)
     del xi, yi, di, nni, ri, ti, wsi, dyi, nyi, rwi, sci, gxi, gyi, wci
+    # K nearest neighbours at tools/ubench/knn_paths.hip's shapes: the search, then both gradients in one gather (the bytes are the rows')
+    for bk, nk, mk, kk in ((32, 1024, 1024, 16), (32, 512, 128, 8), (8, 4096, 4096, 20)):
+        xk, yk = torch.rand(bk, nk, 3, device=dev), torch.rand(bk, mk, 3, device=dev)
+        dk, ik = torch.empty(bk, nk, kk, device=dev), torch.empty(bk, nk, kk, dtype=torch.int32, device=dev)
+        gk, gxk, gyk = torch.rand(bk, nk, kk, device=dev), torch.empty(bk, nk, 3, device=dev), torch.empty(bk, mk, 3, device=dev)
+        timeit("so3_knn_f32 (%d x %d <- %d, K = %d)" % (bk, nk, mk, kk),
+               lambda i: lib.so3_knn_f32(p(xk), p(yk), 3 * mk, None, None, p(dk), p(ik), kk, bk, nk, mk, st), bk * nk * kk * 8, iters=10, warm=2)
+        timeit("so3_knn_bwd_f32 (%d x %d <- %d, K = %d, dX + dY)" % (bk, nk, mk, kk),
+               lambda i: lib.so3_knn_bwd_f32(p(xk), p(yk), None, None, p(ik), p(gk), p(gxk), p(gyk), kk, bk, nk, mk, st),
+               bk * (nk * kk * 8 + (nk + mk) * 24), iters=10, warm=2)
+    del xk, yk, dk, ik, gk, gxk, gyk
     # PointNet++ sampling and grouping at the reference model's first level: a chain of 511 dependent argmaxes per cloud (one workgroup
     # each: latency bound, most compute units idle at B = 32), and one wave per centre over the cloud (the bytes are the index rows')
     bf, nf, sf, kf = 32, 1024, 512, 64
@@ -242,6 +253,9 @@ def main():
         timeit("three_nn: so3_three_nn_f32 (%s, with weights)" % shape, lambda i: lib.so3_three_nn_f32(p(x1), p(x2), p(d3), p(i3), p(w3), bt, nt, stn, st),
                bt * (nt * 48 + stn * 12), iters=20, warm=3)
         timeit("three_nn: so3_three_nn_f32 (%s, without)" % shape, lambda i: lib.so3_three_nn_f32(p(x1), p(x2), p(d3), p(i3), None, bt, nt, stn, st),
+               bt * (nt * 36 + stn * 12), iters=20, warm=3)
+        dk3, ik3 = torch.empty_like(d3), torch.empty_like(i3)      # the same rows from the K-neighbour kernel, for the record
+        timeit("three_nn: so3_knn_f32 (%s, K = 3)" % shape, lambda i: lib.so3_knn_f32(p(x1), p(x2), 3 * stn, None, None, p(dk3), p(ik3), 3, bt, nt, stn, st),
                bt * (nt * 36 + stn * 12), iters=20, warm=3)
         _lib.check(lib.so3_three_nn_f32(p(x1), p(x2), p(d3), p(i3), p(w3), bt, nt, stn, st), "so3_three_nn_f32")
         ft, gt = torch.randn(bt, stn * dt, device=dev), torch.randn(bt, nt * dt, device=dev)

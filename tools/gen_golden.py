@@ -1242,7 +1242,20 @@ def g27_chamfer():
     assert os.path.getsize(os.path.join(OUT, "g27_chamfer.npz")) <= os.path.getsize(os.path.join(OUT, "g21_icp.npz"))
 
 
+def g28_knn():
+    """knn_points: no reference code exists, so the fixture holds the inputs (clouds of unit radius at the shapes of tests/knn_ref.py:
+    SHAPES, each full and ragged -- an empty source, an empty target, a one-point target and a target shorter than K -- and the exact
+    families: X inside Y with duplicates, an all-equal target, lattice points with exact ties, many-to-one) and the float32
+    restatement's outputs -- tests/knn_ref.py: generate, which asserts the float64 excess bound on every case."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import knn_ref as ref
+    save("g28_knn.npz", **ref.generate())
+    assert os.path.getsize(os.path.join(OUT, "g28_knn.npz")) <= 512 * 1024
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "g28":
+        return g28_knn()
     if len(sys.argv) > 1 and sys.argv[1] == "g27":
         return g27_chamfer()
     if len(sys.argv) > 1 and sys.argv[1] == "g26":
@@ -1297,6 +1310,7 @@ def main():
     g20_rigid_align()
     g21_icp()
     g27_chamfer()
+    g28_knn()
     g22_pointnet()
     g23_head_edges()
     # ---- G1: config #1, 256 Gaussian rows ------------------------------------------------------

@@ -18,17 +18,23 @@ def main():
     text = open(sys.argv[1]).read()
     keys = sys.argv[2:]
     rows = []
-    for m in re.finditer(r"^\s*\.amdhsa_kernel (\S+)(.*?)^\s*\.end_amdhsa_kernel", text, re.S | re.M):
+    for m in re.finditer(r"^[ \t]*\.amdhsa_kernel (\S+)(.*?)^[ \t]*\.end_amdhsa_kernel", text, re.S | re.M):
         name, body = m.group(1), m.group(2)
         get = lambda k: (re.search(r"\.amdhsa_%s (\S+)" % k, body) or [None, "?"])[1]
         rows.append([name, get("next_free_vgpr"), get("accum_offset"), get("next_free_sgpr"), get("group_segment_fixed_size"), get("private_segment_fixed_size")])
-    # the comment block after each function has the spill counts
-    spills = {}
-    for m in re.finditer(r"; Kernel info:.*?; Function info:|^(\S+):\s*; @(\S+).*?; ScratchSize: (\d+).*?; Occupancy: (\d+)", text, re.S | re.M):
-        if m.group(2):
-            spills[m.group(2)] = (m.group(3), m.group(4))
-    for m in re.finditer(r"; @(\S+)\n.*?; NumVgprs: (\d+)\n; NumAgprs: (\d+)\n.*?; ScratchSize: (\d+)\n; Occupancy: (\d+)", text, re.S):
-        spills[m.group(1)] = (m.group(4), m.group(5), m.group(2), m.group(3))
+    # the comment block after each function has the spill counts: one pass over the lines (a lazy multi-line pattern is quadratic on
+    # the library's 16 MB listing)
+    spills, current, info = {}, None, {}
+    for line in text.split("\n"):
+        m = re.match(r"(\S+):\s*; @(\S+)", line)
+        if m:
+            current, info = m.group(2), {}
+            continue
+        m = re.match(r"; (NumVgprs|NumAgprs|ScratchSize|Occupancy): (\d+)", line)
+        if m and current is not None:
+            info[m.group(1)] = m.group(2)
+            if m.group(1) == "Occupancy":
+                spills[current] = (info.get("ScratchSize", "?"), info["Occupancy"], info.get("NumVgprs", "?"), info.get("NumAgprs", "?"))
     dm = demangle([r[0] for r in rows])
     print("%-6s %-6s %-6s %-7s %-8s %-4s  kernel" % ("vgpr", "agpr0", "sgpr", "lds", "scratch", "occ"))
     for r in rows:
