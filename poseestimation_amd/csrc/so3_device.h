@@ -1257,12 +1257,16 @@ __device__ __forceinline__ float align_bwd_dw(const float (&k)[kAlignBwdConsts],
 constexpr int kIcpSums = kAlignSums + 2;
 constexpr int kIcpRecord = 20;                   // floats per partial record in the workspace: the sums, padded to five float4
 constexpr int kIcpBlock = 256;                   // lanes per work item (so3proj.hip: kBlock)
-// The points one lane keeps (U in {4, 2, 1}): fewer when the batch alone would not cover the compute units twice.  k_add_s's rule.
-inline int icp_points_per_lane(int64_t B, int32_t N, int64_t cus) {
+// The launch geometry of the search kernels (k_add_s, k_icp_step, k_chamfer_fwd).  A work item is kIcpBlock * u source points of one
+// cloud, so a cloud of N points has search_chunks(N, u) of them.  The points one lane keeps (U in {4, 2, 1}) are halved while the
+// batch's work items do not cover the compute units twice; M counts the source points of a second direction (0: there is none).
+inline int32_t search_chunks(int32_t N, int u) { return (N + kIcpBlock * u - 1) / (kIcpBlock * u); }
+inline int search_points_per_lane(int64_t B, int32_t N, int32_t M, int64_t cus) {
     int u = 4;
-    while (u > 1 && B * ((N + kIcpBlock * u - 1) / (kIcpBlock * u)) < 2 * cus) u >>= 1;
+    while (u > 1 && B * (search_chunks(N, u) + search_chunks(M, u)) < 2 * cus) u >>= 1;
     return u;
 }
+inline int icp_points_per_lane(int64_t B, int32_t N, int64_t cus) { return search_points_per_lane(B, N, 0, cus); }
 // The launch shape of the kernels that give a cloud to a lane or a wave's turn (k_kabsch and its kin, k_add_l1, k_rotate_clouds,
 // k_pc_normalize): enough waves for sixteen per compute unit, at most 64 clouds per wave (one per lane for the SVD), four waves per block.
 inline int clouds_per_wave(int64_t B, int64_t cus) {
@@ -1461,11 +1465,9 @@ inline bool group_bwd_narrow(int32_t D) { return 3 + D <= kGroupNarrowC; }
 //     phi(v) = 2 v  (squared),   v / |v| with 0 at v = 0  (unsquared: sym_add_direction's rule).
 constexpr int kChamferOwners = 64;               // k_chamfer_bwd: the points a wave owns, one per lane
 constexpr int kChamferScanBlocks = 8;            // ... and the 64-entry blocks of the other cloud's `nearest` it keeps in flight
-// The points one lane of k_chamfer_fwd keeps (U in {4, 2, 1}): k_add_s's rule over the work items of BOTH directions.
+// The points one lane of k_chamfer_fwd keeps: search_points_per_lane over the work items of BOTH directions.
 inline int chamfer_points_per_lane(int64_t B, int32_t N, int32_t M, bool single, int64_t cus) {
-    int u = 4;
-    while (u > 1 && B * ((N + kIcpBlock * u - 1) / (kIcpBlock * u) + (single ? 0 : (M + kIcpBlock * u - 1) / (kIcpBlock * u))) < 2 * cus) u >>= 1;
-    return u;
+    return search_points_per_lane(B, N, single ? 0 : M, cus);
 }
 __device__ __forceinline__ int32_t chamfer_length(const int32_t *lengths, int64_t b, int32_t full) {
     if (lengths == nullptr) return full;

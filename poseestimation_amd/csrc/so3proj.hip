@@ -1475,14 +1475,70 @@ __global__ __launch_bounds__(kBlock) void k_add_l1(const float *__restrict__ Tgt
 // ---- ADD-S and the cloud diameter: the N^2 kernel -----------------------------------------------------------------------------------
 // ADDS_b = (1/N) sum_i min_j |x_i - y_j|,  x = T_gt p (outer cloud), y = T_pred p (inner cloud);  diam_b = max_ij |p_i - p_j|.
 // One work item = kBlock * U outer points of one cloud (a cloud is split over workgroups when B is small); a lane keeps U outer points
-// in registers.  The inner cloud goes through LDS in tiles of kAddsTile float4 (posed once per work item by the same pose_point as the
-// outer points), and every lane reads the same float4 per step -- one ds_read_b128 broadcast feeds U pairs.  A tile's tail is padded
-// to the unroll with copies of its last point: a copy never beats the original (strict <, the minimum and the maximum are unchanged).
+// in registers.  The inner cloud goes through tile_search, posed once per work item by the same pose_point as the outer points; one
+// broadcast read feeds U pairs.  A copy of the tile's last point in the padding never beats the original (strict <, the minimum and
+// the maximum are unchanged).
 // The per-point result sqrt(best) goes to point_dist (B,N); k_add_s_rows finishes the rows in a fixed order.  No atomics anywhere.
 constexpr int kAddsTile = 1024;         // 16 KB of LDS per workgroup
 constexpr int kAddsUnroll = 8;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) f32x4 lds_f32x4;
+
+// The tiled broadcast search of k_add_s and k_chamfer_fwd: the workgroup walks a target cloud of `len` points through LDS in tiles of
+// kAddsTile float4, fetch(j) gives target point j for the tile.  A tile's tail is padded to kAddsUnroll with copies of its last point,
+// which never beat the original (strict <; the minimum and the maximum are unchanged).  Every thread then visits every point of the
+// tile in ascending order with the U points (x, y, z) it keeps: add_s_pair leaves the best squared distance and (WANT_INDEX) its
+// index, t0 + k + kk, the point's index in the cloud, not in the tile.  The read is the same address in every lane, a broadcast, and
+// volatile keeps the unused fourth dword in the load: one ds_read_b128 (4 LDS cycles) where the compiler would pick ds_read_b96 (8),
+// which one point per lane cannot hide.  Two barriers per tile: the first also covers whatever the caller kept in the tile after the
+// previous search (item_record).  The search runs in copies of best and idx, as owner_scan's chain does: through the caller's arrays
+// k_chamfer_fwd<., 4> gets the registers of two slots exchanged and its pair loop scheduled around them.
+// k_icp_step and k_three_nn keep this loop written out: called from them, the helper leaves k_icp_step<false, false, false, 4> with an
+// s_nop inside the pair loop and k_three_nn with its selects in another order (profiles/tile_search_refactor_isa.txt).
+template <bool WANT_INDEX, bool DIAMETER, int U, class Fetch>
+__device__ __forceinline__ void tile_search(float4 *tile, int tid, int len, Fetch fetch, const float (&x)[U], const float (&y)[U], const float (&z)[U],
+                                            float (&best)[U], int (&idx)[U]) {
+    float d[U];
+    int n[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) { d[u] = best[u]; n[u] = idx[u]; }
+    for (int t0 = 0; t0 < len; t0 += kAddsTile) {
+        const int cnt = min(kAddsTile, len - t0);
+        const int cntp = (cnt + kAddsUnroll - 1) / kAddsUnroll * kAddsUnroll;      // <= kAddsTile
+        __syncthreads();                                                         // the previous tile has been read
+        for (int k = tid; k < cntp; k += kBlock) tile[k] = fetch(t0 + min(k, cnt - 1));
+        __syncthreads();
+        for (int k = 0; k < cntp; k += kAddsUnroll) {
+#pragma unroll
+            for (int kk = 0; kk < kAddsUnroll; ++kk) {
+                const f32x4 q = *(const volatile lds_f32x4 *)(&tile[k + kk]);
+#pragma unroll
+                for (int u = 0; u < U; ++u) so3::add_s_pair<WANT_INDEX, DIAMETER>(x[u], y[u], z[u], q.x, q.y, q.z, t0 + k + kk, d[u], n[u]);
+            }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) { best[u] = d[u]; idx[u] = n[u]; }
+}
+__device__ __forceinline__ float4 tile_point(const float *cloud, int j) { return make_float4(cloud[j * 3 + 0], cloud[j * 3 + 1], cloud[j * 3 + 2], 0.f); }
+
+// A work item's record of W floats in wave order: lane k < W of every wave brings its wave's sum k, the waves' sums go through the
+// tile the search has finished with, and thread k adds entry k in wave order and writes out[k].
+template <int W>
+__device__ __forceinline__ void item_record(float4 *tile, int tid, float mine, float *out) {
+    float *red = reinterpret_cast<float *>(tile);
+    const int lane = tid & 63, wave = tid >> 6;
+    __syncthreads();                                         // every wave has left the last tile
+    if (lane < W) red[wave * W + lane] = mine;
+    __syncthreads();
+    if (tid < W) {
+        float v = red[tid];
+#pragma unroll
+        for (int wv = 1; wv < kBlock / 64; ++wv) v += red[wv * W + tid];          // in wave order
+        out[tid] = v;
+    }
+}
+
 template <bool WANT_INDEX, bool DIAMETER, int U>
 __global__ __launch_bounds__(kBlock) void k_add_s(const float *__restrict__ Tgt, const float *__restrict__ Tpred, const float *__restrict__ pts,
                                                   float *__restrict__ point_dist, int32_t *__restrict__ nearest, int64_t B, int32_t N,
@@ -1511,32 +1567,12 @@ __global__ __launch_bounds__(kBlock) void k_add_s(const float *__restrict__ Tgt,
             best[u] = DIAMETER ? 0.f : __builtin_huge_valf();
             idx[u] = 0;
         }
-        for (int t0 = 0; t0 < N; t0 += kAddsTile) {
-            const int cnt = min(kAddsTile, N - t0);
-            const int cntp = (cnt + kAddsUnroll - 1) / kAddsUnroll * kAddsUnroll;      // <= kAddsTile
-            __syncthreads();                                                         // the previous tile has been read
-            for (int k = tid; k < cntp; k += kBlock) {
-                const int j = t0 + min(k, cnt - 1);
-                const float px = cloud[j * 3 + 0], py = cloud[j * 3 + 1], pz = cloud[j * 3 + 2];
-                float4 q;
-                if (DIAMETER) { q.x = px; q.y = py; q.z = pz; }
-                else so3::pose_point(mp, px, py, pz, q.x, q.y, q.z);
-                q.w = 0.f;
-                tile[k] = q;
-            }
-            __syncthreads();
-            for (int k = 0; k < cntp; k += kAddsUnroll) {
-#pragma unroll
-                for (int kk = 0; kk < kAddsUnroll; ++kk) {
-                    // the same address in every lane: a broadcast.  Volatile keeps the unused fourth dword in the load: one ds_read_b128
-                    // (4 LDS cycles) where the compiler would pick ds_read_b96 (8), which the one-point-per-lane variant cannot hide
-                    const f32x4 q = *(const volatile lds_f32x4 *)(&tile[k + kk]);
-#pragma unroll
-                    for (int u = 0; u < U; ++u)
-                        so3::add_s_pair<WANT_INDEX, DIAMETER>(x[u], y[u], z[u], q.x, q.y, q.z, t0 + k + kk, best[u], idx[u]);
-                }
-            }
-        }
+        tile_search<WANT_INDEX, DIAMETER>(tile, tid, N,
+            [&](int j) {
+                float4 q = tile_point(cloud, j);
+                if (!DIAMETER) so3::pose_point(mp, q.x, q.y, q.z, q.x, q.y, q.z);
+                return q;
+            }, x, y, z, best, idx);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int i = i_base + u * kBlock + tid;
@@ -1763,14 +1799,13 @@ __global__ __launch_bounds__(kBlock) void k_add_s_bwd(const float *__restrict__ 
 }
 
 // ---- ICP: nearest neighbours between two clouds, fused with rigid_align's sums ------------------------------------------------------
-// k_icp_step is k_add_s's skeleton over two DIFFERENT clouds: one work item = kBlock * U source points of one cloud, the target cloud
-// (M points, its own or one shared by the batch) goes through LDS raw in tiles of kAddsTile float4, every lane reads the same float4
-// per step.  The source points are posed by the current pose (pose == nullptr: the identity, nothing is multiplied); distances come
-// from coordinate differences.  SUMS = false is nearest_neighbors: dist and nearest are all it writes.  SUMS = true is one ICP
-// iteration's first half: after the search a lane gathers q_j(i) (12 B per point, an L2 hit), trims its weight and adds the point to
-// rigid_align's sixteen pivot-relative sums (of the UNPOSED p_i), sum w' d^2 and the inlier count; wave_allsum, the four waves
-// combined through LDS in wave order, one record per work item to rec[b][chunk][.].  k_icp_finish adds a cloud's records in chunk
-// order and writes the next pose.  No atomics anywhere: the same inputs give the same bits.
+// k_icp_step is k_add_s over two DIFFERENT clouds: one work item = kBlock * U source points of one cloud, the target cloud (M points,
+// its own or one shared by the batch) goes through LDS raw, in tile_search's loop written out.  The source points are posed by the current pose (pose ==
+// nullptr: the identity, nothing is multiplied); distances come from coordinate differences.  SUMS = false is nearest_neighbors: dist
+// and nearest are all it writes.  SUMS = true is one ICP iteration's first half: after the search a lane gathers q_j(i) (12 B per
+// point, an L2 hit), trims its weight and adds the point to rigid_align's sixteen pivot-relative sums (of the UNPOSED p_i), sum w' d^2
+// and the inlier count; wave_allsum, then item_record leaves one record per work item in rec[b][chunk][.].  k_icp_finish adds a
+// cloud's records in chunk order and writes the next pose.  No atomics anywhere: the same inputs give the same bits.
 template <bool WEIGHTED, bool TRIMMED, bool SUMS, int U>
 __global__ __launch_bounds__(kBlock) void k_icp_step(const float *__restrict__ P, const float *__restrict__ Q, int64_t q_stride,
                                                      const float *__restrict__ Wt, const float *__restrict__ pose, float max_distance,
@@ -1778,7 +1813,6 @@ __global__ __launch_bounds__(kBlock) void k_icp_step(const float *__restrict__ P
                                                      int64_t B, int32_t N, int32_t M, int32_t chunks) {
     static_assert(kBlock == so3::kIcpBlock, "the host model's chunking");
     __shared__ float4 tile[kAddsTile];
-    float (*red)[so3::kIcpRecord] = reinterpret_cast<float (*)[so3::kIcpRecord]>(tile);      // the waves' sums reuse the tile once it has been read
     const int tid = threadIdx.x;
     const int64_t items = B * chunks;
     for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
@@ -1816,7 +1850,7 @@ __global__ __launch_bounds__(kBlock) void k_icp_step(const float *__restrict__ P
             for (int k = 0; k < cntp; k += kAddsUnroll) {
 #pragma unroll
                 for (int kk = 0; kk < kAddsUnroll; ++kk) {
-                    const f32x4 q = *(const volatile lds_f32x4 *)(&tile[k + kk]);     // k_add_s: the ds_read_b128 broadcast
+                    const f32x4 q = *(const volatile lds_f32x4 *)(&tile[k + kk]);     // tile_search: the ds_read_b128 broadcast
 #pragma unroll
                     for (int u = 0; u < U; ++u)
                         so3::add_s_pair<true, false>(x[u], y[u], z[u], q.x, q.y, q.z, t0 + k + kk, best[u], idx[u]);
@@ -1849,22 +1883,14 @@ __global__ __launch_bounds__(kBlock) void k_icp_step(const float *__restrict__ P
             }
         }
         if (SUMS) {
-            const int lane = tid & 63, wave = tid >> 6;
-            float mine = 0.f;                                    // lane k < kIcpSums keeps sum k of its wave
+            const int lane = tid & 63;
+            float mine = 0.f;                                    // lane k < kIcpSums keeps sum k of its wave, the record's padding 0
 #pragma unroll
             for (int k = 0; k < so3::kIcpSums; ++k) {
                 const float tot = wave_allsum(acc[k]);
                 mine = lane == k ? tot : mine;
             }
-            __syncthreads();                                     // every wave has left the last tile
-            if (lane < so3::kIcpRecord) red[wave][lane] = lane < so3::kIcpSums ? mine : 0.f;
-            __syncthreads();
-            if (tid < so3::kIcpRecord) {
-                float v = red[0][tid];
-#pragma unroll
-                for (int wv = 1; wv < kBlock / 64; ++wv) v += red[wv][tid];          // in wave order
-                rec[(b * chunks + chunk) * so3::kIcpRecord + tid] = v;
-            }
+            item_record<so3::kIcpRecord>(tile, tid, lane < so3::kIcpSums ? mine : 0.f, rec + (b * chunks + chunk) * so3::kIcpRecord);
         }
     }
 }
@@ -1921,12 +1947,12 @@ __global__ __launch_bounds__(kBlock) void k_icp_initial_pose(const float *__rest
 }
 
 // ---- Chamfer distance: both searches in one launch, both gradients in one gather ---------------------------------------------------
-// k_chamfer_fwd is k_icp_step<.., SUMS = false, U>'s skeleton over the work items of BOTH directions: a cloud has chunks_x items
-// that search Y for kBlock * U points of X, then chunks_y items that search X for points of Y (chunks_y = 0: x direction only).  The
-// clouds are ragged: a cloud uses its first n_b / m_b points (wave-uniform, scalar loads), the tile loop runs to the target's own
-// length, slots past the source's length read dist 0 and nearest -1.  A work item leaves the sum of its points' terms in rec[item]:
-// lane-wise in slot order, wave_allsum, the four waves in wave order.  k_chamfer_rows adds a cloud's records in chunk order in float64
-// and WRITES rows (B,2) = the two directions' means.  No atomics, no zero-fill.
+// k_chamfer_fwd is k_icp_step<.., SUMS = false, U> over the work items of BOTH directions: a cloud has chunks_x items that search Y
+// for kBlock * U points of X, then chunks_y items that search X for points of Y (chunks_y = 0: x direction only).  The clouds are
+// ragged: a cloud uses its first n_b / m_b points (wave-uniform, scalar loads), tile_search runs to the target's own length, slots
+// past the source's length read dist 0 and nearest -1.  A work item leaves the sum of its points' terms in rec[item]: lane-wise in
+// slot order, wave_allsum, item_record.  k_chamfer_rows adds a cloud's records in chunk order in float64 and WRITES rows (B,2) = the
+// two directions' means.  No atomics, no zero-fill.
 template <bool SQUARED, int U>
 __global__ __launch_bounds__(kBlock) void k_chamfer_fwd(const float *__restrict__ X, const float *__restrict__ Y, const int32_t *__restrict__ x_len,
                                                         const int32_t *__restrict__ y_len, float *__restrict__ dist_x, int32_t *__restrict__ nearest_x,
@@ -1934,7 +1960,6 @@ __global__ __launch_bounds__(kBlock) void k_chamfer_fwd(const float *__restrict_
                                                         int64_t B, int32_t N, int32_t M, int32_t chunks_x, int32_t chunks_y) {
     static_assert(kBlock == so3::kIcpBlock, "the host model's chunking");
     __shared__ float4 tile[kAddsTile];
-    float *red = reinterpret_cast<float *>(tile);                  // the waves' sums reuse the tile once it has been read
     const int tid = threadIdx.x;
     const int per = chunks_x + chunks_y;
     const int64_t items = B * per;
@@ -1960,27 +1985,7 @@ __global__ __launch_bounds__(kBlock) void k_chamfer_fwd(const float *__restrict_
                 x[u] = src[i * 3 + 0]; y[u] = src[i * 3 + 1]; z[u] = src[i * 3 + 2];
                 best[u] = __builtin_huge_valf();
             }
-            for (int t0 = 0; t0 < len_q; t0 += kAddsTile) {
-                const int cnt = min(kAddsTile, len_q - t0);
-                const int cntp = (cnt + kAddsUnroll - 1) / kAddsUnroll * kAddsUnroll;      // <= kAddsTile
-                __syncthreads();                                                         // the previous tile (and the waves' sums in it) has been read
-                for (int k = tid; k < cntp; k += kBlock) {
-                    const int j = t0 + min(k, cnt - 1);
-                    float4 q;
-                    q.x = tgt[j * 3 + 0]; q.y = tgt[j * 3 + 1]; q.z = tgt[j * 3 + 2]; q.w = 0.f;
-                    tile[k] = q;
-                }
-                __syncthreads();
-                for (int k = 0; k < cntp; k += kAddsUnroll) {
-#pragma unroll
-                    for (int kk = 0; kk < kAddsUnroll; ++kk) {
-                        const f32x4 q = *(const volatile lds_f32x4 *)(&tile[k + kk]);     // k_add_s: the ds_read_b128 broadcast
-#pragma unroll
-                        for (int u = 0; u < U; ++u)
-                            so3::add_s_pair<true, false>(x[u], y[u], z[u], q.x, q.y, q.z, t0 + k + kk, best[u], idx[u]);
-                    }
-                }
-            }
+            tile_search<true, false>(tile, tid, len_q, [=](int j) { return tile_point(tgt, j); }, x, y, z, best, idx);
         }
         float mine = 0.f;
 #pragma unroll
@@ -1994,16 +1999,7 @@ __global__ __launch_bounds__(kBlock) void k_chamfer_fwd(const float *__restrict_
                 if (nearest != nullptr) nearest[b * full + i] = valid ? min(idx[u], len_q - 1) : -1;
             }
         }
-        const float tot = wave_allsum(mine);
-        __syncthreads();                                         // every wave has left the last tile
-        if ((tid & 63) == 0) red[tid >> 6] = tot;
-        __syncthreads();
-        if (tid == 0) {
-            float v = red[0];
-#pragma unroll
-            for (int wv = 1; wv < kBlock / 64; ++wv) v += red[wv];          // in wave order
-            rec[item] = v;
-        }
+        item_record<1>(tile, tid, wave_allsum(mine), rec + item);
     }
 }
 
@@ -2025,13 +2021,56 @@ __global__ __launch_bounds__(kBlock) void k_chamfer_rows(const float *__restrict
     }
 }
 
+// The owner scan of the gather backwards (k_chamfer_bwd, k_knn_bwd's dY).  A wave owns `owners` <= 64 consecutive points from
+// `first`, lane l the point (px, py, pz) = first + l and its accumulator.  The wave reads the `entries` index entries load(e) 64 per
+// block, kChamferScanBlocks blocks in flight, once for all its owners: an entry names one of them when idx - first < owners (one
+// unsigned compare: -1 and every other owner fall out), a ballot collects the block's hits.  The lanes that hold a hit call
+// term(e, ox, oy, oz, ux, uy, uz, g) side by side with their owner's point (ds_bpermute): it gathers the entry's point, forms u and
+// may leave a coefficient in g.  The wave then walks the ballot in ascending e and the owner a hit names takes it with
+// chamfer_hit(coef(g, h), u) -- readlane moves, no memory, one statically indexed accumulator per lane; coef gives a wave-uniform
+// coefficient as it is, or fetches the hit lane h's g.  No loop bound depends on the data.  The chain runs in a copy of the caller's
+// accumulator: through the reference, k_knn_bwd's owner takes a hit under a branch where it was three selects.
+template <class Count, class Load, class Term, class Coef>
+__device__ __forceinline__ void owner_scan(int lane, int first, unsigned owners, Count entries, float px, float py, float pz, Load load,
+                                           Term term, Coef coef, float (&acc)[3]) {
+    float a[3] = {acc[0], acc[1], acc[2]};
+    for (Count e0 = 0; e0 < entries; e0 += 64 * so3::kChamferScanBlocks) {
+        int named[so3::kChamferScanBlocks];
+#pragma unroll
+        for (int s = 0; s < so3::kChamferScanBlocks; ++s) {
+            const Count e = e0 + 64 * s + lane;
+            named[s] = e < entries ? load(e) : -1;
+        }
+#pragma unroll
+        for (int s = 0; s < so3::kChamferScanBlocks; ++s) {
+            const unsigned rel = static_cast<unsigned>(named[s] - first);
+            const bool hit = rel < owners;
+            unsigned long long mask = __ballot(hit);
+            if (mask == 0) continue;
+            const Count e = min(e0 + 64 * s + lane, entries - 1);
+            const int owner = static_cast<int>(rel & 63u);
+            const float ox = __shfl(px, owner, 64), oy = __shfl(py, owner, 64), oz = __shfl(pz, owner, 64);
+            float ux = 0.f, uy = 0.f, uz = 0.f, g = 0.f;
+            if (hit) term(e, ox, oy, oz, ux, uy, uz, g);
+            while (mask != 0) {                                  // ascending e
+                const int h = __builtin_ctzll(mask);
+                mask &= mask - 1;
+                const int o = __builtin_amdgcn_readlane(owner, h);
+                const float hc = coef(g, h);
+                const float hx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ux), h));
+                const float hy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(uy), h));
+                const float hz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(uz), h));
+                if (lane == o) so3::chamfer_hit(hc, hx, hy, hz, a);
+            }
+        }
+    }
+    acc[0] = a[0]; acc[1] = a[1]; acc[2] = a[2];
+}
+
 // k_chamfer_bwd: both gradients as a gather.  A wave owns kChamferOwners = 64 consecutive points of one cloud, one per lane, and a
 // work item is the four waves' 256 points; the items of dX come first, then dY's, as in k_chamfer_fwd.  A lane opens its chain with
-// its own term (its neighbour's 12 bytes gathered from L2).  The wave then reads the OTHER direction's `nearest`, 64 entries per
-// block and kChamferScanBlocks blocks in flight, once for all its owners: an entry names one of them when idx - first < owners (one
-// unsigned compare: -1 and every other owner fall out), a ballot collects the block's hits.  The lanes that hold a hit gather their
-// point and form phi against the owner's point (ds_bpermute) side by side; the wave then walks the ballot in ascending order and the
-// owner a hit names takes it with chamfer_hit -- readlane moves, no memory, one statically indexed accumulator per lane.
+// its own term (its neighbour's 12 bytes gathered from L2).  The wave then takes the OTHER direction's `nearest` through owner_scan:
+// a hit lane gathers its point and forms phi against the owner's point, the coefficient is the cloud's.
 // No LDS, no barrier: the waves of a work item do not meet.  Padded slots and clouds with an empty side get a row of zeros.
 template <bool SQUARED>
 __global__ __launch_bounds__(kBlock) void k_chamfer_bwd(const float *__restrict__ X, const float *__restrict__ Y, const int32_t *__restrict__ x_len,
@@ -2071,35 +2110,11 @@ __global__ __launch_bounds__(kBlock) void k_chamfer_bwd(const float *__restrict_
                 const float cb = s_hit[b];
                 const unsigned owners = static_cast<unsigned>(min(64, len_p - first));
                 const int32_t *hits = near_hit + b * qfull;
-                for (int j0 = 0; j0 < len_q; j0 += 64 * so3::kChamferScanBlocks) {
-                    int idx[so3::kChamferScanBlocks];
-#pragma unroll
-                    for (int s = 0; s < so3::kChamferScanBlocks; ++s) {
-                        const int j = j0 + 64 * s + lane;
-                        idx[s] = j < len_q ? hits[j] : -1;
-                    }
-#pragma unroll
-                    for (int s = 0; s < so3::kChamferScanBlocks; ++s) {
-                        const unsigned rel = static_cast<unsigned>(idx[s] - first);
-                        const bool hit = rel < owners;
-                        unsigned long long mask = __ballot(hit);
-                        if (mask == 0) continue;
-                        const int j = min(j0 + 64 * s + lane, len_q - 1);
-                        const int owner = static_cast<int>(rel & 63u);
-                        const float ox = __shfl(px, owner, 64), oy = __shfl(py, owner, 64), oz = __shfl(pz, owner, 64);
-                        float ux = 0.f, uy = 0.f, uz = 0.f;
-                        if (hit) so3::chamfer_phi<SQUARED>(ox - Q[j * 3 + 0], oy - Q[j * 3 + 1], oz - Q[j * 3 + 2], ux, uy, uz);
-                        while (mask != 0) {                                  // ascending j
-                            const int h = __builtin_ctzll(mask);
-                            mask &= mask - 1;
-                            const int o = __builtin_amdgcn_readlane(owner, h);
-                            const float hx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ux), h));
-                            const float hy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(uy), h));
-                            const float hz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(uz), h));
-                            if (lane == o) so3::chamfer_hit(cb, hx, hy, hz, acc);
-                        }
-                    }
-                }
+                owner_scan(lane, first, owners, len_q, px, py, pz, [&](int j) { return hits[j]; },
+                    [&](int j, float ox, float oy, float oz, float &ux, float &uy, float &uz, float &) {
+                        so3::chamfer_phi<SQUARED>(ox - Q[j * 3 + 0], oy - Q[j * 3 + 1], oz - Q[j * 3 + 2], ux, uy, uz);
+                    },
+                    [&](float, int) { return cb; }, acc);
             }
         }
         if (i < full) {
@@ -2246,7 +2261,7 @@ __global__ __launch_bounds__(kBlock) void k_ball_query(const float *__restrict__
 // ---- PointNet++ feature propagation: three nearest known points, inverse-distance interpolation and its backward -------------------
 constexpr int kThreeMaxGrid = 8192;      // workgroups of a launch; more work items are strided over
 
-// k_three_nn<WPP, WEIGHT>: k_icp_step<false>'s skeleton with a sorted top three per lane.  One work item = kBlock / WPP unknown points
+// k_three_nn<WPP, WEIGHT>: tile_search's loop, written out, with a sorted top three per lane.  One work item = kBlock / WPP unknown points
 // of one cloud; the known cloud goes through LDS in tiles of kAddsTile float4 and every lane of a wave reads the same float4 per step.
 // Thread tid keeps point tid % (kBlock / WPP) and scans slice tid / (kBlock / WPP): the tile's blocks of kAddsUnroll entries are dealt
 // to the WPP slices in turn, so a wave's lanes share their slice and the LDS read stays a broadcast.  A tile's tail is padded with
@@ -2285,7 +2300,7 @@ __global__ __launch_bounds__(kBlock) void k_three_nn(const float *__restrict__ u
             for (int k = slice * kAddsUnroll; k < cntp; k += WPP * kAddsUnroll) {
 #pragma unroll
                 for (int kk = 0; kk < kAddsUnroll; ++kk) {
-                    const f32x4 q = *(const volatile lds_f32x4 *)(&tile[k + kk]);     // k_add_s: the ds_read_b128 broadcast
+                    const f32x4 q = *(const volatile lds_f32x4 *)(&tile[k + kk]);     // tile_search: the ds_read_b128 broadcast
                     so3::three_nn_put<false>(so3::pointnet_dist2(q.x, q.y, q.z, x, y, z), t0 + k + kk, D, J);
                 }
             }
@@ -2561,10 +2576,9 @@ __global__ __launch_bounds__(kBlock) void k_knn(const float *__restrict__ X, con
 
 // k_knn_bwd: both gradients of dist2 as a gather, one launch; the items of dX come first, then dY's, as in k_chamfer_bwd.
 // dX: a lane per query; its chain takes the slots k < r in ascending k (K gathers of 12 bytes), a padded slot (-1) contributes nothing.
-// dY: k_chamfer_bwd's owner scan.  A wave owns 64 consecutive target points, one per lane, and reads the cloud's n_b * K index entries
-//   64 per block, kChamferScanBlocks blocks in flight: an entry names an owner when idx - first < owners (one unsigned compare: -1 and
-//   every other owner fall out).  The hit lanes gather their query point and the entry's g and form the term against the owner's point
-//   (ds_bpermute); the wave walks the ballot in ascending entry order and the owner takes the hit with chamfer_hit (readlane moves).
+// dY: a wave owns 64 consecutive target points, one per lane, and takes the cloud's n_b * K index entries through owner_scan in
+//   ascending (i, k): a hit lane gathers its query point and forms the term against the owner's point, the coefficient is the
+//   entry's own g.
 // An index is clamped before it addresses anything; no loop bound depends on the data.  No LDS, no atomics, no zero-fill.
 __global__ __launch_bounds__(kBlock) void k_knn_bwd(const float *__restrict__ X, const float *__restrict__ Y, const int32_t *__restrict__ x_len,
                                                     const int32_t *__restrict__ y_len, const int32_t *__restrict__ idx, const float *__restrict__ grad,
@@ -2607,40 +2621,13 @@ __global__ __launch_bounds__(kBlock) void k_knn_bwd(const float *__restrict__ X,
             const float px = ys[jc * 3 + 0], py = ys[jc * 3 + 1], pz = ys[jc * 3 + 2];
             const unsigned owners = static_cast<unsigned>(min(64, mb - first));
             const int64_t entries = static_cast<int64_t>(nb) * K;
-            for (int64_t e0 = 0; e0 < entries; e0 += 64 * so3::kChamferScanBlocks) {
-                int named[so3::kChamferScanBlocks];
-#pragma unroll
-                for (int s = 0; s < so3::kChamferScanBlocks; ++s) {
-                    const int64_t e = e0 + 64 * s + lane;
-                    named[s] = e < entries ? rows[e] : -1;
-                }
-#pragma unroll
-                for (int s = 0; s < so3::kChamferScanBlocks; ++s) {
-                    const unsigned rel = static_cast<unsigned>(named[s] - first);
-                    const bool hit = rel < owners;
-                    unsigned long long mask = __ballot(hit);
-                    if (mask == 0) continue;
-                    const int64_t e = min(e0 + 64 * s + lane, entries - 1);
-                    const int owner = static_cast<int>(rel & 63u);
-                    const float ox = __shfl(px, owner, 64), oy = __shfl(py, owner, 64), oz = __shfl(pz, owner, 64);
-                    float ux = 0.f, uy = 0.f, uz = 0.f, g = 0.f;
-                    if (hit) {
-                        const int q = static_cast<int>(e / K);       // the entry's query point, < n_b
-                        so3::chamfer_phi<true>(ox - xs[q * 3 + 0], oy - xs[q * 3 + 1], oz - xs[q * 3 + 2], ux, uy, uz);
-                        g = gs[e];
-                    }
-                    while (mask != 0) {                              // ascending (i, k)
-                        const int h = __builtin_ctzll(mask);
-                        mask &= mask - 1;
-                        const int o = __builtin_amdgcn_readlane(owner, h);
-                        const float hg = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(g), h));
-                        const float hx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ux), h));
-                        const float hy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(uy), h));
-                        const float hz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(uz), h));
-                        if (lane == o) so3::chamfer_hit(hg, hx, hy, hz, acc);
-                    }
-                }
-            }
+            owner_scan(lane, first, owners, entries, px, py, pz, [&](int64_t e) { return rows[e]; },
+                [&](int64_t e, float ox, float oy, float oz, float &ux, float &uy, float &uz, float &g) {
+                    const int q = static_cast<int>(e / K);           // the entry's query point, < n_b
+                    so3::chamfer_phi<true>(ox - xs[q * 3 + 0], oy - xs[q * 3 + 1], oz - xs[q * 3 + 2], ux, uy, uz);
+                    g = gs[e];
+                },
+                [&](float g, int h) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(g), h)); }, acc);
         }
         if (i < full) {
             const bool keep = live && i < len_p;
@@ -4202,15 +4189,21 @@ int launch_add_l1(const float *Tgt, const float *Tpred, const float *points, flo
     return check_launch(what);
 }
 
-// k_add_s over B clouds, then its rows: U outer points per lane, fewer when the batch alone would not cover the CUs twice.
-// The instantiation's name goes to so3_last_kernel; the rows' launches leave it there.
+// The search kernels' launch: at most 64 workgroups per compute unit, which stride over the work items.
+inline unsigned search_grid(int64_t items) { return static_cast<unsigned>(std::min<int64_t>(items, static_cast<int64_t>(device_cus()) * 64)); }
+// The work items of one cloud of N source points in k_add_s and k_icp_step, and the points per lane u they are cut for.
+inline int32_t icp_chunks(int64_t B, int32_t N, int &u) {
+    u = so3::icp_points_per_lane(B, N, device_cus());
+    return so3::search_chunks(N, u);
+}
+
+// k_add_s over B clouds, then its rows.  The instantiation's name goes to so3_last_kernel; the rows' launches leave it there.
 template <bool DIAMETER>
 int launch_add_s(const float *Tgt, const float *Tpred, const float *points, float *point_dist, int32_t *nearest, float *rows, double *total,
                  int64_t B, int32_t N, hipStream_t s, const char *what) {
-    const int64_t cus = device_cus();
-    const int u = so3::icp_points_per_lane(B, N, cus);
-    const int32_t chunks = (N + kBlock * u - 1) / (kBlock * u);
-    const dim3 grid(static_cast<unsigned>(std::min<int64_t>(B * chunks, cus * 64))), block(kBlock);
+    int u;
+    const int32_t chunks = icp_chunks(B, N, u);
+    const dim3 grid(search_grid(B * chunks)), block(kBlock);
     with_flags([&](auto WI) {
         constexpr bool kIndex = WI() && !DIAMETER;             // a diameter has no nearest index: no such instantiation
         with_value<4, 2, 1>(u, [&](auto U) {
@@ -4245,14 +4238,10 @@ void launch_sym_add(const float *Tgt, const float *Tpred, const float *points, c
 }
 
 // k_icp_step over B clouds at k_add_s's launch shape.  The instantiation's name goes to so3_last_kernel.
-int32_t icp_chunks(int64_t B, int32_t N, int &u) {
-    u = so3::icp_points_per_lane(B, N, device_cus());
-    return (N + kBlock * u - 1) / (kBlock * u);
-}
 template <bool SUMS>
 void launch_icp_step(const float *P, const float *Q, int64_t q_stride, const float *w, const float *pose, float max_distance, float *rec,
                      float *dist, int32_t *nearest, int64_t B, int32_t N, int32_t M, int u, int32_t chunks, hipStream_t s) {
-    const dim3 grid(static_cast<unsigned>(std::min<int64_t>(B * chunks, static_cast<int64_t>(device_cus()) * 64))), block(kBlock);
+    const dim3 grid(search_grid(B * chunks)), block(kBlock);
     with_flags([&](auto WW, auto TT) {
         constexpr bool kWeighted = WW() && SUMS, kTrimmed = TT() && SUMS;       // the search alone has neither: no such instantiation
         with_value<4, 2, 1>(u, [&](auto U) {
@@ -4263,14 +4252,12 @@ void launch_icp_step(const float *P, const float *Q, int64_t q_stride, const flo
     }, SUMS && w != nullptr, SUMS && max_distance >= 0.f);
 }
 
-// The work items of one cloud in the Chamfer kernels: `points` points per item, x items first, then the y items (none: x direction only).
+// The work items of one cloud in the Chamfer kernels: kBlock * u points per item, x items first, then the y items (none: x direction only).
 struct ChamferChunks { int32_t x, y; };
-inline ChamferChunks chamfer_chunks(int32_t N, int32_t M, bool single, int points) {
-    return {(N + points - 1) / points, single ? 0 : (M + points - 1) / points};
+inline ChamferChunks chamfer_chunks(int32_t N, int32_t M, bool single, int u) {
+    return {so3::search_chunks(N, u), single ? 0 : so3::search_chunks(M, u)};
 }
-inline unsigned chamfer_grid(int64_t B, ChamferChunks ch) {
-    return static_cast<unsigned>(std::min<int64_t>(B * (ch.x + ch.y), static_cast<int64_t>(device_cus()) * 64));
-}
+inline unsigned chamfer_grid(int64_t B, ChamferChunks ch) { return search_grid(B * (ch.x + ch.y)); }
 }  // namespace
 
 // ---- K4b: the metrics' backward (include/so3proj.h) ------------------------------------------------------------------
@@ -4883,7 +4870,7 @@ int so3_icp_f32(const float *P, const float *Q, int64_t q_stride, const float *w
 size_t so3_chamfer_workspace_bytes(int64_t B, int32_t N, int32_t M) {
     if (B < 0 || B > (INT64_C(1) << 31) || N < 1 || N > SO3_ADD_S_MAX_N || M < 1 || M > SO3_ADD_S_MAX_N) return 0;
     // one float per work item at the smallest work item (U = 1), both directions, whatever the device
-    const ChamferChunks ch = chamfer_chunks(N, M, false, kBlock);
+    const ChamferChunks ch = chamfer_chunks(N, M, false, 1);
     return static_cast<size_t>(B) * (static_cast<size_t>(ch.x) + static_cast<size_t>(ch.y)) * sizeof(float);
 }
 
@@ -4899,7 +4886,7 @@ int so3_chamfer_fwd_f32(const float *X, const float *Y, const int32_t *x_len, co
     SO3_CHECK_ARGS(!single || (dist_y == nullptr && nearest_y == nullptr), "so3_chamfer_fwd_f32: dist_y / nearest_y with SO3_CHAMFER_SINGLE");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int u = so3::chamfer_points_per_lane(B, N, M, single, device_cus());
-    const ChamferChunks ch = chamfer_chunks(N, M, single, kBlock * u);
+    const ChamferChunks ch = chamfer_chunks(N, M, single, u);
     float *rec = static_cast<float *>(work);
     with_flags([&](auto SQ) {
         constexpr bool kSquared = SQ();
@@ -4926,7 +4913,7 @@ int so3_chamfer_bwd_f32(const float *X, const float *Y, const int32_t *x_len, co
                    "so3_chamfer_bwd_f32: null pointer");
     SO3_CHECK_ARGS(single ? (nearest_y == nullptr && scale_y == nullptr) : (nearest_y != nullptr && scale_y != nullptr),
                    "so3_chamfer_bwd_f32: nearest_y and scale_y go with both directions, NULL with SO3_CHAMFER_SINGLE");
-    const ChamferChunks ch = chamfer_chunks(N, M, false, kBlock);
+    const ChamferChunks ch = chamfer_chunks(N, M, false, 1);
     with_flags([&](auto SQ) {
         name_kernel("k_chamfer_bwd", SQ);
         hipLaunchKernelGGL((k_chamfer_bwd<SQ()>), dim3(chamfer_grid(B, ch)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), X, Y, x_len, y_len,
@@ -4960,7 +4947,7 @@ int so3_knn_bwd_f32(const float *X, const float *Y, const int32_t *x_len, const 
     if (B == 0) return 0;
     SO3_CHECK_ARGS(X != nullptr && Y != nullptr && idx != nullptr && grad_dist2 != nullptr && (dX != nullptr || dY != nullptr),
                    "so3_knn_bwd_f32: null pointer");
-    const ChamferChunks ch = chamfer_chunks(N, M, false, kBlock);
+    const ChamferChunks ch = chamfer_chunks(N, M, false, 1);
     name_kernel("k_knn_bwd");
     hipLaunchKernelGGL(k_knn_bwd, dim3(chamfer_grid(B, ch)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), X, Y, x_len, y_len, idx, grad_dist2, dX,
                        dY, K, B, N, M, ch.x, ch.y);

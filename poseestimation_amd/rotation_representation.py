@@ -1382,16 +1382,15 @@ def icp_align(P: torch.Tensor, Q: torch.Tensor, R_init: torch.Tensor = None, t_i
 # --------------------------------------------------------------------------------------------
 # the Chamfer distance: a loss between two clouds, differentiable in both
 # --------------------------------------------------------------------------------------------
-def _chamfer_lengths(name, lengths, b, full, dev):
-    """(the lengths as the C ABI takes them: (B,) int32 or None, the per-cloud point counts as float32 (B,) or None for the full length)."""
+def _cloud_lengths(op, error, name, lengths, b, full, dev):
+    """The lengths of ragged clouds as the C ABI takes them: (B,) int32 clipped to [0, full], or None.  `op` raises `error`."""
     if lengths is None:
-        return None, None
+        return None
     _require_device(lengths)
     if lengths.device != dev or tuple(lengths.shape) != (b,) or lengths.dtype not in (torch.int32, torch.int64):
-        raise RuntimeError("chamfer_distance: expected %s as a (B,) int32 or int64 tensor on %s for B = %d, got %s %s on %s"
-                           % (name, dev, b, tuple(lengths.shape), lengths.dtype, lengths.device))
-    clipped = lengths.detach().clamp(0, full).to(torch.int32).contiguous()
-    return clipped, clipped.to(torch.float32)
+        raise error("%s: expected %s as a (B,) int32 or int64 tensor on %s for B = %d, got %s %s on %s"
+                    % (op, name, dev, b, tuple(lengths.shape), lengths.dtype, lengths.device))
+    return lengths.detach().clamp(0, full).to(torch.int32).contiguous()
 
 
 class _Chamfer(torch.autograd.Function):
@@ -1408,8 +1407,9 @@ class _Chamfer(torch.autograd.Function):
                                % (_lib.ADD_S_MAX_N, tuple(X.shape), tuple(Y.shape)))
         x, y = X.detach().contiguous().float(), Y.detach().contiguous().float()
         b, n, m = x.shape[0], x.shape[1], y.shape[1]
-        xl, nx = _chamfer_lengths("x_lengths", x_lengths, b, n, dev)
-        yl, ny = _chamfer_lengths("y_lengths", y_lengths, b, m, dev)
+        xl = _cloud_lengths("chamfer_distance", RuntimeError, "x_lengths", x_lengths, b, n, dev)
+        yl = _cloud_lengths("chamfer_distance", RuntimeError, "y_lengths", y_lengths, b, m, dev)
+        nx, ny = (None if l is None else l.to(torch.float32) for l in (xl, yl))       # the point counts; None: the full length
         want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         want_grad = want_x or want_y
         flags = (0 if squared else _lib.CHAMFER_UNSQUARED) | (_lib.CHAMFER_SINGLE if single else 0)
@@ -1503,17 +1503,6 @@ def chamfer_distance(X: torch.Tensor, Y: torch.Tensor, x_lengths: torch.Tensor =
 # --------------------------------------------------------------------------------------------
 # K nearest neighbours between two clouds, differentiable in both
 # --------------------------------------------------------------------------------------------
-def _knn_lengths(name, lengths, b, full, dev):
-    """The lengths as the C ABI takes them: (B,) int32 clipped to [0, full], or None."""
-    if lengths is None:
-        return None
-    _require_device(lengths)
-    if lengths.device != dev or tuple(lengths.shape) != (b,) or lengths.dtype not in (torch.int32, torch.int64):
-        raise ValueError("knn_points: expected %s as a (B,) int32 or int64 tensor on %s for B = %d, got %s %s on %s"
-                         % (name, dev, b, tuple(lengths.shape), lengths.dtype, lengths.device))
-    return lengths.detach().clamp(0, full).to(torch.int32).contiguous()
-
-
 class _KnnPoints(torch.autograd.Function):
     """knn_points: one so3_knn_f32 launch; the backward is one so3_knn_bwd_f32 launch that gathers both gradients through the stored
     int32 indices in a fixed order."""
@@ -1530,8 +1519,8 @@ class _KnnPoints(torch.autograd.Function):
             raise ValueError("knn_points: a shared (M, 3) target takes no gradient; pass Y.expand(B, M, 3) to differentiate in it")
         x, y = X.detach().contiguous().float(), Y.detach().contiguous().float()
         b, n, m = x.shape[0], x.shape[1], y.shape[-2]
-        xl = _knn_lengths("x_lengths", x_lengths, b, n, dev)
-        yl = _knn_lengths("y_lengths", y_lengths, b, m, dev)
+        xl = _cloud_lengths("knn_points", ValueError, "x_lengths", x_lengths, b, n, dev)
+        yl = _cloud_lengths("knn_points", ValueError, "y_lengths", y_lengths, b, m, dev)
         dist2 = torch.empty((b, n, k), dtype=torch.float32, device=dev)
         idx = torch.empty((b, n, k), dtype=torch.int32, device=dev)
         with _on_device(dev):

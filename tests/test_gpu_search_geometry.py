@@ -32,6 +32,12 @@ MUTATIONS.  Each applied alone to a scratch copy of the library, rebuilt, this f
   k_icp_step: tile 0 not refilled on later items          9: ICP every_split[G4 G5] x own / shared, search       search excess 0.97 .. 1.9 (3.9e-7); bitwise dist of exactly 37 / 5
      (barriers kept)                                      bits[G4 G5] x own / shared, zero_iterations_at_g4      clouds
 The last two are what the geometry is for: nothing below G4's and G5's item counts fails under them.
+The k_add_s loop these rows name is tile_search's (so3proj.hip), which k_chamfer_fwd shares; k_icp_step and k_three_nn keep theirs.
+Two of the mutations applied to the helper; this file, test_gpu_chamfer.py and test_gpu_three_nn.py run once each:
+  tile_search: index t0 + k + kk -> k + kk       33: the 13 ADD-S tests above and 20 of test_gpu_chamfer.py (16 work splits,
+                                                 2 x G27, four_points_per_lane, a_small_last_hit)
+  tile_search: tile 0 not refilled on later      6: ADD-S every_split[G4 G5] and bits[G4 G5] (point 1.2 and 0.80 against 1.9e-6),
+     items (barriers kept)                       chamfer batch_above_the_grid_cap and its bit_for_bit
 """
 import ctypes
 import math
