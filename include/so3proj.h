@@ -693,6 +693,43 @@ int so3_knn_f32(const float *X, const float *Y, int64_t y_stride, const int32_t 
 int so3_knn_bwd_f32(const float *X, const float *Y, const int32_t *x_len, const int32_t *y_len, const int32_t *idx,
                     const float *grad_dist2, float *dX, float *dY, int32_t K, int64_t B, int32_t N, int32_t M, void *stream);
 
+/* ---- Local frames: per-point PCA over a neighbourhood given by indices (added in 210) ----
+ * For every row of idx (so3_knn_f32's, so3_ball_query_f32's or a caller's own): the 3x3 covariance of the points it names, its
+ * eigenvalues and a right-handed frame of its eigenvectors; the first column is the surface normal.  One launch.
+ * Cloud b is at Y + b*y_stride floats (0: one cloud shared by all, otherwise >= 3*M), as so3_knn_f32; rows i < n_b =
+ * clip(x_len[b], 0, N) are live and points j < m_b = clip(y_len[b], 0, M) exist (NULL: all).
+ * A slot of row (b, i) is VALID when 0 <= idx < m_b (one unsigned compare); every other value -- the -1 padding, an empty ball's
+ * N, garbage -- is skipped and addresses nothing.  Valid slots need not form a prefix.  r = the number of valid slots, j_0 = the
+ * first valid one, the pivot.
+ * The covariance is a definition, not an approximation (float32, bit-exact):
+ *     d_k = y_{j_k} - y_{j_0} per coordinate, one rounded subtraction each;
+ *     s = sum_k d_k, a chain of rounded additions from +0 over the valid slots in ascending k;   m = s / (float)r, IEEE division;
+ *     e_k = d_k - m;   for (xx, xy, xz, yy, yz, zz): S_ab a chain from +0 in ascending k of fma(e_ka, e_kb, S_ab);   C_ab = S_ab / (float)r.
+ *   Centring on the pivot keeps float32's digits however far from the origin the cloud lies; scaling the cloud by a power of two
+ *   scales C by its square, bit for bit.
+ * The eigen stage is an approximation with bounds (tests/local_frames_ref.py): eigenvalues l0 <= l1 <= l2, each >= 0, and unit
+ * eigenvectors e0, e1, e2.  C is prescaled by an exact power of two, so scaling the cloud by 2^k leaves the frame's bits unchanged
+ * and multiplies the eigenvalues by 4^k exactly.  A fixed number of Jacobi sweeps: no loop bound depends on the data.
+ * Signs: in e0 and in e2 the component of largest magnitude is positive (among equal magnitudes the lowest index decides); with a
+ * viewpoint v_b, e0 is then flipped where e0 . (v_b - y_{j_0}) < 0 (exactly 0 keeps the sign); then e1 = e2 x e0 (det = +1).
+ * C == 0 exactly (r = 1, all neighbours equal) gives eigenvalues 0 and the identity frame, with or without a viewpoint.  Rows with r = 0, rows i >= n_b and every
+ * row of a cloud with m_b = 0 are written as zeros in every output.  Every element of every requested output is written; no buffer
+ * needs a zero-fill.  Non-finite coordinates give unspecified values in the rows that name them only.
+ *   Y            in   the clouds, float32;   idx  in  B*N*K int32;   x_len, y_len  in  optional B int32
+ *   viewpoint    in   optional B*3 float32
+ *   cov          out  B*N*6 float32  (xx, xy, xz, yy, yz, zz)
+ *   eigenvalues  out  B*N*3 float32  l0, l1, l2
+ *   normals      out  B*N*3 float32  e0
+ *   frames       out  B*N*9 float32  row-major 3x3, columns e0 e1 e2
+ *   each output optional, not all NULL.
+ * No atomics, no workspace, no host synchronisation: a call can be captured in a graph and the same inputs give the same bits.
+ * 1 <= K <= SO3_KNN_MAX_K, N, M, B as so3_knn_f32 (B == 0: a no-op).  B, N, M and K are checked first: B == 0 with a K out of
+ * range is an error, B == 0 with NULL pointers is not.
+ */
+int so3_local_frames_f32(const float *Y, int64_t y_stride, const int32_t *idx, const int32_t *x_len, const int32_t *y_len,
+                         const float *viewpoint, float *cov, float *eigenvalues, float *normals, float *frames, int32_t K, int64_t B,
+                         int32_t N, int32_t M, void *stream);
+
 /* ---- PointNet++ sampling and grouping: farthest-point sampling and ball query (added in 210) ----
  * The reference's point_cloud/pointnet_utils.py: farthest_point_sample (:53-74, a Python loop of npoint iterations) and
  * query_ball_point (:77-97, a (B,S,N) index tensor sorted along N), each as one launch.

@@ -79,6 +79,7 @@ SYMBOLS = {
     "so3_chamfer_bwd_f32": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U32, _I64, _I32, _I32, _P]),
     "so3_knn_f32": (_INT, [_P, _P, _I64, _P, _P, _P, _P, _I32, _I64, _I32, _I32, _P]),
     "so3_knn_bwd_f32": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I64, _I32, _I32, _P]),
+    "so3_local_frames_f32": (_INT, [_P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I64, _I32, _I32, _P]),
     "so3_fps_f32": (_INT, [_P, _P, _P, _I64, _I32, _I32, _P]),
     "so3_ball_query_f32": (_INT, [_P, _P, ctypes.c_float, _I32, _P, _P, _I64, _I32, _I32, _P]),
     "so3_three_nn_f32": (_INT, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _P]),

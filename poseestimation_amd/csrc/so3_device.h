@@ -1527,4 +1527,126 @@ inline int knn_queries_per_wave(int64_t B, int32_t N, int32_t M) {
     return (M >= kKnnWideTargets && B * N >= kKnnWideQueries) ? kKnnWideQ : kKnnNarrowQ;
 }
 
+// ---- Local frames: the covariance of a point's neighbourhood and its eigen-decomposition (so3proj.hip: k_local_frames;
+// tests/host_model/local_frames.cpp) -------------------------------------------------------------------------------------------------
+// The covariance is a DEFINITION (include/so3proj.h): a slot is valid when group_valid(idx, m_b); the pivot p is the first valid slot's
+// point; per coordinate d = y - p (one rounded subtraction), s a chain of rounded additions from +0 over the valid slots in ascending k,
+// m = s / (float)r (IEEE division: the library is built without fast-math), e = d - m, the six sums S_ab chains from +0 of
+// fma(e_a, e_b, S_ab) in ascending k, C_ab = S_ab / (float)r.  Nothing here may contract: the only fusions are the fmas spelled out.
+#pragma clang fp contract(off)
+// first pass, one valid slot: the chains of s
+__device__ __forceinline__ void frames_sum_slot(float yx, float yy, float yz, float px, float py, float pz, float (&s)[3]) {
+    const float dx = yx - px, dy = yy - py, dz = yz - pz;
+    s[0] = s[0] + dx;
+    s[1] = s[1] + dy;
+    s[2] = s[2] + dz;
+}
+__device__ __forceinline__ void frames_mean(const float (&s)[3], int32_t r, float (&m)[3]) {
+    const float n = static_cast<float>(r);
+    m[0] = s[0] / n;
+    m[1] = s[1] / n;
+    m[2] = s[2] / n;
+}
+// second pass, one valid slot: the six chains (xx, xy, xz, yy, yz, zz)
+__device__ __forceinline__ void frames_cov_slot(float yx, float yy, float yz, float px, float py, float pz, const float (&m)[3], float (&S)[6]) {
+    const float dx = yx - px, dy = yy - py, dz = yz - pz;
+    const float ex = dx - m[0], ey = dy - m[1], ez = dz - m[2];
+    S[0] = __builtin_fmaf(ex, ex, S[0]);
+    S[1] = __builtin_fmaf(ex, ey, S[1]);
+    S[2] = __builtin_fmaf(ex, ez, S[2]);
+    S[3] = __builtin_fmaf(ey, ey, S[3]);
+    S[4] = __builtin_fmaf(ey, ez, S[4]);
+    S[5] = __builtin_fmaf(ez, ez, S[5]);
+}
+__device__ __forceinline__ void frames_cov_finish(const float (&S)[6], int32_t r, float (&C)[6]) {
+    const float n = static_cast<float>(r);
+#pragma unroll
+    for (int a = 0; a < 6; ++a) C[a] = S[a] / n;
+}
+#pragma clang fp contract(on)          // the eigen stage: contraction as written, like the Jacobi path above
+// The eigen stage is an approximation with bounds (tests/local_frames_ref.py holds them).  The matrix is prescaled by an exact power
+// of two so that its largest |entry| lies in [0.5, 1) (signed_svd's idiom): scaling the cloud by 2^k leaves every bit of the frame and
+// scales the eigenvalues by 4^k exactly.  Then kFramesSweeps cyclic sweeps of the two-sided Jacobi method, (0,1) (0,2) (1,2), with the
+// eigenvectors accumulated from the identity -- a FIXED count, no convergence test: no loop bound depends on the data.
+// One plane rotation: rotate()'s division-free angle with d = a_pp - a_qq, g = 2 a_pq,  (c, s) = (d + sgn(d) h, g) normalised,
+// h = sqrt(d^2 + g^2): |theta| <= pi/4 up to a common sign of both new vectors, which J^T A J does not see.  The diagonal moves by
+// w = s (c g - s d), a_pp + w and a_qq - w, so the trace is kept to rounding and a small angle is a small change.  An off-diagonal
+// entry at or below kFramesSkip -- 2^-50 of the matrix's scale, far below its rounding -- is left alone: its square would underflow
+// and (c, s) would lose unit length; that also makes C == 0 the identity frame.
+constexpr int kFramesSweeps = 4;
+constexpr float kFramesSkip = 0x1p-50f;
+__device__ __forceinline__ void sym_rotate(float &app, float &aqq, float &apq, float &arp, float &arq, V3<float> &vp, V3<float> &vq) {
+    const float d = app - aqq;
+    const float g = apq + apq;
+    const float gg = g * g;
+    const float h = hw::sqrt(fmaf(d, d, gg));
+    const float ae = d + copysignf(h, d);
+    const float rw = hw::rsq(fmaf(ae, ae, gg));
+    const bool skip = fabsf(g) <= kFramesSkip;
+    const float c = skip ? 1.f : ae * rw, s = skip ? 0.f : g * rw;
+    const float sd = s * d;
+    const float w = s * fmaf(c, g, -sd);
+    app = app + w;
+    aqq = aqq - w;
+    apq = skip ? apq : 0.f;
+    const float sq = s * arq, sp = s * arp;
+    const float np = fmaf(c, arp, sq), nq = fmaf(c, arq, -sp);
+    arp = np;
+    arq = nq;
+    const V3<float> up = mk<float>(fmaf(c, vp.x, s * vq.x), fmaf(c, vp.y, s * vq.y), fmaf(c, vp.z, s * vq.z));
+    const V3<float> uq = mk<float>(fmaf(c, vq.x, -(s * vp.x)), fmaf(c, vq.y, -(s * vp.y)), fmaf(c, vq.z, -(s * vp.z)));
+    vp = up;
+    vq = uq;
+}
+__device__ __forceinline__ void frames_order(float &la, float &lb, V3<float> &va, V3<float> &vb) {      // (la, va) <= (lb, vb)
+    const bool swap = lb < la;
+    const float l = la;
+    const V3<float> v = va;
+    la = swap ? lb : la; va = sel<float>(swap, vb, va);
+    lb = swap ? l : lb;  vb = sel<float>(swap, v, vb);
+}
+// C: (xx, xy, xz, yy, yz, zz).  -> lam[0] <= lam[1] <= lam[2], each >= 0, and their unit eigenvectors; v1's sign and the
+// handedness of (v0, v1, v2) are not fixed here (frames_orient).
+template <int SWEEPS = kFramesSweeps>
+__device__ __forceinline__ void sym_eigen3(const float (&C)[6], float (&lam)[3], V3<float> &v0, V3<float> &v1, V3<float> &v2) {
+    typedef Tr<float> R;
+    const float mx = R::max(R::max(R::max(R::abs(C[0]), R::abs(C[1])), R::max(R::abs(C[2]), R::abs(C[3]))), R::max(R::abs(C[4]), R::abs(C[5])));
+    const int ex = R::neg_frexp_exp(mx);                 // 0 for mx == 0; finite for inf / NaN too
+    const float sc = R::ldexp(1.f, ex);
+    float a00 = C[0] * sc, a01 = C[1] * sc, a02 = C[2] * sc, a11 = C[3] * sc, a12 = C[4] * sc, a22 = C[5] * sc;      // exact
+    v0 = mk<float>(1.f, 0.f, 0.f); v1 = mk<float>(0.f, 1.f, 0.f); v2 = mk<float>(0.f, 0.f, 1.f);
+#pragma unroll
+    for (int sweep = 0; sweep < SWEEPS; ++sweep) {
+        sym_rotate(a00, a11, a01, a02, a12, v0, v1);
+        sym_rotate(a00, a22, a02, a01, a12, v0, v2);
+        sym_rotate(a11, a22, a12, a01, a02, v1, v2);
+    }
+    frames_order(a00, a11, v0, v1);
+    frames_order(a11, a22, v1, v2);
+    frames_order(a00, a11, v0, v1);
+    lam[0] = R::ldexp(a00 > 0.f ? a00 : 0.f, -ex);
+    lam[1] = R::ldexp(a11 > 0.f ? a11 : 0.f, -ex);
+    lam[2] = R::ldexp(a22 > 0.f ? a22 : 0.f, -ex);
+}
+// The sign rule: the component of largest magnitude is positive, among equal magnitudes the lowest index decides.
+__device__ __forceinline__ V3<float> frames_sign(V3<float> e) {
+    const float ax = fabsf(e.x), ay = fabsf(e.y), az = fabsf(e.z);
+    const float lead = (ax >= ay && ax >= az) ? e.x : (ay >= az ? e.y : e.z);
+    return lead < 0.f ? mk<float>(-e.x, -e.y, -e.z) : e;
+}
+// C == 0 exactly (r = 1, all neighbours equal): the identity frame, which no viewpoint turns.
+__device__ __forceinline__ bool frames_flat(const float (&C)[6]) {
+    return C[0] == 0.f && C[1] == 0.f && C[2] == 0.f && C[3] == 0.f && C[4] == 0.f && C[5] == 0.f;
+}
+// The frame as it is written: e0 and e2 by the sign rule; with a viewpoint v (have_view: one is given and the row is not flat), e0
+// flipped where e0 . (v - pivot) < 0 (exactly 0 keeps it); e1 = e2 x e0, so the frame is right-handed.
+__device__ __forceinline__ void frames_orient(V3<float> &e0, V3<float> &e1, V3<float> &e2, bool have_view, float wx, float wy, float wz) {
+    e0 = frames_sign(e0);
+    e2 = frames_sign(e2);
+    const float toward = dot(e0, mk<float>(wx, wy, wz));
+    e0 = (have_view && toward < 0.f) ? mk<float>(-e0.x, -e0.y, -e0.z) : e0;
+    e1 = cross<float>(e2, e0);
+}
+#pragma clang fp contract(fast)
+
 }  // namespace so3

@@ -2637,6 +2637,85 @@ __global__ __launch_bounds__(kBlock) void k_knn_bwd(const float *__restrict__ X,
     }
 }
 
+// ---- Local frames: the covariance of a point's neighbourhood and its eigen-decomposition, one query per lane -------------------------
+// k_local_frames: a lane serves one row of idx (k_knn_bwd's dX mapping).  It reads the row's K indices from its own contiguous row
+// and gathers 12 bytes per valid slot twice: the first pass finds the pivot (the first valid slot) and the chains of s, the second
+// the six covariance chains about the mean -- the order the definition prescribes; a cloud of a few thousand points stays in L1 / L2
+// between the passes.  A slot is valid when idx < m_b as ONE unsigned compare; an invalid slot loads point 0 of the cloud (m_b > 0
+// here) and its values are dropped by selects, so no index addresses anything before it is tested.  Then the eigen stage in
+// registers (so3::sym_eigen3: a fixed number of Jacobi sweeps, no data-dependent loop, no indexed private array).  Rows past n_b,
+// rows without a valid slot and clouds with m_b == 0 write zeros; every element of every requested output is written.
+// No LDS, no atomics, no workspace; the grid is capped and strided over.
+__global__ __launch_bounds__(kBlock) void k_local_frames(const float *__restrict__ Y, int64_t y_stride, const int32_t *__restrict__ idx,
+                                                         const int32_t *__restrict__ x_len, const int32_t *__restrict__ y_len,
+                                                         const float *__restrict__ viewpoint, float *__restrict__ cov, float *__restrict__ eigenvalues,
+                                                         float *__restrict__ normals, float *__restrict__ frames, int32_t K, int64_t B, int32_t N,
+                                                         int32_t M, int32_t chunks) {
+    const int64_t items = B * chunks;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t b = item / chunks;
+        const int i = static_cast<int>(item - b * chunks) * kBlock + static_cast<int>(threadIdx.x);
+        if (i >= N) continue;
+        const int32_t nb = so3::chamfer_length(x_len, b, N), mb = so3::chamfer_length(y_len, b, M);
+        const float *tgt = Y + b * y_stride;
+        const int64_t q = b * N + i;
+        const int32_t *row = idx + q * K;
+        float C[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, lam[3] = {0.f, 0.f, 0.f};
+        so3::V3<float> e0 = so3::mk<float>(0.f, 0.f, 0.f), e1 = e0, e2 = e0;
+        if (i < nb && mb > 0) {
+            int32_t r = 0;
+            float px = 0.f, py = 0.f, pz = 0.f, s[3] = {0.f, 0.f, 0.f};
+#pragma unroll 4
+            for (int k = 0; k < K; ++k) {
+                const int32_t j = row[k];
+                const bool valid = so3::group_valid(j, mb);
+                const int jc = valid ? j : 0;
+                const float yx = tgt[jc * 3 + 0], yy = tgt[jc * 3 + 1], yz = tgt[jc * 3 + 2];
+                const bool first = valid && r == 0;
+                px = first ? yx : px; py = first ? yy : py; pz = first ? yz : pz;
+                float t[3] = {s[0], s[1], s[2]};
+                so3::frames_sum_slot(yx, yy, yz, px, py, pz, t);
+                s[0] = valid ? t[0] : s[0]; s[1] = valid ? t[1] : s[1]; s[2] = valid ? t[2] : s[2];
+                r += valid ? 1 : 0;
+            }
+            if (r > 0) {
+                float m[3], S[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                so3::frames_mean(s, r, m);
+#pragma unroll 4
+                for (int k = 0; k < K; ++k) {
+                    const int32_t j = row[k];
+                    const bool valid = so3::group_valid(j, mb);
+                    const int jc = valid ? j : 0;
+                    float T[6] = {S[0], S[1], S[2], S[3], S[4], S[5]};
+                    so3::frames_cov_slot(tgt[jc * 3 + 0], tgt[jc * 3 + 1], tgt[jc * 3 + 2], px, py, pz, m, T);
+#pragma unroll
+                    for (int a = 0; a < 6; ++a) S[a] = valid ? T[a] : S[a];
+                }
+                so3::frames_cov_finish(S, r, C);
+                if (eigenvalues != nullptr || normals != nullptr || frames != nullptr) {
+                    so3::sym_eigen3(C, lam, e0, e1, e2);
+                    const bool view = viewpoint != nullptr && !so3::frames_flat(C);
+                    float wx = 0.f, wy = 0.f, wz = 0.f;
+                    if (view) { wx = viewpoint[b * 3 + 0] - px; wy = viewpoint[b * 3 + 1] - py; wz = viewpoint[b * 3 + 2] - pz; }
+                    so3::frames_orient(e0, e1, e2, view, wx, wy, wz);
+                }
+            }
+        }
+        if (cov != nullptr) {
+#pragma unroll
+            for (int a = 0; a < 6; ++a) cov[q * 6 + a] = C[a];
+        }
+        if (eigenvalues != nullptr) { eigenvalues[q * 3 + 0] = lam[0]; eigenvalues[q * 3 + 1] = lam[1]; eigenvalues[q * 3 + 2] = lam[2]; }
+        if (normals != nullptr) { normals[q * 3 + 0] = e0.x; normals[q * 3 + 1] = e0.y; normals[q * 3 + 2] = e0.z; }
+        if (frames != nullptr) {
+            float *f = frames + q * 9;
+            f[0] = e0.x; f[1] = e1.x; f[2] = e2.x;
+            f[3] = e0.y; f[4] = e1.y; f[5] = e2.y;
+            f[6] = e0.z; f[7] = e1.z; f[8] = e2.z;
+        }
+    }
+}
+
 // ---- PointNet++ set abstraction: the grouping gather and its backward -------------------------------------------------------------
 // What sample_and_group does between the ball query and the first Conv2d: gather the grouped coordinates and
 // features, subtract the centre, concatenate, in the layout the caller asks for.  A slot whose index lies outside [0, N) -- an empty
@@ -4952,6 +5031,21 @@ int so3_knn_bwd_f32(const float *X, const float *Y, const int32_t *x_len, const 
     hipLaunchKernelGGL(k_knn_bwd, dim3(chamfer_grid(B, ch)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), X, Y, x_len, y_len, idx, grad_dist2, dX,
                        dY, K, B, N, M, ch.x, ch.y);
     return check_launch("so3_knn_bwd_f32");
+}
+
+int so3_local_frames_f32(const float *Y, int64_t y_stride, const int32_t *idx, const int32_t *x_len, const int32_t *y_len, const float *viewpoint,
+                         float *cov, float *eigenvalues, float *normals, float *frames, int32_t K, int64_t B, int32_t N, int32_t M, void *stream) {
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && M >= 1 && M <= SO3_ADD_S_MAX_N, "so3_local_frames_f32: B/N/M");
+    SO3_CHECK_ARGS(K >= 1 && K <= SO3_KNN_MAX_K, "so3_local_frames_f32: K");
+    if (B == 0) return 0;
+    SO3_CHECK_ARGS(y_stride == 0 || y_stride >= static_cast<int64_t>(M) * 3, "so3_local_frames_f32: y_stride");
+    SO3_CHECK_ARGS(Y != nullptr && idx != nullptr && (cov != nullptr || eigenvalues != nullptr || normals != nullptr || frames != nullptr),
+                   "so3_local_frames_f32: null pointer");
+    const int32_t chunks = (N + kBlock - 1) / kBlock;
+    name_kernel("k_local_frames");
+    hipLaunchKernelGGL(k_local_frames, dim3(static_cast<unsigned>(std::min<int64_t>(B * chunks, kThreeMaxGrid))), dim3(kBlock), 0,
+                       static_cast<hipStream_t>(stream), Y, y_stride, idx, x_len, y_len, viewpoint, cov, eigenvalues, normals, frames, K, B, N, M, chunks);
+    return check_launch("so3_local_frames_f32");
 }
 
 int so3_fps_f32(const float *xyz, const int32_t *start, int32_t *out, int64_t B, int32_t N, int32_t npoint, void *stream) {

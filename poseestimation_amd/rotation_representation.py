@@ -1597,6 +1597,93 @@ def knn_group(K: int, xyz: torch.Tensor, new_xyz: torch.Tensor, points, channels
 
 
 # --------------------------------------------------------------------------------------------
+# Local frames: per-point PCA over a neighbourhood (forward only)
+# --------------------------------------------------------------------------------------------
+def _frames_forward_only(*ts):
+    if _wants_grad(*ts):
+        _warn_once("local_frames", "local_frames and estimate_normals are forward-only: eigenvalues, frames and normals carry no gradient "
+                                   "although an argument requires grad (the gradient through an eigenvector is unbounded at ties).  A loss "
+                                   "that needs one can differentiate the covariance in torch.")
+
+
+def _local_frames_call(points, idx, x_lengths, y_lengths, viewpoint, want):
+    """One so3_local_frames_f32 launch; want = (cov, eigenvalues, normals, frames) flags -> the float32 outputs, None where not wanted."""
+    dev = _require_device(points, idx)
+    _frames_forward_only(points, viewpoint)
+    ok = points.dim() in (2, 3) and points.shape[-1] == 3 and idx.dim() == 3 and (points.dim() == 2 or points.shape[0] == idx.shape[0])
+    if (not ok or idx.dtype not in (torch.int32, torch.int64) or not 1 <= points.shape[-2] <= _lib.ADD_S_MAX_N
+            or not 1 <= idx.shape[1] <= _lib.ADD_S_MAX_N or not 1 <= idx.shape[2] <= _lib.KNN_MAX_K):
+        raise ValueError("local_frames: expected points (B, M, 3) or (M, 3) and idx (B, N, K) (int32 or int64) with 1 <= N, M <= %d and "
+                         "1 <= K <= %d, got %s and %s %s" % (_lib.ADD_S_MAX_N, _lib.KNN_MAX_K, tuple(points.shape), idx.dtype, tuple(idx.shape)))
+    b, n, k = idx.shape
+    m = points.shape[-2]
+    if viewpoint is not None:
+        _require_device(viewpoint)
+        if viewpoint.device != dev or tuple(viewpoint.shape) not in ((b, 3), (3,)) or not viewpoint.is_floating_point():
+            raise ValueError("local_frames: expected viewpoint as a (B, 3) or (3,) floating-point tensor on %s for B = %d, got %s %s on %s"
+                             % (dev, b, tuple(viewpoint.shape), viewpoint.dtype, viewpoint.device))
+        viewpoint = viewpoint.detach().float().expand(b, 3).contiguous()
+    y = points.detach().contiguous().float()
+    xl = _cloud_lengths("local_frames", ValueError, "x_lengths", x_lengths, b, n, dev)
+    yl = _cloud_lengths("local_frames", ValueError, "y_lengths", y_lengths, b, m, dev)
+    # an index beyond int32 is invalid either way: clamp it to one that stays invalid (M <= 2^20) instead of letting it wrap
+    ix = (idx if idx.dtype == torch.int32 else idx.clamp(-1, _lib.ADD_S_MAX_N).to(torch.int32)).contiguous()
+    outs = [torch.empty((b, n, w), dtype=torch.float32, device=dev) if flag else None for flag, w in zip(want, (6, 3, 3, 9))]
+    with _on_device(dev):
+        _check(_libh().so3_local_frames_f32(_ptr(y), 0 if points.dim() == 2 else 3 * m, _ptr(ix), _ptr(xl), _ptr(yl), _ptr(viewpoint),
+                                            *(_ptr(o) for o in outs), k, b, n, m, _stream(dev)), "so3_local_frames_f32")
+    return outs
+
+
+def local_frames(points: torch.Tensor, idx: torch.Tensor, x_lengths: torch.Tensor = None, y_lengths: torch.Tensor = None,
+                 viewpoint: torch.Tensor = None, return_covariance: bool = False):
+    """Per-point PCA: for every row of idx (B,N,K) -- as knn_points, knn_group's search or query_ball_point return it, int32 or int64 --
+    the covariance of the points of `points` (B,M,3), or one shared (M,3), that it names, decomposed: (eigenvalues (B,N,3) ascending and
+    >= 0, frames (B,N,3,3) with the unit eigenvectors as columns, right-handed; frames[..., 0] is the surface normal).  With
+    return_covariance=True also cov (B,N,3,3), symmetric.
+
+    A slot is valid when 0 <= idx < m_b; -1 padding, an empty ball's N and anything else are skipped, wherever in the row they stand.
+    x_lengths, y_lengths: optional (B,) int32 / int64: cloud b's rows i < n_b are live, its points j < m_b exist.  The covariance is a
+    fixed-order float32 definition centred on the row's first valid point (include/so3proj.h), so it keeps its digits far from the
+    origin and repeats bit for bit; the eigen stage is a fixed number of Jacobi sweeps in registers, one launch for everything
+    (so3_local_frames_f32), nothing goes to a batched solver.  Signs: the largest-magnitude component of the normal and of the third
+    axis is positive; with viewpoint (B,3) or (3,) the normal faces the viewpoint instead.  A row whose neighbours are all equal gets
+    eigenvalues 0 and the identity frame, with or without a viewpoint; a row without a valid slot, a row past n_b and a cloud with m_b == 0 get zeros.
+
+    Forward only: the outputs carry no gradient (an argument that requires grad is warned about once).  Outputs are computed in
+    float32 and returned in the cloud's dtype."""
+    cov, lam, _, frames = _local_frames_call(points, idx, x_lengths, y_lengths, viewpoint, (bool(return_covariance), True, False, True))
+    b, n = lam.shape[:2]
+    res = (lam.to(points.dtype), frames.view(b, n, 3, 3).to(points.dtype))
+    if return_covariance:
+        res += (cov[..., [0, 1, 2, 1, 3, 4, 2, 4, 5]].view(b, n, 3, 3).to(points.dtype),)
+    return res
+
+
+def estimate_normals(points: torch.Tensor, K: int = 16, lengths: torch.Tensor = None, viewpoint: torch.Tensor = None, return_curvature: bool = False):
+    """Surface normals of a cloud (B,N,3) from its K nearest neighbours: knn_points(points, points, K, lengths, lengths) followed by
+    local_frames' kernel with only the normals requested -> (B,N,3) unit vectors (zeros in the rows past lengths[b]).  The point
+    itself is its own nearest neighbour and so the pivot of its covariance.  viewpoint (B,3) or (3,): the normals face it; without one
+    their largest-magnitude component is positive.  return_curvature=True also returns the surface variation
+    l0 / (l0 + l1 + l2) (B,N), 0 where the sum is 0.  Forward only, as local_frames."""
+    _frames_forward_only(points, viewpoint)
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= _lib.KNN_MAX_K:
+        raise ValueError("estimate_normals: expected an int 1 <= K <= %d, got %r" % (_lib.KNN_MAX_K, K))
+    _require_device(points)
+    if points.dim() != 3 or points.shape[-1] != 3:
+        raise ValueError("estimate_normals: expected points (B, N, 3), got %s" % (tuple(points.shape),))
+    pts = points.detach()
+    _, idx = knn_points(pts, pts, K, lengths, lengths)
+    _, lam, normals, _ = _local_frames_call(pts, idx, lengths, lengths, viewpoint, (False, bool(return_curvature), True, False))
+    normals = normals.to(points.dtype)
+    if not return_curvature:
+        return normals
+    total = lam.sum(-1)
+    variation = torch.where(total > 0, lam[..., 0] / total.clamp_min(torch.finfo(torch.float32).tiny), torch.zeros_like(total))
+    return normals, variation.to(points.dtype)
+
+
+# --------------------------------------------------------------------------------------------
 # PointNet++ sampling and grouping (reference: point_cloud/pointnet_utils.py)
 # --------------------------------------------------------------------------------------------
 def _cloud_f32(name, what, x, width=3):

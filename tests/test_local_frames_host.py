@@ -1,0 +1,250 @@
+"""local_frames and estimate_normals (so3_local_frames_f32) without a GPU: the boundary (header, binding table, exports, argument
+validation, the Python names), the G29 fixture's own consistency under the judges, and the kernel's device functions compiled for the
+host (tests/host_model/local_frames.cpp with SO3_HOST_MODEL) on G29.
+
+The covariance is a definition (include/so3proj.h), so it is compared EXACTLY with the numpy restatement (tests/local_frames_ref.py:
+cov32).  The eigen stage is judged by bounds whose constants are 4 x what the host model reaches here: the model itself is held to the
+UN-multiplied figures (ref.MEASURED), which is what keeps the constants honest.  tests/test_gpu_local_frames.py imports the checks
+and runs them on the device."""
+import ctypes
+import os
+import re
+import subprocess
+import threading
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import ROOT
+import local_frames_ref as ref
+
+NEW_SYMBOLS = {"so3_local_frames_f32": 15}
+SRC = os.path.join(ROOT, "tests", "host_model", "local_frames.cpp")
+GRID_CAP, BLOCK = 8192, 256          # so3proj.hip: kThreeMaxGrid, kBlock
+SWEEPS = 4                           # so3_device.h: kFramesSweeps
+
+
+# ---- the boundary ---------------------------------------------------------------------------------------------------------
+def test_header_binding_table_and_library_agree(built_library):
+    from poseestimation_amd import _lib
+    raw = open(os.path.join(ROOT, "include", "so3proj.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
+    declared = set(re.findall(r"\b(so3_[a-z0-9_]+)\s*\(", text))
+    exported = subprocess.run(["nm", "-D", "--defined-only", built_library], capture_output=True, text=True, check=True).stdout
+    exported = set(re.findall(r"\b(so3_[a-z0-9_]+)\b", exported))
+    assert declared == set(_lib.SYMBOLS) == exported
+    lib = ctypes.CDLL(built_library)
+    for name, nargs in NEW_SYMBOLS.items():
+        assert name in declared and name in _lib.SYMBOLS and hasattr(lib, name), name
+        args = re.search(r"\b%s\s*\(([^)]*)\)" % name, text).group(1).split(",")
+        assert len(args) == len(_lib.SYMBOLS[name][1]) == nargs, (name, args)
+    assert lib.so3_version() == _lib.ABI_VERSION == 210
+    assert _lib.KNN_MAX_K == ref.MAX_K == 64
+
+
+def test_argument_validation_without_gpu(built_library):
+    """On a thread of its own: so3_last_error is thread-local and never cleared, and other tests read it on the main thread."""
+    failure = []
+
+    def body():
+        try:
+            _argument_validation()
+        except BaseException as exc:               # noqa: BLE001 -- re-raised on the main thread
+            failure.append(exc)
+
+    t = threading.Thread(target=body)
+    t.start()
+    t.join()
+    if failure:
+        raise failure[0]
+
+
+def _argument_validation():
+    from poseestimation_amd import _lib
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.cast(buf, ctypes.c_void_p).value
+    err = lib.so3_last_error
+
+    def call(b, n, m, k=4, Y=p, idx=p, stride=None, cov=p, lam=p, nrm=p, frm=p):
+        return lib.so3_local_frames_f32(Y, 3 * max(m, 0) if stride is None else stride, idx, None, None, None, cov, lam, nrm, frm, k, b, n, m, None)
+
+    assert call(0, 8, 8, Y=None, idx=None, cov=None, lam=None, nrm=None, frm=None) == 0          # B == 0: a no-op, whatever the pointers
+    big = _lib.ADD_S_MAX_N + 1
+    for b, n, m in ((-1, 8, 8), (2**62, 8, 8), (4, 0, 8), (4, 8, 0), (4, -3, 8), (4, big, 8), (4, 8, big)):
+        assert call(b, n, m) != 0 and err() == b"so3_local_frames_f32: B/N/M: invalid argument", (b, n, m, err())
+    for k in (0, -1, 65, 2**31 - 1):
+        assert call(4, 8, 8, k) != 0 and err() == b"so3_local_frames_f32: K: invalid argument", (k, err())
+        assert call(0, 8, 8, k) != 0 and err() == b"so3_local_frames_f32: K: invalid argument"    # K is checked before the no-op
+    for stride in (1, 23, -24):
+        assert call(4, 8, 8, stride=stride) != 0 and err() == b"so3_local_frames_f32: y_stride: invalid argument", (stride, err())
+    for kw in ({"Y": None}, {"idx": None}, {"cov": None, "lam": None, "nrm": None, "frm": None}):      # all outputs NULL is an error
+        assert call(4, 8, 8, **kw) != 0 and err() == b"so3_local_frames_f32: null pointer: invalid argument", (kw, err())
+
+
+def test_python_surface_without_gpu():
+    import poseestimation_amd as pa
+    from poseestimation_amd import rotation_representation as rr
+    for name in ("local_frames", "estimate_normals"):
+        assert name in pa.__all__ and getattr(pa, name) is getattr(rr, name)
+    Y, idx = torch.zeros(2, 7, 3), torch.zeros(2, 5, 4, dtype=torch.long)
+    for fn in (lambda: pa.local_frames(Y, idx), lambda: pa.local_frames(Y[0], idx.int(), return_covariance=True),
+               lambda: pa.local_frames(Y, idx, torch.tensor([1, 2]), torch.tensor([3, 4]), torch.zeros(2, 3)),
+               lambda: pa.estimate_normals(Y), lambda: pa.estimate_normals(Y, 3, torch.tensor([1, 2]), torch.zeros(3), True)):
+        with pytest.raises(RuntimeError, match="HIP device only"):
+            fn()
+    for k in (0, -1, 65, 2.0, True, None):
+        with pytest.raises(ValueError, match="estimate_normals: expected an int 1 <= K <= 64, got"):
+            pa.estimate_normals(Y, k)
+
+
+# ---- the fixture ----------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def g29_cases():
+    return ref.cases(ref.g29())
+
+
+def test_g29_is_self_consistent(g29_cases):
+    assert os.path.getsize(ref.GOLDEN) <= 512 * 1024
+    by_name = {c["name"]: c for c in g29_cases}
+    for fam in ref.SURFACES:
+        for n, m, K in ref.SURFACE_SHAPES:
+            c = by_name["%s_%dx%dx%d" % (fam, n, m, K)]
+            assert (c["n"], c["m"], c["K"]) == (n, m, K) and ref.small_gap_share(c["ref64"][1], c["ref64"][3]) <= ref.SMALL_GAP_SHARE, c["name"]
+    assert by_name["sphere_64x64x3"]["K"] == by_name["plane_64x64x3"]["K"] == 3
+    assert {c["family"] for c in g29_cases} == set(ref.SURFACES) | {"shifted", "lattice_plane", "collinear", "tied", "flat", "r2", "mixed", "ragged", "view"}
+    for c in g29_cases:
+        Y, idx, xl, yl = c["Y"], c["idx"], c["x_lengths"], c["y_lengths"]
+        C64, lam64, E64, r, piv = c["ref64"]
+        assert Y.dtype == np.float32 and np.isfinite(Y).all(), c["name"]
+        if c["family"] != "shifted":
+            assert np.linalg.norm(Y, axis=-1).max() <= 1 + 1e-6, c["name"]
+        assert np.array_equal(ref.bits(ref.cov32(Y, idx, xl, yl)), ref.bits(c["cov32"])), c["name"]
+        _, lam, E, r2, _ = ref.frames64(Y, idx, xl, yl)                                          # the recorded eigh is an eigh of C64
+        assert np.array_equal(r, r2) and np.abs(lam - lam64).max() <= 1e-14 * max(1.0, np.abs(lam64).max()), c["name"]
+        assert np.abs(C64 @ E64 - E64 * lam64[..., None, :]).max() <= 1e-14 and np.abs(np.swapaxes(E64, -1, -2) @ E64 - np.eye(3)).max() <= 1e-14, c["name"]
+        ref.judge(c["name"], Y, idx, xl, yl, c["viewpoint"], cov=c["cov32"], ref64=c["ref64"])      # cov32 is an accurate covariance
+    c = by_name["shifted_100x150x12"]                                                            # the pivot keeps float32's digits
+    assert np.abs(c["Y"]).min() > 98 and ref.judge("shifted", c["Y"], c["idx"], None, None, None, cov=c["cov32"], ref64=c["ref64"])["cov"] <= ref.MEASURED["cov"]
+    c = by_name["lattice_plane"]
+    assert (c["ref64"][1][..., 0] == 0).all() and np.abs(np.abs(c["ref64"][2][..., :, 0]) - [0, 0, 1]).max() <= 1e-15 and (c["cov32"][..., [2, 4, 5]] == 0).all()
+    c = by_name["collinear"]
+    assert (c["ref64"][1][..., 1] <= 1e-13).all() and (c["ref64"][1][..., 2] > 1e-4).all()     # collinear up to the points' own rounding
+    for name in ("octahedron", "cube"):
+        lam = by_name[name]["ref64"][1]
+        assert (lam[..., 2] - lam[..., 0] <= 1e-15).all() and (lam > 0.1).all(), name
+    for name in ("all_equal", "r1"):
+        assert (by_name[name]["ref64"][0] == 0).all() and (by_name[name]["ref64"][3] >= 1).all() and (by_name[name]["cov32"] == 0).all(), name
+    assert (by_name["r1"]["ref64"][3] == 1).all() and (by_name["r2"]["ref64"][3] == 2).all() and (by_name["r2"]["ref64"][1][..., 1] <= 1e-15).all()
+    c = by_name["mixed"]
+    valid = (c["idx"] >= 0) & (c["idx"] < c["m"])
+    assert {-1, c["m"], ref.INT32_MIN} <= set(np.unique(c["idx"][~valid])) and not valid[:, :, 0].any() and (np.diff(valid.astype(int), axis=-1) > 0).any()
+    assert (c["ref64"][3][:, 0] == 0).all() and (c["ref64"][3][:, 1] == 1).all() and (c["ref64"][3][:, 2] == 2).all()
+    c = by_name["ragged"]
+    nl, ml = ref.lengths_of(c["x_lengths"], c["b"], c["n"]), ref.lengths_of(c["y_lengths"], c["b"], c["m"])
+    assert nl[0] == 0 and ml[1] == 0 and ml[2] == 1 and 1 < ml[3] < c["K"] and (c["ref64"][3][:2] == 0).all() and (c["ref64"][3][2, :nl[2]] == 1).all()
+    assert (c["ref64"][3][3, :nl[3]] == ml[3]).all() and (c["ref64"][3][3, nl[3]:] == 0).all()
+    assert np.array_equal(by_name["view_inside"]["Y"], by_name["view_outside"]["Y"]) and np.abs(by_name["view_inside"]["viewpoint"]).max() == 0
+    assert np.linalg.norm(by_name["view_outside"]["viewpoint"]) > 1
+
+
+# ---- the checks, shared with tests/test_gpu_local_frames.py ---------------------------------------------------------------
+def check_case(label, c, outs, constants=ref.CONSTANTS):
+    """outs = (cov, eigenvalues, normals, frames) as numpy arrays or None -> the judges' figures."""
+    cov, lam, nrm, frm = outs
+    got = ref.judge(label + " " + c["name"], c["Y"], c["idx"], c["x_lengths"], c["y_lengths"], c["viewpoint"], cov, lam, nrm, frm,
+                    want_cov=c["cov32"], constants=constants, ref64=c["ref64"])
+    if c["name"] == "lattice_plane" and lam is not None:
+        assert (lam[..., 0] == 0).all(), label                                                   # lambda_0 == 0 exactly
+    if c["name"] == "view_outside" and nrm is not None:                                          # the facing side points outward
+        facing = ref.facing_side(c["Y"][:, :c["n"]], c["viewpoint"])
+        assert facing.sum() >= 5 and ((nrm.astype(np.float64) * c["Y"][:, :c["n"]]).sum(-1)[facing] > 0).all(), label
+    if c["name"] == "view_inside" and nrm is not None:                                           # towards the centre: inward
+        assert ((nrm.astype(np.float64) * c["Y"][:, :c["n"]]).sum(-1) < 0).all(), label
+    return got
+
+
+def check_against_g29(cases, run, label, constants=ref.CONSTANTS):
+    """`run(case)` -> (cov, eigenvalues, normals, frames).  -> the worst figure of each judge over the fixture."""
+    worst = {}
+    for c in cases:
+        for k, v in check_case(label, c, run(c), constants).items():
+            worst[k] = max(worst.get(k, 0.0), v)
+    return worst
+
+
+def scaled_case(c, e):
+    """The case with its cloud (and viewpoint) multiplied by 2^e."""
+    s = np.float32(2.0 ** e)
+    d = dict(c)
+    d["Y"] = c["Y"] * s
+    d["viewpoint"] = None if c["viewpoint"] is None else c["viewpoint"] * s
+    return d
+
+
+def check_power_of_two(label, c, base, run, e=20):
+    """Scaling the cloud by 2^+-e scales cov and the eigenvalues by 4^+-e bit for bit and leaves the frames' bits."""
+    for ee in (e, -e):
+        cov, lam, nrm, frm = run(scaled_case(c, ee))
+        f = np.float32(4.0 ** ee)
+        assert np.array_equal(ref.bits(cov), ref.bits(base[0] * f)), (label, c["name"], ee, "cov")
+        assert np.array_equal(ref.bits(lam), ref.bits(base[1] * f)), (label, c["name"], ee, "eigenvalues")
+        assert np.array_equal(ref.bits(nrm), ref.bits(base[2])) and np.array_equal(ref.bits(frm), ref.bits(base[3])), (label, c["name"], ee, "frames")
+
+
+# ---- the device functions on the host --------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def model(tmp_path_factory):
+    from oracle import kernel_model
+    cxx = kernel_model.clangxx()
+    if cxx is None:
+        pytest.skip("clang++ is not available (ext_vector_type)")
+    out = str(tmp_path_factory.mktemp("local_frames") / "liblocal_frames.so")
+    subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", out, SRC], check=True)
+    lib = ctypes.CDLL(out)
+    P, I64, I32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
+    lib.model_local_frames.argtypes = [P, I64, P, P, P, P, P, P, P, P, I32, I64, I32, I32, I32]
+    return lib
+
+
+def _p(a):
+    return ctypes.c_void_p(a.ctypes.data) if a is not None else None
+
+
+def host_run(model, c, sweeps=SWEEPS, want=(True, True, True, True)):
+    b, n, m, K = c["b"], c["n"], c["m"], c["K"]
+    Y, idx = np.ascontiguousarray(c["Y"], np.float32), np.ascontiguousarray(c["idx"], np.int32)
+    xl, yl, view = (None if c[k] is None else np.ascontiguousarray(c[k], t) for k, t in (("x_lengths", np.int32), ("y_lengths", np.int32), ("viewpoint", np.float32)))
+    outs = [np.full((b, n, w), np.nan, np.float32) if flag else None for flag, w in zip(want, (6, 3, 3, 9))]
+    assert model.model_local_frames(_p(Y), 3 * m, _p(idx), _p(xl), _p(yl), _p(view), *(_p(o) for o in outs), K, b, n, m, sweeps) == 0
+    return tuple(outs)
+
+
+def test_host_model_against_g29(model, g29_cases):
+    """Bit-equal to cov32 and within the UN-multiplied bounds (the judges' constants are 4 x these), twice with the same bits."""
+    assert model.model_local_frames_sweeps() == SWEEPS
+    worst = check_against_g29(g29_cases, lambda c: host_run(model, c), "host", constants=ref.MEASURED)
+    print("host model over G29, in units of u t (orth: u):", {k: round(v, 2) for k, v in sorted(worst.items())})
+    assert all(4 * ref.MEASURED[k] == ref.CONSTANTS[k] for k in ref.MEASURED)
+    assert all(worst[k] > ref.MEASURED[k] / 2 for k in worst), worst                             # the recorded figures are the measured ones, not slack
+    c = next(c for c in g29_cases if c["name"] == "blob_257x300x16")
+    a, b_ = host_run(model, c), host_run(model, c)
+    assert all(np.array_equal(ref.bits(u), ref.bits(v)) for u, v in zip(a, b_))
+    only = host_run(model, c, want=(False, False, True, False))                                  # normals alone
+    assert only[0] is None and np.array_equal(ref.bits(only[2]), ref.bits(a[2]))
+
+
+def test_host_model_sweep_count(model, g29_cases):
+    """One sweep fewer misses the un-multiplied residual figure; one sweep more changes nothing the judges see."""
+    inf = {k: np.inf for k in ref.CONSTANTS}
+    fewer = check_against_g29(g29_cases, lambda c: host_run(model, c, SWEEPS - 1), "host, one sweep fewer", constants=inf)
+    more = check_against_g29(g29_cases, lambda c: host_run(model, c, SWEEPS + 1), "host, one sweep more", constants=ref.MEASURED)
+    print("one sweep fewer:", {k: round(v, 2) for k, v in sorted(fewer.items())}, " one more:", {k: round(v, 2) for k, v in sorted(more.items())})
+    assert fewer["res"] > ref.MEASURED["res"], fewer
+
+
+def test_host_model_power_of_two(model, g29_cases):
+    for c in g29_cases:
+        if c["family"] in ("sphere", "plane", "lattice_plane", "tied", "flat", "mixed", "ragged", "view") and c["n"] <= 257:
+            check_power_of_two("host", c, host_run(model, c), lambda d: host_run(model, d))

@@ -229,6 +229,20 @@ def main():
                lambda i: lib.so3_knn_bwd_f32(p(xk), p(yk), None, None, p(ik), p(gk), p(gxk), p(gyk), kk, bk, nk, mk, st),
                bk * (nk * kk * 8 + (nk + mk) * 24), iters=10, warm=2)
     del xk, yk, dk, ik, gk, gxk, gyk
+    # local frames: the covariance of every point's K nearest neighbours and its eigen-decomposition, from indices that are given (the
+    # bytes are the index rows', one gathered point per slot and the outputs')
+    for bl, nl, kl in ((32, 1024, 16), (8, 4096, 20)):
+        yl_ = torch.rand(bl, nl, 3, device=dev)
+        il = torch.empty(bl, nl, kl, dtype=torch.int32, device=dev)
+        _lib.check(lib.so3_knn_f32(p(yl_), p(yl_), 3 * nl, None, None, None, p(il), kl, bl, nl, nl, st), "so3_knn_f32")
+        cl, el, ml, fl = (torch.empty(bl, nl, w, device=dev) for w in (6, 3, 3, 9))
+        timeit("local_frames: so3_local_frames_f32 (%d x %d, K = %d, all outputs)" % (bl, nl, kl),
+               lambda i: lib.so3_local_frames_f32(p(yl_), 3 * nl, p(il), None, None, None, p(cl), p(el), p(ml), p(fl), kl, bl, nl, nl, st),
+               bl * nl * (kl * 16 + 84), iters=20, warm=3)
+        timeit("local_frames: so3_local_frames_f32 (%d x %d, K = %d, normals only)" % (bl, nl, kl),
+               lambda i: lib.so3_local_frames_f32(p(yl_), 3 * nl, p(il), None, None, None, None, None, p(ml), None, kl, bl, nl, nl, st),
+               bl * nl * (kl * 16 + 12), iters=20, warm=3)
+    del yl_, il, cl, el, ml, fl
     # PointNet++ sampling and grouping at the reference model's first level: a chain of 511 dependent argmaxes per cloud (one workgroup
     # each: latency bound, most compute units idle at B = 32), and one wave per centre over the cloud (the bytes are the index rows')
     bf, nf, sf, kf = 32, 1024, 512, 64

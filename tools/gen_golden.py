@@ -1253,7 +1253,22 @@ def g28_knn():
     assert os.path.getsize(os.path.join(OUT, "g28_knn.npz")) <= 512 * 1024
 
 
+def g29_local_frames():
+    """local_frames: no reference code exists, so the fixture holds the inputs (clouds of unit radius, their index rows, lengths and
+    viewpoints: the surface families at tests/local_frames_ref.py: SURFACE_SHAPES and at K = 3, the sphere shifted by 100, the exact
+    lattice plane, collinear points, the octahedron and the cube, all-equal neighbours, r = 1 and r = 2, rows whose valid slots are
+    no prefix, ragged lengths, a viewpoint inside and one outside the sphere) and the outputs of the float32 restatement of the
+    covariance and of float64 numpy.linalg.eigh -- tests/local_frames_ref.py: generate, which asserts the covariance's bound against
+    float64 and the share of small-gap rows on every case."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import local_frames_ref as ref
+    save("g29_local_frames.npz", **ref.generate())
+    assert os.path.getsize(os.path.join(OUT, "g29_local_frames.npz")) <= 512 * 1024
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "g29":
+        return g29_local_frames()
     if len(sys.argv) > 1 and sys.argv[1] == "g28":
         return g28_knn()
     if len(sys.argv) > 1 and sys.argv[1] == "g27":
@@ -1311,6 +1326,7 @@ def main():
     g21_icp()
     g27_chamfer()
     g28_knn()
+    g29_local_frames()
     g22_pointnet()
     g23_head_edges()
     # ---- G1: config #1, 256 Gaussian rows ------------------------------------------------------
