@@ -624,6 +624,51 @@ int so3_icp_f32(const float *P, const float *Q, int64_t q_stride, const float *w
                 int32_t iterations, float *R, float *t, float *rmse, int32_t *inliers, int32_t *nearest, float *dist,
                 void *workspace, int64_t B, int32_t N, int32_t M, void *stream);
 
+/* ---- point-to-plane ICP over the target's normals (added in 210) ----
+ * so3_icp_plane_f32: `iterations` Gauss-Newton iterations of  min sum_i w'_i (n_j(i) . (R p_i + t - q_j(i)))^2  from the pose
+ * T_init, without early exit.  One iteration from m_k = (R_k | t_k), for cloud b:
+ *   1. search   x_i = pose_point(m_k, p_i);  j(i), d2_i, d_i = sqrt(d2_i) exactly as so3_nearest_f32(x, Q): nearest and dist are
+ *               the bits so3_icp_f32 returns from the same pose.
+ *   2. normal   n_i = normals[b][j(i)]; the normals lie beside Q with the same stride (q_stride == 0: one shared target and one
+ *               shared normal array); j is clamped to M - 1 before anything is addressed.  A normal whose three components are
+ *               all zero names no plane (so3_local_frames_f32's rows past a length, a flat patch).
+ *   3. weight   w'_i = w_i * [d_i <= max_distance] * [n_i != 0]   (max_distance < 0: no trimming).
+ *   4. row      pivot c = pose_point(m_k, p_0), the posed first source point: moments are taken about a point inside the
+ *               cloud, so a cloud 100 units from the origin keeps float32's digits.  a_i = x_i - c, e_i = x_i - q_j(i) (one
+ *               rounded subtraction per coordinate), r_i = n_i . e_i, J_i = (a_i x n_i, n_i) in R^6.
+ *   5. sums     sum w';  the 21 upper-triangle entries of A = sum w' J J^T;  g = sum w' J r;  sum w' r^2;  sum w' d2;  the
+ *               count #{w' > 0}: 31 sums per work item in a record of 32 floats, added in a fixed order (no atomics).
+ *   6. finish   sum w' == 0: not live -- the pose is kept, both rmse are 0, solved = 0.  Otherwise A'_aa = A_aa (1 + damping)
+ *               (Levenberg-Marquardt's diagonal form) and a 6x6 Cholesky A' = L L^T in float32; pivot k passes when
+ *               p_k > SO3_ICP_PLANE_PIVOT_EPS * A'_kk (strictly: an exactly zero column fails).  Any failed pivot: the cloud
+ *               is UNSOLVED -- the pose is kept, solved = 0, rmse and inliers are still reported.  With damping > 0 a column
+ *               with A_kk == 0 (J_k = 0 on every inlier, so its row, its column and g_k are 0 as well) is skipped with
+ *               delta_k = 0 instead of failing: scaling a zero diagonal cannot lift it, and 0 is the limit of Marquardt's
+ *               additive form.  SO3_ICP_PLANE_PIVOT_EPS is the largest power of two at which the float32 arithmetic solves
+ *               every step of the test fixture whose float64 equilibrated condition number is at most 1e3.  Otherwise
+ *               delta = -A'^-1 g, omega = delta[0:3], v = delta[3:6];  with h = omega / 2, s = |h|^2:
+ *                   dR = I + (2 / (1 + s)) (hat(h) + hat(h)^2)       -- the rotation of the quaternion (1, h), no sin / cos,
+ *                   R_k+1 = so3_project_fwd_f32's projection of dR R_k,   t_k+1 = dR (t_k - c) + c + v.
+ *               rmse[k][b] = sqrt(sum w' r^2 / sum w') (point-to-plane), rmse_point[k][b] = sqrt(sum w' d2 / sum w'),
+ *               inliers[k][b] = the count -- all at the pose the iteration started from.
+ * Negating any of the normals changes no bit of any output (r and J flip together), so no orientation step is needed.
+ *   P, Q, q_stride, w, T_init, max_distance, R, t, nearest, dist: as so3_icp_f32
+ *   normals     in   as Q: M*3 float32 per target (B of them, or one with q_stride == 0)
+ *   damping     >= 0 (negative or NaN: invalid argument); 0 is plain Gauss-Newton
+ *   rmse, rmse_point  out optional iterations*B float32;   inliers, solved  out optional iterations*B int32
+ *   workspace   caller-owned, so3_icp_plane_workspace_bytes(B, N) bytes (0 for B or N out of range), 16-byte aligned; no zero-fill.
+ * iterations == 0 returns the initial pose (and, when asked for, nearest and dist of a search at that pose).  An iteration is
+ * two launches on the caller's stream; nothing synchronises with the host and nothing uses atomics or memset, so a call can be
+ * captured in a graph, the same inputs give the same bits, and a NaN or Inf cloud changes no other cloud.  Limits as
+ * so3_icp_f32.  Not differentiable.
+ */
+#define SO3_ICP_PLANE_PIVOT_EPS 0.0078125f /* 2^-7 */
+size_t so3_icp_plane_workspace_bytes(int64_t B, int32_t N);
+int so3_icp_plane_f32(const float *P, const float *Q, const float *normals, int64_t q_stride, const float *w,
+                      const float *T_init, float max_distance, float damping, int32_t iterations, float *R, float *t,
+                      float *rmse, float *rmse_point, int32_t *inliers, int32_t *solved, int32_t *nearest, float *dist,
+                      void *workspace, int64_t B, int32_t N, int32_t M, void *stream);
+
 /* ---- Chamfer distance between two ragged clouds, with gradients to both (added in 210) ----
  * Cloud b uses the first n_b = clip(x_len[b], 0, N) points of X and the first m_b = clip(y_len[b], 0, M) points of Y (NULL: all).
  *     j(i) = the first argmin over j < m_b of |x_i - y_j|^2,   i(j) = the first argmin over i < n_b of |y_j - x_i|^2

@@ -74,6 +74,8 @@ SYMBOLS = {
     "so3_nearest_f32": (_INT, [_P, _P, _I64, _P, _P, _I64, _I32, _I32, _P]),
     "so3_icp_workspace_bytes": (ctypes.c_size_t, [_I64, _I32]),
     "so3_icp_f32": (_INT, [_P, _P, _I64, _P, _P, ctypes.c_float, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P]),
+    "so3_icp_plane_workspace_bytes": (ctypes.c_size_t, [_I64, _I32]),
+    "so3_icp_plane_f32": (_INT, [_P, _P, _P, _I64, _P, _P, ctypes.c_float, ctypes.c_float, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P]),
     "so3_chamfer_workspace_bytes": (ctypes.c_size_t, [_I64, _I32, _I32]),
     "so3_chamfer_fwd_f32": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U32, _I64, _I32, _I32, _P]),
     "so3_chamfer_bwd_f32": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U32, _I64, _I32, _I32, _P]),

@@ -1314,6 +1314,149 @@ __device__ __forceinline__ void icp_finish(const float (&s)[kIcpSums], const flo
     inliers = s[17];
 }
 
+// ---- point-to-plane ICP over target normals (so3proj.hip: k_icp_plane_step, k_icp_plane_finish; tests/host_model/icp_plane.cpp) -----
+// One iteration from the pose m:  x_i = m p_i,  j(i), d2_i, d_i as above,  n_i = normals[j(i)],  w'_i = w_i [d_i <= max_distance] [n_i != 0].
+// With the pivot c = m p_0 (the posed first source point):  a_i = x_i - c,  e_i = x_i - q_j(i),  r_i = n_i . e_i,  J_i = (a_i x n_i, n_i).
+// The linearised residual of the update x' = dR (x - c) + c + v is r + J . (omega, v), so the step solves A delta = -g with
+// A = sum w' J J^T, g = sum w' J r.  A record's 31 sums:
+//     s[0] = sum w',  s[1 + plane_tri(k, l)] = A_kl (k <= l, 21 entries),  s[22 + k] = g_k,  s[28] = sum w' r^2,  s[29] = sum w' d2,
+//     s[30] = #{w' > 0} (a float count).
+// Negating n negates r and J exactly (every operation below is odd in n), and A, g, r^2 only see their products: the same bits.
+constexpr int kPlaneSums = 31;
+constexpr int kPlaneRecord = 32;                 // floats per partial record in the workspace: eight float4
+constexpr float kPlanePivotEps = 1.0f / 128.0f;  // include/so3proj.h: SO3_ICP_PLANE_PIVOT_EPS = 2^-7; DESIGN.md 7l has the rule and its margins
+constexpr int plane_tri(int k, int l) { return k * 6 - k * (k - 1) / 2 + (l - k); }      // the upper triangle, row by row: k <= l
+// One source point's share.  The order inside it: the trimmed weight; r = fma(n_z, e_z, fma(n_y, e_y, n_x e_x)); the cross product as
+// fma(a_y, n_z, -(a_z n_y)) and its rotations; wJ_k = w' J_k; then s[0] += w', A_kl = fma(wJ_k, J_l, A_kl) in plane_tri's order,
+// g_k = fma(wJ_k, r, g_k), wr = w' r, s[28] = fma(wr, r, s[28]), s[29] = fma(w', d2, s[29]), the count.
+template <bool TRIMMED>
+__device__ __forceinline__ void plane_accumulate(float w, float d2, float d, float max_distance, float ax, float ay, float az, float ex, float ey,
+                                                 float ez, float nx, float ny, float nz, float (&s)[kPlaneSums]) {
+    if (TRIMMED) w = d <= max_distance ? w : 0.f;
+    w = (nx != 0.f || ny != 0.f || nz != 0.f) ? w : 0.f;
+    const float r = __builtin_fmaf(nz, ez, __builtin_fmaf(ny, ey, nx * ex));
+    const float J[6] = {__builtin_fmaf(ay, nz, -(az * ny)), __builtin_fmaf(az, nx, -(ax * nz)), __builtin_fmaf(ax, ny, -(ay * nx)), nx, ny, nz};
+    float wJ[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) wJ[k] = w * J[k];
+    s[0] += w;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+#pragma unroll
+        for (int l = k; l < 6; ++l) s[1 + plane_tri(k, l)] = __builtin_fmaf(wJ[k], J[l], s[1 + plane_tri(k, l)]);
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) s[22 + k] = __builtin_fmaf(wJ[k], r, s[22 + k]);
+    const float wr = w * r;
+    s[28] = __builtin_fmaf(wr, r, s[28]);
+    s[29] = __builtin_fmaf(w, d2, s[29]);
+    s[30] += w > 0.f ? 1.f : 0.f;
+}
+// delta = -A^-1 g by a 6x6 Cholesky A = L L^T, row by row, every loop unrolled over constant indices (registers, no stack object).
+// a: the upper triangle in plane_tri's order.  Pivot k is  p_k = A_kk - sum_{m<k} L_km^2  (subtracted in ascending m, one fma each) and
+// passes when p_k > kPlanePivotEps A_kk -- strictly, so a zero column fails, and so does a NaN.  Below the pivot
+// L_ik = (A_ki - sum_{m<k} L_im L_km) / L_kk with 1 / L_kk = rcp(sqrt(p_k)).  Returns whether every pivot passed; `ratio` is the
+// smallest p_k / A_kk met up to and including the first failure (the host model reports it: what kPlanePivotEps was chosen from; dead
+// code on the device).  delta is 0 when unsolved.
+// `damped` (damping > 0): a column with A_kk == 0 is skipped instead of failing.  A_kk = sum w' J_k^2 = 0 means J_k = 0 on every
+// inlier, so row and column k of A and g_k are 0 too: the column takes L_kk = 1 and comes out with delta_k = 0, the limit of
+// Marquardt's additive form, and the other unknowns do not see it.  Scaling a zero diagonal by (1 + damping) could never lift it.
+__device__ __forceinline__ bool plane_solve(const float (&a)[21], const float (&g)[6], bool damped, float (&delta)[6], float &ratio) {
+    float L[21], inv[6], y[6];                  // L_ik (i >= k) lives at plane_tri(k, i)
+    bool ok = true;
+    ratio = __builtin_huge_valf();
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        float p = a[plane_tri(k, k)];
+#pragma unroll
+        for (int m = 0; m < k; ++m) p = __builtin_fmaf(-L[plane_tri(m, k)], L[plane_tri(m, k)], p);
+        const bool skip = damped && a[plane_tri(k, k)] == 0.f;
+        const bool pass = p > kPlanePivotEps * a[plane_tri(k, k)];
+        const float rk = a[plane_tri(k, k)] != 0.f ? p * hw::rcp(a[plane_tri(k, k)]) : 0.f;
+        ratio = ok && !skip ? __builtin_fminf(ratio, rk) : ratio;      // up to and including the first pivot that fails
+        ok = ok && (pass || skip);
+        p = pass ? p : 1.f;                      // a skipped column's L_kk; after a failure it keeps the rest finite, whose result is not used
+        L[plane_tri(k, k)] = hw::sqrt(p);
+        inv[k] = hw::rcp(L[plane_tri(k, k)]);
+#pragma unroll
+        for (int i = k + 1; i < 6; ++i) {
+            float v = a[plane_tri(k, i)];
+#pragma unroll
+            for (int m = 0; m < k; ++m) v = __builtin_fmaf(-L[plane_tri(m, i)], L[plane_tri(m, k)], v);
+            L[plane_tri(k, i)] = v * inv[k];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {                // L y = -g
+        float v = -g[k];
+#pragma unroll
+        for (int m = 0; m < k; ++m) v = __builtin_fmaf(-L[plane_tri(m, k)], y[m], v);
+        y[k] = v * inv[k];
+    }
+#pragma unroll
+    for (int k = 5; k >= 0; --k) {               // L^T delta = y
+        float v = y[k];
+#pragma unroll
+        for (int m = 5; m > k; --m) v = __builtin_fmaf(-L[plane_tri(k, m)], delta[m], v);
+        delta[k] = ok ? v * inv[k] : 0.f;
+    }
+    return ok;
+}
+// dR = I + (2 / (1 + s)) (hat(h) + hat(h)^2),  h = omega / 2,  s = |h|^2: the rotation of the unnormalised quaternion (1, h) (Cayley).
+__device__ __forceinline__ void plane_retraction(float wx, float wy, float wz, float (&dr)[9]) {
+    const float hx = 0.5f * wx, hy = 0.5f * wy, hz = 0.5f * wz;
+    const float f = 2.f * hw::rcp(1.f + pair_dist2(hx, hy, hz));
+    dr[0] = __builtin_fmaf(-f, __builtin_fmaf(hy, hy, hz * hz), 1.f);
+    dr[1] = f * __builtin_fmaf(hx, hy, -hz);
+    dr[2] = f * __builtin_fmaf(hx, hz, hy);
+    dr[3] = f * __builtin_fmaf(hx, hy, hz);
+    dr[4] = __builtin_fmaf(-f, __builtin_fmaf(hx, hx, hz * hz), 1.f);
+    dr[5] = f * __builtin_fmaf(hy, hz, -hx);
+    dr[6] = f * __builtin_fmaf(hx, hz, -hy);
+    dr[7] = f * __builtin_fmaf(hy, hz, hx);
+    dr[8] = __builtin_fmaf(-f, __builtin_fmaf(hx, hx, hy * hy), 1.f);
+}
+// A cloud's summed record -> the next pose, both rmse, the inlier count and whether the step was solved.  c: the pivot the sums were
+// taken about (pose_point(prev, p_0)).  Not live (s[0] == 0): the pose is kept, both rmse 0, solved 0.  A failed pivot: the pose is kept,
+// solved 0, rmse and inliers still reported.  Otherwise R' = project_rotation(dR R), t' = (dR (t - c) + c) + v.
+__device__ __forceinline__ void plane_finish(const float (&s)[kPlaneSums], const float (&c)[3], const float (&prev)[12], float damping,
+                                             float (&next)[12], float &rmse, float &rmse_point, float &inliers, bool &solved) {
+    const bool live = s[0] != 0.f;
+    float a[21], g[6], delta[6], dr[9], h[9], r[9], ratio;
+    const float lm = 1.f + damping;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+#pragma unroll
+        for (int l = k; l < 6; ++l) a[plane_tri(k, l)] = k == l ? s[1 + plane_tri(k, l)] * lm : s[1 + plane_tri(k, l)];
+        g[k] = s[22 + k];
+    }
+    solved = plane_solve(a, g, damping > 0.f, delta, ratio) && live;
+    plane_retraction(solved ? delta[0] : 0.f, solved ? delta[1] : 0.f, solved ? delta[2] : 0.f, dr);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            h[3 * i + j] = __builtin_fmaf(dr[3 * i + 2], prev[8 + j], __builtin_fmaf(dr[3 * i + 1], prev[4 + j], dr[3 * i] * prev[j]));
+    }
+    if (!solved) {                                              // keep the projection away from a pose that may not be finite
+#pragma unroll
+        for (int i = 0; i < 9; ++i) h[i] = (i & 3) == 0 ? 1.f : 0.f;
+    }
+    project_rotation<float>(h, r);
+    const float u[3] = {prev[3] - c[0], prev[7] - c[1], prev[11] - c[2]};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const float t = (__builtin_fmaf(dr[3 * i + 2], u[2], __builtin_fmaf(dr[3 * i + 1], u[1], dr[3 * i] * u[0])) + c[i]) + delta[3 + i];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) next[4 * i + j] = solved ? r[3 * i + j] : prev[4 * i + j];
+        next[4 * i + 3] = solved ? t : prev[4 * i + 3];
+    }
+    const float inv = align_inv_weight(s[0]);
+    rmse = live ? hw::sqrt(s[28] * inv) : 0.f;
+    rmse_point = live ? hw::sqrt(s[29] * inv) : 0.f;
+    inliers = s[30];
+}
+
 // ---- PointNet++ sampling and grouping: farthest-point sampling and ball query (so3proj.hip: k_fps, k_ball_query;
 // tests/host_model/pointnet.cpp) -------------------------------------------------------------------------------------------------
 // Farthest-point sampling is a chain: one argmax that rounds differently changes every later index.  Its arithmetic is therefore a

@@ -1946,6 +1946,120 @@ __global__ __launch_bounds__(kBlock) void k_icp_initial_pose(const float *__rest
     if (j < 3) R[b * 9 + 3 * c + j] = v; else T[b * 3 + c] = v;
 }
 
+// ---- point-to-plane ICP: k_icp_step's search, then the 31 sums of the Gauss-Newton system over the target's normals ----------------
+// The search is k_icp_step's through tile_search (the same add_s_pair in the same order: the same nearest and dist bits).  The 31
+// accumulators are declared after it, so the pair loop holds what k_icp_step's holds.  Per point the epilogue gathers q_j and n_j
+// (12 B each, L2 hits) and REUSES the posed x_i the search kept: 3 U registers stay live past the loop instead of 3 reloads and 9 FMAs
+// per point, and x_i - c, x_i - q_j are then formed from the very bits the search compared.  c = the posed p_0, wave-uniform.
+// wave_allsum per sum, item_record<32> through the tile: one record per work item in rec[b][chunk][.], no atomics.
+template <bool WEIGHTED, bool TRIMMED, int U>
+__global__ __launch_bounds__(kBlock) void k_icp_plane_step(const float *__restrict__ P, const float *__restrict__ Q,
+                                                           const float *__restrict__ Nrm, int64_t q_stride, const float *__restrict__ Wt,
+                                                           const float *__restrict__ pose, float max_distance, float *__restrict__ rec,
+                                                           float *__restrict__ dist, int32_t *__restrict__ nearest, int64_t B, int32_t N,
+                                                           int32_t M, int32_t chunks) {
+    static_assert(kBlock == so3::kIcpBlock, "the host model's chunking");
+    __shared__ float4 tile[kAddsTile];
+    const int tid = threadIdx.x;
+    const int64_t items = B * chunks;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t b = item / chunks;
+        const int chunk = static_cast<int>(item - b * chunks);
+        const int i_base = chunk * (kBlock * U);
+        const float *src = P + b * N * 3, *tgt = Q + b * q_stride, *nrm = Nrm + b * q_stride;
+        float m[12];
+        if (pose != nullptr) {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) m[k] = pose[b * 12 + k];          // wave-uniform: scalar loads
+        }
+        float x[U], y[U], z[U], best[U];
+        int idx[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = min(i_base + u * kBlock + tid, N - 1);             // a slot beyond the cloud repeats its last point; weight 0, not stored
+            const float px = src[i * 3 + 0], py = src[i * 3 + 1], pz = src[i * 3 + 2];
+            if (pose != nullptr) so3::pose_point(m, px, py, pz, x[u], y[u], z[u]);
+            else { x[u] = px; y[u] = py; z[u] = pz; }
+            best[u] = __builtin_huge_valf();
+            idx[u] = 0;
+        }
+        tile_search<true, false, U>(tile, tid, M, [&](int j) { return tile_point(tgt, j); }, x, y, z, best, idx);
+        float c[3] = {src[0], src[1], src[2]};                               // the pivot: the posed first source point, wave-uniform
+        if (pose != nullptr) so3::pose_point(m, src[0], src[1], src[2], c[0], c[1], c[2]);
+        float acc[so3::kPlaneSums];
+#pragma unroll
+        for (int k = 0; k < so3::kPlaneSums; ++k) acc[k] = 0.f;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = i_base + u * kBlock + tid;
+            const bool in = i < N;
+            const int j = min(idx[u], M - 1);
+            const float d = so3::hw::sqrt(best[u]);
+            if (in) {
+                if (dist != nullptr) dist[b * N + i] = d;
+                if (nearest != nullptr) nearest[b * N + i] = j;
+            }
+            const float w = in ? (WEIGHTED ? Wt[b * N + min(i, N - 1)] : 1.f) : 0.f;
+            so3::plane_accumulate<TRIMMED>(w, best[u], d, max_distance, x[u] - c[0], y[u] - c[1], z[u] - c[2], x[u] - tgt[j * 3 + 0],
+                                           y[u] - tgt[j * 3 + 1], z[u] - tgt[j * 3 + 2], nrm[j * 3 + 0], nrm[j * 3 + 1], nrm[j * 3 + 2], acc);
+        }
+        const int lane = tid & 63;
+        float mine = 0.f;                                        // lane k < kPlaneSums keeps sum k of its wave, the record's padding 0
+#pragma unroll
+        for (int k = 0; k < so3::kPlaneSums; ++k) {
+            const float tot = wave_allsum(acc[k]);
+            mine = lane == k ? tot : mine;
+        }
+        item_record<so3::kPlaneRecord>(tile, tid, lane < so3::kPlaneSums ? mine : 0.f, rec + (b * chunks + chunk) * so3::kPlaneRecord);
+    }
+}
+
+// One wave per cloud.  Lane k < kPlaneRecord adds entry k of the cloud's records in chunk order; the sums are broadcast by readlane and
+// every lane runs the same solve (plane_finish: the damped Cholesky, the Cayley retraction, the projection); lanes 0..11 write the next
+// pose, lane 0 the iteration's figures.  prev == nullptr: the iteration started from the identity.  R, T when given: the last iteration.
+__global__ __launch_bounds__(kBlock) void k_icp_plane_finish(const float *__restrict__ P, const float *__restrict__ rec,
+                                                             const float *__restrict__ prev, float damping, float *__restrict__ next,
+                                                             float *__restrict__ R, float *__restrict__ T, float *__restrict__ rmse,
+                                                             float *__restrict__ rmse_point, int32_t *__restrict__ inliers,
+                                                             int32_t *__restrict__ solved, int64_t B, int32_t N, int32_t chunks) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = static_cast<int64_t>(blockIdx.x) * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t nwaves = static_cast<int64_t>(gridDim.x) * (kBlock / 64);
+    for (int64_t b = wave; b < B; b += nwaves) {
+        const float *r = rec + b * chunks * so3::kPlaneRecord;
+        float v = 0.f;
+        if (lane < so3::kPlaneRecord) {
+            for (int c = 0; c < chunks; ++c) v += r[c * so3::kPlaneRecord + lane];
+        }
+        float s[so3::kPlaneSums], c[3], mp[12], mn[12], e, ep, cnt;
+        bool ok;
+#pragma unroll
+        for (int k = 0; k < so3::kPlaneSums; ++k) s[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k));
+#pragma unroll
+        for (int k = 0; k < 12; ++k) mp[k] = prev != nullptr ? prev[b * 12 + k] : ((k % 5) == 0 ? 1.f : 0.f);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) c[k] = P[b * N * 3 + k];
+        if (prev != nullptr) so3::pose_point(mp, P[b * N * 3 + 0], P[b * N * 3 + 1], P[b * N * 3 + 2], c[0], c[1], c[2]);
+        so3::plane_finish(s, c, mp, damping, mn, e, ep, cnt, ok);
+        float out = 0.f;
+#pragma unroll
+        for (int k = 0; k < 12; ++k) out = lane == k ? mn[k] : out;
+        if (lane < 12) {
+            next[b * 12 + lane] = out;
+            if (R != nullptr) {
+                const int cc = lane >> 2, k = lane & 3;
+                if (k < 3) R[b * 9 + 3 * cc + k] = out; else T[b * 3 + cc] = out;
+            }
+        }
+        if (lane == 0) {
+            if (rmse != nullptr) rmse[b] = e;
+            if (rmse_point != nullptr) rmse_point[b] = ep;
+            if (inliers != nullptr) inliers[b] = static_cast<int32_t>(cnt);
+            if (solved != nullptr) solved[b] = ok ? 1 : 0;
+        }
+    }
+}
+
 // ---- Chamfer distance: both searches in one launch, both gradients in one gather ---------------------------------------------------
 // k_chamfer_fwd is k_icp_step<.., SUMS = false, U> over the work items of BOTH directions: a cloud has chunks_x items that search Y
 // for kBlock * U points of X, then chunks_y items that search X for points of Y (chunks_y = 0: x direction only).  The clouds are
@@ -4944,6 +5058,57 @@ int so3_icp_f32(const float *P, const float *Q, int64_t q_stride, const float *w
         cur = next;
     }
     return check_launch("so3_icp_f32");
+}
+
+size_t so3_icp_plane_workspace_bytes(int64_t B, int32_t N) {
+    if (B < 0 || B > (INT64_C(1) << 31) || N < 1 || N > SO3_ADD_S_MAX_N) return 0;
+    // two pose buffers and one record per work item at the smallest work item (U = 1), whatever the device
+    return static_cast<size_t>(B) * (2 * 12 + static_cast<size_t>((N + kBlock - 1) / kBlock) * so3::kPlaneRecord) * sizeof(float);
+}
+
+int so3_icp_plane_f32(const float *P, const float *Q, const float *normals, int64_t q_stride, const float *w, const float *T_init,
+                      float max_distance, float damping, int32_t iterations, float *R, float *t, float *rmse, float *rmse_point,
+                      int32_t *inliers, int32_t *solved, int32_t *nearest, float *dist, void *workspace, int64_t B, int32_t N, int32_t M,
+                      void *stream) {
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && M >= 1 && M <= SO3_ADD_S_MAX_N, "so3_icp_plane_f32: B/N");
+    SO3_CHECK_ARGS(iterations >= 0 && iterations <= SO3_ICP_MAX_ITERATIONS, "so3_icp_plane_f32: iterations");
+    SO3_CHECK_ARGS(damping >= 0.f, "so3_icp_plane_f32: damping");                      // a NaN fails the comparison
+    if (B == 0) return 0;
+    SO3_CHECK_ARGS(q_stride == 0 || q_stride >= static_cast<int64_t>(M) * 3, "so3_icp_plane_f32: q_stride");
+    SO3_CHECK_ARGS(P != nullptr && Q != nullptr && normals != nullptr && R != nullptr && t != nullptr && (iterations == 0 || workspace != nullptr),
+                   "so3_icp_plane_f32: null pointer");
+    static_assert(so3::kPlanePivotEps == SO3_ICP_PLANE_PIVOT_EPS, "include/so3proj.h");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 block(kBlock);
+    int u;
+    const int32_t chunks = icp_chunks(B, N, u);
+    if (iterations == 0) {
+        hipLaunchKernelGGL(k_icp_initial_pose, dim3(static_cast<unsigned>((B * 12 + kBlock - 1) / kBlock)), block, 0, s, T_init, R, t, B);
+        if (nearest != nullptr || dist != nullptr)           // the search at the initial pose, so that the outputs are defined
+            launch_icp_step<false>(P, Q, q_stride, nullptr, T_init, -1.f, nullptr, dist, nearest, B, N, M, u, chunks, s);
+        return check_launch("so3_icp_plane_f32");
+    }
+    float *poses[2] = {static_cast<float *>(workspace), static_cast<float *>(workspace) + B * 12};
+    float *rec = static_cast<float *>(workspace) + B * 24;
+    const dim3 grid(search_grid(B * chunks)), fin_grid(wave_rows_grid(B, 16));
+    const float *cur = T_init;
+    for (int32_t k = 0; k < iterations; ++k) {
+        const bool last = k + 1 == iterations;
+        float *next = poses[k & 1];
+        with_flags([&](auto WW, auto TT) {
+            constexpr bool kWeighted = WW(), kTrimmed = TT();
+            with_value<4, 2, 1>(u, [&](auto U) {
+                name_kernel("k_icp_plane_step", kWeighted, kTrimmed, U);
+                hipLaunchKernelGGL((k_icp_plane_step<kWeighted, kTrimmed, U()>), grid, block, 0, s, P, Q, normals, q_stride, w, cur, max_distance, rec,
+                                   last ? dist : nullptr, last ? nearest : nullptr, B, N, M, chunks);
+            });
+        }, w != nullptr, max_distance >= 0.f);
+        hipLaunchKernelGGL(k_icp_plane_finish, fin_grid, block, 0, s, P, rec, cur, damping, next, last ? R : nullptr, last ? t : nullptr,
+                           rmse != nullptr ? rmse + k * B : nullptr, rmse_point != nullptr ? rmse_point + k * B : nullptr,
+                           inliers != nullptr ? inliers + k * B : nullptr, solved != nullptr ? solved + k * B : nullptr, B, N, chunks);
+        cur = next;
+    }
+    return check_launch("so3_icp_plane_f32");
 }
 
 size_t so3_chamfer_workspace_bytes(int64_t B, int32_t N, int32_t M) {

@@ -1379,6 +1379,80 @@ def icp_align(P: torch.Tensor, Q: torch.Tensor, R_init: torch.Tensor = None, t_i
     return r, t
 
 
+def icp_align_plane(P: torch.Tensor, Q: torch.Tensor, normals: torch.Tensor = None, R_init: torch.Tensor = None, t_init: torch.Tensor = None,
+                    iterations: int = 10, max_distance: float = None, weights: torch.Tensor = None, damping: float = 0.0,
+                    normal_neighbors: int = 16, return_info: bool = False):
+    """Point-to-plane ICP: as icp_align, but an iteration minimises sum w'_i (n_j(i) . (R p_i + t - q_j(i)))^2 over the target's surface
+    normals instead of the point distances, so the source may slide along the surface and the pose converges in a fraction of the
+    iterations on smooth scans.  P: (B,N,3); Q: (B,M,3), or (M,3) for one target shared by the batch.  Returns R (B,3,3), t (B,3).
+
+    normals: (B,M,3), or (M,3) with a shared Q; None computes estimate_normals(Q, normal_neighbors) first.  Their sign does not
+    matter (negating any of them changes no bit of the result), and a zero normal (a row past a length, a flat patch) takes its
+    point out of the sums.  One iteration from (R_k, t_k): icp_align's search; w'_i = w_i [d_i <= max_distance] [n_i != 0]; the 6x6
+    Gauss-Newton system of the linearised residuals about the posed first source point, its diagonal scaled by (1 + damping)
+    (Levenberg-Marquardt; damping >= 0), solved by a Cholesky factorisation in registers; the pose is updated by the Cayley
+    retraction of the rotation step and projected back onto SO(3), so long runs do not drift.  A cloud whose system has no unique
+    solution (a plane, a sphere about its centre, fewer than six inliers: a pivot below 2^-7 of its diagonal entry) keeps its pose
+    and reports solved = 0; damping > 0 makes such a system solvable.  Exactly `iterations` iterations, two launches each, no host
+    synchronisation, no atomics: graph-capturable, the same bits every time.
+
+    return_info=True also returns a dict: "rmse" (iterations,B) the point-to-plane rmse sqrt(sum w' r^2 / sum w'), "rmse_point"
+    (iterations,B) = icp_align's rmse, "inliers" (iterations,B) int64 and "solved" (iterations,B) bool, all at the pose the iteration
+    STARTED from, and "nearest" (B,N) int64, "dist" (B,N) float32 of the last iteration's search.
+
+    Not differentiable.  For gradients, differentiate the last step on the correspondences with rigid_align, as icp_align's
+    docstring shows (the point-to-point step on the converged pairs)."""
+    dev, p, q, stride, b, n, m = _cloud_pair("icp_align_plane", P, Q)
+    extra = [x for x in (normals, R_init, t_init, weights) if x is not None]
+    if extra:
+        _require_device(p, *extra)
+    iterations = int(iterations)
+    if iterations < 0:
+        raise RuntimeError("icp_align_plane: iterations must be >= 0, got %d" % iterations)
+    damping = float(damping)
+    if not damping >= 0.0:
+        raise RuntimeError("icp_align_plane: damping must be >= 0, got %r" % damping)
+    if normals is not None and tuple(normals.shape) != tuple(Q.shape):
+        raise RuntimeError("icp_align_plane: expected normals of the target's shape %s, got %s" % (tuple(Q.shape), tuple(normals.shape)))
+    if (R_init is not None and tuple(R_init.shape) != (b, 3, 3)) or (t_init is not None and tuple(t_init.shape) != (b, 3)) or \
+            (weights is not None and tuple(weights.shape) != (b, n)):
+        raise RuntimeError("icp_align_plane: expected R_init (B, 3, 3), t_init (B, 3) and weights (B, N) for B = %d, N = %d, got %s"
+                           % (b, n, [None if x is None else tuple(x.shape) for x in (R_init, t_init, weights)]))
+    if _wants_grad(P, Q, normals, R_init, t_init, weights):
+        _warn_once("icp_align_plane", "icp_align_plane is not differentiable: R and t carry no gradient although an argument requires grad.  "
+                                      "Call rigid_align on the returned correspondences (see icp_align's docstring) for a differentiable last step.")
+    if normals is None:
+        nrm = estimate_normals(q if q.dim() == 3 else q[None], int(normal_neighbors))
+        nrm = (nrm if q.dim() == 3 else nrm[0]).contiguous()
+    else:
+        nrm = normals.detach().contiguous().float()
+    t0 = None
+    if R_init is not None or t_init is not None:
+        r0 = R_init.detach().float() if R_init is not None else torch.eye(3, dtype=torch.float32, device=dev).expand(b, 3, 3)
+        tt = t_init.detach().float() if t_init is not None else torch.zeros((b, 3), dtype=torch.float32, device=dev)
+        t0 = torch.cat([r0, tt[:, :, None]], 2).contiguous()                       # (B, 3, 4): the rows (R | t)
+    w = None if weights is None else weights.detach().contiguous().float()
+    r = torch.empty((b, 3, 3), dtype=torch.float32, device=dev)
+    t = torch.empty((b, 3), dtype=torch.float32, device=dev)
+    rmse = rmse_point = inl = solved = nearest = dist = None
+    if return_info:
+        rmse = torch.empty((iterations, b), dtype=torch.float32, device=dev)
+        rmse_point = torch.empty((iterations, b), dtype=torch.float32, device=dev)
+        inl = torch.empty((iterations, b), dtype=torch.int32, device=dev)
+        solved = torch.empty((iterations, b), dtype=torch.int32, device=dev)
+        nearest = torch.empty((b, n), dtype=torch.int32, device=dev)
+        dist = torch.empty((b, n), dtype=torch.float32, device=dev)
+    lib = _libh()
+    work = torch.empty((max(int(lib.so3_icp_plane_workspace_bytes(b, n)) // 4, 1),), dtype=torch.float32, device=dev)
+    with _on_device(dev):
+        _check(lib.so3_icp_plane_f32(_ptr(p), _ptr(q), _ptr(nrm), stride, _ptr(w), _ptr(t0), -1.0 if max_distance is None else float(max_distance),
+                                     damping, iterations, _ptr(r), _ptr(t), _ptr(rmse), _ptr(rmse_point), _ptr(inl), _ptr(solved), _ptr(nearest),
+                                     _ptr(dist), _ptr(work), b, n, m, _stream(dev)), "so3_icp_plane_f32")
+    if return_info:
+        return r, t, {"rmse": rmse, "rmse_point": rmse_point, "inliers": inl.long(), "solved": solved.bool(), "nearest": nearest.long(), "dist": dist}
+    return r, t
+
+
 # --------------------------------------------------------------------------------------------
 # the Chamfer distance: a loss between two clouds, differentiable in both
 # --------------------------------------------------------------------------------------------

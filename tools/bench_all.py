@@ -208,6 +208,14 @@ def main():
         timeit("so3_icp_f32 (256 x 1024 x 1024, %d iteration%s)" % (its, "" if its == 1 else "s"),
                lambda i: lib.so3_icp_f32(p(xi), p(yi), 3 * ni, None, None, ctypes.c_float(-1.0), its, p(ri), p(ti), None, None, None, None, p(wsi), bi, ni, ni, st),
                its * bi * ni * 24, iters=10, warm=2)
+    # point-to-plane ICP at the same shape (profiles/icp_plane_bench.txt): the same search, two gathers per point and 31 sums
+    nri = torch.nn.functional.normalize(torch.randn(bi, ni, 3, device=dev), dim=-1)
+    wpi = torch.empty(lib.so3_icp_plane_workspace_bytes(bi, ni) // 4, device=dev)
+    for its in (1, 10):
+        timeit("so3_icp_plane_f32 (256 x 1024 x 1024, %d iteration%s)" % (its, "" if its == 1 else "s"),
+               lambda i: lib.so3_icp_plane_f32(p(xi), p(yi), p(nri), 3 * ni, None, None, ctypes.c_float(-1.0), ctypes.c_float(0.0), its, p(ri), p(ti),
+                                               None, None, None, None, None, None, p(wpi), bi, ni, ni, st),
+               its * bi * ni * 36, iters=10, warm=2)
     # the Chamfer distance at the same shape: both searches in one launch (2 x N * M pairs per cloud), then both gradients in one gather
     dyi, nyi = torch.empty(bi, ni, device=dev), torch.empty(bi, ni, dtype=torch.int32, device=dev)
     rwi, sci = torch.empty(bi, 2, device=dev), torch.full((bi,), 1.0 / ni, device=dev)

@@ -1266,7 +1266,20 @@ def g29_local_frames():
     assert os.path.getsize(os.path.join(OUT, "g29_local_frames.npz")) <= 512 * 1024
 
 
+def g30_icp_plane():
+    """icp_align_plane: no reference code exists, so the fixture holds float32 clouds, normals (stored, or the analytic ellipsoid
+    normals tests/icp_plane_ref.py derives from the target), initial poses and weights, and the answers of the float64 restatement
+    -- tests/icp_plane_ref.py: generate, which asserts the trimming margins, the share of non-unique steps, the degenerate systems,
+    exact convergence and the comparison case's property."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import icp_plane_ref as ref
+    save("g30_icp_plane.npz", **ref.generate())
+    assert os.path.getsize(os.path.join(OUT, "g30_icp_plane.npz")) <= 512 * 1024
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "g30":
+        return g30_icp_plane()
     if len(sys.argv) > 1 and sys.argv[1] == "g29":
         return g29_local_frames()
     if len(sys.argv) > 1 and sys.argv[1] == "g28":
@@ -1327,6 +1340,7 @@ def main():
     g27_chamfer()
     g28_knn()
     g29_local_frames()
+    g30_icp_plane()
     g22_pointnet()
     g23_head_edges()
     # ---- G1: config #1, 256 Gaussian rows ------------------------------------------------------
