@@ -251,6 +251,14 @@ def test_numerically_rank_deficient_input_still_gives_rotations(rr, dtype):
         assert ((best - got) / s[:, 0].clamp_min(1e-30)).max().item() < (2e-6 if dtype == torch.float32 else 1e-12), name
         r.backward(torch.randn(n, 3, 3, device=DEV, generator=gen).to(dtype))
         assert torch.isfinite(x.grad).all(), name               # floored denominators: large but finite
+        # and, where nothing defines the gradient's value, its structure: dM = R [y]x, so R^T dM is skew -- every row, within 4 x what
+        # the host model reaches on the family (tests/project_bwd_ref.py: K; tests/test_project_bwd_host.py: RANK_DEFICIENT_K)
+        from test_project_bwd_host import DEVICE_FACTOR, RANK_DEFICIENT_K
+        w = r.detach().transpose(1, 2) @ x.grad.view(n, 3, 3)
+        skew = (w + w.transpose(1, 2)).abs().flatten(1).amax(1)
+        size = x.grad.abs().flatten(1).amax(1)
+        k = torch.where(size > 0, skew / ((2.0**-24 if dtype == torch.float32 else 2.0**-53) * size), torch.zeros_like(size)).max().item()
+        assert k <= DEVICE_FACTOR * RANK_DEFICIENT_K[name][0 if dtype == torch.float32 else 1], (name, k)
 
 
 def test_a_row_does_not_depend_on_its_neighbours(rr):
@@ -886,6 +894,21 @@ def test_g4_config4_fused_head_loss_backward(rr):
     assert (xu.grad - xf.grad / 2.0).abs().max().item() < 1e-6 * max(1.0, float(np.abs(ref).max()))
 
 
+def _every_row_j(x, g, got):
+    """The largest J over EVERY row with a gap (tests/project_bwd_ref.py: max |dM - dM64| gamma^2 / (u s1 |G|_F) against the float64
+    closed form on the same float32 numbers; rows with gamma / s1 <= 1e-5 have none), beside the quantiles: no row may be arbitrarily
+    wrong.  The bound is 4 x the host model's figure on Gaussian rows (tests/test_project_bwd_host.py)."""
+    import project_bwd_ref as ref
+    fig = ref.j_of(got, ref.answers(x, g))
+    assert np.isnan(fig).mean() < 1e-3                                         # Gaussian rows: all but a handful have a gap
+    return np.nanmax(fig)
+
+
+def _gaussian_j():
+    from test_project_bwd_host import J32
+    return J32["gaussian"]
+
+
 def test_backward_matches_oracle_on_random_batch(rr, c_oracle):
     rng = np.random.default_rng(3)
     x = rng.standard_normal((5000, 9)).astype(np.float32)
@@ -895,6 +918,7 @@ def test_backward_matches_oracle_on_random_batch(rr, c_oracle):
     ref = c_oracle.project_bwd(x, gup).reshape(5000, 9)
     rel = np.abs(xd.grad.cpu().numpy() - ref).max(1) / (1e-3 + np.abs(ref).max(1))
     assert np.median(rel) < 1e-6 and np.quantile(rel, 0.99) < 2e-4
+    assert _every_row_j(x, gup, xd.grad.cpu().numpy()) <= 4 * _gaussian_j()
     # the gradient is orthogonal to M's radial direction: proj(M) is scale invariant
     radial = (xd.grad * xd.detach()).sum(1)
     assert radial.abs().max().item() < 1e-3 * xd.grad.abs().max().item()
@@ -2002,6 +2026,7 @@ def test_engine_dtype_paths_at_size(rr, c_oracle):
     rr.symmetric_orthogonalization(xf).backward(g)
     rel = np.abs(xf.grad.cpu().numpy() - gref).max(1) / (1e-3 + np.abs(gref).max(1))
     assert np.median(rel) < 1e-6 and np.quantile(rel, 0.99) < 2e-4
+    assert _every_row_j(xb.float().cpu().numpy(), g.cpu().numpy(), xf.grad.cpu().numpy()) <= 4 * _gaussian_j()
     rt = rr.symmetric_orthogonalization(torch.randn(n, 9, device=DEV, generator=gen))
     xl = xb.float().requires_grad_(True)
     loss, rf = rr.frobenius_head(xl, rt)
