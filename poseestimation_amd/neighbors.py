@@ -1,0 +1,440 @@
+"""Clouds without known correspondences: the nearest-neighbour search and what stands on it -- both ICPs, the Chamfer distance,
+K nearest neighbours with their gather and grouping, and the per-point local frames and normals.  One family of the Python mirror;
+rotation_representation re-exports its public names."""
+from __future__ import annotations
+
+import torch
+
+from . import _lib
+from ._runtime import _cloud_lengths, _grad_to, _launch, _libh, _no_double_backward, _ptr, _require_device, _wants_grad, _warn_once
+from .pointnet import group_points
+
+
+# --------------------------------------------------------------------------------------------
+# nearest neighbours between two clouds, and ICP on top of them
+# --------------------------------------------------------------------------------------------
+def _cloud_pair(name, X, Y, error=RuntimeError, shared_target=True):
+    """float32 copies of a source (B,N,3) and a target (B,M,3) -- or, where `shared_target` allows it, one (M,3) for the batch --, and
+    the target's stride in floats (0: shared).  The one shape check of the pair operations: `name` raises `error`."""
+    dev = _require_device(X, Y)
+    ok = X.dim() == 3 and X.shape[-1] == 3 and Y.dim() in ((2, 3) if shared_target else (3,)) and Y.shape[-1] == 3 \
+        and (Y.dim() == 2 or Y.shape[0] == X.shape[0])
+    if not ok or not 1 <= X.shape[1] <= _lib.ADD_S_MAX_N or not 1 <= Y.shape[-2] <= _lib.ADD_S_MAX_N:
+        raise error("%s: expected a source (B, N, 3) and a target (B, M, 3)%s with 1 <= N, M <= %d, got %s and %s"
+                    % (name, " or (M, 3)" if shared_target else "", _lib.ADD_S_MAX_N, tuple(X.shape), tuple(Y.shape)))
+    x = X.detach().contiguous().float()
+    y = Y.detach().contiguous().float()
+    m = y.shape[-2]
+    return dev, x, y, (0 if y.dim() == 2 else 3 * m), x.shape[0], x.shape[1], m
+
+
+def nearest_neighbors(X: torch.Tensor, Y: torch.Tensor):
+    """For every point of X its closest point of Y: (dist, idx) with dist (B,N) float32 = min_j |x_i - y_j|_2 and idx (B,N) int64 the
+    argmin (the first of equal candidates).  X: (B,N,3); Y: (B,M,3), or (M,3) for one target shared by the batch.  N and M are
+    independent.  One launch (so3_nearest_f32), N * M arithmetic per cloud and nothing of that size in memory; distances come from
+    coordinate differences, so a point that is in both clouds gets exactly 0.  An evaluation call: not differentiable."""
+    dev, x, y, stride, b, n, m = _cloud_pair("nearest_neighbors", X, Y)
+    if _wants_grad(X, Y):
+        _warn_once("nearest_neighbors", "nearest_neighbors is an evaluation call: dist carries no gradient although an argument requires grad.  "
+                                        "(X - Y.gather(...)).norm() on the returned indices is the differentiable spelling.")
+    dist = torch.empty((b, n), dtype=torch.float32, device=dev)
+    idx = torch.empty((b, n), dtype=torch.int32, device=dev)
+    _launch(dev, "so3_nearest_f32", _ptr(x), _ptr(y), stride, _ptr(dist), _ptr(idx), b, n, m)
+    return dist, idx.long()
+
+
+def _icp_args(name, dev, b, n, R_init, t_init, weights, iterations, return_info):
+    """What both ICPs do with their common arguments once the clouds are checked: the shape check of the extras (`name` raises), then
+    (t0, w, r, t, rmse, inl, nearest, dist) -- the initial pose as (B, 3, 4) rows (R | t) or None, the float32 weights or None, the
+    outputs R and t, and the info buffers, None unless return_info."""
+    if (R_init is not None and tuple(R_init.shape) != (b, 3, 3)) or (t_init is not None and tuple(t_init.shape) != (b, 3)) or \
+            (weights is not None and tuple(weights.shape) != (b, n)):
+        raise RuntimeError("%s: expected R_init (B, 3, 3), t_init (B, 3) and weights (B, N) for B = %d, N = %d, got %s"
+                           % (name, b, n, [None if x is None else tuple(x.shape) for x in (R_init, t_init, weights)]))
+    t0 = None
+    if R_init is not None or t_init is not None:
+        r0 = R_init.detach().float() if R_init is not None else torch.eye(3, dtype=torch.float32, device=dev).expand(b, 3, 3)
+        tt = t_init.detach().float() if t_init is not None else torch.zeros((b, 3), dtype=torch.float32, device=dev)
+        t0 = torch.cat([r0, tt[:, :, None]], 2).contiguous()                       # (B, 3, 4): the rows (R | t)
+    w = None if weights is None else weights.detach().contiguous().float()
+    r = torch.empty((b, 3, 3), dtype=torch.float32, device=dev)
+    t = torch.empty((b, 3), dtype=torch.float32, device=dev)
+    rmse = inl = nearest = dist = None
+    if return_info:
+        rmse = torch.empty((iterations, b), dtype=torch.float32, device=dev)
+        inl = torch.empty((iterations, b), dtype=torch.int32, device=dev)
+        nearest = torch.empty((b, n), dtype=torch.int32, device=dev)
+        dist = torch.empty((b, n), dtype=torch.float32, device=dev)
+    return t0, w, r, t, rmse, inl, nearest, dist
+
+
+def icp_align(P: torch.Tensor, Q: torch.Tensor, R_init: torch.Tensor = None, t_init: torch.Tensor = None, iterations: int = 10,
+              max_distance: float = None, weights: torch.Tensor = None, return_info: bool = False):
+    """Point-to-point ICP (iterative closest point): the pose (R, t) that registers the source clouds P onto the target clouds Q when
+    the correspondences are NOT known.  P: (B,N,3); Q: (B,M,3), or (M,3) for one target shared by the batch; N and M are independent.
+    Returns R (B,3,3) and t (B,3) in float32.
+
+    One iteration, from the pose (R_k, t_k): x_i = R_k p_i + t_k; j(i) = the point of Q closest to x_i and d_i its distance;
+    w'_i = w_i * [d_i <= max_distance] (all of w_i when max_distance is None; w_i = 1 when weights is None); (R_k+1, t_k+1) =
+    rigid_align's answer for the pairs (p_i, q_j(i)) with weights w'.  The pose is solved from the unposed p_i every time, so it is
+    an absolute pose and no composition error builds up.  A cloud without inlier weight keeps its pose.
+
+    R_init (B,3,3) and t_init (B,3) give the initial pose (default: the identity).  Exactly `iterations` iterations run, without an
+    early exit -- a converged cloud repeats its fixed point --, so nothing synchronises with the host and the call can be captured
+    in a graph; the same inputs give the same bits.  iterations=0 returns the initial pose.  weights: None or (B,N), w_i >= 0.
+
+    return_info=True also returns a dict: "rmse" (iterations,B) float32 = sqrt(sum w' d^2 / sum w') and "inliers" (iterations,B)
+    int64 = #{w'_i > 0}, both measured at the pose the iteration STARTED from (0 and 0 where there was no inlier), and "nearest"
+    (B,N) int64, "dist" (B,N) float32 of the last iteration's search.
+
+    Not differentiable (the search is piecewise constant).  For gradients, differentiate the last step on the correspondences:
+        R, t, info = icp_align(P, Q, ..., return_info=True)
+        R, t = rigid_align(P, Q.gather(1, info["nearest"][..., None].expand(-1, -1, 3)), w)     # w: weights * (info["dist"] <= max_distance)"""
+    dev, p, q, stride, b, n, m = _cloud_pair("icp_align", P, Q)
+    extra = [x for x in (R_init, t_init, weights) if x is not None]
+    if extra:
+        _require_device(p, *extra)
+    iterations = int(iterations)
+    if iterations < 0:
+        raise RuntimeError("icp_align: iterations must be >= 0, got %d" % iterations)
+    t0, w, r, t, rmse, inl, nearest, dist = _icp_args("icp_align", dev, b, n, R_init, t_init, weights, iterations, return_info)
+    if _wants_grad(P, Q, R_init, t_init, weights):
+        _warn_once("icp_align", "icp_align is not differentiable: R and t carry no gradient although an argument requires grad.  Call "
+                                "rigid_align on the returned correspondences (see the docstring) for a differentiable last step.")
+    work = torch.empty((max(int(_libh().so3_icp_workspace_bytes(b, n)) // 4, 1),), dtype=torch.float32, device=dev)
+    _launch(dev, "so3_icp_f32", _ptr(p), _ptr(q), stride, _ptr(w), _ptr(t0), -1.0 if max_distance is None else float(max_distance), iterations,
+            _ptr(r), _ptr(t), _ptr(rmse), _ptr(inl), _ptr(nearest), _ptr(dist), _ptr(work), b, n, m)
+    if return_info:
+        return r, t, {"rmse": rmse, "inliers": inl.long(), "nearest": nearest.long(), "dist": dist}
+    return r, t
+
+
+def icp_align_plane(P: torch.Tensor, Q: torch.Tensor, normals: torch.Tensor = None, R_init: torch.Tensor = None, t_init: torch.Tensor = None,
+                    iterations: int = 10, max_distance: float = None, weights: torch.Tensor = None, damping: float = 0.0,
+                    normal_neighbors: int = 16, return_info: bool = False):
+    """Point-to-plane ICP: as icp_align, but an iteration minimises sum w'_i (n_j(i) . (R p_i + t - q_j(i)))^2 over the target's surface
+    normals instead of the point distances, so the source may slide along the surface and the pose converges in a fraction of the
+    iterations on smooth scans.  P: (B,N,3); Q: (B,M,3), or (M,3) for one target shared by the batch.  Returns R (B,3,3), t (B,3).
+
+    normals: (B,M,3), or (M,3) with a shared Q; None computes estimate_normals(Q, normal_neighbors) first.  Their sign does not
+    matter (negating any of them changes no bit of the result), and a zero normal (a row past a length, a flat patch) takes its
+    point out of the sums.  One iteration from (R_k, t_k): icp_align's search; w'_i = w_i [d_i <= max_distance] [n_i != 0]; the 6x6
+    Gauss-Newton system of the linearised residuals about the posed first source point, its diagonal scaled by (1 + damping)
+    (Levenberg-Marquardt; damping >= 0), solved by a Cholesky factorisation in registers; the pose is updated by the Cayley
+    retraction of the rotation step and projected back onto SO(3), so long runs do not drift.  A cloud whose system has no unique
+    solution (a plane, a sphere about its centre, fewer than six inliers: a pivot below 2^-7 of its diagonal entry) keeps its pose
+    and reports solved = 0; damping > 0 makes such a system solvable.  Exactly `iterations` iterations, two launches each, no host
+    synchronisation, no atomics: graph-capturable, the same bits every time.
+
+    return_info=True also returns a dict: "rmse" (iterations,B) the point-to-plane rmse sqrt(sum w' r^2 / sum w'), "rmse_point"
+    (iterations,B) = icp_align's rmse, "inliers" (iterations,B) int64 and "solved" (iterations,B) bool, all at the pose the iteration
+    STARTED from, and "nearest" (B,N) int64, "dist" (B,N) float32 of the last iteration's search.
+
+    Not differentiable.  For gradients, differentiate the last step on the correspondences with rigid_align, as icp_align's
+    docstring shows (the point-to-point step on the converged pairs)."""
+    dev, p, q, stride, b, n, m = _cloud_pair("icp_align_plane", P, Q)
+    extra = [x for x in (normals, R_init, t_init, weights) if x is not None]
+    if extra:
+        _require_device(p, *extra)
+    iterations = int(iterations)
+    if iterations < 0:
+        raise RuntimeError("icp_align_plane: iterations must be >= 0, got %d" % iterations)
+    damping = float(damping)
+    if not damping >= 0.0:
+        raise RuntimeError("icp_align_plane: damping must be >= 0, got %r" % damping)
+    if normals is not None and tuple(normals.shape) != tuple(Q.shape):
+        raise RuntimeError("icp_align_plane: expected normals of the target's shape %s, got %s" % (tuple(Q.shape), tuple(normals.shape)))
+    t0, w, r, t, rmse, inl, nearest, dist = _icp_args("icp_align_plane", dev, b, n, R_init, t_init, weights, iterations, return_info)
+    if _wants_grad(P, Q, normals, R_init, t_init, weights):
+        _warn_once("icp_align_plane", "icp_align_plane is not differentiable: R and t carry no gradient although an argument requires grad.  "
+                                      "Call rigid_align on the returned correspondences (see icp_align's docstring) for a differentiable last step.")
+    if normals is None:
+        nrm = estimate_normals(q if q.dim() == 3 else q[None], int(normal_neighbors))
+        nrm = (nrm if q.dim() == 3 else nrm[0]).contiguous()
+    else:
+        nrm = normals.detach().contiguous().float()
+    rmse_point = solved = None
+    if return_info:
+        rmse_point = torch.empty((iterations, b), dtype=torch.float32, device=dev)
+        solved = torch.empty((iterations, b), dtype=torch.int32, device=dev)
+    work = torch.empty((max(int(_libh().so3_icp_plane_workspace_bytes(b, n)) // 4, 1),), dtype=torch.float32, device=dev)
+    _launch(dev, "so3_icp_plane_f32", _ptr(p), _ptr(q), _ptr(nrm), stride, _ptr(w), _ptr(t0), -1.0 if max_distance is None else float(max_distance),
+            damping, iterations, _ptr(r), _ptr(t), _ptr(rmse), _ptr(rmse_point), _ptr(inl), _ptr(solved), _ptr(nearest), _ptr(dist), _ptr(work),
+            b, n, m)
+    if return_info:
+        return r, t, {"rmse": rmse, "rmse_point": rmse_point, "inliers": inl.long(), "solved": solved.bool(), "nearest": nearest.long(), "dist": dist}
+    return r, t
+
+
+# --------------------------------------------------------------------------------------------
+# the Chamfer distance: a loss between two clouds, differentiable in both
+# --------------------------------------------------------------------------------------------
+
+
+class _Chamfer(torch.autograd.Function):
+    """chamfer_distance: so3_chamfer_fwd_f32 searches both directions and leaves the (B,2) means; the reductions over them are a few
+    (B,)-sized torch statements.  The backward folds the upstream gradient and those reductions into per-cloud scales on the device
+    and makes one so3_chamfer_bwd_f32 call through the stored indices."""
+
+    @staticmethod
+    def forward(ctx, X, Y, x_lengths, y_lengths, squared, point_reduction, batch_reduction, single, return_nearest):
+        dev, x, y, _, b, n, m = _cloud_pair("chamfer_distance", X, Y, shared_target=False)
+        xl = _cloud_lengths("chamfer_distance", RuntimeError, "x_lengths", x_lengths, b, n, dev)
+        yl = _cloud_lengths("chamfer_distance", RuntimeError, "y_lengths", y_lengths, b, m, dev)
+        nx, ny = (None if l is None else l.to(torch.float32) for l in (xl, yl))       # the point counts; None: the full length
+        want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        want_grad = want_x or want_y
+        flags = (0 if squared else _lib.CHAMFER_UNSQUARED) | (_lib.CHAMFER_SINGLE if single else 0)
+
+        def buf(rows, dtype, wanted):
+            return torch.empty((b, rows), dtype=dtype, device=dev) if wanted else None
+
+        near_x = buf(n, torch.int32, want_grad or return_nearest)
+        near_y = buf(m, torch.int32, (want_grad or return_nearest) and not single)
+        dist_x = buf(n, torch.float32, return_nearest)
+        dist_y = buf(m, torch.float32, return_nearest and not single)
+        rows = torch.empty((b, 2), dtype=torch.float32, device=dev)
+        work = torch.empty((max(int(_libh().so3_chamfer_workspace_bytes(b, n, m)) // 4, 1),), dtype=torch.float32, device=dev)
+        _launch(dev, "so3_chamfer_fwd_f32", _ptr(x), _ptr(y), _ptr(xl), _ptr(yl), _ptr(dist_x), _ptr(near_x), _ptr(dist_y), _ptr(near_y), _ptr(rows),
+                _ptr(work), flags, b, n, m)
+        cham_x, cham_y = rows[:, 0], rows[:, 1]
+        if point_reduction == "sum":                       # rows holds the means
+            cham_x = cham_x * (float(n) if nx is None else nx)
+            cham_y = cham_y * (float(m) if ny is None else ny)
+        per_cloud = cham_x if single else cham_x + cham_y
+        out = per_cloud.mean() if batch_reduction == "mean" else (per_cloud.sum() if batch_reduction == "sum" else per_cloud.contiguous())
+        if want_grad:
+            ctx.save_for_backward(x, y, xl, yl, near_x, near_y, nx, ny)
+        ctx.meta = (want_x, want_y, flags, point_reduction, batch_reduction, X.dtype, Y.dtype, b, n, m)
+        if not return_nearest:
+            return out
+        extras = (near_x.long(), dist_x) if single else (near_x.long(), dist_x, near_y.long(), dist_y)
+        ctx.mark_non_differentiable(*extras)
+        return (out,) + extras
+
+    @staticmethod
+    def backward(ctx, grad_out, *unused):
+        _no_double_backward(grad_out)
+        want_x, want_y, flags, point_reduction, batch_reduction, x_dtype, y_dtype, b, n, m = ctx.meta
+        if not (want_x or want_y):
+            return (None,) * 9
+        x, y, xl, yl, near_x, near_y, nx, ny = ctx.saved_tensors
+        dev = x.device
+        g = grad_out.detach().float()
+        if batch_reduction is None:
+            g = g.reshape(b)
+        else:                                              # one upstream scalar for every cloud, kept on the device
+            g = (g.reshape(1) * (1.0 / max(b, 1)) if batch_reduction == "mean" else g.reshape(1)).expand(b)
+        if point_reduction == "mean":                      # an empty cloud takes no gradient: the kernel writes its rows as 0
+            scale_x = g * (1.0 / n) if nx is None else g / nx.clamp(min=1.0)
+            scale_y = g * (1.0 / m) if ny is None else g / ny.clamp(min=1.0)
+        else:
+            scale_x = scale_y = g
+        single = bool(flags & _lib.CHAMFER_SINGLE)
+        scale_x = scale_x.contiguous()
+        scale_y = None if single else scale_y.contiguous()
+        dx = torch.empty((b, n, 3), dtype=torch.float32, device=dev) if want_x else None
+        dy = torch.empty((b, m, 3), dtype=torch.float32, device=dev) if want_y else None
+        _launch(dev, "so3_chamfer_bwd_f32", _ptr(x), _ptr(y), _ptr(xl), _ptr(yl), _ptr(near_x), _ptr(near_y), _ptr(scale_x), _ptr(scale_y),
+                _ptr(dx), _ptr(dy), flags, b, n, m)
+        return (_grad_to(dx, x_dtype), _grad_to(dy, y_dtype)) + (None,) * 7
+
+
+def chamfer_distance(X: torch.Tensor, Y: torch.Tensor, x_lengths: torch.Tensor = None, y_lengths: torch.Tensor = None, squared: bool = True,
+                     point_reduction: str = "mean", batch_reduction: str = "mean", single_directional: bool = False,
+                     return_nearest: bool = False):
+    """The Chamfer distance between the clouds X (B,N,3) and Y (B,M,3), differentiable in BOTH clouds:
+
+        loss_b = mean_{i < n_b} min_{j < m_b} |x_i - y_j|^2  +  mean_{j < m_b} min_{i < n_b} |y_j - x_i|^2.
+
+    x_lengths, y_lengths: optional (B,) int32 / int64 tensors; cloud b uses its first n_b = clip(x_lengths[b], 0, N) and m_b points, a
+    point past the length is neither a source nor a candidate.  A cloud with n_b == 0 or m_b == 0 scores 0 and takes no gradient.
+    squared=False sums the distances instead of their squares (one square root after the minimum; its gradient is the unit direction,
+    0 where the two points coincide).  point_reduction: "mean" or "sum" over a cloud's points; batch_reduction: "mean", "sum" or None
+    for the (B,) rows; single_directional=True keeps the first term alone.
+
+    The searches are nearest_neighbors' (coordinate differences, the first of equal candidates: a point that is in both clouds gets
+    exactly 0) and run in ONE launch; the backward is one launch that gathers both gradients through the stored indices in a fixed
+    order.  No atomics and nothing synchronises with the host: the same inputs give the same bits, and the call captures into a graph.
+
+    return_nearest=True returns (loss, info) with info["nearest_x"] (B,N), info["nearest_y"] (B,M) int64 (-1 in slots past the length)
+    and info["dist_x"], info["dist_y"] float32, the per-point terms (0 in those slots); single_directional leaves the y entries out."""
+    if point_reduction not in ("mean", "sum") or batch_reduction not in ("mean", "sum", None):
+        raise ValueError("chamfer_distance: point_reduction is 'mean' or 'sum' and batch_reduction 'mean', 'sum' or None, got %r and %r"
+                         % (point_reduction, batch_reduction))
+    res = _Chamfer.apply(X, Y, x_lengths, y_lengths, bool(squared), point_reduction, batch_reduction, bool(single_directional), bool(return_nearest))
+    if not return_nearest:
+        return res
+    names = ("nearest_x", "dist_x") if single_directional else ("nearest_x", "dist_x", "nearest_y", "dist_y")
+    return res[0], dict(zip(names, res[1:]))
+
+
+# --------------------------------------------------------------------------------------------
+# K nearest neighbours between two clouds, differentiable in both
+# --------------------------------------------------------------------------------------------
+class _KnnPoints(torch.autograd.Function):
+    """knn_points: one so3_knn_f32 launch; the backward is one so3_knn_bwd_f32 launch that gathers both gradients through the stored
+    int32 indices in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, X, Y, k, x_lengths, y_lengths):
+        dev, x, y, stride, b, n, m = _cloud_pair("knn_points", X, Y, error=ValueError)
+        if stride == 0 and ctx.needs_input_grad[1]:
+            raise ValueError("knn_points: a shared (M, 3) target takes no gradient; pass Y.expand(B, M, 3) to differentiate in it")
+        xl = _cloud_lengths("knn_points", ValueError, "x_lengths", x_lengths, b, n, dev)
+        yl = _cloud_lengths("knn_points", ValueError, "y_lengths", y_lengths, b, m, dev)
+        dist2 = torch.empty((b, n, k), dtype=torch.float32, device=dev)
+        idx = torch.empty((b, n, k), dtype=torch.int32, device=dev)
+        _launch(dev, "so3_knn_f32", _ptr(x), _ptr(y), stride, _ptr(xl), _ptr(yl), _ptr(dist2), _ptr(idx), k, b, n, m)
+        want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if want_x or want_y:
+            ctx.save_for_backward(x, y, xl, yl, idx)
+        ctx.meta = (want_x, want_y, X.dtype, Y.dtype, k, b, n, m)
+        idx64 = idx.long()
+        ctx.mark_non_differentiable(idx64)
+        return dist2.to(X.dtype), idx64
+
+    @staticmethod
+    def backward(ctx, grad_dist2, unused):
+        _no_double_backward(grad_dist2)
+        want_x, want_y, x_dtype, y_dtype, k, b, n, m = ctx.meta
+        if not (want_x or want_y):
+            return None, None, None, None, None
+        x, y, xl, yl, idx = ctx.saved_tensors
+        dev = x.device
+        if y.dim() == 2:                                   # a shared target: the backward takes per-cloud targets
+            y = y.expand(b, m, 3).contiguous()
+        g = grad_dist2.detach().float().contiguous()
+        dx = torch.empty((b, n, 3), dtype=torch.float32, device=dev) if want_x else None
+        dy = torch.empty((b, m, 3), dtype=torch.float32, device=dev) if want_y else None
+        _launch(dev, "so3_knn_bwd_f32", _ptr(x), _ptr(y), _ptr(xl), _ptr(yl), _ptr(idx), _ptr(g), _ptr(dx), _ptr(dy), k, b, n, m)
+        return _grad_to(dx, x_dtype), _grad_to(dy, y_dtype), None, None, None
+
+
+def knn_points(X: torch.Tensor, Y: torch.Tensor, K: int, x_lengths: torch.Tensor = None, y_lengths: torch.Tensor = None):
+    """For every point of X (B,N,3) its K nearest points of Y (B,M,3): (dist2, idx) with dist2 (B,N,K) the squared distances in
+    ascending order and idx (B,N,K) int64, among equal distances the lower index first.  1 <= K <= KNN_MAX_K (64); K > M is legal.
+
+    x_lengths, y_lengths: optional (B,) int32 / int64 tensors; cloud b uses its first n_b = clip(x_lengths[b], 0, N) and m_b points.
+    dist2 = 0 and idx = -1 fill the slots k >= min(K, m_b), the rows i >= n_b and every slot of a cloud with m_b == 0 -- what
+    knn_gather and group_points read as an empty slot.
+
+    The arithmetic is a definition (include/so3proj.h): d = ((dx * dx) + (dy * dy)) + (dz * dz) from coordinate differences in
+    float32 without fused multiply-add, three_nn's distance: K = 3 gives three_nn's bits, and a point that is in both clouds gets
+    exactly 0.  One launch (so3_knn_f32): a wave keeps a query's sorted list across its lanes, nothing of size N * M is in memory.
+
+    dist2 is differentiable in BOTH clouds (dist2 and the gradients come back in the clouds' dtypes; the arithmetic is float32):
+    one backward launch gathers both gradients through the stored indices in a fixed order, without atomics -- the same inputs give
+    the same bits.  Nothing synchronises with the host, so the call captures into a graph.  idx carries no gradient; double
+    backward is refused.  Y may be ONE (M,3) target shared by the batch, forward only: a shared target that requires grad raises
+    (expand it to (B,M,3) instead)."""
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= _lib.KNN_MAX_K:
+        raise ValueError("knn_points: expected an int 1 <= K <= %d, got %r" % (_lib.KNN_MAX_K, K))
+    return _KnnPoints.apply(X, Y, K, x_lengths, y_lengths)
+
+
+def knn_gather(points: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """points (B,M,C) gathered by knn_points' idx (B,N,K) -> (B,N,K,C); a slot of -1 gives a row of zeros.  Plain torch on the tensors'
+    device, differentiable in points."""
+    if points.dim() != 3 or idx.dim() != 3 or idx.shape[0] != points.shape[0] or idx.dtype not in (torch.int32, torch.int64):
+        raise ValueError("knn_gather: expected points (B, M, C) and idx (B, N, K) (int32 or int64), got %s and %s %s"
+                         % (tuple(points.shape), idx.dtype, tuple(idx.shape)))
+    b, n, k = idx.shape
+    c = points.shape[2]
+    at = idx.long().clamp(min=0).reshape(b, n * k, 1).expand(b, n * k, c)
+    out = points.gather(1, at).reshape(b, n, k, c)
+    return torch.where((idx >= 0)[..., None], out, torch.zeros((), dtype=out.dtype, device=out.device))
+
+
+def knn_group(K: int, xyz: torch.Tensor, new_xyz: torch.Tensor, points, channels_first: bool = False) -> torch.Tensor:
+    """The kNN alternative to query_ball_point + group_points: the K nearest points of xyz (B,N,3) around every centre new_xyz (B,S,3)
+    (knn_points(new_xyz, xyz, K)), grouped by group_points with its layouts: (B,S,K,3 + D), or with channels_first=True (points then
+    (B,D,N)) (B,3 + D,K,S).  Differentiable in xyz, new_xyz and points through the grouping; the indices carry no gradient."""
+    _, idx = knn_points(new_xyz.detach(), xyz.detach(), K)
+    return group_points(xyz, new_xyz, points, idx, channels_first=channels_first)
+
+
+# --------------------------------------------------------------------------------------------
+# Local frames: per-point PCA over a neighbourhood (forward only)
+# --------------------------------------------------------------------------------------------
+def _frames_forward_only(*ts):
+    if _wants_grad(*ts):
+        _warn_once("local_frames", "local_frames and estimate_normals are forward-only: eigenvalues, frames and normals carry no gradient "
+                                   "although an argument requires grad (the gradient through an eigenvector is unbounded at ties).  A loss "
+                                   "that needs one can differentiate the covariance in torch.")
+
+
+def _local_frames_call(points, idx, x_lengths, y_lengths, viewpoint, want):
+    """One so3_local_frames_f32 launch; want = (cov, eigenvalues, normals, frames) flags -> the float32 outputs, None where not wanted."""
+    dev = _require_device(points, idx)
+    _frames_forward_only(points, viewpoint)
+    ok = points.dim() in (2, 3) and points.shape[-1] == 3 and idx.dim() == 3 and (points.dim() == 2 or points.shape[0] == idx.shape[0])
+    if (not ok or idx.dtype not in (torch.int32, torch.int64) or not 1 <= points.shape[-2] <= _lib.ADD_S_MAX_N
+            or not 1 <= idx.shape[1] <= _lib.ADD_S_MAX_N or not 1 <= idx.shape[2] <= _lib.KNN_MAX_K):
+        raise ValueError("local_frames: expected points (B, M, 3) or (M, 3) and idx (B, N, K) (int32 or int64) with 1 <= N, M <= %d and "
+                         "1 <= K <= %d, got %s and %s %s" % (_lib.ADD_S_MAX_N, _lib.KNN_MAX_K, tuple(points.shape), idx.dtype, tuple(idx.shape)))
+    b, n, k = idx.shape
+    m = points.shape[-2]
+    if viewpoint is not None:
+        _require_device(viewpoint)
+        if viewpoint.device != dev or tuple(viewpoint.shape) not in ((b, 3), (3,)) or not viewpoint.is_floating_point():
+            raise ValueError("local_frames: expected viewpoint as a (B, 3) or (3,) floating-point tensor on %s for B = %d, got %s %s on %s"
+                             % (dev, b, tuple(viewpoint.shape), viewpoint.dtype, viewpoint.device))
+        viewpoint = viewpoint.detach().float().expand(b, 3).contiguous()
+    y = points.detach().contiguous().float()
+    xl = _cloud_lengths("local_frames", ValueError, "x_lengths", x_lengths, b, n, dev)
+    yl = _cloud_lengths("local_frames", ValueError, "y_lengths", y_lengths, b, m, dev)
+    # an index beyond int32 is invalid either way: clamp it to one that stays invalid (M <= 2^20) instead of letting it wrap
+    ix = (idx if idx.dtype == torch.int32 else idx.clamp(-1, _lib.ADD_S_MAX_N).to(torch.int32)).contiguous()
+    outs = [torch.empty((b, n, w), dtype=torch.float32, device=dev) if flag else None for flag, w in zip(want, (6, 3, 3, 9))]
+    _launch(dev, "so3_local_frames_f32", _ptr(y), 0 if points.dim() == 2 else 3 * m, _ptr(ix), _ptr(xl), _ptr(yl), _ptr(viewpoint),
+            *(_ptr(o) for o in outs), k, b, n, m)
+    return outs
+
+
+def local_frames(points: torch.Tensor, idx: torch.Tensor, x_lengths: torch.Tensor = None, y_lengths: torch.Tensor = None,
+                 viewpoint: torch.Tensor = None, return_covariance: bool = False):
+    """Per-point PCA: for every row of idx (B,N,K) -- as knn_points, knn_group's search or query_ball_point return it, int32 or int64 --
+    the covariance of the points of `points` (B,M,3), or one shared (M,3), that it names, decomposed: (eigenvalues (B,N,3) ascending and
+    >= 0, frames (B,N,3,3) with the unit eigenvectors as columns, right-handed; frames[..., 0] is the surface normal).  With
+    return_covariance=True also cov (B,N,3,3), symmetric.
+
+    A slot is valid when 0 <= idx < m_b; -1 padding, an empty ball's N and anything else are skipped, wherever in the row they stand.
+    x_lengths, y_lengths: optional (B,) int32 / int64: cloud b's rows i < n_b are live, its points j < m_b exist.  The covariance is a
+    fixed-order float32 definition centred on the row's first valid point (include/so3proj.h), so it keeps its digits far from the
+    origin and repeats bit for bit; the eigen stage is a fixed number of Jacobi sweeps in registers, one launch for everything
+    (so3_local_frames_f32), nothing goes to a batched solver.  Signs: the largest-magnitude component of the normal and of the third
+    axis is positive; with viewpoint (B,3) or (3,) the normal faces the viewpoint instead.  A row whose neighbours are all equal gets
+    eigenvalues 0 and the identity frame, with or without a viewpoint; a row without a valid slot, a row past n_b and a cloud with m_b == 0 get zeros.
+
+    Forward only: the outputs carry no gradient (an argument that requires grad is warned about once).  Outputs are computed in
+    float32 and returned in the cloud's dtype."""
+    cov, lam, _, frames = _local_frames_call(points, idx, x_lengths, y_lengths, viewpoint, (bool(return_covariance), True, False, True))
+    b, n = lam.shape[:2]
+    res = (lam.to(points.dtype), frames.view(b, n, 3, 3).to(points.dtype))
+    if return_covariance:
+        res += (cov[..., [0, 1, 2, 1, 3, 4, 2, 4, 5]].view(b, n, 3, 3).to(points.dtype),)
+    return res
+
+
+def estimate_normals(points: torch.Tensor, K: int = 16, lengths: torch.Tensor = None, viewpoint: torch.Tensor = None, return_curvature: bool = False):
+    """Surface normals of a cloud (B,N,3) from its K nearest neighbours: knn_points(points, points, K, lengths, lengths) followed by
+    local_frames' kernel with only the normals requested -> (B,N,3) unit vectors (zeros in the rows past lengths[b]).  The point
+    itself is its own nearest neighbour and so the pivot of its covariance.  viewpoint (B,3) or (3,): the normals face it; without one
+    their largest-magnitude component is positive.  return_curvature=True also returns the surface variation
+    l0 / (l0 + l1 + l2) (B,N), 0 where the sum is 0.  Forward only, as local_frames."""
+    _frames_forward_only(points, viewpoint)
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= _lib.KNN_MAX_K:
+        raise ValueError("estimate_normals: expected an int 1 <= K <= %d, got %r" % (_lib.KNN_MAX_K, K))
+    _require_device(points)
+    if points.dim() != 3 or points.shape[-1] != 3:
+        raise ValueError("estimate_normals: expected points (B, N, 3), got %s" % (tuple(points.shape),))
+    pts = points.detach()
+    _, idx = knn_points(pts, pts, K, lengths, lengths)
+    _, lam, normals, _ = _local_frames_call(pts, idx, lengths, lengths, viewpoint, (False, bool(return_curvature), True, False))
+    normals = normals.to(points.dtype)
+    if not return_curvature:
+        return normals
+    total = lam.sum(-1)
+    variation = torch.where(total > 0, lam[..., 0] / total.clamp_min(torch.finfo(torch.float32).tiny), torch.zeros_like(total))
+    return normals, variation.to(points.dtype)

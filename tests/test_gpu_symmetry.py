@@ -347,15 +347,15 @@ def test_graph_replay_equals_eager(pa):
 def test_first_use_in_a_capture_is_refused(pa, monkeypatch):
     """A table's upload is not capturable: the first use on a device while its stream is captured raises (the capture itself is
     stood in for, so that no graph is left half-captured)."""
-    from poseestimation_amd import rotation_representation as rr
+    from poseestimation_amd import symmetry                                 # SymmetryTable._on looks _capturing up in its own module
     fresh = pa.SymmetryTable(pa.cyclic_symmetry(2))
     r = torch.eye(3).repeat(4, 1, 1).cuda()
-    monkeypatch.setattr(rr, "_capturing", lambda dev: True)
+    monkeypatch.setattr(symmetry, "_capturing", lambda dev: True)
     with pytest.raises(RuntimeError, match=r"table\.to\(device\)"):
         pa.symmetric_loss_frobenius(r, r, fresh)
     monkeypatch.undo()
     fresh.to("cuda")
-    monkeypatch.setattr(rr, "_capturing", lambda dev: True)
+    monkeypatch.setattr(symmetry, "_capturing", lambda dev: True)
     assert fresh._on(r.device) is fresh._dev[r.device.index]                # uploaded: no capture check any more
 
 

@@ -76,11 +76,12 @@ for name, fn in (("floor", stepper(make(None))), ("floor + CDLL call", stepper(m
                  ("mirror (again)", mirror), ("two calls (head, loss)", two_calls)):
     b = blocks(fn)
     print("%-22s median %6.1f  p10 %6.1f  p90 %6.1f  min %6.1f us/step" % (name, 0.5 * (b[9] + b[10]), b[2], b[17], b[0]), flush=True)
-node, rr._so3node = rr._so3node, None              # the same spellings through the Python autograd.Functions
+from poseestimation_amd import _runtime            # _node() looks _so3node up in its own module, not in the facade
+node, _runtime._so3node = _runtime._so3node, None  # the same spellings through the Python autograd.Functions
 for name, fn in (("mirror, Python class", mirror), ("two calls, Python classes", two_calls)):
     b = blocks(fn)
     print("%-26s median %6.1f  p10 %6.1f  p90 %6.1f  min %6.1f us/step" % (name, 0.5 * (b[9] + b[10]), b[2], b[17], b[0]), flush=True)
-rr._so3node = node
+_runtime._so3node = node
 if len(sys.argv) > 1:
     os.sched_setaffinity(0, {0, 1})
     print("-- pinned to cores 0-1")
