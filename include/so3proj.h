@@ -703,6 +703,46 @@ int so3_chamfer_bwd_f32(const float *X, const float *Y, const int32_t *x_len, co
                         const int32_t *nearest_y, const float *scale_x, const float *scale_y, float *dX, float *dY,
                         uint32_t flags, int64_t B, int32_t N, int32_t M, void *stream);
 
+/* ---- Chamfer's normal term: the cosine loss on the nearest pairs, with gradients to both normal sets (added in 210) ----
+ * Lengths, the two searches, nearest_x, nearest_y, dist_x, dist_y and rows are so3_chamfer_fwd_f32's, bit for bit, on the same
+ * input.  NX (B*N*3) and NY (B*M*3) hold a normal per point; they need not be of unit length.  Each direction pairs a point's own
+ * normal a with the normal b of the point its search returned: direction x pairs nx_i with ny_j(i), direction y ny_j with nx_i(j).
+ *     saa = a.a, sbb = b.b, sab = a.b, each one fused multiply-add chain in x, y, z order;
+ *     ra = rsq(saa), rb = rsq(sbb), c = (sab ra) rb;
+ *     a pair is FLAT when !(saa > 0 && saa < inf && sbb > 0 && sbb < inf) -- a zero, NaN or infinite normal, a length whose square
+ *     leaves float32's range: c = 0, the term is 1 and NEITHER normal takes a gradient from the pair;
+ *     t = 1 - |c|, or 1 - c with SO3_CHAMFER_SIGNED_COSINE; t is not clamped (parallel normals may give a t a few ulp below 0);
+ *     rows_n[b] = (sum_{i<n_b} t_i / n_b, sum_{j<m_b} t_j / m_b), the records, float64 chunk-order sums and division of rows;
+ *     (0, 0) for a cloud with an empty side, a second entry of 0 with SO3_CHAMFER_SINGLE.
+ *   rsq is a 1-ulp instruction and not part of the definition: term_*, rows_n, dNX and dNY are defined up to it.
+ * so3_chamfer_normals_fwd_f32: so3_chamfer_fwd_f32's two launches with the term formed behind the search.
+ *   X, Y, NX, NY   in   required;   x_len, y_len  in  optional B int32
+ *   dist_*, nearest_*   out  optional, as so3_chamfer_fwd_f32;   term_x, term_y  out  optional B*N, B*M float32: the per-point t,
+ *                       0 in a slot past its cloud's length (dist_y, nearest_y and term_y must be NULL with SO3_CHAMFER_SINGLE)
+ *   rows, rows_n   out  B*2 float32 each (required)
+ *   work                caller-owned, so3_chamfer_normals_workspace_bytes(B, N, M) bytes (0 out of range), 4-byte aligned, no zero-fill
+ * so3_chamfer_normals_bwd_f32: one launch, both gradients as a gather through the two index arrays the forward left:
+ *     psi(a, b) = dt/da = -sigma ra (b rb - c a ra),  sigma = sgn(c) in {-1, 0, +1}, or 1 with SO3_CHAMFER_SIGNED_COSINE; 0 for a flat pair;
+ *     dNX[b][i] = scale_x[b] psi(nx_i, ny_j(i)) + sum_{j < m_b, i(j) = i} scale_y[b] psi(nx_i, ny_j),   dNY the mirror image
+ *   (t is symmetric in a and b: both uses of a normal take psi with the owner first).  Per coordinate one chain: the own term (a
+ *   rounded product), then fma(scale, psi, acc) over the hits in ascending index.  The term gives no gradient to X or Y: the indices
+ *   are piecewise constant.  scale_x, scale_y  in  B float32: the upstream gradient of rows_n[b][0], rows_n[b][1] times 1 / n_b, 1 / m_b.
+ *   With SO3_CHAMFER_SINGLE nearest_y and scale_y must be NULL (dNY then holds the x direction's hits alone); otherwise both are
+ *   required.  dNX, dNY  out  B*N*3, B*M*3 float32, each optional, not both NULL; a padded slot gets a row of zeros.
+ *   flags: SO3_CHAMFER_UNSQUARED (the forward's e), SO3_CHAMFER_SINGLE, SO3_CHAMFER_SIGNED_COSINE.
+ * Every element of every output is written.  Nothing synchronises with the host and nothing uses atomics or a zero-fill: a call
+ * can be captured in a graph and the same inputs give the same bits.  Limits and the B == 0 no-op as so3_chamfer_fwd_f32.
+ */
+#define SO3_CHAMFER_SIGNED_COSINE 4u
+size_t so3_chamfer_normals_workspace_bytes(int64_t B, int32_t N, int32_t M);
+int so3_chamfer_normals_fwd_f32(const float *X, const float *Y, const float *NX, const float *NY, const int32_t *x_len,
+                                const int32_t *y_len, float *dist_x, int32_t *nearest_x, float *dist_y, int32_t *nearest_y,
+                                float *term_x, float *term_y, float *rows, float *rows_n, void *work, uint32_t flags, int64_t B,
+                                int32_t N, int32_t M, void *stream);
+int so3_chamfer_normals_bwd_f32(const float *NX, const float *NY, const int32_t *x_len, const int32_t *y_len,
+                                const int32_t *nearest_x, const int32_t *nearest_y, const float *scale_x, const float *scale_y,
+                                float *dNX, float *dNY, uint32_t flags, int64_t B, int32_t N, int32_t M, void *stream);
+
 /* ---- K nearest neighbours between two ragged clouds, with gradients to both (added in 210) ----
  * Cloud b uses the first n_b = clip(x_len[b], 0, N) points of X and the first m_b = clip(y_len[b], 0, M) points of Y (NULL: all).
  * The arithmetic is a definition, not an approximation:

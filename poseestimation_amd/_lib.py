@@ -79,6 +79,9 @@ SYMBOLS = {
     "so3_chamfer_workspace_bytes": (ctypes.c_size_t, [_I64, _I32, _I32]),
     "so3_chamfer_fwd_f32": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U32, _I64, _I32, _I32, _P]),
     "so3_chamfer_bwd_f32": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U32, _I64, _I32, _I32, _P]),
+    "so3_chamfer_normals_workspace_bytes": (ctypes.c_size_t, [_I64, _I32, _I32]),
+    "so3_chamfer_normals_fwd_f32": (_INT, [_P] * 15 + [_U32, _I64, _I32, _I32, _P]),
+    "so3_chamfer_normals_bwd_f32": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U32, _I64, _I32, _I32, _P]),
     "so3_knn_f32": (_INT, [_P, _P, _I64, _P, _P, _P, _P, _I32, _I64, _I32, _I32, _P]),
     "so3_knn_bwd_f32": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I64, _I32, _I32, _P]),
     "so3_local_frames_f32": (_INT, [_P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I64, _I32, _I32, _P]),
@@ -99,6 +102,7 @@ SYMBOLS = {
 
 SYM_ADD_L2, SYM_ADD_L1, SYM_ADD_MAX = 0, 1, 2      # include/so3proj.h: SO3_SYM_ADD_L2, SO3_SYM_ADD_L1, SO3_SYM_ADD_MAX (so3_sym_add_f32's flags)
 CHAMFER_UNSQUARED, CHAMFER_SINGLE = 1, 2           # include/so3proj.h: SO3_CHAMFER_UNSQUARED, SO3_CHAMFER_SINGLE
+CHAMFER_SIGNED_COSINE = 4                         # include/so3proj.h: SO3_CHAMFER_SIGNED_COSINE (so3_chamfer_normals_*_f32 only)
 KNN_MAX_K = 64                                    # include/so3proj.h: SO3_KNN_MAX_K
 ADD_S_MAX_N = 1 << 20                             # include/so3proj.h: SO3_ADD_S_MAX_N
 FPS_MAX_N = 16384                                 # include/so3proj.h: SO3_FPS_MAX_N

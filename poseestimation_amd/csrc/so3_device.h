@@ -1635,6 +1635,49 @@ __device__ __forceinline__ void chamfer_hit(float c, float ux, float uy, float u
     acc[2] = __builtin_fmaf(c, uz, acc[2]);
 }
 
+// ---- Chamfer's normal term: the cosine loss on the nearest pairs (so3proj.hip: k_chamfer_normals_fwd, k_chamfer_normals_rows,
+// k_chamfer_normals_bwd; tests/host_model/chamfer_normals.cpp) ------------------------------------------------------------------------
+// A pair is a point's own normal a and the normal b of the point its search returned.  saa, sbb, sab are one fma chain each in x, y, z
+// order; ra = rsq(saa), rb = rsq(sbb), c = (sab ra) rb.  A pair is FLAT unless both squared lengths are positive and finite (a zero, NaN
+// or infinite normal, a length whose square leaves float32): c = 0, the term is 1 and neither normal takes a gradient.
+//     t = 1 - |c|,  or 1 - c when `signed_cos` (SO3_CHAMFER_SIGNED_COSINE; wave-uniform);  t is not clamped.
+//     psi(a, b) = dt/da = -sigma ra (b rb - c a ra),  sigma = sgn(c) in {-1, 0, +1}, or 1 when signed; 0 for a flat pair.
+// t is symmetric in a and b, so both uses of a normal take psi with the OWNER as the first argument.  The gradient of one normal is
+// chamfer_own's chain: the own term s psi first (one rounded product), then chamfer_hit(s', psi) over the hits in ascending index.
+struct ChamferCosine { float c, ra, rb; bool flat; };
+__device__ __forceinline__ float chamfer_dot3(float ax, float ay, float az, float bx, float by, float bz) {
+    return __builtin_fmaf(az, bz, __builtin_fmaf(ay, by, ax * bx));
+}
+__device__ __forceinline__ ChamferCosine chamfer_cosine(float ax, float ay, float az, float bx, float by, float bz) {
+    const float saa = chamfer_dot3(ax, ay, az, ax, ay, az), sbb = chamfer_dot3(bx, by, bz, bx, by, bz), sab = chamfer_dot3(ax, ay, az, bx, by, bz);
+    const float inf = __builtin_huge_valf();
+    ChamferCosine k = {0.f, 0.f, 0.f, !(saa > 0.f && saa < inf && sbb > 0.f && sbb < inf)};
+    if (!k.flat) {
+        k.ra = hw::rsq(saa);
+        k.rb = hw::rsq(sbb);
+        k.c = (sab * k.ra) * k.rb;
+    }
+    return k;
+}
+__device__ __forceinline__ float chamfer_normal_term(float ax, float ay, float az, float bx, float by, float bz, bool signed_cos) {
+    const float c = chamfer_cosine(ax, ay, az, bx, by, bz).c;
+    return 1.f - (signed_cos ? c : __builtin_fabsf(c));
+}
+// psi(a, b); a flat pair gives +0 in every coordinate, whatever its normals hold
+__device__ __forceinline__ void chamfer_normal_psi(float ax, float ay, float az, float bx, float by, float bz, bool signed_cos, float &ux, float &uy,
+                                                   float &uz) {
+    const ChamferCosine k = chamfer_cosine(ax, ay, az, bx, by, bz);
+    const float sigma = signed_cos ? 1.f : (k.c > 0.f ? 1.f : (k.c < 0.f ? -1.f : 0.f));
+    const float g = -sigma * k.ra;                              // exact
+    ux = k.flat ? 0.f : g * __builtin_fmaf(-k.c, ax * k.ra, bx * k.rb);
+    uy = k.flat ? 0.f : g * __builtin_fmaf(-k.c, ay * k.ra, by * k.rb);
+    uz = k.flat ? 0.f : g * __builtin_fmaf(-k.c, az * k.ra, bz * k.rb);
+}
+// the own term: it opens the chain
+__device__ __forceinline__ void chamfer_normal_own(float s, float ux, float uy, float uz, float (&acc)[3]) {
+    acc[0] = s * ux; acc[1] = s * uy; acc[2] = s * uz;
+}
+
 // ---- K nearest neighbours between two ragged clouds, with gradients to both (so3proj.hip: k_knn, k_knn_bwd;
 // tests/host_model/knn.cpp) ----------------------------------------------------------------------------------------------------------
 // The arithmetic is a DEFINITION (include/so3proj.h): d = pointnet_dist2, a row holds the min(K, m_b) smallest candidates under

@@ -2239,6 +2239,157 @@ __global__ __launch_bounds__(kBlock) void k_chamfer_bwd(const float *__restrict_
     }
 }
 
+// ---- Chamfer's normal term: the cosine loss on the pairs the searches return ---------------------------------------------------------
+// k_chamfer_normals_fwd is k_chamfer_fwd with an epilogue per kept slot: the search has left the nearest index in a register, the
+// lane loads its own normal (coalesced, 12 bytes) and gathers its neighbour's (12 bytes from L2), forms t = chamfer_normal_term and
+// keeps a second lane sum in slot order.  The search's x, y, z are dead by then.  A work item leaves TWO floats, rec[item] = (sum of
+// e, sum of t): item_record<2>, whose entry 0 adds the waves' sums in item_record<1>'s order -- dist, nearest and the distance rows
+// are k_chamfer_fwd's bits.  signed_cos is wave-uniform (an SGPR), not a template parameter.  No atomics, no zero-fill.
+template <bool SQUARED, int U>
+__global__ __launch_bounds__(kBlock) void k_chamfer_normals_fwd(const float *__restrict__ X, const float *__restrict__ Y, const float *__restrict__ NX,
+                                                                const float *__restrict__ NY, const int32_t *__restrict__ x_len,
+                                                                const int32_t *__restrict__ y_len, float *__restrict__ dist_x,
+                                                                int32_t *__restrict__ nearest_x, float *__restrict__ dist_y,
+                                                                int32_t *__restrict__ nearest_y, float *__restrict__ term_x,
+                                                                float *__restrict__ term_y, float *__restrict__ rec, int32_t signed_cos, int64_t B,
+                                                                int32_t N, int32_t M, int32_t chunks_x, int32_t chunks_y) {
+    static_assert(kBlock == so3::kIcpBlock, "the host model's chunking");
+    __shared__ float4 tile[kAddsTile];
+    const int tid = threadIdx.x;
+    const int per = chunks_x + chunks_y;
+    const int64_t items = B * per;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t b = item / per;
+        const int c = static_cast<int>(item - b * per);
+        const bool rev = c >= chunks_x;                              // the y direction: Y's points search X
+        const int i_base = (rev ? c - chunks_x : c) * (kBlock * U);
+        const int32_t nb = so3::chamfer_length(x_len, b, N), mb = so3::chamfer_length(y_len, b, M);
+        const int32_t full = rev ? M : N, len_p = rev ? mb : nb, len_q = rev ? nb : mb;
+        const float *src = rev ? Y + b * M * 3 : X + b * N * 3, *tgt = rev ? X + b * N * 3 : Y + b * M * 3;
+        const float *own = rev ? NY + b * M * 3 : NX + b * N * 3, *other = rev ? NX + b * N * 3 : NY + b * M * 3;
+        float *dist = rev ? dist_y : dist_x, *term = rev ? term_y : term_x;
+        int32_t *nearest = rev ? nearest_y : nearest_x;
+        const bool live = len_q > 0 && i_base < len_p;              // the same in every lane of the workgroup
+        float x[U], y[U], z[U], best[U];
+        int idx[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) { x[u] = 0.f; y[u] = 0.f; z[u] = 0.f; best[u] = 0.f; idx[u] = 0; }
+        if (live) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int i = min(i_base + u * kBlock + tid, len_p - 1);    // a slot beyond the cloud repeats its last point; not summed, not stored
+                x[u] = src[i * 3 + 0]; y[u] = src[i * 3 + 1]; z[u] = src[i * 3 + 2];
+                best[u] = __builtin_huge_valf();
+            }
+            tile_search<true, false>(tile, tid, len_q, [=](int j) { return tile_point(tgt, j); }, x, y, z, best, idx);
+        }
+        float mine = 0.f, mine_n = 0.f;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = i_base + u * kBlock + tid;
+            const bool valid = live && i < len_p;
+            const float e = valid ? so3::chamfer_term<SQUARED>(best[u]) : 0.f;
+            mine += e;
+            float t = 0.f;
+            if (live) {                                              // both indices clamped into the live part before they address anything
+                const int ic = min(i, len_p - 1), j = min(max(idx[u], 0), len_q - 1);
+                const float tt = so3::chamfer_normal_term(own[ic * 3 + 0], own[ic * 3 + 1], own[ic * 3 + 2], other[j * 3 + 0], other[j * 3 + 1],
+                                                          other[j * 3 + 2], signed_cos != 0);
+                t = valid ? tt : 0.f;
+            }
+            mine_n += t;
+            if (i < full) {
+                if (dist != nullptr) dist[b * full + i] = e;
+                if (nearest != nullptr) nearest[b * full + i] = valid ? min(idx[u], len_q - 1) : -1;
+                if (term != nullptr) term[b * full + i] = t;
+            }
+        }
+        const float sum_e = wave_allsum(mine), sum_t = wave_allsum(mine_n);
+        item_record<2>(tile, tid, (tid & 63) == 0 ? sum_e : sum_t, rec + item * 2);
+    }
+}
+
+// rows[b] = (cham_x, cham_y) with k_chamfer_rows' arithmetic on the records' first floats, and rows_n[b] the same on their second.
+__global__ __launch_bounds__(kBlock) void k_chamfer_normals_rows(const float *__restrict__ rec, const int32_t *__restrict__ x_len,
+                                                                 const int32_t *__restrict__ y_len, float *__restrict__ rows,
+                                                                 float *__restrict__ rows_n, int64_t B, int32_t N, int32_t M, int32_t chunks_x,
+                                                                 int32_t chunks_y) {
+    const int per = chunks_x + chunks_y;
+    for (int64_t t = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; t < 2 * B; t += static_cast<int64_t>(gridDim.x) * kBlock) {
+        const int64_t b = t >> 1;
+        const bool rev = (t & 1) != 0;
+        const int32_t nb = so3::chamfer_length(x_len, b, N), mb = so3::chamfer_length(y_len, b, M);
+        const float *r = rec + (b * per + (rev ? chunks_x : 0)) * 2;
+        const int chunks = rev ? chunks_y : chunks_x;
+        double acc = 0.0, acc_n = 0.0;
+        for (int c = 0; c < chunks; ++c) { acc += static_cast<double>(r[c * 2]); acc_n += static_cast<double>(r[c * 2 + 1]); }
+        const bool scored = nb > 0 && mb > 0 && chunks > 0;
+        const double len = static_cast<double>(rev ? mb : nb);
+        rows[t] = scored ? static_cast<float>(acc / len) : 0.f;
+        rows_n[t] = scored ? static_cast<float>(acc_n / len) : 0.f;
+    }
+}
+
+// k_chamfer_normals_bwd: both normals' gradients as a gather, at k_chamfer_bwd's geometry (64 owners per wave, one per lane, dNX's
+// items first, no LDS, no barrier).  A lane opens its chain with its own pair (its neighbour's normal gathered through the clamped
+// index), then the wave takes the OTHER direction's `nearest` through owner_scan: the owner's three floats are its normal, a hit lane
+// gathers its own normal and forms psi(owner, hit), the coefficient is the cloud's.  The points themselves are not read.
+__global__ __launch_bounds__(kBlock) void k_chamfer_normals_bwd(const float *__restrict__ NX, const float *__restrict__ NY,
+                                                                const int32_t *__restrict__ x_len, const int32_t *__restrict__ y_len,
+                                                                const int32_t *__restrict__ nearest_x, const int32_t *__restrict__ nearest_y,
+                                                                const float *__restrict__ scale_x, const float *__restrict__ scale_y,
+                                                                float *__restrict__ dNX, float *__restrict__ dNY, int32_t signed_cos, int64_t B,
+                                                                int32_t N, int32_t M, int32_t chunks_x, int32_t chunks_y) {
+    static_assert(so3::kChamferOwners == 64 && kBlock % 64 == 0, "one owner per lane");
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int per = chunks_x + chunks_y;
+    const int64_t items = B * per;
+    const bool sc = signed_cos != 0;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t b = item / per;
+        const int c = static_cast<int>(item - b * per);
+        const bool rev = c >= chunks_x;                              // dNY: Y's normals own, X's hit
+        const int32_t full = rev ? M : N, qfull = rev ? N : M;
+        const int first = (rev ? c - chunks_x : c) * kBlock + wave * 64;
+        float *out = rev ? dNY : dNX;
+        if (out == nullptr || first >= full) continue;
+        const int32_t nb = so3::chamfer_length(x_len, b, N), mb = so3::chamfer_length(y_len, b, M);
+        const int32_t len_p = rev ? mb : nb, len_q = rev ? nb : mb;
+        const float *P = rev ? NY + b * M * 3 : NX + b * N * 3, *Q = rev ? NX + b * N * 3 : NY + b * M * 3;
+        const int32_t *near_own = rev ? nearest_y : nearest_x, *near_hit = rev ? nearest_x : nearest_y;
+        const float *s_own = rev ? scale_y : scale_x, *s_hit = rev ? scale_x : scale_y;
+        const int i = first + lane;
+        float acc[3] = {0.f, 0.f, 0.f};
+        const bool live = len_q > 0 && first < len_p;                // wave-uniform
+        if (live) {
+            const int ic = min(i, len_p - 1);
+            const float px = P[ic * 3 + 0], py = P[ic * 3 + 1], pz = P[ic * 3 + 2];
+            if (s_own != nullptr && near_own != nullptr) {
+                const int j = min(max(near_own[b * full + ic], 0), len_q - 1);
+                float ux, uy, uz;
+                so3::chamfer_normal_psi(px, py, pz, Q[j * 3 + 0], Q[j * 3 + 1], Q[j * 3 + 2], sc, ux, uy, uz);
+                so3::chamfer_normal_own(s_own[b], ux, uy, uz, acc);
+            }
+            if (s_hit != nullptr && near_hit != nullptr) {
+                const float cb = s_hit[b];
+                const unsigned owners = static_cast<unsigned>(min(64, len_p - first));
+                const int32_t *hits = near_hit + b * qfull;
+                owner_scan(lane, first, owners, len_q, px, py, pz, [&](int j) { return hits[j]; },
+                    [&](int j, float ox, float oy, float oz, float &ux, float &uy, float &uz, float &) {
+                        so3::chamfer_normal_psi(ox, oy, oz, Q[j * 3 + 0], Q[j * 3 + 1], Q[j * 3 + 2], sc, ux, uy, uz);
+                    },
+                    [&](float, int) { return cb; }, acc);
+            }
+        }
+        if (i < full) {
+            const bool keep = live && i < len_p;
+            float *o = out + (b * full + i) * 3;
+            o[0] = keep ? acc[0] : 0.f; o[1] = keep ? acc[1] : 0.f; o[2] = keep ? acc[2] : 0.f;
+        }
+    }
+}
+
 // ---- PointNet++ sampling and grouping: farthest-point sampling and ball query ----------------------------------------------------
 // The maximum of a 64-bit key over the wave, in every lane (wave_allmax's partners).
 __device__ __forceinline__ unsigned long long key_max(unsigned long long a, unsigned int lo, unsigned int hi) {
@@ -5164,6 +5315,62 @@ int so3_chamfer_bwd_f32(const float *X, const float *Y, const int32_t *x_len, co
                            nearest_x, nearest_y, scale_x, scale_y, dX, dY, B, N, M, ch.x, ch.y);
     }, (flags & SO3_CHAMFER_UNSQUARED) == 0);
     return check_launch("so3_chamfer_bwd_f32");
+}
+
+size_t so3_chamfer_normals_workspace_bytes(int64_t B, int32_t N, int32_t M) {
+    // two floats per work item (the distance's sum and the normal term's) at the smallest work item (U = 1), both directions
+    return 2 * so3_chamfer_workspace_bytes(B, N, M);
+}
+
+int so3_chamfer_normals_fwd_f32(const float *X, const float *Y, const float *NX, const float *NY, const int32_t *x_len, const int32_t *y_len,
+                                float *dist_x, int32_t *nearest_x, float *dist_y, int32_t *nearest_y, float *term_x, float *term_y, float *rows,
+                                float *rows_n, void *work, uint32_t flags, int64_t B, int32_t N, int32_t M, void *stream) {
+    SO3_CHECK_ARGS((flags & ~static_cast<unsigned>(SO3_CHAMFER_UNSQUARED | SO3_CHAMFER_SINGLE | SO3_CHAMFER_SIGNED_COSINE)) == 0,
+                   "so3_chamfer_normals_fwd_f32: unknown flag");
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && M >= 1 && M <= SO3_ADD_S_MAX_N,
+                   "so3_chamfer_normals_fwd_f32: B/N/M");
+    if (B == 0) return 0;
+    const bool single = (flags & SO3_CHAMFER_SINGLE) != 0;
+    SO3_CHECK_ARGS(X != nullptr && Y != nullptr && NX != nullptr && NY != nullptr && rows != nullptr && rows_n != nullptr && work != nullptr,
+                   "so3_chamfer_normals_fwd_f32: null pointer");
+    SO3_CHECK_ARGS(!single || (dist_y == nullptr && nearest_y == nullptr && term_y == nullptr),
+                   "so3_chamfer_normals_fwd_f32: dist_y / nearest_y / term_y with SO3_CHAMFER_SINGLE");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int u = so3::chamfer_points_per_lane(B, N, M, single, device_cus());      // so3_chamfer_fwd_f32's rule: the same partial sums
+    const ChamferChunks ch = chamfer_chunks(N, M, single, u);
+    float *rec = static_cast<float *>(work);
+    const int32_t signed_cos = (flags & SO3_CHAMFER_SIGNED_COSINE) != 0 ? 1 : 0;
+    with_flags([&](auto SQ) {
+        constexpr bool kSquared = SQ();
+        with_value<4, 2, 1>(u, [&](auto U) {
+            name_kernel("k_chamfer_normals_fwd", kSquared, U);
+            hipLaunchKernelGGL((k_chamfer_normals_fwd<kSquared, U()>), dim3(chamfer_grid(B, ch)), dim3(kBlock), 0, s, X, Y, NX, NY, x_len, y_len, dist_x,
+                               nearest_x, dist_y, nearest_y, term_x, term_y, rec, signed_cos, B, N, M, ch.x, ch.y);
+        });
+    }, (flags & SO3_CHAMFER_UNSQUARED) == 0);
+    const unsigned rows_grid = static_cast<unsigned>(std::min<int64_t>((2 * B + kBlock - 1) / kBlock, static_cast<int64_t>(device_cus()) * 64));
+    hipLaunchKernelGGL(k_chamfer_normals_rows, dim3(rows_grid), dim3(kBlock), 0, s, rec, x_len, y_len, rows, rows_n, B, N, M, ch.x, ch.y);
+    return check_launch("so3_chamfer_normals_fwd_f32");
+}
+
+int so3_chamfer_normals_bwd_f32(const float *NX, const float *NY, const int32_t *x_len, const int32_t *y_len, const int32_t *nearest_x,
+                                const int32_t *nearest_y, const float *scale_x, const float *scale_y, float *dNX, float *dNY, uint32_t flags,
+                                int64_t B, int32_t N, int32_t M, void *stream) {
+    SO3_CHECK_ARGS((flags & ~static_cast<unsigned>(SO3_CHAMFER_UNSQUARED | SO3_CHAMFER_SINGLE | SO3_CHAMFER_SIGNED_COSINE)) == 0,
+                   "so3_chamfer_normals_bwd_f32: unknown flag");
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && M >= 1 && M <= SO3_ADD_S_MAX_N,
+                   "so3_chamfer_normals_bwd_f32: B/N/M");
+    if (B == 0) return 0;
+    const bool single = (flags & SO3_CHAMFER_SINGLE) != 0;
+    SO3_CHECK_ARGS(NX != nullptr && NY != nullptr && nearest_x != nullptr && scale_x != nullptr && (dNX != nullptr || dNY != nullptr),
+                   "so3_chamfer_normals_bwd_f32: null pointer");
+    SO3_CHECK_ARGS(single ? (nearest_y == nullptr && scale_y == nullptr) : (nearest_y != nullptr && scale_y != nullptr),
+                   "so3_chamfer_normals_bwd_f32: nearest_y and scale_y go with both directions, NULL with SO3_CHAMFER_SINGLE");
+    const ChamferChunks ch = chamfer_chunks(N, M, false, 1);
+    name_kernel("k_chamfer_normals_bwd");
+    hipLaunchKernelGGL(k_chamfer_normals_bwd, dim3(chamfer_grid(B, ch)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), NX, NY, x_len, y_len,
+                       nearest_x, nearest_y, scale_x, scale_y, dNX, dNY, (flags & SO3_CHAMFER_SIGNED_COSINE) != 0 ? 1 : 0, B, N, M, ch.x, ch.y);
+    return check_launch("so3_chamfer_normals_bwd_f32");
 }
 
 int so3_knn_f32(const float *X, const float *Y, int64_t y_stride, const int32_t *x_len, const int32_t *y_len, float *dist2, int32_t *idx, int32_t K,

@@ -170,6 +170,33 @@ def icp_align_plane(P: torch.Tensor, Q: torch.Tensor, normals: torch.Tensor = No
 # the Chamfer distance: a loss between two clouds, differentiable in both
 # --------------------------------------------------------------------------------------------
 
+def _chamfer_reduce(rows, nx, ny, n, m, point_reduction, batch_reduction, single):
+    """The loss from the (B,2) means a forward left (the distance's or the normal term's): a few (B,)-sized torch statements.
+    nx, ny: the point counts as float32, None for the full lengths n, m."""
+    cham_x, cham_y = rows[:, 0], rows[:, 1]
+    if point_reduction == "sum":                       # rows holds the means
+        cham_x = cham_x * (float(n) if nx is None else nx)
+        cham_y = cham_y * (float(m) if ny is None else ny)
+    per_cloud = cham_x if single else cham_x + cham_y
+    return per_cloud.mean() if batch_reduction == "mean" else (per_cloud.sum() if batch_reduction == "sum" else per_cloud.contiguous())
+
+
+def _chamfer_scales(grad_out, nx, ny, b, n, m, point_reduction, batch_reduction, single):
+    """_chamfer_reduce's backward folded with the upstream gradient into the per-cloud scales (scale_x, scale_y) the backward kernels
+    take, on the device; scale_y is None for a single direction."""
+    g = grad_out.detach().float()
+    if batch_reduction is None:
+        g = g.reshape(b)
+    else:                                              # one upstream scalar for every cloud, kept on the device
+        g = (g.reshape(1) * (1.0 / max(b, 1)) if batch_reduction == "mean" else g.reshape(1)).expand(b)
+    if point_reduction == "mean":                      # an empty cloud takes no gradient: the kernel writes its rows as 0
+        scale_x = g * (1.0 / n) if nx is None else g / nx.clamp(min=1.0)
+        scale_y = g * (1.0 / m) if ny is None else g / ny.clamp(min=1.0)
+    else:
+        scale_x = scale_y = g
+    return scale_x.contiguous(), None if single else scale_y.contiguous()
+
+
 
 class _Chamfer(torch.autograd.Function):
     """chamfer_distance: so3_chamfer_fwd_f32 searches both directions and leaves the (B,2) means; the reductions over them are a few
@@ -197,12 +224,7 @@ class _Chamfer(torch.autograd.Function):
         work = torch.empty((max(int(_libh().so3_chamfer_workspace_bytes(b, n, m)) // 4, 1),), dtype=torch.float32, device=dev)
         _launch(dev, "so3_chamfer_fwd_f32", _ptr(x), _ptr(y), _ptr(xl), _ptr(yl), _ptr(dist_x), _ptr(near_x), _ptr(dist_y), _ptr(near_y), _ptr(rows),
                 _ptr(work), flags, b, n, m)
-        cham_x, cham_y = rows[:, 0], rows[:, 1]
-        if point_reduction == "sum":                       # rows holds the means
-            cham_x = cham_x * (float(n) if nx is None else nx)
-            cham_y = cham_y * (float(m) if ny is None else ny)
-        per_cloud = cham_x if single else cham_x + cham_y
-        out = per_cloud.mean() if batch_reduction == "mean" else (per_cloud.sum() if batch_reduction == "sum" else per_cloud.contiguous())
+        out = _chamfer_reduce(rows, nx, ny, n, m, point_reduction, batch_reduction, single)
         if want_grad:
             ctx.save_for_backward(x, y, xl, yl, near_x, near_y, nx, ny)
         ctx.meta = (want_x, want_y, flags, point_reduction, batch_reduction, X.dtype, Y.dtype, b, n, m)
@@ -220,19 +242,7 @@ class _Chamfer(torch.autograd.Function):
             return (None,) * 9
         x, y, xl, yl, near_x, near_y, nx, ny = ctx.saved_tensors
         dev = x.device
-        g = grad_out.detach().float()
-        if batch_reduction is None:
-            g = g.reshape(b)
-        else:                                              # one upstream scalar for every cloud, kept on the device
-            g = (g.reshape(1) * (1.0 / max(b, 1)) if batch_reduction == "mean" else g.reshape(1)).expand(b)
-        if point_reduction == "mean":                      # an empty cloud takes no gradient: the kernel writes its rows as 0
-            scale_x = g * (1.0 / n) if nx is None else g / nx.clamp(min=1.0)
-            scale_y = g * (1.0 / m) if ny is None else g / ny.clamp(min=1.0)
-        else:
-            scale_x = scale_y = g
-        single = bool(flags & _lib.CHAMFER_SINGLE)
-        scale_x = scale_x.contiguous()
-        scale_y = None if single else scale_y.contiguous()
+        scale_x, scale_y = _chamfer_scales(grad_out, nx, ny, b, n, m, point_reduction, batch_reduction, bool(flags & _lib.CHAMFER_SINGLE))
         dx = torch.empty((b, n, 3), dtype=torch.float32, device=dev) if want_x else None
         dy = torch.empty((b, m, 3), dtype=torch.float32, device=dev) if want_y else None
         _launch(dev, "so3_chamfer_bwd_f32", _ptr(x), _ptr(y), _ptr(xl), _ptr(yl), _ptr(near_x), _ptr(near_y), _ptr(scale_x), _ptr(scale_y),
@@ -240,9 +250,85 @@ class _Chamfer(torch.autograd.Function):
         return (_grad_to(dx, x_dtype), _grad_to(dy, y_dtype)) + (None,) * 7
 
 
+class _ChamferNormals(torch.autograd.Function):
+    """chamfer_distance with normals: ONE so3_chamfer_normals_fwd_f32 call leaves the distance's and the normal term's (B,2) means,
+    _Chamfer's reductions make (loss, loss_normals) of them.  The backward folds each upstream gradient into per-cloud scales on the
+    device and launches so3_chamfer_bwd_f32 only for a loss that received a gradient and a cloud that wants one,
+    so3_chamfer_normals_bwd_f32 only for a loss_normals that received one and a normal tensor that wants one."""
+
+    @staticmethod
+    def forward(ctx, X, Y, NX, NY, x_lengths, y_lengths, squared, point_reduction, batch_reduction, single, return_nearest, abs_cosine):
+        ctx.set_materialize_grads(False)                   # an unused output costs no launch
+        dev, x, y, _, b, n, m = _cloud_pair("chamfer_distance", X, Y, shared_target=False)
+        _require_device(x, NX, NY)
+        if tuple(NX.shape) != tuple(X.shape) or tuple(NY.shape) != tuple(Y.shape) or not (NX.is_floating_point() and NY.is_floating_point()):
+            raise RuntimeError("chamfer_distance: expected floating-point x_normals of X's shape %s and y_normals of Y's shape %s, got %s %s and %s %s"
+                               % (tuple(X.shape), tuple(Y.shape), NX.dtype, tuple(NX.shape), NY.dtype, tuple(NY.shape)))
+        nrm_x, nrm_y = NX.detach().contiguous().float(), NY.detach().contiguous().float()
+        xl = _cloud_lengths("chamfer_distance", RuntimeError, "x_lengths", x_lengths, b, n, dev)
+        yl = _cloud_lengths("chamfer_distance", RuntimeError, "y_lengths", y_lengths, b, m, dev)
+        nx, ny = (None if l is None else l.to(torch.float32) for l in (xl, yl))       # the point counts; None: the full length
+        want = tuple(ctx.needs_input_grad[:4])
+        want_cloud, want_normal = want[0] or want[1], want[2] or want[3]
+        want_grad = want_cloud or want_normal
+        flags = (0 if squared else _lib.CHAMFER_UNSQUARED) | (_lib.CHAMFER_SINGLE if single else 0) | (0 if abs_cosine else _lib.CHAMFER_SIGNED_COSINE)
+
+        def buf(rows, dtype, wanted):
+            return torch.empty((b, rows), dtype=dtype, device=dev) if wanted else None
+
+        near_x = buf(n, torch.int32, want_grad or return_nearest)
+        near_y = buf(m, torch.int32, (want_grad or return_nearest) and not single)
+        dist_x = buf(n, torch.float32, return_nearest)
+        dist_y = buf(m, torch.float32, return_nearest and not single)
+        term_x = buf(n, torch.float32, return_nearest)
+        term_y = buf(m, torch.float32, return_nearest and not single)
+        rows = torch.empty((b, 2), dtype=torch.float32, device=dev)
+        rows_n = torch.empty((b, 2), dtype=torch.float32, device=dev)
+        work = torch.empty((max(int(_libh().so3_chamfer_normals_workspace_bytes(b, n, m)) // 4, 1),), dtype=torch.float32, device=dev)
+        _launch(dev, "so3_chamfer_normals_fwd_f32", _ptr(x), _ptr(y), _ptr(nrm_x), _ptr(nrm_y), _ptr(xl), _ptr(yl), _ptr(dist_x), _ptr(near_x),
+                _ptr(dist_y), _ptr(near_y), _ptr(term_x), _ptr(term_y), _ptr(rows), _ptr(rows_n), _ptr(work), flags, b, n, m)
+        out = _chamfer_reduce(rows, nx, ny, n, m, point_reduction, batch_reduction, single)
+        out_n = _chamfer_reduce(rows_n, nx, ny, n, m, point_reduction, batch_reduction, single)
+        if want_grad:
+            ctx.save_for_backward(x if want_cloud else None, y if want_cloud else None, nrm_x if want_normal else None,
+                                  nrm_y if want_normal else None, xl, yl, near_x, near_y, nx, ny)
+        ctx.meta = (want, flags, point_reduction, batch_reduction, (X.dtype, Y.dtype, NX.dtype, NY.dtype), b, n, m)
+        if not return_nearest:
+            return out, out_n
+        extras = (near_x.long(), dist_x, term_x) if single else (near_x.long(), dist_x, term_x, near_y.long(), dist_y, term_y)
+        ctx.mark_non_differentiable(*extras)
+        return (out, out_n) + extras
+
+    @staticmethod
+    def backward(ctx, grad_out, grad_normals, *unused):
+        _no_double_backward(grad_out, grad_normals)
+        want, flags, point_reduction, batch_reduction, dtypes, b, n, m = ctx.meta
+        grads = [None, None, None, None]
+        if any(want) and (grad_out is not None or grad_normals is not None):
+            x, y, nrm_x, nrm_y, xl, yl, near_x, near_y, nx, ny = ctx.saved_tensors
+            dev = near_x.device
+            single = bool(flags & _lib.CHAMFER_SINGLE)
+
+            def outs(wx, wy):
+                return (torch.empty((b, n, 3), dtype=torch.float32, device=dev) if wx else None,
+                        torch.empty((b, m, 3), dtype=torch.float32, device=dev) if wy else None)
+
+            if grad_out is not None and (want[0] or want[1]):
+                scale_x, scale_y = _chamfer_scales(grad_out, nx, ny, b, n, m, point_reduction, batch_reduction, single)
+                grads[0], grads[1] = outs(want[0], want[1])
+                _launch(dev, "so3_chamfer_bwd_f32", _ptr(x), _ptr(y), _ptr(xl), _ptr(yl), _ptr(near_x), _ptr(near_y), _ptr(scale_x), _ptr(scale_y),
+                        _ptr(grads[0]), _ptr(grads[1]), flags & ~_lib.CHAMFER_SIGNED_COSINE, b, n, m)
+            if grad_normals is not None and (want[2] or want[3]):
+                scale_x, scale_y = _chamfer_scales(grad_normals, nx, ny, b, n, m, point_reduction, batch_reduction, single)
+                grads[2], grads[3] = outs(want[2], want[3])
+                _launch(dev, "so3_chamfer_normals_bwd_f32", _ptr(nrm_x), _ptr(nrm_y), _ptr(xl), _ptr(yl), _ptr(near_x), _ptr(near_y), _ptr(scale_x),
+                        _ptr(scale_y), _ptr(grads[2]), _ptr(grads[3]), flags, b, n, m)
+        return tuple(_grad_to(g, d) for g, d in zip(grads, dtypes)) + (None,) * 8
+
+
 def chamfer_distance(X: torch.Tensor, Y: torch.Tensor, x_lengths: torch.Tensor = None, y_lengths: torch.Tensor = None, squared: bool = True,
                      point_reduction: str = "mean", batch_reduction: str = "mean", single_directional: bool = False,
-                     return_nearest: bool = False):
+                     return_nearest: bool = False, x_normals: torch.Tensor = None, y_normals: torch.Tensor = None, abs_cosine: bool = True):
     """The Chamfer distance between the clouds X (B,N,3) and Y (B,M,3), differentiable in BOTH clouds:
 
         loss_b = mean_{i < n_b} min_{j < m_b} |x_i - y_j|^2  +  mean_{j < m_b} min_{i < n_b} |y_j - x_i|^2.
@@ -258,10 +344,31 @@ def chamfer_distance(X: torch.Tensor, Y: torch.Tensor, x_lengths: torch.Tensor =
     order.  No atomics and nothing synchronises with the host: the same inputs give the same bits, and the call captures into a graph.
 
     return_nearest=True returns (loss, info) with info["nearest_x"] (B,N), info["nearest_y"] (B,M) int64 (-1 in slots past the length)
-    and info["dist_x"], info["dist_y"] float32, the per-point terms (0 in those slots); single_directional leaves the y entries out."""
+    and info["dist_x"], info["dist_y"] float32, the per-point terms (0 in those slots); single_directional leaves the y entries out.
+
+    x_normals (B,N,3) and y_normals (B,M,3), both or neither, add the normal term of the same pairs and the call returns
+    (loss, loss_normals), or (loss, loss_normals, info) with info["normal_x"], info["normal_y"] float32, the per-point terms:
+
+        loss_normals_b = mean_{i < n_b} (1 - |cos(nx_i, ny_j(i))|)  +  mean_{j < m_b} (1 - |cos(ny_j, nx_i(j))|),
+
+    reduced as loss is; abs_cosine=False takes 1 - cos.  The normals need not be of unit length and may have any float dtype (the
+    arithmetic is float32); a pair with a zero, NaN or infinite normal scores 1 and gives no gradient.  loss_normals is differentiable
+    in both normal tensors and gives no gradient to the clouds (the pairing is piecewise constant); loss is the same bits, with the
+    same gradients, as without normals.  Still one forward launch; the backward makes one launch for each of the two losses that
+    received a gradient, the normals' a gather in a fixed order as the clouds' is."""
     if point_reduction not in ("mean", "sum") or batch_reduction not in ("mean", "sum", None):
         raise ValueError("chamfer_distance: point_reduction is 'mean' or 'sum' and batch_reduction 'mean', 'sum' or None, got %r and %r"
                          % (point_reduction, batch_reduction))
+    if (x_normals is None) != (y_normals is None):
+        raise ValueError("chamfer_distance: x_normals and y_normals go together (single_directional pairs nx_i with ny_j(i) too), got %s alone"
+                         % ("x_normals" if y_normals is None else "y_normals"))
+    if x_normals is not None:
+        res = _ChamferNormals.apply(X, Y, x_normals, y_normals, x_lengths, y_lengths, bool(squared), point_reduction, batch_reduction,
+                                    bool(single_directional), bool(return_nearest), bool(abs_cosine))
+        if not return_nearest:
+            return res
+        names = ("nearest_x", "dist_x", "normal_x") if single_directional else ("nearest_x", "dist_x", "normal_x", "nearest_y", "dist_y", "normal_y")
+        return res[0], res[1], dict(zip(names, res[2:]))
     res = _Chamfer.apply(X, Y, x_lengths, y_lengths, bool(squared), point_reduction, batch_reduction, bool(single_directional), bool(return_nearest))
     if not return_nearest:
         return res

@@ -1,0 +1,154 @@
+// chamfer_normals.cpp -- the device functions of the Chamfer kernels with the normal term (poseestimation_amd/csrc/so3_device.h:
+// add_s_pair, chamfer_length, chamfer_term, chamfer_cosine, chamfer_normal_term, chamfer_normal_psi, chamfer_normal_own, chamfer_hit,
+// chamfer_points_per_lane) compiled for the host (SO3_HOST_MODEL) and driven by loops that keep the kernels' order of operations, so
+// that tests/test_chamfer_normals_host.py measures the float32 arithmetic without a GPU.  TEST INFRASTRUCTURE ONLY.
+// Differences from the device: libm's correctly rounded 1 / sqrt stands in for v_rsq_f32 (1 ulp).  The forward's work items, lane
+// sums, butterfly, wave order and float64 chunk-order sums are tests/host_model/chamfer.cpp's, with a second sum for the term beside
+// the distance's (k_chamfer_normals_fwd, k_chamfer_normals_rows); the backward is one chain per normal: the own pair, then the hits in
+// ascending index (k_chamfer_normals_bwd).
+#define SO3_HOST_MODEL 1
+#include <stdint.h>
+
+#include <algorithm>
+#include <limits>
+
+#include "../../poseestimation_amd/csrc/so3_device.h"
+
+namespace {
+
+float wave_allsum(const float (&lane)[64]) {
+    float v[64], w[64];
+    for (int l = 0; l < 64; ++l) v[l] = lane[l];
+    for (int off = 1; off < 64; off <<= 1) {
+        for (int l = 0; l < 64; ++l) w[l] = v[l] + v[l ^ off];
+        for (int l = 0; l < 64; ++l) v[l] = w[l];
+    }
+    return v[0];
+}
+
+float item_sum(const float (&mine)[so3::kIcpBlock]) {
+    float v = 0.f;
+    for (int wv = 0; wv < so3::kIcpBlock / 64; ++wv) {
+        float lane[64];
+        for (int l = 0; l < 64; ++l) lane[l] = mine[wv * 64 + l];
+        const float tot = wave_allsum(lane);
+        v = wv == 0 ? tot : v + tot;
+    }
+    return v;
+}
+
+// one direction of one cloud: the points src[0 .. len_p) search tgt[0 .. len_q) and pair their normals own[i], other[j(i)];
+// sums[0], sums[1] = the float64 sums of the records (distance, normal term)
+template <bool SQUARED>
+void direction(const float *src, const float *tgt, const float *own, const float *other, int32_t full, int32_t len_p, int32_t len_q, float *dist,
+               int32_t *nearest, float *term, bool signed_cos, int u, double (&sums)[2]) {
+    const int per = so3::kIcpBlock * u, chunks = (full + per - 1) / per;
+    sums[0] = sums[1] = 0.0;
+    for (int c = 0; c < chunks; ++c) {
+        const int i_base = c * per;
+        const bool live = len_q > 0 && i_base < len_p;
+        float mine[so3::kIcpBlock], mine_n[so3::kIcpBlock];
+        for (int t = 0; t < so3::kIcpBlock; ++t) mine[t] = mine_n[t] = 0.f;
+        for (int uu = 0; uu < u; ++uu) {
+            for (int t = 0; t < so3::kIcpBlock; ++t) {
+                const int i = i_base + uu * so3::kIcpBlock + t;
+                const bool valid = live && i < len_p;
+                float best = 0.f, tn = 0.f;
+                int idx = 0;
+                if (valid) {
+                    best = std::numeric_limits<float>::infinity();
+                    for (int j = 0; j < len_q; ++j)
+                        so3::add_s_pair<true, false>(src[i * 3], src[i * 3 + 1], src[i * 3 + 2], tgt[j * 3], tgt[j * 3 + 1], tgt[j * 3 + 2], j, best, idx);
+                    const int j = std::min(std::max(idx, 0), len_q - 1);
+                    tn = so3::chamfer_normal_term(own[i * 3], own[i * 3 + 1], own[i * 3 + 2], other[j * 3], other[j * 3 + 1], other[j * 3 + 2], signed_cos);
+                }
+                const float e = valid ? so3::chamfer_term<SQUARED>(best) : 0.f;
+                mine[t] += e;
+                mine_n[t] += tn;
+                if (i < full) {
+                    if (dist != nullptr) dist[i] = e;
+                    if (nearest != nullptr) nearest[i] = valid ? std::min(idx, len_q - 1) : -1;
+                    if (term != nullptr) term[i] = tn;
+                }
+            }
+        }
+        sums[0] += static_cast<double>(item_sum(mine));
+        sums[1] += static_cast<double>(item_sum(mine_n));
+    }
+}
+
+// one direction of one cloud's gradient: P's normals own, Q's hit
+void gradient(const float *P, const float *Q, int32_t full, int32_t len_p, int32_t len_q, const int32_t *near_own, const int32_t *near_hit,
+              const float *s_own, const float *s_hit, bool signed_cos, float *out) {
+    const bool live_cloud = len_p > 0 && len_q > 0;
+    for (int i = 0; i < full; ++i) {
+        float acc[3] = {0.f, 0.f, 0.f};
+        const bool keep = live_cloud && i < len_p;
+        if (keep) {
+            float ux, uy, uz;
+            if (s_own != nullptr && near_own != nullptr) {
+                const int j = std::min(std::max(near_own[i], 0), len_q - 1);
+                so3::chamfer_normal_psi(P[i * 3], P[i * 3 + 1], P[i * 3 + 2], Q[j * 3], Q[j * 3 + 1], Q[j * 3 + 2], signed_cos, ux, uy, uz);
+                so3::chamfer_normal_own(*s_own, ux, uy, uz, acc);
+            }
+            if (s_hit != nullptr && near_hit != nullptr) {
+                for (int j = 0; j < len_q; ++j) {
+                    if (near_hit[j] != i) continue;
+                    so3::chamfer_normal_psi(P[i * 3], P[i * 3 + 1], P[i * 3 + 2], Q[j * 3], Q[j * 3 + 1], Q[j * 3 + 2], signed_cos, ux, uy, uz);
+                    so3::chamfer_hit(*s_hit, ux, uy, uz, acc);
+                }
+            }
+        }
+        for (int k = 0; k < 3; ++k) out[i * 3 + k] = keep ? acc[k] : 0.f;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+// so3_chamfer_normals_fwd_f32 on a device of `cus` compute units (flags: 1 unsquared, 2 single direction, 4 signed cosine);
+// u_override > 0 sets the points per lane instead of the launcher's rule
+void model_chamfer_normals_fwd(const float *X, const float *Y, const float *NX, const float *NY, const int32_t *x_len, const int32_t *y_len,
+                               float *dist_x, int32_t *nearest_x, float *dist_y, int32_t *nearest_y, float *term_x, float *term_y, float *rows,
+                               float *rows_n, uint32_t flags, int64_t B, int32_t N, int32_t M, int64_t cus, int32_t u_override) {
+    const bool squared = (flags & 1u) == 0, single = (flags & 2u) != 0, sc = (flags & 4u) != 0;
+    const int u = u_override > 0 ? u_override : so3::chamfer_points_per_lane(B, N, M, single, cus);
+    for (int64_t b = 0; b < B; ++b) {
+        const int32_t nb = so3::chamfer_length(x_len, b, N), mb = so3::chamfer_length(y_len, b, M);
+        const float *x = X + b * N * 3, *y = Y + b * M * 3, *nx = NX + b * N * 3, *ny = NY + b * M * 3;
+        float *dx = dist_x != nullptr ? dist_x + b * N : nullptr, *dy = dist_y != nullptr ? dist_y + b * M : nullptr;
+        float *tx = term_x != nullptr ? term_x + b * N : nullptr, *ty = term_y != nullptr ? term_y + b * M : nullptr;
+        int32_t *ix = nearest_x != nullptr ? nearest_x + b * N : nullptr, *iy = nearest_y != nullptr ? nearest_y + b * M : nullptr;
+        double sx[2], sy[2] = {0.0, 0.0};
+        if (squared) direction<true>(x, y, nx, ny, N, nb, mb, dx, ix, tx, sc, u, sx);
+        else direction<false>(x, y, nx, ny, N, nb, mb, dx, ix, tx, sc, u, sx);
+        if (!single) {
+            if (squared) direction<true>(y, x, ny, nx, M, mb, nb, dy, iy, ty, sc, u, sy);
+            else direction<false>(y, x, ny, nx, M, mb, nb, dy, iy, ty, sc, u, sy);
+        }
+        const bool live = nb > 0 && mb > 0;
+        for (int k = 0; k < 2; ++k) {
+            float *r = k == 0 ? rows : rows_n;
+            r[b * 2 + 0] = live ? static_cast<float>(sx[k] / static_cast<double>(nb)) : 0.f;
+            r[b * 2 + 1] = live && !single ? static_cast<float>(sy[k] / static_cast<double>(mb)) : 0.f;
+        }
+    }
+}
+
+// so3_chamfer_normals_bwd_f32 (scale_y and nearest_y NULL: the x direction alone)
+void model_chamfer_normals_bwd(const float *NX, const float *NY, const int32_t *x_len, const int32_t *y_len, const int32_t *nearest_x,
+                               const int32_t *nearest_y, const float *scale_x, const float *scale_y, float *dNX, float *dNY, uint32_t flags, int64_t B,
+                               int32_t N, int32_t M) {
+    const bool sc = (flags & 4u) != 0;
+    for (int64_t b = 0; b < B; ++b) {
+        const int32_t nb = so3::chamfer_length(x_len, b, N), mb = so3::chamfer_length(y_len, b, M);
+        const float *nx = NX + b * N * 3, *ny = NY + b * M * 3;
+        const int32_t *ix = nearest_x + b * N, *iy = nearest_y != nullptr ? nearest_y + b * M : nullptr;
+        const float *sx = scale_x + b, *sy = scale_y != nullptr ? scale_y + b : nullptr;
+        if (dNX != nullptr) gradient(nx, ny, N, nb, mb, ix, iy, sx, sy, sc, dNX + b * N * 3);
+        if (dNY != nullptr) gradient(ny, nx, M, mb, nb, iy, ix, sy, sx, sc, dNY + b * M * 3);
+    }
+}
+
+}  // extern "C"

@@ -1,0 +1,485 @@
+"""Chamfer's normal term on the GPU: G31 through the Python surface and through the raw C ABI with the checks and bounds of
+tests/test_chamfer_normals_host.py (4 x the float32 host model's figures; see its docstring), every work-item size of
+k_chamfer_normals_fwd and the scan's block edges on fresh input against float64 through the returned indices, the bit-equalities with the
+call without normals (nearest, dist, rows; loss, dX, dY through the surface), every reduction, the autograd surface, repeatability,
+replay from a graph, and the speed condition against the torch spelling."""
+import ctypes
+import itertools
+
+import numpy as np
+import pytest
+import torch
+
+import chamfer_ref as cref
+import chamfer_normals_ref as ref
+import test_chamfer_normals_host as host
+
+pytestmark = pytest.mark.gpu
+GUARD = 64                          # elements in front of and behind every raw buffer
+KERNELS = []                        # abi_run: the k_chamfer_normals_fwd instantiation of every checked forward call, in call order
+
+
+@pytest.fixture(scope="module")
+def dev():
+    from poseestimation_amd import _lib
+    _lib.load()
+    assert torch.cuda.is_available()
+    return torch.device("cuda:0")
+
+
+@pytest.fixture(scope="module")
+def g31_cases():
+    return ref.cases(ref.g31())
+
+
+def _d(a, dev, dtype=np.float32):
+    return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
+
+
+def _ptr(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _folded(g, lengths, full):
+    """The float32 scales the surface folds from a per-cloud upstream gradient under point_reduction="mean"."""
+    return g * np.float32(1.0 / full) if lengths is None else g / np.maximum(np.clip(lengths, 0, full), 1).astype(np.float32)
+
+
+def surface_run(c, dev, signed, single=False, squared=True):
+    """Forward and backward through chamfer_distance with normals: per-cloud losses (batch_reduction=None), ref.scales' first vector as
+    the upstream gradient of loss and its second of loss_normals; and the same call without normals under "plain"."""
+    import poseestimation_amd as pa
+    b, n, m = c["b"], c["n"], c["m"]
+    xl, yl = _d(c["x_lengths"], dev, np.int64), _d(c["y_lengths"], dev, np.int64)
+    g, gn = ref.scales(b)
+    kw = dict(squared=squared, batch_reduction=None, single_directional=single, return_nearest=True)
+    X, Y, NX, NY = (_d(c[k], dev).requires_grad_() for k in ("X", "Y", "NX", "NY"))
+    loss, loss_n, info = pa.chamfer_distance(X, Y, xl, yl, x_normals=NX, y_normals=NY, abs_cosine=not signed, **kw)
+    assert loss.shape == loss_n.shape == (b,) and loss_n.dtype == torch.float32 and info["normal_x"].shape == (b, n)
+    sides = ("x",) if single else ("x", "y")
+    assert set(info) == {k + s for s in sides for k in ("nearest_", "dist_", "normal_")}
+    torch.autograd.backward((loss, loss_n), (_d(g, dev), _d(gn, dev)))
+    got = {k.replace("normal_", "term_"): v.cpu().numpy() for k, v in info.items()}
+    got.update(loss=loss.detach().cpu().numpy(), loss_n=loss_n.detach().cpu().numpy(), dX=X.grad.cpu().numpy(), dY=Y.grad.cpu().numpy(),
+               dNX=NX.grad.cpu().numpy(), dNY=NY.grad.cpu().numpy(), scale_x=_folded(gn, c["x_lengths"], n), scale_y=_folded(gn, c["y_lengths"], m))
+    X2, Y2 = _d(c["X"], dev).requires_grad_(), _d(c["Y"], dev).requires_grad_()
+    loss2, info2 = pa.chamfer_distance(X2, Y2, xl, yl, **kw)
+    loss2.backward(_d(g, dev))
+    got["plain"] = {k: v.cpu().numpy() for k, v in info2.items()}
+    got["plain"].update(loss=loss2.detach().cpu().numpy(), dX=X2.grad.cpu().numpy(), dY=Y2.grad.cpu().numpy())
+    return got
+
+
+def _guarded(shape, fill, dtype, dev):
+    count = int(np.prod(shape))
+    whole = torch.full((count + 2 * GUARD,), fill, dtype=dtype, device=dev)
+    return whole, whole[GUARD:GUARD + count].view(shape)
+
+
+def _guards_intact(whole, fill):
+    edge = torch.cat([whole[:GUARD], whole[-GUARD:]])
+    return bool(torch.isnan(edge).all()) if isinstance(fill, float) and np.isnan(fill) else bool((edge == fill).all())
+
+
+def abi_run(c, dev, signed, single=False, squared=True):
+    """One case through the raw C ABI into NaN / -2 pre-filled, guarded device buffers and a NaN workspace (nothing needs a zero-fill),
+    then with every optional output NULL and each gradient alone; "plain": so3_chamfer_fwd_f32 on the same input."""
+    from poseestimation_amd import _lib
+    lib = _lib.load()
+    b, n, m = c["b"], c["n"], c["m"]
+    X, Y, NX, NY = (_d(c[k], dev) for k in ("X", "Y", "NX", "NY"))
+    xl, yl = _d(c["x_lengths"], dev, np.int32), _d(c["y_lengths"], dev, np.int32)
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    flags = (0 if squared else host.UNSQUARED) | (host.SINGLE if single else 0) | (host.SIGNED if signed else 0)
+    spec = {"dist_x": ((b, n), np.nan, torch.float32), "nearest_x": ((b, n), -2, torch.int32), "term_x": ((b, n), np.nan, torch.float32),
+            "rows": ((b, 2), np.nan, torch.float32), "rows_n": ((b, 2), np.nan, torch.float32),
+            "dNX": ((b, n, 3), np.nan, torch.float32), "dNY": ((b, m, 3), np.nan, torch.float32)}
+    if not single:
+        spec.update(dist_y=((b, m), np.nan, torch.float32), nearest_y=((b, m), -2, torch.int32), term_y=((b, m), np.nan, torch.float32))
+    whole, out = {}, {}
+    for k, (shape, fill, dtype) in spec.items():
+        whole[k], out[k] = _guarded(shape, fill, dtype, dev)
+    words = lib.so3_chamfer_normals_workspace_bytes(b, n, m) // 4
+    work_whole, work = _guarded((words,), np.nan, torch.float32, dev)
+    sx, sy = ref.scales(b)
+    sxd, syd = _d(sx, dev), (None if single else _d(sy, dev))
+
+    def fwd(**o):
+        _lib.check(lib.so3_chamfer_normals_fwd_f32(_ptr(X), _ptr(Y), _ptr(NX), _ptr(NY), _ptr(xl), _ptr(yl), _ptr(o.get("dist_x")), _ptr(o.get("nearest_x")),
+                                                   _ptr(o.get("dist_y")), _ptr(o.get("nearest_y")), _ptr(o.get("term_x")), _ptr(o.get("term_y")),
+                                                   _ptr(o["rows"]), _ptr(o["rows_n"]), _ptr(work), flags, b, n, m, st), "so3_chamfer_normals_fwd_f32")
+
+    def bwd(dnx, dny):
+        _lib.check(lib.so3_chamfer_normals_bwd_f32(_ptr(NX), _ptr(NY), _ptr(xl), _ptr(yl), _ptr(out["nearest_x"]), _ptr(out.get("nearest_y")), _ptr(sxd),
+                                                   _ptr(syd), _ptr(dnx), _ptr(dny), flags, b, n, m, st), "so3_chamfer_normals_bwd_f32")
+
+    fwd(**out)
+    KERNELS.append(lib.so3_last_kernel().decode())
+    bwd(out["dNX"], out["dNY"])
+    assert lib.so3_last_kernel().decode() == "k_chamfer_normals_bwd"
+    for leave in [k for k in spec if k.split("_")[0] in ("dist", "nearest", "term")] + [None]:    # each optional output left out, then all
+        o = {k: torch.full(s[0], s[1], dtype=s[2], device=dev) for k, s in spec.items()
+             if k in ("rows", "rows_n") or (leave is not None and k != leave and k.split("_")[0] in ("dist", "nearest", "term"))}
+        fwd(**o)
+        assert all(torch.equal(v, out[k]) for k, v in o.items()), leave
+    for only in ("dNX", "dNY"):                                                                  # each gradient alone
+        alone = torch.full(spec[only][0], np.nan, device=dev)
+        bwd(alone if only == "dNX" else None, alone if only == "dNY" else None)
+        assert torch.equal(alone, out[only])
+    plain = {k: torch.full(s[0], s[1], dtype=s[2], device=dev) for k, s in spec.items() if k.split("_")[0] in ("dist", "nearest", "rows") and k != "rows_n"}
+    _lib.check(lib.so3_chamfer_fwd_f32(_ptr(X), _ptr(Y), _ptr(xl), _ptr(yl), _ptr(plain["dist_x"]), _ptr(plain["nearest_x"]), _ptr(plain.get("dist_y")),
+                                       _ptr(plain.get("nearest_y")), _ptr(plain["rows"]), _ptr(work), flags & ~host.SIGNED, b, n, m, st),
+               "so3_chamfer_fwd_f32")
+    assert lib.so3_last_kernel().decode() == KERNELS[-1].replace("k_chamfer_normals_fwd", "k_chamfer_fwd")
+    torch.cuda.synchronize()
+    for k, (shape, fill, dtype) in spec.items():
+        assert _guards_intact(whole[k], fill), k
+    assert _guards_intact(work_whole, np.nan)
+    got = {k: v.cpu().numpy() for k, v in out.items()}
+    got["plain"] = {k: v.cpu().numpy() for k, v in plain.items()}
+    return got
+
+
+# ---- G31 ------------------------------------------------------------------------------------------------------------------------
+def test_g31_through_the_python_surface(dev, g31_cases):
+    host.check_against_g31(g31_cases, lambda c, s: surface_run(c, dev, s), "surface", bnd=dict(host.bounds(), grad=host.FOLDED_GRAD_TOL))
+
+
+def test_g31_through_the_c_abi(dev, g31_cases):
+    host.check_against_g31(g31_cases, lambda c, s: abi_run(c, dev, s), "abi")
+
+
+def test_g31_single_direction_and_unsquared(dev, g31_cases):
+    picked = [c for c in g31_cases if c["geometry"] in ("random_257x1025", "subset_100x300")]
+    host.check_against_g31(picked, lambda c, s: abi_run(c, dev, s, single=True), "abi single", single=True)
+    host.check_against_g31(picked, lambda c, s: surface_run(c, dev, s, single=True), "surface single", single=True,
+                           bnd=dict(host.bounds(), grad=host.FOLDED_GRAD_TOL))
+    host.check_against_g31(picked[:2], lambda c, s: abi_run(c, dev, s, squared=False), "abi l2")
+    assert KERNELS[-1].startswith("k_chamfer_normals_fwd<false, ")
+
+
+# ---- every work split, the scan's block edges -----------------------------------------------------------------------------------
+def _rule(b, n, m, cus):
+    u = 4
+    while u > 1 and b * ((n + 256 * u - 1) // (256 * u) + (m + 256 * u - 1) // (256 * u)) < 2 * cus:
+        u >>= 1
+    return u
+
+
+def _balls(rng, b, n):
+    d = rng.standard_normal((b, n, 3))
+    return (d / np.linalg.norm(d, axis=-1, keepdims=True) * rng.uniform(0, 1, (b, n, 1)) ** (1 / 3)).astype(np.float32)
+
+
+def _normals(rng, b, n):
+    return ref._random_normals(rng, b * n).reshape(b, n, 3)
+
+
+def fresh_case(b, n, m, ragged):
+    """Fresh clouds of unit radius with random normals (G31's random family), the cosine condition enforced through the float64 search
+    where that is cheap (B N M <= 2^22); larger cases run the signed flavour alone, which has no sign to get wrong."""
+    rng = np.random.default_rng(31000 + 97 * b + 7 * n + m)
+    c = {"name": "fresh %dx%dx%d" % (b, n, m), "family": "fresh", "b": b, "n": n, "m": m, "x_lengths": None, "y_lengths": None,
+         "X": _balls(rng, b, n), "Y": _balls(rng, b, m), "NX": _normals(rng, b, n), "NY": _normals(rng, b, m)}
+    if ragged:
+        c["x_lengths"], c["y_lengths"] = rng.integers(0, n + 1, b), rng.integers(0, m + 1, b)
+        c["x_lengths"][0], c["y_lengths"][0] = n, m
+    c["conditioned"] = b <= 64 and b * n * m <= 1 << 22
+    if c["conditioned"]:
+        f = cref.chamfer64(c["X"], c["Y"], c["x_lengths"], c["y_lengths"])
+        while True:
+            bad = ref.small_cosines(c["NX"], c["NY"], c["x_lengths"], c["y_lengths"], f["nearest_x"], f["nearest_y"])
+            if not bad:
+                break
+            for side, k, i in bad:
+                c["NX" if side == "x" else "NY"][k, i] = ref._random_normals(rng, 1)[0]
+    return c
+
+
+def _clouds(c, got, keep):
+    """The clouds `keep` of a case and of its results."""
+    sub = lambda a: a[keep] if isinstance(a, np.ndarray) and a.ndim >= 1 and len(a) == c["b"] else a
+    return dict({k: sub(v) for k, v in c.items()}, b=len(keep)), {k: sub(v) for k, v in got.items() if k != "plain"}
+
+
+def fresh_check(c, dev, label):
+    """Through the raw C ABI: what the call without normals also produces, bit for bit over the whole batch; the figures over at most
+    66 clouds of it (every (B // 64)-th and the last)."""
+    sx, sy = ref.scales(c["b"])
+    for signed in (False, True) if c["conditioned"] else (True,):
+        got = abi_run(c, dev, signed)
+        assert all(host.same_bits(got[k], v) for k, v in got["plain"].items()), (label, signed)
+        keep = np.union1d(np.arange(0, c["b"], max(c["b"] // 64, 1)), [c["b"] - 1])
+        sub_c, sub_got = _clouds(c, got, keep)
+        sub_got.update(scale_x=sx[keep], scale_y=sy[keep])
+        f = host.case_figures(sub_c, sub_got, signed)
+        print(label, KERNELS[-1], "signed" if signed else "abs", "%d clouds judged" % len(keep), "  ".join("%s %.2e" % kv for kv in f.items()))
+        for k, v in f.items():
+            assert v <= host.bounds()[k], (label, signed, k, v)
+    return KERNELS[-1]
+
+
+SPLITS = [(b, n, m) for b in (1, 3) for n, m in ref.SIZES + [(1025, 1023)]] + [(1, 511, 513), (1, 512, 512), (1, 513, 511)]
+
+
+@pytest.mark.parametrize("b,n,m", SPLITS, ids=lambda v: str(v))
+def test_work_splits_and_scan_edges_against_float64(dev, b, n, m):
+    """B = 1 and 3 at the fixture's sizes and (1025, 1023), and N, M around the scan's 512 entries in flight: ragged on every second."""
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    kernel = fresh_check(fresh_case(b, n, m, ragged=SPLITS.index((b, n, m)) % 2 == 1), dev, "split B=%d N=%d M=%d" % (b, n, m))
+    assert kernel == "k_chamfer_normals_fwd<true, %d>" % _rule(b, n, m, cus)
+
+
+def test_two_and_four_points_per_lane_and_a_batch_above_the_grid_cap(dev):
+    """The smallest batches whose rule gives U = 2 and U = 4 at (513, 513) and (1025, 1023), then more work items than the grid holds
+    (64 workgroups per compute unit) at N = M = 12, U = 4: the three instantiations by name, k_chamfer_normals_bwd by name in abi_run."""
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    for u, (n, m) in ((2, (513, 513)), (4, (1025, 1023))):
+        b = next(b for b in range(1, 8 * cus) if _rule(b, n, m, cus) == u)
+        assert fresh_check(fresh_case(b, n, m, ragged=True), dev, "U = %d B=%d N=%d M=%d" % (u, b, n, m)) == "k_chamfer_normals_fwd<true, %d>" % u
+    b = cus * 32 + 1
+    assert b * 2 > cus * 64
+    assert fresh_check(fresh_case(b, 12, 12, ragged=True), dev, "above the cap B=%d" % b) == "k_chamfer_normals_fwd<true, 4>"
+    assert {"k_chamfer_normals_fwd<true, %d>" % u for u in (1, 2, 4)} <= set(KERNELS) or cus != 256
+
+
+# ---- reductions and the autograd surface -------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def small():
+    c = fresh_case(3, 257, 130, ragged=False)
+    c["x_lengths"], c["y_lengths"] = np.array([257, 100, 31]), np.array([64, 130, 1])
+    f = cref.chamfer64(c["X"], c["Y"], c["x_lengths"], c["y_lengths"])
+    assert ref.small_cosines(c["NX"], c["NY"], c["x_lengths"], c["y_lengths"], f["nearest_x"], f["nearest_y"]) == []
+    return c
+
+
+def test_every_reduction_against_float64(dev, small):
+    """point_reduction x batch_reduction x single x abs_cosine (x ragged).  The bound on loss_normals is counted: a row's ROWS_N_TOL
+    times the length "sum" multiplies it by, plus four roundings relative to the magnitudes added (the product, the sum of the two
+    directions, B - 1 = 2 for the batch) -- tests/test_chamfer_host.py's REDUCTION_TOL in absolute terms."""
+    import poseestimation_amd as pa
+    c, b, n, m = small, small["b"], small["n"], small["m"]
+    gvec = np.array([0.5, -2.0, 1.25])
+    for pr, br, single, signed, ragged in itertools.product(("mean", "sum"), ("mean", "sum", None), (False, True), (False, True), (True, False)):
+        lx, ly = (c["x_lengths"], c["y_lengths"]) if ragged else (None, None)
+        NX, NY = _d(c["NX"], dev).requires_grad_(), _d(c["NY"], dev).requires_grad_()
+        _, loss_n, info = pa.chamfer_distance(_d(c["X"], dev), _d(c["Y"], dev), _d(lx, dev, np.int64), _d(ly, dev, np.int64), point_reduction=pr,
+                                              batch_reduction=br, single_directional=single, return_nearest=True, x_normals=NX, y_normals=NY,
+                                              abs_cosine=not signed)
+        g = gvec if br is None else 0.75
+        loss_n.backward(_d(g, dev) if br is None else torch.tensor(g, device=dev))
+        near_x, near_y = info["nearest_x"].cpu().numpy(), None if single else info["nearest_y"].cpu().numpy()
+        a, cc = cref.fold_scales(g, b, n, m, lx, ly, pr, br)
+        w = ref.normals64(c["NX"], c["NY"], lx, ly, near_x, near_y, signed, a, None if single else cc)
+        per = (w["rows_n"] if pr == "mean" else w["sums_n"])
+        lens = np.stack([ref.lengths_of(lx, b, n), ref.lengths_of(ly, b, m)], 1) if pr == "sum" else np.ones((b, 2))
+        lens = lens[:, :1] if single else lens
+        agg = (lambda v: v.mean()) if br == "mean" else ((lambda v: v.sum()) if br == "sum" else (lambda v: v))
+        want = agg(per.sum(1))
+        tol = agg(lens.sum(1) * host.ROWS_N_TOL + 4 * 2.0 ** -24 * np.abs(per).sum(1))
+        err = np.abs(loss_n.detach().cpu().numpy() - want)
+        grad = max(cref._relative(NX.grad.cpu().numpy(), w["dNX"], np.broadcast_to(w["SX"], w["dNX"].shape)),
+                   cref._relative(NY.grad.cpu().numpy(), w["dNY"], np.broadcast_to(w["SY"], w["dNY"].shape)))
+        print("reduction %-4s %-4s single=%d signed=%d ragged=%d  loss_n err %.2e (bound %.2e)  grad %.2e" % (pr, br, single, signed, ragged, np.max(err), np.min(tol), grad))
+        assert loss_n.shape == (() if br is not None else (b,))
+        assert (err <= tol).all() and grad <= host.FOLDED_GRAD_TOL, (pr, br, single, signed, ragged, err, tol, grad)
+
+
+def test_autograd_surface(dev, small):
+    import poseestimation_amd as pa
+    c = small
+    X0, Y0, NX0, NY0 = (_d(c[k], dev) for k in ("X", "Y", "NX", "NY"))
+
+    def leaves(*names):
+        return [t.clone().requires_grad_() if k in names else t for k, t in zip("X Y NX NY".split(), (X0, Y0, NX0, NY0))]
+
+    def call(ts, **kw):
+        return pa.chamfer_distance(ts[0], ts[1], x_normals=ts[2], y_normals=ts[3], **kw)
+
+    # the call without normals: the same loss and cloud gradients, bit for bit
+    Xp, Yp = X0.clone().requires_grad_(), Y0.clone().requires_grad_()
+    plain = pa.chamfer_distance(Xp, Yp)
+    plain.backward()
+    # loss_normals alone: the clouds get no gradient and the distance's backward is not launched
+    ts = leaves("X", "Y", "NX", "NY")
+    loss, loss_n = call(ts)
+    assert torch.equal(loss, plain.detach()) and loss.requires_grad and loss_n.requires_grad
+    loss_n.backward()
+    assert ts[0].grad is None and ts[1].grad is None and ts[2].grad.abs().sum() > 0 and ts[3].grad.abs().sum() > 0
+    alone = (ts[2].grad, ts[3].grad)
+    # loss alone: the normals get none
+    ts = leaves("X", "Y", "NX", "NY")
+    call(ts)[0].backward()
+    assert ts[2].grad is None and ts[3].grad is None and torch.equal(ts[0].grad, Xp.grad) and torch.equal(ts[1].grad, Yp.grad)
+    # loss + w loss_normals: each part as on its own (w = 2: exact in the folded scales)
+    ts = leaves("X", "Y", "NX", "NY")
+    loss, loss_n = call(ts)
+    (loss + 2.0 * loss_n).backward()
+    assert torch.equal(ts[0].grad, Xp.grad) and torch.equal(ts[1].grad, Yp.grad)
+    assert torch.equal(ts[2].grad, 2.0 * alone[0]) and torch.equal(ts[3].grad, 2.0 * alone[1])
+    # the normals alone require grad; one of them alone; none
+    ts = leaves("NX", "NY")
+    loss, loss_n = call(ts)
+    loss_n.backward()
+    assert torch.equal(ts[2].grad, alone[0]) and torch.equal(ts[3].grad, alone[1])
+    ts = leaves("NY")
+    call(ts)[1].backward()
+    assert torch.equal(ts[3].grad, alone[1])
+    assert not any(t.requires_grad for t in call(leaves()))
+    # a strided per-cloud upstream gradient equals its contiguous copy
+    g = torch.arange(1, 7, device=dev, dtype=torch.float32)[::2]
+    grads = []
+    for up in (g, g.contiguous()):
+        ts = leaves("NX", "NY")
+        call(ts, batch_reduction=None)[1].backward(up)
+        grads.append((ts[2].grad, ts[3].grad))
+    assert torch.equal(grads[0][0], grads[1][0]) and torch.equal(grads[0][1], grads[1][1])
+    # float64 normals: float32 arithmetic on their float32 values, gradients in float64; bfloat16 likewise
+    nxd = NX0.double().requires_grad_()
+    out = pa.chamfer_distance(X0, Y0, x_normals=nxd, y_normals=NY0)
+    out[1].backward()
+    assert nxd.grad.dtype == torch.float64 and torch.equal(nxd.grad.float(), alone[0]) and out[1].dtype == torch.float32
+    nxb, nyb = NX0.bfloat16().requires_grad_(), NY0.bfloat16().requires_grad_()
+    lb = pa.chamfer_distance(X0, Y0, x_normals=nxb, y_normals=nyb)[1]
+    lb.backward()
+    ts = [X0, Y0, NX0.bfloat16().float().requires_grad_(), NY0.bfloat16().float().requires_grad_()]
+    lf = call(ts)[1]
+    lf.backward()
+    assert nxb.grad.dtype == torch.bfloat16 and torch.equal(lb, lf) and torch.equal(nxb.grad, ts[2].grad.bfloat16()) and torch.equal(nyb.grad, ts[3].grad.bfloat16())
+    # double backward is refused
+    ts = leaves("NX")
+    (gx,) = torch.autograd.grad(call(ts)[1], ts[2], create_graph=True)
+    assert not gx.requires_grad
+    w = torch.ones((), device=dev, requires_grad=True)
+    with pytest.raises(RuntimeError, match="double backward"):
+        torch.autograd.grad(call(ts)[1] * w, ts[2], create_graph=True)[0].sum().backward()
+    # bad shapes and dtypes, one normal alone
+    for bad in ((NX0[0], NY0), (NX0, NY0[:, :5]), (NX0[:, :5], NY0), (NY0, NX0), (NX0[..., :2], NY0), (NX0.long(), NY0)):
+        with pytest.raises(RuntimeError, match="chamfer_distance: expected floating-point x_normals of X's shape"):
+            pa.chamfer_distance(X0, Y0, x_normals=bad[0], y_normals=bad[1])
+    with pytest.raises(RuntimeError, match="HIP device only"):
+        pa.chamfer_distance(X0, Y0, x_normals=NX0.cpu(), y_normals=NY0)
+    with pytest.raises(ValueError, match="go together"):
+        pa.chamfer_distance(X0, Y0, x_normals=NX0, single_directional=True)
+
+
+# ---- repeatability --------------------------------------------------------------------------------------------------------------
+def _run(pa, c, dev, NX0, NY0, xl, yl, order=None):
+    o = slice(None) if order is None else order
+    X, Y = _d(c["X"], dev)[o], _d(c["Y"], dev)[o]
+    NX, NY = NX0[o].clone().requires_grad_(), NY0[o].clone().requires_grad_()
+    _, loss_n, info = pa.chamfer_distance(X, Y, xl[o], yl[o], batch_reduction=None, return_nearest=True, x_normals=NX, y_normals=NY)
+    loss_n.backward(torch.linspace(0.5, 2.0, len(X), device=dev)[o])
+    return loss_n.detach(), info["normal_x"], info["normal_y"], NX.grad, NY.grad
+
+
+def test_same_bits_from_call_to_call_in_any_batch_order_and_beside_a_nan_cloud(dev):
+    import poseestimation_amd as pa
+    c = fresh_case(5, 700, 1300, ragged=False)
+    c["Y"][:, :40] = c["X"][:, 5:6]                               # forty points of Y share their nearest x: a chain
+    NX0, NY0 = _d(c["NX"], dev), _d(c["NY"], dev)
+    xl, yl = torch.tensor([700, 650, 1, 700, 333], device=dev), torch.tensor([1300, 64, 1300, 1025, 777], device=dev)
+    first = _run(pa, c, dev, NX0, NY0, xl, yl)
+    again = _run(pa, c, dev, NX0, NY0, xl, yl)
+    assert all(torch.equal(a, b) for a, b in zip(first, again))
+    flipped = _run(pa, c, dev, NX0, NY0, xl, yl, order=torch.arange(4, -1, -1, device=dev))
+    assert all(torch.equal(a.flip(0), b) for a, b in zip(flipped, first))
+    NXn, NYn = NX0.clone(), NY0.clone()                           # NaN normals in one cloud change no other cloud
+    NXn[1] = float("nan")
+    NYn[1, 3] = float("inf")
+    poisoned = _run(pa, c, dev, NXn, NYn, xl, yl)
+    keep = [0, 2, 3, 4]
+    assert all(torch.equal(a[keep], b[keep]) for a, b in zip(first, poisoned))
+    assert all(torch.isfinite(t).all() for t in poisoned) and poisoned[1][1, :650].eq(1).all() and poisoned[3][1].eq(0).all()
+
+
+def test_replay_from_a_captured_graph(dev):
+    import poseestimation_amd as pa
+    c = fresh_case(3, 300, 520, ragged=False)
+    xl, yl = torch.tensor([300, 17, 256], device=dev, dtype=torch.int32), torch.tensor([520, 500, 3], device=dev, dtype=torch.int32)
+    X, Y = _d(c["X"], dev).requires_grad_(), _d(c["Y"], dev).requires_grad_()
+    NX0 = _d(c["NX"], dev)
+    NX, NY = NX0.clone().requires_grad_(), _d(c["NY"], dev).requires_grad_()
+
+    def step():
+        loss, loss_n = pa.chamfer_distance(X, Y, xl, yl, point_reduction="sum", x_normals=NX, y_normals=NY, abs_cosine=False)
+        return (loss.detach(), loss_n.detach()) + torch.autograd.grad(loss + 0.5 * loss_n, (X, Y, NX, NY))
+
+    eager = step()
+    stream = torch.cuda.Stream()
+    stream.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(stream):
+        step()                                                       # warm up on the side stream
+    torch.cuda.current_stream().wait_stream(stream)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        captured = step()
+    for t in captured:
+        t.zero_()
+    graph.replay()
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(eager, captured))
+    with torch.no_grad():                                            # new inputs in place: the replay follows them
+        NX.copy_(NX0.flip(1))
+        X.copy_(X.detach().flip(1))
+    graph.replay()
+    torch.cuda.synchronize()
+    fresh = step()
+    assert all(torch.equal(a, b) for a, b in zip(fresh, captured))
+
+
+# ---- speed ----------------------------------------------------------------------------------------------------------------------
+def test_chamfer_with_normals_is_not_slower_than_the_torch_spelling(dev):
+    """B = 16, N = M = 2048, forward plus backward with normals, HIP events, 5 warm-ups, median of 20: chamfer_distance against the torch
+    spelling on the same device in the same process -- the pairwise (B,N,M) differences, argmin both ways, gathers, cosine_similarity,
+    means, with autograd."""
+    import poseestimation_amd as pa
+    from conftest import REPORT_LINES
+    c = fresh_case(16, 2048, 2048, ragged=False)
+    X, Y, NX, NY = (_d(c[k], dev).requires_grad_() for k in ("X", "Y", "NX", "NY"))
+
+    def torch_spelling(X, Y, NX, NY):
+        with torch.no_grad():
+            d2 = ((X[:, :, None, :] - Y[:, None, :, :]) ** 2).sum(-1)
+            j, i = d2.argmin(2)[..., None].expand(-1, -1, 3), d2.argmin(1)[..., None].expand(-1, -1, 3)
+        ex = ((X - Y.gather(1, j)) ** 2).sum(-1).mean(1)
+        ey = ((Y - X.gather(1, i)) ** 2).sum(-1).mean(1)
+        tx = 1 - torch.nn.functional.cosine_similarity(NX, NY.gather(1, j), dim=2, eps=1e-6).abs()
+        ty = 1 - torch.nn.functional.cosine_similarity(NY, NX.gather(1, i), dim=2, eps=1e-6).abs()
+        return (ex + ey).mean(), (tx.mean(1) + ty.mean(1)).mean()
+
+    def ours_fn(X, Y, NX, NY):
+        return pa.chamfer_distance(X, Y, x_normals=NX, y_normals=NY)
+
+    def both(fn):
+        X.grad = Y.grad = NX.grad = NY.grad = None
+        loss, loss_n = fn(X, Y, NX, NY)
+        (loss + loss_n).backward()
+
+    def median_ms(fn):
+        for _ in range(5):
+            fn()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(20):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            times.append(e0.elapsed_time(e1))
+        return float(np.median(times))
+
+    ours = median_ms(lambda: both(ours_fn))
+    theirs = median_ms(lambda: both(torch_spelling))
+    with torch.no_grad():                                # judged, as everywhere, against float64 through the RETURNED indices
+        _, got, info = pa.chamfer_distance(X, Y, x_normals=NX, y_normals=NY, return_nearest=True)
+        want = ref.normals64(c["NX"], c["NY"], None, None, info["nearest_x"].cpu().numpy(), info["nearest_y"].cpu().numpy())["rows_n"].sum(1).mean()
+    line = "chamfer with normals B=16 N=M=2048 fwd+bwd: chamfer_distance %.4f ms, torch pairwise/argmin/gather/cosine/mean %.4f ms (x%.1f)" % (
+        ours, theirs, theirs / ours)
+    print(line)
+    REPORT_LINES.append(line)
+    # a cloud's two rows, their sum below 4 rounded once (LOSS_N_TOL); the batch mean adds B - 1 = 15 roundings of partial sums below 64
+    # (half an ulp: 2^-19), divided by B with the rest, and one more rounding of the quotient, below 4
+    assert abs(got.item() - want) <= host.LOSS_N_TOL + 15 * 2.0 ** -19 / 16 + 2.0 ** -23, (got.item(), want)
+    assert theirs / ours >= 1.0, line

@@ -225,7 +225,35 @@ def main():
            lambda i: lib.so3_chamfer_fwd_f32(p(xi), p(yi), None, None, None, p(nni), None, p(nyi), p(rwi), p(wci), 0, bi, ni, ni, st), bi * ni * 32, iters=10, warm=2)
     timeit("so3_chamfer_bwd_f32 (256 x 1024 x 1024, dX + dY)",
            lambda i: lib.so3_chamfer_bwd_f32(p(xi), p(yi), None, None, p(nni), p(nyi), p(sci), p(sci), p(gxi), p(gyi), 0, bi, ni, ni, st), bi * ni * 56, iters=10, warm=2)
-    del xi, yi, di, nni, ri, ti, wsi, dyi, nyi, rwi, sci, gxi, gyi, wci
+    # the same with the normal term (profiles/chamfer_normals_bench.txt): the forward adds two 12-byte loads and the cosine per point behind
+    # the search, the backward is the same gather over the normals; then all four entries at the speed condition's shape
+    nxi, nni_y = torch.randn(bi, ni, 3, device=dev), torch.randn(bi, ni, 3, device=dev)
+    rni, wni = torch.empty(bi, 2, device=dev), torch.empty(lib.so3_chamfer_normals_workspace_bytes(bi, ni, ni) // 4, device=dev)
+    timeit("so3_chamfer_normals_fwd_f32 (256 x 1024 x 1024, rows + nearest)",
+           lambda i: lib.so3_chamfer_normals_fwd_f32(p(xi), p(yi), p(nxi), p(nni_y), None, None, None, p(nni), None, p(nyi), None, None, p(rwi), p(rni), p(wni),
+                                                     0, bi, ni, ni, st), bi * ni * 56, iters=10, warm=2)
+    timeit("so3_chamfer_normals_bwd_f32 (256 x 1024 x 1024, dNX + dNY)",
+           lambda i: lib.so3_chamfer_normals_bwd_f32(p(nxi), p(nni_y), None, None, p(nni), p(nyi), p(sci), p(sci), p(gxi), p(gyi), 0, bi, ni, ni, st),
+           bi * ni * 56, iters=10, warm=2)
+    del xi, yi, di, nni, ri, ti, wsi, dyi, nyi, rwi, sci, gxi, gyi, wci, nxi, nni_y, rni, wni
+    bs, ns = 16, 2048
+    xs, ys = torch.rand(bs, ns, 3, device=dev), torch.rand(bs, ns, 3, device=dev)
+    nxs, nys = torch.randn(bs, ns, 3, device=dev), torch.randn(bs, ns, 3, device=dev)
+    ixs, iys = torch.empty(bs, ns, dtype=torch.int32, device=dev), torch.empty(bs, ns, dtype=torch.int32, device=dev)
+    rws, rns, scs = torch.empty(bs, 2, device=dev), torch.empty(bs, 2, device=dev), torch.full((bs,), 1.0 / ns, device=dev)
+    gxs, gys = torch.empty(bs, ns, 3, device=dev), torch.empty(bs, ns, 3, device=dev)
+    wss = torch.empty(lib.so3_chamfer_normals_workspace_bytes(bs, ns, ns) // 4, device=dev)
+    timeit("so3_chamfer_fwd_f32 (16 x 2048 x 2048, rows + nearest)",
+           lambda i: lib.so3_chamfer_fwd_f32(p(xs), p(ys), None, None, None, p(ixs), None, p(iys), p(rws), p(wss), 0, bs, ns, ns, st), bs * ns * 32, iters=10, warm=2)
+    timeit("so3_chamfer_normals_fwd_f32 (16 x 2048 x 2048, rows + nearest)",
+           lambda i: lib.so3_chamfer_normals_fwd_f32(p(xs), p(ys), p(nxs), p(nys), None, None, None, p(ixs), None, p(iys), None, None, p(rws), p(rns), p(wss),
+                                                     0, bs, ns, ns, st), bs * ns * 56, iters=10, warm=2)
+    timeit("so3_chamfer_bwd_f32 (16 x 2048 x 2048, dX + dY)",
+           lambda i: lib.so3_chamfer_bwd_f32(p(xs), p(ys), None, None, p(ixs), p(iys), p(scs), p(scs), p(gxs), p(gys), 0, bs, ns, ns, st), bs * ns * 56, iters=10, warm=2)
+    timeit("so3_chamfer_normals_bwd_f32 (16 x 2048 x 2048, dNX + dNY)",
+           lambda i: lib.so3_chamfer_normals_bwd_f32(p(nxs), p(nys), None, None, p(ixs), p(iys), p(scs), p(scs), p(gxs), p(gys), 0, bs, ns, ns, st),
+           bs * ns * 56, iters=10, warm=2)
+    del xs, ys, nxs, nys, ixs, iys, rws, rns, scs, gxs, gys, wss
     # K nearest neighbours at tools/ubench/knn_paths.hip's shapes: the search, then both gradients in one gather (the bytes are the rows')
     for bk, nk, mk, kk in ((32, 1024, 1024, 16), (32, 512, 128, 8), (8, 4096, 4096, 20)):
         xk, yk = torch.rand(bk, nk, 3, device=dev), torch.rand(bk, mk, 3, device=dev)

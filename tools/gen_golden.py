@@ -1277,7 +1277,19 @@ def g30_icp_plane():
     assert os.path.getsize(os.path.join(OUT, "g30_icp_plane.npz")) <= 512 * 1024
 
 
+def g31_chamfer_normals():
+    """Chamfer's normal term: no reference code exists, so the fixture holds float32 clouds and normals at every work split (ragged
+    lengths as G27's) in seven families and the float64 search's indices -- tests/chamfer_normals_ref.py: generate, which redraws a
+    normal whose cosine through those indices lies in (0, MIN_COSINE).  The float64 expectations are re-formed from these on load."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import chamfer_normals_ref as ref
+    save("g31_chamfer_normals.npz", **ref.generate())
+    assert os.path.getsize(os.path.join(OUT, "g31_chamfer_normals.npz")) <= 512 * 1024
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "g31":
+        return g31_chamfer_normals()
     if len(sys.argv) > 1 and sys.argv[1] == "g30":
         return g30_icp_plane()
     if len(sys.argv) > 1 and sys.argv[1] == "g29":
@@ -1341,6 +1353,7 @@ def main():
     g28_knn()
     g29_local_frames()
     g30_icp_plane()
+    g31_chamfer_normals()
     g22_pointnet()
     g23_head_edges()
     # ---- G1: config #1, 256 Gaussian rows ------------------------------------------------------
