@@ -24,8 +24,8 @@ import os
 import numpy as np
 
 import chamfer_ref as cref
-from chamfer_ref import lengths_of
 from f32_exact import fma32
+from support import lengths_of
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g31_chamfer_normals.npz")
 SIZES = [(1, 1), (3, 7), (255, 1023), (256, 1024), (257, 1025)]

@@ -24,16 +24,13 @@ import os
 import numpy as np
 
 from f32_exact import first_argmin32, fma32, pair_dist2_32
+from support import lengths_of
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g27_chamfer.npz")
 SIZES = [(1, 1), (3, 7), (255, 1023), (256, 1024), (257, 1025), (1000, 2500)]
 B = 4                                   # clouds per geometry: ragged gives cloud 0 n_b = 0, cloud 1 m_b = 0, cloud 2 m_b = 1
 MIN_DISTANCE = 1e-3                     # no non-zero nearest distance of the fixture lies below it (the unsquared gradient's singularity)
 FAMILIES = ("random", "subset", "many_to_one")
-
-
-def lengths_of(lengths, b, full):
-    return np.full(b, full, np.int64) if lengths is None else np.clip(np.asarray(lengths, np.int64), 0, full)
 
 
 def scales(b):

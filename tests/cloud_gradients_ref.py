@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 import rigid_align_ref as ref
+from support import np_ptr
 from test_gpu_cloud_kernels import U, _rotations, make_batch, r_reference
 
 POINTS = (1, 2, 3, 63, 64, 65, 127, 129, 511, 512, 513, 1023, 1025, 1537, 3001)
@@ -264,11 +265,6 @@ def kabsch_bwd_model(P, Q, H, gR, gH):
     return {"dQ": _mat_rows(dh, P, False), "dP": _mat_rows(dh, Q, True)}
 
 
-def _p(a):
-    import ctypes
-    return None if a is None else ctypes.c_void_p(a.ctypes.data)
-
-
 def _c(a):
     return None if a is None else np.ascontiguousarray(a, dtype=np.float32)
 
@@ -280,7 +276,7 @@ def rigid_fwd_model(model, P, Q, w):
     P, Q, w = _c(P), _c(Q), _c(w)
     out = {"R": np.full((b, 3, 3), np.nan, np.float32), "t": np.full((b, 3), np.nan, np.float32), "H": np.full((b, 3, 3), np.nan, np.float32),
            "stats": np.full((b, 7), np.nan, np.float32)}
-    model.model_rigid_align(_p(P), _p(Q), _p(w), _p(out["R"]), _p(out["t"]), _p(out["H"]), _p(out["stats"]), ctypes.c_int64(b), ctypes.c_int32(n))
+    model.model_rigid_align(np_ptr(P), np_ptr(Q), np_ptr(w), np_ptr(out["R"]), np_ptr(out["t"]), np_ptr(out["H"]), np_ptr(out["stats"]), ctypes.c_int64(b), ctypes.c_int32(n))
     return out
 
 
@@ -290,5 +286,5 @@ def rigid_bwd_model(model, P, Q, w, H, R, stats, gR, gt, gH):
     b, n = P.shape[:2]
     args = [_c(v) for v in (P, Q, w, H, R, stats, gR, gt, gH)]
     out = {"dP": np.full((b, n, 3), np.nan, np.float32), "dQ": np.full((b, n, 3), np.nan, np.float32), "dw": np.full((b, n), np.nan, np.float32)}
-    model.model_rigid_align_bwd(*[_p(v) for v in args], _p(out["dP"]), _p(out["dQ"]), _p(out["dw"]), ctypes.c_int64(b), ctypes.c_int32(n))
+    model.model_rigid_align_bwd(*[np_ptr(v) for v in args], np_ptr(out["dP"]), np_ptr(out["dQ"]), np_ptr(out["dw"]), ctypes.c_int64(b), ctypes.c_int32(n))
     return out

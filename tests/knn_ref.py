@@ -23,6 +23,7 @@ import os
 import numpy as np
 
 from f32_exact import fma32
+from support import lengths_of
 import three_nn_ref
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g28_knn.npz")
@@ -32,10 +33,6 @@ MAX_K = 64
 SHAPES = [(1, 1, 1), (3, 7, 4), (5, 3, 8), (64, 65, 64), (255, 1023, 16), (257, 1025, 20), (300, 77, 8)]       # (N, M, K)
 B_FULL, B_RAGGED = 2, 5              # ragged: cloud 0 n_b = 0, cloud 1 m_b = 0, cloud 2 m_b = 1, cloud 3 1 < m_b < K (where K, M allow)
 FAMILIES = ("random", "subset", "all_equal", "lattice", "many_to_one")
-
-
-def lengths_of(lengths, b, full):
-    return np.full(b, full, np.int64) if lengths is None else np.clip(np.asarray(lengths, np.int64), 0, full)
 
 
 def _targets(Y, b):

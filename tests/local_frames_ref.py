@@ -27,6 +27,7 @@ import numpy as np
 
 from f32_exact import fma32
 import knn_ref
+from support import bits, lengths_of
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g29_local_frames.npz")
 U = 2.0 ** -24
@@ -41,10 +42,6 @@ MEASURED = {"cov": 2.5, "orth": 24.0, "eig": 3.6, "res": 3.7, "nrm": 1.6}
 C_COV, C_ORTH, C_EIG, C_RES, C_NRM = (4 * MEASURED[k] for k in ("cov", "orth", "eig", "res", "nrm"))
 CONSTANTS = {"cov": C_COV, "orth": C_ORTH, "eig": C_EIG, "res": C_RES, "nrm": C_NRM}
 C_VIEW = 8.0
-
-
-def lengths_of(lengths, b, full):
-    return np.full(b, full, np.int64) if lengths is None else np.clip(np.asarray(lengths, np.int64), 0, full)
 
 
 def _setup(Y, idx, x_lengths, y_lengths, dtype):
@@ -101,10 +98,6 @@ def expand6(cov):
     """(…, 6) -> the symmetric (…, 3, 3)."""
     cov = np.asarray(cov)
     return cov[..., [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(cov.shape[:-1] + (3, 3))
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _lead(e):

@@ -14,7 +14,6 @@ at most the per-point bound.  tests/test_gpu_add_metrics.py imports the bounds f
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -22,6 +21,7 @@ import torch
 
 from conftest import ROOT
 import add_metrics_ref as ref
+from support import boundary, build_host_model, np_ptr
 
 #                                 measured on the host       bound (4 x)
 HOST_ADD = 1.24e-7;               ADD_TOL = 4 * HOST_ADD                 # noqa: E702
@@ -39,20 +39,10 @@ SRC = os.path.join(ROOT, "tests", "host_model", "add_metrics.cpp")
 # ---- the boundary ---------------------------------------------------------------------------------------------------------
 def test_header_binding_table_and_library_agree(built_library):
     from poseestimation_amd import _lib
-    raw = open(os.path.join(ROOT, "include", "so3proj.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = set(re.findall(r"\b(so3_[a-z0-9_]+)\s*\(", text))
-    lib = ctypes.CDLL(built_library)
-    for name in NEW_SYMBOLS:
-        assert name in declared, name
-        assert name in _lib.SYMBOLS, name
-        assert hasattr(lib, name), name
-        args = re.search(r"\b%s\s*\(([^)]*)\)" % name, text).group(1).split(",")
-        assert len(args) == len(_lib.SYMBOLS[name][1]), (name, args)
+    raw, _ = boundary(built_library, NEW_SYMBOLS)
     assert len(_lib.SYMBOLS["so3_add_l2_f32"][1]) == len(_lib.SYMBOLS["so3_add_l1_f32"][1])           # "arguments as so3_add_l1_f32"
     assert _lib.SYMBOLS["so3_add_l2_f32"] == _lib.SYMBOLS["so3_add_l1_f32"]
     assert int(re.search(r"#define\s+SO3_ADD_S_MAX_N\s+(\d+)", raw).group(1)) == _lib.ADD_S_MAX_N      # the stated upper bound on N
-    assert lib.so3_version() == _lib.ABI_VERSION == 210
 
 
 def test_argument_validation_without_gpu(built_library):
@@ -137,17 +127,7 @@ def test_g19_is_self_consistent(g19, g19_cases):
 # ---- the device functions on the host --------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def model(tmp_path_factory):
-    from oracle import kernel_model
-    cxx = kernel_model.clangxx()
-    if cxx is None:
-        pytest.skip("clang++ is not available (ext_vector_type)")
-    out = str(tmp_path_factory.mktemp("add_metrics") / "libadd_metrics.so")
-    subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", out, SRC], check=True)
-    return ctypes.CDLL(out)
-
-
-def _p(a):
-    return ctypes.c_void_p(a.ctypes.data) if a is not None else None
+    return build_host_model(tmp_path_factory, "add_metrics", SRC)
 
 
 def _c(a):
@@ -163,10 +143,10 @@ def host_run(model, c):
            "add": np.full(b, np.nan, np.float32), "diam": np.full(b, np.nan, np.float32), "grad_add": np.full((b, 4, 4), np.nan, np.float32),
            "grad_adds": np.full((b, 4, 4), np.nan, np.float32)}
     work = np.empty((b, n), np.float32)
-    model.model_add_s_fwd(_p(tg), _p(tp), _p(pts), _p(out["point_dist"]), _p(out["nearest"]), _p(out["adds"]), B, N)
-    model.model_cloud_diameter(_p(pts), _p(work), _p(out["diam"]), B, N)
-    model.model_add_s_bwd(_p(tg), _p(tp), _p(pts), _p(out["nearest"]), None, ctypes.c_float(1.0), _p(out["grad_adds"]), B, N)
-    model.model_add_l2(_p(tg), _p(tp), _p(pts), _p(out["add"]), _p(out["grad_add"]), ctypes.c_float(1.0), B, N)
+    model.model_add_s_fwd(np_ptr(tg), np_ptr(tp), np_ptr(pts), np_ptr(out["point_dist"]), np_ptr(out["nearest"]), np_ptr(out["adds"]), B, N)
+    model.model_cloud_diameter(np_ptr(pts), np_ptr(work), np_ptr(out["diam"]), B, N)
+    model.model_add_s_bwd(np_ptr(tg), np_ptr(tp), np_ptr(pts), np_ptr(out["nearest"]), None, ctypes.c_float(1.0), np_ptr(out["grad_adds"]), B, N)
+    model.model_add_l2(np_ptr(tg), np_ptr(tp), np_ptr(pts), np_ptr(out["add"]), np_ptr(out["grad_add"]), ctypes.c_float(1.0), B, N)
     return out
 
 

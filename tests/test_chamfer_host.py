@@ -13,8 +13,6 @@ tests/test_gpu_chamfer.py imports the bounds and the checks; DESIGN.md section 7
 import ctypes
 import os
 import re
-import subprocess
-import threading
 
 import numpy as np
 import pytest
@@ -22,6 +20,7 @@ import torch
 
 from conftest import ROOT
 import chamfer_ref as ref
+from support import bits, boundary, build_host_model, lengths_of, np_ptr, on_own_thread
 
 #                                 measured on the host       bound (4 x)
 HOST_SEARCH = 0.0;                SEARCH_TOL = 4 * HOST_SEARCH           # noqa: E702
@@ -57,38 +56,14 @@ def bounds():
 # ---- the boundary ---------------------------------------------------------------------------------------------------------
 def test_header_binding_table_and_library_agree(built_library):
     from poseestimation_amd import _lib
-    raw = open(os.path.join(ROOT, "include", "so3proj.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = set(re.findall(r"\b(so3_[a-z0-9_]+)\s*\(", text))
-    exported = subprocess.run(["nm", "-D", "--defined-only", built_library], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r"\b(so3_[a-z0-9_]+)\b", exported))
-    assert declared == set(_lib.SYMBOLS) == exported
-    lib = ctypes.CDLL(built_library)
-    for name, nargs in NEW_SYMBOLS.items():
-        assert name in declared and name in _lib.SYMBOLS and hasattr(lib, name), name
-        args = re.search(r"\b%s\s*\(([^)]*)\)" % name, text).group(1).split(",")
-        assert len(args) == len(_lib.SYMBOLS[name][1]) == nargs, (name, args)
-    assert lib.so3_version() == _lib.ABI_VERSION == 210
+    raw, _ = boundary(built_library, NEW_SYMBOLS)
     for name, value in (("SO3_CHAMFER_UNSQUARED", _lib.CHAMFER_UNSQUARED), ("SO3_CHAMFER_SINGLE", _lib.CHAMFER_SINGLE)):
         assert int(re.search(r"#define %s (\d+)u" % name, raw).group(1)) == value
     assert (_lib.CHAMFER_UNSQUARED, _lib.CHAMFER_SINGLE) == (UNSQUARED, SINGLE)
 
 
 def test_argument_validation_without_gpu(built_library):
-    """On a thread of its own: so3_last_error is thread-local and never cleared, and other tests read it on the main thread."""
-    failure = []
-
-    def body():
-        try:
-            _argument_validation()
-        except BaseException as exc:               # noqa: BLE001 -- re-raised on the main thread
-            failure.append(exc)
-
-    t = threading.Thread(target=body)
-    t.start()
-    t.join()
-    if failure:
-        raise failure[0]
+    on_own_thread(_argument_validation)
 
 
 def _argument_validation():
@@ -152,7 +127,7 @@ def gather_gradients(c, scale_x, scale_y):
     indices (e = |v|^2 or |v|), over the live points."""
     X = torch.tensor(c["X"], dtype=torch.float64, requires_grad=True)
     Y = torch.tensor(c["Y"], dtype=torch.float64, requires_grad=True)
-    nl, ml = ref.lengths_of(c["x_lengths"], c["b"], c["n"]), ref.lengths_of(c["y_lengths"], c["b"], c["m"])
+    nl, ml = lengths_of(c["x_lengths"], c["b"], c["n"]), lengths_of(c["y_lengths"], c["b"], c["m"])
     total = torch.zeros((), dtype=torch.float64)
     for k in range(c["b"]):
         nb, mb = int(nl[k]), int(ml[k])
@@ -179,7 +154,7 @@ def test_g27_is_self_consistent(g27_cases):
         X, Y, xl, yl = c["X"], c["Y"], c["x_lengths"], c["y_lengths"]
         assert X.dtype == np.float32 and Y.dtype == np.float32 and np.abs(X).max() <= 1 and np.abs(Y).max() <= 1, c["name"]
         if c["lengths"] == "ragged":
-            nl, ml = ref.lengths_of(xl, c["b"], c["n"]), ref.lengths_of(yl, c["b"], c["m"])
+            nl, ml = lengths_of(xl, c["b"], c["n"]), lengths_of(yl, c["b"], c["m"])
             assert nl[0] == 0 and ml[1] == 0 and ml[2] == 1 and nl[3] >= 1 and ml[3] >= 1, c["name"]
         assert ref.min_nonzero_distance(X, Y, xl, yl) >= ref.MIN_DISTANCE, c["name"]          # the unsquared gradient's condition
         f = ref.chamfer64(X, Y, xl, yl, c["squared"])
@@ -197,10 +172,6 @@ def test_g27_is_self_consistent(g27_cases):
 
 
 # ---- the checks, shared with tests/test_gpu_chamfer.py -----------------------------------------------------------------------
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 SEARCH32 = {}
 
 
@@ -240,7 +211,7 @@ def case_figures(c, got, single=False):
     if f["exact"] == 0.0:
         f.update(ref.gradient_figures(c["X"], c["Y"], c["x_lengths"], c["y_lengths"], c["squared"], got["nearest_x"],
                                       None if single else got["nearest_y"], sx, None if single else sy, got["dX"], got["dY"]))
-    nl, ml = ref.lengths_of(c["x_lengths"], c["b"], c["n"]), ref.lengths_of(c["y_lengths"], c["b"], c["m"])
+    nl, ml = lengths_of(c["x_lengths"], c["b"], c["n"]), lengths_of(c["y_lengths"], c["b"], c["m"])
     for k in range(c["b"]):                                                              # padded slots and empty clouds: rows of zeros
         nb, mb = (int(nl[k]), int(ml[k])) if nl[k] > 0 and ml[k] > 0 else (0, 0)
         if (got["dX"][k, nb:] != 0).any() or (got["dY"][k, mb:] != 0).any():
@@ -278,23 +249,13 @@ def check_against_g27(cases, run, label, single=False, bnd=None):
 # ---- the device functions on the host --------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def model(tmp_path_factory):
-    from oracle import kernel_model
-    cxx = kernel_model.clangxx()
-    if cxx is None:
-        pytest.skip("clang++ is not available (ext_vector_type)")
-    out = str(tmp_path_factory.mktemp("chamfer") / "libchamfer.so")
-    subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", out, SRC], check=True)
-    lib = ctypes.CDLL(out)
+    lib = build_host_model(tmp_path_factory, "chamfer", SRC)
     P, I64, I32, U32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint32
     lib.model_chamfer_fwd.argtypes = [P] * 9 + [U32, I64, I32, I32, I64]
     lib.model_chamfer_bwd.argtypes = [P] * 10 + [U32, I64, I32, I32]
     lib.model_chamfer_points_per_lane.argtypes = [I64, I32, I32, I32, I64]
     lib.model_chamfer_fwd.restype = lib.model_chamfer_bwd.restype = None
     return lib
-
-
-def _p(a):
-    return ctypes.c_void_p(a.ctypes.data) if a is not None else None
 
 
 def abi_run(fwd, bwd, c, single=False, fwd_tail=(), bwd_tail=(), work=None):
@@ -310,9 +271,9 @@ def abi_run(fwd, bwd, c, single=False, fwd_tail=(), bwd_tail=(), work=None):
     if not single:
         out.update(dist_y=np.full((b, m), np.nan, np.float32), nearest_y=np.full((b, m), -2, np.int32))
     sx, sy = ref.scales(b)
-    fwd(_p(X), _p(Y), _p(xl), _p(yl), _p(out["dist_x"]), _p(out["nearest_x"]), _p(out.get("dist_y")), _p(out.get("nearest_y")), _p(out["rows"]),
+    fwd(np_ptr(X), np_ptr(Y), np_ptr(xl), np_ptr(yl), np_ptr(out["dist_x"]), np_ptr(out["nearest_x"]), np_ptr(out.get("dist_y")), np_ptr(out.get("nearest_y")), np_ptr(out["rows"]),
         *(() if work is None else (work,)), flags, b, n, m, *fwd_tail)
-    bwd(_p(X), _p(Y), _p(xl), _p(yl), _p(out["nearest_x"]), _p(out.get("nearest_y")), _p(sx), None if single else _p(sy), _p(out["dX"]), _p(out["dY"]),
+    bwd(np_ptr(X), np_ptr(Y), np_ptr(xl), np_ptr(yl), np_ptr(out["nearest_x"]), np_ptr(out.get("nearest_y")), np_ptr(sx), None if single else np_ptr(sy), np_ptr(out["dX"]), np_ptr(out["dY"]),
         flags, b, n, m, *bwd_tail)
     return out
 

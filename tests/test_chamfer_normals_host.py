@@ -14,8 +14,6 @@ tests/test_gpu_chamfer_normals.py imports the bounds and the checks; DESIGN.md s
 import ctypes
 import os
 import re
-import subprocess
-import threading
 
 import numpy as np
 import pytest
@@ -23,6 +21,7 @@ import torch
 
 from conftest import ROOT
 import chamfer_normals_ref as ref
+from support import bits, boundary, build_host_model, lengths_of, np_ptr, on_own_thread
 
 #                                 measured on the host       bound (4 x)
 HOST_TERM = 3.289e-7;             TERM_TOL = 4 * HOST_TERM               # noqa: E702
@@ -51,37 +50,13 @@ def bounds():
 # ---- the boundary ---------------------------------------------------------------------------------------------------------
 def test_header_binding_table_and_library_agree(built_library):
     from poseestimation_amd import _lib
-    raw = open(os.path.join(ROOT, "include", "so3proj.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = set(re.findall(r"\b(so3_[a-z0-9_]+)\s*\(", text))
-    exported = subprocess.run(["nm", "-D", "--defined-only", built_library], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r"\b(so3_[a-z0-9_]+)\b", exported))
-    assert declared == set(_lib.SYMBOLS) == exported
-    lib = ctypes.CDLL(built_library)
-    for name, nargs in NEW_SYMBOLS.items():
-        assert name in declared and name in _lib.SYMBOLS and hasattr(lib, name), name
-        args = re.search(r"\b%s\s*\(([^)]*)\)" % name, text).group(1).split(",")
-        assert len(args) == len(_lib.SYMBOLS[name][1]) == nargs, (name, args)
-    assert lib.so3_version() == _lib.ABI_VERSION == 210
+    raw, _ = boundary(built_library, NEW_SYMBOLS)
     assert int(re.search(r"#define SO3_CHAMFER_SIGNED_COSINE (\d+)u", raw).group(1)) == _lib.CHAMFER_SIGNED_COSINE == SIGNED
     assert (_lib.CHAMFER_UNSQUARED, _lib.CHAMFER_SINGLE) == (UNSQUARED, SINGLE)
 
 
 def test_argument_validation_without_gpu(built_library):
-    """On a thread of its own: so3_last_error is thread-local and never cleared, and other tests read it on the main thread."""
-    failure = []
-
-    def body():
-        try:
-            _argument_validation()
-        except BaseException as exc:               # noqa: BLE001 -- re-raised on the main thread
-            failure.append(exc)
-
-    t = threading.Thread(target=body)
-    t.start()
-    t.join()
-    if failure:
-        raise failure[0]
+    on_own_thread(_argument_validation)
 
 
 def _argument_validation():
@@ -151,7 +126,7 @@ def autograd_gradients(c, signed, scale_x, scale_y):
     points whose pair is not flat (a flat pair has term 1 and no gradient BY DEFINITION)."""
     NX = torch.tensor(c["NX"], dtype=torch.float64).nan_to_num(0.0, 0.0, 0.0).requires_grad_(True)
     NY = torch.tensor(c["NY"], dtype=torch.float64).nan_to_num(0.0, 0.0, 0.0).requires_grad_(True)
-    nl, ml = ref.lengths_of(c["x_lengths"], c["b"], c["n"]), ref.lengths_of(c["y_lengths"], c["b"], c["m"])
+    nl, ml = lengths_of(c["x_lengths"], c["b"], c["n"]), lengths_of(c["y_lengths"], c["b"], c["m"])
     total = torch.zeros((), dtype=torch.float64)
     for k in range(c["b"]):
         nb, mb = int(nl[k]), int(ml[k])
@@ -178,7 +153,7 @@ def test_g31_is_self_consistent(g31_cases):
         X, Y, NX, NY, xl, yl = c["X"], c["Y"], c["NX"], c["NY"], c["x_lengths"], c["y_lengths"]
         assert all(a.dtype == np.float32 for a in (X, Y, NX, NY)) and NX.shape == X.shape and NY.shape == Y.shape, c["name"]
         if c["lengths"] == "ragged":
-            nl, ml = ref.lengths_of(xl, c["b"], c["n"]), ref.lengths_of(yl, c["b"], c["m"])
+            nl, ml = lengths_of(xl, c["b"], c["n"]), lengths_of(yl, c["b"], c["m"])
             assert nl[0] == 0 and ml[1] == 0 and ml[2] == 1 and nl[3] >= 1 and ml[3] >= 1, c["name"]
         f = cref.chamfer64(X, Y, xl, yl)
         assert np.array_equal(f["nearest_x"], c["nearest_x"]) and np.array_equal(f["nearest_y"], c["nearest_y"]), c["name"]
@@ -223,10 +198,6 @@ def test_g31_is_self_consistent(g31_cases):
 
 
 # ---- the checks, shared with tests/test_gpu_chamfer_normals.py ------------------------------------------------------------------
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 def same_bits(a, b):
     return np.array_equal(bits(a), bits(b))
 
@@ -251,7 +222,7 @@ def case_figures(c, got, signed, single=False, plain=None, exact32=False):
     if wrong:
         print("%s: arrays whose bits differ: %s" % (c["name"], wrong))
     f["bits"] = np.inf if wrong else 0.0
-    nl, ml = ref.lengths_of(c["x_lengths"], c["b"], c["n"]), ref.lengths_of(c["y_lengths"], c["b"], c["m"])
+    nl, ml = lengths_of(c["x_lengths"], c["b"], c["n"]), lengths_of(c["y_lengths"], c["b"], c["m"])
     ok = True
     for k in range(c["b"]):                                                               # padded slots and empty clouds: rows of zeros
         nb, mb = (int(nl[k]), int(ml[k])) if nl[k] > 0 and ml[k] > 0 else (0, 0)
@@ -299,16 +270,7 @@ def check_against_g31(cases, run, label, single=False, bnd=None, **kw):
 # ---- the device functions on the host --------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def model(tmp_path_factory):
-    from oracle import kernel_model
-    cxx = kernel_model.clangxx()
-    if cxx is None:
-        pytest.skip("clang++ is not available (ext_vector_type)")
-    libs = []
-    for name, src in (("libchamfer_normals.so", SRC), ("libchamfer.so", PLAIN_SRC)):
-        out = str(tmp_path_factory.mktemp("chamfer_normals") / name)
-        subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", out, src], check=True)
-        libs.append(ctypes.CDLL(out))
-    lib, plain = libs
+    lib, plain = build_host_model(tmp_path_factory, "chamfer_normals", SRC), build_host_model(tmp_path_factory, "chamfer", PLAIN_SRC)
     P, I64, I32, U32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint32
     lib.model_chamfer_normals_fwd.argtypes = [P] * 14 + [U32, I64, I32, I32, I64, I32]
     lib.model_chamfer_normals_bwd.argtypes = [P] * 10 + [U32, I64, I32, I32]
@@ -316,10 +278,6 @@ def model(tmp_path_factory):
     lib.model_chamfer_normals_fwd.restype = lib.model_chamfer_normals_bwd.restype = plain.model_chamfer_fwd.restype = None
     lib.plain = plain
     return lib
-
-
-def _p(a):
-    return ctypes.c_void_p(a.ctypes.data) if a is not None else None
 
 
 def abi_run(fwd, bwd, c, signed, single=False, squared=True, fwd_tail=(), bwd_tail=(), work=None):
@@ -336,10 +294,10 @@ def abi_run(fwd, bwd, c, signed, single=False, squared=True, fwd_tail=(), bwd_ta
     if not single:
         out.update(dist_y=np.full((b, m), np.nan, np.float32), nearest_y=np.full((b, m), -2, np.int32), term_y=np.full((b, m), np.nan, np.float32))
     sx, sy = ref.scales(b)
-    fwd(_p(X), _p(Y), _p(NX), _p(NY), _p(xl), _p(yl), _p(out["dist_x"]), _p(out["nearest_x"]), _p(out.get("dist_y")), _p(out.get("nearest_y")),
-        _p(out["term_x"]), _p(out.get("term_y")), _p(out["rows"]), _p(out["rows_n"]), *(() if work is None else (work,)), flags, b, n, m, *fwd_tail)
-    bwd(_p(NX), _p(NY), _p(xl), _p(yl), _p(out["nearest_x"]), _p(out.get("nearest_y")), _p(sx), None if single else _p(sy), _p(out["dNX"]),
-        _p(out["dNY"]), flags, b, n, m, *bwd_tail)
+    fwd(np_ptr(X), np_ptr(Y), np_ptr(NX), np_ptr(NY), np_ptr(xl), np_ptr(yl), np_ptr(out["dist_x"]), np_ptr(out["nearest_x"]), np_ptr(out.get("dist_y")), np_ptr(out.get("nearest_y")),
+        np_ptr(out["term_x"]), np_ptr(out.get("term_y")), np_ptr(out["rows"]), np_ptr(out["rows_n"]), *(() if work is None else (work,)), flags, b, n, m, *fwd_tail)
+    bwd(np_ptr(NX), np_ptr(NY), np_ptr(xl), np_ptr(yl), np_ptr(out["nearest_x"]), np_ptr(out.get("nearest_y")), np_ptr(sx), None if single else np_ptr(sy), np_ptr(out["dNX"]),
+        np_ptr(out["dNY"]), flags, b, n, m, *bwd_tail)
     return out
 
 
@@ -352,8 +310,8 @@ def host_run(model, c, signed, u=0, single=False, squared=True, cus=CUS):
     xl = None if c["x_lengths"] is None else np.ascontiguousarray(c["x_lengths"], np.int32)
     yl = None if c["y_lengths"] is None else np.ascontiguousarray(c["y_lengths"], np.int32)
     # the model of the call without normals picks U by its own rule: the rows' bits are compared where that is the U used here
-    model.plain.model_chamfer_fwd(_p(np.ascontiguousarray(c["X"])), _p(np.ascontiguousarray(c["Y"])), _p(xl), _p(yl), _p(plain["dist_x"]),
-                                  _p(plain["nearest_x"]), _p(plain.get("dist_y")), _p(plain.get("nearest_y")), _p(plain["rows"]),
+    model.plain.model_chamfer_fwd(np_ptr(np.ascontiguousarray(c["X"])), np_ptr(np.ascontiguousarray(c["Y"])), np_ptr(xl), np_ptr(yl), np_ptr(plain["dist_x"]),
+                                  np_ptr(plain["nearest_x"]), np_ptr(plain.get("dist_y")), np_ptr(plain.get("nearest_y")), np_ptr(plain["rows"]),
                                   (0 if squared else UNSQUARED) | (SINGLE if single else 0), b, n, m, cus)
     if u != 0:
         plain["rows"] = out["rows"]

@@ -9,24 +9,18 @@ compiled for the host: tests/host_model/dispatch.cpp).
   4  the cloud kernels' launch shape against its restatement here."""
 import ctypes
 import os
-import subprocess
 
 import pytest
 
 from conftest import ROOT
+from support import build_host_model
 
 SRC = os.path.join(ROOT, "tests", "host_model", "dispatch.cpp")
 
 
 @pytest.fixture(scope="module")
 def model(tmp_path_factory):
-    from oracle import kernel_model
-    cxx = kernel_model.clangxx()
-    if cxx is None:
-        pytest.skip("clang++ is not available (so3_device.h: ext_vector_type)")
-    out = str(tmp_path_factory.mktemp("dispatch") / "libdispatch.so")
-    subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O2", "-fPIC", "-shared", "-o", out, SRC], check=True)
-    lib = ctypes.CDLL(out)
+    lib = build_host_model(tmp_path_factory, "dispatch", SRC, fp_contract_off=False)
     lib.model_with_flags.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.model_with_flags.restype = None
     lib.model_with_value.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]

@@ -11,15 +11,12 @@ import pytest
 
 import chamfer_ref
 import f32_exact as fx
+from support import bits
 import test_chamfer_host as chost
 import test_three_nn_host as thost
 import three_nn_ref
 from test_chamfer_host import model as chamfer_model       # noqa: F401 -- the host-model fixtures, built once per module
 from test_three_nn_host import model as three_nn_model     # noqa: F401
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 @pytest.fixture(scope="module")

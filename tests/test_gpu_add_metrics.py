@@ -1,24 +1,16 @@
 """compute_ADD_loss, compute_ADD_S_loss and cloud_diameter on the GPU: G19 through the Python surface and through the raw C ABI at the
 bounds of tests/test_add_metrics_host.py (4 x the float32 host model's error; see its docstring), the exact cases, the plumbing, the
 gradient through a training step, and the speed condition against the torch composition the feature replaces."""
-import ctypes
 
 import numpy as np
 import pytest
 import torch
 
 import add_metrics_ref as ref
+from support import dev  # noqa: F401
 import test_add_metrics_host as host
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from poseestimation_amd import _lib
-    _lib.load()
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")

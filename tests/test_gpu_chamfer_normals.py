@@ -12,32 +12,16 @@ import torch
 
 import chamfer_ref as cref
 import chamfer_normals_ref as ref
+from support import dev, guarded, guards_intact, lengths_of, ptr, to_device  # noqa: F401
 import test_chamfer_normals_host as host
 
 pytestmark = pytest.mark.gpu
-GUARD = 64                          # elements in front of and behind every raw buffer
 KERNELS = []                        # abi_run: the k_chamfer_normals_fwd instantiation of every checked forward call, in call order
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from poseestimation_amd import _lib
-    _lib.load()
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")
 def g31_cases():
     return ref.cases(ref.g31())
-
-
-def _d(a, dev, dtype=np.float32):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def _folded(g, lengths, full):
@@ -50,35 +34,24 @@ def surface_run(c, dev, signed, single=False, squared=True):
     the upstream gradient of loss and its second of loss_normals; and the same call without normals under "plain"."""
     import poseestimation_amd as pa
     b, n, m = c["b"], c["n"], c["m"]
-    xl, yl = _d(c["x_lengths"], dev, np.int64), _d(c["y_lengths"], dev, np.int64)
+    xl, yl = to_device(c["x_lengths"], dev, np.int64), to_device(c["y_lengths"], dev, np.int64)
     g, gn = ref.scales(b)
     kw = dict(squared=squared, batch_reduction=None, single_directional=single, return_nearest=True)
-    X, Y, NX, NY = (_d(c[k], dev).requires_grad_() for k in ("X", "Y", "NX", "NY"))
+    X, Y, NX, NY = (to_device(c[k], dev).requires_grad_() for k in ("X", "Y", "NX", "NY"))
     loss, loss_n, info = pa.chamfer_distance(X, Y, xl, yl, x_normals=NX, y_normals=NY, abs_cosine=not signed, **kw)
     assert loss.shape == loss_n.shape == (b,) and loss_n.dtype == torch.float32 and info["normal_x"].shape == (b, n)
     sides = ("x",) if single else ("x", "y")
     assert set(info) == {k + s for s in sides for k in ("nearest_", "dist_", "normal_")}
-    torch.autograd.backward((loss, loss_n), (_d(g, dev), _d(gn, dev)))
+    torch.autograd.backward((loss, loss_n), (to_device(g, dev), to_device(gn, dev)))
     got = {k.replace("normal_", "term_"): v.cpu().numpy() for k, v in info.items()}
     got.update(loss=loss.detach().cpu().numpy(), loss_n=loss_n.detach().cpu().numpy(), dX=X.grad.cpu().numpy(), dY=Y.grad.cpu().numpy(),
                dNX=NX.grad.cpu().numpy(), dNY=NY.grad.cpu().numpy(), scale_x=_folded(gn, c["x_lengths"], n), scale_y=_folded(gn, c["y_lengths"], m))
-    X2, Y2 = _d(c["X"], dev).requires_grad_(), _d(c["Y"], dev).requires_grad_()
+    X2, Y2 = to_device(c["X"], dev).requires_grad_(), to_device(c["Y"], dev).requires_grad_()
     loss2, info2 = pa.chamfer_distance(X2, Y2, xl, yl, **kw)
-    loss2.backward(_d(g, dev))
+    loss2.backward(to_device(g, dev))
     got["plain"] = {k: v.cpu().numpy() for k, v in info2.items()}
     got["plain"].update(loss=loss2.detach().cpu().numpy(), dX=X2.grad.cpu().numpy(), dY=Y2.grad.cpu().numpy())
     return got
-
-
-def _guarded(shape, fill, dtype, dev):
-    count = int(np.prod(shape))
-    whole = torch.full((count + 2 * GUARD,), fill, dtype=dtype, device=dev)
-    return whole, whole[GUARD:GUARD + count].view(shape)
-
-
-def _guards_intact(whole, fill):
-    edge = torch.cat([whole[:GUARD], whole[-GUARD:]])
-    return bool(torch.isnan(edge).all()) if isinstance(fill, float) and np.isnan(fill) else bool((edge == fill).all())
 
 
 def abi_run(c, dev, signed, single=False, squared=True):
@@ -87,8 +60,8 @@ def abi_run(c, dev, signed, single=False, squared=True):
     from poseestimation_amd import _lib
     lib = _lib.load()
     b, n, m = c["b"], c["n"], c["m"]
-    X, Y, NX, NY = (_d(c[k], dev) for k in ("X", "Y", "NX", "NY"))
-    xl, yl = _d(c["x_lengths"], dev, np.int32), _d(c["y_lengths"], dev, np.int32)
+    X, Y, NX, NY = (to_device(c[k], dev) for k in ("X", "Y", "NX", "NY"))
+    xl, yl = to_device(c["x_lengths"], dev, np.int32), to_device(c["y_lengths"], dev, np.int32)
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     flags = (0 if squared else host.UNSQUARED) | (host.SINGLE if single else 0) | (host.SIGNED if signed else 0)
     spec = {"dist_x": ((b, n), np.nan, torch.float32), "nearest_x": ((b, n), -2, torch.int32), "term_x": ((b, n), np.nan, torch.float32),
@@ -98,20 +71,20 @@ def abi_run(c, dev, signed, single=False, squared=True):
         spec.update(dist_y=((b, m), np.nan, torch.float32), nearest_y=((b, m), -2, torch.int32), term_y=((b, m), np.nan, torch.float32))
     whole, out = {}, {}
     for k, (shape, fill, dtype) in spec.items():
-        whole[k], out[k] = _guarded(shape, fill, dtype, dev)
+        whole[k], out[k] = guarded(shape, fill, dtype, dev)
     words = lib.so3_chamfer_normals_workspace_bytes(b, n, m) // 4
-    work_whole, work = _guarded((words,), np.nan, torch.float32, dev)
+    work_whole, work = guarded((words,), np.nan, torch.float32, dev)
     sx, sy = ref.scales(b)
-    sxd, syd = _d(sx, dev), (None if single else _d(sy, dev))
+    sxd, syd = to_device(sx, dev), (None if single else to_device(sy, dev))
 
     def fwd(**o):
-        _lib.check(lib.so3_chamfer_normals_fwd_f32(_ptr(X), _ptr(Y), _ptr(NX), _ptr(NY), _ptr(xl), _ptr(yl), _ptr(o.get("dist_x")), _ptr(o.get("nearest_x")),
-                                                   _ptr(o.get("dist_y")), _ptr(o.get("nearest_y")), _ptr(o.get("term_x")), _ptr(o.get("term_y")),
-                                                   _ptr(o["rows"]), _ptr(o["rows_n"]), _ptr(work), flags, b, n, m, st), "so3_chamfer_normals_fwd_f32")
+        _lib.check(lib.so3_chamfer_normals_fwd_f32(ptr(X), ptr(Y), ptr(NX), ptr(NY), ptr(xl), ptr(yl), ptr(o.get("dist_x")), ptr(o.get("nearest_x")),
+                                                   ptr(o.get("dist_y")), ptr(o.get("nearest_y")), ptr(o.get("term_x")), ptr(o.get("term_y")),
+                                                   ptr(o["rows"]), ptr(o["rows_n"]), ptr(work), flags, b, n, m, st), "so3_chamfer_normals_fwd_f32")
 
     def bwd(dnx, dny):
-        _lib.check(lib.so3_chamfer_normals_bwd_f32(_ptr(NX), _ptr(NY), _ptr(xl), _ptr(yl), _ptr(out["nearest_x"]), _ptr(out.get("nearest_y")), _ptr(sxd),
-                                                   _ptr(syd), _ptr(dnx), _ptr(dny), flags, b, n, m, st), "so3_chamfer_normals_bwd_f32")
+        _lib.check(lib.so3_chamfer_normals_bwd_f32(ptr(NX), ptr(NY), ptr(xl), ptr(yl), ptr(out["nearest_x"]), ptr(out.get("nearest_y")), ptr(sxd),
+                                                   ptr(syd), ptr(dnx), ptr(dny), flags, b, n, m, st), "so3_chamfer_normals_bwd_f32")
 
     fwd(**out)
     KERNELS.append(lib.so3_last_kernel().decode())
@@ -127,14 +100,14 @@ def abi_run(c, dev, signed, single=False, squared=True):
         bwd(alone if only == "dNX" else None, alone if only == "dNY" else None)
         assert torch.equal(alone, out[only])
     plain = {k: torch.full(s[0], s[1], dtype=s[2], device=dev) for k, s in spec.items() if k.split("_")[0] in ("dist", "nearest", "rows") and k != "rows_n"}
-    _lib.check(lib.so3_chamfer_fwd_f32(_ptr(X), _ptr(Y), _ptr(xl), _ptr(yl), _ptr(plain["dist_x"]), _ptr(plain["nearest_x"]), _ptr(plain.get("dist_y")),
-                                       _ptr(plain.get("nearest_y")), _ptr(plain["rows"]), _ptr(work), flags & ~host.SIGNED, b, n, m, st),
+    _lib.check(lib.so3_chamfer_fwd_f32(ptr(X), ptr(Y), ptr(xl), ptr(yl), ptr(plain["dist_x"]), ptr(plain["nearest_x"]), ptr(plain.get("dist_y")),
+                                       ptr(plain.get("nearest_y")), ptr(plain["rows"]), ptr(work), flags & ~host.SIGNED, b, n, m, st),
                "so3_chamfer_fwd_f32")
     assert lib.so3_last_kernel().decode() == KERNELS[-1].replace("k_chamfer_normals_fwd", "k_chamfer_fwd")
     torch.cuda.synchronize()
     for k, (shape, fill, dtype) in spec.items():
-        assert _guards_intact(whole[k], fill), k
-    assert _guards_intact(work_whole, np.nan)
+        assert guards_intact(whole[k], fill), k
+    assert guards_intact(work_whole, np.nan)
     got = {k: v.cpu().numpy() for k, v in out.items()}
     got["plain"] = {k: v.cpu().numpy() for k, v in plain.items()}
     return got
@@ -262,17 +235,17 @@ def test_every_reduction_against_float64(dev, small):
     gvec = np.array([0.5, -2.0, 1.25])
     for pr, br, single, signed, ragged in itertools.product(("mean", "sum"), ("mean", "sum", None), (False, True), (False, True), (True, False)):
         lx, ly = (c["x_lengths"], c["y_lengths"]) if ragged else (None, None)
-        NX, NY = _d(c["NX"], dev).requires_grad_(), _d(c["NY"], dev).requires_grad_()
-        _, loss_n, info = pa.chamfer_distance(_d(c["X"], dev), _d(c["Y"], dev), _d(lx, dev, np.int64), _d(ly, dev, np.int64), point_reduction=pr,
+        NX, NY = to_device(c["NX"], dev).requires_grad_(), to_device(c["NY"], dev).requires_grad_()
+        _, loss_n, info = pa.chamfer_distance(to_device(c["X"], dev), to_device(c["Y"], dev), to_device(lx, dev, np.int64), to_device(ly, dev, np.int64), point_reduction=pr,
                                               batch_reduction=br, single_directional=single, return_nearest=True, x_normals=NX, y_normals=NY,
                                               abs_cosine=not signed)
         g = gvec if br is None else 0.75
-        loss_n.backward(_d(g, dev) if br is None else torch.tensor(g, device=dev))
+        loss_n.backward(to_device(g, dev) if br is None else torch.tensor(g, device=dev))
         near_x, near_y = info["nearest_x"].cpu().numpy(), None if single else info["nearest_y"].cpu().numpy()
         a, cc = cref.fold_scales(g, b, n, m, lx, ly, pr, br)
         w = ref.normals64(c["NX"], c["NY"], lx, ly, near_x, near_y, signed, a, None if single else cc)
         per = (w["rows_n"] if pr == "mean" else w["sums_n"])
-        lens = np.stack([ref.lengths_of(lx, b, n), ref.lengths_of(ly, b, m)], 1) if pr == "sum" else np.ones((b, 2))
+        lens = np.stack([lengths_of(lx, b, n), lengths_of(ly, b, m)], 1) if pr == "sum" else np.ones((b, 2))
         lens = lens[:, :1] if single else lens
         agg = (lambda v: v.mean()) if br == "mean" else ((lambda v: v.sum()) if br == "sum" else (lambda v: v))
         want = agg(per.sum(1))
@@ -288,7 +261,7 @@ def test_every_reduction_against_float64(dev, small):
 def test_autograd_surface(dev, small):
     import poseestimation_amd as pa
     c = small
-    X0, Y0, NX0, NY0 = (_d(c[k], dev) for k in ("X", "Y", "NX", "NY"))
+    X0, Y0, NX0, NY0 = (to_device(c[k], dev) for k in ("X", "Y", "NX", "NY"))
 
     def leaves(*names):
         return [t.clone().requires_grad_() if k in names else t for k, t in zip("X Y NX NY".split(), (X0, Y0, NX0, NY0))]
@@ -366,7 +339,7 @@ def test_autograd_surface(dev, small):
 # ---- repeatability --------------------------------------------------------------------------------------------------------------
 def _run(pa, c, dev, NX0, NY0, xl, yl, order=None):
     o = slice(None) if order is None else order
-    X, Y = _d(c["X"], dev)[o], _d(c["Y"], dev)[o]
+    X, Y = to_device(c["X"], dev)[o], to_device(c["Y"], dev)[o]
     NX, NY = NX0[o].clone().requires_grad_(), NY0[o].clone().requires_grad_()
     _, loss_n, info = pa.chamfer_distance(X, Y, xl[o], yl[o], batch_reduction=None, return_nearest=True, x_normals=NX, y_normals=NY)
     loss_n.backward(torch.linspace(0.5, 2.0, len(X), device=dev)[o])
@@ -377,7 +350,7 @@ def test_same_bits_from_call_to_call_in_any_batch_order_and_beside_a_nan_cloud(d
     import poseestimation_amd as pa
     c = fresh_case(5, 700, 1300, ragged=False)
     c["Y"][:, :40] = c["X"][:, 5:6]                               # forty points of Y share their nearest x: a chain
-    NX0, NY0 = _d(c["NX"], dev), _d(c["NY"], dev)
+    NX0, NY0 = to_device(c["NX"], dev), to_device(c["NY"], dev)
     xl, yl = torch.tensor([700, 650, 1, 700, 333], device=dev), torch.tensor([1300, 64, 1300, 1025, 777], device=dev)
     first = _run(pa, c, dev, NX0, NY0, xl, yl)
     again = _run(pa, c, dev, NX0, NY0, xl, yl)
@@ -397,9 +370,9 @@ def test_replay_from_a_captured_graph(dev):
     import poseestimation_amd as pa
     c = fresh_case(3, 300, 520, ragged=False)
     xl, yl = torch.tensor([300, 17, 256], device=dev, dtype=torch.int32), torch.tensor([520, 500, 3], device=dev, dtype=torch.int32)
-    X, Y = _d(c["X"], dev).requires_grad_(), _d(c["Y"], dev).requires_grad_()
-    NX0 = _d(c["NX"], dev)
-    NX, NY = NX0.clone().requires_grad_(), _d(c["NY"], dev).requires_grad_()
+    X, Y = to_device(c["X"], dev).requires_grad_(), to_device(c["Y"], dev).requires_grad_()
+    NX0 = to_device(c["NX"], dev)
+    NX, NY = NX0.clone().requires_grad_(), to_device(c["NY"], dev).requires_grad_()
 
     def step():
         loss, loss_n = pa.chamfer_distance(X, Y, xl, yl, point_reduction="sum", x_normals=NX, y_normals=NY, abs_cosine=False)
@@ -436,7 +409,7 @@ def test_chamfer_with_normals_is_not_slower_than_the_torch_spelling(dev):
     import poseestimation_amd as pa
     from conftest import REPORT_LINES
     c = fresh_case(16, 2048, 2048, ragged=False)
-    X, Y, NX, NY = (_d(c[k], dev).requires_grad_() for k in ("X", "Y", "NX", "NY"))
+    X, Y, NX, NY = (to_device(c[k], dev).requires_grad_() for k in ("X", "Y", "NX", "NY"))
 
     def torch_spelling(X, Y, NX, NY):
         with torch.no_grad():

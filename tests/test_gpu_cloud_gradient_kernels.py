@@ -43,6 +43,7 @@ import pytest
 import torch
 
 import cloud_gradients_ref as cg
+from support import dev, ptr  # noqa: F401
 import test_cloud_gradient_kernels_host as hostk
 import test_rigid_align_host as host
 from test_gpu_cloud_kernels import CANARY, GEOMETRIES, PAD, Out, _rotations, h_bound, make_batch, per_wave, r_reference, wave_slots      # noqa: F401
@@ -53,18 +54,6 @@ ROT_SIDES = (("dP", "dR"), ("dP",), ("dR",))
 KABSCH_SIDES = (("dP", "dQ"), ("dP",), ("dQ",))
 LARGE = 100000
 RIGID_SIDES = tuple(s for r in (3, 2, 1) for s in itertools.combinations(("dP", "dQ", "dw"), r))
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from poseestimation_amd import _lib
-    _lib.load()
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def _optr(o):
@@ -112,14 +101,14 @@ class GradAbi:
     def rotate_bwd(self, P, R, G, transposed, want=("dP", "dR")):
         b, n = P.shape[:2]
         o = {"dP": self._out(b, n, 3) if "dP" in want else None, "dR": self._out(b, 3, 3) if "dR" in want else None}
-        self._lib.check(self.lib.so3_rotate_clouds_bwd_f32(_ptr(P), _ptr(R), _ptr(G), _optr(o["dP"]), _optr(o["dR"]), int(transposed), b, n,
+        self._lib.check(self.lib.so3_rotate_clouds_bwd_f32(ptr(P), ptr(R), ptr(G), _optr(o["dP"]), _optr(o["dR"]), int(transposed), b, n,
                                                            self._st()), "so3_rotate_clouds_bwd_f32")
         return o
 
     def kabsch_bwd(self, P, Q, H, gR, gH, want=("dP", "dQ")):
         b, n = P.shape[:2]
         o = {k: self._out(b, n, 3) if k in want else None for k in ("dP", "dQ")}
-        self._lib.check(self.lib.so3_kabsch_bwd_f32(_ptr(P), _ptr(Q), _ptr(H), _ptr(gR), _ptr(gH), _optr(o["dP"]), _optr(o["dQ"]), b, n, self._st()),
+        self._lib.check(self.lib.so3_kabsch_bwd_f32(ptr(P), ptr(Q), ptr(H), ptr(gR), ptr(gH), _optr(o["dP"]), _optr(o["dQ"]), b, n, self._st()),
                         "so3_kabsch_bwd_f32")
         return o
 
@@ -127,7 +116,7 @@ class GradAbi:
         b, n = P.shape[:2]
         o = {"R": self._out(b, 3, 3), "t": self._out(b, 3), "H": self._out(b, 3, 3) if "H" in want else None,
              "stats": self._out(b, 7) if "stats" in want else None}
-        self._lib.check(self.lib.so3_rigid_align_f32(_ptr(P), _ptr(Q), _ptr(w), o["R"].ptr, o["t"].ptr, _optr(o["H"]), _optr(o["stats"]), b, n, self._st()),
+        self._lib.check(self.lib.so3_rigid_align_f32(ptr(P), ptr(Q), ptr(w), o["R"].ptr, o["t"].ptr, _optr(o["H"]), _optr(o["stats"]), b, n, self._st()),
                         "so3_rigid_align_f32")
         return o
 
@@ -135,7 +124,7 @@ class GradAbi:
         b, n = P.shape[:2]
         o = {"dP": self._out(b, n, 3) if "dP" in want else None, "dQ": self._out(b, n, 3) if "dQ" in want else None,
              "dw": self._out(b, n) if "dw" in want else None}
-        self._lib.check(self.lib.so3_rigid_align_bwd_f32(_ptr(P), _ptr(Q), _ptr(w), _ptr(H), _ptr(R), _ptr(stats), _ptr(gR), _ptr(gt), _ptr(gH),
+        self._lib.check(self.lib.so3_rigid_align_bwd_f32(ptr(P), ptr(Q), ptr(w), ptr(H), ptr(R), ptr(stats), ptr(gR), ptr(gt), ptr(gH),
                                                          _optr(o["dP"]), _optr(o["dQ"]), _optr(o["dw"]), b, n, self._st()), "so3_rigid_align_bwd_f32")
         return o
 
@@ -443,7 +432,7 @@ def test_no_clouds_and_no_points(dev):
     lib, st = abi.lib, abi._st()
     b = 5
     x = {k: torch.ones(b, 8, device=dev) for k in "abcdefghi"}
-    p = [_ptr(v) for v in x.values()]
+    p = [ptr(v) for v in x.values()]
     for bb, nn in ((0, 4), (b, 0)):
         o = {k: Out(dev, (b, 4, 3), True) for k in ("dP", "dQ", "dw", "R", "t", "H", "stats", "dR")}
         assert lib.so3_kabsch_bwd_f32(p[0], p[1], p[2], p[3], p[4], o["dP"].ptr, o["dQ"].ptr, bb, nn, st) == 0

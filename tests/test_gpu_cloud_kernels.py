@@ -27,19 +27,13 @@ import numpy as np
 import pytest
 import torch
 
+from support import dev, ptr, to_device  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24
 CANARY = 0x7FC5A5A5          # a NaN whose payload no arithmetic produces: an output slot that still holds it was not written
 PAD = 67                     # floats in front of and behind a guarded output: 268 bytes, so the output is 4-byte and not 16-byte aligned
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from poseestimation_amd import _lib
-    _lib.load()
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")
@@ -83,14 +77,6 @@ class Out:
         return (self.t if index is None else self.t[index]).cpu().numpy()
 
 
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _d(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-
-
 class Abi:
     """The seven entry points over device tensors; every output is an Out."""
 
@@ -107,25 +93,25 @@ class Abi:
     def kabsch(self, P, Q):
         b, n = P.shape[:2]
         R, H = self._out(b, 3, 3), self._out(b, 3, 3)
-        self._lib.check(self.lib.so3_kabsch_f32(_ptr(P), _ptr(Q), R.ptr, H.ptr, b, n, self._st()), "so3_kabsch_f32")
+        self._lib.check(self.lib.so3_kabsch_f32(ptr(P), ptr(Q), R.ptr, H.ptr, b, n, self._st()), "so3_kabsch_f32")
         return R, H
 
     def synth(self, P, Rgt, sigma, seed):
         b, n = P.shape[:2]
         R, H = self._out(b, 3, 3), self._out(b, 3, 3)
-        self._lib.check(self.lib.so3_kabsch_synth_f32(_ptr(P), _ptr(Rgt), sigma, seed, R.ptr, H.ptr, b, n, self._st()), "so3_kabsch_synth_f32")
+        self._lib.check(self.lib.so3_kabsch_synth_f32(ptr(P), ptr(Rgt), sigma, seed, R.ptr, H.ptr, b, n, self._st()), "so3_kabsch_synth_f32")
         return R, H
 
     def rotate(self, P, R, transposed):
         b, n = P.shape[:2]
         out = self._out(b, 3, n) if transposed else self._out(b, n, 3)
-        self._lib.check(self.lib.so3_rotate_clouds_f32(_ptr(P), _ptr(R), out.ptr, int(transposed), b, n, self._st()), "so3_rotate_clouds_f32")
+        self._lib.check(self.lib.so3_rotate_clouds_f32(ptr(P), ptr(R), out.ptr, int(transposed), b, n, self._st()), "so3_rotate_clouds_f32")
         return out
 
     def normalize(self, P):
         b, n = P.shape[:2]
         out, cen, scl = self._out(b, n, 3), self._out(b, 3), self._out(b)
-        self._lib.check(self.lib.so3_pc_normalize_f32(_ptr(P), out.ptr, cen.ptr, scl.ptr, b, n, self._st()), "so3_pc_normalize_f32")
+        self._lib.check(self.lib.so3_pc_normalize_f32(ptr(P), out.ptr, cen.ptr, scl.ptr, b, n, self._st()), "so3_pc_normalize_f32")
         return out, cen, scl
 
     def add(self, kind, Tgt, Tpred, pts, grad_scale=1.0):
@@ -135,11 +121,11 @@ class Abi:
         dT = self._out(b, 4, 4)
         if kind == "dis":
             dists = None
-            code = self.lib.so3_add_l1_disentangled_f32(_ptr(Tpred), _ptr(Tgt), _ptr(pts), _ptr(loss), dT.ptr, grad_scale, b, n, self._st())
+            code = self.lib.so3_add_l1_disentangled_f32(ptr(Tpred), ptr(Tgt), ptr(pts), ptr(loss), dT.ptr, grad_scale, b, n, self._st())
         else:
             dists = self._out(b)
             fn = self.lib.so3_add_l1_f32 if kind == "l1" else self.lib.so3_add_l2_f32
-            code = fn(_ptr(Tgt), _ptr(Tpred), _ptr(pts), dists.ptr, _ptr(loss), dT.ptr, grad_scale, b, n, self._st())
+            code = fn(ptr(Tgt), ptr(Tpred), ptr(pts), dists.ptr, ptr(loss), dT.ptr, grad_scale, b, n, self._st())
         self._lib.check(code, "so3_add_%s_f32" % kind)
         return dists, loss.cpu().numpy(), dT
 
@@ -309,21 +295,21 @@ def run_part(abi, dev, data, part, label, sigma=0.01, seed=1234):
     float64."""
     so = _so()
     label = "%s %s" % (label, part)
-    P = _d(data["P"], dev)
+    P = to_device(data["P"], dev)
     if part == "kabsch":
-        R, H = abi.kabsch(P, _d(data["Q"], dev))
+        R, H = abi.kabsch(P, to_device(data["Q"], dev))
         check_h_and_r(H.get(), R.get(), data["P"], data["Q"], label)
     elif part in ("synth0", "synth1"):
         sg = float(np.float32(sigma)) if part == "synth1" else 0.0           # the ABI takes sigma as a float32: the reference gets that value
-        R, H = abi.synth(P, _d(data["Rgt"], dev), sg, seed)
+        R, H = abi.synth(P, to_device(data["Rgt"], dev), sg, seed)
         check_h_and_r(H.get(), R.get(), data["P"], so.synth_pairs_np(data["P"], data["Rgt"], sg, seed), label, synth=(data["Rgt"], sg))
     elif part == "clouds":
-        Rgt = _d(data["Rgt"], dev)
+        Rgt = to_device(data["Rgt"], dev)
         check_rotated(abi.rotate(P, Rgt, False).get(), abi.rotate(P, Rgt, True).get(), data["P"], data["Rgt"], label)
         out, cen, scl = abi.normalize(P)
         check_normalized(out.get(), cen.get(), scl.get(), data["P"], label)
     else:
-        dists, loss, dT = abi.add(part, _d(data["Tgt"], dev), _d(data["Tpred"], dev), P)
+        dists, loss, dT = abi.add(part, to_device(data["Tgt"], dev), to_device(data["Tpred"], dev), P)
         worst = check_add(part, None if dists is None else dists.get(), loss, dT.get(), data["Tgt"], data["Tpred"], data["P"], label)
         print("%-44s B %6d N %4d  per-sample gradient err/bound %.3f" % (label, len(data["P"]), data["P"].shape[1], worst))
     torch.cuda.synchronize()
@@ -367,10 +353,10 @@ def test_zero_points_are_refused_with_nothing_written(dev):
     P, T = torch.zeros(4, 1, 3, device=dev), torch.eye(4, device=dev).repeat(4, 1, 1).contiguous()
     out, cen, scl, dists, dT = Out(dev, (4, 1, 3), True), Out(dev, (4, 3), True), Out(dev, (4,), True), Out(dev, (4,), True), Out(dev, (4, 4, 4), True)
     loss = torch.full((3,), float("nan"), dtype=torch.float64, device=dev)
-    assert lib.so3_pc_normalize_f32(_ptr(P), out.ptr, cen.ptr, scl.ptr, 4, 0, st) != 0
-    assert lib.so3_add_l1_f32(_ptr(T), _ptr(T), _ptr(P), dists.ptr, _ptr(loss), dT.ptr, 1.0, 4, 0, st) != 0
-    assert lib.so3_add_l2_f32(_ptr(T), _ptr(T), _ptr(P), dists.ptr, _ptr(loss), dT.ptr, 1.0, 4, 0, st) != 0
-    assert lib.so3_add_l1_disentangled_f32(_ptr(T), _ptr(T), _ptr(P), _ptr(loss), dT.ptr, 1.0, 4, 0, st) != 0
+    assert lib.so3_pc_normalize_f32(ptr(P), out.ptr, cen.ptr, scl.ptr, 4, 0, st) != 0
+    assert lib.so3_add_l1_f32(ptr(T), ptr(T), ptr(P), dists.ptr, ptr(loss), dT.ptr, 1.0, 4, 0, st) != 0
+    assert lib.so3_add_l2_f32(ptr(T), ptr(T), ptr(P), dists.ptr, ptr(loss), dT.ptr, 1.0, 4, 0, st) != 0
+    assert lib.so3_add_l1_disentangled_f32(ptr(T), ptr(T), ptr(P), ptr(loss), dT.ptr, 1.0, 4, 0, st) != 0
     torch.cuda.synchronize()
     assert all(o.untouched() for o in (out, cen, scl, dists, dT)) and bool(torch.isnan(loss).all().item())
 
@@ -423,7 +409,7 @@ def test_a_cloud_does_not_depend_on_where_it_sits(dev, wave_slots, n):
     leave the other rows' bits alone, that is its own property, which test_a_row_does_not_depend_on_its_neighbours pins for K1."""
     w = wave_slots
     data = make_batch(40, n, 31 + n)
-    small = {k: _d(v, dev) for k, v in data.items()}
+    small = {k: to_device(v, dev) for k, v in data.items()}
     abi = Abi(dev)
     alone = _family_outputs(abi, small)
     h_ref = _so().cross_covariance_np(data["P"], data["Q"])
@@ -460,7 +446,7 @@ def test_off_centre_clouds(dev, offset):
     abi = Abi(dev, guarded=True)
     for b, n in ((5, 65), (67, 513), (3, 1025)):
         data = make_batch(b, n, int(offset) + n, offset=offset)
-        P, Q, Rgt = (_d(data[k], dev) for k in ("P", "Q", "Rgt"))
+        P, Q, Rgt = (to_device(data[k], dev) for k in ("P", "Q", "Rgt"))
         R, H = abi.kabsch(P, Q)
         h, r = H.get(), R.get()
         bound = h_bound(data["P"], data["Q"])
@@ -481,7 +467,7 @@ def test_add_with_a_translation_far_larger_than_the_cloud(dev, n):
     abi = Abi(dev, guarded=True)
     for b in (5, 67):
         data = make_batch(b, n, 5 * n + b, extent=0.05, dt_shift=1e3)
-        Tgt, Tpred, P = (_d(data[k], dev) for k in ("Tgt", "Tpred", "P"))
+        Tgt, Tpred, P = (to_device(data[k], dev) for k in ("Tgt", "Tpred", "P"))
         for kind in ("l1", "dis", "l2"):
             dists, loss, dT = abi.add(kind, Tgt, Tpred, P)
             worst = check_add(kind, None if dists is None else dists.get(), loss, dT.get(), data["Tgt"], data["Tpred"], data["P"], "far %s N %d B %d" % (kind, n, b))
@@ -498,7 +484,7 @@ def test_constant_clouds_normalise_as_numpy_does(dev, n):
     with np.errstate(invalid="ignore", divide="ignore"):
         rn, rc, rs = _so().pc_normalize_np(P)
     assert np.isnan(rn).all() and (rs == 0).all() and np.array_equal(rc, pts.astype(np.float64))
-    out, cen, scl = Abi(dev, guarded=True).normalize(_d(P, dev))
+    out, cen, scl = Abi(dev, guarded=True).normalize(to_device(P, dev))
     assert np.array_equal(cen.get(), pts) and (scl.get() == 0).all() and np.isnan(out.get()).all()
 
 
@@ -531,9 +517,9 @@ def test_non_finite_points_stay_in_their_cloud_and_propagate_as_in_numpy(dev, wa
         d, _, _ = add_terms(data["Tgt"][rows], data["Tpred"][rows], dirty[rows], False)
         l1_ref, l2_ref = np.abs(d).mean((1, 2)), np.linalg.norm(d, axis=-1).mean(1)
     abi = Abi(dev)
-    dev_in = {k: _d(v, dev) for k, v in data.items()}
+    dev_in = {k: to_device(v, dev) for k, v in data.items()}
     clean = _family_outputs(abi, dev_in)
-    dev_in["P"] = _d(dirty, dev)
+    dev_in["P"] = to_device(dirty, dev)
     got = _family_outputs(abi, dev_in)
     for key, v in clean.items():
         if key.startswith("synth"):

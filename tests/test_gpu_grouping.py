@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import grouping_ref as ref
+from support import dev, last_kernel, median_ms, ptr, to_device  # noqa: F401
 import test_grouping_host as host
 
 pytestmark = pytest.mark.gpu
@@ -19,29 +20,8 @@ SEEN = set()
 
 
 @pytest.fixture(scope="module")
-def dev():
-    from poseestimation_amd import _lib
-    _lib.load()
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
 def g25():
     return ref.cases(ref.g25())
-
-
-def _d(a, dev, dtype=np.float32):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _last_kernel():
-    from poseestimation_amd import _lib
-    return _lib.load().so3_last_kernel().decode()
 
 
 def _stream():
@@ -50,8 +30,8 @@ def _stream():
 
 def surface_fwd(xyz, centres, feat, idx, channels_first, features_first, dev):
     import poseestimation_amd as pa
-    out = pa.group_points(_d(xyz, dev), _d(centres, dev), _d(feat, dev), _d(idx, dev, np.int64), channels_first, features_first)
-    assert _last_kernel() == "k_group_fwd<%s>" % ("true" if channels_first else "false")
+    out = pa.group_points(to_device(xyz, dev), to_device(centres, dev), to_device(feat, dev), to_device(idx, dev, np.int64), channels_first, features_first)
+    assert last_kernel() == "k_group_fwd<%s>" % ("true" if channels_first else "false")
     assert out.dtype == torch.float32 and out.is_contiguous() and not out.requires_grad
     return out.cpu().numpy()
 
@@ -63,8 +43,8 @@ def surface_bwd(grad, idx, n, d, channels_first, features_first, sel, dev):
     xyz = torch.zeros(b, n, 3, device=dev, requires_grad=sel[0])
     centres = torch.zeros(b, s, 3, device=dev, requires_grad=sel[1])
     feat = torch.zeros((b, d, n) if channels_first else (b, n, d), device=dev, requires_grad=sel[2]) if d else None
-    out = pa.group_points(xyz, centres, feat, _d(idx.clip(-2 ** 31, 2 ** 31 - 1), dev, np.int32), channels_first, features_first)
-    out.backward(_d(grad, dev))
+    out = pa.group_points(xyz, centres, feat, to_device(idx.clip(-2 ** 31, 2 ** 31 - 1), dev, np.int32), channels_first, features_first)
+    out.backward(to_device(grad, dev))
     return tuple(None if t is None or t.grad is None else t.grad.cpu().numpy() for t in (xyz, centres, feat))
 
 
@@ -74,11 +54,11 @@ def abi_fwd(xyz, centres, feat, idx, channels_first, features_first, dev):
     lib = _lib.load()
     b, n, s, k = xyz.shape[0], xyz.shape[1], idx.shape[1], idx.shape[2]
     d = 0 if feat is None else feat.shape[1 if channels_first else 2]
-    x, c, f, i = _d(xyz, dev), _d(centres, dev), _d(feat, dev), _d(idx, dev, np.int32)
+    x, c, f, i = to_device(xyz, dev), to_device(centres, dev), to_device(feat, dev), to_device(idx, dev, np.int32)
     out = torch.full((b, 3 + d, k, s) if channels_first else (b, s, k, 3 + d), float("nan"), device=dev)
-    _lib.check(lib.so3_group_points_f32(_ptr(x), _ptr(c), _ptr(f), _ptr(i), _ptr(out), int(features_first), int(channels_first), b, n, s, k, d, _stream()),
+    _lib.check(lib.so3_group_points_f32(ptr(x), ptr(c), ptr(f), ptr(i), ptr(out), int(features_first), int(channels_first), b, n, s, k, d, _stream()),
                "so3_group_points_f32")
-    SEEN.add(_last_kernel())
+    SEEN.add(last_kernel())
     return out.cpu().numpy()
 
 
@@ -86,17 +66,17 @@ def abi_bwd(grad, idx, n, d, channels_first, features_first, sel, dev):
     from poseestimation_amd import _lib
     lib = _lib.load()
     b, s, k = idx.shape
-    g, i = _d(grad, dev), _d(idx.clip(-2 ** 31, 2 ** 31 - 1), dev, np.int32)
+    g, i = to_device(grad, dev), to_device(idx.clip(-2 ** 31, 2 ** 31 - 1), dev, np.int32)
     gx = torch.full((b, n, 3), float("nan"), device=dev) if sel[0] else None
     gc = torch.full((b, s, 3), float("nan"), device=dev) if sel[1] else None
     gf = torch.full((b, d, n) if channels_first else (b, n, d), float("nan"), device=dev) if sel[2] and d else None
-    _lib.check(lib.so3_group_points_bwd_f32(_ptr(g), _ptr(i), _ptr(gx), _ptr(gc), _ptr(gf), int(features_first), int(channels_first), b, n, s, k, d,
+    _lib.check(lib.so3_group_points_bwd_f32(ptr(g), ptr(i), ptr(gx), ptr(gc), ptr(gf), int(features_first), int(channels_first), b, n, s, k, d,
                                             _stream()), "so3_group_points_bwd_f32")
-    SEEN.add(_last_kernel())
+    SEEN.add(last_kernel())
     if gx is not None or gf is not None:
-        assert _last_kernel() == host.bwd_kernel(d, channels_first)
+        assert last_kernel() == host.bwd_kernel(d, channels_first)
     elif gc is not None:
-        assert _last_kernel() == "k_group_centres_bwd<%s>" % ("true" if channels_first else "false")
+        assert last_kernel() == "k_group_centres_bwd<%s>" % ("true" if channels_first else "false")
     return tuple(None if t is None else t.cpu().numpy() for t in (gx, gc, gf))
 
 
@@ -141,10 +121,10 @@ def test_autograd_with_a_non_contiguous_grad_out(dev, cf, ff):
     idx[1, 3] = n                                                                    # an empty ball
     shape = (b, 3 + d, k, s) if cf else (b, s, k, 3 + d)
     wide = rng.standard_normal(shape[:-1] + (2 * shape[-1],)).astype(np.float32)
-    ts = [_d(a, dev).requires_grad_(True) for a in (xyz, centres, feat)]
-    out = pa.group_points(ts[0], ts[1], ts[2], _d(idx, dev, np.int64), cf, ff)
+    ts = [to_device(a, dev).requires_grad_(True) for a in (xyz, centres, feat)]
+    out = pa.group_points(ts[0], ts[1], ts[2], to_device(idx, dev, np.int64), cf, ff)
     assert out.requires_grad and out.shape == shape
-    cot = _d(wide, dev)[..., ::2]
+    cot = to_device(wide, dev)[..., ::2]
     assert not cot.is_contiguous()
     grads = torch.autograd.grad(out, ts, cot)
     want = ref.backward(wide[..., ::2], idx, n, cf, ff, np.float64)
@@ -155,14 +135,14 @@ def test_autograd_with_a_non_contiguous_grad_out(dev, cf, ff):
     assert not grads[1][1, 3].any()                                                  # the empty ball gives its centre nothing
     # only what is needed is requested: a features-only graph, and one without any input that requires grad
     f = ts[2].detach().clone().requires_grad_(True)
-    only = torch.autograd.grad(pa.group_points(ts[0].detach(), ts[1].detach(), f, _d(idx, dev, np.int64), cf, ff), [f], cot)[0]
+    only = torch.autograd.grad(pa.group_points(ts[0].detach(), ts[1].detach(), f, to_device(idx, dev, np.int64), cf, ff), [f], cot)[0]
     assert torch.equal(only, grads[2])
-    assert not pa.group_points(ts[0].detach(), ts[1].detach(), f.detach(), _d(idx, dev, np.int64), cf, ff).requires_grad
+    assert not pa.group_points(ts[0].detach(), ts[1].detach(), f.detach(), to_device(idx, dev, np.int64), cf, ff).requires_grad
     x = ts[0].detach().clone().requires_grad_(True)
-    out = pa.group_points(x, ts[1].detach(), None, _d(idx, dev, np.int32), cf, ff)
+    out = pa.group_points(x, ts[1].detach(), None, to_device(idx, dev, np.int32), cf, ff)
     (gx,) = torch.autograd.grad(out, [x], torch.ones_like(out), create_graph=True)    # create_graph alone runs as always
     with pytest.raises(RuntimeError, match="differentiate twice"):
-        torch.autograd.grad(pa.group_points(x, ts[1].detach(), None, _d(idx, dev, np.int32), cf, ff), [x], (x * 1.0).sum() * torch.ones_like(out), create_graph=True)
+        torch.autograd.grad(pa.group_points(x, ts[1].detach(), None, to_device(idx, dev, np.int32), cf, ff), [x], (x * 1.0).sum() * torch.ones_like(out), create_graph=True)
 
 
 # ---- determinism ------------------------------------------------------------------------------------------------------------------
@@ -171,8 +151,8 @@ def test_two_calls_give_the_same_bits_and_a_graph_replays_them(dev, g25):
     from poseestimation_amd import _lib
     lib = _lib.load()
     n, s, d = ref.N_FIXTURE, ref.S_FIXTURE, ref.D_FIXTURE
-    xyz, centres = _d(g25["xyz"], dev), _d(g25["msg"]["new_xyz"].transpose(0, 2, 1), dev)
-    feats = [_d(g25["points"], dev), _d(g25["points"].transpose(0, 2, 1), dev)]
+    xyz, centres = to_device(g25["xyz"], dev), to_device(g25["msg"]["new_xyz"].transpose(0, 2, 1), dev)
+    feats = [to_device(g25["points"], dev), to_device(g25["points"].transpose(0, 2, 1), dev)]
     wide = torch.randn(2, n, 40, generator=torch.Generator().manual_seed(25)).to(dev)             # a wide-kernel case beside the narrow one
     jobs = []
     for i, idx in enumerate(g25["msg"]["idx"]):
@@ -181,14 +161,14 @@ def test_two_calls_give_the_same_bits_and_a_graph_replays_them(dev, g25):
             for f in (feats[cf], wide.transpose(1, 2).contiguous() if cf else wide):
                 c = 3 + (f.shape[1] if cf else f.shape[2])
                 g = torch.randn((2, c, k, s) if cf else (2, s, k, c), generator=torch.Generator().manual_seed(26 + i)).to(dev)
-                jobs.append((f, _d(idx, dev, np.int32), g, cf, k, c - 3))
+                jobs.append((f, to_device(idx, dev, np.int32), g, cf, k, c - 3))
 
     def call():
         out = []
         for f, idx, g, cf, k, dd in jobs:
             out.append(pa.group_points(xyz, centres, f, idx, bool(cf), True))
             gx, gc, gf = torch.empty(2, n, 3, device=dev), torch.empty(2, s, 3, device=dev), torch.empty_like(f)
-            _lib.check(lib.so3_group_points_bwd_f32(_ptr(g), _ptr(idx), _ptr(gx), _ptr(gc), _ptr(gf), 1, cf, 2, n, s, k, dd, _stream()), "so3_group_points_bwd_f32")
+            _lib.check(lib.so3_group_points_bwd_f32(ptr(g), ptr(idx), ptr(gx), ptr(gc), ptr(gf), 1, cf, 2, n, s, k, dd, _stream()), "so3_group_points_bwd_f32")
             out += [gx, gc, gf]
         return out
 
@@ -215,12 +195,12 @@ def test_two_calls_give_the_same_bits_and_a_graph_replays_them(dev, g25):
 # ---- the composition ------------------------------------------------------------------------------------------------------------
 def test_set_abstraction_groups_are_the_composition(dev, g25):
     import poseestimation_amd as pa
-    xyz, pts = _d(g25["xyz"], dev), _d(g25["points"], dev)
+    xyz, pts = to_device(g25["xyz"], dev), to_device(g25["points"], dev)
     x_cf, p_cf = xyz.transpose(1, 2).contiguous(), pts.transpose(1, 2).contiguous()
     s = ref.S_FIXTURE
     (r0, k0), (r1, k1) = ref.RADII
     for tag in ("sa", "msg"):
-        start = _d(g25[tag]["fps"][:, 0], dev, np.int64)
+        start = to_device(g25[tag]["fps"][:, 0], dev, np.int64)
         fps = pa.farthest_point_sample(xyz, s, start)
         assert np.array_equal(fps.cpu().numpy(), g25[tag]["fps"])
         centres = pa.index_points(xyz, fps)
@@ -239,10 +219,10 @@ def test_set_abstraction_groups_are_the_composition(dev, g25):
                 idx = pa.query_ball_point(r, k, xyz, centres)
                 assert got.shape == (2, ref.D_FIXTURE + 3, k, s)
                 assert torch.equal(got, pa.group_points(xyz, centres, p_cf, idx, channels_first=True, features_first=True))
-        assert new_xyz.shape == (2, 3, s) and np.array_equal(host.bits(new_xyz.cpu().numpy()), host.bits(g25[tag]["new_xyz"]))
-    xa, pa_ = _d(g25["xyz_all"], dev), _d(g25["points_all"], dev)
+        assert new_xyz.shape == (2, 3, s) and np.array_equal(host.f32_bits(new_xyz.cpu().numpy()), host.f32_bits(g25[tag]["new_xyz"]))
+    xa, pa_ = to_device(g25["xyz_all"], dev), to_device(g25["points_all"], dev)
     new_xyz, got = pa.set_abstraction_group(None, None, None, xa.transpose(1, 2), pa_.transpose(1, 2), group_all=True)
-    assert new_xyz.shape == (2, 3, 1) and not new_xyz.any() and np.array_equal(host.bits(got.cpu().numpy()), host.bits(g25["all"]["t"]))
+    assert new_xyz.shape == (2, 3, 1) and not new_xyz.any() and np.array_equal(host.f32_bits(got.cpu().numpy()), host.f32_bits(g25["all"]["t"]))
     zeros, grouped = pa.sample_and_group_all(xa, pa_)
     assert torch.equal(grouped.permute(0, 3, 2, 1), got) and zeros.shape == (2, 1, 3) and zeros.is_cuda
     assert pa.set_abstraction_group(None, None, None, xa.transpose(1, 2), None, group_all=True)[1].shape == (2, 3, ref.N_ALL, 1)
@@ -254,10 +234,10 @@ def test_gradients_flow_through_the_layer_functions(dev, g25):
     import poseestimation_amd as pa
     n, d, s = ref.N_FIXTURE, ref.D_FIXTURE, ref.S_FIXTURE
     c = g25["msg"]
-    x = _d(g25["xyz"].transpose(0, 2, 1), dev).requires_grad_(True)
-    p = _d(g25["points"].transpose(0, 2, 1), dev).requires_grad_(True)
-    new_xyz, groups = pa.set_abstraction_msg_group(s, [r for r, _ in ref.RADII], [k for _, k in ref.RADII], x, p, start=_d(c["fps"][:, 0], dev, np.int64))
-    sum((t * _d(ref.seeded_g(i, tuple(t.shape)), dev)).sum() for i, t in enumerate(groups)).backward()
+    x = to_device(g25["xyz"].transpose(0, 2, 1), dev).requires_grad_(True)
+    p = to_device(g25["points"].transpose(0, 2, 1), dev).requires_grad_(True)
+    new_xyz, groups = pa.set_abstraction_msg_group(s, [r for r, _ in ref.RADII], [k for _, k in ref.RADII], x, p, start=to_device(c["fps"][:, 0], dev, np.int64))
+    sum((t * to_device(ref.seeded_g(i, tuple(t.shape)), dev)).sum() for i, t in enumerate(groups)).backward()
     wants = [ref.backward(ref.seeded_g(i, t.shape), idx, n, True, True, np.float64) for i, (idx, t) in enumerate(zip(c["idx"], c["t"]))]
     mag, terms = sum(w["mag_xyz"] for w in wants), sum(w["hits"] for w in wants)[:, :, None].astype(np.float64)
     for b in range(2):
@@ -293,21 +273,6 @@ def test_errors(dev):
 
 
 # ---- the speed condition --------------------------------------------------------------------------------------------------------
-def _median_ms(fn):
-    for _ in range(5):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(20):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        times.append(e0.elapsed_time(e1))
-    return float(np.median(times))
-
-
 def torch_group(xyz, new_xyz, points, idx):
     """The torch spelling of point_cloud/pointnet_utils.py:117-122 and :185 on the device: index_points twice, the subtraction, cat, and
     the permute made contiguous as the first Conv2d makes it."""
@@ -336,14 +301,14 @@ def test_grouping_is_not_slower_than_the_torch_spelling(dev):
     theirs = lambda: torch_group(xyz, centres, pts, idx)
     with torch.no_grad():
         assert torch.equal(ours(), theirs())
-        ours_f, theirs_f = _median_ms(ours), _median_ms(theirs)
+        ours_f, theirs_f = median_ms(ours), median_ms(theirs)
 
     def both(fn):
         for t in (xyz, centres, pts, pts_cf):
             t.grad = None
         fn().backward(cot)
 
-    ours_fb, theirs_fb = _median_ms(lambda: both(ours)), _median_ms(lambda: both(theirs))
+    ours_fb, theirs_fb = median_ms(lambda: both(ours)), median_ms(lambda: both(theirs))
     line = ("group_points 32x1024, 512 centres, K=64, D=3, channel-first: forward %.4f ms, torch spelling %.4f ms (x%.1f); forward + backward %.4f ms, "
             "torch %.4f ms (x%.1f)" % (ours_f, theirs_f, theirs_f / ours_f, ours_fb, theirs_fb, theirs_fb / ours_fb))
     print(line)

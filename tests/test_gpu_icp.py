@@ -10,17 +10,10 @@ import pytest
 import torch
 
 import icp_ref as ref
+from support import dev, median_ms, ptr, to_device  # noqa: F401
 import test_icp_host as host
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from poseestimation_amd import _lib
-    _lib.load()
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")
@@ -28,17 +21,9 @@ def g21_cases():
     return ref.cases(ref.g21())
 
 
-def _d(a, dev):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
 def surface_run(c, dev):
     import poseestimation_amd as pa
-    P, Q, w, R0, t0 = (_d(c[k], dev) for k in ("P", "Q", "w", "R0", "t0"))
+    P, Q, w, R0, t0 = (to_device(c[k], dev) for k in ("P", "Q", "w", "R0", "t0"))
     if c["kind"] == "search":
         dist, idx = pa.nearest_neighbors(P, Q)
         assert dist.shape == idx.shape == (c["b"], c["n"]) and dist.dtype == torch.float32 and idx.dtype == torch.int64
@@ -56,24 +41,24 @@ def abi_run(c, dev):
     from poseestimation_amd import _lib
     lib = _lib.load()
     b, n, m, it = c["b"], c["n"], c["m"], c["iterations"]
-    P, Q, w, T0 = _d(c["P"], dev), _d(c["Q"], dev), _d(c["w"], dev), _d(host.initial_rows(c), dev)
+    P, Q, w, T0 = to_device(c["P"], dev), to_device(c["Q"], dev), to_device(c["w"], dev), to_device(host.initial_rows(c), dev)
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     out = {"dist": torch.full((b, n), np.nan, device=dev), "nearest": torch.full((b, n), -1, dtype=torch.int32, device=dev)}
     stride = 0 if c["shared"] else 3 * m
     if c["kind"] == "search":
-        _lib.check(lib.so3_nearest_f32(_ptr(P), _ptr(Q), stride, _ptr(out["dist"]), _ptr(out["nearest"]), b, n, m, st), "so3_nearest_f32")
+        _lib.check(lib.so3_nearest_f32(ptr(P), ptr(Q), stride, ptr(out["dist"]), ptr(out["nearest"]), b, n, m, st), "so3_nearest_f32")
         d2 = torch.full((b, n), np.nan, device=dev)                                        # nearest is optional
-        _lib.check(lib.so3_nearest_f32(_ptr(P), _ptr(Q), stride, _ptr(d2), None, b, n, m, st), "so3_nearest_f32")
+        _lib.check(lib.so3_nearest_f32(ptr(P), ptr(Q), stride, ptr(d2), None, b, n, m, st), "so3_nearest_f32")
         assert torch.equal(d2, out["dist"])
     else:
         out.update(R=torch.full((b, 3, 3), np.nan, device=dev), t=torch.full((b, 3), np.nan, device=dev), rmse=torch.full((it, b), np.nan, device=dev),
                    inliers=torch.full((it, b), -1, dtype=torch.int32, device=dev))
         work = torch.full((lib.so3_icp_workspace_bytes(b, n) // 4,), np.nan, device=dev)
         md = -1.0 if c["max_distance"] is None else c["max_distance"]
-        _lib.check(lib.so3_icp_f32(_ptr(P), _ptr(Q), stride, _ptr(w), _ptr(T0), md, it, _ptr(out["R"]), _ptr(out["t"]), _ptr(out["rmse"]), _ptr(out["inliers"]),
-                                   _ptr(out["nearest"]), _ptr(out["dist"]), _ptr(work), b, n, m, st), "so3_icp_f32")
+        _lib.check(lib.so3_icp_f32(ptr(P), ptr(Q), stride, ptr(w), ptr(T0), md, it, ptr(out["R"]), ptr(out["t"]), ptr(out["rmse"]), ptr(out["inliers"]),
+                                   ptr(out["nearest"]), ptr(out["dist"]), ptr(work), b, n, m, st), "so3_icp_f32")
         R2, t2 = torch.full((b, 3, 3), np.nan, device=dev), torch.full((b, 3), np.nan, device=dev)      # every optional output left out
-        _lib.check(lib.so3_icp_f32(_ptr(P), _ptr(Q), stride, _ptr(w), _ptr(T0), md, it, _ptr(R2), _ptr(t2), None, None, None, None, _ptr(work), b, n, m, st),
+        _lib.check(lib.so3_icp_f32(ptr(P), ptr(Q), stride, ptr(w), ptr(T0), md, it, ptr(R2), ptr(t2), None, None, None, None, ptr(work), b, n, m, st),
                    "so3_icp_f32")
         assert torch.equal(R2, out["R"]) and torch.equal(t2, out["t"])
     return {k: v.cpu().numpy() for k, v in out.items()}
@@ -114,7 +99,7 @@ def test_batch_shapes_against_float64(dev, b, n):
     ang = np.deg2rad(2.0)
     R0 = np.broadcast_to(np.array([[np.cos(ang), -np.sin(ang), 0], [np.sin(ang), np.cos(ang), 0], [0, 0, 1.0]], np.float32), (b, 3, 3)).copy()
     t0 = np.full((b, 3), 0.02, np.float32)
-    R, t, info = pa.icp_align(_d(P, dev), _d(Q, dev), _d(R0, dev), _d(t0, dev), iterations=1, weights=_d(w, dev), return_info=True)
+    R, t, info = pa.icp_align(to_device(P, dev), to_device(Q, dev), to_device(R0, dev), to_device(t0, dev), iterations=1, weights=to_device(w, dev), return_info=True)
     name = _lib.load().so3_last_kernel().decode()
     u = _rule(b, n, torch.cuda.get_device_properties(dev).multi_processor_count)
     assert name == "k_icp_step<true, false, true, %d>" % u, (name, u)
@@ -125,7 +110,7 @@ def test_batch_shapes_against_float64(dev, b, n):
     print("B=%d N=%d U=%d  " % (b, n, u) + "  ".join("%s %.2e" % kv for kv in f.items()))
     for k, v in f.items():
         assert v <= host.bounds()[k], (k, v, host.bounds()[k])
-    dist, idx = pa.nearest_neighbors(_d(ref.pose_points(P, R64, t64), dev), _d(Q, dev))          # the search alone, same U
+    dist, idx = pa.nearest_neighbors(to_device(ref.pose_points(P, R64, t64), dev), to_device(Q, dev))          # the search alone, same U
     assert _lib.load().so3_last_kernel().decode() == "k_icp_step<false, false, false, %d>" % u
     f = host.search_figures(ref.pose_points(P, R64, t64).astype(np.float32), Q, dist.cpu().numpy(), idx.cpu().numpy(), device=dev)
     assert max(f.values()) <= host.SEARCH_TOL, f
@@ -175,7 +160,7 @@ def test_the_documented_gradient_path(dev, g21_cases):
     """rigid_align on the returned correspondences reproduces the last step and is differentiable."""
     import poseestimation_amd as pa
     c = next(c for c in g21_cases if c["kind"] == "noise" and c["max_distance"] is not None)
-    P, Q, R0, t0 = (_d(c[k], dev) for k in ("P", "Q", "R0", "t0"))
+    P, Q, R0, t0 = (to_device(c[k], dev) for k in ("P", "Q", "R0", "t0"))
     R, t, info = pa.icp_align(P, Q, R0, t0, iterations=20, max_distance=c["max_distance"], return_info=True)
     Pg = P.clone().requires_grad_(True)
     w = (info["dist"] <= c["max_distance"]).float()
@@ -189,7 +174,7 @@ def test_replay_from_a_graph(dev, g21_cases):
     """One call captured and replayed twice: a single chain of launches, no host synchronisation, the same bits every time."""
     import poseestimation_amd as pa
     c = next(c for c in g21_cases if c["kind"] == "noise" and c["max_distance"] is not None)
-    P, Q, R0, t0 = (_d(c[k], dev) for k in ("P", "Q", "R0", "t0"))
+    P, Q, R0, t0 = (to_device(c[k], dev) for k in ("P", "Q", "R0", "t0"))
     call = lambda: pa.icp_align(P, Q, R0, t0, iterations=5, max_distance=c["max_distance"], return_info=True)
     R, t, info = call()
     eager = [R.clone(), t.clone()] + [info[k].clone() for k in ("rmse", "inliers", "nearest", "dist")]
@@ -212,21 +197,6 @@ def test_replay_from_a_graph(dev, g21_cases):
 
 
 # ---- the speed conditions -------------------------------------------------------------------------------------------------------
-def _median_ms(fn):
-    for _ in range(5):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(20):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        times.append(e0.elapsed_time(e1))
-    return float(np.median(times))
-
-
 def test_icp_is_not_slower_than_the_composition(dev):
     """B = 256, N = M = 1024, HIP events, 5 warm-ups, median of 20, same process.  (a) nearest_neighbors against torch.cdist(X, Y).min(-1);
     (b) icp_align(iterations=10) against what the parent commit offers: cdist -> argmin -> gather -> rigid_align -> apply, ten times."""
@@ -248,10 +218,10 @@ def test_icp_is_not_slower_than_the_composition(dev):
         return R, t
 
     with torch.no_grad():
-        ours_a = _median_ms(lambda: pa.nearest_neighbors(P, Q))
-        theirs_a = _median_ms(lambda: torch.cdist(P, Q).min(-1))
-        ours_b = _median_ms(lambda: pa.icp_align(P, Q, iterations=10))
-        theirs_b = _median_ms(composed)
+        ours_a = median_ms(lambda: pa.nearest_neighbors(P, Q))
+        theirs_a = median_ms(lambda: torch.cdist(P, Q).min(-1))
+        ours_b = median_ms(lambda: pa.icp_align(P, Q, iterations=10))
+        theirs_b = median_ms(composed)
         (R, t), (Rc, tc) = pa.icp_align(P, Q, iterations=10), composed()
     assert (R - Rc).abs().max().item() < 1e-3 and (t - tc).abs().max().item() < 1e-3      # the same quantity (not an accuracy check)
     for line in ("nearest_neighbors B=256 N=M=1024: %.4f ms, torch.cdist(X, Y).min(-1) %.4f ms (x%.1f)" % (ours_a, theirs_a, theirs_a / ours_a),

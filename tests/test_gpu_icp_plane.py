@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import icp_plane_ref as ref
+from support import dev, median_ms, ptr, to_device  # noqa: F401
 import test_icp_plane_host as host
 
 pytestmark = pytest.mark.gpu
@@ -17,24 +18,8 @@ INFO = ("rmse", "rmse_point", "inliers", "solved", "nearest", "dist")
 
 
 @pytest.fixture(scope="module")
-def dev():
-    from poseestimation_amd import _lib
-    _lib.load()
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
 def g30_cases():
     return ref.cases(ref.g30())
-
-
-def _d(a, dev):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def _np(R, t, info):
@@ -43,7 +28,7 @@ def _np(R, t, info):
 
 def surface_call(c, dev, iterations=None, **over):
     import poseestimation_amd as pa
-    args = {k: over[k] if k in over else _d(c[k], dev) for k in ("P", "Q", "Nrm", "R0", "t0", "w")}      # (no copy where a tensor is given: capture)
+    args = {k: over[k] if k in over else to_device(c[k], dev) for k in ("P", "Q", "Nrm", "R0", "t0", "w")}      # (no copy where a tensor is given: capture)
     return pa.icp_align_plane(args["P"], args["Q"], args["Nrm"], args["R0"], args["t0"], iterations=c["iterations"] if iterations is None else iterations,
                               max_distance=c["max_distance"], weights=args["w"], damping=c["damping"], return_info=True)
 
@@ -54,7 +39,7 @@ def surface_run(c, dev):
     it, b, n = c["iterations"], c["b"], c["n"]
     assert R.shape == (b, 3, 3) and t.shape == (b, 3) and all(info[k].shape == (it, b) for k in INFO[:4]) and set(info) == set(INFO)
     assert info["nearest"].dtype == info["inliers"].dtype == torch.int64 and info["solved"].dtype == torch.bool and info["dist"].shape == (b, n)
-    P, Q, N, R0, t0, w = (_d(c[k], dev) for k in ("P", "Q", "Nrm", "R0", "t0", "w"))
+    P, Q, N, R0, t0, w = (to_device(c[k], dev) for k in ("P", "Q", "Nrm", "R0", "t0", "w"))
     R2, t2 = pa.icp_align_plane(P, Q, N, R0, t0, c["iterations"], c["max_distance"], w, c["damping"])           # the same bits from call to call
     assert torch.equal(R2, R) and torch.equal(t2, t)
     return _np(R, t, info)
@@ -66,7 +51,7 @@ def abi_run(c, dev):
     from poseestimation_amd import _lib
     lib = _lib.load()
     b, n, m, it = c["b"], c["n"], c["m"], c["iterations"]
-    P, Q, N, w, T0 = _d(c["P"], dev), _d(c["Q"], dev), _d(c["Nrm"], dev), _d(c["w"], dev), _d(host.initial_rows(c), dev)
+    P, Q, N, w, T0 = to_device(c["P"], dev), to_device(c["Q"], dev), to_device(c["Nrm"], dev), to_device(c["w"], dev), to_device(host.initial_rows(c), dev)
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     f = lambda *shape: torch.full(shape, np.nan, device=dev)
     i = lambda *shape: torch.full(shape, -1, dtype=torch.int32, device=dev)
@@ -77,8 +62,8 @@ def abi_run(c, dev):
     guarded[words:] = 12345.0
     assert guarded.data_ptr() % 16 == 0
     md = -1.0 if c["max_distance"] is None else c["max_distance"]
-    call = lambda R, t, *opt: _lib.check(lib.so3_icp_plane_f32(_ptr(P), _ptr(Q), _ptr(N), 0 if c["shared"] else 3 * m, _ptr(w), _ptr(T0), md, c["damping"], it,
-                                                               _ptr(R), _ptr(t), *(_ptr(o) for o in opt), _ptr(guarded), b, n, m, st), "so3_icp_plane_f32")
+    call = lambda R, t, *opt: _lib.check(lib.so3_icp_plane_f32(ptr(P), ptr(Q), ptr(N), 0 if c["shared"] else 3 * m, ptr(w), ptr(T0), md, c["damping"], it,
+                                                               ptr(R), ptr(t), *(ptr(o) for o in opt), ptr(guarded), b, n, m, st), "so3_icp_plane_f32")
     opt = [out[k] for k in INFO]
     call(out["R"], out["t"], *opt)
     for leave in range(len(opt) + 1):                                                   # every optional output left out, one at a time and all at once
@@ -170,7 +155,7 @@ def test_batch_shapes_against_float64(dev, b, n, m, shared):
     print(c["name"] + " U=%d  " % u + "  ".join("%s %.2e" % kv for kv in f.items()))
     for k, v in f.items():
         assert v <= host.bounds()[k], (k, v, host.bounds()[k])
-    _, _, point = pa.icp_align(*(_d(c[k], dev) for k in ("P", "Q", "R0", "t0")), iterations=1, weights=_d(c["w"], dev), return_info=True)
+    _, _, point = pa.icp_align(*(to_device(c[k], dev) for k in ("P", "Q", "R0", "t0")), iterations=1, weights=to_device(c["w"], dev), return_info=True)
     assert torch.equal(point["nearest"], info["nearest"]) and torch.equal(point["dist"], info["dist"])
     assert (point["rmse"] - info["rmse_point"]).abs().max().item() <= 4 * host.MEASURED["rmse_point"]      # the same sum in another record
 
@@ -193,7 +178,7 @@ def test_a_batch_beyond_the_finish_grid(dev):
         assert v <= host.bounds()[k], (k, v)
     big = {k: (None if c[k] is None else np.concatenate([c[k]] * reps)) for k in ("P", "Q", "Nrm", "R0", "t0", "w")}
     assert base * reps > cus * 16 * 4
-    Rb, tb, ib = surface_call(c, dev, **{k: _d(v, dev) for k, v in big.items()})
+    Rb, tb, ib = surface_call(c, dev, **{k: to_device(v, dev) for k, v in big.items()})
     assert torch.equal(Rb.view(reps, base, 3, 3), R.expand(reps, base, 3, 3)) and torch.equal(tb.view(reps, base, 3), t.expand(reps, base, 3))
     for k in INFO[:4]:
         assert torch.equal(ib[k].view(reps, base), info[k].expand(reps, base)), k
@@ -209,13 +194,13 @@ def test_reversed_batch_two_calls_zero_iterations_and_negated_normals(dev):
     c = dict(_random_case(7, 300, 500, False, 11, trimmed=True), iterations=4)
     first = surface_call(c, dev)
     assert _same(first, surface_call(c, dev))                                           # two calls
-    rev = surface_call(c, dev, **{k: _d(c[k][::-1], dev) for k in ("P", "Q", "Nrm", "R0", "t0", "w")})
+    rev = surface_call(c, dev, **{k: to_device(c[k][::-1], dev) for k in ("P", "Q", "Nrm", "R0", "t0", "w")})
     assert torch.equal(rev[0].flip(0), first[0]) and torch.equal(rev[1].flip(0), first[1])
     assert all(torch.equal(rev[2][k].flip(1 if k in INFO[:4] else 0), first[2][k]) for k in INFO)
     flip = np.where(np.random.default_rng(5).uniform(0, 1, c["Nrm"].shape[:-1] + (1,)) < 0.5, -1.0, 1.0).astype(np.float32)
-    assert _same(first, surface_call(c, dev, Nrm=_d(c["Nrm"] * flip, dev)))              # the normals' signs do not matter
+    assert _same(first, surface_call(c, dev, Nrm=to_device(c["Nrm"] * flip, dev)))              # the normals' signs do not matter
     zero, one = surface_call(c, dev, iterations=0), surface_call(c, dev, iterations=1)
-    assert torch.equal(zero[0], _d(c["R0"], dev)) and torch.equal(zero[1], _d(c["t0"], dev)) and zero[2]["rmse"].shape == (0, 7)
+    assert torch.equal(zero[0], to_device(c["R0"], dev)) and torch.equal(zero[1], to_device(c["t0"], dev)) and zero[2]["rmse"].shape == (0, 7)
     assert torch.equal(zero[2]["nearest"], one[2]["nearest"]) and torch.equal(zero[2]["dist"], one[2]["dist"])      # the first search
     shared = dict(c, Q=c["Q"][0], Nrm=c["Nrm"][0], shared=True)                          # a shared target is cloud 0's target for everyone
     own = dict(c, Q=np.broadcast_to(c["Q"][0], c["Q"].shape).copy(), Nrm=np.broadcast_to(c["Nrm"][0], c["Nrm"].shape).copy())
@@ -229,7 +214,7 @@ def test_a_nan_cloud_and_an_inf_cloud_change_no_other(dev):
     bad["P"][1, 17, 0] = np.nan
     bad["Q"][4, 3, 2] = np.inf
     bad["Nrm"][2, 5, 1] = np.nan
-    dirty = surface_call(c, dev, **{k: _d(v, dev) for k, v in bad.items()})
+    dirty = surface_call(c, dev, **{k: to_device(v, dev) for k, v in bad.items()})
     ok = torch.tensor([0, 3, 5], device=dev)
     assert torch.equal(dirty[0][ok], clean[0][ok]) and torch.equal(dirty[1][ok], clean[1][ok])
     for k in INFO:
@@ -240,7 +225,7 @@ def test_a_nan_cloud_and_an_inf_cloud_change_no_other(dev):
 def test_replay_from_a_graph(dev, g30_cases):
     """One call captured and replayed twice: a single chain of launches, no host synchronisation, the same bits every time."""
     c = dict(next(c for c in g30_cases if c["kind"] == "converge"), iterations=5)
-    args = {k: _d(c[k], dev) for k in ("P", "Q", "Nrm", "R0", "t0", "w")}
+    args = {k: to_device(c[k], dev) for k in ("P", "Q", "Nrm", "R0", "t0", "w")}
     call = lambda: surface_call(c, dev, **args)
     R, t, info = call()
     eager = [R.clone(), t.clone()] + [info[k].clone() for k in INFO]
@@ -309,9 +294,9 @@ def test_plane_registers_in_k_iterations_what_point_to_point_does_not_in_3k(dev,
     from conftest import REPORT_LINES
     c = next(c for c in g30_cases if c["kind"] == "compare")
     k = c["iterations"]
-    P, Q, R0, t0 = (_d(c[x], dev) for x in ("P", "Q", "R0", "t0"))
+    P, Q, R0, t0 = (to_device(c[x], dev) for x in ("P", "Q", "R0", "t0"))
     judge = lambda R, t: ref.plane_rmse64(c["P"], c["Q"], c["Nrm"], R.cpu().numpy().astype(np.float64), t.cpu().numpy().astype(np.float64)) / c["plateau"]
-    given = judge(*pa.icp_align_plane(P, Q, _d(c["Nrm"], dev), R0, t0, iterations=k))
+    given = judge(*pa.icp_align_plane(P, Q, to_device(c["Nrm"], dev), R0, t0, iterations=k))
     estimated = judge(*pa.icp_align_plane(P, Q, None, R0, t0, iterations=k))
     point = judge(*pa.icp_align(P, Q, R0, t0, iterations=3 * k))
     line = "comparison case, float64 plane rmse / plateau: icp_align_plane(%d) %.3f (normals given) %.3f (estimated), icp_align(%d) %.2f" % (
@@ -322,21 +307,6 @@ def test_plane_registers_in_k_iterations_what_point_to_point_does_not_in_3k(dev,
 
 
 # ---- the speed condition ------------------------------------------------------------------------------------------------------------
-def _median_ms(fn):
-    for _ in range(5):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(20):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        times.append(e0.elapsed_time(e1))
-    return float(np.median(times))
-
-
 def test_icp_plane_is_not_slower_than_the_composition(dev):
     """B = 256, N = M = 1024, HIP events, 5 warm-ups, median of 20, same process.  icp_align_plane(iterations=10, normals given) against
     what the parent commit offers: cdist -> argmin -> two gathers -> einsum -> torch.linalg.solve -> update, ten times.  The ratio to
@@ -345,7 +315,7 @@ def test_icp_plane_is_not_slower_than_the_composition(dev):
     from conftest import REPORT_LINES
     b, n = 256, 1024
     c = _random_case(b, n, n, False, 212, weights=False)
-    P, Q, N = (_d(c[k], dev) for k in ("P", "Q", "Nrm"))
+    P, Q, N = (to_device(c[k], dev) for k in ("P", "Q", "Nrm"))
     eye = torch.eye(3, device=dev)
 
     def hat(v):
@@ -368,9 +338,9 @@ def test_icp_plane_is_not_slower_than_the_composition(dev):
         return R, t
 
     with torch.no_grad():
-        ours = _median_ms(lambda: pa.icp_align_plane(P, Q, N, iterations=10))
-        theirs = _median_ms(composed)
-        point = _median_ms(lambda: pa.icp_align(P, Q, iterations=10))
+        ours = median_ms(lambda: pa.icp_align_plane(P, Q, N, iterations=10))
+        theirs = median_ms(composed)
+        point = median_ms(lambda: pa.icp_align(P, Q, iterations=10))
         (R, t), (Rc, tc) = pa.icp_align_plane(P, Q, N, iterations=10), composed()
     assert (R - Rc).abs().max().item() < 1e-3 and (t - tc).abs().max().item() < 1e-3      # the same quantity (not an accuracy check)
     line = "icp_align_plane(iterations=10) B=256 N=M=1024: %.4f ms, cdist + argmin + gathers + einsum + linalg.solve x 10 %.4f ms (x%.1f); icp_align(iterations=10) %.4f ms (plane / point %.3f)" % (

@@ -10,19 +10,11 @@ import pytest
 import torch
 
 import knn_ref as ref
+from support import bits, dev, guarded, guards_intact, ptr, to_device  # noqa: F401
 import test_knn_host as host
 
 pytestmark = pytest.mark.gpu
-GUARD = 64
 KERNELS = set()                     # the k_knn instantiations the raw calls ran
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from poseestimation_amd import _lib
-    _lib.load()
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")
@@ -30,59 +22,40 @@ def g28_cases():
     return ref.cases(ref.g28())
 
 
-def _d(a, dev, dtype=np.float32):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _guarded(shape, fill, dtype, dev):
-    count = int(np.prod(shape))
-    whole = torch.full((count + 2 * GUARD,), fill, dtype=dtype, device=dev)
-    return whole, whole[GUARD:GUARD + count].view(shape)
-
-
-def _guards_intact(whole, fill):
-    edge = torch.cat([whole[:GUARD], whole[-GUARD:]])
-    return bool(torch.isnan(edge).all()) if isinstance(fill, float) and np.isnan(fill) else bool((edge == fill).all())
-
-
 def abi_run(X, Y, K, xl, yl, g, dev, shared=False):
     """The raw C ABI into guarded buffers, then again with each optional output left out.  -> (dist2, idx, dX, dY) numpy."""
     from poseestimation_amd import _lib
     lib = _lib.load()
     b, n, m = X.shape[0], X.shape[1], Y.shape[-2]
-    Xd, Yd, xld, yld, gd = _d(X, dev), _d(Y, dev), _d(xl, dev, np.int32), _d(yl, dev, np.int32), _d(g, dev)
+    Xd, Yd, xld, yld, gd = to_device(X, dev), to_device(Y, dev), to_device(xl, dev, np.int32), to_device(yl, dev, np.int32), to_device(g, dev)
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     spec = {"dist2": ((b, n, K), np.nan, torch.float32), "idx": ((b, n, K), -2, torch.int32), "dX": ((b, n, 3), np.nan, torch.float32),
             "dY": ((b, m, 3), np.nan, torch.float32)}
     whole, out = {}, {}
     for k, (shape, fill, dtype) in spec.items():
-        whole[k], out[k] = _guarded(shape, fill, dtype, dev)
+        whole[k], out[k] = guarded(shape, fill, dtype, dev)
     stride = 0 if shared else 3 * m
-    _lib.check(lib.so3_knn_f32(_ptr(Xd), _ptr(Yd), stride, _ptr(xld), _ptr(yld), _ptr(out["dist2"]), _ptr(out["idx"]), K, b, n, m, st), "so3_knn_f32")
+    _lib.check(lib.so3_knn_f32(ptr(Xd), ptr(Yd), stride, ptr(xld), ptr(yld), ptr(out["dist2"]), ptr(out["idx"]), K, b, n, m, st), "so3_knn_f32")
     kernel = lib.so3_last_kernel().decode()
     assert kernel == "k_knn<%d>" % host.queries_per_wave(b, n, m), kernel
     KERNELS.add(kernel)
     alone = torch.full((b, n, K), -2, dtype=torch.int32, device=dev)                        # dist2 left out
-    _lib.check(lib.so3_knn_f32(_ptr(Xd), _ptr(Yd), stride, _ptr(xld), _ptr(yld), None, _ptr(alone), K, b, n, m, st), "so3_knn_f32")
+    _lib.check(lib.so3_knn_f32(ptr(Xd), ptr(Yd), stride, ptr(xld), ptr(yld), None, ptr(alone), K, b, n, m, st), "so3_knn_f32")
     assert torch.equal(alone, out["idx"])
     if shared:
         Yd = Yd.expand(b, m, 3).contiguous()
     if g is not None:
-        args = (_ptr(Xd), _ptr(Yd), _ptr(xld), _ptr(yld), _ptr(out["idx"]), _ptr(gd))
-        _lib.check(lib.so3_knn_bwd_f32(*args, _ptr(out["dX"]), _ptr(out["dY"]), K, b, n, m, st), "so3_knn_bwd_f32")
+        args = (ptr(Xd), ptr(Yd), ptr(xld), ptr(yld), ptr(out["idx"]), ptr(gd))
+        _lib.check(lib.so3_knn_bwd_f32(*args, ptr(out["dX"]), ptr(out["dY"]), K, b, n, m, st), "so3_knn_bwd_f32")
         assert lib.so3_last_kernel().decode() == "k_knn_bwd"
         for only in ("dX", "dY"):                                                           # each gradient alone
             one = torch.full(spec[only][0], np.nan, device=dev)
-            _lib.check(lib.so3_knn_bwd_f32(*args, _ptr(one) if only == "dX" else None, _ptr(one) if only == "dY" else None, K, b, n, m, st),
+            _lib.check(lib.so3_knn_bwd_f32(*args, ptr(one) if only == "dX" else None, ptr(one) if only == "dY" else None, K, b, n, m, st),
                        "so3_knn_bwd_f32")
             assert torch.equal(one, out[only]), only
     torch.cuda.synchronize()
     for k, (shape, fill, dtype) in spec.items():
-        assert _guards_intact(whole[k], fill), k
+        assert guards_intact(whole[k], fill), k
     res = {k: v.cpu().numpy() for k, v in out.items()}
     return res["dist2"], res["idx"], (res["dX"] if g is not None else None), (res["dY"] if g is not None else None)
 
@@ -90,11 +63,11 @@ def abi_run(X, Y, K, xl, yl, g, dev, shared=False):
 def surface_run(X, Y, K, xl, yl, g, dev, long_lengths=False):
     import poseestimation_amd as pa
     ltype = np.int64 if long_lengths else np.int32
-    Xd, Yd = _d(X, dev).requires_grad_(), _d(Y, dev).requires_grad_()
-    dist2, idx = pa.knn_points(Xd, Yd, K, _d(xl, dev, ltype), _d(yl, dev, ltype))
+    Xd, Yd = to_device(X, dev).requires_grad_(), to_device(Y, dev).requires_grad_()
+    dist2, idx = pa.knn_points(Xd, Yd, K, to_device(xl, dev, ltype), to_device(yl, dev, ltype))
     assert dist2.dtype == torch.float32 and idx.dtype == torch.int64 and dist2.shape == idx.shape == (X.shape[0], X.shape[1], K)
     assert not idx.requires_grad and dist2.requires_grad
-    dist2.backward(_d(g, dev))
+    dist2.backward(to_device(g, dev))
     return dist2.detach().cpu().numpy(), idx.cpu().numpy(), Xd.grad.cpu().numpy(), Yd.grad.cpu().numpy()
 
 
@@ -221,10 +194,10 @@ def test_k3_is_three_nn_and_a_shared_target_is_the_expanded_one(dev):
     lib = _lib.load()
     rng = np.random.default_rng(2850)
     b, n, m = 3, 300, 77
-    X, Y = _d(ref._ball(rng, b, n), dev), _d(ref._ball(rng, b, m), dev)
+    X, Y = to_device(ref._ball(rng, b, n), dev), to_device(ref._ball(rng, b, m), dev)
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     d3, i3 = torch.empty(b, n, 3, device=dev), torch.empty(b, n, 3, dtype=torch.int32, device=dev)
-    _lib.check(lib.so3_three_nn_f32(_ptr(X), _ptr(Y), _ptr(d3), _ptr(i3), None, b, n, m, st), "so3_three_nn_f32")
+    _lib.check(lib.so3_three_nn_f32(ptr(X), ptr(Y), ptr(d3), ptr(i3), None, b, n, m, st), "so3_three_nn_f32")
     d2, idx = pa.knn_points(X, Y, 3)
     assert torch.equal(idx, i3.long()) and torch.equal(d2.view(torch.int32), d3.view(torch.int32))
     ds, is_ = pa.knn_points(X, Y[0], 6)                                                  # one shared target
@@ -251,23 +224,23 @@ def test_autograd(dev):
     _, want_i = ref.knn32(Xn, Yn, K)
     want_dX, want_dY = ref.grad32(Xn, Yn, None, None, want_i, g)
     _, _, abi_dX, abi_dY = abi_run(Xn, Yn, K, None, None, g, dev)
-    X, Y = _d(Xn, dev).requires_grad_(), _d(Yn, dev).requires_grad_()
+    X, Y = to_device(Xn, dev).requires_grad_(), to_device(Yn, dev).requires_grad_()
     wide = torch.zeros(b, n, 2 * K, device=dev)
-    wide[..., ::2] = _d(g, dev)
+    wide[..., ::2] = to_device(g, dev)
     d2, idx = pa.knn_points(X, Y, K)
     gX, gY = torch.autograd.grad(d2, (X, Y), wide[..., ::2])                              # a strided upstream gradient; the C ABI's bits
-    assert np.array_equal(host.bits(gX.cpu().numpy()), host.bits(abi_dX)) and np.array_equal(host.bits(gY.cpu().numpy()), host.bits(abi_dY))
-    assert np.array_equal(host.bits(abi_dX), host.bits(want_dX)) and np.array_equal(host.bits(abi_dY), host.bits(want_dY))
-    Yo = _d(Yn, dev).requires_grad_()                                                     # only Y requires grad
-    d2o, _ = pa.knn_points(_d(Xn, dev), Yo, K)
-    d2o.backward(_d(g, dev))
+    assert np.array_equal(bits(gX.cpu().numpy()), bits(abi_dX)) and np.array_equal(bits(gY.cpu().numpy()), bits(abi_dY))
+    assert np.array_equal(bits(abi_dX), bits(want_dX)) and np.array_equal(bits(abi_dY), bits(want_dY))
+    Yo = to_device(Yn, dev).requires_grad_()                                                     # only Y requires grad
+    d2o, _ = pa.knn_points(to_device(Xn, dev), Yo, K)
+    d2o.backward(to_device(g, dev))
     assert torch.equal(Yo.grad, gY)
-    X64, Y64 = _d(Xn, dev).double().requires_grad_(), _d(Yn, dev).double().requires_grad_()      # float64 clouds: results in their dtype
+    X64, Y64 = to_device(Xn, dev).double().requires_grad_(), to_device(Yn, dev).double().requires_grad_()      # float64 clouds: results in their dtype
     d64, i64 = pa.knn_points(X64, Y64, K)
-    d64.backward(_d(g, dev).double())
+    d64.backward(to_device(g, dev).double())
     assert d64.dtype == X64.grad.dtype == Y64.grad.dtype == torch.float64 and torch.equal(i64, idx)
     assert torch.equal(X64.grad, gX.double()) and torch.equal(Y64.grad, gY.double()) and torch.equal(d64, d2.detach().double())
-    Xd = _d(Xn, dev).requires_grad_()
+    Xd = to_device(Xn, dev).requires_grad_()
     d2d, _ = pa.knn_points(Xd, Y, K)
     (first,) = torch.autograd.grad(d2d.sum(), Xd, create_graph=True)
     assert not first.requires_grad
@@ -291,8 +264,8 @@ def test_repeatable_reversed_and_isolated(dev):
     rng = np.random.default_rng(2870)
     b, n, m, K = 5, 130, 200, 20
     Xn, Yn = ref._ball(rng, b, n), ref._ball(rng, b, m)
-    xl, yl = _d(rng.integers(1, n + 1, b), dev, np.int32), _d(rng.integers(1, m + 1, b), dev, np.int32)
-    g = _d(ref.upstream(b, n, K), dev)
+    xl, yl = to_device(rng.integers(1, n + 1, b), dev, np.int32), to_device(rng.integers(1, m + 1, b), dev, np.int32)
+    g = to_device(ref.upstream(b, n, K), dev)
 
     def run(X, Y, xl, yl, g):
         X, Y = X.clone().requires_grad_(), Y.clone().requires_grad_()
@@ -300,7 +273,7 @@ def test_repeatable_reversed_and_isolated(dev):
         d2.backward(g)
         return d2.detach(), idx, X.grad, Y.grad
 
-    X, Y = _d(Xn, dev), _d(Yn, dev)
+    X, Y = to_device(Xn, dev), to_device(Yn, dev)
     one, two = run(X, Y, xl, yl, g), run(X, Y, xl, yl, g)
     assert all(torch.equal(u, v) for u, v in zip(one, two))                               # two calls, the same bits
     rev = run(X.flip(0), Y.flip(0), xl.flip(0), yl.flip(0), g.flip(0))
@@ -317,8 +290,8 @@ def test_replay_from_a_captured_graph(dev):
     import poseestimation_amd as pa
     rng = np.random.default_rng(2880)
     b, n, m, K = 2, 100, 150, 8
-    X, Y = _d(ref._ball(rng, b, n), dev).requires_grad_(), _d(ref._ball(rng, b, m), dev).requires_grad_()
-    g = _d(ref.upstream(b, n, K), dev)
+    X, Y = to_device(ref._ball(rng, b, n), dev).requires_grad_(), to_device(ref._ball(rng, b, m), dev).requires_grad_()
+    g = to_device(ref.upstream(b, n, K), dev)
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
@@ -331,8 +304,8 @@ def test_replay_from_a_captured_graph(dev):
         gX, gY = torch.autograd.grad(d2, (X, Y), g)
     Xn, Yn = ref._ball(rng, b, n), ref._ball(rng, b, m)
     with torch.no_grad():
-        X.copy_(_d(Xn, dev))
-        Y.copy_(_d(Yn, dev))
+        X.copy_(to_device(Xn, dev))
+        Y.copy_(to_device(Yn, dev))
     graph.replay()
     torch.cuda.synchronize()
     want_d, want_i = ref.knn32(Xn, Yn, K)
@@ -344,8 +317,8 @@ def test_knn_gather_and_knn_group(dev):
     import poseestimation_amd as pa
     rng = np.random.default_rng(2890)
     b, n, s, K, d = 2, 120, 30, 6, 5
-    xyz, new_xyz, pts = _d(ref._ball(rng, b, n), dev), _d(ref._ball(rng, b, s), dev), _d(rng.standard_normal((b, n, d)), dev)
-    d2, idx = pa.knn_points(new_xyz, xyz, K, None, _d(np.array([n, 3]), dev, np.int64))          # cloud 1: three real slots, three of -1
+    xyz, new_xyz, pts = to_device(ref._ball(rng, b, n), dev), to_device(ref._ball(rng, b, s), dev), to_device(rng.standard_normal((b, n, d)), dev)
+    d2, idx = pa.knn_points(new_xyz, xyz, K, None, to_device(np.array([n, 3]), dev, np.int64))          # cloud 1: three real slots, three of -1
     got = pa.knn_gather(pts, idx)
     want = pts[torch.arange(b, device=dev)[:, None, None], idx.clamp(min=0)] * (idx >= 0)[..., None]
     assert got.shape == (b, s, K, d) and torch.equal(got, want) and (got[1, :, 3:] == 0).all() and (idx[1, :, 3:] == -1).all()
@@ -365,7 +338,7 @@ def test_faster_than_the_torch_spelling(dev):
     from conftest import REPORT_LINES
     rng = np.random.default_rng(2899)
     b, n, m, K = 32, 1024, 1024, 16
-    X, Y = _d(ref._ball(rng, b, n), dev).requires_grad_(), _d(ref._ball(rng, b, m), dev).requires_grad_()
+    X, Y = to_device(ref._ball(rng, b, n), dev).requires_grad_(), to_device(ref._ball(rng, b, m), dev).requires_grad_()
     g = torch.rand(b, n, K, device=dev)
 
     def ours():

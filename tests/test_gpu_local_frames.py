@@ -12,33 +12,17 @@ import pytest
 import torch
 
 import local_frames_ref as ref
+from support import bits, dev, guarded, guards_intact, ptr, to_device  # noqa: F401
 import test_local_frames_host as host
 
 pytestmark = pytest.mark.gpu
-GUARD = 64
 WIDTHS = (6, 3, 3, 9)                # cov, eigenvalues, normals, frames
 ALL = (True, True, True, True)
 
 
 @pytest.fixture(scope="module")
-def dev():
-    from poseestimation_amd import _lib
-    _lib.load()
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
 def g29_cases():
     return ref.cases(ref.g29())
-
-
-def _d(a, dev, dtype=np.float32):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def make_case(name, Y, idx, xl=None, yl=None, view=None):
@@ -56,25 +40,25 @@ def abi_run(c, dev, want=ALL, shared=False):
     from poseestimation_amd import _lib
     lib = _lib.load()
     b, n, m, K = c["b"], c["n"], c["m"], c["K"]
-    Yd, id_, xld, yld, vd = _d(c["Y"], dev), _d(c["idx"], dev, np.int32), _d(c["x_lengths"], dev, np.int32), _d(c["y_lengths"], dev, np.int32), _d(c["viewpoint"], dev)
+    Yd, id_, vd = to_device(c["Y"], dev), to_device(c["idx"], dev, np.int32), to_device(c["viewpoint"], dev)
+    xld, yld = to_device(c["x_lengths"], dev, np.int32), to_device(c["y_lengths"], dev, np.int32)
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    whole = [torch.full((b * n * w + 2 * GUARD,), float("nan"), device=dev) if flag else None for flag, w in zip(want, WIDTHS)]
-    outs = [None if t is None else t[GUARD:-GUARD] for t in whole]
-    _lib.check(lib.so3_local_frames_f32(_ptr(Yd), 0 if shared else 3 * m, _ptr(id_), _ptr(xld), _ptr(yld), _ptr(vd), *(_ptr(o) for o in outs), K, b, n, m, st),
+    whole, outs = zip(*(guarded((b * n * w,), float("nan"), torch.float32, dev) if flag else (None, None) for flag, w in zip(want, WIDTHS)))
+    _lib.check(lib.so3_local_frames_f32(ptr(Yd), 0 if shared else 3 * m, ptr(id_), ptr(xld), ptr(yld), ptr(vd), *(ptr(o) for o in outs), K, b, n, m, st),
                "so3_local_frames_f32")
     assert lib.so3_last_kernel().decode() == "k_local_frames"
     torch.cuda.synchronize()
     for t in whole:
-        assert t is None or bool(torch.isnan(torch.cat([t[:GUARD], t[-GUARD:]])).all()), "a guard was written"
+        assert t is None or guards_intact(t, float("nan")), "a guard was written"
     return tuple(None if o is None else o.view(b, n, w).cpu().numpy() for o, w in zip(outs, WIDTHS))
 
 
 def surface_run(c, dev, long=False, shared=False):
     import poseestimation_amd as pa
     itype = np.int64 if long else np.int32
-    Y = _d(c["Y"][0] if shared else c["Y"], dev)
-    lam, frames, cov = pa.local_frames(Y, _d(c["idx"], dev, itype), _d(c["x_lengths"], dev, itype), _d(c["y_lengths"], dev, itype),
-                                       _d(c["viewpoint"], dev), return_covariance=True)
+    Y = to_device(c["Y"][0] if shared else c["Y"], dev)
+    lam, frames, cov = pa.local_frames(Y, to_device(c["idx"], dev, itype), to_device(c["x_lengths"], dev, itype), to_device(c["y_lengths"], dev, itype),
+                                       to_device(c["viewpoint"], dev), return_covariance=True)
     b, n = c["b"], c["n"]
     assert lam.shape == (b, n, 3) and frames.shape == cov.shape == (b, n, 3, 3) and lam.dtype == frames.dtype == cov.dtype == torch.float32
     assert not (lam.requires_grad or frames.requires_grad or cov.requires_grad) and torch.equal(cov, cov.transpose(-1, -2))
@@ -84,7 +68,7 @@ def surface_run(c, dev, long=False, shared=False):
 
 
 def same_bits(a, b_):
-    return all((u is None and v is None) or np.array_equal(ref.bits(u), ref.bits(v)) for u, v in zip(a, b_))
+    return all((u is None and v is None) or np.array_equal(bits(u), bits(v)) for u, v in zip(a, b_))
 
 
 # ---- G29 --------------------------------------------------------------------------------------------------------------------
@@ -155,8 +139,8 @@ def test_indices_straight_from_the_searches(dev):
     import poseestimation_amd as pa
     rng = np.random.default_rng(2940)
     b, n, s = 2, 200, 40
-    xyz = _d(ref.sphere(rng, b, n), dev)
-    lengths = _d(np.array([200, 150]), dev, np.int64)
+    xyz = to_device(ref.sphere(rng, b, n), dev)
+    lengths = to_device(np.array([200, 150]), dev, np.int64)
     _, idx = pa.knn_points(xyz, xyz, 12, lengths, lengths)                                           # int64, -1 rows past the length
     lam, frames = pa.local_frames(xyz, idx, lengths, lengths)
     c = make_case("knn_points", xyz.cpu().numpy(), idx.cpu().numpy(), np.array([200, 150], np.int32), np.array([200, 150], np.int32))
@@ -209,7 +193,7 @@ def test_replay_from_a_captured_graph(dev):
     import poseestimation_amd as pa
     rng = np.random.default_rng(2960)
     b, n, K = 2, 150, 10
-    Y, view = _d(ref.sphere(rng, b, n), dev), _d(np.zeros((b, 3)), dev)
+    Y, view = to_device(ref.sphere(rng, b, n), dev), to_device(np.zeros((b, 3)), dev)
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
@@ -222,7 +206,7 @@ def test_replay_from_a_captured_graph(dev):
         _, idx = pa.knn_points(Y, Y, K)
         lam, frames = pa.local_frames(Y, idx, viewpoint=view)
     Yn = ref.sphere(rng, b, n)
-    Y.copy_(_d(Yn, dev))
+    Y.copy_(to_device(Yn, dev))
     graph.replay()
     torch.cuda.synchronize()
     c = make_case("replay", Yn, idx.cpu().numpy(), view=np.zeros((b, 3), np.float32))
@@ -236,8 +220,8 @@ def test_estimate_normals_is_knn_points_then_local_frames(dev):
     import poseestimation_amd as pa
     rng = np.random.default_rng(2970)
     b, n, K = 3, 300, 16
-    Y = _d(ref.sphere(rng, b, n), dev)
-    lengths = _d(np.array([300, 1, 120]), dev, np.int32)
+    Y = to_device(ref.sphere(rng, b, n), dev)
+    lengths = to_device(np.array([300, 1, 120]), dev, np.int32)
     for ln, view in ((None, None), (lengths, None), (lengths, torch.zeros(3, device=dev)), (None, torch.zeros(b, 3, device=dev, dtype=torch.float64))):
         normals, variation = pa.estimate_normals(Y, K, ln, view, return_curvature=True)
         _, idx = pa.knn_points(Y, Y, K, ln, ln)
@@ -256,16 +240,16 @@ def test_estimate_normals_is_knn_points_then_local_frames(dev):
 def test_the_lattice_plane_is_flat_and_the_sphere_faces_its_centre(dev, g29_cases):
     import poseestimation_amd as pa
     c = next(c for c in g29_cases if c["name"] == "lattice_plane")
-    normals, variation = pa.estimate_normals(_d(c["Y"], dev), c["K"], return_curvature=True)
+    normals, variation = pa.estimate_normals(to_device(c["Y"], dev), c["K"], return_curvature=True)
     assert (variation == 0).all() and (normals == torch.tensor([0.0, 0.0, 1.0], device=dev)).all()
-    flat, zero = pa.estimate_normals(_d(np.zeros((1, 20, 3)), dev), 4, return_curvature=True)       # all lambda 0: the variation is 0, not NaN
+    flat, zero = pa.estimate_normals(to_device(np.zeros((1, 20, 3)), dev), 4, return_curvature=True)       # all lambda 0: the variation is 0, not NaN
     assert (zero == 0).all() and (flat == torch.tensor([1.0, 0.0, 0.0], device=dev)).all()
     rng = np.random.default_rng(2980)
     Yn = ref.sphere(rng, 2, 400)
-    normals = pa.estimate_normals(_d(Yn, dev), 12, viewpoint=torch.zeros(3, device=dev)).cpu().numpy()
+    normals = pa.estimate_normals(to_device(Yn, dev), 12, viewpoint=torch.zeros(3, device=dev)).cpu().numpy()
     idx = ref.self_knn(Yn, 400, 12)
     c = make_case("sphere, the centre as viewpoint", Yn, idx, view=np.zeros((2, 3), np.float32))
-    frames = pa.local_frames(_d(Yn, dev), _d(idx, dev, np.int32), viewpoint=torch.zeros(2, 3, device=dev))[1].cpu().numpy()
+    frames = pa.local_frames(to_device(Yn, dev), to_device(idx, dev, np.int32), viewpoint=torch.zeros(2, 3, device=dev))[1].cpu().numpy()
     host.check_case("surface", c, (None, None, normals, frames.reshape(2, 400, 9)))                  # within the normal bound of float64's normal ...
     inward = -(normals.astype(np.float64) * Yn).sum(-1)                                             # ... which is -x / |x| up to the patch's lean
     assert (inward > np.cos(np.radians(20.0))).all(), inward.min()
@@ -324,7 +308,7 @@ def test_not_slower_than_the_torch_spelling(dev):
     from conftest import REPORT_LINES
     rng = np.random.default_rng(2999)
     b, n, K = 32, 1024, 16
-    Y = _d(ref.sphere(rng, b, n), dev)
+    Y = to_device(ref.sphere(rng, b, n), dev)
     _, idx = pa.knn_points(Y, Y, K)
 
     def ours():

@@ -10,17 +10,10 @@ import pytest
 import torch
 
 import pointnet_ref as ref
+from support import dev, last_kernel, median_ms, ptr, to_device  # noqa: F401
 import test_pointnet_host as host
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from poseestimation_amd import _lib
-    _lib.load()
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")
@@ -28,33 +21,20 @@ def g22_cases():
     return ref.cases(ref.g22())
 
 
-def _d(a, dev, dtype=np.float32):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _last_kernel():
-    from poseestimation_amd import _lib
-    return _lib.load().so3_last_kernel().decode()
-
-
 def surface_fps(xyz, npoint, start, dev):
     import poseestimation_amd as pa
-    out = pa.farthest_point_sample(_d(xyz, dev), npoint, _d(start, dev, np.int64))
+    out = pa.farthest_point_sample(to_device(xyz, dev), npoint, to_device(start, dev, np.int64))
     assert out.shape == (len(xyz), npoint) and out.dtype == torch.int64 and out.is_cuda
     return out.cpu().numpy()
 
 
 def surface_ball(radius, nsample, xyz, centres, dev):
     import poseestimation_amd as pa
-    x, c = _d(xyz, dev), _d(centres, dev)
+    x, c = to_device(xyz, dev), to_device(centres, dev)
     idx, count = pa.query_ball_point(radius, nsample, x, c, return_counts=True)
-    assert _last_kernel() == "k_ball_query<true>"
+    assert last_kernel() == "k_ball_query<true>"
     alone = pa.query_ball_point(radius, nsample, x, c)                       # the scan with the early exit writes the same rows
-    assert _last_kernel() == "k_ball_query<false>"
+    assert last_kernel() == "k_ball_query<false>"
     assert idx.dtype == count.dtype == alone.dtype == torch.int64 and torch.equal(alone, idx)
     assert idx.shape == (len(xyz), centres.shape[1], min(nsample, xyz.shape[1])) and count.shape == idx.shape[:2]
     return idx.cpu().numpy(), count.cpu().numpy()
@@ -64,10 +44,10 @@ def abi_fps(xyz, npoint, start, dev):
     """The raw C ABI into a buffer pre-filled with -1."""
     from poseestimation_amd import _lib
     lib = _lib.load()
-    x, first = _d(xyz, dev), _d(start, dev, np.int32)
+    x, first = to_device(xyz, dev), to_device(start, dev, np.int32)
     out = torch.full((len(xyz), npoint), -1, dtype=torch.int32, device=dev)
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    _lib.check(lib.so3_fps_f32(_ptr(x), _ptr(first), _ptr(out), len(xyz), xyz.shape[1], npoint, st), "so3_fps_f32")
+    _lib.check(lib.so3_fps_f32(ptr(x), ptr(first), ptr(out), len(xyz), xyz.shape[1], npoint, st), "so3_fps_f32")
     return out.cpu().numpy()
 
 
@@ -75,13 +55,13 @@ def abi_ball(radius, nsample, xyz, centres, dev):
     """The raw C ABI into buffers pre-filled with -1, with count given and omitted."""
     from poseestimation_amd import _lib
     lib = _lib.load()
-    x, c = _d(xyz, dev), _d(centres, dev)
+    x, c = to_device(xyz, dev), to_device(centres, dev)
     b, n, s = len(xyz), xyz.shape[1], centres.shape[1]
     idx, idx2 = (torch.full((b, s, min(nsample, n)), -1, dtype=torch.int32, device=dev) for _ in range(2))
     count = torch.full((b, s), -1, dtype=torch.int32, device=dev)
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    _lib.check(lib.so3_ball_query_f32(_ptr(x), _ptr(c), radius, nsample, _ptr(idx), _ptr(count), b, n, s, st), "so3_ball_query_f32")
-    _lib.check(lib.so3_ball_query_f32(_ptr(x), _ptr(c), radius, nsample, _ptr(idx2), None, b, n, s, st), "so3_ball_query_f32")
+    _lib.check(lib.so3_ball_query_f32(ptr(x), ptr(c), radius, nsample, ptr(idx), ptr(count), b, n, s, st), "so3_ball_query_f32")
+    _lib.check(lib.so3_ball_query_f32(ptr(x), ptr(c), radius, nsample, ptr(idx2), None, b, n, s, st), "so3_ball_query_f32")
     assert torch.equal(idx, idx2)
     return idx.cpu().numpy(), count.cpu().numpy()
 
@@ -101,10 +81,10 @@ def test_fps_shapes_equal_the_restatement_and_reach_every_instantiation(dev):
     seen = set()
     for c, want in zip(host.fps_shape_cases(), host.fps_expected()):
         got = surface_fps(c["xyz"], c["npoint"], c["start"], dev)
-        seen.add(_last_kernel())
+        seen.add(last_kernel())
         assert np.array_equal(got, want), (c["name"], np.argwhere(got != want)[:4])
         if (c["start"] == c["start"][0]).all():                                            # the same start as an int
-            again = pa.farthest_point_sample(_d(c["xyz"], dev), c["npoint"], start=int(c["start"][0]))
+            again = pa.farthest_point_sample(to_device(c["xyz"], dev), c["npoint"], start=int(c["start"][0]))
             assert np.array_equal(again.cpu().numpy(), want), c["name"]
         if c["xyz"].shape[1] <= 257:
             assert np.array_equal(abi_fps(c["xyz"], c["npoint"], c["start"], dev), want), c["name"]
@@ -185,7 +165,7 @@ def test_replay_from_a_graph(dev, g22_cases):
     """Two eager calls give the same bits; one call of each function captured and replayed twice into zeroed outputs equals them."""
     import poseestimation_amd as pa
     c = next(c for c in g22_cases if c["kind"] == "ball" and c["nsample"] == 64 and c["xyz"].shape[1] == 1024)
-    xyz, centres = _d(c["xyz"], dev), _d(c["centres"], dev)
+    xyz, centres = to_device(c["xyz"], dev), to_device(c["centres"], dev)
 
     def call():
         rows, count = pa.query_ball_point(c["radius"], c["nsample"], xyz, centres, return_counts=True)
@@ -239,21 +219,6 @@ def test_errors(dev):
 
 
 # ---- the speed conditions -------------------------------------------------------------------------------------------------------
-def _median_ms(fn):
-    for _ in range(5):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(20):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        times.append(e0.elapsed_time(e1))
-    return float(np.median(times))
-
-
 def torch_fps_loop(xyz, npoint, start):
     """The loop farthest_point_sample replaces, in torch on the device: npoint iterations, each a gather of the centre, the squared
     distances, the running minimum (torch.minimum: no masked assignment, which would synchronise with the host) and an argmax."""
@@ -297,11 +262,11 @@ def test_sampling_and_grouping_are_not_slower_than_the_torch_spellings(dev):
         sorted_rows = torch_ball_by_sorting(radius, k, xyz, centres)
         assert torch.equal(fps_idx[:, :8], loop_idx[:, :8])                                # the same quantity (not an accuracy check:
         assert (rows != sorted_rows).any(-1).float().mean().item() < 0.01                 #  torch rounds its own way)
-        ours_a = _median_ms(lambda: pa.farthest_point_sample(xyz, npoint, start))
-        theirs_a = _median_ms(lambda: torch_fps_loop(xyz, npoint, start))
-        ours_b = _median_ms(lambda: pa.query_ball_point(radius, k, xyz, centres))
-        ours_c = _median_ms(lambda: pa.query_ball_point(radius, k, xyz, centres, return_counts=True))
-        theirs_b = _median_ms(lambda: torch_ball_by_sorting(radius, k, xyz, centres))
+        ours_a = median_ms(lambda: pa.farthest_point_sample(xyz, npoint, start))
+        theirs_a = median_ms(lambda: torch_fps_loop(xyz, npoint, start))
+        ours_b = median_ms(lambda: pa.query_ball_point(radius, k, xyz, centres))
+        ours_c = median_ms(lambda: pa.query_ball_point(radius, k, xyz, centres, return_counts=True))
+        theirs_b = median_ms(lambda: torch_ball_by_sorting(radius, k, xyz, centres))
     for line in ("farthest_point_sample 32x1024->512: %.4f ms (%.3f us per iteration), torch loop %.4f ms (x%.1f)" % (ours_a, 1e3 * ours_a / npoint, theirs_a, theirs_a / ours_a),
                  "query_ball_point 32x1024, 512 centres, r=0.2, K=64 (mean count %.1f): %.4f ms, with counts %.4f ms, mask + sort + slice %.4f ms (x%.1f)"
                  % (count.float().mean().item(), ours_b, ours_c, theirs_b, theirs_b / ours_b)):

@@ -8,17 +8,10 @@ import pytest
 import torch
 
 import rigid_align_ref as ref
+from support import dev, median_ms, ptr, to_device  # noqa: F401
 import test_rigid_align_host as host
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from poseestimation_amd import _lib
-    _lib.load()
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")
@@ -31,28 +24,20 @@ def g20_grads(g20_cases):
     return [ref.case_grads(c) for c in g20_cases]
 
 
-def _d(a, dev):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
 def abi_run(c, dev, which=("dP", "dQ", "dw")):
     """One case through the raw C ABI: the forward with H and stats, then one backward writing the gradients `which` names."""
     from poseestimation_amd import _lib
     lib = _lib.load()
     b, n = c["b"], c["n"]
-    P, Q, w, gR, gt, gH = (_d(c[k], dev) for k in ("P", "Q", "w", "gR", "gt", "gH"))
+    P, Q, w, gR, gt, gH = (to_device(c[k], dev) for k in ("P", "Q", "w", "gR", "gt", "gH"))
     out = {"R": torch.full((b, 3, 3), np.nan, device=dev), "t": torch.full((b, 3), np.nan, device=dev), "H": torch.full((b, 3, 3), np.nan, device=dev),
            "stats": torch.full((b, 7), np.nan, device=dev)}
     grads = {"dP": torch.full((b, n, 3), np.nan, device=dev), "dQ": torch.full((b, n, 3), np.nan, device=dev), "dw": torch.full((b, n), np.nan, device=dev)}
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    _lib.check(lib.so3_rigid_align_f32(_ptr(P), _ptr(Q), _ptr(w), _ptr(out["R"]), _ptr(out["t"]), _ptr(out["H"]), _ptr(out["stats"]), b, n, st),
+    _lib.check(lib.so3_rigid_align_f32(ptr(P), ptr(Q), ptr(w), ptr(out["R"]), ptr(out["t"]), ptr(out["H"]), ptr(out["stats"]), b, n, st),
                "so3_rigid_align_f32")
-    _lib.check(lib.so3_rigid_align_bwd_f32(_ptr(P), _ptr(Q), _ptr(w), _ptr(out["H"]), _ptr(out["R"]), _ptr(out["stats"]), _ptr(gR), _ptr(gt), _ptr(gH),
-                                           *[_ptr(grads[k]) if k in which else None for k in ("dP", "dQ", "dw")], b, n, st), "so3_rigid_align_bwd_f32")
+    _lib.check(lib.so3_rigid_align_bwd_f32(ptr(P), ptr(Q), ptr(w), ptr(out["H"]), ptr(out["R"]), ptr(out["stats"]), ptr(gR), ptr(gt), ptr(gH),
+                                           *[ptr(grads[k]) if k in which else None for k in ("dP", "dQ", "dw")], b, n, st), "so3_rigid_align_bwd_f32")
     for k in ("dP", "dQ", "dw"):                       # a gradient that was not asked for is not written
         if k not in which:
             assert torch.isnan(grads[k]).all(), k
@@ -63,7 +48,7 @@ def abi_run(c, dev, which=("dP", "dQ", "dw")):
 def surface_run(c, dev, which=("dP", "dQ", "dw")):
     """One case through rigid_align(..., return_h=True) and autograd, with only the arguments `which` names requiring grad."""
     import poseestimation_amd as pa
-    P, Q, w, gR, gt, gH = (_d(c[k], dev) for k in ("P", "Q", "w", "gR", "gt", "gH"))
+    P, Q, w, gR, gt, gH = (to_device(c[k], dev) for k in ("P", "Q", "w", "gR", "gt", "gH"))
     args = {"dP": P, "dQ": Q, "dw": w}
     wanted = [k for k in which if args[k] is not None]
     for k in wanted:
@@ -130,7 +115,7 @@ def test_exact_recovery(dev, n, offset):
     import poseestimation_amd as pa
     b = 64
     P, Q, R0, t0 = _pairs(b, n, offset, seed=500 + n)
-    R, t = pa.rigid_align(_d(P, dev), _d(Q, dev))
+    R, t = pa.rigid_align(to_device(P, dev), to_device(Q, dev))
     R, t = R.cpu().numpy().astype(np.float64), t.cpu().numpy().astype(np.float64)
     want = ref.answers(P, Q, None)
     scale = np.maximum(1.0, np.abs(want["stats"][:, :6]).max(1))
@@ -153,9 +138,9 @@ def test_masked_tail_equals_the_truncated_call(dev):
     Q[:, keep:] = rng.uniform(-10, 10, (b, n - keep, 3))
     w = np.zeros((b, n), np.float32)
     w[:, :keep] = 1
-    Pd, Qd, wd = _d(P, dev).requires_grad_(True), _d(Q, dev).requires_grad_(True), _d(w, dev).requires_grad_(True)
+    Pd, Qd, wd = to_device(P, dev).requires_grad_(True), to_device(Q, dev).requires_grad_(True), to_device(w, dev).requires_grad_(True)
     R, t = pa.rigid_align(Pd, Qd, wd)
-    Rt, tt = pa.rigid_align(_d(P[:, :keep], dev), _d(Q[:, :keep], dev))
+    Rt, tt = pa.rigid_align(to_device(P[:, :keep], dev), to_device(Q[:, :keep], dev))
     scale = max(1.0, float(np.abs(P[:, :keep]).max()), float(np.abs(Q[:, :keep]).max()))
     assert (R - Rt).abs().max().item() <= 2 * host.R_TOL and (t - tt).abs().max().item() / scale <= 2 * host.T_TOL      # two results, each within the bound
     dP, dQ, dw = torch.autograd.grad(R.sum() + t.sum(), [Pd, Qd, wd])
@@ -195,7 +180,7 @@ def test_launch_shapes_against_float64(dev, many):
     b = 2 * 16 * torch.cuda.get_device_properties(dev).multi_processor_count + 37 if many else 1
     P, Q, _, _ = _pairs(b, 8, 10.0, seed=71, sigma=0.01)
     w = np.random.default_rng(72).uniform(0.05, 1.0, (b, 8)).astype(np.float32)
-    Pd, Qd, wd = _d(P, dev).requires_grad_(True), _d(Q, dev).requires_grad_(True), _d(w, dev).requires_grad_(True)
+    Pd, Qd, wd = to_device(P, dev).requires_grad_(True), to_device(Q, dev).requires_grad_(True), to_device(w, dev).requires_grad_(True)
     R, t, H = pa.rigid_align(Pd, Qd, wd, return_h=True)
     g = torch.Generator().manual_seed(73)
     gR, gt, gH = torch.randn(b, 3, 3, generator=g), torch.randn(b, 3, generator=g), torch.randn(b, 3, 3, generator=g)
@@ -221,8 +206,8 @@ def test_agrees_with_kabsch_rotation_on_centred_clouds(dev):
     P, Q, _, _ = _pairs(32, 300, 5.0, seed=81, sigma=0.01)
     Pc = (P.astype(np.float64) - P.astype(np.float64).mean(1, keepdims=True)).astype(np.float32)
     Qc = (Q.astype(np.float64) - Q.astype(np.float64).mean(1, keepdims=True)).astype(np.float32)
-    R, t = pa.rigid_align(_d(Pc, dev), _d(Qc, dev))
-    Rk = pa.kabsch_rotation(_d(Pc, dev), _d(Qc, dev))
+    R, t = pa.rigid_align(to_device(Pc, dev), to_device(Qc, dev))
+    Rk = pa.kabsch_rotation(to_device(Pc, dev), to_device(Qc, dev))
     assert (R - Rk).abs().max().item() <= 2 * host.R_TOL
     assert t.abs().max().item() <= host.T_TOL
 
@@ -232,7 +217,7 @@ def test_views_dtypes_and_a_side_stream(dev):
     import poseestimation_amd as pa
     P, Q, _, _ = _pairs(6, 130, 0.0, seed=91, sigma=0.01)
     w = np.random.default_rng(92).uniform(0.05, 1.0, (6, 130)).astype(np.float32)
-    Pd, Qd, wd = _d(P, dev), _d(Q, dev), _d(w, dev)
+    Pd, Qd, wd = to_device(P, dev), to_device(Q, dev), to_device(w, dev)
     R, t = pa.rigid_align(Pd, Qd, wd)
     wide = torch.zeros(6, 130, 6, device=dev)
     wide[..., ::2] = Pd
@@ -267,7 +252,7 @@ def test_training_step_through_add_loss(dev):
     import poseestimation_amd as pa
     b, n = 16, 256
     P, Q, R0, t0 = _pairs(b, n, 2.0, seed=95, sigma=0.02)
-    Pd, Qd = _d(P, dev), _d(Q, dev)
+    Pd, Qd = to_device(P, dev), to_device(Q, dev)
     logits = torch.randn(b, n, device=dev, requires_grad=True)
     R, t = pa.rigid_align(Pd, Qd, torch.sigmoid(logits))
     bottom = torch.tensor([0.0, 0.0, 0.0, 1.0], device=dev).expand(b, 1, 4)
@@ -284,7 +269,7 @@ def test_forward_and_backward_replay_from_a_graph(dev):
     import poseestimation_amd as pa
     P, Q, _, _ = _pairs(40, 100, 10.0, seed=97, sigma=0.01)
     w = np.random.default_rng(98).uniform(0.05, 1.0, (40, 100)).astype(np.float32)
-    Pd, Qd, wd = _d(P, dev).requires_grad_(True), _d(Q, dev).requires_grad_(True), _d(w, dev).requires_grad_(True)
+    Pd, Qd, wd = to_device(P, dev).requires_grad_(True), to_device(Q, dev).requires_grad_(True), to_device(w, dev).requires_grad_(True)
 
     def step():
         R, t, H = pa.rigid_align(Pd, Qd, wd, return_h=True)
@@ -308,21 +293,6 @@ def test_forward_and_backward_replay_from_a_graph(dev):
 
 
 # ---- 10. the speed conditions -------------------------------------------------------------------------------------------------
-def _median_ms(fn):
-    for _ in range(5):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(20):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        times.append(e0.elapsed_time(e1))
-    return float(np.median(times))
-
-
 def test_rigid_align_is_not_slower_than_the_compositions(dev):
     """B = 4096, N = 1024, HIP events, 5 warm-ups, median of 20, same process.  Unweighted: against centring with torch and
     kabsch_rotation, the spelling available before rigid_align.  Weighted forward + backward: against the torch-composed weighted chain
@@ -348,8 +318,8 @@ def test_rigid_align_is_not_slower_than_the_compositions(dev):
         return R, qbar - torch.einsum("bij,bj->bi", R, pbar)
 
     with torch.no_grad():
-        ours = _median_ms(lambda: pa.rigid_align(P, Q))
-        theirs = _median_ms(lambda: composed(P, Q))
+        ours = median_ms(lambda: pa.rigid_align(P, Q))
+        theirs = median_ms(lambda: composed(P, Q))
         (R, t), (Rc, tc) = pa.rigid_align(P, Q), composed(P, Q)
     assert (R - Rc).abs().max().item() < 1e-4 and (t - tc).abs().max().item() < 1e-4      # the same quantity (not an accuracy check)
     line = "rigid_align B=4096 N=1024 unweighted: %.4f ms, mean + centre + kabsch_rotation %.4f ms (x%.1f)" % (ours, theirs, theirs / ours)
@@ -362,8 +332,8 @@ def test_rigid_align_is_not_slower_than_the_compositions(dev):
         R, t = fn(Pg, Qg, wg)
         torch.autograd.grad(R.sum() + t.sum(), [Pg, Qg, wg])
 
-    ours_w = _median_ms(lambda: train(pa.rigid_align))
-    theirs_w = _median_ms(lambda: train(composed_weighted))
+    ours_w = median_ms(lambda: train(pa.rigid_align))
+    theirs_w = median_ms(lambda: train(composed_weighted))
     line = "rigid_align B=4096 N=1024 weighted forward + backward: %.4f ms, torch-composed chain %.4f ms (x%.1f)" % (ours_w, theirs_w, theirs_w / ours_w)
     print(line)
     REPORT_LINES.append(line)

@@ -50,6 +50,7 @@ import add_metrics_ref as aref
 import f32_exact as fx
 import icp_ref
 import search_geometry_ref as geo
+from support import ptr, to_device
 import test_add_metrics_host as ahost
 import test_icp_host as ihost
 from test_gpu_cloud_kernels import CANARY, Out
@@ -86,14 +87,6 @@ def ctx():
     torch.cuda.empty_cache()
 
 
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _d(a, dev):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
 class Buf(Out):
     """A guarded Out of float32 or int32 (a slot that still holds CANARY, as an index 0x7FC5A5A5, was not written)."""
 
@@ -126,12 +119,12 @@ def run_adds(ctx, tg, tp, pts, rows=None, guarded=True, diameter=True):
     nn = mk((b, n), torch.int32) if guarded else None
     nn_t = nn.t if guarded else torch.full((b, n), -1, dtype=torch.int32, device=ctx.dev)
     chk = ctx._lib.check
-    chk(ctx.lib.so3_add_s_fwd_f32(_ptr(tg), _ptr(tp), _ptr(pts), pd.ptr, _ptr(nn_t), dists.ptr, None, b, n, ctx.stream), "so3_add_s_fwd_f32")
+    chk(ctx.lib.so3_add_s_fwd_f32(ptr(tg), ptr(tp), ptr(pts), pd.ptr, ptr(nn_t), dists.ptr, None, b, n, ctx.stream), "so3_add_s_fwd_f32")
     out = {"name": _name(ctx)}
-    chk(ctx.lib.so3_add_s_bwd_f32(_ptr(tg), _ptr(tp), _ptr(pts), _ptr(nn_t), _ptr(rows), GRAD_SCALE, dT.ptr, b, n, ctx.stream), "so3_add_s_bwd_f32")
+    chk(ctx.lib.so3_add_s_bwd_f32(ptr(tg), ptr(tp), ptr(pts), ptr(nn_t), ptr(rows), GRAD_SCALE, dT.ptr, b, n, ctx.stream), "so3_add_s_bwd_f32")
     if diameter:
         work, diam = mk((b, n)), mk((b,))
-        chk(ctx.lib.so3_cloud_diameter_f32(_ptr(pts), work.ptr, diam.ptr, b, n, ctx.stream), "so3_cloud_diameter_f32")
+        chk(ctx.lib.so3_cloud_diameter_f32(ptr(pts), work.ptr, diam.ptr, b, n, ctx.stream), "so3_cloud_diameter_f32")
         out["diam_name"] = _name(ctx)
     torch.cuda.synchronize()
     get = (lambda o: o.checked()) if guarded else (lambda o: o.t)
@@ -271,7 +264,7 @@ def test_exact_add_s_families(ctx, name, n, b):
     if isinstance(b, str):
         u, b = ctx.cases[b]["u_adds"], ctx.cases[b]["b"]
     f = geo.exact_adds_family(name, n, b, geo.exact_seed(name, n))
-    tg, tp, pts = (_d(f[k], ctx.dev) for k in ("tgt", "tpred", "pts"))
+    tg, tp, pts = (to_device(f[k], ctx.dev, None) for k in ("tgt", "tpred", "pts"))
     rows = torch.randn(b, generator=torch.Generator().manual_seed(4)).to(ctx.dev)
     got = run_adds(ctx, tg, tp, pts, rows)
     assert got["name"] == "k_add_s<true, false, %d>" % (u or geo.rule(b, n, ctx.cus)), got["name"]
@@ -295,7 +288,7 @@ def test_exact_add_s_families(ctx, name, n, b):
 
 def run_nearest(ctx, X, Y, stride, b, n, m, want_index=True):
     dist, nn = Buf(ctx.dev, (b, n)), Buf(ctx.dev, (b, n), torch.int32)
-    ctx._lib.check(ctx.lib.so3_nearest_f32(_ptr(X), _ptr(Y), stride, dist.ptr, nn.ptr if want_index else None, b, n, m, ctx.stream), "so3_nearest_f32")
+    ctx._lib.check(ctx.lib.so3_nearest_f32(ptr(X), ptr(Y), stride, dist.ptr, nn.ptr if want_index else None, b, n, m, ctx.stream), "so3_nearest_f32")
     name = _name(ctx)
     torch.cuda.synchronize()
     out = {"dist": dist.checked(), "name": name}
@@ -310,7 +303,7 @@ def run_nearest(ctx, X, Y, stride, b, n, m, want_index=True):
 @pytest.mark.parametrize("name,n", geo.EXACT_SEARCH, ids=lambda v: str(v))
 def test_exact_search_families(ctx, name, n):
     f = geo.exact_search_family(name, n, geo.exact_seed(name, n) + 1)
-    got = run_nearest(ctx, _d(f["X"], ctx.dev), _d(f["Y"], ctx.dev), 3 * f["m"], 2, n, f["m"])
+    got = run_nearest(ctx, to_device(f["X"], ctx.dev, None), to_device(f["Y"], ctx.dev, None), 3 * f["m"], 2, n, f["m"])
     assert got["name"] == "k_icp_step<false, false, false, 1>", got["name"]
     nn, dist = got["nearest"].cpu().numpy(), got["dist"].cpu().numpy()
     wrong = np.argwhere(nn != f["nearest"])
@@ -320,7 +313,7 @@ def test_exact_search_families(ctx, name, n):
         assert (dist == 0).all() and (nn[:, [1023, 1024, 2048]] == 5).all() and (nn[:, 2047] == 1030).all()
     else:
         assert (nn[:, f["special"] + [n - 1]] == n - 1).all() and (dist[:, f["special"]] == geo.QUANTUM).all()
-    shared = run_nearest(ctx, _d(f["X"], ctx.dev), _d(f["Y"][0], ctx.dev), 0, 2, n, f["m"])      # one shared target: cloud 0's
+    shared = run_nearest(ctx, to_device(f["X"], ctx.dev, None), to_device(f["Y"][0], ctx.dev, None), 0, 2, n, f["m"])      # one shared target: cloud 0's
     assert torch.equal(shared["nearest"][0], got["nearest"][0]) and torch.equal(shared["dist"][0], got["dist"][0])
 
 
@@ -345,10 +338,10 @@ def run_icp(ctx, P, Q, stride, w, T0, md, it, b, n, m, optional=True, guarded=Tr
             inl_t, nn_t = inl.t, nn.t
         else:
             inl_t, nn_t = torch.full((max(it, 1), b), -1, dtype=torch.int32, device=dev), torch.full((b, n), -1, dtype=torch.int32, device=dev)
-        args = (rmse.ptr if it else None, _ptr(inl_t) if it else None, _ptr(nn_t), dist.ptr)
+        args = (rmse.ptr if it else None, ptr(inl_t) if it else None, ptr(nn_t), dist.ptr)
     else:
         args = (None, None, None, None)
-    ctx._lib.check(ctx.lib.so3_icp_f32(_ptr(P), _ptr(Q), stride, _ptr(w), _ptr(T0), -1.0 if md is None else md, it, R.ptr, t.ptr, *args, _ptr(inner),
+    ctx._lib.check(ctx.lib.so3_icp_f32(ptr(P), ptr(Q), stride, ptr(w), ptr(T0), -1.0 if md is None else md, it, R.ptr, t.ptr, *args, ptr(inner),
                                        b, n, m, ctx.stream), "so3_icp_f32")
     out["name"] = _name(ctx)
     torch.cuda.synchronize()
@@ -370,7 +363,7 @@ def icp_inputs(ctx, case_id):
         d = geo.icp_case_inputs(c, ctx.cus)
         R0, t0 = d["R0"], d["t0"]
         d["T0"] = None if R0 is None else np.ascontiguousarray(np.concatenate([R0, t0[:, :, None]], 2).reshape(-1, 12))
-        ctx.cache["icp", case_id] = (d, {k: _d(v, ctx.dev) for k, v in d.items()})
+        ctx.cache["icp", case_id] = (d, {k: to_device(v, ctx.dev, None) for k, v in d.items()})
     return ctx.cache["icp", case_id]
 
 
@@ -503,7 +496,7 @@ def test_optional_outputs_at_g4(ctx):
     pd, nn = Buf(ctx.dev, (b, n)), Buf(ctx.dev, (b, n), torch.int32)
     total = torch.full((3,), float("nan"), dtype=torch.float64, device=ctx.dev)
     # no indices, no rows: one workgroup walks all 64 CUs + 37 rows and leaves their sum
-    ctx._lib.check(ctx.lib.so3_add_s_fwd_f32(_ptr(tg), _ptr(tp), _ptr(pts), pd.ptr, None, None, ctypes.c_void_p(total.data_ptr() + 8), b, n, ctx.stream), "so3_add_s_fwd_f32")
+    ctx._lib.check(ctx.lib.so3_add_s_fwd_f32(ptr(tg), ptr(tp), ptr(pts), pd.ptr, None, None, ctypes.c_void_p(total.data_ptr() + 8), b, n, ctx.stream), "so3_add_s_fwd_f32")
     assert _name(ctx) == "k_add_s<false, false, %d>" % c["u_adds"]
     torch.cuda.synchronize()
     assert torch.equal(pd.checked(), got["point_dist"]) and nn.untouched()
@@ -513,7 +506,7 @@ def test_optional_outputs_at_g4(ctx):
     assert np.isnan(t[0]) and np.isnan(t[2]) and abs(t[1] - want) <= 1e-12 * b, (t, want)
     # rows and the total: the second, one-workgroup sum over the rows
     dists = Buf(ctx.dev, (b,))
-    ctx._lib.check(ctx.lib.so3_add_s_fwd_f32(_ptr(tg), _ptr(tp), _ptr(pts), pd.ptr, None, dists.ptr, _ptr(total), b, n, ctx.stream), "so3_add_s_fwd_f32")
+    ctx._lib.check(ctx.lib.so3_add_s_fwd_f32(ptr(tg), ptr(tp), ptr(pts), pd.ptr, None, dists.ptr, ptr(total), b, n, ctx.stream), "so3_add_s_fwd_f32")
     torch.cuda.synchronize()
     assert torch.equal(dists.checked(), got["adds"]) and abs(total[0].item() - want) <= 1e-12 * b
     # grad_rows == NULL is a row of ones

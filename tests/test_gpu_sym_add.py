@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+from support import dev  # noqa: F401
 import sym_add_ref as ref
 import test_sym_add_host as host
 import test_gpu_add_metrics as add_gpu
@@ -20,14 +21,6 @@ import test_gpu_add_metrics as add_gpu
 pytestmark = pytest.mark.gpu
 
 MODES = (ref.L2, ref.L1, ref.MAX)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from poseestimation_amd import _lib
-    _lib.load()
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+from support import bits, dev, last_kernel, median_ms, ptr, to_device  # noqa: F401
 import three_nn_ref as ref
 import test_three_nn_host as host
 
@@ -21,29 +22,8 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
-def dev():
-    from poseestimation_amd import _lib
-    _lib.load()
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
 def g24_cases():
     return ref.cases(ref.g24())
-
-
-def _d(a, dev, dtype=np.float32):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _last_kernel():
-    from poseestimation_amd import _lib
-    return _lib.load().so3_last_kernel().decode()
 
 
 def _dims(feat, idx, channels_first):
@@ -57,10 +37,10 @@ SEEN = set()
 
 def surface_nn(xyz1, xyz2, want_weight, dev):
     import poseestimation_amd as pa
-    out = pa.three_nn(_d(xyz1, dev), _d(xyz2, dev), return_weights=want_weight)
-    SEEN.add(_last_kernel())
+    out = pa.three_nn(to_device(xyz1, dev), to_device(xyz2, dev), return_weights=want_weight)
+    SEEN.add(last_kernel())
     b, n, s = xyz1.shape[0], xyz1.shape[1], xyz2.shape[1]
-    assert _last_kernel() == "k_three_nn<%d, %s>" % (host.waves_per_point(b, n, s), "true" if want_weight else "false")
+    assert last_kernel() == "k_three_nn<%d, %s>" % (host.waves_per_point(b, n, s), "true" if want_weight else "false")
     assert len(out) == (3 if want_weight else 2) and out[0].dtype == torch.float32 and out[1].dtype == torch.int64
     assert all(t.shape == (b, n, 3) and t.is_cuda and not t.requires_grad for t in out)
     return out[0].cpu().numpy(), out[1].cpu().numpy(), out[2].cpu().numpy() if want_weight else None
@@ -70,20 +50,20 @@ def abi_nn(xyz1, xyz2, want_weight, dev):
     """The raw C ABI into buffers pre-filled with NaN / -1."""
     from poseestimation_amd import _lib
     lib = _lib.load()
-    a, k = _d(xyz1, dev), _d(xyz2, dev)
+    a, k = to_device(xyz1, dev), to_device(xyz2, dev)
     b, n, s = xyz1.shape[0], xyz1.shape[1], xyz2.shape[1]
     d3 = torch.full((b, n, 3), float("nan"), device=dev)
     idx = torch.full((b, n, 3), -1, dtype=torch.int32, device=dev)
     w = torch.full((b, n, 3), float("nan"), device=dev) if want_weight else None
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    _lib.check(lib.so3_three_nn_f32(_ptr(a), _ptr(k), _ptr(d3), _ptr(idx), _ptr(w), b, n, s, st), "so3_three_nn_f32")
+    _lib.check(lib.so3_three_nn_f32(ptr(a), ptr(k), ptr(d3), ptr(idx), ptr(w), b, n, s, st), "so3_three_nn_f32")
     return d3.cpu().numpy(), idx.cpu().numpy(), w.cpu().numpy() if want_weight else None
 
 
 def surface_fwd(feat, idx, weight, channels_first, dev):
     import poseestimation_amd as pa
-    out = pa.three_interpolate(_d(feat, dev), _d(idx, dev, np.int64), _d(weight, dev), channels_first)
-    assert _last_kernel() == "k_three_interp<%s>" % ("true" if channels_first else "false")
+    out = pa.three_interpolate(to_device(feat, dev), to_device(idx, dev, np.int64), to_device(weight, dev), channels_first)
+    assert last_kernel() == "k_three_interp<%s>" % ("true" if channels_first else "false")
     return out.cpu().numpy()
 
 
@@ -93,8 +73,8 @@ def surface_bwd(grad, idx, weight, s, channels_first, dev):
     b, n = idx.shape[:2]
     d = grad.shape[1] if channels_first else grad.shape[2]
     feat = torch.zeros((b, d, s) if channels_first else (b, s, d), device=dev, requires_grad=True)
-    out = pa.three_interpolate(feat, _d(idx, dev, np.int32), _d(weight, dev), channels_first)
-    out.backward(_d(grad, dev))                                                  # (on autograd's thread: so3_last_kernel is per thread, see abi_bwd)
+    out = pa.three_interpolate(feat, to_device(idx, dev, np.int32), to_device(weight, dev), channels_first)
+    out.backward(to_device(grad, dev))                                                  # (on autograd's thread: so3_last_kernel is per thread, see abi_bwd)
     return feat.grad.cpu().numpy()
 
 
@@ -102,11 +82,11 @@ def abi_fwd(feat, idx, weight, channels_first, dev):
     from poseestimation_amd import _lib
     lib = _lib.load()
     b, n, s, d = _dims(feat, idx, channels_first)
-    f, i, w = _d(feat, dev), _d(idx, dev, np.int32), _d(weight, dev)
+    f, i, w = to_device(feat, dev), to_device(idx, dev, np.int32), to_device(weight, dev)
     out = torch.full((b, d, n) if channels_first else (b, n, d), float("nan"), device=dev)
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    _lib.check(lib.so3_three_interpolate_f32(_ptr(f), _ptr(i), _ptr(w), _ptr(out), int(channels_first), b, n, s, d, st), "so3_three_interpolate_f32")
-    assert _last_kernel() == "k_three_interp<%s>" % ("true" if channels_first else "false")
+    _lib.check(lib.so3_three_interpolate_f32(ptr(f), ptr(i), ptr(w), ptr(out), int(channels_first), b, n, s, d, st), "so3_three_interpolate_f32")
+    assert last_kernel() == "k_three_interp<%s>" % ("true" if channels_first else "false")
     return out.cpu().numpy()
 
 
@@ -115,11 +95,11 @@ def abi_bwd(grad, idx, weight, s, channels_first, dev):
     lib = _lib.load()
     b, n = idx.shape[:2]
     d = grad.shape[1] if channels_first else grad.shape[2]
-    g, i, w = _d(grad, dev), _d(idx, dev, np.int32), _d(weight, dev)
+    g, i, w = to_device(grad, dev), to_device(idx, dev, np.int32), to_device(weight, dev)
     out = torch.full((b, d, s) if channels_first else (b, s, d), float("nan"), device=dev)
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    _lib.check(lib.so3_three_interpolate_bwd_f32(_ptr(g), _ptr(i), _ptr(w), _ptr(out), int(channels_first), b, n, s, d, st), "so3_three_interpolate_bwd_f32")
-    assert _last_kernel() == ("k_three_interp_bwd_cf" if channels_first else "k_three_interp_bwd_cl")
+    _lib.check(lib.so3_three_interpolate_bwd_f32(ptr(g), ptr(i), ptr(w), ptr(out), int(channels_first), b, n, s, d, st), "so3_three_interpolate_bwd_f32")
+    assert last_kernel() == ("k_three_interp_bwd_cf" if channels_first else "k_three_interp_bwd_cl")
     return out.cpu().numpy()
 
 
@@ -198,8 +178,8 @@ def test_gradient_against_autograd_through_the_float64_restatement(dev, channels
     assert ((got.double() - want).abs() <= bound).all(), ((got.double() - want).abs().max().item())
     # autograd's gradient is the C ABI's, bit for bit, and both are the defined order's
     direct = abi_bwd(grad.contiguous().cpu().numpy(), idx.cpu().numpy(), w.cpu().numpy(), s, channels_first, dev)
-    assert np.array_equal(host.bits(got.cpu().numpy()), host.bits(direct))
-    assert np.array_equal(host.bits(direct), host.bits(ref.backward32(grad.contiguous().cpu().numpy(), idx.cpu().numpy(), w.cpu().numpy(), s, channels_first)))
+    assert np.array_equal(bits(got.cpu().numpy()), bits(direct))
+    assert np.array_equal(bits(direct), bits(ref.backward32(grad.contiguous().cpu().numpy(), idx.cpu().numpy(), w.cpu().numpy(), s, channels_first)))
     with pytest.raises(RuntimeError, match="differentiate twice|double backward"):
         f2 = feat.detach().clone().requires_grad_(True)
         o2 = pa.three_interpolate(f2, idx, w, channels_first)
@@ -211,10 +191,10 @@ def test_gradient_against_autograd_through_the_float64_restatement(dev, channels
 def test_two_calls_give_the_same_bits_and_a_graph_replays_them(dev, g24_cases):
     import poseestimation_amd as pa
     c = g24_cases[0]
-    xyz1, xyz2 = _d(c["xyz1"], dev), _d(c["xyz2"], dev)
+    xyz1, xyz2 = to_device(c["xyz1"], dev), to_device(c["xyz2"], dev)
     g = torch.Generator().manual_seed(12)
     grad = torch.randn(2, 1024, 16, generator=g).to(dev)
-    feats = [_d(c["feat"], dev), _d(c["feat"].transpose(0, 2, 1), dev)]
+    feats = [to_device(c["feat"], dev), to_device(c["feat"].transpose(0, 2, 1), dev)]
     grads = [grad, grad.transpose(1, 2).contiguous()]
     from poseestimation_amd import _lib
     lib = _lib.load()
@@ -226,7 +206,7 @@ def test_two_calls_give_the_same_bits_and_a_graph_replays_them(dev, g24_cases):
         for cf in (0, 1):
             out.append(pa.three_interpolate(feats[cf], idx, w, bool(cf)))
             gf = torch.empty_like(feats[cf])
-            _lib.check(lib.so3_three_interpolate_bwd_f32(_ptr(grads[cf]), _ptr(i32), _ptr(w), _ptr(gf), cf, 2, 1024, 512, 16,
+            _lib.check(lib.so3_three_interpolate_bwd_f32(ptr(grads[cf]), ptr(i32), ptr(w), ptr(gf), cf, 2, 1024, 512, 16,
                                                          ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "so3_three_interpolate_bwd_f32")
             out.append(gf)
         return out
@@ -335,21 +315,6 @@ def test_errors_and_warnings(dev):
 
 
 # ---- the speed condition --------------------------------------------------------------------------------------------------------
-def _median_ms(fn):
-    for _ in range(5):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(20):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        times.append(e0.elapsed_time(e1))
-    return float(np.median(times))
-
-
 def torch_interpolate(xyz1, xyz2, points2):
     """The torch spelling of point_cloud/pointnet_utils.py:286-293 on the device: the expanded squared distances, a full sort along S,
     the weight lines, the (B, N, 3, D) gather, product and sum."""
@@ -378,15 +343,15 @@ def test_feature_interpolation_is_not_slower_than_the_torch_spelling(dev):
     with torch.no_grad():
         ours, theirs = pa.interpolate_features(xyz1, xyz2, feat), torch_interpolate(xyz1, xyz2, feat)
         assert ((ours - theirs).abs().amax(-1) > 1e-3).float().mean().item() < 0.01   # the same quantity (not an accuracy check)
-        ours_f = _median_ms(lambda: pa.interpolate_features(xyz1, xyz2, feat))
-        theirs_f = _median_ms(lambda: torch_interpolate(xyz1, xyz2, feat))
+        ours_f = median_ms(lambda: pa.interpolate_features(xyz1, xyz2, feat))
+        theirs_f = median_ms(lambda: torch_interpolate(xyz1, xyz2, feat))
 
     def both(fn):
         feat.grad = None
         fn(xyz1, xyz2, feat).backward(cot)
 
-    ours_fb = _median_ms(lambda: both(pa.interpolate_features))
-    theirs_fb = _median_ms(lambda: both(torch_interpolate))
+    ours_fb = median_ms(lambda: both(pa.interpolate_features))
+    theirs_fb = median_ms(lambda: both(torch_interpolate))
     line = ("interpolate_features 32x1024<-512, D=128: forward %.4f ms, torch spelling %.4f ms (x%.1f); forward + backward %.4f ms, torch %.4f ms (x%.1f)"
             % (ours_f, theirs_f, theirs_f / ours_f, ours_fb, theirs_fb, theirs_fb / ours_fb))
     print(line)

@@ -14,7 +14,6 @@ import ctypes
 import functools
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -22,6 +21,7 @@ import torch
 
 from conftest import ROOT
 import grouping_ref as ref
+from support import bits, boundary, build_host_model, np_ptr, on_own_thread
 
 NEW_SYMBOLS = {"so3_group_points_f32": 13, "so3_group_points_bwd_f32": 13}
 NEW_NAMES = ("group_points", "sample_and_group_all", "set_abstraction_group", "set_abstraction_msg_group")
@@ -146,34 +146,12 @@ def test_the_shape_list_holds_what_it_promises():
 # ---- the boundary -----------------------------------------------------------------------------------------------------------------
 def test_header_binding_table_and_library_agree(built_library):
     from poseestimation_amd import _lib
-    raw = open(os.path.join(ROOT, "include", "so3proj.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = set(re.findall(r"\b(so3_[a-z0-9_]+)\s*\(", text))
-    lib = ctypes.CDLL(built_library)
-    for name, nargs in NEW_SYMBOLS.items():
-        assert name in declared and name in _lib.SYMBOLS and hasattr(lib, name), name
-        args = re.search(r"\b%s\s*\(([^)]*)\)" % name, text).group(1).split(",")
-        assert len(args) == len(_lib.SYMBOLS[name][1]) == nargs, (name, args)
-    assert lib.so3_version() == _lib.ABI_VERSION == 210
+    raw, _ = boundary(built_library, NEW_SYMBOLS)
     assert int(re.search(r"#define SO3_GROUP_MAX_K (\d+)", raw).group(1)) == _lib.GROUP_MAX_K == 65536
 
 
 def test_argument_validation_without_gpu(built_library):
-    """On a thread of its own: so3_last_error is thread-local and never cleared, and other tests read it on the main thread."""
-    import threading
-    failure = []
-
-    def body():
-        try:
-            _argument_validation()
-        except BaseException as exc:               # noqa: BLE001 -- re-raised on the main thread
-            failure.append(exc)
-
-    t = threading.Thread(target=body)
-    t.start()
-    t.join()
-    if failure:
-        raise failure[0]
+    on_own_thread(_argument_validation)
 
 
 def _argument_validation():
@@ -252,21 +230,21 @@ def test_g25_holds_the_cases_and_the_cap(g25):
 
 
 # ---- the checks, shared with tests/test_gpu_grouping.py ------------------------------------------------------------------------------
-def bits(a):
-    a = np.ascontiguousarray(a)
-    assert a.dtype == np.float32, a.dtype
-    return a.view(np.uint32)
+def f32_bits(a):
+    """support.bits of what must be float32 already: bits() alone would round a float64 result and then find it equal."""
+    assert np.asarray(a).dtype == np.float32, np.asarray(a).dtype
+    return bits(a)
 
 
 def check_forward(name, run_fwd, xyz, centres, feat, idx, channels_first, features_first, want=None):
     """run_fwd(xyz, centres, feat, idx, channels_first, features_first) -> out.  Bit-equal to the restatement."""
     want = ref.forward(xyz, centres, feat, idx, channels_first, features_first) if want is None else want
     got = np.asarray(run_fwd(xyz, centres, feat, idx, channels_first, features_first))
-    assert got.shape == want.shape and np.array_equal(bits(got), bits(want)), (name, channels_first, features_first, np.argwhere(bits(got) != bits(want))[:4])
+    assert got.shape == want.shape and np.array_equal(f32_bits(got), f32_bits(want)), (name, channels_first, features_first, np.argwhere(f32_bits(got) != f32_bits(want))[:4])
     bad = ~ref.valid(idx, xyz.shape[1])
     if bad.any():
         slots = got.transpose(0, 3, 2, 1) if channels_first else got
-        assert not bits(slots[bad]).any(), name                                   # +0 in every channel of an invalid slot
+        assert not f32_bits(slots[bad]).any(), name                                   # +0 in every channel of an invalid slot
     return got
 
 
@@ -289,13 +267,13 @@ def check_backward(name, run_bwd, grad, idx, n, d, channels_first, features_firs
         err = np.abs(g.astype(np.float64) - want64[key])
         assert (err <= bound[key]).all(), (name, key, channels_first, features_first, err.max(), (err - bound[key]).max())
         if exact:
-            assert np.array_equal(bits(g), bits(want32[key])), (name, key, channels_first, features_first)
+            assert np.array_equal(f32_bits(g), f32_bits(want32[key])), (name, key, channels_first, features_first)
         if key == "grad_centres":
-            assert not bits(g[want64["slots"] == 0]).any(), name                   # a row without a valid slot: +0
+            assert not f32_bits(g[want64["slots"] == 0]).any(), name                   # a row without a valid slot: +0
         else:
             none = hits == 0
             untouched = np.broadcast_to(none[:, None, :] if key == "grad_feat" and channels_first else none[:, :, None], g.shape)
-            assert not bits(g[untouched]).any(), (name, key)                       # exactly +0 (and written: the buffers start as NaN)
+            assert not f32_bits(g[untouched]).any(), (name, key)                       # exactly +0 (and written: the buffers start as NaN)
     if subsets:
         for sel in ((True, False, False), (False, True, False), (False, False, True), (True, False, True)):
             if sel[2] and d == 0:
@@ -304,7 +282,7 @@ def check_backward(name, run_bwd, grad, idx, n, d, channels_first, features_firs
             for key, asked, a in zip(keys, sel, alone):
                 assert (a is not None) == asked, (name, sel)
                 if asked:
-                    assert np.array_equal(bits(a), bits(got[key])), (name, key, sel)
+                    assert np.array_equal(f32_bits(a), f32_bits(got[key])), (name, key, sel)
     return got
 
 
@@ -330,12 +308,12 @@ def check_g25_forward(g25, run_fwd):
             for cf in (False, True):
                 feat = np.ascontiguousarray(pts.transpose(0, 2, 1)) if cf else pts
                 got = check_forward("G25 " + tag, run_fwd, xyz, centres, feat, idx, cf, ff)
-                assert np.array_equal(bits(got if cf else got.transpose(0, 3, 2, 1)), bits(t)), (tag, cf)
+                assert np.array_equal(f32_bits(got if cf else got.transpose(0, 3, 2, 1)), f32_bits(t)), (tag, cf)
     a = g25["all"]
     idx = np.broadcast_to(np.arange(ref.N_ALL), (2, 1, ref.N_ALL))
     got = check_forward("G25 group_all", run_fwd, g25["xyz_all"], np.zeros((2, 1, 3), np.float32), np.ascontiguousarray(g25["points_all"].transpose(0, 2, 1)),
                         idx, True, False)
-    assert np.array_equal(bits(got), bits(a["t"]))
+    assert np.array_equal(f32_bits(got), f32_bits(a["t"]))
 
 
 def check_g25_gradients(g25, run_bwd, exact):
@@ -384,28 +362,18 @@ def check_g25_gradients(g25, run_bwd, exact):
     g = ref.seeded_g(0, a["t"].shape)
     idx = np.broadcast_to(np.arange(ref.N_ALL), (2, 1, ref.N_ALL))
     got = check_backward("G25 group_all", run_bwd, g, idx, ref.N_ALL, d, True, False, exact)
-    assert np.array_equal(bits(got["grad_xyz"].transpose(0, 2, 1)), bits(a["grad_xyz"])) and np.array_equal(bits(got["grad_feat"]), bits(a["grad_points"]))
-    assert np.array_equal(bits(got["grad_xyz"].transpose(0, 2, 1)), bits(g[:, :3, :, 0]))
+    assert np.array_equal(f32_bits(got["grad_xyz"].transpose(0, 2, 1)), f32_bits(a["grad_xyz"])) and np.array_equal(f32_bits(got["grad_feat"]), f32_bits(a["grad_points"]))
+    assert np.array_equal(f32_bits(got["grad_xyz"].transpose(0, 2, 1)), f32_bits(g[:, :3, :, 0]))
 
 
 # ---- the host model -----------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def model(tmp_path_factory):
-    from oracle import kernel_model
-    cxx = kernel_model.clangxx()
-    if cxx is None:
-        pytest.skip("clang++ is not available (ext_vector_type)")
-    out = str(tmp_path_factory.mktemp("grouping") / "libgrouping.so")
-    subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", out, SRC], check=True)
-    lib = ctypes.CDLL(out)
+    lib = build_host_model(tmp_path_factory, "grouping", SRC)
     lib.model_group_points.argtypes = lib.model_group_points_bwd.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int32] * 2 + [ctypes.c_int64] + [ctypes.c_int32] * 4
     lib.model_group_points.restype = lib.model_group_points_bwd.restype = None
     lib.model_group_bwd_narrow.argtypes, lib.model_group_bwd_narrow.restype = [ctypes.c_int32], ctypes.c_int32
     return lib
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
 def model_fwd(lib, xyz, centres, feat, idx, channels_first, features_first):
@@ -414,7 +382,7 @@ def model_fwd(lib, xyz, centres, feat, idx, channels_first, features_first):
     b, n, s, k = xyz.shape[0], xyz.shape[1], idx.shape[1], idx.shape[2]
     d = 0 if feat is None else feat.shape[1 if channels_first else 2]
     out = np.full((b, 3 + d, k, s) if channels_first else (b, s, k, 3 + d), np.nan, np.float32)
-    lib.model_group_points(_p(xyz), _p(centres), _p(feat), _p(idx), _p(out), int(features_first), int(channels_first), b, n, s, k, d)
+    lib.model_group_points(np_ptr(xyz), np_ptr(centres), np_ptr(feat), np_ptr(idx), np_ptr(out), int(features_first), int(channels_first), b, n, s, k, d)
     return out
 
 
@@ -424,7 +392,7 @@ def model_bwd(lib, grad, idx, n, d, channels_first, features_first, sel):
     gx = np.full((b, n, 3), np.nan, np.float32) if sel[0] else None
     gc = np.full((b, s, 3), np.nan, np.float32) if sel[1] else None
     gf = np.full((b, d, n) if channels_first else (b, n, d), np.nan, np.float32) if sel[2] and d else None
-    lib.model_group_points_bwd(_p(grad), _p(idx), _p(gx), _p(gc), _p(gf), int(features_first), int(channels_first), b, n, s, k, d)
+    lib.model_group_points_bwd(np_ptr(grad), np_ptr(idx), np_ptr(gx), np_ptr(gc), np_ptr(gf), int(features_first), int(channels_first), b, n, s, k, d)
     return gx, gc, gf
 
 

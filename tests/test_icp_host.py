@@ -22,7 +22,6 @@ checks; DESIGN.md section 7d quotes them."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -31,6 +30,7 @@ import torch
 from conftest import ROOT
 import icp_ref as ref
 import rigid_align_ref as ra
+from support import boundary, build_host_model, np_ptr, on_own_thread
 
 #                                 measured on the host       bound (4 x)
 HOST_SEARCH = 9.795e-8;           SEARCH_TOL = 4 * HOST_SEARCH           # noqa: E702
@@ -66,36 +66,12 @@ def bounds_g4():
 # ---- the boundary ---------------------------------------------------------------------------------------------------------
 def test_header_binding_table_and_library_agree(built_library):
     from poseestimation_amd import _lib
-    raw = open(os.path.join(ROOT, "include", "so3proj.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = set(re.findall(r"\b(so3_[a-z0-9_]+)\s*\(", text))
-    lib = ctypes.CDLL(built_library)
-    for name, nargs in NEW_SYMBOLS.items():
-        assert name in declared, name
-        assert name in _lib.SYMBOLS, name
-        assert hasattr(lib, name), name
-        args = re.search(r"\b%s\s*\(([^)]*)\)" % name, text).group(1).split(",")
-        assert len(args) == len(_lib.SYMBOLS[name][1]) == nargs, (name, args)
-    assert lib.so3_version() == _lib.ABI_VERSION == 210
+    raw, _ = boundary(built_library, NEW_SYMBOLS)
     assert int(re.search(r"#define SO3_ADD_S_MAX_N (\d+)", raw).group(1)) == _lib.ADD_S_MAX_N
 
 
 def test_argument_validation_without_gpu(built_library):
-    """On a thread of its own: so3_last_error is thread-local and never cleared, and other tests read it on the main thread."""
-    import threading
-    failure = []
-
-    def body():
-        try:
-            _argument_validation()
-        except BaseException as exc:               # noqa: BLE001 -- re-raised on the main thread
-            failure.append(exc)
-
-    t = threading.Thread(target=body)
-    t.start()
-    t.join()
-    if failure:
-        raise failure[0]
+    on_own_thread(_argument_validation)
 
 
 def _argument_validation():
@@ -273,22 +249,12 @@ def check_against_g21(cases, run, label):
 # ---- the device functions on the host --------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def model(tmp_path_factory):
-    from oracle import kernel_model
-    cxx = kernel_model.clangxx()
-    if cxx is None:
-        pytest.skip("clang++ is not available (ext_vector_type)")
-    out = str(tmp_path_factory.mktemp("icp") / "libicp.so")
-    subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", out, SRC], check=True)
-    lib = ctypes.CDLL(out)
+    lib = build_host_model(tmp_path_factory, "icp", SRC)
     lib.model_icp.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_int32] + \
         [ctypes.c_void_p] * 6 + [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64]
     lib.model_nearest.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]
     lib.model_icp_points_per_lane.argtypes = [ctypes.c_int64, ctypes.c_int32, ctypes.c_int64]
     return lib
-
-
-def _p(a):
-    return ctypes.c_void_p(a.ctypes.data) if a is not None else None
 
 
 def initial_rows(c):
@@ -303,14 +269,14 @@ def abi_run(near, icp, c, tail=(), iterations=None, workspace=None):
     P, Q = np.ascontiguousarray(c["P"]), np.ascontiguousarray(c["Q"])
     out = {"dist": np.full((b, n), np.nan, np.float32), "nearest": np.full((b, n), -1, np.int32)}
     if c["kind"] == "search":
-        near(_p(P), _p(Q), stride, _p(out["dist"]), _p(out["nearest"]), b, n, m, *tail)
+        near(np_ptr(P), np_ptr(Q), stride, np_ptr(out["dist"]), np_ptr(out["nearest"]), b, n, m, *tail)
         return out
     it = c["iterations"] if iterations is None else iterations
     out.update(R=np.full((b, 3, 3), np.nan, np.float32), t=np.full((b, 3), np.nan, np.float32), rmse=np.full((it, b), np.nan, np.float32),
                inliers=np.full((it, b), -1, np.int32))
     w, T0 = (None if c["w"] is None else np.ascontiguousarray(c["w"])), initial_rows(c)
     md = -1.0 if c["max_distance"] is None else c["max_distance"]
-    icp(_p(P), _p(Q), stride, _p(w), _p(T0), md, it, _p(out["R"]), _p(out["t"]), _p(out["rmse"]), _p(out["inliers"]), _p(out["nearest"]), _p(out["dist"]),
+    icp(np_ptr(P), np_ptr(Q), stride, np_ptr(w), np_ptr(T0), md, it, np_ptr(out["R"]), np_ptr(out["t"]), np_ptr(out["rmse"]), np_ptr(out["inliers"]), np_ptr(out["nearest"]), np_ptr(out["dist"]),
         *(() if workspace is None else (workspace,)), b, n, m, *tail)
     return out
 

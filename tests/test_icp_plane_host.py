@@ -31,6 +31,7 @@ import torch
 from conftest import ROOT
 import icp_plane_ref as ref
 import rigid_align_ref as ra
+from support import boundary, build_host_model, np_ptr, on_own_thread
 
 #            measured on the host (the bound is 4 x)
 MEASURED = {"search": 1.078e-7, "R": 4.172e-6, "T": 1.501e-6, "rmse": 5.109e-6, "rmse_point": 4.515e-6, "rotation": 1.304e-7,
@@ -49,37 +50,12 @@ def bounds():
 
 # ---- the boundary ---------------------------------------------------------------------------------------------------------
 def test_header_binding_table_and_library_agree(built_library):
-    from poseestimation_amd import _lib
-    raw = open(os.path.join(ROOT, "include", "so3proj.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = set(re.findall(r"\b(so3_[a-z0-9_]+)\s*\(", text))
-    lib = ctypes.CDLL(built_library)
-    exported = subprocess.run(["nm", "-D", "--defined-only", built_library], capture_output=True, text=True, check=True).stdout
-    for name, nargs in NEW_SYMBOLS.items():
-        assert name in declared and name in _lib.SYMBOLS and hasattr(lib, name), name
-        assert re.search(r"\b%s\b" % name, exported), name
-        args = re.search(r"\b%s\s*\(([^)]*)\)" % name, text).group(1).split(",")
-        assert len(args) == len(_lib.SYMBOLS[name][1]) == nargs, (name, args)
-    assert lib.so3_version() == _lib.ABI_VERSION == 210
+    raw, _ = boundary(built_library, NEW_SYMBOLS)
     assert float(re.search(r"#define SO3_ICP_PLANE_PIVOT_EPS ([0-9.]+)f", raw).group(1)) == PIVOT_EPS
 
 
 def test_argument_validation_without_gpu(built_library):
-    """On a thread of its own: so3_last_error is thread-local and never cleared, and other tests read it on the main thread."""
-    import threading
-    failure = []
-
-    def body():
-        try:
-            _argument_validation()
-        except BaseException as exc:               # noqa: BLE001 -- re-raised on the main thread
-            failure.append(exc)
-
-    t = threading.Thread(target=body)
-    t.start()
-    t.join()
-    if failure:
-        raise failure[0]
+    on_own_thread(_argument_validation)
 
 
 def _argument_validation():
@@ -251,23 +227,13 @@ def check_against_g30(cases, run, label):
 # ---- the device functions on the host --------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def model(tmp_path_factory):
-    from oracle import kernel_model
-    cxx = kernel_model.clangxx()
-    if cxx is None:
-        pytest.skip("clang++ is not available (ext_vector_type)")
-    out = str(tmp_path_factory.mktemp("icp_plane") / "libicp_plane.so")
-    subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", out, SRC], check=True)
-    lib = ctypes.CDLL(out)
+    lib = build_host_model(tmp_path_factory, "icp_plane", SRC)
     lib.model_icp_plane.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_int32] + \
         [ctypes.c_void_p] * 9 + [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64]
     lib.model_plane_solve.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]
     lib.model_plane_retraction.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     lib.model_plane_pivot_eps.restype = ctypes.c_float
     return lib
-
-
-def _p(a):
-    return ctypes.c_void_p(a.ctypes.data) if a is not None else None
 
 
 def initial_rows(c):
@@ -285,15 +251,15 @@ def abi_run(icp, c, tail=(), iterations=None, workspace=(), normals=None):
            "inliers": np.full((it, b), -1, np.int32), "solved": np.full((it, b), -1, np.int32)}
     w, T0 = (None if c["w"] is None else np.ascontiguousarray(c["w"])), initial_rows(c)
     md = -1.0 if c["max_distance"] is None else c["max_distance"]
-    icp(_p(P), _p(Q), _p(N), 0 if c["shared"] else 3 * m, _p(w), _p(T0), md, c["damping"], it, _p(out["R"]), _p(out["t"]), _p(out["rmse"]),
-        _p(out["rmse_point"]), _p(out["inliers"]), _p(out["solved"]), _p(out["nearest"]), _p(out["dist"]), *workspace, b, n, m, *tail)
+    icp(np_ptr(P), np_ptr(Q), np_ptr(N), 0 if c["shared"] else 3 * m, np_ptr(w), np_ptr(T0), md, c["damping"], it, np_ptr(out["R"]), np_ptr(out["t"]), np_ptr(out["rmse"]),
+        np_ptr(out["rmse_point"]), np_ptr(out["inliers"]), np_ptr(out["solved"]), np_ptr(out["nearest"]), np_ptr(out["dist"]), *workspace, b, n, m, *tail)
     return out
 
 
 def host_run(model, c, cus=CUS, iterations=None, normals=None, want_ratio=False):
     it = c["iterations"] if iterations is None else iterations
     ratio = np.full((it, c["b"]), np.nan, np.float32)
-    out = abi_run(model.model_icp_plane, c, (cus,), iterations, (_p(ratio),), normals)
+    out = abi_run(model.model_icp_plane, c, (cus,), iterations, (np_ptr(ratio),), normals)
     if want_ratio:
         out["ratio"] = ratio
     return out
@@ -371,7 +337,7 @@ def test_negated_normals_give_the_same_bits(model, g30_cases):
 def _solve(model, A, g, damping=0.0):
     A32, g32 = np.ascontiguousarray(A, np.float32), np.ascontiguousarray(g, np.float32)
     delta, ratio = np.full(6, np.nan, np.float32), np.full(1, np.nan, np.float32)
-    ok = model.model_plane_solve(_p(A32), _p(g32), damping, _p(delta), _p(ratio))
+    ok = model.model_plane_solve(np_ptr(A32), np_ptr(g32), damping, np_ptr(delta), np_ptr(ratio))
     return bool(ok), delta, float(ratio[0])
 
 
@@ -443,7 +409,7 @@ def test_the_retraction_is_orthogonal_and_the_cayley_formula(model):
         axis = rng.standard_normal(3)
         omega = (axis / np.linalg.norm(axis) * 10.0 ** rng.uniform(-6, np.log10(3.0))).astype(np.float32)
         dr = np.full(9, np.nan, np.float32)
-        model.model_plane_retraction(_p(omega), _p(dr))
+        model.model_plane_retraction(np_ptr(omega), np_ptr(dr))
         dr = dr.reshape(3, 3).astype(np.float64)
         want = ref.cayley64(omega.astype(np.float64))
         err, orth = np.abs(dr - want).max(), np.abs(dr.T @ dr - np.eye(3)).max()

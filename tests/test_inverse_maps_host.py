@@ -10,8 +10,6 @@ normalisation for the gradient bound: gradients are max |difference| per row ove
 the gradient is of order one, relative where it is large (Euler's 1 / cos(e2) reaches 20 outside the excluded band).  tests/test_gpu_inverse_maps.py imports the bounds from here; DESIGN.md quotes them."""
 import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -19,6 +17,7 @@ import torch
 
 from conftest import ROOT
 import inverse_maps_ref as ref
+from support import boundary, build_host_model, np_ptr
 
 #                                measured on the host        bound (4 x)
 HOST_QUAT_VALUE = 1.42e-7;       QUAT_VALUE_TOL = 4 * HOST_QUAT_VALUE          # noqa: E702   (must stay below 1e-6)
@@ -49,17 +48,7 @@ SRC = os.path.join(ROOT, "tests", "host_model", "inverse_maps.cpp")
 
 # ---- the boundary ---------------------------------------------------------------------------------------------------------
 def test_header_binding_table_and_library_agree(built_library):
-    from poseestimation_amd import _lib
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "so3proj.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(so3_[a-z0-9_]+)\s*\(", text))
-    lib = ctypes.CDLL(built_library)
-    for name in NEW_SYMBOLS:
-        assert name in declared, name
-        assert name in _lib.SYMBOLS, name
-        assert hasattr(lib, name), name
-        args = re.search(r"\b%s\s*\(([^)]*)\)" % name, text).group(1).split(",")
-        assert len(args) == len(_lib.SYMBOLS[name][1]), (name, args)
-    assert lib.so3_version() == _lib.ABI_VERSION == 210
+    boundary(built_library, NEW_SYMBOLS)
 
 
 def test_argument_validation_without_gpu(built_library):
@@ -131,17 +120,7 @@ def test_g18_is_self_consistent(g18):
 # ---- the device operations on the host ----------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def model(tmp_path_factory):
-    from oracle import kernel_model
-    cxx = kernel_model.clangxx()
-    if cxx is None:
-        pytest.skip("clang++ is not available (ext_vector_type)")
-    out = str(tmp_path_factory.mktemp("inverse_maps") / "libinverse_maps.so")
-    subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", out, SRC], check=True)
-    return ctypes.CDLL(out)
-
-
-def _p(a):
-    return ctypes.c_void_p(a.ctypes.data) if a is not None else None
+    return build_host_model(tmp_path_factory, "inverse_maps", SRC)
 
 
 def _c(a):
@@ -151,14 +130,14 @@ def _c(a):
 def run_fwd(model, name, r, width, packed):
     r = _c(r)
     out = np.full((len(r), width), np.nan, np.float32)
-    getattr(model, "model_%s_fwd" % name)(_p(r), _p(out), ctypes.c_int64(len(r)), int(packed))
+    getattr(model, "model_%s_fwd" % name)(np_ptr(r), np_ptr(out), ctypes.c_int64(len(r)), int(packed))
     return out
 
 
 def run_bwd(model, name, r, g, packed):
     r, g = _c(r), _c(g)
     out = np.full((len(r), 9), np.nan, np.float32)
-    getattr(model, "model_%s_bwd" % name)(_p(r), _p(g), _p(out), ctypes.c_int64(len(r)), int(packed))
+    getattr(model, "model_%s_bwd" % name)(np_ptr(r), np_ptr(g), np_ptr(out), ctypes.c_int64(len(r)), int(packed))
     return out.reshape(-1, 3, 3)
 
 
@@ -167,11 +146,11 @@ def run_rel(model, r1, r2, packed, g=None, want1=True, want2=True):
     n = ctypes.c_int64(len(r1))
     if g is None:
         out = np.full((len(r1), 3), np.nan, np.float32)
-        model.model_relative_log_fwd(_p(r1), _p(r2), _p(out), n, int(packed))
+        model.model_relative_log_fwd(np_ptr(r1), np_ptr(r2), np_ptr(out), n, int(packed))
         return out
     d1 = np.full((len(r1), 9), np.nan, np.float32) if want1 else None
     d2 = np.full((len(r1), 9), np.nan, np.float32) if want2 else None
-    model.model_relative_log_bwd(_p(r1), _p(r2), _p(_c(g)), _p(d1), _p(d2), n, int(packed))
+    model.model_relative_log_bwd(np_ptr(r1), np_ptr(r2), np_ptr(_c(g)), np_ptr(d1), np_ptr(d2), n, int(packed))
     return d1, d2
 
 
@@ -279,7 +258,7 @@ def test_atan2_against_long_double(model):
     x = np.array([0.0, 0.0, -0.0, 0.0, 0.0, -1.0, 1.0, np.nan], np.float32)
     for packed in (0, 1):
         out = np.empty(8, np.float32)
-        model.model_atan2(_p(y), _p(x), _p(out), ctypes.c_int64(8), packed)
+        model.model_atan2(np_ptr(y), np_ptr(x), np_ptr(out), ctypes.c_int64(8), packed)
         assert (out[:3] == 0).all() and out[3] == np.float32(np.pi / 2) and out[4] == -np.float32(np.pi / 2) and out[5] == np.float32(np.pi)
         assert np.isnan(out[6:]).all()
 

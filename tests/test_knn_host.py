@@ -11,8 +11,6 @@ import ctypes
 import functools
 import os
 import re
-import subprocess
-import threading
 
 import numpy as np
 import pytest
@@ -20,6 +18,7 @@ import torch
 
 from conftest import ROOT
 import knn_ref as ref
+from support import bits, boundary, build_host_model, lengths_of, np_ptr, on_own_thread
 import three_nn_ref
 
 NEW_SYMBOLS = {"so3_knn_f32": 12, "so3_knn_bwd_f32": 13}
@@ -36,36 +35,12 @@ def queries_per_wave(b, n, m):
 # ---- the boundary ---------------------------------------------------------------------------------------------------------
 def test_header_binding_table_and_library_agree(built_library):
     from poseestimation_amd import _lib
-    raw = open(os.path.join(ROOT, "include", "so3proj.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = set(re.findall(r"\b(so3_[a-z0-9_]+)\s*\(", text))
-    exported = subprocess.run(["nm", "-D", "--defined-only", built_library], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r"\b(so3_[a-z0-9_]+)\b", exported))
-    assert declared == set(_lib.SYMBOLS) == exported
-    lib = ctypes.CDLL(built_library)
-    for name, nargs in NEW_SYMBOLS.items():
-        assert name in declared and name in _lib.SYMBOLS and hasattr(lib, name), name
-        args = re.search(r"\b%s\s*\(([^)]*)\)" % name, text).group(1).split(",")
-        assert len(args) == len(_lib.SYMBOLS[name][1]) == nargs, (name, args)
-    assert lib.so3_version() == _lib.ABI_VERSION == 210
+    raw, _ = boundary(built_library, NEW_SYMBOLS)
     assert int(re.search(r"#define SO3_KNN_MAX_K (\d+)", raw).group(1)) == _lib.KNN_MAX_K == ref.MAX_K == 64
 
 
 def test_argument_validation_without_gpu(built_library):
-    """On a thread of its own: so3_last_error is thread-local and never cleared, and other tests read it on the main thread."""
-    failure = []
-
-    def body():
-        try:
-            _argument_validation()
-        except BaseException as exc:               # noqa: BLE001 -- re-raised on the main thread
-            failure.append(exc)
-
-    t = threading.Thread(target=body)
-    t.start()
-    t.join()
-    if failure:
-        raise failure[0]
+    on_own_thread(_argument_validation)
 
 
 def _argument_validation():
@@ -156,7 +131,7 @@ def test_g28_is_self_consistent(g28_cases):
         assert X.dtype == Y.dtype == np.float32 and np.isfinite(both).all() and np.linalg.norm(both, axis=-1).max() <= 1 + 1e-6, c["name"]
         d2, idx = ref.knn32(X, Y, K, xl, yl)
         assert np.array_equal(idx, c["idx"]) and np.array_equal(d2.view(np.uint32), c["dist2"].view(np.uint32)), c["name"]
-        nl, ml = ref.lengths_of(xl, c["b"], c["n"]), ref.lengths_of(yl, c["b"], c["m"])
+        nl, ml = lengths_of(xl, c["b"], c["n"]), lengths_of(yl, c["b"], c["m"])
         if c["lengths"] == "ragged":
             assert c["b"] == ref.B_RAGGED and nl[0] == 0 and ml[1] == 0 and ml[2] == 1 and nl[1:].min() >= 1, c["name"]
             assert 1 < ml[3] < K or min(K, c["m"] + 1) <= 2, c["name"]
@@ -211,10 +186,6 @@ def test_knn32_at_k3_is_three_nn_on_g24():
 
 
 # ---- the checks, shared with tests/test_gpu_knn.py -----------------------------------------------------------------------
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 @functools.lru_cache(maxsize=None)
 def _g28_expected():
     out = {}
@@ -262,23 +233,13 @@ def check_against_g28(cases, run, label):
 # ---- the device functions on the host --------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def model(tmp_path_factory):
-    from oracle import kernel_model
-    cxx = kernel_model.clangxx()
-    if cxx is None:
-        pytest.skip("clang++ is not available (ext_vector_type)")
-    out = str(tmp_path_factory.mktemp("knn") / "libknn.so")
-    subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", out, SRC], check=True)
-    lib = ctypes.CDLL(out)
+    lib = build_host_model(tmp_path_factory, "knn", SRC)
     P, I64, I32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
     lib.model_knn.argtypes = [P, P, I64, P, P, P, P, I32, I64, I32, I32, I32]
     lib.model_knn_bwd.argtypes = [P] * 8 + [I32, I64, I32, I32]
     lib.model_knn_queries_per_wave.argtypes = [I64, I32, I32]
     lib.model_knn.restype = lib.model_knn_bwd.restype = None
     return lib
-
-
-def _p(a):
-    return ctypes.c_void_p(a.ctypes.data) if a is not None else None
 
 
 def host_run(model, c, g, q):
@@ -288,8 +249,8 @@ def host_run(model, c, g, q):
     yl = None if c["y_lengths"] is None else np.ascontiguousarray(c["y_lengths"], np.int32)
     d2, idx = np.full((b, n, K), np.nan, np.float32), np.full((b, n, K), -2, np.int32)
     dX, dY = np.full((b, n, 3), np.nan, np.float32), np.full((b, m, 3), np.nan, np.float32)
-    model.model_knn(_p(X), _p(Y), 3 * m, _p(xl), _p(yl), _p(d2), _p(idx), K, b, n, m, q)
-    model.model_knn_bwd(_p(X), _p(Y), _p(xl), _p(yl), _p(idx), _p(np.ascontiguousarray(g)), _p(dX), _p(dY), K, b, n, m)
+    model.model_knn(np_ptr(X), np_ptr(Y), 3 * m, np_ptr(xl), np_ptr(yl), np_ptr(d2), np_ptr(idx), K, b, n, m, q)
+    model.model_knn_bwd(np_ptr(X), np_ptr(Y), np_ptr(xl), np_ptr(yl), np_ptr(idx), np_ptr(np.ascontiguousarray(g)), np_ptr(dX), np_ptr(dY), K, b, n, m)
     return d2, idx, dX, dY
 
 

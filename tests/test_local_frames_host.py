@@ -8,9 +8,6 @@ UN-multiplied figures (ref.MEASURED), which is what keeps the constants honest. 
 and runs them on the device."""
 import ctypes
 import os
-import re
-import subprocess
-import threading
 
 import numpy as np
 import pytest
@@ -18,6 +15,7 @@ import torch
 
 from conftest import ROOT
 import local_frames_ref as ref
+from support import bits, boundary, build_host_model, lengths_of, np_ptr, on_own_thread
 
 NEW_SYMBOLS = {"so3_local_frames_f32": 15}
 SRC = os.path.join(ROOT, "tests", "host_model", "local_frames.cpp")
@@ -28,36 +26,12 @@ SWEEPS = 4                           # so3_device.h: kFramesSweeps
 # ---- the boundary ---------------------------------------------------------------------------------------------------------
 def test_header_binding_table_and_library_agree(built_library):
     from poseestimation_amd import _lib
-    raw = open(os.path.join(ROOT, "include", "so3proj.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = set(re.findall(r"\b(so3_[a-z0-9_]+)\s*\(", text))
-    exported = subprocess.run(["nm", "-D", "--defined-only", built_library], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r"\b(so3_[a-z0-9_]+)\b", exported))
-    assert declared == set(_lib.SYMBOLS) == exported
-    lib = ctypes.CDLL(built_library)
-    for name, nargs in NEW_SYMBOLS.items():
-        assert name in declared and name in _lib.SYMBOLS and hasattr(lib, name), name
-        args = re.search(r"\b%s\s*\(([^)]*)\)" % name, text).group(1).split(",")
-        assert len(args) == len(_lib.SYMBOLS[name][1]) == nargs, (name, args)
-    assert lib.so3_version() == _lib.ABI_VERSION == 210
+    boundary(built_library, NEW_SYMBOLS)
     assert _lib.KNN_MAX_K == ref.MAX_K == 64
 
 
 def test_argument_validation_without_gpu(built_library):
-    """On a thread of its own: so3_last_error is thread-local and never cleared, and other tests read it on the main thread."""
-    failure = []
-
-    def body():
-        try:
-            _argument_validation()
-        except BaseException as exc:               # noqa: BLE001 -- re-raised on the main thread
-            failure.append(exc)
-
-    t = threading.Thread(target=body)
-    t.start()
-    t.join()
-    if failure:
-        raise failure[0]
+    on_own_thread(_argument_validation)
 
 
 def _argument_validation():
@@ -120,7 +94,7 @@ def test_g29_is_self_consistent(g29_cases):
         assert Y.dtype == np.float32 and np.isfinite(Y).all(), c["name"]
         if c["family"] != "shifted":
             assert np.linalg.norm(Y, axis=-1).max() <= 1 + 1e-6, c["name"]
-        assert np.array_equal(ref.bits(ref.cov32(Y, idx, xl, yl)), ref.bits(c["cov32"])), c["name"]
+        assert np.array_equal(bits(ref.cov32(Y, idx, xl, yl)), bits(c["cov32"])), c["name"]
         _, lam, E, r2, _ = ref.frames64(Y, idx, xl, yl)                                          # the recorded eigh is an eigh of C64
         assert np.array_equal(r, r2) and np.abs(lam - lam64).max() <= 1e-14 * max(1.0, np.abs(lam64).max()), c["name"]
         assert np.abs(C64 @ E64 - E64 * lam64[..., None, :]).max() <= 1e-14 and np.abs(np.swapaxes(E64, -1, -2) @ E64 - np.eye(3)).max() <= 1e-14, c["name"]
@@ -142,7 +116,7 @@ def test_g29_is_self_consistent(g29_cases):
     assert {-1, c["m"], ref.INT32_MIN} <= set(np.unique(c["idx"][~valid])) and not valid[:, :, 0].any() and (np.diff(valid.astype(int), axis=-1) > 0).any()
     assert (c["ref64"][3][:, 0] == 0).all() and (c["ref64"][3][:, 1] == 1).all() and (c["ref64"][3][:, 2] == 2).all()
     c = by_name["ragged"]
-    nl, ml = ref.lengths_of(c["x_lengths"], c["b"], c["n"]), ref.lengths_of(c["y_lengths"], c["b"], c["m"])
+    nl, ml = lengths_of(c["x_lengths"], c["b"], c["n"]), lengths_of(c["y_lengths"], c["b"], c["m"])
     assert nl[0] == 0 and ml[1] == 0 and ml[2] == 1 and 1 < ml[3] < c["K"] and (c["ref64"][3][:2] == 0).all() and (c["ref64"][3][2, :nl[2]] == 1).all()
     assert (c["ref64"][3][3, :nl[3]] == ml[3]).all() and (c["ref64"][3][3, nl[3]:] == 0).all()
     assert np.array_equal(by_name["view_inside"]["Y"], by_name["view_outside"]["Y"]) and np.abs(by_name["view_inside"]["viewpoint"]).max() == 0
@@ -188,28 +162,18 @@ def check_power_of_two(label, c, base, run, e=20):
     for ee in (e, -e):
         cov, lam, nrm, frm = run(scaled_case(c, ee))
         f = np.float32(4.0 ** ee)
-        assert np.array_equal(ref.bits(cov), ref.bits(base[0] * f)), (label, c["name"], ee, "cov")
-        assert np.array_equal(ref.bits(lam), ref.bits(base[1] * f)), (label, c["name"], ee, "eigenvalues")
-        assert np.array_equal(ref.bits(nrm), ref.bits(base[2])) and np.array_equal(ref.bits(frm), ref.bits(base[3])), (label, c["name"], ee, "frames")
+        assert np.array_equal(bits(cov), bits(base[0] * f)), (label, c["name"], ee, "cov")
+        assert np.array_equal(bits(lam), bits(base[1] * f)), (label, c["name"], ee, "eigenvalues")
+        assert np.array_equal(bits(nrm), bits(base[2])) and np.array_equal(bits(frm), bits(base[3])), (label, c["name"], ee, "frames")
 
 
 # ---- the device functions on the host --------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def model(tmp_path_factory):
-    from oracle import kernel_model
-    cxx = kernel_model.clangxx()
-    if cxx is None:
-        pytest.skip("clang++ is not available (ext_vector_type)")
-    out = str(tmp_path_factory.mktemp("local_frames") / "liblocal_frames.so")
-    subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", out, SRC], check=True)
-    lib = ctypes.CDLL(out)
+    lib = build_host_model(tmp_path_factory, "local_frames", SRC)
     P, I64, I32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
     lib.model_local_frames.argtypes = [P, I64, P, P, P, P, P, P, P, P, I32, I64, I32, I32, I32]
     return lib
-
-
-def _p(a):
-    return ctypes.c_void_p(a.ctypes.data) if a is not None else None
 
 
 def host_run(model, c, sweeps=SWEEPS, want=(True, True, True, True)):
@@ -217,7 +181,7 @@ def host_run(model, c, sweeps=SWEEPS, want=(True, True, True, True)):
     Y, idx = np.ascontiguousarray(c["Y"], np.float32), np.ascontiguousarray(c["idx"], np.int32)
     xl, yl, view = (None if c[k] is None else np.ascontiguousarray(c[k], t) for k, t in (("x_lengths", np.int32), ("y_lengths", np.int32), ("viewpoint", np.float32)))
     outs = [np.full((b, n, w), np.nan, np.float32) if flag else None for flag, w in zip(want, (6, 3, 3, 9))]
-    assert model.model_local_frames(_p(Y), 3 * m, _p(idx), _p(xl), _p(yl), _p(view), *(_p(o) for o in outs), K, b, n, m, sweeps) == 0
+    assert model.model_local_frames(np_ptr(Y), 3 * m, np_ptr(idx), np_ptr(xl), np_ptr(yl), np_ptr(view), *(np_ptr(o) for o in outs), K, b, n, m, sweeps) == 0
     return tuple(outs)
 
 
@@ -230,9 +194,9 @@ def test_host_model_against_g29(model, g29_cases):
     assert all(worst[k] > ref.MEASURED[k] / 2 for k in worst), worst                             # the recorded figures are the measured ones, not slack
     c = next(c for c in g29_cases if c["name"] == "blob_257x300x16")
     a, b_ = host_run(model, c), host_run(model, c)
-    assert all(np.array_equal(ref.bits(u), ref.bits(v)) for u, v in zip(a, b_))
+    assert all(np.array_equal(bits(u), bits(v)) for u, v in zip(a, b_))
     only = host_run(model, c, want=(False, False, True, False))                                  # normals alone
-    assert only[0] is None and np.array_equal(ref.bits(only[2]), ref.bits(a[2]))
+    assert only[0] is None and np.array_equal(bits(only[2]), bits(a[2]))
 
 
 def test_host_model_sweep_count(model, g29_cases):

@@ -14,7 +14,6 @@ import ctypes
 import functools
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -22,6 +21,7 @@ import torch
 
 from conftest import ROOT
 import pointnet_ref as ref
+from support import boundary, build_host_model, np_ptr, on_own_thread
 
 NEW_SYMBOLS = {"so3_fps_f32": 7, "so3_ball_query_f32": 10}
 SRC = os.path.join(ROOT, "tests", "host_model", "pointnet.cpp")
@@ -132,34 +132,12 @@ def test_the_shape_lists_hold_what_they_promise():
 # ---- the boundary ---------------------------------------------------------------------------------------------------------
 def test_header_binding_table_and_library_agree(built_library):
     from poseestimation_amd import _lib
-    raw = open(os.path.join(ROOT, "include", "so3proj.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = set(re.findall(r"\b(so3_[a-z0-9_]+)\s*\(", text))
-    lib = ctypes.CDLL(built_library)
-    for name, nargs in NEW_SYMBOLS.items():
-        assert name in declared and name in _lib.SYMBOLS and hasattr(lib, name), name
-        args = re.search(r"\b%s\s*\(([^)]*)\)" % name, text).group(1).split(",")
-        assert len(args) == len(_lib.SYMBOLS[name][1]) == nargs, (name, args)
-    assert lib.so3_version() == _lib.ABI_VERSION == 210
+    raw, _ = boundary(built_library, NEW_SYMBOLS)
     assert int(re.search(r"#define SO3_FPS_MAX_N (\d+)", raw).group(1)) == _lib.FPS_MAX_N == ref.FPS_MAX_N >= 16384
 
 
 def test_argument_validation_without_gpu(built_library):
-    """On a thread of its own: so3_last_error is thread-local and never cleared, and other tests read it on the main thread."""
-    import threading
-    failure = []
-
-    def body():
-        try:
-            _argument_validation()
-        except BaseException as exc:               # noqa: BLE001 -- re-raised on the main thread
-            failure.append(exc)
-
-    t = threading.Thread(target=body)
-    t.start()
-    t.join()
-    if failure:
-        raise failure[0]
+    on_own_thread(_argument_validation)
 
 
 def _argument_validation():
@@ -258,13 +236,7 @@ def check_against_g22(g22_cases, run_fps, run_ball):
 # ---- the host model ---------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def model(tmp_path_factory):
-    from oracle import kernel_model
-    cxx = kernel_model.clangxx()
-    if cxx is None:
-        pytest.skip("clang++ is not available (ext_vector_type)")
-    out = str(tmp_path_factory.mktemp("pointnet") / "libpointnet.so")
-    subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", out, SRC], check=True)
-    lib = ctypes.CDLL(out)
+    lib = build_host_model(tmp_path_factory, "pointnet", SRC)
     lib.model_fps.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]
     lib.model_ball_query.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                      ctypes.c_int32, ctypes.c_int32]
@@ -273,16 +245,12 @@ def model(tmp_path_factory):
     return lib
 
 
-def _p(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
-
-
 def model_fps(lib, xyz, npoint, start):
     xyz = np.ascontiguousarray(xyz, np.float32)
     b, n, _ = xyz.shape
     first = np.ascontiguousarray(np.broadcast_to(np.asarray(start), (b,)), np.int32)
     out = np.full((b, npoint), -1, np.int32)
-    lib.model_fps(_p(xyz), _p(first), _p(out), b, n, npoint)
+    lib.model_fps(np_ptr(xyz), np_ptr(first), np_ptr(out), b, n, npoint)
     return out
 
 
@@ -292,7 +260,7 @@ def model_ball(lib, radius, nsample, xyz, centres, want_count=True):
     s = centres.shape[1]
     idx = np.full((b, s, min(nsample, n)), -1, np.int32)
     count = np.full((b, s), -1, np.int32) if want_count else None
-    lib.model_ball_query(_p(xyz), _p(centres), radius, nsample, _p(idx), None if count is None else _p(count), b, n, s)
+    lib.model_ball_query(np_ptr(xyz), np_ptr(centres), radius, nsample, np_ptr(idx), None if count is None else np_ptr(count), b, n, s)
     return idx, count
 
 

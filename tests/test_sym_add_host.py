@@ -17,14 +17,13 @@ tests/test_gpu_sym_add.py imports the bounds from here; DESIGN.md section 7h quo
 import ctypes
 import os
 import re
-import subprocess
-import threading
 
 import numpy as np
 import pytest
 import torch
 
 from conftest import ROOT
+from support import boundary, build_host_model, np_ptr, on_own_thread
 import sym_add_ref as ref
 
 #                                 measured on the host       bound (4 x)
@@ -45,34 +44,15 @@ STAT_KEY = {ref.L2: "stat_l2", ref.L1: "stat_l1", ref.MAX: "stat_max"}
 # ---- the boundary ---------------------------------------------------------------------------------------------------------
 def test_header_binding_table_and_library_agree(built_library):
     from poseestimation_amd import _lib
-    raw = open(os.path.join(ROOT, "include", "so3proj.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = set(re.findall(r"\b(so3_[a-z0-9_]+)\s*\(", text))
-    exported = subprocess.run(["nm", "-D", "--defined-only", built_library], capture_output=True, text=True, check=True).stdout
-    assert SYMBOL in declared and SYMBOL in _lib.SYMBOLS and re.search(r"\b%s\b" % SYMBOL, exported)
-    args = re.search(r"\b%s\s*\(([^)]*)\)" % SYMBOL, text).group(1).split(",")
-    assert len(args) == len(_lib.SYMBOLS[SYMBOL][1]) == 16
+    raw, _ = boundary(built_library, {SYMBOL: 16})
     for name, value in (("SO3_SYM_ADD_L2", _lib.SYM_ADD_L2), ("SO3_SYM_ADD_L1", _lib.SYM_ADD_L1), ("SO3_SYM_ADD_MAX", _lib.SYM_ADD_MAX)):
         assert int(re.search(r"#define\s+%s\s+(\d+)u" % name, raw).group(1)) == value
     assert (_lib.SYM_ADD_L2, _lib.SYM_ADD_L1, _lib.SYM_ADD_MAX) == (ref.L2, ref.L1, ref.MAX) and ref.L2 == 0
-    assert ctypes.CDLL(built_library).so3_version() == _lib.ABI_VERSION == 210
 
 
 def test_argument_validation_without_gpu(built_library):
-    """Each bad argument returns SO3_ERR_INVALID with a so3_last_error text before any launch; B == 0 is a no-op.  No device is touched.
-    On a thread of its own: so3_last_error() is per thread, and other tests expect the main thread's to be empty."""
-    errors = []
-
-    def run():
-        try:
-            check_arguments()
-        except BaseException as e:          # re-raised on the test's thread
-            errors.append(e)
-    worker = threading.Thread(target=run)
-    worker.start()
-    worker.join()
-    if errors:
-        raise errors[0]
+    """Each bad argument returns SO3_ERR_INVALID with a so3_last_error text before any launch; B == 0 is a no-op.  No device is touched."""
+    on_own_thread(check_arguments)
 
 
 def check_arguments():
@@ -166,21 +146,11 @@ def test_g26_is_self_consistent(g26_cases):
 # ---- the device functions on the host --------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def model(tmp_path_factory):
-    from oracle import kernel_model
-    cxx = kernel_model.clangxx()
-    if cxx is None:
-        pytest.skip("clang++ is not available (ext_vector_type)")
-    out = str(tmp_path_factory.mktemp("sym_add") / "libsym_add.so")
-    subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", out, SRC], check=True)
-    lib = ctypes.CDLL(out)
+    lib = build_host_model(tmp_path_factory, "sym_add", SRC)
     lib.model_sym_add.restype = ctypes.c_int
     lib.model_sym_add.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int32] * 2 + [ctypes.c_void_p] * 4 + [ctypes.c_float, ctypes.c_uint32,
                                                                                                             ctypes.c_int64, ctypes.c_int32]
     return lib
-
-
-def _p(a):
-    return ctypes.c_void_p(a.ctypes.data) if a is not None else None
 
 
 def host_run(model, c, grad_scale=1.0):
@@ -194,7 +164,7 @@ def host_run(model, c, grad_scale=1.0):
         dist, index = np.full(b, np.nan, np.float32), np.full(b, -2, np.int32)
         every = np.full((b, c["K"]), np.nan, np.float32)
         grad = None if mode == ref.MAX else np.full((b, 4, 4), np.nan, np.float32)
-        assert model.model_sym_add(_p(tg), _p(tp), _p(pts), _p(S), _p(cls), c["C"], c["K"], _p(dist), _p(index), _p(every), _p(grad),
+        assert model.model_sym_add(np_ptr(tg), np_ptr(tp), np_ptr(pts), np_ptr(S), np_ptr(cls), c["C"], c["K"], np_ptr(dist), np_ptr(index), np_ptr(every), np_ptr(grad),
                                    grad_scale, mode, b, n) == 0
         out[mode] = {"dist": dist, "index": index, "grad": grad, "all": every}
     return out
@@ -282,15 +252,12 @@ def test_host_model_exact_cases(model, g26_cases):
     assert {"exact_c4", "identical_points"} <= seen
 
 
-def test_host_model_with_the_trivial_table_is_plain_add(model, g26_cases):
+def test_host_model_with_the_trivial_table_is_plain_add(model, g26_cases, tmp_path_factory):
     """Table {I}: compute_ADD_loss / compute_ADD_L1_loss's values and gradients within the bounds (not bit for bit: the sweeps' totals
     are added after the butterfly here, k_add_l1 adds per lane across sweeps).  ADD through the host model of k_add_l1<.., L2>
     (tests/host_model/add_metrics.cpp), ADD-L1 through the float64 definition."""
-    from oracle import kernel_model
     import test_add_metrics_host as add_host
-    out = os.path.join(os.path.dirname(model._name), "libadd_metrics.so")
-    subprocess.run([kernel_model.clangxx(), "-x", "c++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", out, add_host.SRC], check=True)
-    add_model = ctypes.CDLL(out)
+    add_model = build_host_model(tmp_path_factory, "add_metrics", add_host.SRC)
     eye = np.eye(3, dtype=np.float32).reshape(1, 1, 3, 3)
     for c in g26_cases:
         one = dict(c, S=eye, C=1, K=1, cls=None)
@@ -299,7 +266,7 @@ def test_host_model_with_the_trivial_table_is_plain_add(model, g26_cases):
         f = lambda a: np.ascontiguousarray(a, dtype=np.float32)
         tg, tp, pts = f(c["tgt"]), f(c["tpred"]), f(c["pts"])
         add, g_add = np.full(b, np.nan, np.float32), np.full((b, 4, 4), np.nan, np.float32)
-        add_model.model_add_l2(_p(tg), _p(tp), _p(pts), _p(add), _p(g_add), ctypes.c_float(1.0), ctypes.c_int64(b), ctypes.c_int32(n))
+        add_model.model_add_l2(np_ptr(tg), np_ptr(tp), np_ptr(pts), np_ptr(add), np_ptr(g_add), ctypes.c_float(1.0), ctypes.c_int64(b), ctypes.c_int32(n))
         assert np.abs(got[ref.L2]["dist"].astype(np.float64) - add).max() <= L2_TOL and np.abs(got[ref.L2]["grad"].astype(np.float64) - g_add).max() <= L2_GRAD_TOL
         assert (got[ref.L2]["index"] == 0).all() and (got[ref.L1]["index"] == 0).all()
         d = ref.residuals(tg, tp, pts, np.broadcast_to(np.eye(3), (b, 1, 3, 3)))[:, 0]

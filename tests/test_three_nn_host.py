@@ -19,13 +19,13 @@ import ctypes
 import functools
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from conftest import ROOT
+from support import bits, boundary, build_host_model, np_ptr, on_own_thread
 import three_nn_ref as ref
 
 NEW_SYMBOLS = {"so3_three_nn_f32": 9, "so3_three_interpolate_f32": 10, "so3_three_interpolate_bwd_f32": 10}
@@ -158,34 +158,12 @@ def test_the_shape_lists_hold_what_they_promise():
 # ---- the boundary ---------------------------------------------------------------------------------------------------------
 def test_header_binding_table_and_library_agree(built_library):
     from poseestimation_amd import _lib
-    raw = open(os.path.join(ROOT, "include", "so3proj.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = set(re.findall(r"\b(so3_[a-z0-9_]+)\s*\(", text))
-    lib = ctypes.CDLL(built_library)
-    for name, nargs in NEW_SYMBOLS.items():
-        assert name in declared and name in _lib.SYMBOLS and hasattr(lib, name), name
-        args = re.search(r"\b%s\s*\(([^)]*)\)" % name, text).group(1).split(",")
-        assert len(args) == len(_lib.SYMBOLS[name][1]) == nargs, (name, args)
-    assert lib.so3_version() == _lib.ABI_VERSION == 210
+    raw, _ = boundary(built_library, NEW_SYMBOLS)
     assert int(re.search(r"#define SO3_THREE_MAX_D (\d+)", raw).group(1)) == _lib.THREE_MAX_D == 65536
 
 
 def test_argument_validation_without_gpu(built_library):
-    """On a thread of its own: so3_last_error is thread-local and never cleared, and other tests read it on the main thread."""
-    import threading
-    failure = []
-
-    def body():
-        try:
-            _argument_validation()
-        except BaseException as exc:               # noqa: BLE001 -- re-raised on the main thread
-            failure.append(exc)
-
-    t = threading.Thread(target=body)
-    t.start()
-    t.join()
-    if failure:
-        raise failure[0]
+    on_own_thread(_argument_validation)
 
 
 def _argument_validation():
@@ -267,10 +245,6 @@ def check_nn(name, run_nn, xyz1, xyz2, want=None):
     return d3, idx, w
 
 
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 def expected32(c):
     """(out, grad_feat) of an interpolation case in the DEFINED float32 order, channel-last; the other layout is their transpose (the
     arithmetic of an element does not depend on the layout)."""
@@ -339,13 +313,7 @@ def check_against_g24(g24_cases, run_nn, run_fwd, run_bwd):
 # ---- the host model ---------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def model(tmp_path_factory):
-    from oracle import kernel_model
-    cxx = kernel_model.clangxx()
-    if cxx is None:
-        pytest.skip("clang++ is not available (ext_vector_type)")
-    out = str(tmp_path_factory.mktemp("three_nn") / "libthree_nn.so")
-    subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", out, SRC], check=True)
-    lib = ctypes.CDLL(out)
+    lib = build_host_model(tmp_path_factory, "three_nn", SRC)
     lib.model_three_nn.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
     lib.model_three_interpolate.argtypes = lib.model_three_interpolate_bwd.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int32, ctypes.c_int64] + [ctypes.c_int32] * 3
     lib.model_three_nn_waves_per_point.argtypes = [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]
@@ -354,16 +322,12 @@ def model(tmp_path_factory):
     return lib
 
 
-def _p(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
-
-
 def model_nn(lib, xyz1, xyz2, want_weight, slices=1):
     xyz1, xyz2 = np.ascontiguousarray(xyz1, np.float32), np.ascontiguousarray(xyz2, np.float32)
     b, n, s = xyz1.shape[0], xyz1.shape[1], xyz2.shape[1]
     d3, idx = np.full((b, n, 3), np.nan, np.float32), np.full((b, n, 3), -1, np.int32)
     w = np.full((b, n, 3), np.nan, np.float32) if want_weight else None
-    lib.model_three_nn(_p(xyz1), _p(xyz2), _p(d3), _p(idx), None if w is None else _p(w), b, n, s, slices)
+    lib.model_three_nn(np_ptr(xyz1), np_ptr(xyz2), np_ptr(d3), np_ptr(idx), None if w is None else np_ptr(w), b, n, s, slices)
     return d3, idx, w
 
 
@@ -372,7 +336,7 @@ def model_fwd(lib, feat, idx, weight, channels_first):
     b, n = idx.shape[:2]
     d, s = (feat.shape[1], feat.shape[2]) if channels_first else (feat.shape[2], feat.shape[1])
     out = np.full((b, d, n) if channels_first else (b, n, d), np.nan, np.float32)
-    lib.model_three_interpolate(_p(feat), _p(idx), _p(weight), _p(out), int(channels_first), b, n, s, d)
+    lib.model_three_interpolate(np_ptr(feat), np_ptr(idx), np_ptr(weight), np_ptr(out), int(channels_first), b, n, s, d)
     return out
 
 
@@ -381,7 +345,7 @@ def model_bwd(lib, grad, idx, weight, s, channels_first):
     b, n = idx.shape[:2]
     d = grad.shape[1] if channels_first else grad.shape[2]
     out = np.full((b, d, s) if channels_first else (b, s, d), np.nan, np.float32)
-    lib.model_three_interpolate_bwd(_p(grad), _p(idx), _p(weight), _p(out), int(channels_first), b, n, s, d)
+    lib.model_three_interpolate_bwd(np_ptr(grad), np_ptr(idx), np_ptr(weight), np_ptr(out), int(channels_first), b, n, s, d)
     return out
 
 
