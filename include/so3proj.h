@@ -409,7 +409,10 @@ int so3_expmap_bwd_f32(const float *X, const float *G, float *dX, int64_t B, voi
  *                  e2 = atan2(clamp(-r1, -1, 1), |(r2, r0)|), clamped to the float32 just below pi/2: asin(-r1) for a
  *                  rotation, taken through the two entries that still hold cos(e2) next to gimbal lock (a float32 r1
  *                  rounds to 1 below cos(e2) = 3.5e-4, and asin(-r1) alone then misses R by up to that much).
- *                  At exact gimbal lock e1 = 0.  |e2| <= pi/2.
+ *                  GIMBAL LOCK is r0^2 + r2^2, formed in float32, below float32's smallest normal 2^-126 (that is
+ *                  |(r2, r0)| below about 1.1e-19, not zero alone: the hardware reciprocal square root reads a subnormal
+ *                  as 0).  At gimbal lock cos(e2) = 0 and (s3, c3) = (0, 1): e1 = 0, |e2| is the clamp, e0 =
+ *                  atan2(-r5, r8), and the gradient is the floor's.  A NaN row is not at lock: it stays NaN.  |e2| <= pi/2.
  *   relative_log   V out B*3 = log(R1^T R2) in one launch; |v| is the geodesic angle between R1 and R2.
  * GRADIENT CONVENTION.  Every backward returns the TANGENT-SPACE gradient at R: for an inverse map f and the incoming
  * gradient g (G in, shaped like the forward's output) let w = (d f(R exp(hat delta)) / d delta)^T g; then

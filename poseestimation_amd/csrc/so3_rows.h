@@ -1931,6 +1931,7 @@ struct OpSe3UpdateBwd : OpBase {
 // along tangent directions, so chaining through a head is exact.
 constexpr float kEulerMaxMiddle = 1.57079625f;   // the float32 below pi/2 (float32(pi/2) lies above it): |e2| <= pi/2 in any arithmetic
 constexpr float kEulerMinCos = 1e-6f;            // floor of cos(e2) in the Euler gradient's 1 / c2: finite at gimbal lock
+constexpr float kEulerMinH = 0x1p-126f;          // r0^2 + r2^2 below float32's smallest normal is gimbal lock (v_rsq_f32 reads a subnormal as 0)
 
 // dR = 1/2 R hat(w): row i of R crossed with w
 template <class T> __device__ __forceinline__ void tangent_gradient(const T (&r)[9], V3<T> w, T (&d)[9]) {
@@ -2066,11 +2067,14 @@ template <bool BWD> struct OpLogMap : OpBase {
 };
 
 // R (B,9) -> (e0, e1, e2) (B,3) in OpEuler's convention (e2 the middle angle, R = X(e0) Z(e2) Y(e1)):
-//     e2 = asin(clamp(-r1, -1, 1)),  (s3, c3) = (r2, r0) / |(r2, r0)| = sincos(e1)  ((0, 1) at exact gimbal lock: e1 = 0),
+//     e2 = asin(clamp(-r1, -1, 1)),  (s3, c3) = (r2, r0) / |(r2, r0)| = sincos(e1)  ((0, 1) at gimbal lock: e1 = 0),
 //     e0 = atan2(s3 r3 - c3 r5, c3 r8 - s3 r6)      -- well conditioned at gimbal lock, where atan2(r7, r4) is 0 / 0.
 // The arc sine is taken as atan2(s2, c2) with c2 = |(r2, r0)|, which is sqrt(1 - r1^2) for a rotation: next to gimbal lock a float32
 // r1 no longer holds c2 (r1 = 1 - c2^2 / 2 rounds to 1 below c2 = 3.5e-4) and asin(-r1) alone misses R by up to that much;
 // r0 and r2 still carry it to full relative precision.
+// GIMBAL LOCK is h = r0^2 + r2^2 below float32's smallest normal (kEulerMinH), not h = 0 alone: v_rsq_f32 and v_sqrt_f32 read a
+// subnormal h as 0, so for 0 < |(r2, r0)| < 1.1e-19 rsq(h) was +inf and the row came out NaN, forward and backward (libm's 1 / sqrt
+// on the host did not show it).  There c2 = 0 and (s3, c3) = (0, 1), as at h = 0.  The comparison is false for a NaN: a NaN row stays NaN.
 // backward: in1 = g (B,3), out0 = dR (B,9).  With p = (delta_x c3 + delta_z s3) / c2:
 //     de0 = p,  de1 = delta_y + s2 p,  de2 = c3 delta_z - s3 delta_x;       c2 is clamped from below at kEulerMinCos.
 template <bool BWD> struct OpMatToEuler : OpBase {
@@ -2083,18 +2087,18 @@ template <bool BWD> struct OpMatToEuler : OpBase {
         const T one = R::splat(1.f), zero = R::splat(0.f);
         const T s2 = R::clamp(-r[1], R::splat(-1.f), one);
         const T h = R::fma(r[2], r[2], r[0] * r[0]);
-        const typename R::mask lock = R::le(h, zero);
+        const typename R::mask lock = R::gt(R::splat(kEulerMinH), h);
         const T ih = R::rsq(h);
         const T c3 = R::sel(lock, one, r[0] * ih), s3 = R::sel(lock, zero, r[2] * ih);
         if constexpr (!BWD) {
-            const T c2 = R::sqrt(h);
+            const T c2 = R::sel(lock, zero, R::sqrt(h));
             rows.o0[0] = R::atan2(R::fma(s3, r[3], -(c3 * r[5])), R::fma(c3, r[8], -(s3 * r[6])));
             rows.o0[1] = R::atan2(s3, c3);
             const T e2 = R::atan2(s2, c2), top = R::splat(kEulerMaxMiddle);                 // (selects, not med3: a NaN stays a NaN)
             rows.o0[2] = R::sel(R::gt(e2, top), top, R::sel(R::gt(-top, e2), -top, e2));
         } else {
             const T (&g)[3] = rows.b;
-            const T ic = R::rcp(R::max(h * ih, R::splat(kEulerMinCos)));          // (h rsq(h) = sqrt(h); NaN at h = 0 falls to the floor)
+            const T ic = R::rcp(R::max(R::sel(lock, zero, h * ih), R::splat(kEulerMinCos)));          // (h rsq(h) = sqrt(h); the floor at lock)
             const T p = R::fma(g[1], s2, g[0]) * ic;
             const V3<T> w = mk<T>(R::fma(c3, p, -(s3 * g[2])), g[1], R::fma(s3, p, c3 * g[2]));
             tangent_gradient<T>(r, w, rows.o0);

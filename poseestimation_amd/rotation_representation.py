@@ -857,7 +857,8 @@ def matrix_to_euler(R: torch.Tensor) -> torch.Tensor:
     (e[:,2] is the middle angle, |e[:,2]| <= pi/2): (s3, c3) = (r2, r0) / |(r2, r0)| = sincos(e1), e0 = atan2(s3 r3 - c3 r5, c3 r8 - s3 r6),
     which keeps forward(inverse(R)) within rounding of R at gimbal lock, and e2 = atan2(clamp(-r1, -1, 1), |(r2, r0)|), clamped to the
     float32 just below pi/2 -- asin(-r1) for a rotation, computed from the two entries that still hold cos(e2) next to gimbal lock, where
-    a float32 r1 has rounded to +-1.  At exact gimbal lock e1 = 0.
+    a float32 r1 has rounded to +-1.  At gimbal lock -- r0^2 + r2^2 below float32's smallest normal, |(r2, r0)| below about 1.1e-19 --
+    cos(e2) counts as 0 and e1 = 0.
     Differentiable (tangent-space gradient); the Jacobian carries 1 / cos(e2), and cos(e2) is clamped from below at
     EULER_GIMBAL_COS_FLOOR, so the gradient is finite everywhere."""
     return _MatToEuler.apply(R)

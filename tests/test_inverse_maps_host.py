@@ -41,6 +41,34 @@ NORM_TOL = 4 * 2.0**-23                              # | |q| - 1 | <= 4 ulp
 EULER_GRAD_GIMBAL_BAND = 0.05
 assert QUAT_VALUE_TOL < 1e-6 and max(QUAT_CLOSURE_TOL, LOG_CLOSURE_TOL, EULER_CLOSURE_TOL) < 4e-6
 
+# ROW BY ROW, NO EXEMPTIONS (test_every_row_within_its_family_bound, tests/test_gpu_inverse_maps_rows.py).  HOST_ROWS[check][family] is
+# the largest figure of the float32 host model (either instantiation) on that family of inverse_maps_ref.rows() -- G18's eleven families
+# and the five edge families -- against the float64 definition evaluated on the SAME float32 rows (ref.quat64 / ref.log64 / ref.rel64,
+# ref.euler_def64 / ref.euler_grad_def64 with the floor 1e-6; gradients of the others by float64 autograd, projected to the tangent
+# space).  The gradient figures are the largest over the table's g and ref.G_DRAWS further seeded draws of g (ref.redrawn; this
+# file's convention above: the fixture's g and a random g): a family's largest gradient error depends on g as much as on the row, and under
+# the table's g alone the three rows of theta_pi_coordinate_axis gave 2.85e-8 for dR1 of the relative log where other draws give 1.07e-7.
+# ROW_TOL is 4 x the host figure, on the host and on the GPU alike, for the reason given above.  Figures
+# (ref.row_error): values max |difference| per row (e0, e1 modulo 2 pi); the log map on theta_small and log_small relative,
+# max |difference| / max |answer|, and exactly 0 where the answer is 0; gradients max |difference| / max(1, max |answer|).  A family the
+# host model gets exactly (the identity; half turns about a coordinate axis) has the bound 0.  The relative maps' rows ON the cut
+# theta = pi are held to the nearer of the two branches' float64 answers (ref.on_cut says why no exemption-free reference exists there).
+ROW_FAMILIES = ["random", "theta_small", "theta_near_pi", "theta_zero", "theta_pi_random_axis", "theta_pi_coordinate_axis", "axis_aligned", "gimbal_near",
+                "gimbal_exact", "tie_diagonal", "tie_half_turn", "euler_floor", "euler_underflow", "log_small", "rel_residual", "rel_cut"]
+HOST_ROWS = {check: dict(zip(ROW_FAMILIES, figures)) for check, figures in {
+    #             random    th_small  near_pi   zero      pi_rand   pi_coord  axis_al   gimb_near gimb_ex   tie_diag  tie_half  e_floor   e_underfl log_small rel_resid rel_cut
+    "quat":       [1.41e-7, 1.18e-7,  1.17e-7,  0,        9.36e-8,  0,        1.21e-8,  9.61e-8,  6.64e-8,  1.02e-7,  9.89e-8,  9.43e-8,  7.14e-8,  1.02e-7,  1.02e-7,  1.32e-7],
+    "log":        [5.21e-7, 1.56e-7,  6.49e-7,  0,        2.89e-7,  8.74e-8,  1.63e-7,  3.55e-7,  2.89e-7,  4.29e-7,  3.30e-7,  3.49e-7,  3.04e-7,  1.08e-7,  4.58e-7,  3.67e-7],
+    "euler":      [2.77e-7, 1.38e-10, 2.50e-7,  0,        2.20e-7,  8.74e-8,  8.74e-8,  2.44e-7,  2.02e-7,  2.34e-7,  2.45e-7,  2.27e-7,  2.53e-7,  1.21e-9,  2.77e-7,  2.28e-7],
+    "rel":        [5.55e-7, 4.75e-7,  5.98e-7,  2.89e-7,  5.73e-7,  1.04e-7,  3.72e-7,  5.92e-7,  3.94e-7,  4.23e-7,  4.00e-7,  5.15e-7,  3.83e-7,  4.16e-7,  2.15e-8,  6.01e-7],
+    "quat_grad":  [1.61e-7, 1.32e-7,  1.26e-7,  0,        1.14e-7,  0,        4.47e-8,  1.19e-7,  1.14e-7,  1.17e-7,  1.34e-7,  1.29e-7,  1.27e-7,  1.17e-7,  1.73e-7,  1.66e-7],
+    "log_grad":   [3.31e-7, 1.50e-7,  4.30e-7,  0,        3.78e-7,  1.21e-7,  1.72e-7,  2.55e-7,  2.97e-7,  2.35e-7,  3.11e-7,  2.72e-7,  2.45e-7,  1.74e-7,  3.02e-7,  2.78e-7],
+    "euler_grad": [2.72e-7, 1.87e-7,  2.36e-7,  0,        2.14e-7,  0,        1.12e-7,  2.42e-7,  2.34e-7,  1.84e-7,  2.14e-7,  2.29e-7,  1.60e-7,  2.28e-7,  1.93e-7,  2.57e-7],
+    "rel_grad1":  [3.29e-7, 2.76e-7,  3.01e-7,  2.28e-7,  2.69e-7,  1.07e-7,  3.22e-7,  3.01e-7,  2.29e-7,  2.59e-7,  2.69e-7,  2.89e-7,  2.60e-7,  3.59e-7,  1.55e-7,  3.75e-7],
+    "rel_grad2":  [3.74e-7, 3.31e-7,  3.12e-7,  2.07e-7,  2.74e-7,  1.85e-7,  2.54e-7,  2.96e-7,  2.44e-7,  2.36e-7,  1.98e-7,  2.62e-7,  2.30e-7,  2.43e-7,  1.22e-7,  3.35e-7],
+}.items()}
+ROW_TOL = {check: {family: 4 * figure for family, figure in per_family.items()} for check, per_family in HOST_ROWS.items()}
+
 NEW_SYMBOLS = ["so3_mat_to_quat_fwd_f32", "so3_mat_to_quat_bwd_f32", "so3_logmap_fwd_f32", "so3_logmap_bwd_f32",
                "so3_mat_to_euler_fwd_f32", "so3_mat_to_euler_bwd_f32", "so3_relative_log_fwd_f32", "so3_relative_log_bwd_f32"]
 SRC = os.path.join(ROOT, "tests", "host_model", "inverse_maps.cpp")
@@ -155,6 +183,17 @@ def run_rel(model, r1, r2, packed, g=None, want1=True, want2=True):
 
 
 MAPS = [("mat_to_quat", 4), ("logmap", 3), ("mat_to_euler", 3)]
+
+
+def run_all(model, t, packed):
+    """Every map, forward and backward, on the table of inverse_maps_ref.rows() -> {check: float32 array}, keyed as ref.CHECKS."""
+    g4, g3 = t["g"], np.ascontiguousarray(t["g"][:, :3])
+    out = {"quat": run_fwd(model, "mat_to_quat", t["r"], 4, packed), "log": run_fwd(model, "logmap", t["r"], 3, packed),
+           "euler": run_fwd(model, "mat_to_euler", t["r"], 3, packed), "rel": run_rel(model, t["r"], t["r2"], packed),
+           "quat_grad": run_bwd(model, "mat_to_quat", t["r"], g4, packed), "log_grad": run_bwd(model, "logmap", t["r"], g3, packed),
+           "euler_grad": run_bwd(model, "mat_to_euler", t["r"], g3, packed)}
+    out["rel_grad1"], out["rel_grad2"] = run_rel(model, t["r"], t["r2"], packed, g3)
+    return out
 
 
 def test_single_and_packed_instantiations_agree_bit_for_bit(model, g18):
@@ -273,3 +312,154 @@ def test_against_scipy(model, g18):
     ex = ref.exemptions(d)
     assert ref.up_to_sign_error(run_fwd(model, "mat_to_quat", d["r"], 4, 1), q, ex["quat"]).max() <= QUAT_VALUE_TOL
     assert ref.up_to_sign_error(run_fwd(model, "logmap", d["r"], 3, 1), rot.as_rotvec(), ex["rotvec"]).max() <= LOG_VALUE_TOL
+
+
+# ---- row by row against the float64 definition: G18 and the edge families, nothing left out ----------------------------------------
+@pytest.fixture(scope="module")
+def table():
+    return ref.rows()
+
+
+def test_edge_rows_are_the_families_they_claim(table):
+    t, e = table, ref.edge_rows()
+    assert t["names"] == ROW_FAMILIES and len(t["r"]) == len(ref.g18()["r"]) + len(e["r"])
+    for k, name in enumerate(ref.EDGE_FAMILIES):
+        assert 200 <= (e["family"] == k).sum() <= 500, name
+    r = t["r"].astype(np.float64).reshape(-1, 3, 3)
+    assert np.abs(r.transpose(0, 2, 1) @ r - np.eye(3)).max() < 4e-7 and np.abs(np.linalg.det(r) - 1).max() < 4e-7      # float32-rounded rotations
+    r2 = t["r2"].astype(np.float64).reshape(-1, 3, 3)
+    assert np.abs(r2.transpose(0, 2, 1) @ r2 - np.eye(3)).max() < 4e-7
+    fam = lambda name: t["fam"] == t["names"].index(name)                                                         # noqa: E731
+    c2 = np.hypot(r[:, 0, 0], r[:, 0, 2])
+    floor = c2[fam("euler_floor")]
+    assert ((floor > 0) & (floor < ref.EULER_MIN_COS)).sum() >= 100 and (floor > ref.EULER_MIN_COS).sum() >= 100 and (floor == 0).sum() >= 8
+    assert ((floor > 0.98e-6) & (floor < 1e-6)).any() and ((floor > 1e-6) & (floor < 1.02e-6)).any()                     # next to the floor, both sides
+    f = r[fam("euler_floor")]
+    assert ((f[:, 0, 0] == 0) & (f[:, 0, 2] != 0)).any() and ((f[:, 0, 2] == 0) & (f[:, 0, 0] != 0)).any() and (f[:, 0, 1] > 0).any() and (f[:, 0, 1] < 0).any()
+    h = ref._h32(torch.as_tensor(t["r"].astype(np.float64)))
+    under = h[fam("euler_underflow")]
+    assert ((under > 0) & (under < ref.FLT_MIN)).sum() >= 100 and (under == 0).sum() >= 40                              # subnormal h, and h = 0 off exact lock
+    u = np.abs(t["r"][fam("euler_underflow")][:, [0, 2]])
+    assert ((u > 0) & (u < ref.FLT_MIN)).any(1).sum() >= 20                                                            # r0 or r2 itself subnormal
+    assert not ((h[~fam("euler_underflow")] > 0) & (h[~fam("euler_underflow")] < 1e-33)).any()
+    small = np.linalg.norm(t["want"]["log"][fam("log_small")], axis=1)
+    for theta in ref.LOG_SMALL_THETAS:
+        assert (np.abs(small / theta - 1) < 1e-6).sum() == 30, theta
+    res = np.linalg.norm(t["want"]["rel"][fam("rel_residual")], axis=1)
+    for delta in ref.REL_RESIDUALS:
+        assert (np.abs(res - delta) <= 2e-7).sum() >= 50, delta                                                       # (the rounding of R2 moves it by ~1e-7)
+    assert (res == 0).sum() == 50                                                                                      # R2 = R1: R1^T R1 is exactly symmetric
+    gap = np.pi - np.linalg.norm(t["want"]["rel"][fam("rel_cut")], axis=1)
+    assert (gap < ref.CUT_BAND).sum() == 120 and ((gap > 5e-6) & (gap < 2e-5)).sum() == 60 and ((gap > 5e-4) & (gap < 2e-3)).sum() == 60
+    on = ref.on_cut(t)
+    far = np.pi - np.linalg.norm(t["want"]["rel"], axis=1)
+    assert not ((far >= ref.CUT_BAND) & (far < 5e-6)).any() and on.sum() < 0.04 * len(on)                                 # nothing next to the band's edge
+
+
+def test_euler_definition_equals_autograd_off_the_floor(table):
+    """euler_grad_def64 is the tangent-projected float64 autograd gradient of euler_def64 off the floor (c2 > 1e-4), and of the plain
+    asin / atan2 definition euler64 where that is defined.  ON the manifold -- the rows' nearest float64 rotations -- they agree to
+    float64's own conditioning (1 / c2 for the first; asin(-r1) loses 1 / c2^2 for the second).  On the float32-ROUNDED rows, which
+    are off the manifold by 2^-24 per entry, the closed form and the projected autograd gradient differ by that over c2; outside the old
+    tests' 0.05 rad band the two definitions' autograd gradients differ from the closed form by 6.4e-7."""
+    t = table
+    r = t["r"].astype(np.float64).reshape(-1, 3, 3)
+    u, _, vt = np.linalg.svd(r)
+    g3 = t["g"][:, :3].astype(np.float64)
+    for label, mats in (("on the manifold", u @ vt), ("rounded rows", r)):
+        m = torch.as_tensor(mats)
+        c2 = ref._euler_parts(m)[1].numpy()
+        off = c2 > 1e-4
+        assert off.sum() > 4000
+        want = ref.euler_grad_def64(m, torch.as_tensor(g3)).numpy()
+        (through_def,) = ref.autograd_tangent(ref.euler_def64, g3, mats)
+        (through_asin,) = ref.autograd_tangent(ref.euler64, g3, mats)
+        e_def, e_asin = ref.rel_grad_error(through_def, want), ref.rel_grad_error(through_asin, want)
+        assert np.isfinite(e_def[off]).all() and np.isfinite(e_asin[c2 > 0.05]).all()
+        defined = off & np.isfinite(e_asin)
+        print("%-16s def64 vs autograd(def64) %.2e, vs autograd(euler64) %.2e (outside the band %.2e)" % (label, e_def[off].max(), e_asin[defined].max(), e_asin[c2 > 0.05].max()))
+        if label == "on the manifold":
+            assert (e_def[off] <= 64 * 2.0**-53 / c2[off]).all()
+            assert (e_asin[defined] <= 64 * 2.0**-53 / c2[defined] ** 2).all() and defined.sum() > 4000
+        else:
+            assert (e_def[off] <= 4 * 2.0**-24 / c2[off]).all()
+            assert e_asin[c2 > 0.05].max() <= 1e-6
+    # the closed form of the relative log's gradients (the reference for the OTHER branch on the cut) is autograd's at v
+    m, m2 = torch.as_tensor(u @ vt), torch.as_tensor(t["r2"].astype(np.float64).reshape(-1, 3, 3))
+    u2, _, vt2 = np.linalg.svd(m2.numpy())
+    m2 = torch.as_tensor(u2 @ vt2)
+    off_cut = torch.pi - ref.rel64(m, m2).norm(dim=1).numpy() > 1e-3
+    for closed, auto in zip(ref.rel_grad_def64(m, m2, torch.as_tensor(g3)), ref.autograd_tangent_t(ref.rel64, torch.as_tensor(g3), m, m2)):
+        assert ref.rel_grad_error(closed.numpy()[off_cut], auto.numpy()[off_cut]).max() < 1e-9
+
+
+@pytest.mark.parametrize("packed", [0, 1])
+def test_every_row_within_its_family_bound(model, table, packed):
+    """Every map, forward and backward, on every row of G18 and of the edge families: no row left out, none compared up to sign or by
+    closure, each held to its own family's bound; the gradients under the table's g and under every further draw of g."""
+    t = table
+    got = run_all(model, t, packed)
+    failures = []
+    for draw in range(ref.G_DRAWS + 1):
+        td = ref.redrawn(draw)
+        gd = got if draw == 0 else run_all(model, td, packed)
+        for check in ref.CHECKS if draw == 0 else [c for c in ref.CHECKS if "_grad" in c]:
+            assert np.isfinite(gd[check]).all(), check
+            fig, bound = ref.row_error(check, gd[check], td), ref.row_bound(check, ROW_TOL, td)
+            for k, name in enumerate(t["names"]):
+                rows = t["fam"] == k
+                print("%-10s %-26s draw %d %.3e  (host %.3e, bound %.3e)" % (check, name, draw, fig[rows].max(), HOST_ROWS[check][name], ROW_TOL[check][name]))
+            if not (fig <= bound).all():
+                worst = int(np.argmax(fig / np.maximum(bound, 1e-300)))
+                failures.append((check, draw, t["names"][t["fam"][worst]], worst, fig[worst], bound[worst], int((fig > bound).sum())))
+    assert not failures, failures
+    # an answer that is exactly 0 comes out exactly 0: the identity's rotation vector, log(R1^T R1)
+    for check in ("log", "rel"):
+        zero = (t["want"][check] == 0).all(1)
+        assert zero.sum() >= (8 if check == "log" else 50) and (got[check][zero] == 0).all(), check
+    cut = ref.on_cut(t)
+    print("rows on the cut: %d; on the float64 answer's other branch: value %d, dR1 %d, dR2 %d" % (
+        cut.sum(), *(ref.cut_branch(c, got[c], t).sum() for c in ("rel", "rel_grad1", "rel_grad2"))))
+
+
+@pytest.mark.parametrize("packed", [0, 1])
+def test_euler_underflow_is_finite_and_the_definition(model, table, packed):
+    """h = r0^2 + r2^2 below float32's smallest normal IS gimbal lock (include/so3proj.h): e1 = 0 exactly, |e2| the clamp, e0 from
+    (-r5, r8), the gradient the floor's with (s3, c3) = (0, 1) -- finite, and the float64 definition's to the family's bound."""
+    t = table
+    rows = np.flatnonzero(t["fam"] == t["names"].index("euler_underflow"))
+    r, g3 = t["r"][rows], np.ascontiguousarray(t["g"][rows, :3])
+    e, d = run_fwd(model, "mat_to_euler", r, 3, packed), run_bwd(model, "mat_to_euler", r, g3, packed)
+    assert np.isfinite(e).all() and np.isfinite(d).all()
+    lock = ref._h32(torch.as_tensor(r.astype(np.float64))) < ref.FLT_MIN
+    assert lock.sum() >= 140 and (~lock).sum() >= 8
+    assert (e[lock, 1] == 0).all() and (np.abs(e[lock, 2]) == np.float32(ref.EULER_MAX_MIDDLE)).all()
+    assert (ref.row_error("euler", e, t, rows) <= ref.row_bound("euler", ROW_TOL, t, rows)).all()
+    assert (ref.row_error("euler_grad", d, t, rows) <= ref.row_bound("euler_grad", ROW_TOL, t, rows)).all()
+
+
+@pytest.mark.parametrize("packed", [0, 1])
+def test_one_gradient_alone_row_by_row_on_the_cut_too(model, table, packed):
+    """so3_relative_log_bwd with one output runs the swapped pair under -g.  dR2 alone is the same bits.  dR1 alone is the same bits
+    off the cut; a row within 1e-3 of theta = pi (the old test leaves those out) must be within REL_GRAD_TOL of the both-gradients dR1
+    or of the float64 gradient on the OTHER branch than the one the both-gradients dR1 took (at -v: log(D^T) = -log(D) fails only at
+    theta = pi itself).  Which one is counted; no row is neither."""
+    t = table
+    g3 = np.ascontiguousarray(t["g"][:, :3])
+    d1, d2 = run_rel(model, t["r"], t["r2"], packed, g3)
+    o1, _ = run_rel(model, t["r"], t["r2"], packed, g3, want2=False)
+    _, o2 = run_rel(model, t["r"], t["r2"], packed, g3, want1=False)
+    assert np.array_equal(o2, d2)
+    cut = np.pi - np.linalg.norm(t["want"]["rel"], axis=1) <= 1e-3
+    assert cut.sum() >= 200 and np.array_equal(o1[~cut], d1[~cut])
+    plus, other = t["want"]["rel_grad1"][cut], t["want"]["rel_grad1_other"][cut]
+    d1_on_other = ref.rel_grad_error(d1[cut], other) < ref.rel_grad_error(d1[cut], plus)
+    across = np.where(d1_on_other[:, None], plus, other)                           # the float64 gradient on the branch d1 did NOT take
+    same = ref.rel_grad_error(o1[cut], d1[cut].astype(np.float64).reshape(len(plus), -1)) <= REL_GRAD_TOL
+    flipped = ref.rel_grad_error(o1[cut], across) <= REL_GRAD_TOL
+    print("cut rows %d: dR1 alone equals the both-gradients dR1 on %d (bit for bit on %d), the other branch's float64 gradient on %d, neither on %d" % (
+        cut.sum(), same.sum(), (o1[cut] == d1[cut]).all(1).sum(), (flipped & ~same).sum(), (~same & ~flipped).sum()))
+    assert (same | flipped).all()
+    for check, out in (("rel_grad1", o1), ("rel_grad2", o2)):                    # and each alone, row by row, like the pair
+        fig, bound = ref.row_error(check, out, t), ref.row_bound(check, ROW_TOL, t)
+        assert (fig <= bound).all(), (check, int(np.argmax(fig - bound)), fig.max())
