@@ -818,6 +818,52 @@ int so3_local_frames_f32(const float *Y, int64_t y_stride, const int32_t *idx, c
                          const float *viewpoint, float *cov, float *eigenvalues, float *normals, float *frames, int32_t K, int64_t B,
                          int32_t N, int32_t M, void *stream);
 
+/* ---- FPFH: Fast Point Feature Histograms over a cloud's own neighbourhoods (added in 210) ----
+ * The descriptor of Rusu et al. 2009 as PCL and Open3D ship it: 33 floats per point that a rigid motion of the cloud leaves alone.
+ * Two launches: so3_spfh_f32 builds every point's simplified histogram (SPFH) over its row of idx, so3_fpfh_f32 adds the distance-
+ * weighted mean of the neighbours' histograms.  The queries are the cloud's own points: row i of idx (B*N*K) is point i's
+ * neighbourhood in the same cloud.  Cloud b has n_b = clip(len[b], 0, N) points (NULL: all).  Normals are used as given; unit length is
+ * a precondition.
+ * PAIR.  Slot k of row (b, i) with j = idx[b,i,k] is a pair when all of these hold:
+ *     0 <= j < n_b (one unsigned compare);   j != i;
+ *     dp = p_j - p_i (one rounded subtraction per coordinate) has d2 = fma(dp_z, dp_z, fma(dp_y, dp_y, dp_x * dp_x)) > 0;
+ *     neither n_i nor n_j has all three components zero (so3_icp_plane_f32's rule);
+ *     |dp x n1|^2 > 0 after the choice of roles below;   none of the three features is NaN.
+ *   A row is a multiset: an index that stands twice counts twice (so3_ball_query_f32 pads with its first hit; a caller who wants a set
+ *   overwrites that padding with -1).  No index addresses anything before it is tested.
+ * FEATURES.  d = sqrt(d2), a1 = (n_i . dp) / d, a2 = (n_j . dp) / d.  If |a1| < |a2| (strictly) the roles swap: n1 = n_j, n2 = n_i,
+ *   dp <- -dp, f3 = -a2; otherwise n1 = n_i, n2 = n_j, f3 = a1.  v = (dp x n1) / |dp x n1|, w = n1 x v, f2 = v . n2,
+ *   f1 = atan2(w . n2, n1 . n2).
+ * BINS.  h(g) = min(10, max(0, (int)floor(g))) with g1 = 11 (f1 + pi) / (2 pi), g2 = 11 (f2 + 1) / 2, g3 = 11 (f3 + 1) / 2; the
+ *   histogram's 33 slots are [h(g1) | 11 + h(g2) | 22 + h(g3)].  The arithmetic that produces g is NOT part of the bit contract
+ *   (reciprocal square roots, a polynomial atan2 and contraction are free): the counts are, for inputs whose g stay clear of the
+ *   integers (tests/fpfh_ref.py: the margin condition).
+ * SPFH.  pairs[b,i] = r, the number of pairs of the row; spfh[b,i,s] = (100 c_s) / (float)r with c_s the integer count of slot s:
+ *   100 c_s is exact and the division is IEEE, so spfh is bit-exact given the counts.  Each of the three sub-histograms sums to 100.
+ *   r = 0, rows i >= n_b and clouds with n_b = 0 are written as zeros.
+ * FPFH is a definition, bit for bit (float32; the fusions are the fmas spelled out, divisions are IEEE).  For slot k in ascending
+ *   order with 0 <= j < n_b, j != i and d2 > 0:   w = 1 / d2;   the slot is used when w < inf and pairs[b,j] > 0;
+ *       W <- W + w, a rounded chain from +0;     A_s <- fma(w, spfh[b,j,s], A_s), from +0;
+ *   then fpfh[b,i,s] = spfh[b,i,s] + (W > 0 ? A_s / W : 0).  Every neighbour's sub-histogram sums to 100, so W is the normaliser
+ *   Open3D obtains by summing bins: each sub-histogram of fpfh sums to 200 up to rounding (100 or 0 where a side is empty).
+ *   Rows i >= n_b are written as zeros.
+ * Scaling the cloud by a power of two leaves pairs, spfh and fpfh bit-identical (within float32's range).  A NaN or infinite point or
+ * normal changes only the rows that name it (for fpfh: and the rows that name those).  Every element of every requested output is
+ * written; no buffer needs a zero-fill.  No atomics, no workspace, no host synchronisation: the calls can be captured in a graph and
+ * the same inputs give the same bits.
+ *   X, normals  in   B*N*3 float32;   idx  in  B*N*K int32;   len  in  optional B int32
+ *   spfh        out (so3_spfh_f32) / in (so3_fpfh_f32)   B*N*33 float32
+ *   pairs       out (so3_spfh_f32) / in (so3_fpfh_f32)   B*N int32
+ *   fpfh        out  B*N*33 float32
+ *   so3_spfh_f32's outputs are each optional, not both NULL.
+ * 1 <= K <= SO3_KNN_MAX_K, 1 <= N <= SO3_ADD_S_MAX_N, B as so3_knn_f32 (B == 0: a no-op).  B, N and K are checked first: B == 0 with
+ * a K out of range is an error, B == 0 with NULL pointers is not.
+ */
+int so3_spfh_f32(const float *X, const float *normals, const int32_t *idx, const int32_t *len, float *spfh, int32_t *pairs, int32_t K,
+                 int64_t B, int32_t N, void *stream);
+int so3_fpfh_f32(const float *X, const int32_t *idx, const int32_t *len, const float *spfh, const int32_t *pairs, float *fpfh, int32_t K,
+                 int64_t B, int32_t N, void *stream);
+
 /* ---- PointNet++ sampling and grouping: farthest-point sampling and ball query (added in 210) ----
  * The reference's point_cloud/pointnet_utils.py: farthest_point_sample (:53-74, a Python loop of npoint iterations) and
  * query_ball_point (:77-97, a (B,S,N) index tensor sorted along N), each as one launch.

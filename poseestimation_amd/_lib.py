@@ -85,6 +85,8 @@ SYMBOLS = {
     "so3_knn_f32": (_INT, [_P, _P, _I64, _P, _P, _P, _P, _I32, _I64, _I32, _I32, _P]),
     "so3_knn_bwd_f32": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I64, _I32, _I32, _P]),
     "so3_local_frames_f32": (_INT, [_P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I64, _I32, _I32, _P]),
+    "so3_spfh_f32": (_INT, [_P, _P, _P, _P, _P, _P, _I32, _I64, _I32, _P]),
+    "so3_fpfh_f32": (_INT, [_P, _P, _P, _P, _P, _P, _I32, _I64, _I32, _P]),
     "so3_fps_f32": (_INT, [_P, _P, _P, _I64, _I32, _I32, _P]),
     "so3_ball_query_f32": (_INT, [_P, _P, ctypes.c_float, _I32, _P, _P, _I64, _I32, _I32, _P]),
     "so3_three_nn_f32": (_INT, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _P]),

@@ -1835,4 +1835,60 @@ __device__ __forceinline__ void frames_orient(V3<float> &e0, V3<float> &e1, V3<f
 }
 #pragma clang fp contract(fast)
 
+// ---- FPFH: point feature histograms over a cloud's own neighbourhoods (so3proj.hip: k_spfh, k_fpfh; tests/host_model/fpfh.cpp) ------
+// include/so3proj.h holds the definition.  What is DEFINED bit for bit: dp = p_j - p_i (one rounded subtraction per coordinate),
+// d2 = fma(dz, dz, fma(dy, dy, dx * dx)), spfh = (100 c) / (float)r, and the weighted sum of k_fpfh (w = 1 / d2, W a chain of rounded
+// additions, A_s a chain of fma(w, spfh_js, A_s), fpfh = spfh + A / W).  The three features that choose a bin are NOT: only the counts
+// they lead to are judged, away from the bins' edges (tests/fpfh_ref.py: the margin condition), so rsq, the polynomial atan2 and
+// contraction are free there.
+constexpr int kFpfhBins = 11, kFpfhSlots = 3 * kFpfhBins;
+#pragma clang fp contract(off)
+__device__ __forceinline__ float fpfh_d2(float dx, float dy, float dz) { return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)); }
+// c = the slot's integer count in one sub-histogram, r = the row's pairs: 100 c is exact (c <= 64), the division is IEEE.
+__device__ __forceinline__ float spfh_value(int32_t c, int32_t r) { return r > 0 ? (100.f * static_cast<float>(c)) / static_cast<float>(r) : 0.f; }
+// One slot of k_fpfh's sum.  slot: the index is valid and is not the query's own; pairs_j, spfh_js: the neighbour's row.
+__device__ __forceinline__ void fpfh_slot(bool slot, float pix, float piy, float piz, float pjx, float pjy, float pjz, int32_t pairs_j,
+                                          float spfh_js, float &W, float &A) {
+    const float d2 = fpfh_d2(pjx - pix, pjy - piy, pjz - piz);
+    const float w = 1.f / d2;
+    const bool use = slot && d2 > 0.f && w < __builtin_inff() && pairs_j > 0;
+    const float Wn = W + w, An = __builtin_fmaf(w, spfh_js, A);
+    W = use ? Wn : W;
+    A = use ? An : A;
+}
+__device__ __forceinline__ float fpfh_finish(float spfh_is, float W, float A) { return spfh_is + (W > 0.f ? A / W : 0.f); }
+#pragma clang fp contract(fast)
+// The bin of g: min(10, max(0, floor(g))); g is no NaN here (fpfh_pair), +-inf lands in the outer bins.
+__device__ __forceinline__ int fpfh_bin(float g) { return static_cast<int>(Tr<float>::clamp(floorf(g), 0.f, static_cast<float>(kFpfhBins - 1))); }
+// The pair (i, j) of one slot: is it one, and where do its three features fall, as g1, g2, g3 in bins' units ([0, 11]).
+// slot: the index is valid and is not the query's own.  Everything after d2 works on the unit direction u = dp / d, so a cloud scaled
+// by a power of two goes through the same bits (rsq of 4^k x is 2^-k rsq(x)) and no square of a small cross product underflows
+// because the cloud is small.  The Darboux frame is Open3D's / PCL's: the point whose normal makes the smaller angle with the line
+// between them is the source (|a1| < |a2| strictly swaps the roles).
+__device__ __forceinline__ bool fpfh_pair(bool slot, V3<float> pi, V3<float> ni, V3<float> pj, V3<float> nj, float &g1, float &g2, float &g3) {
+    typedef Tr<float> R;
+    const float dx = pj.x - pi.x, dy = pj.y - pi.y, dz = pj.z - pi.z;
+    const float d2 = fpfh_d2(dx, dy, dz);
+    const bool zero_i = ni.x == 0.f && ni.y == 0.f && ni.z == 0.f, zero_j = nj.x == 0.f && nj.y == 0.f && nj.z == 0.f;
+    bool ok = slot && d2 > 0.f && !zero_i && !zero_j;
+    const float rd = R::rsq(d2);
+    V3<float> u = mk<float>(dx * rd, dy * rd, dz * rd);
+    const float a1 = dot(ni, u), a2 = dot(nj, u);
+    const bool swap = fabsf(a1) < fabsf(a2);
+    const V3<float> n1 = sel<float>(swap, nj, ni), n2 = sel<float>(swap, ni, nj);
+    u = swap ? mk<float>(-u.x, -u.y, -u.z) : u;
+    const float f3 = swap ? -a2 : a1;
+    const V3<float> c = cross<float>(u, n1);
+    const float c2 = dot(c, c);
+    ok = ok && c2 > 0.f;
+    const V3<float> v = scale<float>(c, R::rsq(c2));
+    const V3<float> w = cross<float>(n1, v);
+    const float f2 = dot(v, n2);
+    const float f1 = R::atan2(dot(w, n2), dot(n1, n2));
+    g1 = (f1 + kPiF) * (static_cast<float>(kFpfhBins) / (2.f * kPiF));
+    g2 = (f2 + 1.f) * (0.5f * kFpfhBins);
+    g3 = (f3 + 1.f) * (0.5f * kFpfhBins);
+    return ok && g1 == g1 && g2 == g2 && g3 == g3;
+}
+
 }  // namespace so3

@@ -2981,6 +2981,95 @@ __global__ __launch_bounds__(kBlock) void k_local_frames(const float *__restrict
     }
 }
 
+// ---- FPFH: point feature histograms over a cloud's own neighbourhoods (include/so3proj.h holds the definition) ------------------------
+// k_spfh<G>: G = the power of two >= K, 1 .. 64.  A group of G lanes serves one query, one neighbour per lane, a wave 64 / G queries,
+// a work item kBlock / G consecutive queries of one cloud.  The group's lanes read the row's K indices side by side and gather the
+// neighbour's point and normal; the query's own point and normal are one address for the whole group, which the memory pipeline
+// serves as one request.  A lane forms its three bin numbers or "no pair" (so3::fpfh_pair, fpfh_bin); the histogram is 33 ballots,
+// a slot's count the population count of the ballot under the group's lanes.  Lane k keeps the counts of the slots k, k + G, ... in
+// registers (compile-time positions), so the 33 floats of a query leave as ceil(33 / G) stores of G consecutive floats.  An invalid
+// slot reads point 0 and is dropped by selects: no index addresses anything before it is tested.  Every lane of a wave runs every
+// ballot: the only loop bounds are the work item's and compile-time ones.  No LDS, no scratch, no atomics.
+template <int G>
+__global__ __launch_bounds__(kBlock) void k_spfh(const float *__restrict__ X, const float *__restrict__ normals, const int32_t *__restrict__ idx,
+                                                 const int32_t *__restrict__ len, float *__restrict__ spfh, int32_t *__restrict__ pairs,
+                                                 int32_t K, int64_t B, int32_t N, int32_t chunks) {
+    static_assert(G >= 1 && G <= 64 && (G & (G - 1)) == 0, "a group is a power of two of lanes inside one wave");
+    constexpr int kQueries = kBlock / G, kMine = (so3::kFpfhSlots + G - 1) / G;
+    const int tid = threadIdx.x, lane = tid & 63, k = tid & (G - 1);
+    const unsigned long long group = G == 64 ? ~0ull : ((1ull << (G & 63)) - 1ull) << (lane & ~(G - 1));
+    const int64_t items = B * chunks;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t b = item / chunks;
+        const int i0 = static_cast<int>(item - b * chunks) * kQueries + tid / G;
+        const bool row = i0 < N;
+        const int i = row ? i0 : N - 1;
+        const int32_t nb = so3::chamfer_length(len, b, N);
+        const float *pts = X + b * N * 3, *nrm = normals + b * N * 3;
+        const int64_t q = b * N + i;
+        const int32_t j = k < K ? idx[q * K + k] : -1;
+        const bool slot = row && i < nb && so3::group_valid(j, nb) && j != i;
+        const int jc = slot ? j : 0;
+        const so3::V3<float> pi = so3::mk<float>(pts[i * 3 + 0], pts[i * 3 + 1], pts[i * 3 + 2]);
+        const so3::V3<float> ni = so3::mk<float>(nrm[i * 3 + 0], nrm[i * 3 + 1], nrm[i * 3 + 2]);
+        const so3::V3<float> pj = so3::mk<float>(pts[jc * 3 + 0], pts[jc * 3 + 1], pts[jc * 3 + 2]);
+        const so3::V3<float> nj = so3::mk<float>(nrm[jc * 3 + 0], nrm[jc * 3 + 1], nrm[jc * 3 + 2]);
+        float g1, g2, g3;
+        const bool pair = so3::fpfh_pair(slot, pi, ni, pj, nj, g1, g2, g3);
+        const int h1 = so3::fpfh_bin(g1), h2 = so3::kFpfhBins + so3::fpfh_bin(g2), h3 = 2 * so3::kFpfhBins + so3::fpfh_bin(g3);
+        const int32_t r = __popcll(__builtin_amdgcn_ballot_w64(pair) & group);
+        int32_t mine[kMine];
+#pragma unroll
+        for (int s = 0; s < so3::kFpfhSlots; ++s) {
+            const int h = s < so3::kFpfhBins ? h1 : (s < 2 * so3::kFpfhBins ? h2 : h3);
+            const int32_t c = __popcll(__builtin_amdgcn_ballot_w64(pair && h == s) & group);
+            mine[s / G] = (s % G) == k ? c : ((s % G) == 0 ? 0 : mine[s / G]);
+        }
+        if (row && spfh != nullptr) {
+#pragma unroll
+            for (int t = 0; t < kMine; ++t) {
+                const int s = t * G + k;
+                if (s < so3::kFpfhSlots) spfh[q * so3::kFpfhSlots + s] = so3::spfh_value(mine[t], r);
+            }
+        }
+        if (row && pairs != nullptr && k == 0) pairs[q] = r;
+    }
+}
+
+// k_fpfh: one output element per lane, e = i * 33 + s inside a cloud, so consecutive lanes write consecutive floats.  A lane walks
+// its query's K slots in ascending order -- the index and the neighbour's point are one address for the query's lanes, the 33
+// floats of the neighbour's spfh row lie side by side across them -- and keeps the two chains of the definition (so3::fpfh_slot,
+// fpfh_finish); w is recomputed per lane from the two points.  No cross-lane operation, no LDS, no atomics.
+__global__ __launch_bounds__(kBlock) void k_fpfh(const float *__restrict__ X, const int32_t *__restrict__ idx, const int32_t *__restrict__ len,
+                                                 const float *__restrict__ spfh, const int32_t *__restrict__ pairs, float *__restrict__ fpfh,
+                                                 int32_t K, int64_t B, int32_t N, int32_t chunks) {
+    const int32_t E = N * so3::kFpfhSlots;
+    const int64_t items = B * chunks;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t b = item / chunks;
+        const int e = static_cast<int>(item - b * chunks) * kBlock + static_cast<int>(threadIdx.x);
+        if (e >= E) continue;
+        const int i = e / so3::kFpfhSlots, s = e - i * so3::kFpfhSlots;
+        const int32_t nb = so3::chamfer_length(len, b, N);
+        float out = 0.f;
+        if (i < nb) {
+            const float *pts = X + b * N * 3, *hist = spfh + b * N * so3::kFpfhSlots;
+            const int32_t *row = idx + (b * N + i) * K, *cnt = pairs + b * N;
+            const float px = pts[i * 3 + 0], py = pts[i * 3 + 1], pz = pts[i * 3 + 2];
+            float W = 0.f, A = 0.f;
+#pragma unroll 4
+            for (int k = 0; k < K; ++k) {
+                const int32_t j = row[k];
+                const bool slot = so3::group_valid(j, nb) && j != i;
+                const int jc = slot ? j : 0;
+                so3::fpfh_slot(slot, px, py, pz, pts[jc * 3 + 0], pts[jc * 3 + 1], pts[jc * 3 + 2], cnt[jc], hist[jc * so3::kFpfhSlots + s], W, A);
+            }
+            out = so3::fpfh_finish(hist[i * so3::kFpfhSlots + s], W, A);
+        }
+        fpfh[b * N * so3::kFpfhSlots + e] = out;
+    }
+}
+
 // ---- PointNet++ set abstraction: the grouping gather and its backward -------------------------------------------------------------
 // What sample_and_group does between the ball query and the first Conv2d: gather the grouped coordinates and
 // features, subtract the centre, concatenate, in the layout the caller asks for.  A slot whose index lies outside [0, N) -- an empty
@@ -5418,6 +5507,38 @@ int so3_local_frames_f32(const float *Y, int64_t y_stride, const int32_t *idx, c
     hipLaunchKernelGGL(k_local_frames, dim3(static_cast<unsigned>(std::min<int64_t>(B * chunks, kThreeMaxGrid))), dim3(kBlock), 0,
                        static_cast<hipStream_t>(stream), Y, y_stride, idx, x_len, y_len, viewpoint, cov, eigenvalues, normals, frames, K, B, N, M, chunks);
     return check_launch("so3_local_frames_f32");
+}
+
+int so3_spfh_f32(const float *X, const float *normals, const int32_t *idx, const int32_t *len, float *spfh, int32_t *pairs, int32_t K, int64_t B,
+                 int32_t N, void *stream) {
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N, "so3_spfh_f32: B/N");
+    SO3_CHECK_ARGS(K >= 1 && K <= SO3_KNN_MAX_K, "so3_spfh_f32: K");
+    if (B == 0) return 0;
+    SO3_CHECK_ARGS(X != nullptr && normals != nullptr && idx != nullptr && (spfh != nullptr || pairs != nullptr), "so3_spfh_f32: null pointer");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int width = 1;                                               // the power of two >= K
+    while (width < K) width *= 2;
+    with_value<1, 2, 4, 8, 16, 32, 64>(width, [&](auto GG) {
+        constexpr int G = GG();
+        const int32_t chunks = (N + kBlock / G - 1) / (kBlock / G);
+        name_kernel("k_spfh", GG);
+        hipLaunchKernelGGL((k_spfh<G>), dim3(static_cast<unsigned>(std::min<int64_t>(B * chunks, kThreeMaxGrid))), dim3(kBlock), 0, s, X, normals, idx,
+                           len, spfh, pairs, K, B, N, chunks);
+    });
+    return check_launch("so3_spfh_f32");
+}
+
+int so3_fpfh_f32(const float *X, const int32_t *idx, const int32_t *len, const float *spfh, const int32_t *pairs, float *fpfh, int32_t K, int64_t B,
+                 int32_t N, void *stream) {
+    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N, "so3_fpfh_f32: B/N");
+    SO3_CHECK_ARGS(K >= 1 && K <= SO3_KNN_MAX_K, "so3_fpfh_f32: K");
+    if (B == 0) return 0;
+    SO3_CHECK_ARGS(X != nullptr && idx != nullptr && spfh != nullptr && pairs != nullptr && fpfh != nullptr, "so3_fpfh_f32: null pointer");
+    const int32_t chunks = (N * so3::kFpfhSlots + kBlock - 1) / kBlock;
+    name_kernel("k_fpfh");
+    hipLaunchKernelGGL(k_fpfh, dim3(static_cast<unsigned>(std::min<int64_t>(B * chunks, kThreeMaxGrid))), dim3(kBlock), 0,
+                       static_cast<hipStream_t>(stream), X, idx, len, spfh, pairs, fpfh, K, B, N, chunks);
+    return check_launch("so3_fpfh_f32");
 }
 
 int so3_fps_f32(const float *xyz, const int32_t *start, int32_t *out, int64_t B, int32_t N, int32_t npoint, void *stream) {

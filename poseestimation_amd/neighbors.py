@@ -545,3 +545,111 @@ def estimate_normals(points: torch.Tensor, K: int = 16, lengths: torch.Tensor = 
     total = lam.sum(-1)
     variation = torch.where(total > 0, lam[..., 0] / total.clamp_min(torch.finfo(torch.float32).tiny), torch.zeros_like(total))
     return normals, variation.to(points.dtype)
+
+
+# --------------------------------------------------------------------------------------------
+# FPFH: a rigid-motion invariant descriptor per point, and matching by it (forward only)
+# --------------------------------------------------------------------------------------------
+def fpfh_features(points: torch.Tensor, normals: torch.Tensor, idx: torch.Tensor = None, K: int = 16, lengths: torch.Tensor = None,
+                  return_spfh: bool = False):
+    """Fast Point Feature Histograms (Rusu et al. 2009; PCL's and Open3D's descriptor): for every point of points (B,N,3) with unit
+    normals (B,N,3) -- estimate_normals' -- 33 floats (B,N,33) that do not change when the cloud is moved rigidly: three 11-bin
+    histograms of the angles between the point's normal, its neighbours' normals and the lines to them, each summing to 100, plus
+    the 1 / d^2-weighted mean of the neighbours' own histograms (each sub-histogram of the result sums to 200).
+
+    idx (B,N,K) int32 / int64: row i is point i's neighbourhood in the SAME cloud, as knn_points(points, points, K) or
+    query_ball_point(r, K, points, points) return it; idx=None runs knn_points(points, points, K, lengths, lengths).  A slot counts
+    when 0 <= idx < n_b, it is not the point itself, the two points differ, neither normal is zero and the line is not parallel to
+    the source normal; everything else (-1 padding, an empty ball's N) is skipped.  A row is a multiset: an index that stands twice
+    counts twice.  query_ball_point pads a short row by repeating its first hit -- overwrite that padding with -1 where a set is
+    meant.  lengths: optional (B,) int32 / int64, cloud b has n_b = clip(lengths[b], 0, N) points; rows past it are zeros.
+
+    Two launches (so3_spfh_f32, so3_fpfh_f32), no atomics and nothing of size (B,N,K,.) in memory; the same inputs give the same
+    bits, and scaling the cloud by a power of two changes none.  The normals are used as given.  return_spfh=True also returns
+    spfh (B,N,33) and pairs (B,N) int64, the number of slots that counted.  Any float dtype is accepted; the arithmetic is float32
+    and the histograms come back in float32.  Forward only: a histogram is piecewise constant (an argument that requires grad is
+    warned about once).  match_features pairs two clouds by these descriptors."""
+    dev = _require_device(points, normals)
+    if _wants_grad(points, normals):
+        _warn_once("fpfh_features", "fpfh_features is forward-only: a histogram is piecewise constant, so the descriptor carries no gradient "
+                                    "although an argument requires grad.")
+    if (points.dim() != 3 or points.shape[-1] != 3 or tuple(normals.shape) != tuple(points.shape) or not points.is_floating_point()
+            or not normals.is_floating_point() or not 1 <= points.shape[1] <= _lib.ADD_S_MAX_N):
+        raise ValueError("fpfh_features: expected points and normals as (B, N, 3) floating-point tensors with 1 <= N <= %d, got %s %s and %s %s"
+                         % (_lib.ADD_S_MAX_N, points.dtype, tuple(points.shape), normals.dtype, tuple(normals.shape)))
+    b, n = points.shape[:2]
+    x = points.detach().contiguous().float()
+    nr = normals.detach().contiguous().float()
+    if idx is None:
+        if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= _lib.KNN_MAX_K:
+            raise ValueError("fpfh_features: expected an int 1 <= K <= %d, got %r" % (_lib.KNN_MAX_K, K))
+        _, idx = knn_points(x, x, K, lengths, lengths)
+    else:
+        _require_device(idx)
+        if (idx.device != dev or idx.dim() != 3 or tuple(idx.shape[:2]) != (b, n) or idx.dtype not in (torch.int32, torch.int64)
+                or not 1 <= idx.shape[2] <= _lib.KNN_MAX_K):
+            raise ValueError("fpfh_features: expected idx (B, N, K) (int32 or int64) on %s with B = %d, N = %d and 1 <= K <= %d, got %s %s on %s"
+                             % (dev, b, n, _lib.KNN_MAX_K, idx.dtype, tuple(idx.shape), idx.device))
+    k = idx.shape[2]
+    ln = _cloud_lengths("fpfh_features", ValueError, "lengths", lengths, b, n, dev)
+    # an index beyond int32 is invalid either way: clamp it to one that stays invalid (N <= 2^20) instead of letting it wrap
+    ix = (idx if idx.dtype == torch.int32 else idx.clamp(-1, _lib.ADD_S_MAX_N).to(torch.int32)).contiguous()
+    spfh = torch.empty((b, n, 33), dtype=torch.float32, device=dev)
+    pairs = torch.empty((b, n), dtype=torch.int32, device=dev)
+    fpfh = torch.empty((b, n, 33), dtype=torch.float32, device=dev)
+    _launch(dev, "so3_spfh_f32", _ptr(x), _ptr(nr), _ptr(ix), _ptr(ln), _ptr(spfh), _ptr(pairs), k, b, n)
+    _launch(dev, "so3_fpfh_f32", _ptr(x), _ptr(ix), _ptr(ln), _ptr(spfh), _ptr(pairs), _ptr(fpfh), k, b, n)
+    return (fpfh, spfh, pairs.long()) if return_spfh else fpfh
+
+
+def match_features(fx: torch.Tensor, fy: torch.Tensor, x_lengths: torch.Tensor = None, y_lengths: torch.Tensor = None, mutual: bool = True):
+    """Correspondences by descriptor: for every row of fx (B,N,D) the nearest row of fy (B,M,D) in the Euclidean distance -> (B,N) int64,
+    the first of equal candidates.  -1 for the rows past x_lengths[b], for every row when cloud b of fy is empty (y_lengths[b] == 0),
+    and, with mutual=True, where the match does not point back (the nearest row of fx to fy[b, j] is not i).  Rows of fy past
+    y_lengths[b] are never matched.
+
+    Plain torch on the tensors' device (CPU tensors work too), as index_points: the (B,N,M) distance matrix is torch.cdist's GEMM
+    work.  With keep = match[b] >= 0, the pairs P[b, keep] and Q[b, match[b, keep]] -- or, batched, Q gathered by match.clamp(min=0)
+    with keep.float() as the weights -- are what rigid_align takes: fpfh_features on two clouds in arbitrary relative pose,
+    match_features, rigid_align, then icp_align from that start.  No gradient."""
+    if (fx.dim() != 3 or fy.dim() != 3 or fx.shape[0] != fy.shape[0] or fx.shape[2] != fy.shape[2] or fx.device != fy.device
+            or not fx.is_floating_point() or not fy.is_floating_point()):
+        raise ValueError("match_features: expected fx (B, N, D) and fy (B, M, D) as floating-point tensors on one device, got %s %s on %s and %s %s on %s"
+                         % (fx.dtype, tuple(fx.shape), fx.device, fy.dtype, tuple(fy.shape), fy.device))
+    b, n, m = fx.shape[0], fx.shape[1], fy.shape[1]
+    dev = fx.device
+    lens = []
+    for name, lengths, full in (("x_lengths", x_lengths, n), ("y_lengths", y_lengths, m)):
+        if lengths is None:
+            lens.append(torch.full((b,), full, dtype=torch.long, device=dev))
+            continue
+        if (not isinstance(lengths, torch.Tensor) or lengths.device != dev or tuple(lengths.shape) != (b,)
+                or lengths.dtype not in (torch.int32, torch.int64)):
+            raise ValueError("match_features: expected %s as a (B,) int32 or int64 tensor on %s for B = %d" % (name, dev, b))
+        lens.append(lengths.detach().long().clamp(0, full))
+    nl, ml = lens
+    if n == 0 or m == 0 or b == 0:
+        return torch.full((b, n), -1, dtype=torch.long, device=dev)
+    with torch.no_grad():
+        dtype = torch.promote_types(fx.dtype, fy.dtype)
+        dist = torch.cdist(fx.detach().to(dtype), fy.detach().to(dtype))                            # (B, N, M)
+        live_x = torch.arange(n, device=dev)[None, :] < nl[:, None]                                  # (B, N)
+        live_y = torch.arange(m, device=dev)[None, :] < ml[:, None]                                  # (B, M)
+        inf = torch.full((), float("inf"), dtype=dist.dtype, device=dev)
+        dist = torch.where(live_x[:, :, None] & live_y[:, None, :], dist, inf)
+        forward = _first_argmin(dist, 2)                                                             # (B, N)
+        keep = live_x & (ml > 0)[:, None]
+        if mutual:
+            back = _first_argmin(dist, 1)                                                            # (B, M)
+            keep = keep & (back.gather(1, forward) == torch.arange(n, device=dev)[None, :])
+        return torch.where(keep, forward, torch.full((), -1, dtype=torch.long, device=dev))
+
+
+def _first_argmin(dist, dim):
+    """argmin along dim, the FIRST of equal candidates (torch.argmin leaves the choice among ties open)."""
+    best = dist.min(dim, keepdim=True).values
+    size = dist.shape[dim]
+    shape = [1, 1, 1]
+    shape[dim] = size
+    at = torch.arange(size, device=dist.device).view(shape)
+    return torch.where(dist == best, at, torch.full((), size, dtype=torch.long, device=dist.device)).min(dim).values.clamp(max=size - 1)

@@ -279,6 +279,19 @@ def main():
                lambda i: lib.so3_local_frames_f32(p(yl_), 3 * nl, p(il), None, None, None, None, None, p(ml), None, kl, bl, nl, nl, st),
                bl * nl * (kl * 16 + 12), iters=20, warm=3)
     del yl_, il, cl, el, ml, fl
+    # FPFH beside the local frames: the same index rows, a point and a normal gathered per slot, 33 floats and a count out; then per
+    # output element K slots of a broadcast index and point and one float of the neighbour's row (the bytes are the rows', one pass)
+    for bh, nh, kh in ((32, 1024, 16), (8, 4096, 32)):
+        xh = torch.rand(bh, nh, 3, device=dev)
+        nrh = torch.nn.functional.normalize(torch.randn(bh, nh, 3, device=dev), dim=-1)
+        ih = torch.empty(bh, nh, kh, dtype=torch.int32, device=dev)
+        _lib.check(lib.so3_knn_f32(p(xh), p(xh), 3 * nh, None, None, None, p(ih), kh, bh, nh, nh, st), "so3_knn_f32")
+        sh, ph, fh = torch.empty(bh, nh, 33, device=dev), torch.empty(bh, nh, dtype=torch.int32, device=dev), torch.empty(bh, nh, 33, device=dev)
+        timeit("fpfh, beside local_frames: so3_spfh_f32 (%d x %d, K = %d, spfh + pairs)" % (bh, nh, kh),
+               lambda i: lib.so3_spfh_f32(p(xh), p(nrh), p(ih), None, p(sh), p(ph), kh, bh, nh, st), bh * nh * (kh * 28 + 24 + 136), iters=20, warm=3)
+        timeit("fpfh, beside local_frames: so3_fpfh_f32 (%d x %d, K = %d)" % (bh, nh, kh),
+               lambda i: lib.so3_fpfh_f32(p(xh), p(ih), None, p(sh), p(ph), p(fh), kh, bh, nh, st), bh * nh * (kh * (4 + 12 + 4 + 132) + 264), iters=20, warm=3)
+    del xh, nrh, ih, sh, ph, fh
     # PointNet++ sampling and grouping at the reference model's first level: a chain of 511 dependent argmaxes per cloud (one workgroup
     # each: latency bound, most compute units idle at B = 32), and one wave per centre over the cloud (the bytes are the index rows')
     bf, nf, sf, kf = 32, 1024, 512, 64

@@ -1287,7 +1287,21 @@ def g31_chamfer_normals():
     assert os.path.getsize(os.path.join(OUT, "g31_chamfer_normals.npz")) <= 512 * 1024
 
 
+def g32_fpfh():
+    """fpfh_features: no reference code exists, so the fixture holds float32 clouds, normals and index rows (tests/fpfh_ref.py: the
+    sphere and the blob at SURFACE_SHAPES, the exact lattices, coincident points, zero normals, rows with invalid, missing and repeated
+    indices, K = 1, 2, 3, K > n_b, ragged lengths, non-finite values, and the moved copies) and the float64 counts -- tests/fpfh_ref.py:
+    generate, which redraws points until the margin condition holds and asserts every family's premise.  The expectations are
+    re-formed from the counts on load."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import fpfh_ref as ref
+    save("g32_fpfh.npz", **ref.generate())
+    assert os.path.getsize(os.path.join(OUT, "g32_fpfh.npz")) <= 512 * 1024
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "g32":
+        return g32_fpfh()
     if len(sys.argv) > 1 and sys.argv[1] == "g31":
         return g31_chamfer_normals()
     if len(sys.argv) > 1 and sys.argv[1] == "g30":
@@ -1354,6 +1368,7 @@ def main():
     g29_local_frames()
     g30_icp_plane()
     g31_chamfer_normals()
+    g32_fpfh()
     g22_pointnet()
     g23_head_edges()
     # ---- G1: config #1, 256 Gaussian rows ------------------------------------------------------
