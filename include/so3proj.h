@@ -846,7 +846,8 @@ int so3_local_frames_f32(const float *Y, int64_t y_stride, const int32_t *idx, c
  *       W <- W + w, a rounded chain from +0;     A_s <- fma(w, spfh[b,j,s], A_s), from +0;
  *   then fpfh[b,i,s] = spfh[b,i,s] + (W > 0 ? A_s / W : 0).  Every neighbour's sub-histogram sums to 100, so W is the normaliser
  *   Open3D obtains by summing bins: each sub-histogram of fpfh sums to 200 up to rounding (100 or 0 where a side is empty).
- *   Rows i >= n_b are written as zeros.
+ *   Rows i >= n_b are written as zeros.  w < inf does not keep A_s finite: from about w = 2^121 a spfh of 100 overflows the fma, and
+ *   the defined result is then inf or NaN.
  * Scaling the cloud by a power of two leaves pairs, spfh and fpfh bit-identical (within float32's range).  A NaN or infinite point or
  * normal changes only the rows that name it (for fpfh: and the rows that name those).  Every element of every requested output is
  * written; no buffer needs a zero-fill.  No atomics, no workspace, no host synchronisation: the calls can be captured in a graph and

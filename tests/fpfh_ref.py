@@ -24,14 +24,18 @@ compared EXACTLY.  The margin is justified by a measured figure: the largest |g3
 
 fpfh against float64 is judged per element as |got - want| / want, and as exact 0 where want == 0 (every term is non-negative, so the
 figure means something everywhere); the bound is 4 x the host model's largest figure over G32 (MEASURED["fpfh"]), the rule of the
-other families."""
+other families.
+
+THE BRANCH CASES (tie_case, outer_case, weight_case, below) are the opposite of the margin condition: inputs built ON the strict swap,
+beyond the two clamps of the bin and on "used when w < inf", each asserting that it reaches its branch, judged exactly under undecided()."""
+import functools
 import os
 
 import numpy as np
 
 from f32_exact import fma32, pair_dist2_32
 import knn_ref
-from support import lengths_of
+from support import bits, lengths_of
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g32_fpfh.npz")
 MAX_K = 64
@@ -78,7 +82,7 @@ def _darboux(u, ni, nj, a1, a2, swap):
 
 def features64(X, normals, idx, lengths=None):
     """Every slot's float64 features: pair (B, N, K), g (B, N, K, 3), the other role assignment's g_alt, cn and cn_alt = |dp x n1| / d
-    of both, tie (| |a1| - |a2| | < MARGIN), valid, at (the clamped index), d2."""
+    of both, tie (| |a1| - |a2| | < MARGIN), valid, at (the clamped index), d2, a1, a2."""
     with np.errstate(all="ignore"):
         valid, at, pi, ni, pj, nj = _gather(X, normals, idx, lengths, np.float64)
         ni, pi = np.broadcast_to(ni, nj.shape), np.broadcast_to(pi, pj.shape)
@@ -92,7 +96,7 @@ def features64(X, normals, idx, lengths=None):
         nonzero = (ni != 0).any(-1) & (nj != 0).any(-1)
         pair = valid & (d2 > 0) & nonzero & (cn > 0) & ~np.isnan(g).any(-1)
         tie = np.abs(np.abs(a1) - np.abs(a2)) < MARGIN
-    return {"pair": pair, "g": g, "g_alt": g_alt, "cn": cn, "cn_alt": cn_alt, "tie": tie, "valid": valid, "at": at, "d2": d2}
+    return {"pair": pair, "g": g, "g_alt": g_alt, "cn": cn, "cn_alt": cn_alt, "tie": tie, "valid": valid, "at": at, "d2": d2, "a1": a1, "a2": a2}
 
 
 def bins_of(g):
@@ -123,6 +127,30 @@ def violations(f):
         own = _near_edge(f["g"]) | ((f["cn"] > 0) & (f["cn"] < MARGIN))
         other = _near_edge(f["g_alt"]) | ~(f["cn_alt"] >= MARGIN) | (bins_of(f["g"]) != bins_of(f["g_alt"])).any(-1)
     return f["pair"] & (own | (f["tie"] & other))
+
+
+def _near_interior_edge(g):
+    """_near_edge for the branch cases: the interior integers 1 .. 10 are the only real edges.  h() clamps at 0 and at 10, so a g at
+    0, at 11 or beyond either of them lands in the outer bin in any arithmetic."""
+    with np.errstate(invalid="ignore"):
+        k = np.round(g)
+        return ((np.abs(g - k) < MARGIN) & (k >= 1) & (k <= BINS - 1)).any(-1)
+
+
+def same_normals(f, normals):
+    """The slots (B, N, K) whose two normals are bit-identical."""
+    nb = bits(normals)
+    return (nb[:, :, None, :] == nb[np.arange(nb.shape[0])[:, None, None], f["at"]]).all(-1)
+
+
+def undecided(f, normals):
+    """The second acceptance rule, for the branch cases: the slots (B, N, K) that break it.  violations() with two differences: only
+    the interior integers are edges (_near_interior_edge), and a swap tie is DECIDED when the two normals are bit-identical -- a1 and a2
+    are then the same float32 value in any arithmetic, |a1| < |a2| is false, and the header says no swap."""
+    with np.errstate(invalid="ignore"):
+        own = _near_interior_edge(f["g"]) | ((f["cn"] > 0) & (f["cn"] < MARGIN))
+        other = _near_interior_edge(f["g_alt"]) | ~(f["cn_alt"] >= MARGIN) | (bins_of(f["g"]) != bins_of(f["g_alt"])).any(-1)
+    return f["pair"] & (own | (f["tie"] & ~same_normals(f, normals) & other))
 
 
 def clean_rows(X, normals, idx, lengths=None):
@@ -392,3 +420,178 @@ def cases(z):
                 c["fpfh64"] = fpfh64(c["X"], idx, lengths, c["counts"], c["pairs"])
                 out.append(c)
     return out
+
+
+# ---- the branch cases: inputs that sit exactly ON the definition's branches --------------------------------------------------------
+# G32 keeps away from every branch on purpose (the margin condition).  These generators go the other way: each builds inputs on which
+# one branch rule of the header alone decides the counts, asserts in float64 on the stored float32 inputs that the branch is reached, and
+# leaves every OTHER quantity far enough from an edge that float32 and float64 must agree.  Pure numpy, fixed seeds, no fixture file;
+# judged under undecided() instead of violations().
+EDGE_B, EDGE_N, EDGE_KS = 3, 257, (5, 16, 33)                                 # k_spfh<8>, k_spfh<16>, k_spfh<64>
+EDGE_ROWS = (0, 63, 64, 255, 256)                                             # a wave's and a workgroup's first and last query, the tail
+EDGE_LENGTHS = {"ties": (257, 257, 130), "outer": (257, 257, 200)}            # one ragged cloud each
+LONG = 1.0 + 2.0 ** -18                                                       # a "unit" normal a few float32 ulp long
+OFF = 2.0 ** -10                                                              # rad: how far a pair leans off the exact degenerate direction
+OVERSHOOT = 1e-5                                                              # g past 11 or below 0 by more than this: > 10 float32 ulp of 11
+# A pair built OFF rad from a degenerate direction has |dp x n1| / d (or |n2 x v|) = sin OFF ~ 1e-3, so float32's 1e-7 of rounding
+# turns its two well-defined-but-ill-conditioned features by up to ~1e-4 rad: 6e-4 in bins' units, more than MARGIN.  Those features
+# are therefore held WIDE from every integer, 80 x that.
+WIDE = 0.05
+TILTS = ((0.6, 0.0, 0.8), (0.0, -0.8, 0.6), (0.48, 0.64, 0.6))                # one tilted normal per cloud, the same bits on every point
+
+
+def _branch_case(name, family, X, Nr, idx, lengths):
+    X, Nr, idx = np.ascontiguousarray(X, np.float32), np.ascontiguousarray(Nr, np.float32), np.ascontiguousarray(idx, np.int32)
+    lengths = np.asarray(lengths, np.int32)
+    f = features64(X, Nr, idx, lengths)
+    assert not undecided(f, Nr).any(), name
+    counts, _ = counts_of(f["pair"], f["g"])
+    c = _case(name, family, X, Nr, idx, lengths, counts)
+    assert c["spfh_rows"].all() and c["fpfh_rows"].all() and (c["n"], c["b"]) == (EDGE_N, EDGE_B), name
+    c["f"] = f
+    return c
+
+
+def tie_case(K):
+    """EXACT SWAP TIES.  Every cloud is a flat patch (z = 0, random x and y) whose points all carry one tilted normal, bit for bit; a
+    row is the point's K - 1 nearest (itself among them) and one -1.  a1 and a2 are dots of the SAME normal with the same u: equal in
+    any arithmetic, and the header says |a1| < |a2| strictly, so no pair swaps.  Premises (asserted): every pair's normals are
+    bit-identical; both role assignments keep MARGIN from the interior integers; on at least half of the pairs they give different
+    bins, so swapping on the tie changes the histogram."""
+    rng = np.random.default_rng(3300 + K)
+    lengths = np.array(EDGE_LENGTHS["ties"], np.int32)
+    X = np.zeros((EDGE_B, EDGE_N, 3), np.float32)
+    X[..., :2] = rng.uniform(-1, 1, (EDGE_B, EDGE_N, 2))
+    Nr = np.broadcast_to(np.array(TILTS, np.float32)[:, None, :], X.shape).copy()
+    for _ in range(200):
+        idx = np.concatenate([knn_rows(X, K - 1, lengths), np.full((EDGE_B, EDGE_N, 1), -1, np.int64)], -1)
+        f = features64(X, Nr, idx, lengths)
+        bad = (undecided(f, Nr) | (f["pair"] & _near_interior_edge(f["g_alt"]))).any(-1)
+        if not bad.any():
+            break
+        X[bad, :2] = rng.uniform(-1, 1, (int(bad.sum()), 2))
+    c = _branch_case("ties_%d" % K, "ties", X, Nr, idx, lengths)
+    f, pair = c["f"], c["f"]["pair"]
+    assert same_normals(f, Nr)[pair].all() and f["tie"][pair].all()
+    assert (f["a1"][pair] == f["a2"][pair]).all() and not _near_interior_edge(f["g_alt"])[pair].any()
+    nl = lengths_of(lengths, EDGE_B, EDGE_N)
+    assert all((c["pairs"][b, :nl[b]] == K - 2).all() and (c["pairs"][b, nl[b]:] == 0).all() for b in range(EDGE_B))
+    c["ties"] = int(pair.sum())
+    c["ties_that_differ"] = int((bins_of(f["g"]) != bins_of(f["g_alt"])).any(-1)[pair].sum())
+    assert c["ties"] >= (K - 2) * int(nl.sum()) and 2 * c["ties_that_differ"] >= c["ties"]
+    return c
+
+
+def _one_pair(pi, ni, pj, nj):
+    """features64 of the single pair (i -> j), squeezed."""
+    f = features64(np.array([[pi, pj]], np.float32), np.array([[ni, nj]], np.float32), np.array([[[1], [0]]]))
+    return {k: v[0, 0, 0] for k, v in f.items()}
+
+
+def _wide(g):
+    return np.abs(g - np.round(g)) >= WIDE
+
+
+def outer_case(K):
+    """BEYOND THE OUTER EDGES.  The queries stand in EDGE_ROWS; each has its own neighbours elsewhere in the cloud, every other point is
+    filler with an empty row.  All normals have length LONG (the queries' exactly, along an axis).
+      g3 queries: the neighbours lie OFF rad off the normal's line, alternately in front and behind, at distances 0.5 .. 1.0, so
+                  f3 = a1 = +-LONG cos OFF: g3 = 11.000018 or -0.000018.  The neighbour's normal is drawn with |a2| <= 0.8.
+      g2 queries: the neighbour's normal leans OFF rad off +-v = +-(dp x n1) / |dp x n1|, so f2 = +-LONG cos OFF and a2 ~ 0; dp makes
+                  an angle with the query's normal that puts g3 in the middle of a bin, the lean's direction puts g1 in one.
+    A neighbour's own row names its query back: the same pair seen from the other side swaps the roles and must overshoot too.
+    Premises (asserted): on at least two pairs each g3 > 11 + OVERSHOOT, g3 < -OVERSHOOT, g2 > 11 + OVERSHOOT, g2 < -OVERSHOOT; every
+    pair has |dp x n1| > 0 and | |a1| - |a2| | >= 0.1 (no swap tie); every feature that does not overshoot keeps WIDE from every
+    integer.  The float64 counts then hold bins 10 and 0."""
+    rng = np.random.default_rng(3400 + K)
+    lengths = np.array(EDGE_LENGTHS["outer"], np.int32)
+    X = np.zeros((EDGE_B, EDGE_N, 3), np.float32)
+    X[..., 0], X[..., 1], X[..., 2] = 16 + np.arange(EDGE_N) / 8.0, -16.0, 16.0           # the filler: far from every query
+    Nr = np.broadcast_to(np.array([0, 0, 1], np.float32), X.shape).copy()
+    idx = np.full((EDGE_B, EDGE_N, K), -1, np.int32)
+    mids = [(m + 0.5) / 5.5 - 1 for m in (1, 2, 3, 7, 8, 9)]                              # a1 with g3 in the middle of bin m
+
+    def unit(v):
+        return v / np.linalg.norm(v)
+
+    for b in range(EDGE_B):
+        free = iter(i for i in range(EDGE_N) if i not in EDGE_ROWS)
+        for qi, q in enumerate(EDGE_ROWS):
+            kind = "g3" if (qi + b) % 2 == 0 else "g2"
+            axis, sign = np.eye(3)[(qi + b) % 3], 1.0 if (qi // 3 + b) % 2 == 0 else -1.0
+            p1, p2 = np.eye(3)[(qi + b + 1) % 3], np.eye(3)[(qi + b + 2) % 3]
+            X[b, q], Nr[b, q] = (4.0 * qi - 8, 4.0 * b - 4, 2.0 * (qi % 2)), sign * LONG * axis
+            k = max(2, K - 1 - qi % 2)
+            for t in range(k):
+                j = next(free)
+                idx[b, q, t], idx[b, j, 0] = j, q
+                side, dist, phi = (1.0 if t % 2 == 0 else -1.0), 0.5 + 0.5 * t / (k - 1), rng.uniform(0, 2 * np.pi)
+                around = np.cos(phi) * p1 + np.sin(phi) * p2
+                for _ in range(1000):
+                    if kind == "g3":
+                        u = side * np.cos(OFF) * sign * axis + np.sin(OFF) * around
+                        X[b, j] = X[b, q].astype(np.float64) + dist * u
+                        Nr[b, j] = LONG * unit(rng.standard_normal(3))
+                    else:
+                        a1 = mids[(t // 2) % len(mids)]
+                        u = a1 * sign * axis + np.sqrt(1 - a1 * a1) * around
+                        X[b, j] = X[b, q].astype(np.float64) + dist * u
+                        n1 = Nr[b, q].astype(np.float64)
+                        dp = X[b, j].astype(np.float64) - X[b, q].astype(np.float64)               # the stored, rounded points
+                        v = unit(np.cross(dp, n1))
+                        psi = ((t + qi) % BINS + 0.5) * 2 * np.pi / BINS - np.pi                    # f1: the middle of a bin
+                        lean = np.cos(psi) * unit(n1) + np.sin(psi) * unit(np.cross(n1, v))
+                        Nr[b, j] = LONG * (np.cos(OFF) * side * v + np.sin(OFF) * lean)
+                    s = _one_pair(X[b, q], Nr[b, q], X[b, j], Nr[b, j])
+                    over = (s["g"] > BINS + OVERSHOOT) | (s["g"] < -OVERSHOOT)
+                    if s["pair"] and abs(abs(s["a1"]) - abs(s["a2"])) >= 0.1 and (over | _wide(s["g"])).all() and over[2 if kind == "g3" else 1]:
+                        break
+                    phi = rng.uniform(0, 2 * np.pi)
+                    around = np.cos(phi) * p1 + np.sin(phi) * p2
+                else:
+                    raise AssertionError("no neighbour found")
+    c = _branch_case("outer_%d" % K, "outer", X, Nr, idx, lengths)
+    f, pair = c["f"], c["f"]["pair"]
+    g = f["g"][pair]
+    over, under = g > BINS + OVERSHOOT, g < -OVERSHOOT
+    assert (f["cn"][pair] > 0).all() and (np.abs(np.abs(f["a1"]) - np.abs(f["a2"]))[pair] >= 0.1).all() and not f["tie"][pair].any()
+    assert (over | under | _wide(g)).all() and not (over | under)[:, 0].any()
+    c["beyond"] = {"g2>11": int(over[:, 1].sum()), "g2<0": int(under[:, 1].sum()), "g3>11": int(over[:, 2].sum()), "g3<0": int(under[:, 2].sum())}
+    assert min(c["beyond"].values()) >= 2, c["beyond"]
+    swapped = (np.abs(f["a1"]) < np.abs(f["a2"]))[pair]                                    # both role assignments reach the outer bins
+    assert (over | under).any(-1)[swapped].sum() >= 4 and (over | under).any(-1)[~swapped].sum() >= 4
+    for s, col in ((BINS, 1), (2 * BINS, 2)):                                              # the float64 counts hold bins 10 and 0
+        assert c["counts"][..., s + BINS - 1].sum() >= over[:, col].sum() and c["counts"][..., s].sum() >= under[:, col].sum()
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def branch_cases(K):
+    """The tie case and the outer-edge case at one K of EDGE_KS; built once, shared by the host and the device tests, never changed."""
+    return (tie_case(K), outer_case(K))
+
+
+@functools.lru_cache(maxsize=None)
+def weight_case():
+    """THE WEIGHT RULE, for so3_fpfh_f32 alone: points, rows, and GIVEN spfh (small multiples of 25) and pairs, so every row used has a
+    known, finite answer.  Points 0 and 1 are 2^-65 apart: d2 = 2^-130, which a device may keep (w = 1 / d2 = inf: "used when w < inf"
+    skips the slot) or flush to 0 (d2 > 0 skips it) -- the same answer.  Points 0 and 2 are 2^-59 apart: w = 2^118, used, and it
+    dominates the row.  Points 1 and 2 never meet in a row (their d2 = 2^-118 + 2^-130 would depend on the flush).  Point 5 has
+    pairs = 0.  Premises (asserted, float32 numpy): a slot with d2 > 0 and 1 / d2 == inf, a used slot with w >= 2^100, and a finite
+    fpfh32 everywhere."""
+    rng = np.random.default_rng(3500)
+    X = np.array([[[0, 0, 0], [2.0 ** -65, 0, 0], [0, 2.0 ** -59, 0], [0.5, 0.25, 0], [-0.25, 0.5, 0.125], [0.125, -0.5, 0.75]]], np.float32)
+    idx = np.array([[[1, 2, 3, 4, -1], [0, 3, 4, 5, -1], [0, 3, -1, 4, 5], [0, 1, 2, 4, 5], [5, 3, 2, 1, 0], [-1, 0, 1, 3, 6]]], np.int32)
+    spfh = (25 * rng.integers(0, 5, (1, 6, SLOTS))).astype(np.float32)
+    pairs = np.array([[3, 2, 4, 1, 3, 0]], np.int32)
+    want = fpfh32(X, idx, None, spfh, pairs)
+    with np.errstate(all="ignore"):
+        valid, at, pi, _, pj, _ = _gather(X, X, idx, None, np.float32)
+        dp = pj - pi
+        d2 = pair_dist2_32(dp[..., 0], dp[..., 1], dp[..., 2]).astype(np.float32)
+        w = (np.float32(1) / d2).astype(np.float32)
+        used = valid & (d2 > 0) & (w < np.inf) & (pairs[0][at] > 0)
+    assert (valid & (d2 > 0) & np.isinf(w)).sum() == 2 and (used & (w >= 2.0 ** 100)).sum() == 2 and np.isfinite(want).all()
+    assert (valid & (pairs[0][at] == 0)).any() and (want != spfh).any()
+    normals = np.broadcast_to(np.array([0, 0, 1], np.float32), X.shape).copy()                       # unused by the second launch
+    return {"name": "weights", "X": X, "normals": normals, "idx": idx, "lengths": None, "spfh": spfh, "pairs": pairs, "fpfh32": want, "b": 1, "n": 6, "K": 5}

@@ -21,6 +21,7 @@ The eigen stage is an approximation; its judges, with u = 2^-24 and t = tr C64, 
 Each constant is 4 x what the float32 host model of the kernel's own device functions (tests/host_model/local_frames.cpp, libm's
 sqrt and 1 / sqrt) reaches over G29 -- the rule of the head-edge tests: the device rounds v_rsq_f32 and v_sqrt_f32 differently (1 ulp),
 and 4 x has covered that there.  MEASURED holds the host model's figures; tests/test_local_frames_host.py holds the model to them."""
+import functools
 import os
 
 import numpy as np
@@ -307,4 +308,96 @@ def cases(z):
         c["b"], c["n"], c["K"] = c["idx"].shape
         c["m"] = c["Y"].shape[1]
         out.append(c)
+    return out
+
+
+# ---- the branch cases: inputs that sit exactly ON the sign rules ----------------------------------------------------------------------
+# G29 is drawn at random, so no two components of a vector are ever bit-equal and no viewpoint ever lies exactly in a patch's plane.
+# These patches are integer lattices on the planes x_p = +-x_q and along the lines e_p - e_q, shifted by (5, 5, 5): every step of the
+# covariance is exact, the tied axes get bit-equal diagonal entries and exactly zero couplings to the third axis, and in sym_rotate
+# d == 0 makes (c, s) = (|g|, g) / |(g, g)|, so the eigenvector's two tied components have the same magnitude bit for bit whatever rsq
+# returns.  "The lowest index decides" and "exactly 0 keeps the sign" then decide alone.  Pure numpy, no fixture file.
+EDGE_B, EDGE_N, EDGE_K, EDGE_VALID = 3, 257, 16, 9
+EDGE_ROWS = (0, 63, 64, 255, 256)                                             # a wave's and a workgroup's first and last query, the tail
+TIED_AXES = ((1, 2), (0, 1), (0, 2))                                          # (p, q), p < q: the planes y = +-z, x = +-y, x = +-z
+SHIFT = 5.0
+
+
+def lattice_plane(p, q, sigma):
+    """The 9 points x_r in {-2, 0, 2}, x_p in {-1, 0, 1}, x_q = sigma x_p, shifted: the normal is (e_p - sigma e_q) / sqrt 2."""
+    r = 3 - p - q
+    pts = np.zeros((9, 3))
+    a, c = np.meshgrid([-2.0, 0.0, 2.0], [-1.0, 0.0, 1.0], indexing="ij")
+    pts[:, r], pts[:, p], pts[:, q] = a.ravel(), c.ravel(), sigma * c.ravel()
+    return (pts + SHIFT).astype(np.float32)
+
+
+def lattice_line(p, q):
+    """The 9 points t (e_p - e_q), t = -4 .. 4, shifted: e2 is (e_p - e_q) / sqrt 2, the other two eigenvalues are 0."""
+    pts = np.zeros((9, 3))
+    pts[:, p], pts[:, q] = np.arange(-4.0, 5.0), -np.arange(-4.0, 5.0)
+    return (pts + SHIFT).astype(np.float32)
+
+
+def _padded_row(points, i, m, keep_pivot=False):
+    """The 9 indices `points` as a row of EDGE_K slots: their order rolled by i (keep_pivot: all but the first), between -1, the
+    out-of-range indices m and INT32_MIN, in one of three layouts."""
+    v = list(points[:1]) + list(np.roll(points[1:], i)) if keep_pivot else list(np.roll(points, i))
+    row = (v, [-1, v[0], m] + v[1:], [INT32_MIN, -1] + v[:4] + [m] + v[4:])[i % 3]
+    return row + [-1] * (EDGE_K - len(row) - 1) + [m if i % 3 == 0 else -1]
+
+
+def _branch_case(name, Y, idx, view=None, **more):
+    Y, idx = np.ascontiguousarray(Y, np.float32), np.ascontiguousarray(idx, np.int32)
+    c = {"name": name, "family": "branch", "Y": Y, "idx": idx, "x_lengths": None, "y_lengths": None,
+         "viewpoint": None if view is None else np.ascontiguousarray(view, np.float32), "cov32": cov32(Y, idx), "ref64": frames64(Y, idx), "m": Y.shape[1]}
+    c["b"], c["n"], c["K"] = idx.shape
+    c.update(more)
+    assert (c["b"], c["n"], c["K"]) == (EDGE_B, EDGE_N, EDGE_K) and (c["ref64"][3] == EDGE_VALID).all(), name
+    p, q = c["tied"][..., 0], c["tied"][..., 1]
+    cov = bits(c["cov32"]).reshape(EDGE_B, EDGE_N, 6)
+    diag, pair = np.array([0, 3, 5]), {(0, 1): 1, (0, 2): 2, (1, 2): 4}
+    coupling = np.array([[pair[tuple(sorted((a, 3 - t[0] - t[1])))] for a in t] for t in TIED_AXES])      # (tied axes) -> C_pr, C_qr
+    which = np.array([TIED_AXES.index((int(a), int(b_))) for a, b_ in zip(p.ravel(), q.ravel())]).reshape(p.shape)
+    take = lambda cols: np.take_along_axis(cov, cols[..., None], -1)[..., 0]                               # noqa: E731
+    assert (take(diag[p]) == take(diag[q])).all() and (c["cov32"] != 0).any(-1).all(), name               # the tied diagonal entries: bit-equal
+    assert (take(coupling[which, 0]) << 1 == 0).all() and (take(coupling[which, 1]) << 1 == 0).all(), name  # their couplings to the third axis: 0
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def sign_tie_case():
+    """SIGN TIES.  One cloud of nine patches, shared by the three batch entries: the planes x_p = x_q (normal (e_p - e_q) / sqrt 2: the
+    tie rule alone picks its sign), their mirrors x_p = -x_q, and the lines along e_p - e_q (e2 ties).  Row (b, i) names patch
+    (4 i + b) mod 9 -- EDGE_ROWS reach all nine -- through 9 valid slots among 16.  No viewpoint.
+    -> the case, with per row: tied (p, q), line (the tied vector is e2, else e0), opposite (the tied components' signs differ)."""
+    patches = [lattice_plane(p, q, 1.0) for p, q in TIED_AXES] + [lattice_plane(p, q, -1.0) for p, q in TIED_AXES] + [lattice_line(p, q) for p, q in TIED_AXES]
+    Y = np.concatenate(patches)
+    m = len(Y)
+    which = (4 * np.arange(EDGE_N)[None, :] + np.arange(EDGE_B)[:, None]) % 9
+    assert {int(w) for w in which[:, EDGE_ROWS].ravel()} == set(range(9))
+    idx = np.array([[_padded_row(np.arange(9) + 9 * which[b, i], i, m) for i in range(EDGE_N)] for b in range(EDGE_B)], np.int64)
+    return _branch_case("sign_ties", np.broadcast_to(Y, (EDGE_B, m, 3)), idx, tied=np.array(TIED_AXES)[which % 3], line=which >= 6,
+                        opposite=(which < 3) | (which >= 6))
+
+
+@functools.lru_cache(maxsize=None)
+def viewpoint_cases(mirror):
+    """A VIEWPOINT EXACTLY IN THE PLANE.  Cloud b is the plane patch of TIED_AXES[b] (mirror: x_p = -x_q); every row keeps the patch's
+    first point as its pivot.  -> four cases over the same rows: "none" (no viewpoint), "in" (v = pivot + 2 e_r + 4 t, t the in-plane
+    lattice direction e_p + sigma e_q: the tied products are s * 4 and -s * 4, exact, so e0 . (v - pivot) is 0 in any order), and
+    "above" / "below" (one lattice step e_p - sigma e_q off the plane on either side)."""
+    sigma = -1.0 if mirror else 1.0
+    Y = np.stack([lattice_plane(p, q, sigma) for p, q in TIED_AXES])
+    idx = np.array([[_padded_row(np.arange(9), i, 9, keep_pivot=True) for i in range(EDGE_N)] for b in range(EDGE_B)], np.int64)
+    inside, off = np.zeros((EDGE_B, 3)), np.zeros((EDGE_B, 3))
+    for b, (p, q) in enumerate(TIED_AXES):
+        inside[b, 3 - p - q], inside[b, p], inside[b, q] = 2, 4, 4 * sigma
+        off[b, p], off[b, q] = 1, -sigma
+    pivot = Y[:, 0].astype(np.float64)
+    views = {"none": None, "in": pivot + inside, "above": pivot + inside + off, "below": pivot + inside - off}
+    tied = np.broadcast_to(np.array(TIED_AXES)[:, None, :], (EDGE_B, EDGE_N, 2))
+    flags = dict(tied=tied, line=np.zeros((EDGE_B, EDGE_N), bool), opposite=np.full((EDGE_B, EDGE_N), not mirror))
+    out = {k: _branch_case("viewpoint %s%s" % (k, ", mirrored" if mirror else ""), Y, idx, v, **flags) for k, v in views.items()}
+    assert all((c["ref64"][4] == pivot[:, None, :]).all() for c in out.values())
     return out

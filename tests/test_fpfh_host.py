@@ -1,6 +1,7 @@
 """fpfh_features and match_features (so3_spfh_f32, so3_fpfh_f32) without a GPU: the boundary (header, binding table, exports, argument
 validation, the Python names), the G32 fixture's own consistency under the margin condition, the kernels' device functions compiled
-for the host (tests/host_model/fpfh.cpp with SO3_HOST_MODEL) on G32, and match_features -- plain torch -- against a brute-force loop.
+for the host (tests/host_model/fpfh.cpp with SO3_HOST_MODEL) on G32 and on the branch cases (exact swap ties, features past the outer
+edges, the weight rule), and match_features -- plain torch -- against a brute-force loop.
 
 Under the margin condition (tests/fpfh_ref.py) pairs and counts are compared EXACTLY with float64, spfh bit for bit with (100 c) / r,
 and fpfh bit for bit with the numpy restatement of its defined order; fpfh against float64 is held to ref.MEASURED here and to 4 x that
@@ -281,6 +282,57 @@ def check_nonfinite_is_contained(label, c, run):
 
 def test_host_model_nonfinite_is_contained(model, g32_cases):
     check_nonfinite_is_contained("host", next(c for c in g32_cases if c["name"] == "nonfinite"), lambda d: host_run(model, d))
+
+
+# ---- where the definition branches exactly (tests/fpfh_ref.py: the branch cases) ------------------------------------------------------
+def check_branch_case(label, c, spfh, pairs, fpfh):
+    """A tie or outer-edge case: pairs and counts EXACTLY the float64 ones, spfh bit-equal to (100 c) / r, fpfh bit-equal to fpfh32.
+    Every comparison is exact; fpfh's distance from float64 is G32's measured figure and is not judged on these inputs."""
+    check_case(label, c, spfh, pairs, fpfh, bound=float("inf"))
+
+
+def check_weight_case(label, c, fpfh):
+    """so3_fpfh_f32 alone from the GIVEN spfh and pairs: bit-equal to fpfh32, which is finite everywhere."""
+    assert fpfh.dtype == np.float32 and fpfh.shape == c["fpfh32"].shape, label
+    assert np.array_equal(bits(fpfh), bits(c["fpfh32"])), (label, np.argwhere(bits(fpfh) != bits(c["fpfh32"]))[:4])
+
+
+def test_branch_cases_reach_their_branches():
+    """The generators assert their premises as they build; what the cases promise the tests is re-asserted here."""
+    assert [1 << int(np.ceil(np.log2(K))) for K in ref.EDGE_KS] == [8, 16, 64]                   # k_spfh<8>, <16>, <64>
+    for K in ref.EDGE_KS:
+        ties, outer = ref.branch_cases(K)
+        for c in (ties, outer):
+            assert (c["b"], c["n"], c["K"]) == (ref.EDGE_B, ref.EDGE_N, K) and c["lengths"].min() < ref.EDGE_N and (c["idx"] == -1).any(), c["name"]
+            live = np.array(ref.EDGE_ROWS)[None, :] < lengths_of(c["lengths"], c["b"], c["n"])[:, None]
+            assert (c["pairs"][:, ref.EDGE_ROWS][live] >= min(K - 2, 2)).all(), c["name"]          # the judged rows hold the branch's pairs
+            assert not ref.undecided(c["f"], c["normals"]).any(), c["name"]
+        assert ref.violations(ties["f"]).sum() >= ties["ties_that_differ"] >= ties["ties"] / 2 > 100   # the margin condition rejects them
+        assert min(outer["beyond"].values()) >= 2 and ref.violations(outer["f"]).sum() >= sum(outer["beyond"].values())
+    w = ref.weight_case()
+    assert 4 <= w["n"] <= 8 and np.isfinite(w["fpfh32"]).all()
+
+
+@pytest.mark.parametrize("K", ref.EDGE_KS)
+def test_host_model_swap_ties_and_outer_edges(model, K):
+    ties, outer = ref.branch_cases(K)
+    for c in (ties, outer):
+        base = host_run(model, c)
+        check_branch_case("host", c, *base)
+        check_power_of_two("host", c, base, lambda d: host_run(model, d))
+    _, _, g, pair = host_spfh(model, ties, features=True)                                         # float32 reaches the branch too: a1 == a2 ...
+    f = ties["f"]
+    assert np.array_equal(pair, f["pair"]) and np.abs(g - f["g"])[pair].max() <= ref.MARGIN / 4
+    _, _, g, pair = host_spfh(model, outer, features=True)                                        # ... and g past the outer edges
+    f = outer["f"]
+    assert np.array_equal(pair, f["pair"])
+    beyond = (f["g"] > ref.BINS + ref.OVERSHOOT) | (f["g"] < -ref.OVERSHOOT)
+    assert (((g > ref.BINS) | (g < 0)) == beyond)[pair].all() and np.abs(g - f["g"])[pair[..., None] & beyond].max() <= ref.OVERSHOOT / 2
+
+
+def test_host_model_weight_rule(model):
+    c = ref.weight_case()
+    check_weight_case("host", c, host_fpfh(model, c, c["spfh"], c["pairs"]))
 
 
 # ---- match_features: plain torch, so it runs here ----------------------------------------------------------------------------

@@ -3,8 +3,8 @@ bit for bit the restatement of its defined order and within 4 x the host model's
 Python surface and through the raw C ABI into pre-filled, guarded buffers -- G32, spfh alone and pairs alone, every group width and N
 around a wave's and a workgroup's queries, B, a batch above the grid cap, int32 and int64 indices and lengths, indices straight from
 knn_points and query_ball_point, idx=None, estimate_normals' normals end to end, the power-of-two property, repeatability, the
-reversed batch, the non-finite cloud, replay from a graph, the moved copy matched by match_features, the warning, the surface's
-errors, and the speed condition against the torch spelling."""
+reversed batch, the non-finite cloud, exact swap ties, features past the outer edges and the weight rule, replay from a graph, the
+moved copy matched by match_features, the warning, the surface's errors, and the speed condition against the torch spelling."""
 import ctypes
 import math
 import warnings
@@ -146,6 +146,35 @@ def test_a_batch_above_the_grid_cap(dev):
     c = {k: (v[sel] if isinstance(v, np.ndarray) else v) for k, v in base.items()}
     c.update(name="beyond the grid", b=b)
     host.check_case("abi", c, *abi_run(c, dev, kernel="k_spfh<8>"))                                  # abi_run asserts so3_last_kernel of both
+
+
+# ---- where the definition branches exactly (tests/fpfh_ref.py: the branch cases) ------------------------------------------------------
+@pytest.mark.parametrize("K", ref.EDGE_KS)
+def test_swap_ties_and_outer_edges(dev, K):
+    """Exact swap ties (no swap) and features past the outer edges (bins 10 and 0), N = 257, B = 3, one ragged cloud, rows padded with
+    -1, in k_spfh<8>, <16> and <64>: exact counts, spfh and fpfh bit for bit, and the same bits at 2^+-20."""
+    for c in ref.branch_cases(K):
+        base = abi_run(c, dev, kernel="k_spfh<%d>" % {5: 8, 16: 16, 33: 64}[K])
+        host.check_branch_case("abi", c, *base)
+        host.check_branch_case("surface", c, *surface_run(c, dev, long=K == 16))
+        host.check_power_of_two("abi", c, base, lambda d: abi_run(d, dev))
+
+
+def test_the_weight_rule_through_the_second_launch_alone(dev):
+    """so3_fpfh_f32 from GIVEN spfh and pairs: a slot with 1 / d2 = inf is skipped, one with w = 2^118 is used; the answer is the same
+    whether the device keeps or flushes the subnormal d2."""
+    from poseestimation_amd import _lib
+    lib = _lib.load()
+    c = ref.weight_case()
+    b, n, K = c["b"], c["n"], c["K"]
+    Xd, id_, sd, pd = to_device(c["X"], dev), to_device(c["idx"], dev, np.int32), to_device(c["spfh"], dev), to_device(c["pairs"], dev, np.int32)
+    whole, f = guarded((b, n, ref.SLOTS), float("nan"), torch.float32, dev)
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _lib.check(lib.so3_fpfh_f32(ptr(Xd), ptr(id_), None, ptr(sd), ptr(pd), ptr(f), K, b, n, st), "so3_fpfh_f32")
+    assert last_kernel() == "k_fpfh"
+    torch.cuda.synchronize()
+    assert guards_intact(whole, float("nan")), "a guard was written"
+    host.check_weight_case("abi", c, f.cpu().numpy())
 
 
 # ---- indices from the library's own searches -------------------------------------------------------------------------------------

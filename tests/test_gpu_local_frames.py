@@ -2,8 +2,8 @@
 stage under its judges, through the Python surface and through the raw C ABI into NaN-pre-filled, guarded buffers -- G29, every
 launch geometry (K, N around a wave's and a workgroup's queries, B, a batch above the grid cap), each optional output left out, a
 shared cloud, int32 and int64 indices and lengths, indices straight from knn_points, knn_group's search and query_ball_point, the
-power-of-two property, repeatability, the reversed batch, a NaN cloud, replay from a graph, estimate_normals, the warning, the surface's
-errors, and the speed condition against the torch spelling."""
+power-of-two property, repeatability, the reversed batch, a NaN cloud, sign ties and a viewpoint exactly in the plane,
+replay from a graph, estimate_normals, the warning, the surface's errors, and the speed condition against the torch spelling."""
 import ctypes
 import warnings
 
@@ -132,6 +132,27 @@ def test_a_shared_cloud_is_the_expanded_one(dev):
     expanded = abi_run(c, dev)
     host.check_case("expanded", c, expanded)
     assert same_bits(abi_run(c, dev, shared=True), expanded) and same_bits(surface_run(c, dev, shared=True), expanded)
+
+
+# ---- where the sign rules branch exactly (tests/local_frames_ref.py: the branch cases) -------------------------------------------------
+def test_sign_ties_the_lowest_index_decides(dev):
+    """Lattice patches on the planes x_p = +-x_q and along e_p - e_q: the tied components are bit-equal in magnitude and the lower index
+    is positive -- N = 257, B = 3, K = 9 of 16 slots, each optional output left out once, the shared cloud, the surface, 2^+-20."""
+    c = ref.sign_tie_case()
+    base = host.check_left_out_and_shared("abi", c, lambda d, want, shared: abi_run(d, dev, want, shared))
+    host.check_sign_ties("abi", c, base)
+    host.check_sign_ties("surface", c, surface_run(c, dev))
+    assert same_bits(surface_run(c, dev, long=True, shared=True), base)
+    host.check_power_of_two("abi", c, base, lambda d: abi_run(d, dev))
+
+
+@pytest.mark.parametrize("mirror", [False, True])
+def test_a_viewpoint_exactly_in_the_plane_keeps_the_sign(dev, mirror):
+    cases = ref.viewpoint_cases(mirror)
+    host.check_viewpoint_in_the_plane("abi", cases, lambda c: abi_run(c, dev))
+    host.check_viewpoint_in_the_plane("surface", cases, lambda c: surface_run(c, dev, long=mirror))
+    for k in ("in", "below"):
+        host.check_power_of_two("abi", cases[k], abi_run(cases[k], dev), lambda d: abi_run(d, dev))
 
 
 # ---- indices from the library's own searches -------------------------------------------------------------------------------------

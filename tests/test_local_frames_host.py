@@ -1,6 +1,6 @@
 """local_frames and estimate_normals (so3_local_frames_f32) without a GPU: the boundary (header, binding table, exports, argument
 validation, the Python names), the G29 fixture's own consistency under the judges, and the kernel's device functions compiled for the
-host (tests/host_model/local_frames.cpp with SO3_HOST_MODEL) on G29.
+host (tests/host_model/local_frames.cpp with SO3_HOST_MODEL) on G29 and on the branch cases (sign ties, a viewpoint exactly in the plane).
 
 The covariance is a definition (include/so3proj.h), so it is compared EXACTLY with the numpy restatement (tests/local_frames_ref.py:
 cov32).  The eigen stage is judged by bounds whose constants are 4 x what the host model reaches here: the model itself is held to the
@@ -167,6 +167,63 @@ def check_power_of_two(label, c, base, run, e=20):
         assert np.array_equal(bits(nrm), bits(base[2])) and np.array_equal(bits(frm), bits(base[3])), (label, c["name"], ee, "frames")
 
 
+# ---- where the sign rules branch exactly (tests/local_frames_ref.py: the branch cases) -------------------------------------------------
+def flipped(a):
+    """The bits of -a."""
+    return bits(a) ^ np.uint32(0x80000000)
+
+
+def check_sign_ties(label, c, outs):
+    """The existing judges, and on every row the tied vector (e0 of a plane, e2 of a line): its two tied components bit-equal in
+    magnitude (the premise, asserted on the output), the lower-indexed one positive, the other one's sign the patch's, the third
+    component a zero.  With a viewpoint e0's own sign is the caller's to judge (check_viewpoint_in_the_plane)."""
+    got = check_case(label, c, outs)
+    cov, lam, nrm, frm = outs
+    what = (label, c["name"])
+    E = None if frm is None else frm.reshape(frm.shape[:2] + (3, 3))
+    e0, e2 = (None, None) if E is None else (E[..., :, 0], E[..., :, 2])
+    for vec, rows, is_e0 in ((nrm, ~c["line"], True), (e0, ~c["line"], True), (e2, c["line"], False)):
+        if vec is None or not rows.any():
+            continue
+        p, q = c["tied"][..., :1], c["tied"][..., 1:]
+        vp, vq, vr = (np.take_along_axis(vec, a, -1)[..., 0][rows] for a in (p, q, 3 - p - q))
+        assert np.array_equal(bits(np.abs(vp)), bits(np.abs(vq))) and (np.abs(vp) > 0.7).all(), (what, "the tied components are no tie")
+        assert (vr == 0).all(), what
+        if c["viewpoint"] is None or not is_e0:
+            assert (vp > 0).all(), (what, "the lowest index decides")
+        assert ((vp > 0) != (vq > 0))[c["opposite"][rows]].all() and ((vp > 0) == (vq > 0))[~c["opposite"][rows]].all(), what
+    return got
+
+
+def check_viewpoint_in_the_plane(label, cases, run):
+    """cases: ref.viewpoint_cases(...); run(case) -> (cov, eigenvalues, normals, frames).  A viewpoint exactly in the plane keeps the
+    normal the call without one gives, bit for bit; one lattice step off the plane on either side gives the two opposite signs."""
+    outs = {k: run(c) for k, c in cases.items()}
+    for k, c in cases.items():
+        check_sign_ties(label, c, outs[k])
+    none = outs["none"]
+    for k in ("in", "above"):
+        assert all(np.array_equal(bits(u), bits(v)) for u, v in zip(outs[k], none)), (label, k, "exactly 0 keeps the sign")
+    cov, lam, nrm, frm = outs["below"]
+    assert np.array_equal(bits(cov), bits(none[0])) and np.array_equal(bits(lam), bits(none[1])), label
+    assert np.array_equal(bits(nrm), flipped(none[2])), (label, "below the plane: the other sign")
+    f, f0 = frm.reshape(frm.shape[:2] + (3, 3)), none[3].reshape(frm.shape[:2] + (3, 3))
+    assert np.array_equal(bits(f[..., :, 0]), flipped(f0[..., :, 0])) and np.array_equal(bits(f[..., :, 2]), bits(f0[..., :, 2])), label
+    assert np.array_equal(f[..., :, 1], -f0[..., :, 1]), label                                   # e1 = e2 x e0 turns with e0 (zeros may keep their sign)
+
+
+def check_left_out_and_shared(label, c, run):
+    """run(case, want, shared) -> the outputs.  Each optional output left out once, and the shared cloud once: the same bits."""
+    full = run(c, (True, True, True, True), False)
+    for drop in range(4):
+        want = tuple(k != drop for k in range(4))
+        got = run(c, want, False)
+        assert all((g is None and not w) or (w and np.array_equal(bits(g), bits(f))) for g, f, w in zip(got, full, want)), (label, drop)
+        check_sign_ties(label, c, got)
+    assert all(np.array_equal(bits(g), bits(f)) for g, f in zip(run(c, (True, True, True, True), True), full)), (label, "shared")
+    return full
+
+
 # ---- the device functions on the host --------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def model(tmp_path_factory):
@@ -176,12 +233,14 @@ def model(tmp_path_factory):
     return lib
 
 
-def host_run(model, c, sweeps=SWEEPS, want=(True, True, True, True)):
+def host_run(model, c, sweeps=SWEEPS, want=(True, True, True, True), shared=False):
+    """shared: the first cloud alone with y_stride 0."""
     b, n, m, K = c["b"], c["n"], c["m"], c["K"]
-    Y, idx = np.ascontiguousarray(c["Y"], np.float32), np.ascontiguousarray(c["idx"], np.int32)
+    Y, idx = np.ascontiguousarray(c["Y"][0] if shared else c["Y"], np.float32), np.ascontiguousarray(c["idx"], np.int32)
     xl, yl, view = (None if c[k] is None else np.ascontiguousarray(c[k], t) for k, t in (("x_lengths", np.int32), ("y_lengths", np.int32), ("viewpoint", np.float32)))
     outs = [np.full((b, n, w), np.nan, np.float32) if flag else None for flag, w in zip(want, (6, 3, 3, 9))]
-    assert model.model_local_frames(np_ptr(Y), 3 * m, np_ptr(idx), np_ptr(xl), np_ptr(yl), np_ptr(view), *(np_ptr(o) for o in outs), K, b, n, m, sweeps) == 0
+    stride = 0 if shared else 3 * m
+    assert model.model_local_frames(np_ptr(Y), stride, np_ptr(idx), np_ptr(xl), np_ptr(yl), np_ptr(view), *(np_ptr(o) for o in outs), K, b, n, m, sweeps) == 0
     return tuple(outs)
 
 
@@ -212,3 +271,22 @@ def test_host_model_power_of_two(model, g29_cases):
     for c in g29_cases:
         if c["family"] in ("sphere", "plane", "lattice_plane", "tied", "flat", "mixed", "ragged", "view") and c["n"] <= 257:
             check_power_of_two("host", c, host_run(model, c), lambda d: host_run(model, d))
+
+
+def test_host_model_sign_ties(model):
+    c = ref.sign_tie_case()
+    assert (np.diff(c["Y"], axis=0) == 0).all() and {-1, c["m"], ref.INT32_MIN} <= set(np.unique(c["idx"]).tolist())
+    base = check_left_out_and_shared("host", c, lambda d, want, shared: host_run(model, d, want=want, shared=shared))
+    check_sign_ties("host", c, base)
+    check_power_of_two("host", c, base, lambda d: host_run(model, d))
+    y_eq_z = np.argwhere((c["tied"] == (1, 2)).all(-1) & c["opposite"] & ~c["line"])[0]          # the plane y = z: e0 = (+-0, s, -s), lambda = (0, 4/3, 8/3)
+    assert np.array_equal(np.abs(base[2][tuple(y_eq_z)]), np.float32([0, np.sqrt(0.5), np.sqrt(0.5)])) and base[2][tuple(y_eq_z)][2] < 0
+    assert np.array_equal(base[1][tuple(y_eq_z)], np.float32([0, 4 / 3, 8 / 3]))
+
+
+@pytest.mark.parametrize("mirror", [False, True])
+def test_host_model_viewpoint_in_the_plane(model, mirror):
+    cases = ref.viewpoint_cases(mirror)
+    check_viewpoint_in_the_plane("host", cases, lambda c: host_run(model, c))
+    for k in ("in", "below"):
+        check_power_of_two("host", cases[k], host_run(model, cases[k]), lambda d: host_run(model, d))

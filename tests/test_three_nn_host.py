@@ -74,6 +74,18 @@ def nn_shape_cases():
 
 
 @functools.lru_cache(maxsize=None)
+def nn_nonfinite_cases():
+    """Dicts (name, xyz1, xyz2) with NaN and infinite coordinates: the clouds of the device's test_non_finite_coordinates_keep_indices
+    _in_range.  A NaN or +inf d fails every <, so a list may end without a candidate; what is written is unspecified but every index
+    stays in [0, S) -- three_nn_finish's clamp.  Judged by check_nn_in_range, not by the restatement."""
+    rng = np.random.default_rng(2404)
+    xyz1, xyz2 = rng.uniform(0, 1, (2, 300, 3)).astype(np.float32), rng.uniform(0, 1, (2, 70, 3)).astype(np.float32)
+    xyz1[0, 5, 0], xyz1[1, 0, 1], xyz2[0, 7, 2], xyz2[1, 0, 0], xyz2[1, 69, 1] = np.nan, np.inf, np.inf, np.nan, -np.inf
+    return [{"name": "non-finite S=70", "xyz1": xyz1, "xyz2": xyz2}, {"name": "non-finite S=2", "xyz1": xyz1, "xyz2": xyz2[:, :2].copy()},
+            {"name": "an all-NaN known cloud S=5", "xyz1": xyz1, "xyz2": np.full((2, 5, 3), np.nan, np.float32)}]
+
+
+@functools.lru_cache(maxsize=None)
 def nn_expected():
     return [ref.three_nn(c["xyz1"], c["xyz2"]) for c in nn_shape_cases()]
 
@@ -245,6 +257,18 @@ def check_nn(name, run_nn, xyz1, xyz2, want=None):
     return d3, idx, w
 
 
+def check_nn_in_range(name, run_nn, xyz1, xyz2):
+    """Non-finite coordinates: every index stays in [0, S), with and without weights; the rows they do not reach equal the restatement."""
+    s = xyz2.shape[1]
+    for want_weight in (True, False):
+        got_d, got_i, _ = run_nn(xyz1, xyz2, want_weight)
+        got_i = np.asarray(got_i, np.int64)
+        assert got_i.shape == xyz1.shape[:2] + (3,) and got_i.min() >= 0 and got_i.max() < s, (name, got_i.min(), got_i.max())
+        clean = np.isfinite(xyz1).all(-1) & np.isfinite(xyz2).all((-1, -2))[:, None]
+        d3, idx, _ = ref.three_nn(np.where(np.isfinite(xyz1), xyz1, 0), np.where(np.isfinite(xyz2), xyz2, 0))
+        assert np.array_equal(got_i[clean], idx[clean]) and np.array_equal(np.asarray(got_d)[clean].view(np.uint32), d3[clean].view(np.uint32)), name
+
+
 def expected32(c):
     """(out, grad_feat) of an interpolation case in the DEFINED float32 order, channel-last; the other layout is their transpose (the
     arithmetic of an element does not depend on the layout)."""
@@ -359,6 +383,15 @@ def test_host_model_equals_the_restatement_however_the_scan_is_split(model):
             check_nn(c["name"], lambda a, k, wt: model_nn(model, a, k, wt, slices), c["xyz1"], c["xyz2"], want)
         b, n, s = c["xyz1"].shape[0], c["xyz1"].shape[1], c["xyz2"].shape[1]
         assert model.model_three_nn_waves_per_point(b, n, s) == waves_per_point(b, n, s), c["name"]
+
+
+def test_host_model_non_finite_coordinates_keep_indices_in_range(model):
+    seen = 0
+    for c in nn_nonfinite_cases():
+        for slices in (1, 2, 4):
+            check_nn_in_range(c["name"], lambda a, k, wt: model_nn(model, a, k, wt, slices), c["xyz1"], c["xyz2"])
+        seen += int((~np.isfinite(c["xyz1"]).all(-1) | np.isnan(c["xyz2"]).all((-1, -2))[:, None]).sum())
+    assert seen >= 600                                                                   # rows whose list ends without a candidate
 
 
 def test_host_model_interpolation_and_backward_on_the_shape_lists(model):
