@@ -1495,6 +1495,9 @@ typedef __attribute__((address_space(3))) f32x4 lds_f32x4;
 // k_chamfer_fwd<., 4> gets the registers of two slots exchanged and its pair loop scheduled around them.
 // k_icp_step and k_three_nn keep this loop written out: called from them, the helper leaves k_icp_step<false, false, false, 4> with an
 // s_nop inside the pair loop and k_three_nn with its selects in another order (profiles/tile_search_refactor_isa.txt).
+// Who uses what: tile_search -- k_add_s, k_icp_plane_step, chamfer_search (both Chamfer forwards); item_record -- k_icp_step,
+// k_icp_plane_step, chamfer_search; owner_scan -- k_chamfer_bwd, k_chamfer_normals_bwd, k_knn_bwd's dY; two_way_item -- chamfer_search,
+// k_chamfer_bwd, k_chamfer_normals_bwd; record_sum / pose_entry / store_pose -- both ICP finish kernels (profiles/cloud_skeletons_isa.txt).
 template <bool WANT_INDEX, bool DIAMETER, int U, class Fetch>
 __device__ __forceinline__ void tile_search(float4 *tile, int tid, int len, Fetch fetch, const float (&x)[U], const float (&y)[U], const float (&z)[U],
                                             float (&best)[U], int (&idx)[U]) {
@@ -1895,6 +1898,31 @@ __global__ __launch_bounds__(kBlock) void k_icp_step(const float *__restrict__ P
     }
 }
 
+// What the finish kernels of both ICPs share.  record_sum: lane k < W adds entry k of a cloud's records in chunk order (the other lanes
+// keep 0).  pose_entry: entry k of the (3,4) pose a cloud starts an iteration from -- prev == nullptr is the identity.  store_pose:
+// lanes 0..11 each hold one entry of the new pose, write it to next (when given) and scatter it to the caller's R | T (when given).
+template <int W> __device__ __forceinline__ float record_sum(const float *r, int lane, int chunks) {
+    float v = 0.f;
+    if (lane < W) {
+        for (int c = 0; c < chunks; ++c) v += r[c * W + lane];
+    }
+    return v;
+}
+__device__ __forceinline__ float pose_entry(const float *prev, int64_t at, int k) { return prev != nullptr ? prev[at] : ((k % 5) == 0 ? 1.f : 0.f); }
+__device__ __forceinline__ void scatter_pose(float *R, float *T, int64_t b, int k, float v) {
+    const int c = k >> 2, j = k & 3;
+    if (j < 3) R[b * 9 + 3 * c + j] = v; else T[b * 3 + c] = v;
+}
+__device__ __forceinline__ void store_pose(int lane, const float (&mn)[12], float *next, float *R, float *T, int64_t b) {
+    float out = 0.f;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) out = lane == k ? mn[k] : out;
+    if (lane < 12) {
+        next[b * 12 + lane] = out;
+        if (R != nullptr) scatter_pose(R, T, b, lane, out);
+    }
+}
+
 // One wave per cloud.  Lane k < kIcpRecord adds entry k of the cloud's records in chunk order; the sums are then broadcast and every
 // lane finishes the same cloud (icp_finish: align_finish, the projection, align_translation), lane 0..11 write the next pose.
 // prev == nullptr: the iteration started from the identity.  R, t (the caller's results) are written when given: the last iteration.
@@ -1906,29 +1934,16 @@ __global__ __launch_bounds__(kBlock) void k_icp_finish(const float *__restrict__
     const int64_t wave = static_cast<int64_t>(blockIdx.x) * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t nwaves = static_cast<int64_t>(gridDim.x) * (kBlock / 64);
     for (int64_t b = wave; b < B; b += nwaves) {
-        const float *r = rec + b * chunks * so3::kIcpRecord;
-        float v = 0.f;
-        if (lane < so3::kIcpRecord) {
-            for (int c = 0; c < chunks; ++c) v += r[c * so3::kIcpRecord + lane];
-        }
+        const float v = record_sum<so3::kIcpRecord>(rec + b * chunks * so3::kIcpRecord, lane, chunks);
         float s[so3::kIcpSums], p0[3], q0[3], mp[12], mn[12], e, cnt;
 #pragma unroll
         for (int k = 0; k < so3::kIcpSums; ++k) s[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k));
 #pragma unroll
         for (int k = 0; k < 3; ++k) { p0[k] = P[b * N * 3 + k]; q0[k] = Q[b * q_stride + k]; }
 #pragma unroll
-        for (int k = 0; k < 12; ++k) mp[k] = prev != nullptr ? prev[b * 12 + k] : ((k % 5) == 0 ? 1.f : 0.f);
+        for (int k = 0; k < 12; ++k) mp[k] = pose_entry(prev, b * 12 + k, k);
         so3::icp_finish(s, p0, q0, mp, mn, e, cnt);
-        float out = 0.f;
-#pragma unroll
-        for (int k = 0; k < 12; ++k) out = lane == k ? mn[k] : out;
-        if (lane < 12) {
-            next[b * 12 + lane] = out;
-            if (R != nullptr) {
-                const int c = lane >> 2, k = lane & 3;
-                if (k < 3) R[b * 9 + 3 * c + k] = out; else T[b * 3 + c] = out;
-            }
-        }
+        store_pose(lane, mn, next, R, T, b);
         if (lane == 0) {
             if (rmse != nullptr) rmse[b] = e;
             if (inliers != nullptr) inliers[b] = static_cast<int32_t>(cnt);
@@ -1941,9 +1956,8 @@ __global__ __launch_bounds__(kBlock) void k_icp_initial_pose(const float *__rest
     const int64_t e = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
     if (e >= B * 12) return;
     const int64_t b = e / 12;
-    const int k = static_cast<int>(e - b * 12), c = k >> 2, j = k & 3;
-    const float v = init != nullptr ? init[e] : ((k % 5) == 0 ? 1.f : 0.f);
-    if (j < 3) R[b * 9 + 3 * c + j] = v; else T[b * 3 + c] = v;
+    const int k = static_cast<int>(e - b * 12);
+    scatter_pose(R, T, b, k, pose_entry(init, e, k));
 }
 
 // ---- point-to-plane ICP: k_icp_step's search, then the 31 sums of the Gauss-Newton system over the target's normals ----------------
@@ -1952,6 +1966,8 @@ __global__ __launch_bounds__(kBlock) void k_icp_initial_pose(const float *__rest
 // (12 B each, L2 hits) and REUSES the posed x_i the search kept: 3 U registers stay live past the loop instead of 3 reloads and 9 FMAs
 // per point, and x_i - c, x_i - q_j are then formed from the very bits the search compared.  c = the posed p_0, wave-uniform.
 // wave_allsum per sum, item_record<32> through the tile: one record per work item in rec[b][chunk][.], no atomics.
+// It shares no helper with k_icp_step: a common prologue (pose load, U posed points) flipped the polarity of every k_icp_step's
+// pose != nullptr branches, a common epilogue (wave_allsum per sum, item_record) rescheduled 800-1400 lines of this kernel.
 template <bool WEIGHTED, bool TRIMMED, int U>
 __global__ __launch_bounds__(kBlock) void k_icp_plane_step(const float *__restrict__ P, const float *__restrict__ Q,
                                                            const float *__restrict__ Nrm, int64_t q_stride, const float *__restrict__ Wt,
@@ -2026,31 +2042,18 @@ __global__ __launch_bounds__(kBlock) void k_icp_plane_finish(const float *__rest
     const int64_t wave = static_cast<int64_t>(blockIdx.x) * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t nwaves = static_cast<int64_t>(gridDim.x) * (kBlock / 64);
     for (int64_t b = wave; b < B; b += nwaves) {
-        const float *r = rec + b * chunks * so3::kPlaneRecord;
-        float v = 0.f;
-        if (lane < so3::kPlaneRecord) {
-            for (int c = 0; c < chunks; ++c) v += r[c * so3::kPlaneRecord + lane];
-        }
+        const float v = record_sum<so3::kPlaneRecord>(rec + b * chunks * so3::kPlaneRecord, lane, chunks);
         float s[so3::kPlaneSums], c[3], mp[12], mn[12], e, ep, cnt;
         bool ok;
 #pragma unroll
         for (int k = 0; k < so3::kPlaneSums; ++k) s[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k));
 #pragma unroll
-        for (int k = 0; k < 12; ++k) mp[k] = prev != nullptr ? prev[b * 12 + k] : ((k % 5) == 0 ? 1.f : 0.f);
+        for (int k = 0; k < 12; ++k) mp[k] = pose_entry(prev, b * 12 + k, k);
 #pragma unroll
         for (int k = 0; k < 3; ++k) c[k] = P[b * N * 3 + k];
         if (prev != nullptr) so3::pose_point(mp, P[b * N * 3 + 0], P[b * N * 3 + 1], P[b * N * 3 + 2], c[0], c[1], c[2]);
         so3::plane_finish(s, c, mp, damping, mn, e, ep, cnt, ok);
-        float out = 0.f;
-#pragma unroll
-        for (int k = 0; k < 12; ++k) out = lane == k ? mn[k] : out;
-        if (lane < 12) {
-            next[b * 12 + lane] = out;
-            if (R != nullptr) {
-                const int cc = lane >> 2, k = lane & 3;
-                if (k < 3) R[b * 9 + 3 * cc + k] = out; else T[b * 3 + cc] = out;
-            }
-        }
+        store_pose(lane, mn, next, R, T, b);
         if (lane == 0) {
             if (rmse != nullptr) rmse[b] = e;
             if (rmse_point != nullptr) rmse_point[b] = ep;
@@ -2067,25 +2070,53 @@ __global__ __launch_bounds__(kBlock) void k_icp_plane_finish(const float *__rest
 // past the source's length read dist 0 and nearest -1.  A work item leaves the sum of its points' terms in rec[item]: lane-wise in
 // slot order, wave_allsum, item_record.  k_chamfer_rows adds a cloud's records in chunk order in float64 and WRITES rows (B,2) = the
 // two directions' means.  No atomics, no zero-fill.
-template <bool SQUARED, int U>
-__global__ __launch_bounds__(kBlock) void k_chamfer_fwd(const float *__restrict__ X, const float *__restrict__ Y, const int32_t *__restrict__ x_len,
-                                                        const int32_t *__restrict__ y_len, float *__restrict__ dist_x, int32_t *__restrict__ nearest_x,
-                                                        float *__restrict__ dist_y, int32_t *__restrict__ nearest_y, float *__restrict__ rec,
-                                                        int64_t B, int32_t N, int32_t M, int32_t chunks_x, int32_t chunks_y) {
+//
+// One work item of a two-direction kernel (the Chamfer forwards, the gather backwards): of a cloud's chunks_x + chunks_y items the
+// first chunks_x serve the x direction -- X's points search or own, Y's are searched or hit -- the others the y direction (rev: the
+// roles exchanged).  two_way_lengths reads the cloud's ragged lengths, wave-uniform scalar loads; the gather backwards call it after
+// their early exit.
+struct TwoWayItem {
+    int64_t b;
+    bool rev;
+    int chunk;                                   // within its direction
+    int32_t full, qfull, len_p, len_q;           // the own and the other cloud's padded extents and live lengths
+};
+__device__ __forceinline__ TwoWayItem two_way_item(int64_t item, int per, int32_t chunks_x, int32_t N, int32_t M) {
+    TwoWayItem it;
+    it.b = item / per;
+    const int c = static_cast<int>(item - it.b * per);
+    it.rev = c >= chunks_x;
+    it.chunk = it.rev ? c - chunks_x : c;
+    it.full = it.rev ? M : N; it.qfull = it.rev ? N : M;
+    return it;
+}
+__device__ __forceinline__ void two_way_lengths(TwoWayItem &it, const int32_t *x_len, const int32_t *y_len, int32_t N, int32_t M) {
+    const int32_t nb = so3::chamfer_length(x_len, it.b, N), mb = so3::chamfer_length(y_len, it.b, M);
+    it.len_p = it.rev ? mb : nb; it.len_q = it.rev ? nb : mb;
+}
+
+// The work-item loop of both Chamfer forwards.  NORMALS adds k_chamfer_normals_fwd's epilogue per kept slot and a second lane sum; the
+// record is then two floats (sum of e, sum of t), item_record<2>, whose entry 0 adds the waves' sums in item_record<1>'s order.
+template <bool SQUARED, int U, bool NORMALS>
+__device__ __forceinline__ void chamfer_search(float4 *tile, const float *X, const float *Y, const float *NX, const float *NY, const int32_t *x_len,
+                                               const int32_t *y_len, float *dist_x, int32_t *nearest_x, float *dist_y, int32_t *nearest_y,
+                                               float *term_x, float *term_y, float *rec, int32_t signed_cos, int64_t B, int32_t N, int32_t M,
+                                               int32_t chunks_x, int32_t chunks_y) {
     static_assert(kBlock == so3::kIcpBlock, "the host model's chunking");
-    __shared__ float4 tile[kAddsTile];
+    constexpr int W = NORMALS ? 2 : 1;
     const int tid = threadIdx.x;
     const int per = chunks_x + chunks_y;
     const int64_t items = B * per;
     for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
-        const int64_t b = item / per;
-        const int c = static_cast<int>(item - b * per);
-        const bool rev = c >= chunks_x;                              // the y direction: Y's points search X
-        const int i_base = (rev ? c - chunks_x : c) * (kBlock * U);
-        const int32_t nb = so3::chamfer_length(x_len, b, N), mb = so3::chamfer_length(y_len, b, M);
-        const int32_t full = rev ? M : N, len_p = rev ? mb : nb, len_q = rev ? nb : mb;
+        TwoWayItem it = two_way_item(item, per, chunks_x, N, M);     // rev, the y direction: Y's points search X
+        two_way_lengths(it, x_len, y_len, N, M);
+        const int64_t b = it.b;
+        const bool rev = it.rev;
+        const int i_base = it.chunk * (kBlock * U);
+        const int32_t full = it.full, len_p = it.len_p, len_q = it.len_q;
         const float *src = rev ? Y + b * M * 3 : X + b * N * 3, *tgt = rev ? X + b * N * 3 : Y + b * M * 3;
-        float *dist = rev ? dist_y : dist_x;
+        const float *own = rev ? NY + b * M * 3 : NX + b * N * 3, *other = rev ? NX + b * N * 3 : NY + b * M * 3;      // NORMALS
+        float *dist = rev ? dist_y : dist_x, *term = rev ? term_y : term_x;
         int32_t *nearest = rev ? nearest_y : nearest_x;
         const bool live = len_q > 0 && i_base < len_p;              // the same in every lane of the workgroup
         float x[U], y[U], z[U], best[U];
@@ -2101,20 +2132,67 @@ __global__ __launch_bounds__(kBlock) void k_chamfer_fwd(const float *__restrict_
             }
             tile_search<true, false>(tile, tid, len_q, [=](int j) { return tile_point(tgt, j); }, x, y, z, best, idx);
         }
-        float mine = 0.f;
+        float mine = 0.f, mine_n = 0.f;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int i = i_base + u * kBlock + tid;
             const bool valid = live && i < len_p;
             const float e = valid ? so3::chamfer_term<SQUARED>(best[u]) : 0.f;
             mine += e;
+            float t = 0.f;
+            if (NORMALS && live) {                                   // both indices clamped into the live part before they address anything
+                const int ic = min(i, len_p - 1), j = min(max(idx[u], 0), len_q - 1);
+                const float tt = so3::chamfer_normal_term(own[ic * 3 + 0], own[ic * 3 + 1], own[ic * 3 + 2], other[j * 3 + 0], other[j * 3 + 1],
+                                                          other[j * 3 + 2], signed_cos != 0);
+                t = valid ? tt : 0.f;
+            }
+            mine_n += t;
             if (i < full) {
                 if (dist != nullptr) dist[b * full + i] = e;
                 if (nearest != nullptr) nearest[b * full + i] = valid ? min(idx[u], len_q - 1) : -1;
+                if (NORMALS && term != nullptr) term[b * full + i] = t;
             }
         }
-        item_record<1>(tile, tid, wave_allsum(mine), rec + item);
+        float sum = wave_allsum(mine);                               // every lane runs both butterflies
+        if (NORMALS) { const float sum_t = wave_allsum(mine_n); sum = (tid & 63) == 0 ? sum : sum_t; }
+        item_record<W>(tile, tid, sum, rec + item * W);
     }
+}
+
+// The rows of both forwards, W floats per record: a thread per (cloud, direction) adds each of the W entries of the cloud's records in
+// chunk order in float64, divides by the length and writes rows[w][2 b + direction].
+template <int W>
+__device__ __forceinline__ void chamfer_rows(const float *rec, const int32_t *x_len, const int32_t *y_len, float *const (&rows)[W], int64_t B,
+                                             int32_t N, int32_t M, int32_t chunks_x, int32_t chunks_y) {
+    const int per = chunks_x + chunks_y;
+    for (int64_t t = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; t < 2 * B; t += static_cast<int64_t>(gridDim.x) * kBlock) {
+        const int64_t b = t >> 1;
+        const bool rev = (t & 1) != 0;
+        const int32_t nb = so3::chamfer_length(x_len, b, N), mb = so3::chamfer_length(y_len, b, M);
+        const float *r = rec + (b * per + (rev ? chunks_x : 0)) * W;
+        const int chunks = rev ? chunks_y : chunks_x;
+        double acc[W];
+#pragma unroll
+        for (int w = 0; w < W; ++w) acc[w] = 0.0;
+        for (int c = 0; c < chunks; ++c) {
+#pragma unroll
+            for (int w = 0; w < W; ++w) acc[w] += static_cast<double>(r[c * W + w]);
+        }
+        const bool scored = nb > 0 && mb > 0 && chunks > 0;
+        const double len = static_cast<double>(rev ? mb : nb);
+#pragma unroll
+        for (int w = 0; w < W; ++w) rows[w][t] = scored ? static_cast<float>(acc[w] / len) : 0.f;
+    }
+}
+
+template <bool SQUARED, int U>
+__global__ __launch_bounds__(kBlock) void k_chamfer_fwd(const float *__restrict__ X, const float *__restrict__ Y, const int32_t *__restrict__ x_len,
+                                                        const int32_t *__restrict__ y_len, float *__restrict__ dist_x, int32_t *__restrict__ nearest_x,
+                                                        float *__restrict__ dist_y, int32_t *__restrict__ nearest_y, float *__restrict__ rec,
+                                                        int64_t B, int32_t N, int32_t M, int32_t chunks_x, int32_t chunks_y) {
+    __shared__ float4 tile[kAddsTile];
+    chamfer_search<SQUARED, U, false>(tile, X, Y, nullptr, nullptr, x_len, y_len, dist_x, nearest_x, dist_y, nearest_y, nullptr, nullptr, rec, 0, B,
+                                      N, M, chunks_x, chunks_y);
 }
 
 // rows[b] = (cham_x, cham_y): a thread per (cloud, direction) adds the records in chunk order in float64 and divides by the length.
@@ -2122,17 +2200,8 @@ __global__ __launch_bounds__(kBlock) void k_chamfer_fwd(const float *__restrict_
 __global__ __launch_bounds__(kBlock) void k_chamfer_rows(const float *__restrict__ rec, const int32_t *__restrict__ x_len,
                                                          const int32_t *__restrict__ y_len, float *__restrict__ rows, int64_t B, int32_t N, int32_t M,
                                                          int32_t chunks_x, int32_t chunks_y) {
-    const int per = chunks_x + chunks_y;
-    for (int64_t t = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; t < 2 * B; t += static_cast<int64_t>(gridDim.x) * kBlock) {
-        const int64_t b = t >> 1;
-        const bool rev = (t & 1) != 0;
-        const int32_t nb = so3::chamfer_length(x_len, b, N), mb = so3::chamfer_length(y_len, b, M);
-        const float *r = rec + b * per + (rev ? chunks_x : 0);
-        const int chunks = rev ? chunks_y : chunks_x;
-        double acc = 0.0;
-        for (int c = 0; c < chunks; ++c) acc += static_cast<double>(r[c]);
-        rows[t] = (nb > 0 && mb > 0 && chunks > 0) ? static_cast<float>(acc / static_cast<double>(rev ? mb : nb)) : 0.f;
-    }
+    float *const out[1] = {rows};
+    chamfer_rows<1>(rec, x_len, y_len, out, B, N, M, chunks_x, chunks_y);
 }
 
 // The owner scan of the gather backwards (k_chamfer_bwd, k_knn_bwd's dY).  A wave owns `owners` <= 64 consecutive points from
@@ -2181,6 +2250,10 @@ __device__ __forceinline__ void owner_scan(int lane, int first, unsigned owners,
     acc[0] = a[0]; acc[1] = a[1]; acc[2] = a[2];
 }
 
+// The three gather backwards (k_chamfer_bwd, k_chamfer_normals_bwd, k_knn_bwd) keep their frame written out.  One frame taking the
+// kernel's chain as a callable (own term, then owner_scan) was tried with the decode as a struct, as plain locals, by value and by
+// reference, its lambdas forced inline: every spelling left the three with one or three SGPRs fewer or more, the scan blocks' eight
+// e < entries compares signed where they were unsigned and k_knn_bwd 16 instructions longer (profiles/cloud_skeletons_isa.txt).
 // k_chamfer_bwd: both gradients as a gather.  A wave owns kChamferOwners = 64 consecutive points of one cloud, one per lane, and a
 // work item is the four waves' 256 points; the items of dX come first, then dY's, as in k_chamfer_fwd.  A lane opens its chain with
 // its own term (its neighbour's 12 bytes gathered from L2).  The wave then takes the OTHER direction's `nearest` through owner_scan:
@@ -2198,15 +2271,15 @@ __global__ __launch_bounds__(kBlock) void k_chamfer_bwd(const float *__restrict_
     const int per = chunks_x + chunks_y;
     const int64_t items = B * per;
     for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
-        const int64_t b = item / per;
-        const int c = static_cast<int>(item - b * per);
-        const bool rev = c >= chunks_x;                              // dY: Y's points own, X's points hit
-        const int32_t full = rev ? M : N, qfull = rev ? N : M;
-        const int first = (rev ? c - chunks_x : c) * kBlock + wave * 64;
+        TwoWayItem it = two_way_item(item, per, chunks_x, N, M);     // rev, dY: Y's points own, X's points hit
+        const int64_t b = it.b;
+        const bool rev = it.rev;
+        const int32_t full = it.full, qfull = it.qfull;
+        const int first = it.chunk * kBlock + wave * 64;
         float *out = rev ? dY : dX;
         if (out == nullptr || first >= full) continue;
-        const int32_t nb = so3::chamfer_length(x_len, b, N), mb = so3::chamfer_length(y_len, b, M);
-        const int32_t len_p = rev ? mb : nb, len_q = rev ? nb : mb;
+        two_way_lengths(it, x_len, y_len, N, M);
+        const int32_t len_p = it.len_p, len_q = it.len_q;
         const float *P = rev ? Y + b * M * 3 : X + b * N * 3, *Q = rev ? X + b * N * 3 : Y + b * M * 3;
         const int32_t *near_own = rev ? nearest_y : nearest_x, *near_hit = rev ? nearest_x : nearest_y;
         const float *s_own = rev ? scale_y : scale_x, *s_hit = rev ? scale_x : scale_y;
@@ -2253,81 +2326,18 @@ __global__ __launch_bounds__(kBlock) void k_chamfer_normals_fwd(const float *__r
                                                                 int32_t *__restrict__ nearest_y, float *__restrict__ term_x,
                                                                 float *__restrict__ term_y, float *__restrict__ rec, int32_t signed_cos, int64_t B,
                                                                 int32_t N, int32_t M, int32_t chunks_x, int32_t chunks_y) {
-    static_assert(kBlock == so3::kIcpBlock, "the host model's chunking");
     __shared__ float4 tile[kAddsTile];
-    const int tid = threadIdx.x;
-    const int per = chunks_x + chunks_y;
-    const int64_t items = B * per;
-    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
-        const int64_t b = item / per;
-        const int c = static_cast<int>(item - b * per);
-        const bool rev = c >= chunks_x;                              // the y direction: Y's points search X
-        const int i_base = (rev ? c - chunks_x : c) * (kBlock * U);
-        const int32_t nb = so3::chamfer_length(x_len, b, N), mb = so3::chamfer_length(y_len, b, M);
-        const int32_t full = rev ? M : N, len_p = rev ? mb : nb, len_q = rev ? nb : mb;
-        const float *src = rev ? Y + b * M * 3 : X + b * N * 3, *tgt = rev ? X + b * N * 3 : Y + b * M * 3;
-        const float *own = rev ? NY + b * M * 3 : NX + b * N * 3, *other = rev ? NX + b * N * 3 : NY + b * M * 3;
-        float *dist = rev ? dist_y : dist_x, *term = rev ? term_y : term_x;
-        int32_t *nearest = rev ? nearest_y : nearest_x;
-        const bool live = len_q > 0 && i_base < len_p;              // the same in every lane of the workgroup
-        float x[U], y[U], z[U], best[U];
-        int idx[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) { x[u] = 0.f; y[u] = 0.f; z[u] = 0.f; best[u] = 0.f; idx[u] = 0; }
-        if (live) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int i = min(i_base + u * kBlock + tid, len_p - 1);    // a slot beyond the cloud repeats its last point; not summed, not stored
-                x[u] = src[i * 3 + 0]; y[u] = src[i * 3 + 1]; z[u] = src[i * 3 + 2];
-                best[u] = __builtin_huge_valf();
-            }
-            tile_search<true, false>(tile, tid, len_q, [=](int j) { return tile_point(tgt, j); }, x, y, z, best, idx);
-        }
-        float mine = 0.f, mine_n = 0.f;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int i = i_base + u * kBlock + tid;
-            const bool valid = live && i < len_p;
-            const float e = valid ? so3::chamfer_term<SQUARED>(best[u]) : 0.f;
-            mine += e;
-            float t = 0.f;
-            if (live) {                                              // both indices clamped into the live part before they address anything
-                const int ic = min(i, len_p - 1), j = min(max(idx[u], 0), len_q - 1);
-                const float tt = so3::chamfer_normal_term(own[ic * 3 + 0], own[ic * 3 + 1], own[ic * 3 + 2], other[j * 3 + 0], other[j * 3 + 1],
-                                                          other[j * 3 + 2], signed_cos != 0);
-                t = valid ? tt : 0.f;
-            }
-            mine_n += t;
-            if (i < full) {
-                if (dist != nullptr) dist[b * full + i] = e;
-                if (nearest != nullptr) nearest[b * full + i] = valid ? min(idx[u], len_q - 1) : -1;
-                if (term != nullptr) term[b * full + i] = t;
-            }
-        }
-        const float sum_e = wave_allsum(mine), sum_t = wave_allsum(mine_n);
-        item_record<2>(tile, tid, (tid & 63) == 0 ? sum_e : sum_t, rec + item * 2);
-    }
+    chamfer_search<SQUARED, U, true>(tile, X, Y, NX, NY, x_len, y_len, dist_x, nearest_x, dist_y, nearest_y, term_x, term_y, rec, signed_cos, B, N,
+                                     M, chunks_x, chunks_y);
 }
 
-// rows[b] = (cham_x, cham_y) with k_chamfer_rows' arithmetic on the records' first floats, and rows_n[b] the same on their second.
+// rows[b] = (cham_x, cham_y) from the records' first floats, k_chamfer_rows' bits, and rows_n[b] the same from their second.
 __global__ __launch_bounds__(kBlock) void k_chamfer_normals_rows(const float *__restrict__ rec, const int32_t *__restrict__ x_len,
                                                                  const int32_t *__restrict__ y_len, float *__restrict__ rows,
                                                                  float *__restrict__ rows_n, int64_t B, int32_t N, int32_t M, int32_t chunks_x,
                                                                  int32_t chunks_y) {
-    const int per = chunks_x + chunks_y;
-    for (int64_t t = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; t < 2 * B; t += static_cast<int64_t>(gridDim.x) * kBlock) {
-        const int64_t b = t >> 1;
-        const bool rev = (t & 1) != 0;
-        const int32_t nb = so3::chamfer_length(x_len, b, N), mb = so3::chamfer_length(y_len, b, M);
-        const float *r = rec + (b * per + (rev ? chunks_x : 0)) * 2;
-        const int chunks = rev ? chunks_y : chunks_x;
-        double acc = 0.0, acc_n = 0.0;
-        for (int c = 0; c < chunks; ++c) { acc += static_cast<double>(r[c * 2]); acc_n += static_cast<double>(r[c * 2 + 1]); }
-        const bool scored = nb > 0 && mb > 0 && chunks > 0;
-        const double len = static_cast<double>(rev ? mb : nb);
-        rows[t] = scored ? static_cast<float>(acc / len) : 0.f;
-        rows_n[t] = scored ? static_cast<float>(acc_n / len) : 0.f;
-    }
+    float *const out[2] = {rows, rows_n};
+    chamfer_rows<2>(rec, x_len, y_len, out, B, N, M, chunks_x, chunks_y);
 }
 
 // k_chamfer_normals_bwd: both normals' gradients as a gather, at k_chamfer_bwd's geometry (64 owners per wave, one per lane, dNX's
@@ -2347,15 +2357,15 @@ __global__ __launch_bounds__(kBlock) void k_chamfer_normals_bwd(const float *__r
     const int64_t items = B * per;
     const bool sc = signed_cos != 0;
     for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
-        const int64_t b = item / per;
-        const int c = static_cast<int>(item - b * per);
-        const bool rev = c >= chunks_x;                              // dNY: Y's normals own, X's hit
-        const int32_t full = rev ? M : N, qfull = rev ? N : M;
-        const int first = (rev ? c - chunks_x : c) * kBlock + wave * 64;
+        TwoWayItem it = two_way_item(item, per, chunks_x, N, M);     // rev, dNY: Y's normals own, X's hit
+        const int64_t b = it.b;
+        const bool rev = it.rev;
+        const int32_t full = it.full, qfull = it.qfull;
+        const int first = it.chunk * kBlock + wave * 64;
         float *out = rev ? dNY : dNX;
         if (out == nullptr || first >= full) continue;
-        const int32_t nb = so3::chamfer_length(x_len, b, N), mb = so3::chamfer_length(y_len, b, M);
-        const int32_t len_p = rev ? mb : nb, len_q = rev ? nb : mb;
+        two_way_lengths(it, x_len, y_len, N, M);
+        const int32_t len_p = it.len_p, len_q = it.len_q;
         const float *P = rev ? NY + b * M * 3 : NX + b * N * 3, *Q = rev ? NX + b * N * 3 : NY + b * M * 3;
         const int32_t *near_own = rev ? nearest_y : nearest_x, *near_hit = rev ? nearest_x : nearest_y;
         const float *s_own = rev ? scale_y : scale_x, *s_hit = rev ? scale_x : scale_y;
@@ -4227,6 +4237,11 @@ inline unsigned persistent_grid(int64_t B) { return capped_grid(B, 2048u); }
 #define SO3_CHECK_ARGS(cond, name) \
     do { if (!(cond)) return fail(SO3_ERR_INVALID, name); } while (0)
 #define SO3_MAX_B (INT64_C(2147483647) * kBlock)
+// The cloud entry points' dimensions: up to 2^31 clouds of 1..max points and, where there is one, a second extent of 1..max; and K.
+inline bool cloud_dims_ok(int64_t B, int32_t N, int32_t M = 1, int32_t max = SO3_ADD_S_MAX_N) {
+    return B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= max && M >= 1 && M <= max;
+}
+inline bool knn_k_ok(int32_t K) { return K >= 1 && K <= SO3_KNN_MAX_K; }
 
 // Compute units of the current device (queried once per device; 256 on an MI355X in SPX mode, fewer in CPX / DPX partitions).
 inline int device_cus() {
@@ -4691,6 +4706,70 @@ inline ChamferChunks chamfer_chunks(int32_t N, int32_t M, bool single, int u) {
     return {so3::search_chunks(N, u), single ? 0 : so3::search_chunks(M, u)};
 }
 inline unsigned chamfer_grid(int64_t B, ChamferChunks ch) { return search_grid(B * (ch.x + ch.y)); }
+inline int chamfer_invalid(const char *name, const char *what) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: %s", name, what);
+    return fail(SO3_ERR_INVALID, msg);
+}
+#define SO3_CHAMFER_CHECK(cond, what) \
+    do { if (!(cond)) return chamfer_invalid(name, what); } while (0)
+
+// so3_chamfer_fwd_f32 and so3_chamfer_normals_fwd_f32 (NORMALS: the normals, term_x / term_y, rows_n and the signed-cosine flag come
+// with it): the checks, the search over the work items of both directions, the rows.  Both take u from the same rule, so the
+// distance's partial sums are the same.
+template <bool NORMALS>
+int launch_chamfer_fwd(const char *name, const float *X, const float *Y, const float *NX, const float *NY, const int32_t *x_len, const int32_t *y_len,
+                       float *dist_x, int32_t *nearest_x, float *dist_y, int32_t *nearest_y, float *term_x, float *term_y, float *rows,
+                       float *rows_n, void *work, uint32_t flags, int64_t B, int32_t N, int32_t M, void *stream) {
+    const unsigned known = SO3_CHAMFER_UNSQUARED | SO3_CHAMFER_SINGLE | (NORMALS ? SO3_CHAMFER_SIGNED_COSINE : 0);
+    SO3_CHAMFER_CHECK((flags & ~known) == 0, "unknown flag");
+    SO3_CHAMFER_CHECK(cloud_dims_ok(B, N, M), "B/N/M");
+    if (B == 0) return 0;
+    const bool single = (flags & SO3_CHAMFER_SINGLE) != 0;
+    SO3_CHAMFER_CHECK(X != nullptr && Y != nullptr && rows != nullptr && work != nullptr &&
+                          (!NORMALS || (NX != nullptr && NY != nullptr && rows_n != nullptr)), "null pointer");
+    SO3_CHAMFER_CHECK(!single || (dist_y == nullptr && nearest_y == nullptr && term_y == nullptr),
+                      NORMALS ? "dist_y / nearest_y / term_y with SO3_CHAMFER_SINGLE" : "dist_y / nearest_y with SO3_CHAMFER_SINGLE");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int u = so3::chamfer_points_per_lane(B, N, M, single, device_cus());
+    const ChamferChunks ch = chamfer_chunks(N, M, single, u);
+    float *rec = static_cast<float *>(work);
+    const dim3 grid(chamfer_grid(B, ch)), block(kBlock);
+    const dim3 rows_grid(static_cast<unsigned>(std::min<int64_t>((2 * B + kBlock - 1) / kBlock, static_cast<int64_t>(device_cus()) * 64)));
+    const int32_t signed_cos = (flags & SO3_CHAMFER_SIGNED_COSINE) != 0 ? 1 : 0;
+    with_flags([&](auto SQ) {
+        constexpr bool kSquared = SQ();
+        with_value<4, 2, 1>(u, [&](auto U) {
+            if constexpr (NORMALS) {
+                name_kernel("k_chamfer_normals_fwd", kSquared, U);
+                hipLaunchKernelGGL((k_chamfer_normals_fwd<kSquared, U()>), grid, block, 0, s, X, Y, NX, NY, x_len, y_len, dist_x, nearest_x, dist_y,
+                                   nearest_y, term_x, term_y, rec, signed_cos, B, N, M, ch.x, ch.y);
+            } else {
+                name_kernel("k_chamfer_fwd", kSquared, U);
+                hipLaunchKernelGGL((k_chamfer_fwd<kSquared, U()>), grid, block, 0, s, X, Y, x_len, y_len, dist_x, nearest_x, dist_y, nearest_y, rec, B,
+                                   N, M, ch.x, ch.y);
+            }
+        });
+    }, (flags & SO3_CHAMFER_UNSQUARED) == 0);
+    if (NORMALS) hipLaunchKernelGGL(k_chamfer_normals_rows, rows_grid, block, 0, s, rec, x_len, y_len, rows, rows_n, B, N, M, ch.x, ch.y);
+    else hipLaunchKernelGGL(k_chamfer_rows, rows_grid, block, 0, s, rec, x_len, y_len, rows, B, N, M, ch.x, ch.y);
+    return check_launch(name);
+}
+
+// What both Chamfer backwards ask of their arguments (A, Bq: the two clouds' points or normals).  0: go on; B == 0 is the caller's.
+inline int check_chamfer_bwd(const char *name, unsigned known, const void *A, const void *Bq, const int32_t *nearest_x, const int32_t *nearest_y,
+                             const float *scale_x, const float *scale_y, const void *dA, const void *dB, uint32_t flags, int64_t B, int32_t N,
+                             int32_t M) {
+    SO3_CHAMFER_CHECK((flags & ~known) == 0, "unknown flag");
+    SO3_CHAMFER_CHECK(cloud_dims_ok(B, N, M), "B/N/M");
+    if (B == 0) return 0;
+    const bool single = (flags & SO3_CHAMFER_SINGLE) != 0;
+    SO3_CHAMFER_CHECK(A != nullptr && Bq != nullptr && nearest_x != nullptr && scale_x != nullptr && (dA != nullptr || dB != nullptr), "null pointer");
+    SO3_CHAMFER_CHECK(single ? (nearest_y == nullptr && scale_y == nullptr) : (nearest_y != nullptr && scale_y != nullptr),
+                      "nearest_y and scale_y go with both directions, NULL with SO3_CHAMFER_SINGLE");
+    return 0;
+}
+#undef SO3_CHAMFER_CHECK
 }  // namespace
 
 // ---- K4b: the metrics' backward (include/so3proj.h) ------------------------------------------------------------------
@@ -5207,21 +5286,21 @@ int so3_relative_log_bwd_f32(const float *R1, const float *R2, const float *G, f
 
 int so3_add_l1_f32(const float *Tgt, const float *Tpred, const float *points, float *dists, double *loss_sum, float *dTpred,
                    float grad_scale, int64_t B, int32_t N, void *stream) {
-    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= 150000000, "so3_add_l1_f32: B/N");
+    SO3_CHECK_ARGS(cloud_dims_ok(B, N, 1, 150000000), "so3_add_l1_f32: B/N");
     SO3_CHECK_ARGS(B == 0 || (Tgt != nullptr && Tpred != nullptr && points != nullptr), "so3_add_l1_f32: null pointer");
     return launch_add_l1<false>(Tgt, Tpred, points, dists, loss_sum, dTpred, grad_scale, B, N, static_cast<hipStream_t>(stream), "so3_add_l1_f32");
 }
 
 int so3_add_l2_f32(const float *Tgt, const float *Tpred, const float *points, float *dists, double *loss_sum, float *dTpred,
                    float grad_scale, int64_t B, int32_t N, void *stream) {
-    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= 150000000, "so3_add_l2_f32: B/N");
+    SO3_CHECK_ARGS(cloud_dims_ok(B, N, 1, 150000000), "so3_add_l2_f32: B/N");
     SO3_CHECK_ARGS(B == 0 || (Tgt != nullptr && Tpred != nullptr && points != nullptr), "so3_add_l2_f32: null pointer");
     return launch_add_l1<false, true>(Tgt, Tpred, points, dists, loss_sum, dTpred, grad_scale, B, N, static_cast<hipStream_t>(stream), "so3_add_l2_f32");
 }
 
 int so3_add_s_fwd_f32(const float *Tgt, const float *Tpred, const float *points, float *point_dist, int32_t *nearest, float *dists,
                       double *loss_sum, int64_t B, int32_t N, void *stream) {
-    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N, "so3_add_s_fwd_f32: B/N");
+    SO3_CHECK_ARGS(cloud_dims_ok(B, N), "so3_add_s_fwd_f32: B/N");
     SO3_CHECK_ARGS(B == 0 || (Tgt != nullptr && Tpred != nullptr && points != nullptr && point_dist != nullptr), "so3_add_s_fwd_f32: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (B == 0) {
@@ -5233,7 +5312,7 @@ int so3_add_s_fwd_f32(const float *Tgt, const float *Tpred, const float *points,
 
 int so3_add_s_bwd_f32(const float *Tgt, const float *Tpred, const float *points, const int32_t *nearest, const float *grad_rows,
                       float grad_scale, float *dTpred, int64_t B, int32_t N, void *stream) {
-    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N, "so3_add_s_bwd_f32: B/N");
+    SO3_CHECK_ARGS(cloud_dims_ok(B, N), "so3_add_s_bwd_f32: B/N");
     SO3_CHECK_ARGS(B == 0 || (Tgt != nullptr && Tpred != nullptr && points != nullptr && nearest != nullptr && dTpred != nullptr),
                    "so3_add_s_bwd_f32: null pointer");
     if (B == 0) return 0;
@@ -5243,7 +5322,7 @@ int so3_add_s_bwd_f32(const float *Tgt, const float *Tpred, const float *points,
 }
 
 int so3_cloud_diameter_f32(const float *points, float *work, float *diam, int64_t B, int32_t N, void *stream) {
-    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N, "so3_cloud_diameter_f32: B/N");
+    SO3_CHECK_ARGS(cloud_dims_ok(B, N), "so3_cloud_diameter_f32: B/N");
     SO3_CHECK_ARGS(B == 0 || (points != nullptr && work != nullptr && diam != nullptr), "so3_cloud_diameter_f32: null pointer");
     if (B == 0) return 0;
     return launch_add_s<true>(nullptr, nullptr, points, work, nullptr, diam, nullptr, B, N, static_cast<hipStream_t>(stream), "so3_cloud_diameter_f32");
@@ -5251,7 +5330,7 @@ int so3_cloud_diameter_f32(const float *points, float *work, float *diam, int64_
 
 int so3_nearest_f32(const float *X, const float *Y, int64_t y_stride, float *dist, int32_t *nearest, int64_t B, int32_t N, int32_t M,
                     void *stream) {
-    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && M >= 1 && M <= SO3_ADD_S_MAX_N, "so3_nearest_f32: B/N");
+    SO3_CHECK_ARGS(cloud_dims_ok(B, N, M), "so3_nearest_f32: B/N");
     if (B == 0) return 0;
     SO3_CHECK_ARGS(y_stride == 0 || y_stride >= static_cast<int64_t>(M) * 3, "so3_nearest_f32: y_stride");
     SO3_CHECK_ARGS(X != nullptr && Y != nullptr && dist != nullptr, "so3_nearest_f32: null pointer");
@@ -5262,7 +5341,7 @@ int so3_nearest_f32(const float *X, const float *Y, int64_t y_stride, float *dis
 }
 
 size_t so3_icp_workspace_bytes(int64_t B, int32_t N) {
-    if (B < 0 || B > (INT64_C(1) << 31) || N < 1 || N > SO3_ADD_S_MAX_N) return 0;
+    if (!cloud_dims_ok(B, N)) return 0;
     // two pose buffers and one record per work item at the smallest work item (U = 1), whatever the device
     return static_cast<size_t>(B) * (2 * 12 + static_cast<size_t>((N + kBlock - 1) / kBlock) * so3::kIcpRecord) * sizeof(float);
 }
@@ -5270,7 +5349,7 @@ size_t so3_icp_workspace_bytes(int64_t B, int32_t N) {
 int so3_icp_f32(const float *P, const float *Q, int64_t q_stride, const float *w, const float *T_init, float max_distance, int32_t iterations,
                 float *R, float *t, float *rmse, int32_t *inliers, int32_t *nearest, float *dist, void *workspace, int64_t B, int32_t N,
                 int32_t M, void *stream) {
-    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && M >= 1 && M <= SO3_ADD_S_MAX_N, "so3_icp_f32: B/N");
+    SO3_CHECK_ARGS(cloud_dims_ok(B, N, M), "so3_icp_f32: B/N");
     SO3_CHECK_ARGS(iterations >= 0 && iterations <= SO3_ICP_MAX_ITERATIONS, "so3_icp_f32: iterations");
     if (B == 0) return 0;
     SO3_CHECK_ARGS(q_stride == 0 || q_stride >= static_cast<int64_t>(M) * 3, "so3_icp_f32: q_stride");
@@ -5301,7 +5380,7 @@ int so3_icp_f32(const float *P, const float *Q, int64_t q_stride, const float *w
 }
 
 size_t so3_icp_plane_workspace_bytes(int64_t B, int32_t N) {
-    if (B < 0 || B > (INT64_C(1) << 31) || N < 1 || N > SO3_ADD_S_MAX_N) return 0;
+    if (!cloud_dims_ok(B, N)) return 0;
     // two pose buffers and one record per work item at the smallest work item (U = 1), whatever the device
     return static_cast<size_t>(B) * (2 * 12 + static_cast<size_t>((N + kBlock - 1) / kBlock) * so3::kPlaneRecord) * sizeof(float);
 }
@@ -5310,7 +5389,7 @@ int so3_icp_plane_f32(const float *P, const float *Q, const float *normals, int6
                       float max_distance, float damping, int32_t iterations, float *R, float *t, float *rmse, float *rmse_point,
                       int32_t *inliers, int32_t *solved, int32_t *nearest, float *dist, void *workspace, int64_t B, int32_t N, int32_t M,
                       void *stream) {
-    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && M >= 1 && M <= SO3_ADD_S_MAX_N, "so3_icp_plane_f32: B/N");
+    SO3_CHECK_ARGS(cloud_dims_ok(B, N, M), "so3_icp_plane_f32: B/N");
     SO3_CHECK_ARGS(iterations >= 0 && iterations <= SO3_ICP_MAX_ITERATIONS, "so3_icp_plane_f32: iterations");
     SO3_CHECK_ARGS(damping >= 0.f, "so3_icp_plane_f32: damping");                      // a NaN fails the comparison
     if (B == 0) return 0;
@@ -5352,7 +5431,7 @@ int so3_icp_plane_f32(const float *P, const float *Q, const float *normals, int6
 }
 
 size_t so3_chamfer_workspace_bytes(int64_t B, int32_t N, int32_t M) {
-    if (B < 0 || B > (INT64_C(1) << 31) || N < 1 || N > SO3_ADD_S_MAX_N || M < 1 || M > SO3_ADD_S_MAX_N) return 0;
+    if (!cloud_dims_ok(B, N, M)) return 0;
     // one float per work item at the smallest work item (U = 1), both directions, whatever the device
     const ChamferChunks ch = chamfer_chunks(N, M, false, 1);
     return static_cast<size_t>(B) * (static_cast<size_t>(ch.x) + static_cast<size_t>(ch.y)) * sizeof(float);
@@ -5361,42 +5440,16 @@ size_t so3_chamfer_workspace_bytes(int64_t B, int32_t N, int32_t M) {
 int so3_chamfer_fwd_f32(const float *X, const float *Y, const int32_t *x_len, const int32_t *y_len, float *dist_x, int32_t *nearest_x,
                         float *dist_y, int32_t *nearest_y, float *rows, void *work, uint32_t flags, int64_t B, int32_t N, int32_t M,
                         void *stream) {
-    SO3_CHECK_ARGS((flags & ~static_cast<unsigned>(SO3_CHAMFER_UNSQUARED | SO3_CHAMFER_SINGLE)) == 0, "so3_chamfer_fwd_f32: unknown flag");
-    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && M >= 1 && M <= SO3_ADD_S_MAX_N,
-                   "so3_chamfer_fwd_f32: B/N/M");
-    if (B == 0) return 0;
-    const bool single = (flags & SO3_CHAMFER_SINGLE) != 0;
-    SO3_CHECK_ARGS(X != nullptr && Y != nullptr && rows != nullptr && work != nullptr, "so3_chamfer_fwd_f32: null pointer");
-    SO3_CHECK_ARGS(!single || (dist_y == nullptr && nearest_y == nullptr), "so3_chamfer_fwd_f32: dist_y / nearest_y with SO3_CHAMFER_SINGLE");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int u = so3::chamfer_points_per_lane(B, N, M, single, device_cus());
-    const ChamferChunks ch = chamfer_chunks(N, M, single, u);
-    float *rec = static_cast<float *>(work);
-    with_flags([&](auto SQ) {
-        constexpr bool kSquared = SQ();
-        with_value<4, 2, 1>(u, [&](auto U) {
-            name_kernel("k_chamfer_fwd", kSquared, U);
-            hipLaunchKernelGGL((k_chamfer_fwd<kSquared, U()>),dim3(chamfer_grid(B, ch)), dim3(kBlock), 0, s, X, Y, x_len, y_len, dist_x, nearest_x, dist_y,
-                               nearest_y, rec, B, N, M, ch.x, ch.y);
-        });
-    }, (flags & SO3_CHAMFER_UNSQUARED) == 0);
-    const unsigned rows_grid = static_cast<unsigned>(std::min<int64_t>((2 * B + kBlock - 1) / kBlock, static_cast<int64_t>(device_cus()) * 64));
-    hipLaunchKernelGGL(k_chamfer_rows, dim3(rows_grid), dim3(kBlock), 0, s, rec, x_len, y_len, rows, B, N, M, ch.x, ch.y);
-    return check_launch("so3_chamfer_fwd_f32");
+    return launch_chamfer_fwd<false>("so3_chamfer_fwd_f32", X, Y, nullptr, nullptr, x_len, y_len, dist_x, nearest_x, dist_y, nearest_y, nullptr, nullptr,
+                                     rows, nullptr, work, flags, B, N, M, stream);
 }
 
 int so3_chamfer_bwd_f32(const float *X, const float *Y, const int32_t *x_len, const int32_t *y_len, const int32_t *nearest_x,
                         const int32_t *nearest_y, const float *scale_x, const float *scale_y, float *dX, float *dY, uint32_t flags, int64_t B,
                         int32_t N, int32_t M, void *stream) {
-    SO3_CHECK_ARGS((flags & ~static_cast<unsigned>(SO3_CHAMFER_UNSQUARED | SO3_CHAMFER_SINGLE)) == 0, "so3_chamfer_bwd_f32: unknown flag");
-    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && M >= 1 && M <= SO3_ADD_S_MAX_N,
-                   "so3_chamfer_bwd_f32: B/N/M");
+    if (int e = check_chamfer_bwd("so3_chamfer_bwd_f32", SO3_CHAMFER_UNSQUARED | SO3_CHAMFER_SINGLE, X, Y, nearest_x, nearest_y, scale_x, scale_y, dX, dY,
+                                  flags, B, N, M)) return e;
     if (B == 0) return 0;
-    const bool single = (flags & SO3_CHAMFER_SINGLE) != 0;
-    SO3_CHECK_ARGS(X != nullptr && Y != nullptr && nearest_x != nullptr && scale_x != nullptr && (dX != nullptr || dY != nullptr),
-                   "so3_chamfer_bwd_f32: null pointer");
-    SO3_CHECK_ARGS(single ? (nearest_y == nullptr && scale_y == nullptr) : (nearest_y != nullptr && scale_y != nullptr),
-                   "so3_chamfer_bwd_f32: nearest_y and scale_y go with both directions, NULL with SO3_CHAMFER_SINGLE");
     const ChamferChunks ch = chamfer_chunks(N, M, false, 1);
     with_flags([&](auto SQ) {
         name_kernel("k_chamfer_bwd", SQ);
@@ -5414,47 +5467,16 @@ size_t so3_chamfer_normals_workspace_bytes(int64_t B, int32_t N, int32_t M) {
 int so3_chamfer_normals_fwd_f32(const float *X, const float *Y, const float *NX, const float *NY, const int32_t *x_len, const int32_t *y_len,
                                 float *dist_x, int32_t *nearest_x, float *dist_y, int32_t *nearest_y, float *term_x, float *term_y, float *rows,
                                 float *rows_n, void *work, uint32_t flags, int64_t B, int32_t N, int32_t M, void *stream) {
-    SO3_CHECK_ARGS((flags & ~static_cast<unsigned>(SO3_CHAMFER_UNSQUARED | SO3_CHAMFER_SINGLE | SO3_CHAMFER_SIGNED_COSINE)) == 0,
-                   "so3_chamfer_normals_fwd_f32: unknown flag");
-    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && M >= 1 && M <= SO3_ADD_S_MAX_N,
-                   "so3_chamfer_normals_fwd_f32: B/N/M");
-    if (B == 0) return 0;
-    const bool single = (flags & SO3_CHAMFER_SINGLE) != 0;
-    SO3_CHECK_ARGS(X != nullptr && Y != nullptr && NX != nullptr && NY != nullptr && rows != nullptr && rows_n != nullptr && work != nullptr,
-                   "so3_chamfer_normals_fwd_f32: null pointer");
-    SO3_CHECK_ARGS(!single || (dist_y == nullptr && nearest_y == nullptr && term_y == nullptr),
-                   "so3_chamfer_normals_fwd_f32: dist_y / nearest_y / term_y with SO3_CHAMFER_SINGLE");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int u = so3::chamfer_points_per_lane(B, N, M, single, device_cus());      // so3_chamfer_fwd_f32's rule: the same partial sums
-    const ChamferChunks ch = chamfer_chunks(N, M, single, u);
-    float *rec = static_cast<float *>(work);
-    const int32_t signed_cos = (flags & SO3_CHAMFER_SIGNED_COSINE) != 0 ? 1 : 0;
-    with_flags([&](auto SQ) {
-        constexpr bool kSquared = SQ();
-        with_value<4, 2, 1>(u, [&](auto U) {
-            name_kernel("k_chamfer_normals_fwd", kSquared, U);
-            hipLaunchKernelGGL((k_chamfer_normals_fwd<kSquared, U()>), dim3(chamfer_grid(B, ch)), dim3(kBlock), 0, s, X, Y, NX, NY, x_len, y_len, dist_x,
-                               nearest_x, dist_y, nearest_y, term_x, term_y, rec, signed_cos, B, N, M, ch.x, ch.y);
-        });
-    }, (flags & SO3_CHAMFER_UNSQUARED) == 0);
-    const unsigned rows_grid = static_cast<unsigned>(std::min<int64_t>((2 * B + kBlock - 1) / kBlock, static_cast<int64_t>(device_cus()) * 64));
-    hipLaunchKernelGGL(k_chamfer_normals_rows, dim3(rows_grid), dim3(kBlock), 0, s, rec, x_len, y_len, rows, rows_n, B, N, M, ch.x, ch.y);
-    return check_launch("so3_chamfer_normals_fwd_f32");
+    return launch_chamfer_fwd<true>("so3_chamfer_normals_fwd_f32", X, Y, NX, NY, x_len, y_len, dist_x, nearest_x, dist_y, nearest_y, term_x, term_y, rows,
+                                    rows_n, work, flags, B, N, M, stream);
 }
 
 int so3_chamfer_normals_bwd_f32(const float *NX, const float *NY, const int32_t *x_len, const int32_t *y_len, const int32_t *nearest_x,
                                 const int32_t *nearest_y, const float *scale_x, const float *scale_y, float *dNX, float *dNY, uint32_t flags,
                                 int64_t B, int32_t N, int32_t M, void *stream) {
-    SO3_CHECK_ARGS((flags & ~static_cast<unsigned>(SO3_CHAMFER_UNSQUARED | SO3_CHAMFER_SINGLE | SO3_CHAMFER_SIGNED_COSINE)) == 0,
-                   "so3_chamfer_normals_bwd_f32: unknown flag");
-    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && M >= 1 && M <= SO3_ADD_S_MAX_N,
-                   "so3_chamfer_normals_bwd_f32: B/N/M");
+    if (int e = check_chamfer_bwd("so3_chamfer_normals_bwd_f32", SO3_CHAMFER_UNSQUARED | SO3_CHAMFER_SINGLE | SO3_CHAMFER_SIGNED_COSINE, NX, NY, nearest_x,
+                                  nearest_y, scale_x, scale_y, dNX, dNY, flags, B, N, M)) return e;
     if (B == 0) return 0;
-    const bool single = (flags & SO3_CHAMFER_SINGLE) != 0;
-    SO3_CHECK_ARGS(NX != nullptr && NY != nullptr && nearest_x != nullptr && scale_x != nullptr && (dNX != nullptr || dNY != nullptr),
-                   "so3_chamfer_normals_bwd_f32: null pointer");
-    SO3_CHECK_ARGS(single ? (nearest_y == nullptr && scale_y == nullptr) : (nearest_y != nullptr && scale_y != nullptr),
-                   "so3_chamfer_normals_bwd_f32: nearest_y and scale_y go with both directions, NULL with SO3_CHAMFER_SINGLE");
     const ChamferChunks ch = chamfer_chunks(N, M, false, 1);
     name_kernel("k_chamfer_normals_bwd");
     hipLaunchKernelGGL(k_chamfer_normals_bwd, dim3(chamfer_grid(B, ch)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), NX, NY, x_len, y_len,
@@ -5465,8 +5487,8 @@ int so3_chamfer_normals_bwd_f32(const float *NX, const float *NY, const int32_t 
 int so3_knn_f32(const float *X, const float *Y, int64_t y_stride, const int32_t *x_len, const int32_t *y_len, float *dist2, int32_t *idx, int32_t K,
                 int64_t B, int32_t N, int32_t M, void *stream) {
     static_assert(SO3_KNN_MAX_K == so3::kKnnMaxK, "the header's limit is the kernel's");
-    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && M >= 1 && M <= SO3_ADD_S_MAX_N, "so3_knn_f32: B/N/M");
-    SO3_CHECK_ARGS(K >= 1 && K <= SO3_KNN_MAX_K, "so3_knn_f32: K");
+    SO3_CHECK_ARGS(cloud_dims_ok(B, N, M), "so3_knn_f32: B/N/M");
+    SO3_CHECK_ARGS(knn_k_ok(K), "so3_knn_f32: K");
     if (B == 0) return 0;
     SO3_CHECK_ARGS(y_stride == 0 || y_stride >= static_cast<int64_t>(M) * 3, "so3_knn_f32: y_stride");
     SO3_CHECK_ARGS(X != nullptr && Y != nullptr && idx != nullptr, "so3_knn_f32: null pointer");
@@ -5482,8 +5504,8 @@ int so3_knn_f32(const float *X, const float *Y, int64_t y_stride, const int32_t 
 
 int so3_knn_bwd_f32(const float *X, const float *Y, const int32_t *x_len, const int32_t *y_len, const int32_t *idx, const float *grad_dist2,
                     float *dX, float *dY, int32_t K, int64_t B, int32_t N, int32_t M, void *stream) {
-    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && M >= 1 && M <= SO3_ADD_S_MAX_N, "so3_knn_bwd_f32: B/N/M");
-    SO3_CHECK_ARGS(K >= 1 && K <= SO3_KNN_MAX_K, "so3_knn_bwd_f32: K");
+    SO3_CHECK_ARGS(cloud_dims_ok(B, N, M), "so3_knn_bwd_f32: B/N/M");
+    SO3_CHECK_ARGS(knn_k_ok(K), "so3_knn_bwd_f32: K");
     if (B == 0) return 0;
     SO3_CHECK_ARGS(X != nullptr && Y != nullptr && idx != nullptr && grad_dist2 != nullptr && (dX != nullptr || dY != nullptr),
                    "so3_knn_bwd_f32: null pointer");
@@ -5496,8 +5518,8 @@ int so3_knn_bwd_f32(const float *X, const float *Y, const int32_t *x_len, const 
 
 int so3_local_frames_f32(const float *Y, int64_t y_stride, const int32_t *idx, const int32_t *x_len, const int32_t *y_len, const float *viewpoint,
                          float *cov, float *eigenvalues, float *normals, float *frames, int32_t K, int64_t B, int32_t N, int32_t M, void *stream) {
-    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && M >= 1 && M <= SO3_ADD_S_MAX_N, "so3_local_frames_f32: B/N/M");
-    SO3_CHECK_ARGS(K >= 1 && K <= SO3_KNN_MAX_K, "so3_local_frames_f32: K");
+    SO3_CHECK_ARGS(cloud_dims_ok(B, N, M), "so3_local_frames_f32: B/N/M");
+    SO3_CHECK_ARGS(knn_k_ok(K), "so3_local_frames_f32: K");
     if (B == 0) return 0;
     SO3_CHECK_ARGS(y_stride == 0 || y_stride >= static_cast<int64_t>(M) * 3, "so3_local_frames_f32: y_stride");
     SO3_CHECK_ARGS(Y != nullptr && idx != nullptr && (cov != nullptr || eigenvalues != nullptr || normals != nullptr || frames != nullptr),
@@ -5511,8 +5533,8 @@ int so3_local_frames_f32(const float *Y, int64_t y_stride, const int32_t *idx, c
 
 int so3_spfh_f32(const float *X, const float *normals, const int32_t *idx, const int32_t *len, float *spfh, int32_t *pairs, int32_t K, int64_t B,
                  int32_t N, void *stream) {
-    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N, "so3_spfh_f32: B/N");
-    SO3_CHECK_ARGS(K >= 1 && K <= SO3_KNN_MAX_K, "so3_spfh_f32: K");
+    SO3_CHECK_ARGS(cloud_dims_ok(B, N), "so3_spfh_f32: B/N");
+    SO3_CHECK_ARGS(knn_k_ok(K), "so3_spfh_f32: K");
     if (B == 0) return 0;
     SO3_CHECK_ARGS(X != nullptr && normals != nullptr && idx != nullptr && (spfh != nullptr || pairs != nullptr), "so3_spfh_f32: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -5530,8 +5552,8 @@ int so3_spfh_f32(const float *X, const float *normals, const int32_t *idx, const
 
 int so3_fpfh_f32(const float *X, const int32_t *idx, const int32_t *len, const float *spfh, const int32_t *pairs, float *fpfh, int32_t K, int64_t B,
                  int32_t N, void *stream) {
-    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N, "so3_fpfh_f32: B/N");
-    SO3_CHECK_ARGS(K >= 1 && K <= SO3_KNN_MAX_K, "so3_fpfh_f32: K");
+    SO3_CHECK_ARGS(cloud_dims_ok(B, N), "so3_fpfh_f32: B/N");
+    SO3_CHECK_ARGS(knn_k_ok(K), "so3_fpfh_f32: K");
     if (B == 0) return 0;
     SO3_CHECK_ARGS(X != nullptr && idx != nullptr && spfh != nullptr && pairs != nullptr && fpfh != nullptr, "so3_fpfh_f32: null pointer");
     const int32_t chunks = (N * so3::kFpfhSlots + kBlock - 1) / kBlock;
@@ -5543,7 +5565,7 @@ int so3_fpfh_f32(const float *X, const int32_t *idx, const int32_t *len, const f
 
 int so3_fps_f32(const float *xyz, const int32_t *start, int32_t *out, int64_t B, int32_t N, int32_t npoint, void *stream) {
     static_assert(SO3_FPS_MAX_N == so3::kFpsMaxN, "the header's limit is the dispatch's");
-    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_FPS_MAX_N && npoint >= 1 && npoint <= SO3_FPS_MAX_N, "so3_fps_f32: B/N/npoint");
+    SO3_CHECK_ARGS(cloud_dims_ok(B, N, npoint, SO3_FPS_MAX_N), "so3_fps_f32: B/N/npoint");
     if (B == 0) return 0;
     SO3_CHECK_ARGS(xyz != nullptr && start != nullptr && out != nullptr, "so3_fps_f32: null pointer");
     int ppl, block;
@@ -5564,7 +5586,7 @@ int so3_fps_f32(const float *xyz, const int32_t *start, int32_t *out, int64_t B,
 
 int so3_ball_query_f32(const float *xyz, const float *centres, float radius, int32_t nsample, int32_t *idx, int32_t *count, int64_t B,
                        int32_t N, int32_t S, void *stream) {
-    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && S >= 1 && S <= SO3_ADD_S_MAX_N && nsample >= 1,
+    SO3_CHECK_ARGS(cloud_dims_ok(B, N, S) && nsample >= 1,
                    "so3_ball_query_f32: B/N/S/nsample");
     if (B == 0) return 0;
     SO3_CHECK_ARGS(xyz != nullptr && centres != nullptr && idx != nullptr, "so3_ball_query_f32: null pointer");
@@ -5580,7 +5602,7 @@ int so3_ball_query_f32(const float *xyz, const float *centres, float radius, int
 
 int so3_three_nn_f32(const float *unknown, const float *known, float *dist2, int32_t *idx, float *weight, int64_t B, int32_t N, int32_t S,
                      void *stream) {
-    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && S >= 1 && S <= SO3_ADD_S_MAX_N, "so3_three_nn_f32: B/N/S");
+    SO3_CHECK_ARGS(cloud_dims_ok(B, N, S), "so3_three_nn_f32: B/N/S");
     if (B == 0) return 0;
     SO3_CHECK_ARGS(unknown != nullptr && known != nullptr && dist2 != nullptr && idx != nullptr, "so3_three_nn_f32: null pointer");
     const int wpp = so3::three_nn_waves_per_point(B, N, S);
@@ -5599,7 +5621,7 @@ int so3_three_nn_f32(const float *unknown, const float *known, float *dist2, int
 
 int so3_three_interpolate_f32(const float *feat, const int32_t *idx, const float *weight, float *out, int32_t channels_first, int64_t B,
                               int32_t N, int32_t S, int32_t D, void *stream) {
-    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && S >= 1 && S <= SO3_ADD_S_MAX_N && D >= 1 && D <= SO3_THREE_MAX_D,
+    SO3_CHECK_ARGS(cloud_dims_ok(B, N, S) && D >= 1 && D <= SO3_THREE_MAX_D,
                    "so3_three_interpolate_f32: B/N/S/D");
     if (B == 0) return 0;
     SO3_CHECK_ARGS(feat != nullptr && idx != nullptr && weight != nullptr && out != nullptr, "so3_three_interpolate_f32: null pointer");
@@ -5623,7 +5645,7 @@ int so3_three_interpolate_f32(const float *feat, const int32_t *idx, const float
 
 int so3_three_interpolate_bwd_f32(const float *grad_out, const int32_t *idx, const float *weight, float *grad_feat, int32_t channels_first,
                                   int64_t B, int32_t N, int32_t S, int32_t D, void *stream) {
-    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && S >= 1 && S <= SO3_ADD_S_MAX_N && D >= 1 && D <= SO3_THREE_MAX_D,
+    SO3_CHECK_ARGS(cloud_dims_ok(B, N, S) && D >= 1 && D <= SO3_THREE_MAX_D,
                    "so3_three_interpolate_bwd_f32: B/N/S/D");
     if (B == 0) return 0;
     SO3_CHECK_ARGS(grad_out != nullptr && idx != nullptr && weight != nullptr && grad_feat != nullptr, "so3_three_interpolate_bwd_f32: null pointer");
@@ -5638,7 +5660,7 @@ int so3_three_interpolate_bwd_f32(const float *grad_out, const int32_t *idx, con
 
 int so3_group_points_f32(const float *xyz, const float *centres, const float *feat, const int32_t *idx, float *out, int32_t features_first,
                          int32_t channels_first, int64_t B, int32_t N, int32_t S, int32_t K, int32_t D, void *stream) {
-    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && S >= 1 && S <= SO3_ADD_S_MAX_N && K >= 1 &&
+    SO3_CHECK_ARGS(cloud_dims_ok(B, N, S) && K >= 1 &&
                        K <= SO3_GROUP_MAX_K && D >= 0 && D <= SO3_THREE_MAX_D,
                    "so3_group_points_f32: B/N/S/K/D");
     if (B == 0) return 0;
@@ -5665,7 +5687,7 @@ int so3_group_points_f32(const float *xyz, const float *centres, const float *fe
 
 int so3_group_points_bwd_f32(const float *grad_out, const int32_t *idx, float *grad_xyz, float *grad_centres, float *grad_feat,
                              int32_t features_first, int32_t channels_first, int64_t B, int32_t N, int32_t S, int32_t K, int32_t D, void *stream) {
-    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= SO3_ADD_S_MAX_N && S >= 1 && S <= SO3_ADD_S_MAX_N && K >= 1 &&
+    SO3_CHECK_ARGS(cloud_dims_ok(B, N, S) && K >= 1 &&
                        K <= SO3_GROUP_MAX_K && D >= 0 && D <= SO3_THREE_MAX_D,
                    "so3_group_points_bwd_f32: B/N/S/K/D");
     if (B == 0) return 0;
@@ -5697,7 +5719,7 @@ int so3_group_points_bwd_f32(const float *grad_out, const int32_t *idx, float *g
 
 int so3_add_l1_disentangled_f32(const float *Tpred, const float *Tgt, const float *points, double *loss_sum, float *dTpred,
                                 float grad_scale, int64_t B, int32_t N, void *stream) {
-    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= 150000000, "so3_add_l1_disentangled_f32: B/N");
+    SO3_CHECK_ARGS(cloud_dims_ok(B, N, 1, 150000000), "so3_add_l1_disentangled_f32: B/N");
     SO3_CHECK_ARGS(B == 0 || (Tgt != nullptr && Tpred != nullptr && points != nullptr), "so3_add_l1_disentangled_f32: null pointer");
     return launch_add_l1<true>(Tgt, Tpred, points, nullptr, loss_sum, dTpred, grad_scale, B, N, static_cast<hipStream_t>(stream),
                                "so3_add_l1_disentangled_f32");
@@ -5715,7 +5737,7 @@ int so3_rotate_clouds_f32(const float *P, const float *R, float *out, int transp
 }
 
 int so3_pc_normalize_f32(const float *P, float *out, float *centroid, float *scale, int64_t B, int32_t N, void *stream) {
-    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= 150000000, "so3_pc_normalize_f32: B/N");
+    SO3_CHECK_ARGS(cloud_dims_ok(B, N, 1, 150000000), "so3_pc_normalize_f32: B/N");
     if (B == 0) return 0;
     SO3_CHECK_ARGS(P != nullptr && out != nullptr, "so3_pc_normalize_f32: null pointer");
     const CloudShape shape = cloud_shape(B);
@@ -6011,7 +6033,7 @@ int so3_sym_add_f32(const float *Tgt, const float *Tpred, const float *points, c
                     int32_t K, float *dists, int32_t *index, double *loss_sum, float *dTpred, float grad_scale, unsigned flags, int64_t B,
                     int32_t N, void *stream) {
     SO3_CHECK_ARGS(flags <= static_cast<unsigned>(SO3_SYM_ADD_MAX), "so3_sym_add_f32: unknown flag (the mode: SO3_SYM_ADD_L2, _L1 or _MAX)");
-    SO3_CHECK_ARGS(B >= 0 && B <= (INT64_C(1) << 31) && N >= 1 && N <= 150000000, "so3_sym_add_f32: B/N");
+    SO3_CHECK_ARGS(cloud_dims_ok(B, N, 1, 150000000), "so3_sym_add_f32: B/N");
     SO3_SYM_CHECK("so3_sym_add_f32");
     SO3_CHECK_ARGS(flags != static_cast<unsigned>(SO3_SYM_ADD_MAX) || dTpred == nullptr, "so3_sym_add_f32: dTpred must be null with SO3_SYM_ADD_MAX (no gradient)");
     if (B == 0) return 0;

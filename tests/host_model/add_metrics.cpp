@@ -10,18 +10,9 @@
 #include <limits>
 
 #include "../../poseestimation_amd/csrc/so3_device.h"
+#include "wave_model.h"
 
 namespace {
-
-float wave_allsum(const float (&lane)[64]) {
-    float v[64], w[64];
-    for (int l = 0; l < 64; ++l) v[l] = lane[l];
-    for (int off = 1; off < 64; off <<= 1) {
-        for (int l = 0; l < 64; ++l) w[l] = v[l] + v[l ^ off];
-        for (int l = 0; l < 64; ++l) v[l] = w[l];
-    }
-    return v[0];
-}
 
 void top_rows(const float *T, float (&m)[12]) {
     for (int k = 0; k < 12; ++k) m[k] = T[k];

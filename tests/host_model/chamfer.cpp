@@ -14,59 +14,9 @@
 #include <limits>
 
 #include "../../poseestimation_amd/csrc/so3_device.h"
+#include "wave_model.h"
 
 namespace {
-
-float wave_allsum(const float (&lane)[64]) {
-    float v[64], w[64];
-    for (int l = 0; l < 64; ++l) v[l] = lane[l];
-    for (int off = 1; off < 64; off <<= 1) {
-        for (int l = 0; l < 64; ++l) w[l] = v[l] + v[l ^ off];
-        for (int l = 0; l < 64; ++l) v[l] = w[l];
-    }
-    return v[0];
-}
-
-// one direction of one cloud: the points src[0 .. len_p) search tgt[0 .. len_q); returns the float64 sum of the records
-template <bool SQUARED>
-double direction(const float *src, const float *tgt, int32_t full, int32_t len_p, int32_t len_q, float *dist, int32_t *nearest, int u) {
-    const int per = so3::kIcpBlock * u, chunks = (full + per - 1) / per;
-    double total = 0.0;
-    for (int c = 0; c < chunks; ++c) {
-        const int i_base = c * per;
-        const bool live = len_q > 0 && i_base < len_p;
-        float mine[so3::kIcpBlock];
-        for (int t = 0; t < so3::kIcpBlock; ++t) mine[t] = 0.f;
-        for (int uu = 0; uu < u; ++uu) {
-            for (int t = 0; t < so3::kIcpBlock; ++t) {
-                const int i = i_base + uu * so3::kIcpBlock + t;
-                const bool valid = live && i < len_p;
-                float best = 0.f;
-                int idx = 0;
-                if (valid) {
-                    best = std::numeric_limits<float>::infinity();
-                    for (int j = 0; j < len_q; ++j)
-                        so3::add_s_pair<true, false>(src[i * 3], src[i * 3 + 1], src[i * 3 + 2], tgt[j * 3], tgt[j * 3 + 1], tgt[j * 3 + 2], j, best, idx);
-                }
-                const float e = valid ? so3::chamfer_term<SQUARED>(best) : 0.f;
-                mine[t] += e;
-                if (i < full) {
-                    if (dist != nullptr) dist[i] = e;
-                    if (nearest != nullptr) nearest[i] = valid ? std::min(idx, len_q - 1) : -1;
-                }
-            }
-        }
-        float v = 0.f;
-        for (int wv = 0; wv < so3::kIcpBlock / 64; ++wv) {
-            float lane[64];
-            for (int l = 0; l < 64; ++l) lane[l] = mine[wv * 64 + l];
-            const float tot = wave_allsum(lane);
-            v = wv == 0 ? tot : v + tot;
-        }
-        total += static_cast<double>(v);
-    }
-    return total;
-}
 
 // one direction of one cloud's gradient: P's points own, Q's points hit
 template <bool SQUARED>
@@ -112,12 +62,16 @@ void model_chamfer_fwd(const float *X, const float *Y, const int32_t *x_len, con
         const float *x = X + b * N * 3, *y = Y + b * M * 3;
         float *dx = dist_x != nullptr ? dist_x + b * N : nullptr, *dy = dist_y != nullptr ? dist_y + b * M : nullptr;
         int32_t *ix = nearest_x != nullptr ? nearest_x + b * N : nullptr, *iy = nearest_y != nullptr ? nearest_y + b * M : nullptr;
-        const double sx = squared ? direction<true>(x, y, N, nb, mb, dx, ix, u) : direction<false>(x, y, N, nb, mb, dx, ix, u);
-        double sy = 0.0;
-        if (!single) sy = squared ? direction<true>(y, x, M, mb, nb, dy, iy, u) : direction<false>(y, x, M, mb, nb, dy, iy, u);
+        double sx[2], sy[2] = {0.0, 0.0};
+        if (squared) chamfer_direction<true, false>(x, y, nullptr, nullptr, N, nb, mb, dx, ix, nullptr, false, u, sx);
+        else chamfer_direction<false, false>(x, y, nullptr, nullptr, N, nb, mb, dx, ix, nullptr, false, u, sx);
+        if (!single) {
+            if (squared) chamfer_direction<true, false>(y, x, nullptr, nullptr, M, mb, nb, dy, iy, nullptr, false, u, sy);
+            else chamfer_direction<false, false>(y, x, nullptr, nullptr, M, mb, nb, dy, iy, nullptr, false, u, sy);
+        }
         const bool live = nb > 0 && mb > 0;
-        rows[b * 2 + 0] = live ? static_cast<float>(sx / static_cast<double>(nb)) : 0.f;
-        rows[b * 2 + 1] = live && !single ? static_cast<float>(sy / static_cast<double>(mb)) : 0.f;
+        rows[b * 2 + 0] = live ? static_cast<float>(sx[0] / static_cast<double>(nb)) : 0.f;
+        rows[b * 2 + 1] = live && !single ? static_cast<float>(sy[0] / static_cast<double>(mb)) : 0.f;
     }
 }
 

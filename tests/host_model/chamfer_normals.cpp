@@ -3,7 +3,7 @@
 // chamfer_points_per_lane) compiled for the host (SO3_HOST_MODEL) and driven by loops that keep the kernels' order of operations, so
 // that tests/test_chamfer_normals_host.py measures the float32 arithmetic without a GPU.  TEST INFRASTRUCTURE ONLY.
 // Differences from the device: libm's correctly rounded 1 / sqrt stands in for v_rsq_f32 (1 ulp).  The forward's work items, lane
-// sums, butterfly, wave order and float64 chunk-order sums are tests/host_model/chamfer.cpp's, with a second sum for the term beside
+// sums, butterfly, wave order and float64 chunk-order sums are wave_model.h's chamfer_direction, with a second sum for the term beside
 // the distance's (k_chamfer_normals_fwd, k_chamfer_normals_rows); the backward is one chain per normal: the own pair, then the hits in
 // ascending index (k_chamfer_normals_bwd).
 #define SO3_HOST_MODEL 1
@@ -13,69 +13,9 @@
 #include <limits>
 
 #include "../../poseestimation_amd/csrc/so3_device.h"
+#include "wave_model.h"
 
 namespace {
-
-float wave_allsum(const float (&lane)[64]) {
-    float v[64], w[64];
-    for (int l = 0; l < 64; ++l) v[l] = lane[l];
-    for (int off = 1; off < 64; off <<= 1) {
-        for (int l = 0; l < 64; ++l) w[l] = v[l] + v[l ^ off];
-        for (int l = 0; l < 64; ++l) v[l] = w[l];
-    }
-    return v[0];
-}
-
-float item_sum(const float (&mine)[so3::kIcpBlock]) {
-    float v = 0.f;
-    for (int wv = 0; wv < so3::kIcpBlock / 64; ++wv) {
-        float lane[64];
-        for (int l = 0; l < 64; ++l) lane[l] = mine[wv * 64 + l];
-        const float tot = wave_allsum(lane);
-        v = wv == 0 ? tot : v + tot;
-    }
-    return v;
-}
-
-// one direction of one cloud: the points src[0 .. len_p) search tgt[0 .. len_q) and pair their normals own[i], other[j(i)];
-// sums[0], sums[1] = the float64 sums of the records (distance, normal term)
-template <bool SQUARED>
-void direction(const float *src, const float *tgt, const float *own, const float *other, int32_t full, int32_t len_p, int32_t len_q, float *dist,
-               int32_t *nearest, float *term, bool signed_cos, int u, double (&sums)[2]) {
-    const int per = so3::kIcpBlock * u, chunks = (full + per - 1) / per;
-    sums[0] = sums[1] = 0.0;
-    for (int c = 0; c < chunks; ++c) {
-        const int i_base = c * per;
-        const bool live = len_q > 0 && i_base < len_p;
-        float mine[so3::kIcpBlock], mine_n[so3::kIcpBlock];
-        for (int t = 0; t < so3::kIcpBlock; ++t) mine[t] = mine_n[t] = 0.f;
-        for (int uu = 0; uu < u; ++uu) {
-            for (int t = 0; t < so3::kIcpBlock; ++t) {
-                const int i = i_base + uu * so3::kIcpBlock + t;
-                const bool valid = live && i < len_p;
-                float best = 0.f, tn = 0.f;
-                int idx = 0;
-                if (valid) {
-                    best = std::numeric_limits<float>::infinity();
-                    for (int j = 0; j < len_q; ++j)
-                        so3::add_s_pair<true, false>(src[i * 3], src[i * 3 + 1], src[i * 3 + 2], tgt[j * 3], tgt[j * 3 + 1], tgt[j * 3 + 2], j, best, idx);
-                    const int j = std::min(std::max(idx, 0), len_q - 1);
-                    tn = so3::chamfer_normal_term(own[i * 3], own[i * 3 + 1], own[i * 3 + 2], other[j * 3], other[j * 3 + 1], other[j * 3 + 2], signed_cos);
-                }
-                const float e = valid ? so3::chamfer_term<SQUARED>(best) : 0.f;
-                mine[t] += e;
-                mine_n[t] += tn;
-                if (i < full) {
-                    if (dist != nullptr) dist[i] = e;
-                    if (nearest != nullptr) nearest[i] = valid ? std::min(idx, len_q - 1) : -1;
-                    if (term != nullptr) term[i] = tn;
-                }
-            }
-        }
-        sums[0] += static_cast<double>(item_sum(mine));
-        sums[1] += static_cast<double>(item_sum(mine_n));
-    }
-}
 
 // one direction of one cloud's gradient: P's normals own, Q's hit
 void gradient(const float *P, const float *Q, int32_t full, int32_t len_p, int32_t len_q, const int32_t *near_own, const int32_t *near_hit,
@@ -121,11 +61,11 @@ void model_chamfer_normals_fwd(const float *X, const float *Y, const float *NX, 
         float *tx = term_x != nullptr ? term_x + b * N : nullptr, *ty = term_y != nullptr ? term_y + b * M : nullptr;
         int32_t *ix = nearest_x != nullptr ? nearest_x + b * N : nullptr, *iy = nearest_y != nullptr ? nearest_y + b * M : nullptr;
         double sx[2], sy[2] = {0.0, 0.0};
-        if (squared) direction<true>(x, y, nx, ny, N, nb, mb, dx, ix, tx, sc, u, sx);
-        else direction<false>(x, y, nx, ny, N, nb, mb, dx, ix, tx, sc, u, sx);
+        if (squared) chamfer_direction<true, true>(x, y, nx, ny, N, nb, mb, dx, ix, tx, sc, u, sx);
+        else chamfer_direction<false, true>(x, y, nx, ny, N, nb, mb, dx, ix, tx, sc, u, sx);
         if (!single) {
-            if (squared) direction<true>(y, x, ny, nx, M, mb, nb, dy, iy, ty, sc, u, sy);
-            else direction<false>(y, x, ny, nx, M, mb, nb, dy, iy, ty, sc, u, sy);
+            if (squared) chamfer_direction<true, true>(y, x, ny, nx, M, mb, nb, dy, iy, ty, sc, u, sy);
+            else chamfer_direction<false, true>(y, x, ny, nx, M, mb, nb, dy, iy, ty, sc, u, sy);
         }
         const bool live = nb > 0 && mb > 0;
         for (int k = 0; k < 2; ++k) {

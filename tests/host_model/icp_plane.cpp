@@ -9,18 +9,9 @@
 #include <vector>
 
 #include "../../poseestimation_amd/csrc/so3_device.h"
+#include "wave_model.h"
 
 namespace {
-
-float wave_allsum(const float (&lane)[64]) {
-    float v[64], w[64];
-    for (int l = 0; l < 64; ++l) v[l] = lane[l];
-    for (int off = 1; off < 64; off <<= 1) {
-        for (int l = 0; l < 64; ++l) w[l] = v[l] + v[l ^ off];
-        for (int l = 0; l < 64; ++l) v[l] = w[l];
-    }
-    return v[0];
-}
 
 // the posed point and its search: the target in index order (tiles and their padding change neither the order nor the result)
 void search(const float *pose, const float *p, const float *tgt, int32_t M, float (&x)[3], float &best, int &idx) {
