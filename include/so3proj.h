@@ -865,6 +865,54 @@ int so3_spfh_f32(const float *X, const float *normals, const int32_t *idx, const
 int so3_fpfh_f32(const float *X, const int32_t *idx, const int32_t *len, const float *spfh, const int32_t *pairs, float *fpfh, int32_t K,
                  int64_t B, int32_t N, void *stream);
 
+/* ---- RANSAC over feature matches: global registration from correspondences that are mostly wrong (added in 210) ----
+ * The step after FPFH in PCL's SampleConsensusPrerejective and Open3D's registration_ransac_based_on_correspondence: H hypotheses per
+ * cloud, each the pose of three sampled pairs, each scored on ALL matched pairs; the best one wins.  Two launches:
+ * so3_ransac_score_f32 writes every hypothesis' pose and score, so3_ransac_select_f32 picks the winner and writes what
+ * so3_rigid_align_f32 needs to refine it.  Cloud b has n_b = clip(x_len[b], 0, N) source and m_b = clip(y_len[b], 0, M) target points
+ * (NULL: all).  The sampler is the caller's: samples (B*H*3) holds indices into the source cloud.
+ * VALID PAIR.  Pair i is valid when i < n_b and 0 <= corr[b,i] < m_b (one unsigned compare: -1, M and INT32_MIN are all "no match");
+ *   its target is q_i = Q[b, corr[b,i]].  No index addresses anything before it is tested.
+ * ADMISSIBLE HYPOTHESIS, a bit definition.  h with (i0, i1, i2) = samples[b,h] is admissible when each i_k lies in [0, N) and names a
+ *   valid pair, the three i_k are pairwise distinct, their three corr values are pairwise distinct, and for each edge (a, c) of
+ *   (0,1), (0,2), (1,2), with d2(v) = fma(v_z, v_z, fma(v_y, v_y, v_x * v_x)) of rounded coordinate differences,
+ *       lp2 = d2(p_a - p_c),  lq2 = d2(q_a - q_c),  s2 = edge_similarity * edge_similarity (one float32 multiply):
+ *       lp2 >= s2 * lq2  and  lq2 >= s2 * lp2   (each side one rounded multiply; a NaN fails).
+ *   Open3D's edge-length checker on squares; edge_similarity = 0 leaves only the rejection of non-finite edges.
+ * POSE.  T_hyp[b,h] is 12 floats, the rows (R | t) of so3_add_s_fwd_f32's pose layout: so3_rigid_align_f32's answer for the three pairs
+ *   with unit weights about the pivot (p_i0, q_i0).  An inadmissible hypothesis gets the identity, exactly.  The pose's arithmetic is
+ *   NOT part of the bit contract (three pairs give a rank-two H; the rotation's error grows as s1 / s2 of its singular values, and a
+ *   collinear triple gets some finite pose and loses the vote); everything below is defined GIVEN the pose that was written.
+ * SCORE, a bit definition given T.  r2 = max_distance * max_distance (float32).  For i = 0 .. N-1 ascending, valid pairs only:
+ *       x = T p_i, per coordinate fma(T0, p_x, fma(T1, p_y, fma(T2, p_z, T3)));   d2 = d2(x - q_i);
+ *       d2 <= r2 (a NaN is no inlier):   count <- count + 1;   err <- err + d2, one float32 chain from +0 in that order.
+ *   An inadmissible hypothesis has count = -1, err = 0.
+ * SELECTION, a bit definition.  best[b] = the h with the largest count >= 0, among equals the smallest err, among equals the smallest
+ *   h; -1 when no hypothesis has count >= 0, and T_best is then the identity.  so3_ransac_select_f32 reads T_hyp, count and err as
+ *   given -- it recomputes no pose -- so crafted arrays are legal input.  With T = T_best, for every row i < N:
+ *       weights[b,i] = 1 where pair i is valid, best >= 0 and d2 <= r2 (the score's arithmetic), else 0;
+ *       targets[b,i] = q_i for a valid pair;  T p_i for an invalid pair with i < n_b (inside the cloud, so that so3_rigid_align_f32's
+ *       pivot and "a point of weight 0 must still be finite" hold);  0 for i >= n_b.
+ *   inliers[b] = max(count, 0) and rmse[b] = sqrt(err / (float)count) of the winner (IEEE division, correctly rounded root; 0 when
+ *   count <= 0);  T_best[b] = the winner's 12 floats.
+ * Every element of every output is written.  No atomics, no workspace, no host synchronisation: both calls can be captured in a graph
+ * and the same inputs give the same bits.
+ *   P  in  B*N*3 float32;  Q  in  B*M*3 float32;  corr  in  B*N int32;  x_len, y_len  in  optional B int32;  samples  in  B*H*3 int32
+ *   T_hyp  B*H*12 float32, count  B*H int32, err  B*H float32:   out (so3_ransac_score_f32) / in (so3_ransac_select_f32)
+ *   best  out  B int32;  T_best  out  B*12 float32;  inliers  out  B int32;  rmse  out  B float32;  weights  out  B*N float32;
+ *   targets  out  B*N*3 float32.  No output is optional.
+ * 1 <= N, M <= SO3_ADD_S_MAX_N, 1 <= H <= SO3_RANSAC_MAX_HYPOTHESES, max_distance finite and >= 0, 0 <= edge_similarity <= 1, B as
+ * so3_knn_f32.  Checked in this order: B/N/M, H, then B == 0 returns (a no-op), max_distance, edge_similarity, NULL pointers.
+ */
+#define SO3_RANSAC_MAX_HYPOTHESES 1048576
+int so3_ransac_score_f32(const float *P, const float *Q, const int32_t *corr, const int32_t *x_len, const int32_t *y_len,
+                         const int32_t *samples, float max_distance, float edge_similarity, float *T_hyp, int32_t *count,
+                         float *err, int64_t B, int32_t N, int32_t M, int32_t H, void *stream);
+int so3_ransac_select_f32(const float *P, const float *Q, const int32_t *corr, const int32_t *x_len, const int32_t *y_len,
+                          const float *T_hyp, const int32_t *count, const float *err, float max_distance, int32_t *best,
+                          float *T_best, int32_t *inliers, float *rmse, float *weights, float *targets,
+                          int64_t B, int32_t N, int32_t M, int32_t H, void *stream);
+
 /* ---- PointNet++ sampling and grouping: farthest-point sampling and ball query (added in 210) ----
  * The reference's point_cloud/pointnet_utils.py: farthest_point_sample (:53-74, a Python loop of npoint iterations) and
  * query_ball_point (:77-97, a (B,S,N) index tensor sorted along N), each as one launch.

@@ -87,6 +87,8 @@ SYMBOLS = {
     "so3_local_frames_f32": (_INT, [_P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I64, _I32, _I32, _P]),
     "so3_spfh_f32": (_INT, [_P, _P, _P, _P, _P, _P, _I32, _I64, _I32, _P]),
     "so3_fpfh_f32": (_INT, [_P, _P, _P, _P, _P, _P, _I32, _I64, _I32, _P]),
+    "so3_ransac_score_f32": (_INT, [_P, _P, _P, _P, _P, _P, ctypes.c_float, ctypes.c_float, _P, _P, _P, _I64, _I32, _I32, _I32, _P]),
+    "so3_ransac_select_f32": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_float, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _P]),
     "so3_fps_f32": (_INT, [_P, _P, _P, _I64, _I32, _I32, _P]),
     "so3_ball_query_f32": (_INT, [_P, _P, ctypes.c_float, _I32, _P, _P, _I64, _I32, _I32, _P]),
     "so3_three_nn_f32": (_INT, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _P]),
@@ -107,6 +109,7 @@ CHAMFER_UNSQUARED, CHAMFER_SINGLE = 1, 2           # include/so3proj.h: SO3_CHAM
 CHAMFER_SIGNED_COSINE = 4                         # include/so3proj.h: SO3_CHAMFER_SIGNED_COSINE (so3_chamfer_normals_*_f32 only)
 KNN_MAX_K = 64                                    # include/so3proj.h: SO3_KNN_MAX_K
 ADD_S_MAX_N = 1 << 20                             # include/so3proj.h: SO3_ADD_S_MAX_N
+RANSAC_MAX_HYPOTHESES = 1 << 20                   # include/so3proj.h: SO3_RANSAC_MAX_HYPOTHESES
 FPS_MAX_N = 16384                                 # include/so3proj.h: SO3_FPS_MAX_N
 THREE_MAX_D = 65536                               # include/so3proj.h: SO3_THREE_MAX_D
 GROUP_MAX_K = 65536                               # include/so3proj.h: SO3_GROUP_MAX_K

@@ -1891,4 +1891,86 @@ __device__ __forceinline__ bool fpfh_pair(bool slot, V3<float> pi, V3<float> ni,
     return ok && g1 == g1 && g2 == g2 && g3 == g3;
 }
 
+// ---- RANSAC over feature matches: hypotheses from sampled triples, scored on the matched pairs (so3proj.hip: k_ransac_score,
+// k_ransac_select; tests/host_model/ransac.cpp) ---------------------------------------------------------------------------------------
+// include/so3proj.h holds the definition.  What is DEFINED bit for bit: which pairs are valid, which hypotheses are admissible (the edge
+// test on squares, one rounded multiply per side), the score of a GIVEN pose (pose_point, pair_dist2 of rounded differences, d2 <= r2,
+// err a chain of rounded additions in ascending i), the selection's total order, weights, targets and rmse.  The hypothesis' pose is
+// NOT: it is rigid_align's arithmetic on three pairs (align_accumulate x 3, align_finish, project_rotation, align_translation) and is
+// judged against float64; whoever scores reads the pose that was written.
+constexpr int kRansacTile = 1024;                 // pairs per LDS tile of k_ransac_score: two float4 each (p | q), 32 KB
+constexpr int kRansacMaxHypotheses = 1 << 20;     // include/so3proj.h: SO3_RANSAC_MAX_HYPOTHESES
+#pragma clang fp contract(off)
+// pair i of cloud b: i < n_b and 0 <= corr < m_b, each one unsigned compare
+__device__ __forceinline__ bool ransac_valid(int32_t i, int32_t nb, int32_t c, int32_t mb) { return group_valid(i, nb) && group_valid(c, mb); }
+// one edge of the sampled triangle: both lp2 >= s2 lq2 and lq2 >= s2 lp2 (a NaN fails)
+__device__ __forceinline__ bool ransac_edge(float s2, V3<float> pa, V3<float> pc, V3<float> qa, V3<float> qc) {
+    const float lp2 = pair_dist2(pa.x - pc.x, pa.y - pc.y, pa.z - pc.z);
+    const float lq2 = pair_dist2(qa.x - qc.x, qa.y - qc.y, qa.z - qc.z);
+    const float a = s2 * lq2, c = s2 * lp2;
+    return lp2 >= a && lq2 >= c;
+}
+// The admissibility of a hypothesis whose three indices name valid pairs (ok), with their corr values c and their points.
+__device__ __forceinline__ bool ransac_admissible(bool ok, const int32_t (&i)[3], const int32_t (&c)[3], const V3<float> (&p)[3],
+                                                  const V3<float> (&q)[3], float edge_similarity) {
+    const float s2 = edge_similarity * edge_similarity;
+    ok = ok && i[0] != i[1] && i[0] != i[2] && i[1] != i[2] && c[0] != c[1] && c[0] != c[2] && c[1] != c[2];
+    const bool e01 = ransac_edge(s2, p[0], p[1], q[0], q[1]), e02 = ransac_edge(s2, p[0], p[2], q[0], q[2]);
+    const bool e12 = ransac_edge(s2, p[1], p[2], q[1], q[2]);
+    return ok && e01 && e02 && e12;
+}
+__device__ __forceinline__ void ransac_identity(float (&T)[12]) {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) T[k] = (k % 5) == 0 ? 1.f : 0.f;
+}
+// One pair's share of a hypothesis' score under the pose T: q = NaN (how an invalid pair is staged) is no inlier.  (x, y, z) = T p, the
+// posed point, is what k_ransac_select writes as an invalid pair's target.
+__device__ __forceinline__ bool ransac_inlier(const float (&T)[12], float px, float py, float pz, float qx, float qy, float qz, float r2, float &x,
+                                              float &y, float &z, float &d2) {
+    pose_point(T, px, py, pz, x, y, z);
+    d2 = pair_dist2(x - qx, y - qy, z - qz);
+    return d2 <= r2;
+}
+__device__ __forceinline__ void ransac_score_pair(const float (&T)[12], float px, float py, float pz, float qx, float qy, float qz, float r2,
+                                                  int32_t &count, float &err) {
+    float x, y, z, d2;
+    const bool in = ransac_inlier(T, px, py, pz, qx, qy, qz, r2, x, y, z, d2);
+    const float e = err + d2;
+    count += in ? 1 : 0;
+    err = in ? e : err;
+}
+// The selection's order: is the hypothesis (c, e, h) better than the best so far (bc, be, bh)?  An inadmissible one (c < 0) never is;
+// "none yet" is (-1, 0, -1).  Among admissible ones the order is total (e is a finite sum), so any reduction shape gives one answer.
+__device__ __forceinline__ bool ransac_better(int32_t c, float e, int32_t h, int32_t bc, float be, int32_t bh) {
+    return c > bc || (c == bc && c >= 0 && (e < be || (e == be && h < bh)));
+}
+// sqrt(err / count), an IEEE division and a correctly rounded square root; 0 without an inlier
+__device__ __forceinline__ float ransac_rmse(int32_t count, float err) { return count > 0 ? __builtin_sqrtf(err / static_cast<float>(count)) : 0.f; }
+#pragma clang fp contract(fast)
+// The pose of one hypothesis, rows (R | t): rigid_align's answer for three pairs of unit weight about the pivot (p_0, q_0).  Not
+// admissible: the projection runs on the identity (its result is not used) and the identity pose comes out.  Every lane of a wave
+// calls this together (the projection's hard-row test is a ballot).
+__device__ __forceinline__ void ransac_pose(bool admissible, const V3<float> (&p)[3], const V3<float> (&q)[3], float (&T)[12]) {
+    float s[kAlignSums], h[9], st[7], r[9], t[3];
+#pragma unroll
+    for (int k = 0; k < kAlignSums; ++k) s[k] = 0.f;
+    const float p0[3] = {p[0].x, p[0].y, p[0].z}, q0[3] = {q[0].x, q[0].y, q[0].z};
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        align_accumulate(1.f, p[k].x - p0[0], p[k].y - p0[1], p[k].z - p0[2], q[k].x - q0[0], q[k].y - q0[1], q[k].z - q0[2], s);
+    align_finish(s, p0, q0, h, st);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) h[k] = admissible ? h[k] : ((k & 3) == 0 ? 1.f : 0.f);
+    project_rotation<float>(h, r);
+    align_translation(r, st, t);
+    float id[12];
+    ransac_identity(id);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) T[4 * c + k] = admissible ? r[3 * c + k] : id[4 * c + k];
+        T[4 * c + 3] = admissible ? t[c] : 0.f;
+    }
+}
+
 }  // namespace so3

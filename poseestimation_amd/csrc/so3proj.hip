@@ -3080,6 +3080,149 @@ __global__ __launch_bounds__(kBlock) void k_fpfh(const float *__restrict__ X, co
     }
 }
 
+// ---- RANSAC over feature matches (include/so3proj.h holds the definition; so3_device.h the arithmetic) --------------------------------
+// k_ransac_score: one hypothesis per lane, a work item = kBlock consecutive hypotheses of one cloud.  A lane gathers its three sampled
+// pairs, decides admissibility and keeps its pose in twelve registers (so3::ransac_pose: every lane runs the projection, an
+// inadmissible one on the identity).  The workgroup then streams the cloud's first n_b pairs through LDS in tiles of kRansacTile: each
+// lane stages its share (p_i, and q_i or NaN for an invalid pair, so that d2 <= r2 drops it without a branch); after the barrier every
+// lane walks the tile in ascending i, all 64 lanes of a wave at one LDS address (two ds_read_b128 broadcasts per pair).  count and err
+// stay in registers, in the definition's order by construction: no cross-lane operation, no atomics, no indexed private array.
+__global__ __launch_bounds__(kBlock) void k_ransac_score(const float *__restrict__ P, const float *__restrict__ Q, const int32_t *__restrict__ corr,
+                                                         const int32_t *__restrict__ x_len, const int32_t *__restrict__ y_len,
+                                                         const int32_t *__restrict__ samples, float max_distance, float edge_similarity,
+                                                         float *__restrict__ T_hyp, int32_t *__restrict__ count, float *__restrict__ err,
+                                                         int64_t B, int32_t N, int32_t M, int32_t H, int32_t chunks) {
+    __shared__ float4 tile_p[so3::kRansacTile];
+    __shared__ float4 tile_q[so3::kRansacTile];
+    const int tid = threadIdx.x;
+    const float r2 = max_distance * max_distance;
+    const int64_t items = B * chunks;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t b = item / chunks;
+        const int h0 = static_cast<int>(item - b * chunks) * kBlock + tid;
+        const bool live = h0 < H;
+        const int h = live ? h0 : H - 1;
+        const int32_t nb = so3::chamfer_length(x_len, b, N), mb = so3::chamfer_length(y_len, b, M);
+        const float *src = P + b * N * 3, *tgt = Q + b * M * 3;
+        const int32_t *cr = corr + b * N, *tri = samples + (b * H + h) * 3;
+        int32_t si[3], sc[3];
+        so3::V3<float> p[3], q[3];
+        bool ok = true;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            si[k] = tri[k];
+            const int ic = so3::group_valid(si[k], N) ? si[k] : 0;          // no index addresses anything before it is tested
+            sc[k] = cr[ic];
+            const bool valid = so3::group_valid(si[k], N) && so3::ransac_valid(si[k], nb, sc[k], mb);
+            const int jc = valid ? sc[k] : 0;
+            p[k] = so3::mk<float>(src[ic * 3 + 0], src[ic * 3 + 1], src[ic * 3 + 2]);
+            q[k] = so3::mk<float>(tgt[jc * 3 + 0], tgt[jc * 3 + 1], tgt[jc * 3 + 2]);
+            ok = ok && valid;
+        }
+        const bool admissible = so3::ransac_admissible(ok, si, sc, p, q, edge_similarity);
+        float T[12];
+        so3::ransac_pose(admissible, p, q, T);
+        int32_t cnt = 0;
+        float e = 0.f;
+        for (int t0 = 0; t0 < nb; t0 += so3::kRansacTile) {
+            const int len = min(so3::kRansacTile, nb - t0);
+            __syncthreads();                                                    // the previous tile has been read
+            for (int k = tid; k < len; k += kBlock) {
+                const int i = t0 + k;
+                const int32_t c = cr[i];
+                const bool valid = so3::ransac_valid(i, nb, c, mb);
+                const int jc = valid ? c : 0;
+                float4 a, t;
+                a.x = src[i * 3 + 0]; a.y = src[i * 3 + 1]; a.z = src[i * 3 + 2]; a.w = 0.f;
+                t.x = valid ? tgt[jc * 3 + 0] : __builtin_nanf(""); t.y = tgt[jc * 3 + 1]; t.z = tgt[jc * 3 + 2]; t.w = 0.f;
+                tile_p[k] = a;
+                tile_q[k] = t;
+            }
+            __syncthreads();
+#pragma unroll 4
+            for (int k = 0; k < len; ++k) {
+                const f32x4 a = *(const volatile lds_f32x4 *)(&tile_p[k]);      // wave-uniform addresses: broadcasts
+                const f32x4 t = *(const volatile lds_f32x4 *)(&tile_q[k]);
+                so3::ransac_score_pair(T, a.x, a.y, a.z, t.x, t.y, t.z, r2, cnt, e);
+            }
+        }
+        if (live) {
+            const int64_t at = b * H + h0;
+#pragma unroll
+            for (int k = 0; k < 12; ++k) T_hyp[at * 12 + k] = T[k];
+            count[at] = admissible ? cnt : -1;
+            err[at] = admissible ? e : 0.f;
+        }
+    }
+}
+
+// k_ransac_select: one workgroup per cloud.  Lanes stride over the H hypotheses and keep their best under so3::ransac_better, a tree
+// through LDS joins the 256 candidates (the order is total: the tree's shape cannot change the answer), every lane reads the winner's
+// pose as it was WRITTEN (nothing is recomputed from the samples) and the workgroup walks the N rows for weights and targets.
+__global__ __launch_bounds__(kBlock) void k_ransac_select(const float *__restrict__ P, const float *__restrict__ Q, const int32_t *__restrict__ corr,
+                                                          const int32_t *__restrict__ x_len, const int32_t *__restrict__ y_len,
+                                                          const float *__restrict__ T_hyp, const int32_t *__restrict__ count,
+                                                          const float *__restrict__ err, float max_distance, int32_t *__restrict__ best,
+                                                          float *__restrict__ T_best, int32_t *__restrict__ inliers, float *__restrict__ rmse,
+                                                          float *__restrict__ weights, float *__restrict__ targets, int64_t B, int32_t N,
+                                                          int32_t M, int32_t H) {
+    __shared__ int32_t s_c[kBlock], s_h[kBlock];
+    __shared__ float s_e[kBlock];
+    const int tid = threadIdx.x;
+    const float r2 = max_distance * max_distance;
+    for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
+        int32_t bc = -1, bh = -1;
+        float be = 0.f;
+        for (int h = tid; h < H; h += kBlock) {
+            const int32_t c = count[b * H + h];
+            const float e = err[b * H + h];
+            const bool take = so3::ransac_better(c, e, h, bc, be, bh);
+            bc = take ? c : bc; be = take ? e : be; bh = take ? h : bh;
+        }
+        __syncthreads();                                                        // the previous cloud's winner has been read
+        s_c[tid] = bc; s_e[tid] = be; s_h[tid] = bh;
+        __syncthreads();
+        for (int s = kBlock / 2; s > 0; s >>= 1) {
+            if (tid < s) {
+                const bool take = so3::ransac_better(s_c[tid + s], s_e[tid + s], s_h[tid + s], s_c[tid], s_e[tid], s_h[tid]);
+                if (take) { s_c[tid] = s_c[tid + s]; s_e[tid] = s_e[tid + s]; s_h[tid] = s_h[tid + s]; }
+            }
+            __syncthreads();
+        }
+        bc = s_c[0]; be = s_e[0]; bh = s_h[0];
+        const bool found = bh >= 0;
+        float T[12];
+        so3::ransac_identity(T);
+        if (found) {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) T[k] = T_hyp[(b * H + bh) * 12 + k];      // wave-uniform: scalar loads
+        }
+        if (tid == 0) {
+            best[b] = bh;
+            inliers[b] = bc > 0 ? bc : 0;
+            rmse[b] = so3::ransac_rmse(bc, be);
+#pragma unroll
+            for (int k = 0; k < 12; ++k) T_best[b * 12 + k] = T[k];
+        }
+        const int32_t nb = so3::chamfer_length(x_len, b, N), mb = so3::chamfer_length(y_len, b, M);
+        const float *src = P + b * N * 3, *tgt = Q + b * M * 3;
+        for (int i = tid; i < N; i += kBlock) {
+            const int32_t c = corr[b * N + i];
+            const bool valid = so3::ransac_valid(i, nb, c, mb);
+            const int jc = valid ? c : 0;
+            const float px = src[i * 3 + 0], py = src[i * 3 + 1], pz = src[i * 3 + 2];
+            const float qx = tgt[jc * 3 + 0], qy = tgt[jc * 3 + 1], qz = tgt[jc * 3 + 2];
+            float x, y, z, d2;
+            const bool in = so3::ransac_inlier(T, px, py, pz, qx, qy, qz, r2, x, y, z, d2) && valid && found;
+            weights[b * N + i] = in ? 1.f : 0.f;
+            const bool row = i < nb;
+            targets[(b * N + i) * 3 + 0] = valid ? qx : (row ? x : 0.f);
+            targets[(b * N + i) * 3 + 1] = valid ? qy : (row ? y : 0.f);
+            targets[(b * N + i) * 3 + 2] = valid ? qz : (row ? z : 0.f);
+        }
+    }
+}
+
 // ---- PointNet++ set abstraction: the grouping gather and its backward -------------------------------------------------------------
 // What sample_and_group does between the ball query and the first Conv2d: gather the grouped coordinates and
 // features, subtract the centre, concatenate, in the layout the caller asks for.  A slot whose index lies outside [0, N) -- an empty
@@ -5561,6 +5704,47 @@ int so3_fpfh_f32(const float *X, const int32_t *idx, const int32_t *len, const f
     hipLaunchKernelGGL(k_fpfh, dim3(static_cast<unsigned>(std::min<int64_t>(B * chunks, kThreeMaxGrid))), dim3(kBlock), 0,
                        static_cast<hipStream_t>(stream), X, idx, len, spfh, pairs, fpfh, K, B, N, chunks);
     return check_launch("so3_fpfh_f32");
+}
+
+inline bool ransac_hypotheses_ok(int32_t H) {
+    static_assert(SO3_RANSAC_MAX_HYPOTHESES == so3::kRansacMaxHypotheses, "the header's limit is the device header's");
+    return H >= 1 && H <= SO3_RANSAC_MAX_HYPOTHESES;
+}
+inline bool ransac_distance_ok(float max_distance) { return max_distance >= 0.f && max_distance < __builtin_inff(); }   // a NaN fails
+
+int so3_ransac_score_f32(const float *P, const float *Q, const int32_t *corr, const int32_t *x_len, const int32_t *y_len, const int32_t *samples,
+                         float max_distance, float edge_similarity, float *T_hyp, int32_t *count, float *err, int64_t B, int32_t N, int32_t M,
+                         int32_t H, void *stream) {
+    SO3_CHECK_ARGS(cloud_dims_ok(B, N, M), "so3_ransac_score_f32: B/N/M");
+    SO3_CHECK_ARGS(ransac_hypotheses_ok(H), "so3_ransac_score_f32: H");
+    if (B == 0) return 0;
+    SO3_CHECK_ARGS(ransac_distance_ok(max_distance), "so3_ransac_score_f32: max_distance");
+    SO3_CHECK_ARGS(edge_similarity >= 0.f && edge_similarity <= 1.f, "so3_ransac_score_f32: edge_similarity");
+    SO3_CHECK_ARGS(P != nullptr && Q != nullptr && corr != nullptr && samples != nullptr && T_hyp != nullptr && count != nullptr && err != nullptr,
+                   "so3_ransac_score_f32: null pointer");
+    const int32_t chunks = (H + kBlock - 1) / kBlock;
+    name_kernel("k_ransac_score");
+    hipLaunchKernelGGL(k_ransac_score, dim3(static_cast<unsigned>(std::min<int64_t>(B * chunks, kThreeMaxGrid))), dim3(kBlock), 0,
+                       static_cast<hipStream_t>(stream), P, Q, corr, x_len, y_len, samples, max_distance, edge_similarity, T_hyp, count, err, B, N, M, H,
+                       chunks);
+    return check_launch("so3_ransac_score_f32");
+}
+
+int so3_ransac_select_f32(const float *P, const float *Q, const int32_t *corr, const int32_t *x_len, const int32_t *y_len, const float *T_hyp,
+                          const int32_t *count, const float *err, float max_distance, int32_t *best, float *T_best, int32_t *inliers, float *rmse,
+                          float *weights, float *targets, int64_t B, int32_t N, int32_t M, int32_t H, void *stream) {
+    SO3_CHECK_ARGS(cloud_dims_ok(B, N, M), "so3_ransac_select_f32: B/N/M");
+    SO3_CHECK_ARGS(ransac_hypotheses_ok(H), "so3_ransac_select_f32: H");
+    if (B == 0) return 0;
+    SO3_CHECK_ARGS(ransac_distance_ok(max_distance), "so3_ransac_select_f32: max_distance");
+    SO3_CHECK_ARGS(P != nullptr && Q != nullptr && corr != nullptr && T_hyp != nullptr && count != nullptr && err != nullptr && best != nullptr &&
+                       T_best != nullptr && inliers != nullptr && rmse != nullptr && weights != nullptr && targets != nullptr,
+                   "so3_ransac_select_f32: null pointer");
+    name_kernel("k_ransac_select");
+    hipLaunchKernelGGL(k_ransac_select, dim3(static_cast<unsigned>(std::min<int64_t>(B, kThreeMaxGrid))), dim3(kBlock), 0,
+                       static_cast<hipStream_t>(stream), P, Q, corr, x_len, y_len, T_hyp, count, err, max_distance, best, T_best, inliers, rmse, weights,
+                       targets, B, N, M, H);
+    return check_launch("so3_ransac_select_f32");
 }
 
 int so3_fps_f32(const float *xyz, const int32_t *start, int32_t *out, int64_t B, int32_t N, int32_t npoint, void *stream) {

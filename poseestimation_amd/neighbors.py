@@ -1,5 +1,6 @@
 """Clouds without known correspondences: the nearest-neighbour search and what stands on it -- both ICPs, the Chamfer distance,
-K nearest neighbours with their gather and grouping, and the per-point local frames and normals.  One family of the Python mirror;
+K nearest neighbours with their gather and grouping, the per-point local frames and normals, FPFH descriptors with their matching, and
+RANSAC over the matches up to a whole global registration.  One family of the Python mirror;
 rotation_representation re-exports its public names."""
 from __future__ import annotations
 
@@ -653,3 +654,127 @@ def _first_argmin(dist, dim):
     shape[dim] = size
     at = torch.arange(size, device=dist.device).view(shape)
     return torch.where(dist == best, at, torch.full((), size, dtype=torch.long, device=dist.device)).min(dim).values.clamp(max=size - 1)
+
+
+# --------------------------------------------------------------------------------------------
+# RANSAC over the matches: a pose from correspondences that are mostly wrong, and the whole global registration (forward only)
+# --------------------------------------------------------------------------------------------
+def _ransac_samples(valid, hypotheses, generator):
+    """(B,H,3) int32 triples of indices drawn uniformly among each cloud's valid pairs, on the device and without a host sync: ranks in
+    [0, c_b) from torch.rand, mapped to indices through a stable sort of the validity mask (the valid rows first, in ascending order).
+    A cloud with c_b < 3 gets -1 everywhere: every hypothesis of it is inadmissible."""
+    b, n = valid.shape
+    c = valid.sum(1)
+    order = torch.sort((~valid).to(torch.uint8), dim=1, stable=True).indices
+    u = torch.rand((b, hypotheses * 3), dtype=torch.float32, device=valid.device, generator=generator)
+    rank = torch.minimum((u * c[:, None]).long(), (c - 1).clamp(min=0)[:, None])
+    idx = torch.where((c >= 3)[:, None], order.gather(1, rank), torch.full((), -1, dtype=torch.long, device=valid.device))
+    return idx.view(b, hypotheses, 3).to(torch.int32)
+
+
+def ransac_align(P: torch.Tensor, Q: torch.Tensor, corr: torch.Tensor, max_distance: float, hypotheses: int = 4096, edge_similarity: float = 0.9,
+                 samples: torch.Tensor = None, generator: torch.Generator = None, x_lengths: torch.Tensor = None, y_lengths: torch.Tensor = None,
+                 refine: bool = True, return_info: bool = False):
+    """Global registration from correspondences of which a large share is wrong: the pose (R (B,3,3), t (B,3)) that maps the most pairs
+    (p_i, Q[b, corr[b,i]]) to within max_distance of each other.  P: (B,N,3) source clouds, Q: (B,M,3) target clouds, corr: (B,N)
+    int64 as match_features returns it, or int32; a pair is valid when i < n_b and 0 <= corr < m_b (-1 and anything else out of range
+    is "no match").  The step between match_features and icp_align (PCL's SampleConsensusPrerejective, Open3D's
+    registration_ransac_based_on_correspondence).
+
+    `hypotheses` triples of valid pairs are drawn per cloud; a triple whose three edge lengths in P and in Q do not agree within the
+    ratio edge_similarity (0 <= . <= 1; 0 switches the test off), or that repeats a source or a target point, is rejected before it
+    is scored; each remaining one gives rigid_align's pose of its three pairs, scored by the number of valid pairs it brings within
+    max_distance (ties: the smaller sum of squared distances, then the earlier hypothesis).  Two launches (so3_ransac_score_f32: one
+    hypothesis per lane, the pairs streamed through on-chip memory, nothing of size B * H * N in memory; so3_ransac_select_f32), no
+    atomics and no host synchronisation: the call captures into a graph.  include/so3proj.h holds the bit-exact definition of the
+    score and the selection.
+
+    samples: (B,H,3) int32 / int64 indices into the source cloud; given, the call is a pure function of its inputs (the same bits every
+    time).  None draws them on the device from torch.rand(generator=generator), uniformly among the valid pairs; a cloud with fewer
+    than three valid pairs has no admissible hypothesis and gets the identity with zero inliers.  x_lengths, y_lengths: optional (B,)
+    int32 / int64, cloud b has n_b and m_b points.  refine=True ends with rigid_align on the winner's inliers (one more launch);
+    refine=False returns the winning triple's own pose.
+
+    return_info=True also returns a dict: "best" (B,) int64 the winning hypothesis (-1: none), "inliers" (B,) int64, "rmse" (B,) float32
+    over the inliers at the winning pose, "weights" (B,N) float32 the 0 / 1 inlier mask, "targets" (B,N,3) float32 the matched target
+    points (a finite stand-in where there is no match), "samples" (B,H,3) int64 and "T_best" (B,3,4) the rows (R | t) before refinement.
+
+    Forward only (the vote is piecewise constant; an argument that requires grad is warned about once).  The differentiable tail is
+    rigid_align(P, info["targets"], info["weights"]), which is what refine=True computes."""
+    dev, p, q, _, b, n, m = _cloud_pair("ransac_align", P, Q, shared_target=False)
+    _require_device(p, corr)
+    if corr.device != dev or tuple(corr.shape) != (b, n) or corr.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError("ransac_align: expected corr (B, N) (int32 or int64) on %s with B = %d, N = %d, got %s %s on %s"
+                           % (dev, b, n, corr.dtype, tuple(corr.shape), corr.device))
+    max_distance, edge_similarity = float(max_distance), float(edge_similarity)
+    if not 0.0 <= max_distance < float("inf") or not 0.0 <= edge_similarity <= 1.0:
+        raise RuntimeError("ransac_align: expected a finite max_distance >= 0 and 0 <= edge_similarity <= 1, got %r and %r"
+                           % (max_distance, edge_similarity))
+    if samples is None:
+        if isinstance(hypotheses, bool) or not isinstance(hypotheses, int) or not 1 <= hypotheses <= _lib.RANSAC_MAX_HYPOTHESES:
+            raise RuntimeError("ransac_align: expected an int 1 <= hypotheses <= %d, got %r" % (_lib.RANSAC_MAX_HYPOTHESES, hypotheses))
+    else:
+        _require_device(p, samples)
+        if (samples.dim() != 3 or samples.shape[0] != b or samples.shape[2] != 3 or samples.dtype not in (torch.int32, torch.int64)
+                or not 1 <= samples.shape[1] <= _lib.RANSAC_MAX_HYPOTHESES):
+            raise RuntimeError("ransac_align: expected samples (B, H, 3) (int32 or int64) with B = %d and 1 <= H <= %d, got %s %s"
+                               % (b, _lib.RANSAC_MAX_HYPOTHESES, samples.dtype, tuple(samples.shape)))
+    if _wants_grad(P, Q):
+        _warn_once("ransac_align", "ransac_align is forward-only: R and t carry no gradient although an argument requires grad.  "
+                                   "rigid_align(P, info['targets'], info['weights']) on return_info=True's dict is the differentiable tail.")
+    xl = _cloud_lengths("ransac_align", RuntimeError, "x_lengths", x_lengths, b, n, dev)
+    yl = _cloud_lengths("ransac_align", RuntimeError, "y_lengths", y_lengths, b, m, dev)
+    # an index beyond int32 is invalid either way: clamp it to one that stays invalid (M <= 2^20) instead of letting it wrap
+    cr = (corr if corr.dtype == torch.int32 else corr.detach().clamp(-1, _lib.ADD_S_MAX_N).to(torch.int32)).contiguous()
+    if samples is None:
+        # xl, yl are _cloud_lengths' (already clipped to [0, N] and [0, M]): the mask is the kernels' "valid pair"
+        rows = torch.arange(n, device=dev)[None, :]
+        valid = (cr >= 0) & (cr < (m if yl is None else yl[:, None]))
+        if xl is not None:
+            valid = valid & (rows < xl[:, None])
+        sm = _ransac_samples(valid, hypotheses, generator)
+    else:
+        sm = (samples if samples.dtype == torch.int32 else samples.detach().clamp(-1, _lib.ADD_S_MAX_N).to(torch.int32)).contiguous()
+    h = sm.shape[1]
+    t_hyp = torch.empty((b, h, 12), dtype=torch.float32, device=dev)
+    count = torch.empty((b, h), dtype=torch.int32, device=dev)
+    err = torch.empty((b, h), dtype=torch.float32, device=dev)
+    best = torch.empty((b,), dtype=torch.int32, device=dev)
+    t_best = torch.empty((b, 3, 4), dtype=torch.float32, device=dev)
+    inliers = torch.empty((b,), dtype=torch.int32, device=dev)
+    rmse = torch.empty((b,), dtype=torch.float32, device=dev)
+    weights = torch.empty((b, n), dtype=torch.float32, device=dev)
+    targets = torch.empty((b, n, 3), dtype=torch.float32, device=dev)
+    _launch(dev, "so3_ransac_score_f32", _ptr(p), _ptr(q), _ptr(cr), _ptr(xl), _ptr(yl), _ptr(sm), max_distance, edge_similarity, _ptr(t_hyp),
+            _ptr(count), _ptr(err), b, n, m, h)
+    _launch(dev, "so3_ransac_select_f32", _ptr(p), _ptr(q), _ptr(cr), _ptr(xl), _ptr(yl), _ptr(t_hyp), _ptr(count), _ptr(err), max_distance,
+            _ptr(best), _ptr(t_best), _ptr(inliers), _ptr(rmse), _ptr(weights), _ptr(targets), b, n, m, h)
+    if refine:
+        r = torch.empty((b, 3, 3), dtype=torch.float32, device=dev)
+        t = torch.empty((b, 3), dtype=torch.float32, device=dev)
+        _launch(dev, "so3_rigid_align_f32", _ptr(p), _ptr(targets), _ptr(weights), _ptr(r), _ptr(t), None, None, b, n)
+    else:
+        r, t = t_best[:, :, :3].contiguous(), t_best[:, :, 3].contiguous()
+    if return_info:
+        return r, t, {"best": best.long(), "inliers": inliers.long(), "rmse": rmse, "weights": weights, "targets": targets,
+                      "samples": sm.long() if samples is None else samples.detach().long(), "T_best": t_best}
+    return r, t
+
+
+def global_registration(P: torch.Tensor, Q: torch.Tensor, max_distance: float, K: int = 16, hypotheses: int = 4096, icp_iterations: int = 10,
+                        generator: torch.Generator = None, return_info: bool = False):
+    """The pose (R (B,3,3), t (B,3)) that registers the clouds P (B,N,3) onto Q (B,M,3) from ARBITRARY relative pose, without an
+    initial guess: estimate_normals and fpfh_features on both clouds (K neighbours), match_features (mutual), ransac_align on the
+    matches and icp_align from its answer (icp_iterations iterations, the same max_distance).  A plain composition of those calls,
+    full clouds only; generator seeds ransac_align's draws.  The normals face each cloud's own centroid: a rule a rigid motion
+    carries along, which the default sign rule of estimate_normals (largest component positive) is not, and the descriptor depends
+    on the normals' sides.  return_info=True also returns a dict: "corr" (B,N) int64 the matches,
+    "R_ransac", "t_ransac" the pose before ICP, and ransac_align's entries.  Forward only."""
+    fp = fpfh_features(P, estimate_normals(P, K, viewpoint=P.detach().mean(1)), K=K)
+    fq = fpfh_features(Q, estimate_normals(Q, K, viewpoint=Q.detach().mean(1)), K=K)
+    corr = match_features(fp, fq)
+    r0, t0, info = ransac_align(P, Q, corr, max_distance, hypotheses=hypotheses, generator=generator, return_info=True)
+    r, t = icp_align(P, Q, R_init=r0, t_init=t0, iterations=icp_iterations, max_distance=max_distance)
+    if return_info:
+        return r, t, dict(info, corr=corr, R_ransac=r0, t_ransac=t0)
+    return r, t

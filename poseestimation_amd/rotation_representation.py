@@ -932,8 +932,8 @@ from .symmetry import SymmetryTable, cyclic_symmetry, symmetric_angle_error, sym
 from .angle_statistics import STAT_FIELDS, angle_error_statistics  # noqa: E402,F401
 from .clouds import (get_sampled_rotation_matrices_by_axisAngle, kabsch_rotation, kabsch_rotation_synthetic, pc_normalize,  # noqa: E402,F401
                      rigid_align, rotate_point_clouds, rotations_from_axis_angle_draws)
-from .neighbors import (chamfer_distance, estimate_normals, fpfh_features, icp_align, icp_align_plane, knn_gather, knn_group,  # noqa: E402,F401
-                        knn_points, local_frames, match_features, nearest_neighbors)
+from .neighbors import (chamfer_distance, estimate_normals, fpfh_features, global_registration, icp_align, icp_align_plane,  # noqa: E402,F401
+                        knn_gather, knn_group, knn_points, local_frames, match_features, nearest_neighbors, ransac_align)
 from .pointnet import (farthest_point_sample, group_points, index_points, interpolate_features, propagate_features,  # noqa: E402,F401
                        query_ball_point, sample_and_group, sample_and_group_all, set_abstraction_group, set_abstraction_msg_group,
                        three_interpolate, three_nn)

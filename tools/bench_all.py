@@ -292,6 +292,21 @@ def main():
         timeit("fpfh, beside local_frames: so3_fpfh_f32 (%d x %d, K = %d)" % (bh, nh, kh),
                lambda i: lib.so3_fpfh_f32(p(xh), p(ih), None, p(sh), p(ph), p(fh), kh, bh, nh, st), bh * nh * (kh * (4 + 12 + 4 + 132) + 264), iters=20, warm=3)
     del xh, nrh, ih, sh, ph, fh
+    # RANSAC over feature matches: every pair valid, the triples drawn by the host; the bytes are what each entry reads and writes once
+    for br, nr, hr in ((8, 2048, 4096), (4, 1024, 2048)):
+        pr, qr = torch.rand(br, nr, 3, device=dev), torch.rand(br, nr, 3, device=dev)
+        cr = torch.randint(0, nr, (br, nr), dtype=torch.int32, device=dev)
+        sr = torch.randint(0, nr, (br, hr, 3), dtype=torch.int32, device=dev)
+        th, ch, eh = torch.empty(br, hr, 12, device=dev), torch.empty(br, hr, dtype=torch.int32, device=dev), torch.empty(br, hr, device=dev)
+        bb, ib = torch.empty(br, dtype=torch.int32, device=dev), torch.empty(br, dtype=torch.int32, device=dev)
+        tb, rb, wb, gb = torch.empty(br, 12, device=dev), torch.empty(br, device=dev), torch.empty(br, nr, device=dev), torch.empty(br, nr, 3, device=dev)
+        timeit("ransac: so3_ransac_score_f32 (%d x %d points, %d hypotheses)" % (br, nr, hr),
+               lambda i: lib.so3_ransac_score_f32(p(pr), p(qr), p(cr), None, None, p(sr), 0.05, 0.0, p(th), p(ch), p(eh), br, nr, nr, hr, st),
+               br * (nr * 28 + hr * (12 + 56)), iters=20, warm=3)
+        timeit("ransac: so3_ransac_select_f32 (%d x %d points, %d hypotheses)" % (br, nr, hr),
+               lambda i: lib.so3_ransac_select_f32(p(pr), p(qr), p(cr), None, None, p(th), p(ch), p(eh), 0.05, p(bb), p(tb), p(ib), p(rb), p(wb), p(gb),
+                                                   br, nr, nr, hr, st), br * (nr * (28 + 16) + hr * 8), iters=20, warm=3)
+    del pr, qr, cr, sr, th, ch, eh, bb, ib, tb, rb, wb, gb
     # PointNet++ sampling and grouping at the reference model's first level: a chain of 511 dependent argmaxes per cloud (one workgroup
     # each: latency bound, most compute units idle at B = 32), and one wave per centre over the cloud (the bytes are the index rows')
     bf, nf, sf, kf = 32, 1024, 512, 64
